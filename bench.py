@@ -39,6 +39,8 @@ VALU_SLOT_NS = 1.9     # one wave64 VALU instruction of the loop's dominant (VOP
 SIMDS = 1024           # 256 CUs x 4
 COPY_PEAK_GBS = 6300.0 # what a device copy kernel reaches of the 8 TB/s (MI355X_MICROARCH.md)
 SHADER_GHZ = 2.1       # shader clock under this load (per-wave s_memtime stamps against s_memrealtime: DESIGN.md 5)
+DUMP_VALUES = 1 << 22  # --dump-outputs: at most this many decoded bytes in all (float32), at seeded positions when the output is larger
+DUMP_SEED = 20241008
 
 
 def _cpu_model() -> str:
@@ -170,6 +172,25 @@ def _permuted(data: np.ndarray, k: int) -> np.ndarray:
     return synth._permutation(1000 + k)[data]
 
 
+def _dump_positions(n: int, outputs: int) -> np.ndarray:
+    """--dump-outputs: the byte positions written out of each decoded output (all of it when it fits, else a fixed seeded sample)"""
+    m = DUMP_VALUES // outputs
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, m))
+
+
+def _write_dump(directory: str, positions: np.ndarray, outs: list) -> dict:
+    """DIR/decoded.npy (DIR/decoded_<k>.npy for a step that decodes several streams): the decoded bytes at `positions` as float32;
+    DIR/decoded_positions.npy: those positions as float64."""
+    os.makedirs(directory, exist_ok=True)
+    names = ["decoded"] if len(outs) == 1 else [f"decoded_{k}" for k in range(len(outs))]
+    for name, o in zip(names, outs):
+        np.save(os.path.join(directory, name + ".npy"), o.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(directory, "decoded_positions.npy"), positions.astype(np.float64))
+    return {"dir": directory, "arrays": names + ["decoded_positions"], "values_per_array": int(positions.size)}
+
+
 def headline(args, world, rank, dev, dev_index, ctx, dist):
     n, S, bits = args.size, args.states, args.bits
     # BASELINE config 2's generator for the 100 MB workload; multi-GiB runs (tools/profile.sh) tile it (the generator makes ~7 MB/s)
@@ -282,6 +303,14 @@ def headline(args, world, rank, dev, dev_index, ctx, dist):
             settle_launches += 64
             torch.cuda.synchronize()
     regions = [timed_region(r * (args.warmup + args.steps)) for r in range(max(1, args.repeats))]
+    # --dump-outputs: the output(s) of the last timed step, sampled on the device now (written out after every leg has run)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        last = len(regions) * (args.warmup + args.steps) - 1
+        outs = [p["d_out"] for p in pairs] if one_batch is not None else [pairs[last % P]["d_out"]]
+        positions = _dump_positions(n, len(outs))
+        d_pos = torch.from_numpy(positions).to(dev)
+        dump = (positions, [o.index_select(0, d_pos) for o in outs])
     region_s = np.array([r[0] for r in regions])
     region_span_ms = np.array([r[1] for r in regions])
     elapsed = float(np.median(region_s))
@@ -599,6 +628,8 @@ def headline(args, world, rank, dev, dev_index, ctx, dist):
         if c4 is not None:  # (the N > 1 line is another workload — this is the N = 1 value to set it against)
             result["sharded_workload_one_gpu"] = {"MiB_s": c4["MiB_s"], "us": c4["us"], "frac_of_hbm_peak": c4["frac_of_hbm_peak"],
                                                   "note": "`bench.py --gpus N` (N > 1) decodes ONE 2^30-byte mt_ stream sharded over N ranks: compare its `value` with THIS figure, not with the headline's"}
+    if dump is not None:
+        result["dump_outputs"] = _write_dump(args.dump_outputs, *dump)
     return result
 
 
@@ -1135,6 +1166,9 @@ def main() -> None:
     ap.add_argument("--rehearse", action="store_true",
                     help="NO GPU: ranks over gloo, sub-runs decoded by the library's host decoder — rehearses rank spawn, sharding and the pipelined "
                          "exchange where there is no GPU (tests); the line is marked as not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline: write what the last timed step decoded to DIR/*.npy (float32; a fixed seeded sample of at most "
+                         f"{DUMP_VALUES} bytes in all, with their positions), to compare two builds output for output")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1148,6 +1182,8 @@ def main() -> None:
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.workload is None:
         args.workload = "headline" if world == 1 else "sharded"
+    if args.dump_outputs and args.workload != "headline":
+        raise SystemExit("--dump-outputs exists for the headline workload only")
     if args.steps is None:
         args.steps = 50 if args.workload == "headline" else 20 if args.workload == "sharded" else 8
     if args.size is None:

@@ -344,8 +344,10 @@ std::vector<BlockSpan> reference_blocks(int container, const uint8_t *in, size_t
   size_t target = (((n - 1) & ~(size_t)(S - 1)) & ~(unit - 1));
   if (target > unit)
     target -= unit;
+#ifndef HSRANS_KEEP_SHORT_LAST_BLOCK // (defined only by the test build of oracle/Makefile: the reference's own choice, for its streams)
   if (target > 0 && n - target < S) // see the note above: never leave a last block shorter than one group
     target -= unit;
+#endif
   size_t stale_end = n; // `blockBackPoint`: the end of the PREVIOUSLY chosen block while the next one is being chosen
   size_t block_end = n;
   bool first = true;

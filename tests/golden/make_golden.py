@@ -7,11 +7,16 @@
                       is wrong, SURVEY.md §8 quirks: the bytes held here are what the reference produces)
   manifest.json       SHA-256 of stream / decoded output for 1 MiB inputs (too big to commit), raw histogram counts,
                       and the reference's capacity() values
+  reference_calls.json.gz  what the reference returned for every call the tests make of the ``ref`` fixture (oracle_lib.RecordedRef):
+                      tests/test_oracle_vs_ref.py run against the compiled reference, plus the reference-encoded streams of the
+                      GPU tests (tests/test_gpu_parity.py), enumerated below.  `make_golden.py --calls` writes this file only.
 """
 import hashlib
 import json
 import os
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -21,7 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from hypersonic_rans_amd import synth  # noqa: E402  (pure numpy data generator)
-from oracle_lib import BLOCK, MT, RAW, Ref  # noqa: E402
+from oracle_lib import BLOCK, MT, RAW, RecordedRef, Ref  # noqa: E402
 
 NAMES = {RAW: "raw", BLOCK: "block", MT: "mt"}
 
@@ -85,5 +90,54 @@ def main():
     print("wrote", len(small), "arrays;", os.path.getsize(os.path.join(HERE, "small_vectors.npz")), "bytes npz")
 
 
+def _gpu_test_encodes(rec: RecordedRef):
+    """The ref.encode calls of tests/test_gpu_parity.py (its zipf / nonstat fixtures and case lists)."""
+    zipf, nonstat = synth.enwik8_shaped(1 << 20, seed=11), synth.nonstationary(3_000_000)
+    for cont in (RAW, BLOCK, MT):  # test_reference_encoded_streams
+        for S in (32, 64):
+            for bits in range(10, 16):
+                for src, n in ((zipf, 65537), (zipf, 65560), (zipf, 65599), (zipf, 65600), (zipf, 131073), (zipf, 524300), (nonstat, 3_000_000)):
+                    rec.encode(cont, S, bits, src[:n])
+    for S in (32, 64):
+        for bits, src, n in ((11, zipf, 65560), (14, zipf, 1 << 20), (11, nonstat, 3_000_000)):  # test_device_side_mt_walk_matches_host_planner,
+            rec.encode(MT, S, bits, src[:n])                                                      # test_index_build_for_reference_mt_streams,
+        rec.encode(RAW, S, 11, zipf[:400_037])                                                    # test_first_decode_of_an_unindexed_stream_...
+        for bits in (11, 13):  # test_index_build_for_block_streams
+            for src, n in ((nonstat, 3_000_000), (zipf, 1 << 20), (zipf, 524_300)):
+                rec.encode(BLOCK, S, bits, src[:n])
+    n = 3_000_000  # test_plain_host_decode_keeps_the_index_of_its_first_call
+    for cont in (MT, RAW):
+        rec.encode(cont, 64, 11, nonstat[:n])
+        rec.encode(cont, 32, 12, nonstat[:n][::-1])
+        rec.encode(cont, 64, 11, nonstat[:300_000])
+    runs = np.concatenate([np.full(70_000, 7, np.uint8), zipf[:100_000], np.full(200_000, 200, np.uint8), zipf[:33]])
+    one = np.full(50_000, 65, np.uint8)
+    for S in (32, 64):  # test_gpu_raw_encoder_matches_host_encoder_and_reference
+        for bits in range(10, 16):
+            for src, n in ((zipf, 1), (zipf, 31), (zipf, 63), (zipf, 64), (zipf, 65), (zipf, 255), (zipf, 256), (zipf, 4096 + 17), (zipf, 8192), (zipf, 12288 + 64 + 3),
+                           (zipf, 100_000), (zipf, 300_001), (nonstat, 1_000_003), (runs, runs.size), (one, one.size)):
+                rec.encode(RAW, S, bits, src[:n])
+
+
+def record_calls():
+    """reference_calls.json.gz: the CPU differential tests run against the compiled reference, then the GPU tests' encodes; every
+    entry is then replayed once (the product encoder must reproduce each recorded stream)."""
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "calls.json.gz")
+        subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py")],
+                              cwd=ROOT, env=dict(os.environ, HSRANS_REF_RECORD=path))
+        rec = RecordedRef(live=Ref())
+        rec.calls = RecordedRef(path=path).calls
+    _gpu_test_encodes(rec)
+    rec.save()
+    _gpu_test_encodes(RecordedRef())
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py")], cwd=ROOT)
+    print("wrote", len(rec.calls), "reference calls;", os.path.getsize(rec.path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--calls"]:
+        record_calls()
+    else:
+        main()
+        record_calls()

@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     HsransError,
     capacity,
     encode,
+    block_choices,
+    BLOCK_CHOICE,
     lib_path,
     load_library,
     make_hist,
@@ -29,6 +31,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "RAW", "BLOCK", "MT", "Context", "HsransError", "capacity", "encode", "make_hist", "plan_build", "plan_chain_count",
+    "RAW", "BLOCK", "MT", "Context", "HsransError", "capacity", "encode", "block_choices", "BLOCK_CHOICE", "make_hist", "plan_build", "plan_chain_count",
     "plan_chain_range", "plan_decoded_length", "plan_slice", "plan_stream_ranges", "plan_thin", "index_boundaries", "batch_deal", "index_boundaries_batch", "lib_path", "load_library",
 ]

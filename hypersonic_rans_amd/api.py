@@ -222,6 +222,12 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_encode_device_raw.argtypes = [_vp, _i, _u32, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(_sz), _vp, ctypes.POINTER(_vp)]
     L.hsrans_encode_device.restype = _sz
     L.hsrans_encode_device.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _u32, _u32, _vp, ctypes.POINTER(_vp)]
+    L.hsrans_block_choices.restype = _sz
+    L.hsrans_block_choices.argtypes = [_i, _i, _u32, _vp, _sz, _u32, _vp, _sz]
+    L.hsrans_block_choices_device.restype = _sz
+    L.hsrans_block_choices_device.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz, _vp]
+    L.hsrans_encode_device_ex.restype = _sz
+    L.hsrans_encode_device_ex.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(Hist), ctypes.POINTER(EncodeOpts), _vp, ctypes.POINTER(_vp)]
     L.hsrans_index_build.restype = _sz
     L.hsrans_index_build.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz]
     L.hsrans_index_build_at.restype = _sz
@@ -324,6 +330,21 @@ def encode(container: int, states: int, bits: int, data, hist: Hist | None = Non
     if not want_plan:
         return out[:m].copy()
     return out[:m].copy(), plan[:opts.plan_size].copy()
+
+
+BLOCK_CHOICE = np.dtype([("begin", np.uint64), ("end", np.uint64), ("single", np.uint32), ("symbol", np.uint32), ("counts", np.uint16, 256)])
+
+
+def block_choices(container: int, states: int, bits: int, data, block_size: int = 0) -> np.ndarray:
+    """The host encoder's block choice for block_/mt_ (hsrans_block_choices): a BLOCK_CHOICE record per block, in stream order."""
+    L = load_library()
+    data = _u8(data)
+    n = L.hsrans_block_choices(container, states, bits, _p(data), data.size, block_size, None, 0)
+    if n == 0:
+        raise HsransError("hsrans_block_choices failed")
+    out = np.zeros(n, BLOCK_CHOICE)
+    L.hsrans_block_choices(container, states, bits, _p(data), data.size, block_size, out.ctypes.data, n)
+    return out
 
 
 def plan_thin(plan, groups) -> np.ndarray:
@@ -910,6 +931,50 @@ class Context:
         if want_device_plan:
             out.append(DevicePlan(self, h))
         return out[0] if len(out) == 1 else tuple(out)
+
+    def encode_device_ex(self, container: int, states: int, bits: int, d_in: torch.Tensor, d_out: torch.Tensor, hist=None, block_size: int = 0,
+                         independent_blocks: bool = False, index_interval: int = 0, index_groups=None, want_plan: bool = False,
+                         want_device_plan: bool = False, stream: torch.cuda.Stream | None = None):
+        """GPU twin of :func:`encode` (hsrans_encode_device_ex): every container, the adaptive (``block_size=0``) or fixed blocks, the
+        same stream bytes and plan.  Returns the stream length, followed by the plan blob (``want_plan``) and/or a DevicePlan
+        (``want_device_plan``) when an index (``index_interval`` or ``index_groups``) is asked for."""
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        groups = np.ascontiguousarray(index_groups, dtype=np.uint64) if index_groups is not None else None
+        if groups is not None and groups.size == 0:  # a stream too short for more than one chain (as encode())
+            groups, index_interval = None, 4
+        n_groups = 0 if groups is None else groups.size
+        indexed = index_interval != 0 or n_groups != 0
+        plan = np.zeros(1, np.uint8)
+        if indexed:
+            pcap = (self.L.hsrans_plan_capacity_chains(container, states, d_in.numel(), n_groups, block_size) if n_groups
+                    else self.L.hsrans_plan_capacity(container, states, d_in.numel(), index_interval, block_size))
+            plan = np.zeros(max(pcap, 1), np.uint8)
+        opts = EncodeOpts(block_size, 0 if n_groups else index_interval, plan.ctypes.data if indexed else None, plan.size if indexed else 0, 0,
+                          ENC_INDEPENDENT_BLOCKS if independent_blocks else 0, 0, groups.ctypes.data if n_groups else None, n_groups)
+        h = _vp()
+        n = self.L.hsrans_encode_device_ex(self.handle, container, states, bits, d_in.data_ptr(), d_in.numel(), d_out.data_ptr(), d_out.numel(),
+                                           ctypes.byref(hist) if hist is not None else None, ctypes.byref(opts), ctypes.c_void_p(s.cuda_stream),
+                                           ctypes.byref(h) if want_device_plan and indexed else None)
+        if n == 0:
+            raise HsransError("hsrans_encode_device_ex failed")
+        out = [n]
+        if want_plan and indexed:
+            out.append(plan[: opts.plan_size].copy())
+        if want_device_plan and indexed:
+            out.append(DevicePlan(self, h))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
+                             stream: torch.cuda.Stream | None = None) -> np.ndarray:
+        """The block choice hsrans_encode_device_ex makes (hsrans_block_choices_device): BLOCK_CHOICE records, as block_choices()."""
+        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        args = (self.handle, container, states, bits, d_in.data_ptr(), d_in.numel(), block_size)
+        n = self.L.hsrans_block_choices_device(*args, None, 0, ctypes.c_void_p(s.cuda_stream))
+        if n == 0:
+            raise HsransError("hsrans_block_choices_device failed")
+        out = np.zeros(n, BLOCK_CHOICE)
+        self.L.hsrans_block_choices_device(*args, out.ctypes.data, n, ctypes.c_void_p(s.cuda_stream))
+        return out
 
     def index_build_at(self, container: int, states: int, bits: int, stream, groups) -> np.ndarray:
         stream = _u8(stream)

@@ -1,4 +1,5 @@
-// hsrans_capi_encode.cpp — GPU encoder entries: hsrans_encode_device (mt_, one wavefront per block), hsrans_encode_device_raw.
+// hsrans_capi_encode.cpp — GPU encoder entries: hsrans_encode_device (mt_, one wavefront per block), hsrans_encode_device_raw,
+// hsrans_encode_device_ex (every format hsrans_encode_ex writes).
 // Part of the C ABI of libhsrans_hip.so (include/hsrans_hip.h); split out of hsrans_capi.cpp in round 5 by concern.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,8 +26,101 @@ using namespace hsrans;
 #include "hsrans_batch.h"
 
 
+namespace
+{
+// the block choice of a chain encode: unit summaries on the device (counts, the run that ends each unit, and for the adaptive policy
+// every unit's own code length), the walk on the host (the host encoder's code).  Caller holds ctx->lock, device set.
+bool device_block_walk(hsrans_ctx *ctx, int container, uint32_t S, uint32_t bits, const void *d_in, size_t length, size_t block, hipStream_t s,
+                       std::vector<BlockSpan> *spans, size_t *n_units_out, double *summaries_us, double *walk_us)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool fixed = block != 0;
+  const size_t unit = fixed ? block : walk_unit(container, S, bits);
+  const size_t n_units = (length + unit - 1) / unit;
+  std::vector<UnitSummary> units(n_units);
+  std::vector<float> table(fixed ? 0 : (1u << bits) + 1);
+  if (!fixed)
+    walk_log_table(bits, table.data());
+  EncParams ep{};
+  ep.S = S;
+  ep.bits = bits;
+  ep.in = (const uint8_t *)d_in;
+  ep.n = length;
+  ep.block = unit;
+  ep.n_blocks = (uint32_t)n_units;
+  const size_t table_at = (n_units * sizeof(UnitSummary) + 255) & ~(size_t)255;
+  if (n_units > 0xFFFFFFFFull || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, table_at + table.size() * 4))
+    return false;
+  const float *d_table = fixed ? nullptr : (const float *)(ctx->d_enc_meta + table_at);
+  if ((!fixed && hipMemcpyAsync((void *)d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
+      launch_unit_summaries(ep, ctx->d_enc_meta, d_table, s) != hipSuccess ||
+      hipMemcpyAsync(units.data(), ctx->d_enc_meta, n_units * sizeof(UnitSummary), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return false;
+  }
+  const auto t1 = std::chrono::steady_clock::now();
+  if (!(fixed ? fixed_blocks(length, block, S, bits, units.data(), spans) : reference_blocks(container, length, S, bits, units.data(), spans)))
+    return false;
+  const auto t2 = std::chrono::steady_clock::now();
+  *n_units_out = n_units;
+  *summaries_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
+  *walk_us = std::chrono::duration<double, std::micro>(t2 - t1).count();
+  return true;
+}
+
+size_t copy_choices(const std::vector<BlockSpan> &spans, hsrans_block_choice *out, size_t capacity)
+{
+  for (size_t b = 0; b < spans.size() && b < capacity && out != nullptr; b++)
+  {
+    out[b].begin = spans[b].begin;
+    out[b].end = spans[b].end;
+    out[b].single = spans[b].single ? 1 : 0;
+    out[b].symbol = spans[b].single ? spans[b].symbol : 0;
+    if (spans[b].single)
+      memset(out[b].counts, 0, 512);
+    else
+      memcpy(out[b].counts, spans[b].hist.symbolCount, 512);
+  }
+  return spans.size();
+}
+} // namespace
+
 extern "C"
 {
+
+size_t hsrans_block_choices(int container, int states, uint32_t bits, const void *in, size_t length, uint32_t block_size, hsrans_block_choice *out, size_t capacity)
+{
+  if ((container != HSRANS_BLOCK && container != HSRANS_MT) || !valid_codec(container, states, bits) || in == nullptr || length == 0 || block_size % 64 != 0)
+    return 0;
+  const size_t unit = block_size ? block_size : walk_unit(container, (uint32_t)states, bits);
+  std::vector<UnitSummary> units((length + unit - 1) / unit);
+  unit_summaries((const uint8_t *)in, length, unit, units.data());
+  std::vector<BlockSpan> spans;
+  if (block_size == 0)
+    unit_fresh_costs(container, length, (uint32_t)states, bits, units.data());
+  if (!(block_size ? fixed_blocks(length, block_size, (uint32_t)states, bits, units.data(), &spans)
+                   : reference_blocks(container, length, (uint32_t)states, bits, units.data(), &spans)))
+    return 0;
+  return copy_choices(spans, out, capacity);
+}
+
+size_t hsrans_block_choices_device(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, uint32_t block_size,
+                                   hsrans_block_choice *out, size_t capacity, void *hip_stream)
+{
+  if (ctx == nullptr || (container != HSRANS_BLOCK && container != HSRANS_MT) || !valid_codec(container, states, bits) || d_in == nullptr || length == 0 ||
+      block_size % 64 != 0 || ((uintptr_t)d_in & 15) != 0 || length > 0x7FFF0000ull)
+    return 0;
+  std::lock_guard<std::mutex> guard(ctx->lock);
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return 0;
+  std::vector<BlockSpan> spans;
+  size_t n_units = 0;
+  double a = 0, b = 0;
+  if (!device_block_walk(ctx, container, (uint32_t)states, bits, d_in, length, block_size, (hipStream_t)hip_stream, &spans, &n_units, &a, &b))
+    return 0;
+  return copy_choices(spans, out, capacity);
+}
 
 size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity, const hsrans_hist *hist,
                                 uint32_t index_interval, const uint64_t *index_groups, size_t n_index_groups, uint8_t *plan_out, size_t plan_capacity,
@@ -348,6 +442,226 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
   d->spread_min_block = d->groups_lean ? ep.max_ck + 1 : 0; // (every coded block but the last has max_ck + 1 chains)
   dplan_blocks_from_device_groups(d, s); // (k_decode_dealt's dealing wants the blocks as chain ranges: 32 bytes a group, once)
   *out_dplan = d;
+  return total;
+}
+
+
+size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity,
+                               const hsrans_hist *hist, hsrans_encode_opts *opts, void *hip_stream, hsrans_dplan **out_dplan)
+{
+  // The device twin of hsrans_encode_ex: same arguments accepted and refused (hsrans_host.cpp encode()), same stream, same plan.
+  //   raw                               -> hsrans_encode_device_raw (one wavefront)
+  //   mt_, fixed, independent, no index -> hsrans_encode_device (one wavefront per block)
+  //   everything else                   -> the chain: k_unit_summaries (wide) -> the block walk on the host (hsrans_host.cpp
+  //                                        reference_blocks / fixed_blocks, the host encoder's own code) -> k_encode_chain (one
+  //                                        wavefront: the states run through every block) -> k_gather_chain (wide)
+  if (out_dplan)
+    *out_dplan = nullptr;
+  if (opts)
+    opts->plan_size = 0;
+  if (ctx == nullptr || !valid_codec(container, states, bits) || d_in == nullptr || d_out == nullptr || length == 0)
+    return 0;
+  if (out_capacity < capacity(container, states, length) || ((uintptr_t)d_in & 15) != 0 || ((uintptr_t)d_out & 15) != 0)
+    return 0;
+  const uint32_t S = (uint32_t)states;
+  const uint64_t *ig = opts && opts->n_index_groups ? opts->index_groups : nullptr;
+  const size_t n_ig = ig ? opts->n_index_groups : 0;
+  const uint32_t interval = ig ? 0 : (opts ? opts->index_interval : 0);
+  const bool want_plan = interval != 0 || ig != nullptr;
+  if (want_plan && ((interval % 4) != 0 || opts->plan_out == nullptr))
+    return 0;
+  for (size_t k = 0; k < n_ig; k++)
+    if (ig[k] == 0 || (ig[k] % 4) != 0 || (k > 0 && ig[k] <= ig[k - 1]))
+      return 0;
+  const bool fixed = opts && opts->block_size != 0;
+  const bool independent = opts && (opts->flags & HSRANS_ENC_INDEPENDENT_BLOCKS) != 0;
+  if (independent && (container != HSRANS_MT || !fixed))
+    return 0;
+  const size_t block = fixed ? opts->block_size : 0;
+  if (block % 64 != 0)
+    return 0;
+  if (container == HSRANS_RAW)
+    return hsrans_encode_device_raw(ctx, states, bits, d_in, length, d_out, out_capacity, hist, interval, ig, n_ig, want_plan ? opts->plan_out : nullptr,
+                                    want_plan ? opts->plan_capacity : 0, want_plan ? &opts->plan_size : nullptr, hip_stream, want_plan ? out_dplan : nullptr);
+  if (independent && !want_plan)
+    return hsrans_encode_device(ctx, container, states, bits, d_in, length, d_out, out_capacity, (uint32_t)block, 0, hip_stream, nullptr);
+  if (independent && interval != 0) // the one-wave-per-block launch writes the host encoder's plan on the device (k_plan_blocks): copied back
+  {
+    hsrans_dplan *dp = nullptr;
+    const size_t total = hsrans_encode_device(ctx, container, states, bits, d_in, length, d_out, out_capacity, (uint32_t)block, interval, hip_stream, &dp);
+    if (total == 0)
+      return 0;
+    const size_t psize = hsrans_dplan_read_plan(dp, opts->plan_out, opts->plan_capacity);
+    if (psize == 0 || out_dplan == nullptr)
+      hsrans_dplan_destroy(dp);
+    if (psize == 0)
+      return 0;
+    opts->plan_size = psize;
+    if (out_dplan != nullptr)
+      *out_dplan = dp;
+    return total;
+  }
+  // limits of the one-wavefront pass: byte offsets inside a block's slot are 32-bit (as the raw encoder's; a fixed block longer than the
+  // input is the input: one block); listed checkpoints sit on set boundaries (4 groups) of a block, which fixed blocks of a group count
+  // that is not a multiple of 4 do not keep
+  if (length > 0x7FFF0000ull || (ig && fixed && (block / S) % 4 != 0))
+    return 0;
+
+  std::lock_guard<std::mutex> guard(ctx->lock);
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return 0;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const bool stamps = getenv("HSRANS_DEBUG_STAMPS") != nullptr;
+
+  // ---- a./b. unit summaries on the device, the block walk (the host encoder's) on the host ----
+  std::vector<BlockSpan> spans;
+  size_t n_units = 0;
+  double summaries_us = 0, walk_us = 0;
+  if (!device_block_walk(ctx, container, S, bits, d_in, length, block, s, &spans, &n_units, &summaries_us, &walk_us))
+    return 0;
+  const auto t2 = std::chrono::steady_clock::now();
+  const size_t nb = spans.size();
+  const uint64_t T = length + 1 >= S ? (length - S + 1 + S - 1) / S : 0; // whole groups of the file
+  std::vector<ChainBlock> cb(nb);
+  std::vector<uint16_t> counts(nb * 256);
+  uint64_t slot_at = 0, slot_max = 0;
+  uint32_t n_ck = 0;
+  for (size_t b = 0; b < nb; b++)
+  {
+    const BlockSpan &sp = spans[b];
+    ChainBlock &c = cb[b];
+    c.begin = sp.begin;
+    c.end = sp.end;
+    c.slot_bytes = sp.single ? 512 : encode_slot_bytes(sp.end - sp.begin, S);
+    slot_at += c.slot_bytes;
+    slot_max = std::max<uint64_t>(slot_max, c.slot_bytes);
+    c.slot_end = slot_at;
+    c.single = sp.single ? 0x100u | sp.symbol : 0;
+    c.ck_base = n_ck;
+    if (!sp.single)
+    {
+      memcpy(&counts[b * 256], sp.hist.symbolCount, 512);
+      const uint64_t whole = (sp.end - sp.begin) / S;
+      if (interval != 0 && whole >= 1)
+        n_ck += (uint32_t)((whole - 1) / interval);
+    }
+  }
+  // listed checkpoints: the entries the host encoder meets (inside a coded block, not its first group, below T), and their blocks
+  std::vector<uint32_t> ck_list;
+  std::vector<uint32_t> ck_block; // (interval checkpoints too: the block of every checkpoint slot)
+  if (ig)
+  {
+    size_t b = 0;
+    for (size_t k = 0; k < n_ig && ig[k] < T; k++)
+    {
+      while (b < nb && (spans[b].end - 1) / S < ig[k])
+        b++;
+      if (b == nb)
+        break;
+      if (!spans[b].single && ig[k] > spans[b].begin / S)
+      {
+        ck_list.push_back((uint32_t)ig[k]);
+        ck_block.push_back((uint32_t)b);
+      }
+    }
+    n_ck = (uint32_t)ck_list.size();
+  }
+  else if (want_plan)
+  {
+    ck_block.reserve(n_ck);
+    for (size_t b = 0; b < nb; b++)
+    {
+      const uint32_t next = b + 1 < nb ? cb[b + 1].ck_base : n_ck;
+      for (uint32_t k = cb[b].ck_base; k < next; k++)
+        ck_block.push_back((uint32_t)b);
+    }
+  }
+
+  // ---- c. the chain: one wavefront, blocks back to front; then the images into place ----
+  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t off_bytes = 0, off_off = up256(nb * 8), off_result = off_off + up256(nb * 8), off_blocks = off_result + 256,
+               off_counts = off_blocks + up256(nb * sizeof(ChainBlock)), off_list = off_counts + up256(nb * 512), meta_bytes = off_list + up256(ck_list.size() * 4 + 4);
+  const size_t ck_slots = n_ck ? n_ck : 1;
+  const size_t states_bytes = want_plan ? nb * (size_t)S * 4 : 0;
+  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, slot_at) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta_bytes) ||
+      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck_slots * ((size_t)S * 4 + 4) + states_bytes))
+    return 0;
+  uint8_t *meta = ctx->d_enc_meta;
+  EncParams ep{};
+  ep.S = S;
+  ep.bits = bits;
+  ep.in = (const uint8_t *)d_in;
+  ep.n = length;
+  ep.out = (uint8_t *)d_out;
+  ep.out_cap = out_capacity;
+  ep.scratch = ctx->d_enc_scratch;
+  ep.slot_bytes = slot_max;
+  ep.n_blocks = (uint32_t)nb;
+  ep.image_bytes = (uint64_t *)(meta + off_bytes);
+  ep.image_off = (uint64_t *)(meta + off_off);
+  ep.result = (uint64_t *)(meta + off_result);
+  ep.chain_blocks = (const ChainBlock *)(meta + off_blocks);
+  ep.given_counts = (const uint16_t *)(meta + off_counts);
+  ep.ck_groups = ck_list.empty() ? nullptr : (const uint32_t *)(meta + off_list);
+  ep.n_ck_groups = (uint32_t)ck_list.size();
+  ep.interval = want_plan ? interval : 0;
+  ep.ck_states = (uint32_t *)ctx->d_enc_ck;
+  ep.ck_pos = ep.ck_states + ck_slots * S;
+  ep.block_states = want_plan ? ep.ck_pos + ck_slots : nullptr;
+  ep.chain_mt = container == HSRANS_MT ? 1 : 0;
+  ep.chain_independent = independent ? 1 : 0;
+  uint64_t result[kEncResultWords] = {};
+  bool ok = hipMemcpyAsync((void *)ep.chain_blocks, cb.data(), nb * sizeof(ChainBlock), hipMemcpyHostToDevice, s) == hipSuccess &&
+            hipMemcpyAsync((void *)ep.given_counts, counts.data(), nb * 512, hipMemcpyHostToDevice, s) == hipSuccess &&
+            (ck_list.empty() || hipMemcpyAsync((void *)ep.ck_groups, ck_list.data(), ck_list.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess) &&
+            launch_encode_chain(ep, s, &ctx->enc_chain_prepared) == hipSuccess &&
+            hipMemcpyAsync(result, ep.result, sizeof(result), hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (cb / counts / ck_list may be read until here)
+  {
+    (void)hipGetLastError();
+    return 0;
+  }
+  const auto t3 = std::chrono::steady_clock::now();
+  if (stamps)
+    fprintf(stderr, "[hsrans chain encode] blocks %zu  units %zu  summaries %.1f us  walk %.1f us  chain+gather %.1f us\n", nb, n_units,
+            summaries_us, walk_us,
+            std::chrono::duration<double, std::micro>(t3 - t2).count());
+  // result[1] == 0 cannot happen (out_capacity >= hsrans_capacity was checked) and result[2] != 0 only if the host's filtering of the
+  // listed checkpoints and the kernel disagree: internal consistency failures, not refusals — d_out may have been written by then
+  if (result[1] != 1 || result[2] != 0)
+    return 0;
+  const size_t total = (size_t)result[0];
+  if (!want_plan)
+    return total;
+
+  // ---- d. the plan: the device's block and checkpoint records through the host encoder's plan assembly ----
+  std::vector<uint64_t> img_bytes(nb), img_off(nb);
+  std::vector<uint32_t> blk_states(nb * S), ck_states((size_t)n_ck * S), ck_pos(n_ck);
+  if (hipMemcpy(img_bytes.data(), ep.image_bytes, nb * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(img_off.data(), ep.image_off, nb * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(blk_states.data(), ep.block_states, nb * (size_t)S * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      (n_ck && (hipMemcpy(ck_states.data(), ep.ck_states, (size_t)n_ck * S * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(ck_pos.data(), ep.ck_pos, (size_t)n_ck * 4, hipMemcpyDeviceToHost) != hipSuccess)))
+    return 0;
+  const uint64_t counts_at = container == HSRANS_MT ? 16 + 4 * (uint64_t)S : 8; // the counts inside a coded block's image
+  std::vector<EncodedBlock> blocks(nb);
+  for (size_t b = 0; b < nb; b++)
+    blocks[b] = EncodedBlock{spans[b].begin, spans[b].end, spans[b].single, spans[b].symbol, total - (img_off[b] + counts_at + 512),
+                             total - (img_off[b] + counts_at), &blk_states[b * S]};
+  std::vector<uint64_t> ck_group(n_ck), ck_wfe(n_ck);
+  for (uint32_t k = 0; k < n_ck; k++)
+  {
+    const uint32_t b = ck_block[k];
+    ck_group[k] = ig ? ck_list[k] : spans[b].begin / S + (uint64_t)(k - cb[b].ck_base + 1) * interval;
+    ck_wfe[k] = total - (img_off[b] + img_bytes[b]) + ck_pos[k]; // (ck_pos: bytes from the cursor to the end of the block's words)
+  }
+  const size_t psize = blocks_plan_from_checkpoints(container, states, bits, length, total, interval, blocks.data(), nb, n_ck, ck_group.data(), ck_wfe.data(),
+                                                    ck_states.data(), opts->plan_out, opts->plan_capacity);
+  if (psize == 0)
+    return 0;
+  opts->plan_size = psize;
+  if (out_dplan != nullptr && hsrans_dplan_create(ctx, opts->plan_out, psize, out_dplan) != HSRANS_OK)
+    return 0;
   return total;
 }
 

@@ -8,6 +8,16 @@
 namespace hsrans
 {
 
+// one block of a chain encode (launch_encode_chain), in stream order; its image ends at scratch + slot_end
+struct ChainBlock
+{
+  uint64_t begin, end;   // symbols [begin, end) of the input
+  uint64_t slot_end;     // byte offset in scratch where the block's image ends
+  uint64_t slot_bytes;   // encode_slot_bytes(end - begin, S): the slot below slot_end
+  uint32_t ck_base;      // first checkpoint slot of the block (index_interval checkpoints)
+  uint32_t single;       // 0x100 | symbol: single-symbol block (the 8-byte marker only); 0: coded with its counts in given_counts[b]
+};
+
 struct EncParams
 {
   const uint8_t *in; // device, 16-byte aligned
@@ -41,6 +51,11 @@ struct EncParams
   const uint16_t *given_counts; // [256] or null: the caller's normalised histogram (hist_t::symbolCount), used instead
   const uint32_t *ck_groups;    // or null: ascending group indices (multiples of 4) to checkpoint at, instead of `interval`
   uint32_t n_ck_groups;
+  // chain encodes (launch_encode_chain): block_/mt_ streams whose states run through every block, one wavefront back to front
+  const ChainBlock *chain_blocks; // [n_blocks]; given_counts then holds [n_blocks][256] normalised counts
+  uint32_t chain_mt;              // 1: mt_ block headers {size, skip, states, counts}; 0: block_ {size, counts} and the states in the file header
+  uint32_t chain_independent;     // 1: every block starts from fresh states (HSRANS_ENC_INDEPENDENT_BLOCKS)
+  uint32_t *block_states;         // [n_blocks * S] or null: the decoder's states at each coded block's start (for the plan)
   uint64_t *stamps; // diagnostics (HSRANS_DEBUG_STAMPS=1): per block {start, histogram done, table done, words done} s_memrealtime; else null
 };
 
@@ -52,6 +67,14 @@ constexpr uint32_t kEncResultWords = 8;
 hipError_t launch_encode(const EncParams &ep, hipStream_t stream, bool *prepared);
 // asynchronous on `stream`: [memset + K_hist ->] K_raw -> K_copy.  result[0] stream length, [1] fits out_cap, [2] listed checkpoints not met (0)
 hipError_t launch_encode_raw(const EncParams &ep, uint32_t *d_counts, hipStream_t stream, bool *prepared);
+// asynchronous on `stream`: the unit summaries the block walk reads (hsrans_host.h UnitSummary, kUnitSummaryBytes each) of ep.n_blocks
+// units of ep.block symbols (the last ends at ep.n) into `summaries`; with `log_table` (walk_log_table's, 2^bits + 1 floats, device
+// memory) also every whole unit's fresh_cost, normalised at ep.block symbols
+constexpr uint32_t kUnitSummaryBytes = 1040;
+hipError_t launch_unit_summaries(const EncParams &ep, void *summaries, const float *log_table, hipStream_t stream);
+// asynchronous on `stream`: K_chain (one wavefront, blocks back to front) -> K_gather_chain.  result[0] stream length, [1] fits
+// out_cap, [2] listed checkpoints not met (0); image_off / image_bytes per block
+hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream, bool *prepared);
 // asynchronous on `stream`: K_plan (needs ep.plan, ep.n_chains; after launch_encode's results are known)
 hipError_t launch_encode_plan(const EncParams &ep, hipStream_t stream);
 

@@ -619,16 +619,20 @@ __device__ __forceinline__ void encode_set_fast(uint32_t &x, const uint4 (&e)[4]
 // RAW = true: a whole raw stream (rANS32x64_16w.cpp:34-166 is ONE dependent chain per coder state, so one wavefront is all the
 // format has work for): the counts come from the caller or from k_raw_histogram, checkpoints may sit at listed groups, and the
 // image in the slot is the finished stream [n][total][counts][states][words].
-template <uint32_t S, bool RAW, uint32_t CHUNK>
-__device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t b, WaveLdsT<CHUNK> &L, const uint32_t lane)
+// CHAIN = true: block b of ep.chain_blocks, one step of k_encode_chain's walk: the states come in through *carry_x and leave
+// through it, the counts are the walk's (given_counts[b]), listed checkpoints are absolute groups counted down in *carry_ck.
+template <uint32_t S, bool RAW, uint32_t CHUNK, bool CHAIN = false>
+__device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t b, WaveLdsT<CHUNK> &L, const uint32_t lane, uint32_t *carry_x = nullptr,
+                                            uint32_t *carry_ck = nullptr)
 {
   constexpr uint32_t kChunk = CHUNK, kRing = 2 * CHUNK;
   using Chunk = ChunkT<CHUNK>;
-  const uint64_t begin = RAW ? 0 : (uint64_t)b * ep.block;
-  const uint64_t end = RAW || b + 1 == ep.n_blocks ? ep.n : begin + ep.block;
+  const uint64_t begin = CHAIN ? ep.chain_blocks[b].begin : RAW ? 0 : (uint64_t)b * ep.block;
+  const uint64_t end = CHAIN ? ep.chain_blocks[b].end : RAW || b + 1 == ep.n_blocks ? ep.n : begin + ep.block;
   const uint32_t size = (uint32_t)(end - begin);
   const uint8_t *in = ep.in;
-  uint8_t *slot_end = ep.scratch + (uint64_t)(b + 1) * ep.slot_bytes;
+  const uint64_t slot_bytes = CHAIN ? ep.chain_blocks[b].slot_bytes : ep.slot_bytes;
+  uint8_t *slot_end = CHAIN ? ep.scratch + ep.chain_blocks[b].slot_end : ep.scratch + (uint64_t)(b + 1) * ep.slot_bytes;
 
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
   uint32_t raw[4] = {0, 0, 0, 0};
@@ -651,6 +655,21 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
       }
       return;
     }
+  }
+  else if constexpr (CHAIN)
+  {
+    const uint32_t single = ep.chain_blocks[b].single;
+    if (single != 0) // single-symbol block: only the marker word, states untouched (mt_rANS32x64_16w_encode.cpp:289-295)
+    {
+      if (lane == 0)
+      {
+        ((U64a2 *)(slot_end - 8))->v = (uint64_t)size | ((uint64_t)1 << 63) | ((uint64_t)(single & 0xFF) << 54);
+        ep.image_bytes[b] = 8;
+      }
+      return;
+    }
+    for (uint32_t k = 0; k < 4; k++) // the walk's normalised counts (hsrans_host.cpp reference_blocks / fixed_blocks)
+      raw[k] = ep.given_counts[(uint64_t)b * 256 + lane * 4 + k];
   }
   else
   {
@@ -733,7 +752,7 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
   const float factor = (float)target / (float)(uint64_t)size;
   uint32_t sc[4];
   uint32_t part = 0;
-  const bool normalised = RAW && ep.given_counts != nullptr; // the caller's hist_t: already sums to 2^bits (checked on the host)
+  const bool normalised = (RAW || CHAIN) && ep.given_counts != nullptr; // the caller's hist_t: already sums to 2^bits (checked on the host)
   for (uint32_t k = 0; k < 4; k++)
   {
     const float v = __fmul_rn((float)raw[k], factor); // one rounding per operation, like the reference's build
@@ -751,11 +770,12 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
   // (a block whose scaled counts sum above the target replays ~130 extractions of the heap sort, the others a handful; raising those
   // wavefronts' priority — s_setprio 3 — where two share a SIMD was measured: their normalisation 56 -> 49 us at the 90th percentile,
   // the kernel's length unchanged, 138 us: not kept)
-  if (sum != target && !normalised)
-  {
-    adjust_counts<!RAW>(L, lane, sc, sum, target);
-    part = sc[0] + sc[1] + sc[2] + sc[3];
-  }
+  if constexpr (!CHAIN) // (a chain's counts are normalised by the walk)
+    if (sum != target && !normalised)
+    {
+      adjust_counts<!RAW>(L, lane, sc, sum, target);
+      part = sc[0] + sc[1] + sc[2] + sc[3];
+    }
   // exclusive prefix over the 256 counts: lane-local then across lanes
   uint32_t incl = part;
   for (int d = 1; d < 64; d <<= 1)
@@ -799,9 +819,9 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
   // chunk on its way in registers; symbols and their table entries are fetched one and two sets (of four groups) ahead of
   // the set being coded, so that the state update is the only dependent chain.
   const uint32_t byte_in_group = enc_lane_to_byte(lane) & (S - 1);
-  uint32_t x = 1u << 15;
-  uint8_t *slot = slot_end - ep.slot_bytes; // the block's scratch slot; words are written from its end downwards
-  uint32_t p = (uint32_t)ep.slot_bytes;     // byte offset (from `slot`) of the lowest word written so far
+  uint32_t x = CHAIN ? *carry_x : 1u << 15;
+  uint8_t *slot = slot_end - slot_bytes; // the block's scratch slot; words are written from its end downwards
+  uint32_t p = (uint32_t)slot_bytes;     // byte offset (from `slot`) of the lowest word written so far
   // (asking for this first input ahead of the normalisation, which uses neither the ring nor these registers, was measured: nothing)
   const uint32_t n_chunks = (size + kChunk - 1) / kChunk;
   chunk_to_lds(L, chunk_load<CHUNK>(in, begin, end, n_chunks - 1, lane), n_chunks - 1, lane);
@@ -819,29 +839,38 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
     if (lane < S)
       ep.ck_states[ck * S + lane] = x;
     if (lane == 0)
-      ep.ck_pos[ck] = (uint32_t)ep.slot_bytes - p;
+      ep.ck_pos[ck] = (uint32_t)slot_bytes - p;
   };
-  auto checkpoint = [&](uint32_t gr) { checkpoint_at((uint64_t)b * ep.max_ck + (gr / ep.interval - 1)); };
-  if (!RAW && lane == 0)
+  auto checkpoint = [&](uint32_t gr) { checkpoint_at((CHAIN ? (uint64_t)ep.chain_blocks[b].ck_base : (uint64_t)b * ep.max_ck) + (gr / ep.interval - 1)); };
+  if (!RAW && !CHAIN && lane == 0)
     ep.chain_count[b] = 1 + (ep.interval != 0 && whole_groups >= 1 ? (whole_groups - 1) / ep.interval : 0);
   // RAW with listed checkpoints (ascending group indices, multiples of 4; hsrans_host.cpp encode(): `wanted`): the list is walked
   // from its end; entries at or behind the last whole group are never checkpoints
-  uint32_t ck_left = RAW && ep.ck_groups ? ep.n_ck_groups : 0;
-  while (ck_left != 0 && ep.ck_groups[ck_left - 1] >= whole_groups)
+  // CHAIN: the host keeps only the entries that are checkpoints (inside a coded block, not its first group, below the file's last
+  // whole group) and this block's are the highest ones left; ck_want is relative to the block's first group g_first
+  const uint64_t g_first = begin / S;
+  uint32_t ck_left = CHAIN ? *carry_ck : RAW && ep.ck_groups ? ep.n_ck_groups : 0;
+  while (!CHAIN && ck_left != 0 && ep.ck_groups[ck_left - 1] >= whole_groups)
     ck_left--;
-  uint32_t ck_want = ck_left ? ep.ck_groups[ck_left - 1] : 0; // (0 is never asked for)
+  auto want_of = [&](uint32_t left) -> uint32_t {
+    if (left == 0)
+      return 0;
+    const uint64_t g = ep.ck_groups[left - 1];
+    return CHAIN ? (g > g_first ? (uint32_t)(g - g_first) : 0) : (uint32_t)g;
+  };
+  uint32_t ck_want = want_of(ck_left); // (0 is never asked for)
   auto listed = [&](uint32_t gr) {
-    if (!RAW || gr != ck_want || gr == 0)
+    if (!(RAW || CHAIN) || gr != ck_want || gr == 0)
       return;
     checkpoint_at(ck_left - 1);
     ck_left--;
-    ck_want = ck_left ? ep.ck_groups[ck_left - 1] : 0;
+    ck_want = want_of(ck_left);
   };
 
   // emitted words: [p, flushed_to) of the slot is still in the LDS ring only; a whole segment leaves with one 8-byte store per lane
   const uint32_t out_ring = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)L.order;
   const uint32_t sink = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)L.sink + 4 * lane;
-  uint32_t flushed_to = (uint32_t)ep.slot_bytes; // (a multiple of kOutSeg: encode_slot_bytes)
+  uint32_t flushed_to = (uint32_t)slot_bytes; // (a multiple of kOutSeg: encode_slot_bytes)
   auto flush_segment = [&]() {
     flushed_to -= kOutSeg;
     const uint2 v = *(const uint2 *)((const uint8_t *)L.order + ((flushed_to & (kOutRing - 1)) + lane * 8));
@@ -901,7 +930,7 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
   // the next set (<= t) that ends a chunk whose ring half is wanted / that a checkpoint follows / that a listed checkpoint follows; -1: none
   int32_t ev_chunk = t >= (int32_t)(2 * kSetsPerChunk) ? (int32_t)((uint32_t)t / kSetsPerChunk * kSetsPerChunk) : -1;
   int32_t ev_ck = ck_sets != 0 && t >= (int32_t)ck_sets ? (int32_t)((uint32_t)t / ck_sets * ck_sets) : -1;
-  auto listed_set = [&]() { return RAW && ck_want != 0 && (int32_t)(ck_want / 4) <= t ? (int32_t)(ck_want / 4) : -1; };
+  auto listed_set = [&]() { return (RAW || CHAIN) && ck_want != 0 && (int32_t)(ck_want / 4) <= t ? (int32_t)(ck_want / 4) : -1; };
   int32_t ev_listed = listed_set();
   auto max3 = [](int32_t a, int32_t b, int32_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); };
   int32_t event = max3(ev_chunk, ev_ck, ev_listed);
@@ -912,7 +941,7 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
       checkpoint((uint32_t)(4 * t));
       ev_ck = t > (int32_t)ck_sets ? t - (int32_t)ck_sets : -1; // (never after set 0: group 0 starts no chain of its own)
     }
-    if (RAW && t == ev_listed)
+    if ((RAW || CHAIN) && t == ev_listed)
     {
       listed((uint32_t)(4 * t));
       ev_listed = listed_set();
@@ -984,7 +1013,14 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
     ep.stamps[b * 4 + 2] = t2;
     ep.stamps[b * 4 + 3] = t3;
   }
-  const uint32_t words_bytes = (uint32_t)ep.slot_bytes - p;
+  const uint32_t words_bytes = (uint32_t)slot_bytes - p;
+  if constexpr (CHAIN)
+  {
+    *carry_x = x;
+    *carry_ck = ck_left;
+    if (ep.block_states != nullptr && lane < S)
+      ep.block_states[(uint64_t)b * S + lane] = x;
+  }
   wave_sync();
   for (uint32_t o = p + 2 * lane; o < flushed_to; o += 128) // the ring's rest (less than two segments), word by word
     *(uint16_t *)(slot + o) = *(const uint16_t *)((const uint8_t *)L.order + (o & (kOutRing - 1)));
@@ -1008,6 +1044,19 @@ __device__ __forceinline__ void encode_body(const EncParams &ep, const uint32_t 
       *(uint16_t *)(h + 16 + 2 * (lane * 4 + k)) = (uint16_t)sc[k];
     if (lane < S)
       ((U32a2 *)(h + 16 + 512 + 4 * lane))->v = x;
+    return;
+  }
+  if (CHAIN && !ep.chain_mt)
+  {
+    // ---- block_ header in front of the words: [size u64][counts 256 x u16] (block_rANS32x64_16w_encode.cpp; hsrans_host.cpp encode()) ----
+    uint8_t *hb = slot + p - (8 + 512);
+    if (lane == 0)
+    {
+      ((U64a2 *)hb)->v = (uint64_t)size;
+      ep.image_bytes[b] = (uint64_t)(slot_end - hb);
+    }
+    for (uint32_t k = 0; k < 4; k++)
+      *(uint16_t *)(hb + 8 + 2 * (lane * 4 + k)) = (uint16_t)sc[k];
     return;
   }
   // ---- block header in front of the words: [size u64][skip u64][states S x u32][counts 256 x u16] ----
@@ -1123,6 +1172,119 @@ __global__ void __launch_bounds__(256) k_block_histograms(EncParams ep, uint32_t
   for (uint32_t c = 0; c < kCopies; c++) // (thread t sums symbol t's copies starting at copy t: the 32 lanes served together read 32 banks)
     v += sub[threadIdx.x * kCopies + ((threadIdx.x + c) & (kCopies - 1))];
   counts[(uint64_t)b * 256 + threadIdx.x] = v;
+}
+
+// the unit summaries of the block walk (hsrans_host.h UnitSummary: counts[256], run_len, run_sym, fresh_cost; 1040 bytes), a workgroup per unit
+// of ep.block symbols: k_block_histograms' counting, and per thread the highest position whose byte differs from the unit's last
+// byte (one compare per byte; the run that ends the unit starts behind the highest of them)
+__global__ void __launch_bounds__(256) k_unit_summaries(EncParams ep, uint8_t *summaries)
+{
+  constexpr uint32_t kCopies = 32;
+  __shared__ uint32_t sub[256 * kCopies];
+  __shared__ uint32_t differ;
+  const uint32_t b = blockIdx.x;
+  const uint64_t begin = (uint64_t)b * ep.block;
+  const uint64_t end = b + 1 == ep.n_blocks ? ep.n : begin + ep.block;
+  const uint32_t last = ep.in[end - 1];
+  for (uint32_t k = threadIdx.x; k < 256 * kCopies; k += 256)
+    sub[k] = 0;
+  if (threadIdx.x == 0)
+    differ = 0;
+  __syncthreads();
+  uint32_t *mine = sub + (threadIdx.x & (kCopies - 1));
+  uint32_t my_differ = 0; // 1 + offset (from begin) of the highest byte seen that is not `last`; 0: none
+  auto count = [&](const uint4 &d, uint64_t off, uint32_t have) {
+    const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++)
+      if (k < have)
+      {
+        const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
+        atomicAdd(&mine[c * kCopies], 1u);
+        my_differ = c != last ? (uint32_t)(off - begin) + k + 1 : my_differ; // (offsets ascend per thread)
+      }
+  };
+  uint64_t off = begin + threadIdx.x * 16;
+  for (; off + 3 * 4096 + 16 <= end; off += 4 * 4096)
+  {
+    uint4 d[4];
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++)
+      d[u] = *(const uint4 *)(ep.in + off + u * 4096);
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++)
+      count(d[u], off + u * 4096, 16);
+  }
+  for (; off < end; off += 4096)
+    count(load16_guarded(ep.in, off, end), off, end - off < 16 ? (uint32_t)(end - off) : 16);
+  if (my_differ)
+    atomicMax(&differ, my_differ);
+  __syncthreads();
+  uint32_t v = 0;
+  for (uint32_t c = 0; c < kCopies; c++)
+    v += sub[threadIdx.x * kCopies + ((threadIdx.x + c) & (kCopies - 1))];
+  uint32_t *out = (uint32_t *)(summaries + (uint64_t)b * kUnitSummaryBytes);
+  out[threadIdx.x] = v;
+  if (threadIdx.x == 0)
+  {
+    out[256] = (uint32_t)(end - begin) - differ;
+    out[257] = last;
+    out[258] = 0; // fresh_cost: k_unit_costs
+    out[259] = 0;
+  }
+}
+
+// The adaptive walk's per-unit term (hsrans_host.cpp unit_fresh_cost): the unit's counts normalised at the unit size — the coding
+// wavefront's normalisation, one rounding per operation and the heap sort's tie order, which is normalize_counts bit for bit — and its
+// code length under them, sum of counts[s] * log2f(fresh[s] / 2^bits) with the logarithms from the host's table, each product and
+// each difference rounded on its own (__fmul_rn / __fsub_rn: no contraction), subtracted in symbol order.  A wavefront per whole
+// unit; the host keeps only the old histogram's term of _CanExtendHist.  (A short last unit is never a candidate: 0.)
+struct UnitCostLds
+{
+  uint32_t order[256]; // heap_take_largest's sort, as in WaveLdsT
+  uint4 table[256];    // (its scratch)
+  float prod[256];
+};
+__global__ void __launch_bounds__(64) k_unit_costs(EncParams ep, uint8_t *summaries, const float *log_table)
+{
+  __shared__ UnitCostLds L;
+  const uint32_t lane = lane_id(), u = blockIdx.x;
+  uint32_t *sw = (uint32_t *)(summaries + (uint64_t)u * kUnitSummaryBytes);
+  if ((uint64_t)(u + 1) * ep.block > ep.n)
+  {
+    if (lane == 0)
+      sw[258] = 0;
+    return;
+  }
+  const uint32_t target = 1u << ep.bits;
+  const float factor = (float)target / (float)ep.block;
+  uint32_t raw[4], sc[4], part = 0;
+  for (uint32_t k = 0; k < 4; k++)
+  {
+    raw[k] = sw[lane * 4 + k];
+    const float v = __fmul_rn((float)raw[k], factor);
+    uint32_t c = (uint32_t)(uint16_t)__fadd_rn(v, 0.5f);
+    if (c == 0 && raw[k] != 0)
+      c = 1;
+    sc[k] = c;
+    part += c;
+    L.order[lane * 4 + k] = (c << 8) | (lane * 4 + k);
+  }
+  const uint32_t sum = wave_sum(part);
+  wave_sync();
+  if (sum != target)
+    adjust_counts<true>(L, lane, sc, sum, target);
+  for (uint32_t k = 0; k < 4; k++)
+    L.prod[lane * 4 + k] = raw[k] != 0 ? __fmul_rn((float)raw[k], log_table[sc[k]]) : 0.0f;
+  wave_sync();
+  if (lane == 0)
+  {
+    float cost = (float)(2 * 256 + ep.S * 4 + 8 * 2) * 0.5f;
+    for (uint32_t k = 0; k < 256; k++)
+      if (sw[k] != 0)
+        cost = __fsub_rn(cost, L.prod[k]);
+    ((float *)sw)[258] = cost;
+  }
 }
 
 template <uint32_t S>
@@ -1427,6 +1589,87 @@ __global__ void __launch_bounds__(256) k_copy_image(EncParams ep)
       *(uint16_t *)(ep.out + i) = *(const uint16_t *)(src + i);
 }
 
+// ---- chain encodes: block_ / mt_ streams whose coder states run through every block ----------------------------------------
+// The reference carries the states from block to block (mt_rANS32x64_16w_encode.cpp:220-222, the block_ encoders alike), so the
+// whole input is ONE dependent chain per state: one wavefront codes the blocks back to front (encode_body<CHAIN>), each into a
+// slot of its own, then adds up the image sizes and writes the file header; K_gather_chain moves the images into place.
+template <uint32_t S>
+__global__ void __launch_bounds__(64) k_encode_chain(EncParams ep)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  const uint32_t lane = lane_id();
+  WaveLdsT<kChunkFew> &L = *(WaveLdsT<kChunkFew> *)lds_raw;
+  uint32_t x = 1u << 15;
+  uint32_t ck_left = ep.ck_groups ? ep.n_ck_groups : 0;
+  for (uint32_t b = ep.n_blocks; b-- > 0;)
+  {
+    if (ep.chain_independent)
+      x = 1u << 15;
+    encode_body<S, false, kChunkFew, true>(ep, b, L, lane, &x, &ck_left);
+    wave_sync(); // (the next block rebuilds the table and the rings this one read; its image sizes are read below)
+  }
+  // placement: image b at the file header plus the images in front of it
+  const uint64_t head = 16 + (ep.chain_mt ? 0 : 4 * (uint64_t)S);
+  uint64_t at = head;
+  for (uint32_t base = 0; base < ep.n_blocks; base += 64)
+  {
+    const uint32_t i = base + lane;
+    const uint64_t v = i < ep.n_blocks ? ep.image_bytes[i] : 0;
+    uint64_t incl = v;
+    for (int d = 1; d < 64; d <<= 1)
+    {
+      const uint64_t o = __shfl_up(incl, d, 64);
+      if ((int)lane >= d)
+        incl += o;
+    }
+    if (i < ep.n_blocks)
+      ep.image_off[i] = at + incl - v;
+    at += __shfl(incl, 63, 64);
+  }
+  const uint64_t total = at;
+  const bool fits = total <= ep.out_cap;
+  if (lane == 0)
+  {
+    ep.result[0] = total;
+    ep.result[1] = fits ? 1 : 0;
+    ep.result[2] = ck_left; // (listed checkpoints that were not met: 0 unless the list was not what the host filtered)
+    if (fits)
+    {
+      ((uint64_t *)ep.out)[0] = ep.n;
+      ((uint64_t *)ep.out)[1] = total;
+    }
+  }
+  if (fits && !ep.chain_mt && lane < S) // block_: the states after the first block follow the file header
+    ((uint32_t *)(ep.out + 16))[lane] = x;
+}
+
+// copies image b (blockIdx.x) of a chain encode to its place, cut into gridDim.y parts; source and destination are 2-byte aligned
+__global__ void __launch_bounds__(256) k_gather_chain(EncParams ep)
+{
+  if (ep.result[1] == 0)
+    return;
+  const uint32_t b = blockIdx.x, part = blockIdx.y, parts = gridDim.y;
+  const uint64_t bytes = ep.image_bytes[b];
+  const uint8_t *src = ep.scratch + ep.chain_blocks[b].slot_end - bytes;
+  uint8_t *dst = ep.out + ep.image_off[b];
+  uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
+  if (head > bytes)
+    head = bytes;
+  const uint64_t body = (bytes - head) / 16;
+  if (part == 0)
+    for (uint64_t i = threadIdx.x * 2; i < head; i += 512)
+      *(uint16_t *)(dst + i) = *(const uint16_t *)(src + i);
+  const uint64_t lo = body * part / parts, hi = body * (part + 1) / parts;
+  for (uint64_t i = lo + threadIdx.x; i < hi; i += 256)
+  {
+    const U128a2 v = *(const U128a2 *)(src + head + i * 16);
+    *(uint4 *)(dst + head + i * 16) = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
+  }
+  if (part + 1 == parts)
+    for (uint64_t k = head + body * 16 + threadIdx.x * 2; k < bytes; k += 512)
+      *(uint16_t *)(dst + k) = *(const uint16_t *)(src + k);
+}
+
 } // namespace
 
 uint32_t encode_block_count(uint64_t n, uint64_t block, uint32_t S)
@@ -1516,6 +1759,40 @@ hipError_t launch_encode_raw(const EncParams &ep, uint32_t *d_counts, hipStream_
   else
     hipLaunchKernelGGL(k_encode_raw<32>, dim3(1), dim3(64), lds, stream, ep);
   hipLaunchKernelGGL(k_copy_image, dim3(1024), dim3(256), 0, stream, ep);
+  return hipGetLastError();
+}
+
+hipError_t launch_unit_summaries(const EncParams &ep, void *summaries, const float *log_table, hipStream_t stream)
+{
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_unit_summaries, dim3(ep.n_blocks), dim3(256), 0, stream, ep, (uint8_t *)summaries);
+  if (log_table != nullptr)
+    hipLaunchKernelGGL(k_unit_costs, dim3(ep.n_blocks), dim3(64), 0, stream, ep, (uint8_t *)summaries, log_table);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
+{
+  bool local = false;
+  bool &prepared = prepared_flag ? *prepared_flag : local;
+  const size_t lds = sizeof(WaveLdsT<kChunkFew>);
+  if (!prepared)
+  {
+    hipError_t e = hipFuncSetAttribute((const void *)k_encode_chain<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void *)k_encode_chain<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+      return e;
+    prepared = true;
+  }
+  (void)hipGetLastError();
+  if (ep.S == 64)
+    hipLaunchKernelGGL(k_encode_chain<64>, dim3(1), dim3(64), lds, stream, ep);
+  else
+    hipLaunchKernelGGL(k_encode_chain<32>, dim3(1), dim3(64), lds, stream, ep);
+  // parts per image: about 1 MiB each of the largest slot (ep.slot_bytes here), so that few large adaptive blocks still spread over the device
+  const uint32_t parts = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, ep.slot_bytes >> 20));
+  hipLaunchKernelGGL(k_gather_chain, dim3(ep.n_blocks, parts), dim3(256), 0, stream, ep);
   return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <thread>
 
 namespace hsrans
 {
@@ -221,52 +222,6 @@ struct Coder
   }
 };
 
-struct BlockSpan
-{
-  size_t begin, end;
-  bool single;
-  hsrans_hist hist; // histogram the block is coded with (unused for single-symbol blocks)
-};
-
-// fixed-size blocks; the last one absorbs a remainder shorter than S so that the reference decoders' loop condition
-// (`i < outLen - S + 1`, block_…decode.cpp:90) always reaches its header
-std::vector<BlockSpan> split_blocks(const uint8_t *in, size_t n, size_t block, uint32_t S, uint32_t bits)
-{
-  std::vector<BlockSpan> v;
-  size_t count = (n + block - 1) / block;
-  if (count > 1 && n - (count - 1) * block < S)
-    count--;
-  for (size_t b = 0; b < count; b++)
-  {
-    BlockSpan s;
-    s.begin = b * block;
-    s.end = b + 1 == count ? n : (b + 1) * block;
-    s.single = true;
-    for (size_t i = s.begin + 1; i < s.end && s.single; i++)
-      s.single = in[i] == in[s.begin];
-    if (!s.single)
-    {
-      uint32_t raw[256] = {};
-      for (size_t i = s.begin; i < s.end; i++)
-        raw[in[i]]++;
-      normalize_counts(&s.hist, raw, s.end - s.begin, bits);
-    }
-    v.push_back(s);
-  }
-  return v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The reference's adaptive block policy (block_rANS32x64_16w_encode.cpp:137-349, mt_rANS32x64_16w_encode.cpp:140-356 and
-// their 32-state twins), restated: blocks are chosen back to front in units of MinBlockSize; a block keeps growing
-// towards the front while a cost model (order-0 code length under the block's histogram vs. a fresh histogram for the
-// next unit) says one histogram is cheaper than two; runs of one symbol become single-symbol blocks.
-// Reproduces the reference's choices byte for byte, including two things that look like accidents: every block but the
-// last is modelled on the bytes up to the END of the block behind it (`blockBackPoint` is updated late, :344), and the
-// mt_ size cap is measured against that stale end too.  One deliberate deviation: the reference can leave a last block
-// shorter than S symbols (MinBlockSize < n < MinBlockSize + S), which its own decoders then mis-decode (SURVEY.md §8
-// quirks); here that remainder is merged into the block before it.
-// ---------------------------------------------------------------------------------------------------------------
 struct Policy
 {
   uint32_t min_block_bits;
@@ -293,50 +248,193 @@ Policy reference_policy(int container, uint32_t S, uint32_t bits)
   return p;
 }
 
-// _CanExtendHist (mt_…encode.cpp:61-136): would coding [start, start+size) with `old` cost less than 8 x replace_mul/4096
-// x 2^bits bits more than with a histogram of its own?  `counts` receives the unit's raw counts.
-bool can_extend(const uint8_t *in, size_t start, size_t size, const hsrans_hist &old, uint32_t bits, const Policy &pol, uint32_t S)
+} // namespace
+
+// ---------------------------------------------------------------------------------------------------------------
+// Unit summaries: what the block choices below read instead of the bytes.  The input is cut into aligned units of
+// `unit` symbols (the last one ends at n); per unit its 256 byte counts and the run of equal bytes that ends it.  The
+// walk only ever asks for the counts of [a, e) with a on a unit boundary and e a unit boundary, n, or ceil_S(start of
+// a run that ends e's unit) — single-symbol blocks start at ceil_S(run start) and the next block ends there — and the
+// counts of that last unit's prefix [unit start, ceil_S(run start)) are its counts less the run's bytes behind the cut.
+// The host encoder fills the summaries here, the gfx950 one in k_unit_summaries (hsrans_encode.hip); one walk serves both.
+// ---------------------------------------------------------------------------------------------------------------
+void unit_summaries(const uint8_t *in, size_t n, size_t unit, UnitSummary *out)
 {
-  uint32_t counts[256] = {};
-  for (size_t i = start; i < start + size; i++)
-    counts[in[i]]++;
-  hsrans_hist fresh;
-  normalize_counts(&fresh, counts, (size_t)1 << pol.min_block_bits, bits);
-  const float total = (float)(1u << bits);
+  const size_t n_units = (n + unit - 1) / unit;
+  for (size_t k = 0; k < n_units; k++)
+  {
+    UnitSummary &u = out[k];
+    const size_t b = k * unit, e = std::min(n, b + unit);
+    memset(u.counts, 0, sizeof(u.counts));
+    for (size_t i = b; i < e; i++)
+      u.counts[in[i]]++;
+    const uint8_t last = in[e - 1];
+    size_t r = e - 1;
+    while (r > b && in[r - 1] == last)
+      r--;
+    u.run_sym = last;
+    u.run_len = (uint32_t)(e - r);
+    u.fresh_cost = 0;
+    u.reserved = 0;
+  }
+}
+
+namespace
+{
+
+struct UnitView
+{
+  const UnitSummary *u;
+  size_t n, unit;
+  uint32_t S;
+
+  size_t unit_end(size_t k) const { return std::min(n, (k + 1) * unit); }
+  // counts of [a, e), a on a unit boundary (see above); false: e is not an end the walk can ask for
+  bool range(uint32_t counts[256], size_t a, size_t e, uint32_t *distinct, uint8_t *last_symbol) const
+  {
+    memset(counts, 0, 256 * sizeof(uint32_t));
+    for (size_t k = a / unit; k * unit < e; k++)
+    {
+      const UnitSummary &s = u[k];
+      const size_t ue = unit_end(k);
+      for (int c = 0; c < 256; c++)
+        counts[c] += s.counts[c];
+      if (ue <= e)
+        continue;
+      const size_t cut = std::max(k * unit, (ue - s.run_len + S - 1) & ~(size_t)(S - 1)); // ceil_S(run start), inside the unit
+      if (cut != e)
+        return false;
+      counts[s.run_sym] -= (uint32_t)(ue - cut);
+      break;
+    }
+    *distinct = 0;
+    for (int c = 0; c < 256; c++)
+      if (counts[c])
+      {
+        (*distinct)++;
+        *last_symbol = (uint8_t)c;
+      }
+    return true;
+  }
+};
+
+// _CanExtendHist (mt_…encode.cpp:61-136): would coding a unit with raw counts `counts` with `old` cost less than
+// 8 x replace_mul/4096 x 2^bits bits more than with a histogram of its own?  The unit's own term (`cost_new`, the code length
+// under its fresh histogram) depends on the unit alone and comes with its summary (unit_fresh_costs, or k_unit_costs on the
+// device); `table` is walk_log_table's.  One rounding per operation, accumulated in symbol order, as the reference does.
+bool can_extend(const uint32_t counts[256], float cost_new, const hsrans_hist &old, uint32_t bits, const Policy &pol, const float *table)
+{
+#pragma clang fp contract(off)
   const size_t replace_point = ((size_t)(1u << bits) * pol.replace_mul) >> 12;
   float cost_old = 0;
+  for (int s = 0; s < 256; s++)
+  {
+    if (counts[s] == 0)
+      continue;
+    const float before = (float)(counts[s] - 1) * table[old.symbolCount[s]];
+    cost_old -= before;
+  }
+  return cost_old - cost_new < (float)replace_point;
+}
+
+} // namespace
+
+void walk_log_table(uint32_t bits, float *table)
+{
+  const float total = (float)(1u << bits);
+  for (uint32_t k = 0; k <= (1u << bits); k++)
+    table[k] = log2f((float)k / total);
+}
+
+float unit_fresh_cost(const uint32_t counts[256], const uint16_t fresh[256], uint32_t S, const float *table)
+{
+#pragma clang fp contract(off)
   float cost_new = (float)(2 * 256 + S * 4 + 8 * 2) * 0.5f;
   for (int s = 0; s < 256; s++)
   {
     if (counts[s] == 0)
       continue;
-    const float before = (float)(counts[s] - 1) * log2f((float)old.symbolCount[s] / total);
-    const float after = (float)counts[s] * log2f((float)fresh.symbolCount[s] / total);
-    cost_old -= before;
+    const float after = (float)counts[s] * table[fresh[s]];
     cost_new -= after;
   }
-  return cost_old - cost_new < (float)replace_point;
+  return cost_new;
 }
 
-void count_range(uint32_t counts[256], const uint8_t *in, size_t begin, size_t end, uint32_t *distinct, uint8_t *last_symbol)
+void unit_fresh_costs(int container, size_t n, uint32_t S, uint32_t bits, UnitSummary *units)
 {
-  memset(counts, 0, 256 * sizeof(uint32_t));
-  for (size_t i = begin; i < end; i++)
-    counts[in[i]]++;
-  *distinct = 0;
-  for (int s = 0; s < 256; s++)
-    if (counts[s])
-    {
-      (*distinct)++;
-      *last_symbol = (uint8_t)s;
-    }
+  const size_t unit = walk_unit(container, S, bits);
+  std::vector<float> table((1u << bits) + 1);
+  walk_log_table(bits, table.data());
+  for (size_t k = 0; k < (n + unit - 1) / unit; k++)
+  {
+    units[k].fresh_cost = 0; // (a short last unit is never a candidate)
+    if ((k + 1) * unit > n)
+      continue;
+    hsrans_hist fresh;
+    normalize_counts(&fresh, units[k].counts, unit, bits);
+    units[k].fresh_cost = unit_fresh_cost(units[k].counts, fresh.symbolCount, S, table.data());
+  }
 }
 
-std::vector<BlockSpan> reference_blocks(int container, const uint8_t *in, size_t n, uint32_t S, uint32_t bits)
+size_t walk_unit(int container, uint32_t S, uint32_t bits)
+{
+  return (size_t)1 << reference_policy(container, S, bits).min_block_bits;
+}
+
+// fixed-size blocks from summaries with unit == block; the last one absorbs a remainder shorter than S so that the
+// reference decoders' loop condition (`i < outLen - S + 1`, block_…decode.cpp:90) always reaches its header
+bool fixed_blocks(size_t n, size_t block, uint32_t S, uint32_t bits, const UnitSummary *units, std::vector<BlockSpan> *out)
+{
+  out->clear();
+  size_t count = (n + block - 1) / block;
+  if (count > 1 && n - (count - 1) * block < S)
+    count--;
+  const UnitView view{units, n, block, S};
+  for (size_t b = 0; b < count; b++)
+  {
+    BlockSpan s{};
+    s.begin = b * block;
+    s.end = b + 1 == count ? n : (b + 1) * block;
+    uint32_t counts[256], distinct = 0;
+    uint8_t sym = 0;
+    if (!view.range(counts, s.begin, s.end, &distinct, &sym))
+      return false;
+    s.single = distinct == 1;
+    s.symbol = sym;
+    if (!s.single)
+      normalize_counts(&s.hist, counts, s.end - s.begin, bits);
+    out->push_back(s);
+  }
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The reference's adaptive block policy (block_rANS32x64_16w_encode.cpp:137-349, mt_rANS32x64_16w_encode.cpp:140-356 and
+// their 32-state twins), restated: blocks are chosen back to front in units of MinBlockSize; a block keeps growing
+// towards the front while a cost model (order-0 code length under the block's histogram vs. a fresh histogram for the
+// next unit) says one histogram is cheaper than two; runs of one symbol become single-symbol blocks.
+// Reproduces the reference's choices byte for byte, including two things that look like accidents: every block but the
+// last is modelled on the bytes up to the END of the block behind it (`blockBackPoint` is updated late, :344), and the
+// mt_ size cap is measured against that stale end too.  One deliberate deviation: the reference can leave a last block
+// shorter than S symbols (MinBlockSize < n < MinBlockSize + S), which its own decoders then mis-decode (SURVEY.md §8
+// quirks); here that remainder is merged into the block before it.
+// Reads unit summaries of unit walk_unit() (see unit_summaries above), never the bytes.
+// ---------------------------------------------------------------------------------------------------------------
+bool reference_blocks(int container, size_t n, uint32_t S, uint32_t bits, const UnitSummary *units, std::vector<BlockSpan> *out)
 {
   const Policy pol = reference_policy(container, S, bits);
   const size_t unit = (size_t)1 << pol.min_block_bits;
-  std::vector<BlockSpan> back_to_front;
+  const UnitView view{units, n, unit, S};
+  std::vector<BlockSpan> &back_to_front = *out;
+  back_to_front.clear();
+  std::vector<float> table((1u << bits) + 1);
+  walk_log_table(bits, table.data());
+  struct Final // a coded block's histogram: normalised after the walk (no decision reads it), several blocks at a time
+  {
+    uint32_t counts[256];
+    uint64_t total;
+  };
+  std::vector<Final> finals;
   uint32_t counts[256];
   uint32_t distinct;
   uint8_t symbol = 0;
@@ -354,15 +452,28 @@ std::vector<BlockSpan> reference_blocks(int container, const uint8_t *in, size_t
   while (true)
   {
     BlockSpan b{};
-    count_range(counts, in, target, block_end, &distinct, &symbol);
+    if (!view.range(counts, target, block_end, &distinct, &symbol))
+      return false;
     if (distinct == 1)
     {
-      // single-symbol block: swallow the whole run, then give back what does not start on a group boundary
+      // single-symbol block: swallow the whole run, then give back what does not start on a group boundary.  target is on a
+      // unit boundary: the run goes on through whole units of that symbol and stops inside the first unit whose own run is shorter
       size_t run = target;
-      while (run > 0 && in[run - 1] == symbol)
-        run--;
+      while (run > 0)
+      {
+        const UnitSummary &u = units[run / unit - 1];
+        if (u.run_sym != symbol)
+          break;
+        if (u.run_len < unit)
+        {
+          run -= u.run_len;
+          break;
+        }
+        run -= unit;
+      }
       target = (run + S - 1) & ~(size_t)(S - 1);
       b.single = true;
+      b.symbol = symbol;
     }
     else
     {
@@ -374,14 +485,18 @@ std::vector<BlockSpan> reference_blocks(int container, const uint8_t *in, size_t
           extra++;
         }
       normalize_counts(&b.hist, counts, first ? block_end - target + extra : unit, bits);
-      while (target > 0 && stale_end - target < pol.max_block && can_extend(in, target - unit, unit, b.hist, bits, pol, S))
+      while (target > 0 && stale_end - target < pol.max_block &&
+             can_extend(units[target / unit - 1].counts, units[target / unit - 1].fresh_cost, b.hist, bits, pol, table.data()))
         target -= unit;
       // the histogram that is actually used: counts of [target, stale_end) — for every block but the last that range
       // reaches into the block behind it
+      Final f;
       uint32_t d2;
       uint8_t s2;
-      count_range(counts, in, target, stale_end, &d2, &s2);
-      normalize_counts(&b.hist, counts, stale_end - target, bits);
+      if (!view.range(f.counts, target, stale_end, &d2, &s2))
+        return false;
+      f.total = stale_end - target;
+      finals.push_back(f);
       b.single = false;
     }
     b.begin = target;
@@ -397,11 +512,27 @@ std::vector<BlockSpan> reference_blocks(int container, const uint8_t *in, size_t
     if (target > 0 && block_end - target < unit * 2 / 3)
       target -= unit;
   }
+  // the coded blocks' histograms, in stream order (finals are back to front like the blocks)
   std::reverse(back_to_front.begin(), back_to_front.end());
-  return back_to_front;
+  std::reverse(finals.begin(), finals.end());
+  std::vector<BlockSpan *> coded;
+  for (BlockSpan &b : back_to_front)
+    if (!b.single)
+      coded.push_back(&b);
+  auto normalise = [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++)
+      normalize_counts(&coded[i]->hist, finals[i].counts, finals[i].total, bits);
+  };
+  const size_t workers = coded.size() < 256 ? 1 : std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
+  std::vector<std::thread> pool;
+  for (size_t w = 1; w < workers; w++)
+    pool.emplace_back(normalise, coded.size() * w / workers, coded.size() * (w + 1) / workers);
+  normalise(0, coded.size() / workers);
+  for (std::thread &t : pool)
+    t.join();
+  return true;
 }
 
-} // namespace
 
 size_t encode(int container, int states, uint32_t bits, const uint8_t *in, size_t n, uint8_t *out, size_t cap, const hsrans_hist *hist,
               hsrans_encode_opts *opts)
@@ -430,17 +561,16 @@ size_t encode(int container, int states, uint32_t bits, const uint8_t *in, size_
   };
   // block_/mt_: block_size == 0 selects the reference's adaptive block policy (byte-identical streams), anything else
   // fixed blocks of that many symbols
-  const bool fixed_blocks = opts && opts->block_size != 0;
+  const bool fixed = opts && opts->block_size != 0;
   const bool independent = opts && (opts->flags & HSRANS_ENC_INDEPENDENT_BLOCKS) != 0;
-  if (independent && (container != HSRANS_MT || !fixed_blocks))
+  if (independent && (container != HSRANS_MT || !fixed))
     return 0;
-  const size_t block = fixed_blocks ? opts->block_size : 65536;
+  const size_t block = fixed ? opts->block_size : 65536;
   if (block % 64 != 0)
     return 0;
 
-  // decoder view of the whole file: T whole groups then `tail` symbols (rANS32x64_16w.cpp:220-250)
+  // decoder view of the whole file: T whole groups then n - T * S symbols (rANS32x64_16w.cpp:220-250)
   const uint64_t T = n + 1 >= S ? (n - S + 1 + S - 1) / S : 0;
-  const uint32_t tail = (uint32_t)(n - T * S);
   const size_t last_group_start = (n - 1) / S * S;
 
   const size_t header_bytes = container == HSRANS_RAW ? 16 + 512 + 4 * (size_t)S : container == HSRANS_BLOCK ? 16 + 4 * (size_t)S : 16;
@@ -486,7 +616,14 @@ size_t encode(int container, int states, uint32_t bits, const uint8_t *in, size_
   }
   else
   {
-    const std::vector<BlockSpan> spans = fixed_blocks ? split_blocks(in, n, block, S, bits) : reference_blocks(container, in, n, S, bits);
+    const size_t unit = fixed ? block : walk_unit(container, S, bits);
+    std::vector<UnitSummary> units((n + unit - 1) / unit);
+    unit_summaries(in, n, unit, units.data());
+    if (!fixed)
+      unit_fresh_costs(container, n, S, bits, units.data());
+    std::vector<BlockSpan> spans;
+    if (!(fixed ? fixed_blocks(n, block, S, bits, units.data(), &spans) : reference_blocks(container, n, S, bits, units.data(), &spans)))
+      return 0;
     uint64_t next_header_from_end = 0;
     for (size_t b = spans.size(); b-- > 0;)
     {
@@ -569,6 +706,42 @@ size_t encode(int container, int states, uint32_t bits, const uint8_t *in, size_
     return total;
 
   // ---- sidecar plan: chains in output order ----
+  std::reverse(cps.begin(), cps.end()); // now ascending by group
+  std::vector<uint64_t> ck_group(cps.size()), ck_wfe(cps.size());
+  std::vector<uint32_t> ck_states(cps.size() * (size_t)S);
+  for (size_t k = 0; k < cps.size(); k++)
+  {
+    ck_group[k] = cps[k].group;
+    ck_wfe[k] = cps[k].words_from_end;
+    memcpy(&ck_states[k * S], cps[k].states, 4 * (size_t)S);
+  }
+  if (container == HSRANS_RAW)
+  {
+    opts->plan_size = raw_plan_from_checkpoints(states, bits, n, total, c.hist.symbolCount, c.x, cps.size(), ck_group.data(), ck_wfe.data(), ck_states.data(), interval,
+                                                opts->plan_out, opts->plan_capacity);
+    return opts->plan_size ? total : 0;
+  }
+  std::vector<EncodedBlock> blocks(metas.size()); // (metas are back to front: the plan wants stream order)
+  for (size_t b = 0; b < metas.size(); b++)
+  {
+    const BlockMeta &m = metas[metas.size() - 1 - b];
+    blocks[b] = EncodedBlock{m.span.begin, m.span.end, m.span.single, in[m.span.begin], m.words_from_end, m.hist_from_end, m.start_states};
+  }
+  opts->plan_size = blocks_plan_from_checkpoints(container, states, bits, n, total, interval, blocks.data(), blocks.size(), cps.size(), ck_group.data(), ck_wfe.data(),
+                                                 ck_states.data(), opts->plan_out, opts->plan_capacity);
+  return opts->plan_size ? total : 0;
+}
+
+// The sidecar plan of a block_/mt_ stream (the host encoder above, or the gfx950 one: hsrans_capi_encode.cpp hsrans_encode_device_ex):
+// chains in output order — per single-symbol block one fill chain, per coded block one chain from its start states plus one per
+// checkpoint inside it.
+size_t blocks_plan_from_checkpoints(int container, int states, uint32_t bits, uint64_t n, uint64_t total, uint32_t interval, const EncodedBlock *blocks,
+                                    size_t n_blocks, size_t n_ck, const uint64_t *ck_group, const uint64_t *ck_words_from_end, const uint32_t *ck_states,
+                                    uint8_t *plan_out, size_t plan_capacity)
+{
+  const uint32_t S = (uint32_t)states;
+  const uint64_t T = n + 1 >= S ? (n - S + 1 + S - 1) / S : 0; // whole groups (rANS32x64_16w.cpp:220-250)
+  const uint32_t tail = (uint32_t)(n - T * S);
   PlanBuilder pb;
   pb.begin(container, states, bits, n, total);
   pb.hdr.interval = interval;
@@ -582,61 +755,43 @@ size_t encode(int container, int states, uint32_t bits, const uint8_t *in, size_
     p.steps = (uint32_t)(whole_end > g_begin ? whole_end - g_begin : 0);
     return p;
   };
-  std::reverse(cps.begin(), cps.end()); // now ascending by group
-  if (container == HSRANS_RAW)
+  size_t k = 0;
+  for (size_t b = 0; b < n_blocks; b++)
   {
-    std::vector<uint64_t> ck_group(cps.size()), ck_wfe(cps.size());
-    std::vector<uint32_t> ck_states(cps.size() * (size_t)S);
-    for (size_t k = 0; k < cps.size(); k++)
+    const EncodedBlock &m = blocks[b];
+    if (m.single)
     {
-      ck_group[k] = cps[k].group;
-      ck_wfe[k] = cps[k].words_from_end;
-      memcpy(&ck_states[k * S], cps[k].states, 4 * (size_t)S);
+      Piece p{};
+      p.out_off = m.begin;
+      p.hist_off = m.symbol;
+      p.fill_len = m.end - m.begin;
+      p.flags = kPieceChainStart | kPieceFill;
+      pb.add_chain(p, nullptr);
+      continue;
     }
-    opts->plan_size = raw_plan_from_checkpoints(states, bits, n, total, c.hist.symbolCount, c.x, cps.size(), ck_group.data(), ck_wfe.data(), ck_states.data(), interval,
-                                                opts->plan_out, opts->plan_capacity);
-    return opts->plan_size ? total : 0;
-  }
-  {
-    size_t k = 0;
-    for (size_t b = metas.size(); b-- > 0;) // metas are back to front: walk in output order
+    const uint64_t g_first = m.begin / S;
+    const uint64_t g_last_excl = (m.end - 1) / S + 1;
+    const bool is_last_block = m.end == n;
+    uint64_t g = g_first;
+    const uint32_t *st = m.start_states;
+    uint64_t wfe = m.words_from_end;
+    while (true)
     {
-      const BlockMeta &m = metas[b];
-      if (m.span.single)
-      {
-        Piece p{};
-        p.out_off = m.span.begin;
-        p.hist_off = in[m.span.begin];
-        p.fill_len = m.span.end - m.span.begin;
-        p.flags = kPieceChainStart | kPieceFill;
-        pb.add_chain(p, nullptr);
-        continue;
-      }
-      const uint64_t g_first = m.span.begin / S;
-      const uint64_t g_last_excl = (m.span.end - 1) / S + 1;
-      const bool is_last_block = m.span.end == n;
-      uint64_t g = g_first;
-      const uint32_t *st = m.start_states;
-      uint64_t wfe = m.words_from_end;
-      while (true)
-      {
-        const bool more = k < cps.size() && cps[k].group < g_last_excl && cps[k].group > g_first;
-        const uint64_t g_next = more ? cps[k].group : g_last_excl;
-        Piece p = rans_piece(g, g_next, wfe, total - m.hist_from_end);
-        p.tail = (uint16_t)((!more && is_last_block) ? tail : 0);
-        p.flags = kPieceChainStart;
-        pb.add_chain(p, st);
-        if (!more)
-          break;
-        g = g_next;
-        st = cps[k].states;
-        wfe = cps[k].words_from_end;
-        k++;
-      }
+      const bool more = k < n_ck && ck_group[k] < g_last_excl && ck_group[k] > g_first;
+      const uint64_t g_next = more ? ck_group[k] : g_last_excl;
+      Piece p = rans_piece(g, g_next, wfe, total - m.hist_from_end);
+      p.tail = (uint16_t)((!more && is_last_block) ? tail : 0);
+      p.flags = kPieceChainStart;
+      pb.add_chain(p, st);
+      if (!more)
+        break;
+      g = g_next;
+      st = ck_states + k * S;
+      wfe = ck_words_from_end[k];
+      k++;
     }
   }
-  opts->plan_size = pb.serialize(opts->plan_out, opts->plan_capacity);
-  return opts->plan_size ? total : 0;
+  return pb.serialize(plan_out, plan_capacity);
 }
 
 // The sidecar plan of a raw stream from what its encoder recorded (the host encoder above, or the gfx950 one: hsrans_capi.cpp

@@ -33,6 +33,50 @@ size_t raw_plan_from_checkpoints(int states, uint32_t bits, uint64_t n, uint64_t
                                  const uint64_t *ck_group, const uint64_t *ck_words_from_end, const uint32_t *ck_states, uint32_t interval, uint8_t *plan_out,
                                  size_t plan_capacity);
 
+// ---- block_/mt_ block choice, shared by the host encoder and the gfx950 one (hsrans_capi_encode.cpp hsrans_encode_device_ex) ----
+// per aligned unit of the input: its byte counts and the run of equal bytes that ends it (1032 bytes; the device writes the same layout)
+struct UnitSummary
+{
+  uint32_t counts[256];
+  uint32_t run_len; // bytes of the run of equal bytes that ends the unit (the whole unit: its length)
+  uint32_t run_sym; // that byte
+  float fresh_cost; // adaptive walk: the unit's code length under a histogram of its own, normalised at the unit size (_CanExtendHist's cost_new)
+  uint32_t reserved;
+};
+static_assert(sizeof(UnitSummary) == 1040, "k_unit_summaries / k_unit_costs write this layout");
+struct BlockSpan
+{
+  uint64_t begin, end;
+  bool single;       // one symbol: coded as the 8-byte marker only
+  uint8_t symbol;    // (single blocks)
+  hsrans_hist hist;  // histogram the block is coded with (unused for single-symbol blocks)
+};
+void unit_summaries(const uint8_t *in, size_t n, size_t unit, UnitSummary *out); // ceil(n / unit) entries
+size_t walk_unit(int container, uint32_t S, uint32_t bits);                       // the adaptive policy's unit (1 << MinBlockSize bits)
+void walk_log_table(uint32_t bits, float *table); // log2f(k / 2^bits), k = 0 .. 2^bits: the cost model's code lengths
+// a unit's code length under its own normalised histogram `fresh`: one rounding per operation, in symbol order (k_unit_costs is its twin)
+float unit_fresh_cost(const uint32_t counts[256], const uint16_t fresh[256], uint32_t S, const float *table);
+void unit_fresh_costs(int container, size_t n, uint32_t S, uint32_t bits, UnitSummary *units); // fills fresh_cost on the host
+// the reference's adaptive block policy from summaries of unit walk_unit() with their fresh_cost; false only if the summaries are inconsistent
+bool reference_blocks(int container, size_t n, uint32_t S, uint32_t bits, const UnitSummary *units, std::vector<BlockSpan> *out);
+// fixed blocks of `block` symbols from summaries of unit `block` (the last block absorbs a remainder shorter than S)
+bool fixed_blocks(size_t n, size_t block, uint32_t S, uint32_t bits, const UnitSummary *units, std::vector<BlockSpan> *out);
+
+// sidecar plan of a block_/mt_ stream from what its encoder recorded: blocks in stream order, checkpoints ascending by group
+// (states n_ck x `states`).  What encode() emits; the gfx950 encoder fills the same records from its device arrays.
+struct EncodedBlock
+{
+  uint64_t begin, end;
+  bool single;
+  uint8_t symbol;
+  uint64_t words_from_end;      // decoder cursor at the block's start: bytes to the end of the stream
+  uint64_t hist_from_end;       // bytes between the block's counts and the end of the stream
+  const uint32_t *start_states; // the decoder's states at the block's start
+};
+size_t blocks_plan_from_checkpoints(int container, int states, uint32_t bits, uint64_t n, uint64_t total, uint32_t interval, const EncodedBlock *blocks,
+                                    size_t n_blocks, size_t n_ck, const uint64_t *ck_group, const uint64_t *ck_words_from_end, const uint32_t *ck_states,
+                                    uint8_t *plan_out, size_t plan_capacity);
+
 // in-memory plan under construction
 struct PlanBuilder
 {

@@ -386,6 +386,36 @@ int hsrans_decode_device_indexing(hsrans_ctx *ctx, hsrans_dplan *dplan, const vo
 size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity,
                             uint32_t block_size, uint32_t index_interval, void *hip_stream, hsrans_dplan **out_dplan);
 
+/* Every format hsrans_encode_ex writes, on the GPU: the same arguments, the same stream bytes at d_out, the same plan blob at
+ * opts->plan_out (opts->plan_size set) when opts asks for an index; out_dplan != NULL also returns that plan as a device plan for
+ * hsrans_decode_device.  What hsrans_encode_ex refuses, this call refuses too (0, nothing launched).  d_in / d_out are device
+ * pointers, 16-byte aligned; `hist` is used by HSRANS_RAW only (as hsrans_encode_ex).  Synchronises `hip_stream`.
+ *   HSRANS_RAW: hsrans_encode_device_raw.  HSRANS_MT with fixed HSRANS_ENC_INDEPENDENT_BLOCKS and no index: hsrans_encode_device.
+ *   Otherwise (block_ and mt_, the reference's adaptive blocks with block_size == 0 or fixed blocks, the states carried from block
+ *   to block as the reference's encoders carry them): the per-unit byte counts are taken on the device, the host walks the block
+ *   policy over them (the host encoder's own code), and ONE wavefront codes the blocks back to front — the carried states make the
+ *   whole input one dependent chain, like the raw format.
+ *   Independent mt_ blocks with index_interval also take the one-wave-per-block launch (its plan is copied back); with index_groups
+ *   they take the one-wavefront chain (fresh states per block): about 1 GB/s instead of hundreds.
+ * Limits: length <= 2^31 - 2^16 (as hsrans_encode_device_raw); index_groups with fixed blocks need block_size / states to be a
+ * multiple of 4 (checkpoints are taken between sets of four groups); both refused with 0.  Any block_size that is a multiple of 64
+ * is accepted (one longer than the input makes one block). */
+size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity,
+                               const hsrans_hist *hist, hsrans_encode_opts *opts, void *hip_stream, hsrans_dplan **out_dplan);
+/* The block choice behind block_ / mt_ streams (block_size 0: the reference's adaptive policy; else fixed blocks), as the host
+ * encoder makes it and as hsrans_encode_device_ex makes it from device-side unit summaries: blocks in stream order, `counts` the
+ * normalised histogram a block is coded with (zero for single-symbol blocks).  Returns the number of blocks (only the first
+ * `capacity` are written), 0 on bad arguments.  For inspection and tests; the device variant synchronises `hip_stream`. */
+typedef struct hsrans_block_choice
+{
+  uint64_t begin, end;
+  uint32_t single, symbol;
+  uint16_t counts[256];
+} hsrans_block_choice;
+size_t hsrans_block_choices(int container, int states, uint32_t bits, const void *in, size_t length, uint32_t block_size, hsrans_block_choice *out, size_t capacity);
+size_t hsrans_block_choices_device(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, uint32_t block_size,
+                                   hsrans_block_choice *out, size_t capacity, void *hip_stream);
+
 /* The raw format on the GPU (replaces src/rANS32x64_16w.cpp:34-166 `rANS32x64_16w_encode_scalar_N` / src/rANS32x32_16w.cpp for
  * data that lives in HBM): the format carries every coder state from the last symbol to the first, so it
  * is ONE wavefront's work — about 3.5x one host core, not a throughput kernel; mt_ (hsrans_encode_device) is the format to encode

@@ -376,56 +376,29 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
   // ---- the stream's plan, written on the device (K_plan), wrapped into a device plan ready for hsrans_decode_device ----
   if (result[2] == 0 || result[2] > 0xFFFFFFFFull)
     return 0;
-  hsrans_dplan *d = new (std::nothrow) hsrans_dplan;
+  hsrans_dplan *d = dplan_new(ctx);
   if (d == nullptr)
     return 0;
-  d->ctx = ctx;
-  PlanHeader h{};
-  memcpy(h.magic, "HSRPLAN1", 8);
-  h.container = HSRANS_MT;
-  h.states = ep.S;
-  h.bits = bits;
-  h.decoded_len = length;
-  h.stream_len = total;
-  h.n_chains = h.n_pieces = (uint32_t)result[2];
+  PlanHeader h = mt_plan_header(ep.S, bits, length, total, (uint32_t)result[2]);
   h.shared_hist = result[3] == 1 ? 1 : 0; // exactly one block with a histogram (hsrans_host.cpp PlanBuilder::serialize)
   h.aux_off = h.shared_hist ? result[4] : 0;
   h.interval = ep.interval;
-  const size_t bytes = (size_t)plan_size(h.n_chains, h.n_pieces, h.states, 0);
   const bool grouped = ep.interval != 0 && ep.n_blocks < h.n_chains;
-  // few large blocks: cut every block's chains into parts so that there are about two workgroup tasks per resident workgroup
-  // (parts of >= 128 chains, only while there are fewer blocks than resident workgroups: see hsrans_dplan_create)
-  const size_t want = (size_t)kGroupPartsPerCU * ctx->geom.num_cus;
-  ep.group_split = 1;
-  if (grouped && nb < want)
-    ep.group_split = (uint32_t)std::max<size_t>(1, std::min<size_t>({(want + nb - 1) / nb, (size_t)(ep.max_ck + 1) / kGroupPartChains, (size_t)64}));
+  // few large blocks: every block's chains in parts (every coded block but the last has max_ck + 1 chains; at most 64 parts a block)
+  ep.group_split = grouped ? group_parts_of(ep.max_ck + 1, std::min(group_parts_max(ctx->geom, nb), 64u)) : 1;
   // ONE device allocation for the status word, the ticket counters of the dynamic group order (as dplan_fill; without them the launch
   // falls back to the static order), the plan and the group list, one memset over the first three, one synchronisation (round 4:
   // up to four hipMalloc, three memsets, three synchronisations — 0.14 ms on top of a 0.2 ms encode)
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t cbytes = grouped ? (size_t)kCounterSets * kDynQueues * kDynQueueStride * 8 : 0;
-  const size_t gbytes = grouped ? nb * ep.group_split * sizeof(Group) : 0;
-  const size_t off_counters = 256, off_plan = off_counters + up256(cbytes), off_groups = off_plan + up256(bytes);
-  const size_t arena = off_groups + up256(gbytes);
-  bool ok = hipMalloc((void **)&d->d_arena, arena) == hipSuccess;
-  if (ok)
-  {
-    d->d_arena_cap = arena;
-    d->arena_used = arena;
-    d->d_status = (uint32_t *)d->d_arena;
-    d->d_counters = cbytes ? (unsigned long long *)(d->d_arena + off_counters) : nullptr;
-    d->d_plan = d->d_arena + off_plan;
-    d->d_plan_cap = bytes;
-    d->d_groups = gbytes ? d->d_arena + off_groups : nullptr;
-    d->d_groups_cap = gbytes;
-    ok = hipMemsetAsync(d->d_arena, 0, off_plan + bytes, s) == hipSuccess && hipMemcpyAsync(d->d_plan, &h, sizeof(h), hipMemcpyHostToDevice, s) == hipSuccess;
-  }
-  else
-    (void)hipGetLastError();
+  DplanRegions r;
+  r.counters = grouped;
+  r.plan = (size_t)plan_size(h.n_chains, h.n_pieces, h.states, 0);
+  r.groups = grouped ? nb * ep.group_split * sizeof(Group) : 0;
+  r.zero = kZeroThroughPlan;
+  bool ok = dplan_arena(d, r, s) == HSRANS_OK && hipMemcpyAsync(d->d_plan, &h, sizeof(h), hipMemcpyHostToDevice, s) == hipSuccess;
   if (ok)
   {
     ep.plan = d->d_plan;
-    ep.groups = grouped ? d->d_groups : nullptr;
+    ep.groups = d->d_groups;
     ep.n_chains = h.n_chains;
     ok = launch_encode_plan(ep, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   }
@@ -434,13 +407,7 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
     hsrans_dplan_destroy(d);
     return 0;
   }
-  d->hdr = h;
-  d->plan_bytes = bytes;
-  d->out_hi = h.decoded_len;
-  d->n_groups = grouped ? ep.n_blocks * ep.group_split : 0;
-  d->groups_lean = grouped && h.states == 64; // k_plan_blocks writes mergeable runs and fill groups only
-  d->spread_min_block = d->groups_lean ? ep.max_ck + 1 : 0; // (every coded block but the last has max_ck + 1 chains)
-  dplan_blocks_from_device_groups(d, s); // (k_decode_dealt's dealing wants the blocks as chain ranges: 32 bytes a group, once)
+  dplan_adopt(d, h, grouped ? ep.n_blocks * ep.group_split : 0, ep.max_ck + 1, s);
   *out_dplan = d;
   return total;
 }

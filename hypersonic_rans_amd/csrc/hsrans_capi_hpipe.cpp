@@ -141,12 +141,11 @@ try
            plan_chain_range(plan, plan_size, first, last - first, &sl.out_begin, &sl.out_end);
       if (ok)
       {
-        sl.dplan = new (std::nothrow) hsrans_dplan;
+        sl.dplan = dplan_new(ctx);
         ok = sl.dplan != nullptr;
       }
       if (ok)
       {
-        sl.dplan->ctx = ctx;
         ok = dplan_fill(sl.dplan, blob.data(), bytes, hs, nullptr) == HSRANS_OK && hipStreamSynchronize(nullptr) == hipSuccess &&
              hipEventCreateWithFlags(&sl.up_done, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&sl.dec_done, hipEventDisableTiming) == hipSuccess;
       }

@@ -359,36 +359,25 @@ try
     if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, st_bytes + wd_bytes))
       return HSRANS_E_HIP;
     const uint32_t nb = h.n_chains;
-    // few large blocks: every block's chains in parts, so that there are about two workgroup tasks per resident workgroup (as dplan_fill)
-    const size_t want = (size_t)kGroupPartsPerCU * ctx->geom.num_cus;
-    uint32_t group_split = 1;
-    if (nb < want)
-      group_split = (uint32_t)std::max<size_t>(1, std::min<size_t>({(want + nb - 1) / nb, (size_t)(n_ck / nb + 1) / kGroupPartChains, (size_t)64}));
-    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t plan_max = (size_t)plan_size(max_chains, max_chains, S, 0);
-    const size_t counter_bytes = (size_t)kCounterSets * kDynQueues * kDynQueueStride * 8;
-    const size_t group_bytes = (size_t)nb * group_split * sizeof(Group);
-    hsrans_dplan *nd = new (std::nothrow) hsrans_dplan;
+    // few large blocks: every block's chains in parts (at most 64 parts a block), as dplan_fill
+    const uint32_t group_split = group_parts_of((uint32_t)std::min<uint64_t>(n_ck / nb + 1, 0xFFFFFFFFu), std::min(group_parts_max(ctx->geom, nb), 64u));
+    hsrans_dplan *nd = dplan_new(ctx);
     if (nd == nullptr)
       return HSRANS_E_HIP;
-    nd->ctx = ctx;
-    const size_t arena = 256 + up256(counter_bytes) + up256(plan_max) + up256(group_bytes) + up256((size_t)nb * 4) + 256;
-    if (!grow(&nd->d_arena, &nd->d_arena_cap, arena))
+    DplanRegions r;
+    r.counters = true;
+    r.plan = (size_t)plan_size(max_chains, max_chains, S, 0);
+    r.groups = (size_t)nb * group_split * sizeof(Group);
+    r.scratch = 256 + (size_t)nb * 4; // the assembly's result words, then its chain offsets
+    r.zero = kZeroAll;
+    uint8_t *scratch = nullptr;
+    if (dplan_arena(nd, r, s, &scratch) != HSRANS_OK)
     {
       hsrans_dplan_destroy(nd);
       return HSRANS_E_HIP;
     }
-    uint8_t *at = nd->d_arena;
-    auto carve = [&](size_t bytes) { uint8_t *ptr = at; at += up256(bytes); return ptr; };
-    nd->d_status = (uint32_t *)carve(64);
-    nd->d_counters = (unsigned long long *)carve(counter_bytes);
-    nd->d_plan = carve(plan_max);
-    nd->d_plan_cap = plan_max;
-    nd->d_groups = carve(group_bytes);
-    nd->d_groups_cap = group_bytes;
-    uint32_t *d_chain_off = (uint32_t *)carve((size_t)nb * 4);
-    uint64_t *d_result = (uint64_t *)carve(64);
-    nd->arena_used = (size_t)(at - nd->d_arena);
+    uint64_t *d_result = (uint64_t *)scratch;
+    uint32_t *d_chain_off = (uint32_t *)(scratch + 256);
     KParams kp{};
     kp.stream = (const uint8_t *)d_stream;
     kp.stream_len = stream_length;
@@ -418,7 +407,7 @@ try
     uint32_t status = 0xFFFFFFFF;
     uint64_t counted[4] = {}; // chains in all, blocks with a histogram, the (one) histogram's offset, fewest chains of a coded block but the last
     const uint64_t &total = counted[0];
-    const bool ok = hipMemsetAsync(nd->d_arena, 0, nd->arena_used, s) == hipSuccess && launch_decode(kp, hl, ctx->geom, s, nullptr) == hipSuccess &&
+    const bool ok = launch_decode(kp, hl, ctx->geom, s, nullptr) == hipSuccess &&
                     launch_index_assemble(ia, s) == hipSuccess && hipMemcpyAsync(counted, d_result, sizeof(counted), hipMemcpyDeviceToHost, s) == hipSuccess &&
                     hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
     const bool synced = hipStreamSynchronize(s) == hipSuccess; // (nothing queued above may still be running when this returns, whatever failed)
@@ -433,24 +422,14 @@ try
       hsrans_dplan_destroy(nd);
       return rc;
     }
-    nd->hdr = h;
-    nd->hdr.n_chains = nd->hdr.n_pieces = (uint32_t)total;
-    nd->hdr.interval = index_interval;
-    nd->hdr.shared_hist = counted[1] == 1 ? 1 : 0;
-    nd->hdr.aux_off = nd->hdr.shared_hist ? counted[2] : 0;
-    nd->plan_bytes = (size_t)plan_size((uint32_t)total, (uint32_t)total, S, 0);
-    nd->out_hi = h.decoded_len;
-    const bool grouped = total > nb; // (no checkpoint fell inside any block: one chain per block, the ungrouped launch)
-    nd->n_groups = grouped ? nb * group_split : 0;
-    nd->groups_lean = grouped && S == 64;
-    const uint64_t fewest = counted[3] == 0 ? ~0ull : ~counted[3]; // ([3]: ~(the fewest chains of a coded block that is not the last); 0 = there is none)
-    nd->spread_min_block = nd->groups_lean ? (uint32_t)std::min<uint64_t>(fewest, 0xFFFFFFFFu) : 0;
-    if (!grouped)
-      nd->d_groups = nullptr, nd->d_counters = nullptr;
-    if (grouped)
-      dplan_blocks_from_device_groups(nd, s); // (k_decode_dealt's dealing wants the blocks as chain ranges)
-    if (getenv("HSRANS_DEBUG_STAMPS") && hipMalloc((void **)&nd->d_stamps, kStampWaves * 8 * 8) == hipSuccess)
-      (void)hipMemset(nd->d_stamps, 0, kStampWaves * 8 * 8);
+    PlanHeader hn = h;
+    hn.n_chains = hn.n_pieces = (uint32_t)total;
+    hn.interval = index_interval;
+    hn.shared_hist = counted[1] == 1 ? 1 : 0;
+    hn.aux_off = hn.shared_hist ? counted[2] : 0;
+    // (total == nb: no checkpoint fell inside any block — one chain per block, the ungrouped launch; counted[3]: ~(the fewest chains of a
+    // coded block that is not the last), 0 = there is none)
+    dplan_adopt(nd, hn, total > nb ? nb * group_split : 0, counted[3] == 0 ? ~0ull : ~counted[3], s);
     if (trace)
       fprintf(stderr, "hsrans_decode_device_indexing: on the device: %.3f ms in all (%llu chains, %zu plan bytes)\n", ms(t0, now()), (unsigned long long)total, nd->plan_bytes);
     *indexed = nd;

@@ -267,7 +267,7 @@ static int sharded_create_impl(hsrans_ctx *ctx, hsrans_comm *comm, int rank, int
     {
       const size_t n = hsrans_plan_slice(plan, plan_size, first, count, slice.data(), slice.size());
       hsrans_dplan *w = nullptr;
-      if (n != 0 && dplan_create_with_parts(ctx, slice.data(), n, ends, &w) == HSRANS_OK && w->n_groups != 0 && w->groups_lean && w->part_units.size() == parts &&
+      if (n != 0 && dplan_create(ctx, slice.data(), n, &ends, &w) == HSRANS_OK && w->n_groups != 0 && w->groups_lean && w->part_units.size() == parts &&
           hipMalloc((void **)&s->d_words, (size_t)(parts + 1) * kWordStride * 4) == hipSuccess && hipMemset(s->d_words, 0, (size_t)(parts + 1) * kWordStride * 4) == hipSuccess)
         s->whole = w;
       else

@@ -1,4 +1,4 @@
-// hsrans_internal.h — what the translation units behind the C ABI (hsrans_capi*.cpp, hsrans_batch.cpp, hsrans_comm.cpp) share: the
+// hsrans_internal.h — what the translation units behind the C ABI (hsrans_capi*.cpp, hsrans_dplan.cpp, hsrans_batch.cpp, hsrans_comm.cpp) share: the
 // context and device-plan objects behind the opaque handles of include/hsrans_hip.h, and the few helpers that work on them.
 // Not installed; nothing outside csrc/ includes it.
 #ifndef HSRANS_INTERNAL_H
@@ -70,41 +70,30 @@ inline uint64_t next_dplan_uid()
   return n.fetch_add(1, std::memory_order_relaxed);
 }
 
-struct hsrans_dplan
+// What a fill derives from the plan it launches.  Every (re)fill resets all of it in one assignment (dplan_fill), so no field here can carry
+// one plan's launch state into the next.
+struct DplanState
 {
-  hsrans_ctx *ctx = nullptr;
-  uint64_t uid = next_dplan_uid();
+  uint64_t uid = next_dplan_uid(); // (a refill is another plan)
   PlanHeader hdr{};
-  uint8_t *d_plan = nullptr;
-  size_t d_plan_cap = 0;
-  uint32_t *d_status = nullptr;
   size_t plan_bytes = 0;
-  // dplan_fill puts status word, ticket counters, plan blob, host-built table and group list into ONE device allocation (a
-  // device plan used to cost up to five hipMalloc calls and three synchronisations: 3.2 ms for a 2.5 MB index): the pointers
-  // below then point into d_arena and are not freed one by one.  Plans written on the device (K2, the GPU encoder) still own theirs.
-  uint8_t *d_arena = nullptr;
-  size_t d_arena_cap = 0, arena_used = 0;
-  uint64_t *d_stamps = nullptr; // diagnostics (HSRANS_DEBUG_STAMPS=1)
-  uint64_t *d_finish = nullptr; // hsrans_ctx_calibrate: per-wave finish times of the plan's launches (owned by the calibration)
+  // regions of d_arena (dplan_arena): not freed one by one
+  uint8_t *d_plan = nullptr;
+  uint32_t *d_status = nullptr;
   unsigned long long *d_counters = nullptr; // uniform persistent launches: kCounterSets sets of monotonic queue heads
-  std::atomic<uint32_t> epoch{0};           // launches so far: launch k uses counter set k % kCounterSets
   uint8_t *d_table = nullptr;               // host-built decode table (plans that carry their histogram)
-  size_t d_table_cap = 0;
   uint8_t *d_groups = nullptr;              // grouped launches (block_/mt_ plans with checkpoints)
-  size_t d_groups_cap = 0;
   uint32_t n_groups = 0;
   bool groups_lean = false; // 64 states, every group a mergeable run or fills only
   uint32_t spread_min_block = 0; // plans k_decode_spread can take (single-piece chains, mergeable / fill groups): the fewest chains of a coded block that is not the last; else 0
   PersistentArgs pa{};
   SingleArgs single{};
-  LaunchInfo info{};
   // what the plan's chains touch, recorded by dplan_fill: the lowest stream byte any of them reads (its own words, its
   // histogram / header, the shared histogram when the plan carries no copy of it) and the output bytes they write
   uint64_t body_lo = 0, out_lo = 0, out_hi = 0;
-  // a rank's sub-runs decoded by ONE launch of this plan (hsrans_comm.cpp): part k = chains [part_ends[k - 1], part_ends[k]) — set before
-  // dplan_fill, which then tags every group with the parts it overlaps (Group::flags, kGroupPartShift) and counts them: part_units[k];
-  // part_cum[k] = units counted into part k by all launches so far (the device's counters are never reset: launch_decode, PartPlan)
-  std::vector<uint32_t> part_ends, part_units, part_cum;
+  // part_units[k]: the groups that count into sub-run k of part_ends (below); part_cum[k] = units counted into part k by all launches so far
+  // (the device's counters are never reset: launch_decode, PartPlan)
+  std::vector<uint32_t> part_units, part_cum;
   // k_decode_dealt (kernels_dealt.h): the plan's blocks as chain ranges — block k = chains [block_begin[k], block_begin[k + 1]) — kept where the
   // plan is a lean grouped one of coded blocks only (no single-symbol blocks); empty otherwise.  `dealt` = the shares for `dealt_weights`
   // (dealt_state 1: valid, -1: the plan does not suit the launch with these weights, 0: not dealt yet); re-dealt when a calibration changes the weights.
@@ -116,8 +105,53 @@ struct hsrans_dplan
   uint32_t dealt_weights[8] = {};
   int dealt_state = 0;
 };
-// fills d->block_begin from the device plan's group list (plans written on the device: the GPU encoder's, an indexing decode's); synchronises `s`
-void dplan_blocks_from_device_groups(hsrans_dplan *d, hipStream_t s);
+
+// A device plan.  Every one comes from dplan_new and holds its device memory in ONE allocation, d_arena (a device plan used to cost up to
+// five hipMalloc calls and three synchronisations: 3.2 ms for a 2.5 MB index); hsrans_dplan_destroy frees d_stamps and d_arena.
+struct hsrans_dplan : DplanState
+{
+  hsrans_ctx *ctx = nullptr;
+  uint8_t *d_arena = nullptr;
+  size_t d_arena_cap = 0;
+  uint64_t *d_stamps = nullptr; // diagnostics (HSRANS_DEBUG_STAMPS=1)
+  uint64_t *d_finish = nullptr; // hsrans_ctx_calibrate: per-wave finish times of the plan's launches (owned by the calibration)
+  std::atomic<uint32_t> epoch{0}; // launches so far: launch k uses counter set k % kCounterSets
+  // a rank's sub-runs decoded by ONE launch of this plan (hsrans_comm.cpp): part k = chains [part_ends[k - 1], part_ends[k]) — set before
+  // dplan_fill, which then tags every group with the parts it overlaps (Group::flags, kGroupPartShift) and counts them: part_units
+  std::vector<uint32_t> part_ends;
+  LaunchInfo info{};
+};
+
+// a fresh device plan of ctx (with the stamps buffer when HSRANS_DEBUG_STAMPS is set); null when out of memory
+hsrans_dplan *dplan_new(hsrans_ctx *ctx);
+// hsrans_dplan_create; part_ends (may be null): the chains [part_ends[k - 1], part_ends[k]) are the sub-runs of a sharded decode
+// (hsrans_comm.cpp), and the group list is tagged with them.  *out_dplan's part_units is empty when the plan is of a kind no one-launch kernel takes.
+int dplan_create(hsrans_ctx *ctx, const uint8_t *plan, size_t plan_size, const std::vector<uint32_t> *part_ends, hsrans_dplan **out_dplan);
+
+// The regions of a plan's device memory, in this order, each 256-byte aligned: status word, ticket counters, plan blob, host-built table,
+// group list, caller scratch.  An empty region's pointer is null (the status word and the plan are always there).
+enum DplanZero { kZeroThroughCounters, kZeroThroughPlan, kZeroAll };
+struct DplanRegions
+{
+  bool counters = false;
+  size_t plan = 0, table = 0, groups = 0, scratch = 0; // bytes
+  DplanZero zero = kZeroThroughCounters; // what starts at zero (one memset on the caller's stream)
+};
+// lays them out in d_arena (kept and grown across refills), sets the d_* pointers and epoch, queues the memset; *scratch: the caller's region
+int dplan_arena(hsrans_dplan *d, const DplanRegions &r, hipStream_t s, uint8_t **scratch = nullptr);
+// takes over a plan the device wrote into d's arena: its header, its group count (0: ungrouped, groups and counters are dropped) and the fewest
+// chains of a coded block that is not the last; fills block_begin from the group list (synchronises `s` when there is one)
+void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_groups, uint64_t spread_min_block, hipStream_t s);
+// the header of an mt_ plan written on the device (the GPU encoder's, K2's): n_chains single-piece chains
+PlanHeader mt_plan_header(uint32_t states, uint32_t bits, uint64_t decoded_len, uint64_t stream_len, uint32_t n_chains);
+
+// Few, large blocks would leave workgroup slots empty (one workgroup per group): while a plan has fewer groups than kGroupPartsPerCU per CU,
+// each is cut into up to this many parts of >= kGroupPartChains chains (hsrans_kernels.h group_parts_of: the rule and what was measured); 1 = no cut
+inline uint32_t group_parts_max(const DeviceGeom &geom, size_t n_groups)
+{
+  const size_t want = (size_t)kGroupPartsPerCU * geom.num_cus;
+  return n_groups != 0 && n_groups < want ? (uint32_t)((want + n_groups - 1) / n_groups) : 1;
+}
 
 constexpr size_t kStampWaves = 16384;
 
@@ -200,7 +234,7 @@ struct hsrans_batch
   std::vector<uint32_t> order_run; // per member: the slot order its chains were dealt with (diagnostics)
 };
 
-// (Re)fills a device plan from a validated host plan blob; one launch of a filled device plan (hsrans_capi.cpp)
+// (Re)fills a device plan from a validated host plan blob; one launch of a filled device plan (hsrans_dplan.cpp)
 int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_size, const PlanHeader &h, hipStream_t s);
 int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity, hipStream_t s, uint64_t stream_lo = 0,
                  const PartArgs *part_words = nullptr);
@@ -209,8 +243,6 @@ int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stream_length, vo
 // part_words: a sharded decode's sub-runs in this one launch (completion words, sequence number; hsrans_comm.cpp)
 int dplan_launch_ranges(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_window, size_t window_offset, size_t window_length, void *d_out, size_t out_offset,
                         size_t out_length, void *hip_stream, const PartArgs *part_words);
-
-int dplan_create_with_parts(hsrans_ctx *ctx, const uint8_t *plan, size_t plan_size, const std::vector<uint32_t> &part_ends, hsrans_dplan **out_dplan);
 
 // a page-locked, device-mapped host range: the address the GPU reaches it at, else null (hsrans_capi.cpp)
 uint8_t *device_view_of_host(const void *ptr, size_t bytes);

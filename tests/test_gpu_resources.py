@@ -27,6 +27,7 @@ def test_no_device_memory_leak_over_create_destroy_cycles(gpu_ctx):
         assert gpu_ctx.status(dp) == 0
         dp.close()
         dp = gpu_ctx.make_device_plan_from_stream(H.MT, 64, 11, d_enc, m, d.size)
+        gpu_ctx.decode_device_indexing(dp, d_enc, d_out, 32, stream_length=m).close()
         dp.close()
         gpu_ctx.index_build(H.RAW, 64, 11, s, 64)
         r, _ = gpu_ctx.decode_host(H.RAW, 64, 11, s, d.size, plan=plan)

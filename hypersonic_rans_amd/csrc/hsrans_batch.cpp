@@ -138,7 +138,7 @@ try
       // finishes evenly when what is handed out last is short
       std::stable_sort(all.begin(), all.end(), [](const Group &x, const Group &y) { return x.count > y.count; });
       G.n_groups = (uint32_t)all.size();
-      G.shape = batch_grouped_shape(ctx->geom, bits, G.n_groups, chains);
+      G.shape = batch_grouped_shape(b->tuning, ctx->geom, bits, G.n_groups, chains);
       const size_t counter_bytes = (size_t)kCounterSets * kDynQueueStride * 8;
       auto up256g = [](size_t v) { return (v + 255) & ~(size_t)255; };
       const size_t bytes = up256g(gm.size() * sizeof(GroupMember)) + up256g(all.size() * sizeof(Group)) + counter_bytes;
@@ -224,7 +224,7 @@ try
     uint64_t launch_groups = 0;
     for (const BatchDealMember &dm : deal_in)
       launch_groups += dm.total_groups;
-    L.shape = batch_direct_shape(ctx->geom, max_bits, launch_groups, launch_states);
+    L.shape = batch_direct_shape(b->tuning, ctx->geom, max_bits, launch_groups, launch_states);
     const BatchDeal deal = batch_deal(deal_in, L.shape.grid, L.shape.waves, L.shape.weights, L.shape.kind == kBatchDirect ? 1 : 2);
     // a wave reads its run through one 32-bit window of the stream (run_direct_span: win_open)
     for (const BatchSlot &s : deal.slots)
@@ -283,7 +283,7 @@ try
       off += host_blobs[l].size();
     }
   }
-  if (getenv("HSRANS_BATCH_STAMPS") != nullptr && !b->direct.empty())
+  if (b->tuning.batch_stamps && !b->direct.empty())
   {
     b->finish_slots = b->direct[0].shape.grid * b->direct[0].shape.waves;
     if (hipMalloc((void **)&b->d_finish, ((size_t)b->finish_slots + 1) * 8) != hipSuccess)
@@ -416,6 +416,7 @@ try
   if ((states != 64 && states != 32) || bits < 10 || bits > (states == 64 ? 15u : 12u) || decoded_sizes == nullptr || groups_out == nullptr || count == 0 || count > kBatchMax || member >= count)
     return 0;
   const DeviceGeom dg = ctx ? ctx->geom : default_geom();
+  const Tuning tn = ctx ? ctx->tuning : read_tuning();
   std::vector<uint64_t> totals(count);
   uint64_t all = 0;
   for (uint32_t k = 0; k < count; k++)
@@ -423,7 +424,7 @@ try
     totals[k] = decoded_sizes[k] + 1 >= (size_t)states ? (decoded_sizes[k] - states + 1 + states - 1) / states : 0; // whole groups, as hsrans_index_boundaries
     all += totals[k];
   }
-  const BatchShape shape = batch_direct_shape(dg, bits, all, (uint32_t)states);
+  const BatchShape shape = batch_direct_shape(tn, dg, bits, all, (uint32_t)states);
   // (32 states: two chains per wave slot, one per wave half — run_batch_pair)
   const size_t chains = batch_boundaries(totals.data(), count, member, shape.grid, shape.waves, shape.weights, groups_out, capacity, shape.kind == kBatchDirect ? 1 : 2);
   return chains > 1 ? chains - 1 : 0;
@@ -454,7 +455,7 @@ try
   uint32_t w8[8];
   if (weights == nullptr)
   {
-    const BatchShape shape = batch_direct_shape(default_geom(), 11);
+    const BatchShape shape = batch_direct_shape(read_tuning(), default_geom(), 11);
     memcpy(w8, shape.weights, sizeof(w8));
   }
   else

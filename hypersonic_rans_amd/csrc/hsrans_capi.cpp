@@ -193,13 +193,12 @@ int hsrans_ctx_create(int device, hsrans_ctx **out_ctx)
   }
   // HSRANS_CALIBRATE=1: fit the one-chain-per-wave index's class lengths to this device right away (~0.5 s; for callers that cannot
   // call hsrans_ctx_calibrate themselves, e.g. the drop-in entries, which create their one context on first use)
-  if (const char *e = getenv("HSRANS_CALIBRATE"))
-    if (atoi(e) != 0)
-    {
-      const int crc = hsrans_ctx_calibrate(ctx, 11, 0, nullptr); // (a failed fit leaves the compiled-in lengths in place: the context is still usable)
-      if (crc != HSRANS_OK)
-        fprintf(stderr, "hsrans: HSRANS_CALIBRATE=1: hsrans_ctx_calibrate failed (code %d); the compiled-in class lengths stay in use\n", crc);
-    }
+  if (ctx->tuning.calibrate)
+  {
+    const int crc = hsrans_ctx_calibrate(ctx, 11, 0, nullptr); // (a failed fit leaves the compiled-in lengths in place: the context is still usable)
+    if (crc != HSRANS_OK)
+      fprintf(stderr, "hsrans: HSRANS_CALIBRATE=1: hsrans_ctx_calibrate failed (code %d); the compiled-in class lengths stay in use\n", crc);
+  }
   *out_ctx = ctx;
   return HSRANS_OK;
 }
@@ -281,7 +280,7 @@ try
   // missing index once: the first call's decode records checkpoints (hsrans_decode_device_indexing) and the plan it leaves is kept
   // in the context; later calls on the same bytes launch it.  "The same bytes" is checked on ALL of them: the stream is uploaded
   // anyway, a wide kernel fingerprints it there, and the decode that ran beside it only counts when the fingerprint matches.
-  const bool cacheable = plan == nullptr && (container == HSRANS_MT || container == HSRANS_RAW) && in_length >= 16 && getenv("HSRANS_HOST_INDEX_CACHE_OFF") == nullptr;
+  const bool cacheable = plan == nullptr && (container == HSRANS_MT || container == HSRANS_RAW) && in_length >= 16 && !ctx->tuning.host_index_cache_off;
   const uint64_t codec_key = (uint64_t)container | ((uint64_t)states << 8) | ((uint64_t)bits << 16) | (1ull << 32);
   if (cacheable)
   {
@@ -375,9 +374,7 @@ try
                       hipMemcpyAsync(&sum, ctx->d_enc_meta, 8, hipMemcpyDeviceToHost, s) == hipSuccess;
     // HSRANS_HIP_STRICT=1: nothing of a `*_decode_hip_N` call runs on a host core — the raw stream's checkpoints are recorded by the one
     // wavefront that decodes it (hsrans_decode_device_indexing: ~125 ms for 100 MB, once) instead of by the host SIMD decoder's pass (~35 ms)
-    const char *e_strict = getenv("HSRANS_HIP_STRICT");
-    const bool strict = e_strict != nullptr && e_strict[0] != '\0' && e_strict[0] != '0';
-    if (have_index && container == HSRANS_RAW && !strict)
+    if (have_index && container == HSRANS_RAW && !ctx->tuning.hip_strict)
     try
     {
       // a raw stream is ONE chain: the pass that records its checkpoints is the host SIMD decoder's (2-4 GB/s on one core, while the
@@ -548,7 +545,8 @@ try
   DealtTable dt{};
   uint32_t w8[8];
   const DeviceGeom dg = ctx ? ctx->geom : default_geom();
-  const bool ok = deal_shares(dg, block_begin, n_blocks, n_chains, total_groups, bits, &dt, w8);
+  const Tuning tn = ctx ? ctx->tuning : read_tuning();
+  const bool ok = deal_shares(tn, dg, block_begin, n_blocks, n_chains, total_groups, bits, &dt, w8);
   memcpy(begin_out, dt.begin, sizeof(dt.begin));
   memcpy(split_out, dt.split, sizeof(dt.split));
   return ok ? 1 : 0;
@@ -581,9 +579,10 @@ size_t hsrans_index_boundaries(const hsrans_ctx *ctx, int states, uint32_t bits,
   if ((states != 32 && states != 64) || bits < 10 || bits > 15 || groups_out == nullptr)
     return 0;
   const DeviceGeom dg = ctx ? ctx->geom : default_geom();
+  const Tuning tn = ctx ? ctx->tuning : read_tuning();
   const uint64_t S = (uint64_t)states;
   const uint64_t T = decoded_size + 1 >= S ? (decoded_size - S + 1 + S - 1) / S : 0; // whole groups (rANS32x64_16w.cpp:223)
-  const size_t chains = direct_boundaries(dg, (uint32_t)states, bits, T, groups_out, capacity);
+  const size_t chains = direct_boundaries(tn, dg, (uint32_t)states, bits, T, groups_out, capacity);
   return chains > 1 ? chains - 1 : 0;
 }
 

@@ -151,8 +151,8 @@ static int calibrate_impl(hsrans_ctx *ctx, uint32_t bits, uint32_t iterations, u
     {
       PlanHeader h{};
       h.states = 64, h.bits = bits, h.shared_hist = 1, h.n_chains = 1u << 30;
-      const TableChoice tc = choose_table(bits, 64, true);
-      const LaunchShape L = launch_shape(h, ctx->geom, true, tc.mode, 0, false, true, tc.dual);
+      const TableChoice tc = choose_table(ctx->tuning, bits, 64, true);
+      const LaunchShape L = launch_shape(ctx->tuning, h, ctx->geom, true, tc.mode, 0, false, true, tc.dual);
       if (L.dual || L.waves != 16 || L.grid <= ctx->geom.num_cus) // not the launch shape the classes are defined for: nothing to fit
       {
         rc = HSRANS_E_ARG;
@@ -172,11 +172,11 @@ static int calibrate_impl(hsrans_ctx *ctx, uint32_t bits, uint32_t iterations, u
       size_t chains;
       BatchShape bshape{};
       if (copies == 1)
-        chains = direct_boundaries(ctx->geom, 64, bits, T, groups.data(), groups.size());
+        chains = direct_boundaries(ctx->tuning, ctx->geom, 64, bits, T, groups.data(), groups.size());
       else
       {
         // `copies` members of this one stream in one launch: every member indexed for its share of the wave slots (batch_boundaries)
-        bshape = batch_direct_shape(ctx->geom, bits, 0);
+        bshape = batch_direct_shape(ctx->tuning, ctx->geom, bits, 0);
         std::vector<uint64_t> totals(copies, T);
         chains = batch_boundaries(totals.data(), copies, 0, bshape.grid, bshape.waves, cur_w, groups.data(), groups.size());
       }

@@ -224,7 +224,7 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
     (void)hipGetLastError();
     return 0;
   }
-  if (getenv("HSRANS_DEBUG_STAMPS"))
+  if (ctx->tuning.debug_stamps)
   {
     uint64_t st[4] = {};
     if (hipMemcpy(st, ep.stamps, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess)
@@ -299,7 +299,7 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
   std::lock_guard<std::mutex> guard(ctx->lock);
   if (hipSetDevice(ctx->device) != hipSuccess)
     return 0;
-  const bool stamps = getenv("HSRANS_DEBUG_STAMPS") != nullptr;
+  const bool stamps = ctx->tuning.debug_stamps;
   const size_t nb = ep.n_blocks;
   const bool wide_hist = true; // (false: the coding wavefront counts its own block, as in rounds 1-3: 29.5 us per 64 KiB block — one wavefront's LDS atomics — against 23.5 us for the whole input by K_hist; the knob is gone)
   const size_t meta_bytes = (nb * 2 + kEncResultWords) * 8 + nb * 2 * 4 + (stamps ? nb * 4 * 8 : 0) + 64 + (wide_hist ? nb * 1024 + 16 : 0);
@@ -478,7 +478,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
   if (hipSetDevice(ctx->device) != hipSuccess)
     return 0;
   hipStream_t s = (hipStream_t)hip_stream;
-  const bool stamps = getenv("HSRANS_DEBUG_STAMPS") != nullptr;
+  const bool stamps = ctx->tuning.debug_stamps;
 
   // ---- a./b. unit summaries on the device, the block walk (the host encoder's) on the host ----
   std::vector<BlockSpan> spans;

@@ -32,6 +32,7 @@ extern "C"
 struct hsrans_hpipe
 {
   hsrans_ctx *ctx = nullptr;
+  Tuning tuning = read_tuning(); // (at hsrans_hpipe_create: its decodes' output leg and trace)
   PlanHeader hdr{};
   struct Slice
   {
@@ -183,13 +184,13 @@ size_t hsrans_hpipe_decode(hsrans_hpipe *p, const uint8_t *in, size_t in_length,
   // made every comparison before that a comparison of hardware-queue assignments): 2^30 bytes 47.4 GB/s either way; 100 MB
   // 36.2-38.8 k MiB/s staged against 29.3-33.8 k direct (the 32-state kernels' 128-byte rows make poor PCIe writes), 27.4-30.9 k
   // for upload, decode, download one after the other.
-  uint8_t *out_view = getenv("HSRANS_HPIPE_DIRECT") != nullptr && ((uintptr_t)out & 3) == 0 ? device_view_of_host(out, (size_t)p->hdr.decoded_len) : nullptr;
+  uint8_t *out_view = p->tuning.hpipe_direct && ((uintptr_t)out & 3) == 0 ? device_view_of_host(out, (size_t)p->hdr.decoded_len) : nullptr;
   const bool direct = out_view != nullptr;
   if (!direct && p->d_out == nullptr && hipMalloc((void **)&p->d_out, p->hdr.decoded_len + 16) != hipSuccess)
     return 0;
   bool ok = true;
   // HSRANS_HPIPE_TRACE=1: per-slice timeline on stderr (timing events around every leg; diagnostics only)
-  const bool trace = getenv("HSRANS_HPIPE_TRACE") != nullptr;
+  const bool trace = p->tuning.hpipe_trace;
   std::vector<hipEvent_t> tev;
   auto mark = [&](hipStream_t st) {
     if (!trace)

@@ -165,7 +165,7 @@ static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint3
     kp.walk_max_blocks = (uint32_t)(max_blocks > 0xFFFFFFFFull ? 0xFFFFFFFFull : max_blocks);
     PlanHeader hl = h;
     hl.shared_hist = 0; // private tables: every chain of the pass builds its own (raw has one chain, mt_ one per block)
-    if (launch_decode(kp, hl, ctx->geom, s, nullptr) != hipSuccess)
+    if (launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr) != hipSuccess)
       break;
     if (hipMemcpyAsync(ck_states.data(), d_ck_states, n_ck * S * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(ck_words.data(), d_ck_words, n_ck * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -339,7 +339,7 @@ try
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const bool trace = getenv("HSRANS_INDEXING_TRACE") != nullptr;
+  const bool trace = ctx->tuning.indexing_trace;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto t0 = now();
@@ -348,7 +348,7 @@ try
   // mt_ streams (one single-piece chain per block, histograms in the stream): the indexed plan is assembled ON THE DEVICE behind the
   // recording pass — one allocation, three launches, one synchronisation; nothing but two words comes back to the host
   // (HSRANS_INDEX_ASSEMBLE_ON_HOST=1: round 3's path — checkpoints down, blob built by one core, blob up — still what raw plans take)
-  if (h.container == HSRANS_MT && (h.flags & (kPlanWalk | kPlanHasHist | kPlanMergeable)) == 0 && getenv("HSRANS_INDEX_ASSEMBLE_ON_HOST") == nullptr)
+  if (h.container == HSRANS_MT && (h.flags & (kPlanWalk | kPlanHasHist | kPlanMergeable)) == 0 && !ctx->tuning.index_assemble_on_host)
   {
     std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer belongs to the context)
     if (!have_lock)
@@ -407,7 +407,7 @@ try
     uint32_t status = 0xFFFFFFFF;
     uint64_t counted[4] = {}; // chains in all, blocks with a histogram, the (one) histogram's offset, fewest chains of a coded block but the last
     const uint64_t &total = counted[0];
-    const bool ok = launch_decode(kp, hl, ctx->geom, s, nullptr) == hipSuccess &&
+    const bool ok = launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr) == hipSuccess &&
                     launch_index_assemble(ia, s) == hipSuccess && hipMemcpyAsync(counted, d_result, sizeof(counted), hipMemcpyDeviceToHost, s) == hipSuccess &&
                     hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
     const bool synced = hipStreamSynchronize(s) == hipSuccess; // (nothing queued above may still be running when this returns, whatever failed)
@@ -470,7 +470,7 @@ try
     PlanHeader hl = h;
     hl.shared_hist = 0; // private tables, as in hsrans_index_build's pass
     uint32_t status = 0xFFFFFFFF;
-    if (launch_decode(kp, hl, ctx->geom, s, nullptr) != hipSuccess ||
+    if (launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr) != hipSuccess ||
         hipMemcpyAsync(base, d->d_plan, d->plan_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(ck_states, d_ck_states, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(ck_words, d_ck_words, wd_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||

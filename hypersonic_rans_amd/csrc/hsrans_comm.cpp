@@ -82,6 +82,7 @@ struct hsrans_sharded
 {
   hsrans_ctx *ctx = nullptr;
   hsrans_comm *comm = nullptr;
+  Tuning tuning = read_tuning(); // (at hsrans_sharded_create)
   uint32_t world = 1, rank = 0, parts = 1;
   int root = -1;
   std::vector<hsrans_shard> shards; // [world * parts]
@@ -247,7 +248,7 @@ static int sharded_create_impl(hsrans_ctx *ctx, hsrans_comm *comm, int rank, int
   std::vector<uint8_t> slice(plan_size + 1024);
   // the sub-runs as one launch: block_/mt_ plans with checkpoints (the grouped / spread kernels count their units into the sub-runs), where the
   // device can make a stream wait for a word in memory; HSRANS_SHARD_ONE_LAUNCH=0 keeps a launch per sub-run (comparison: tools/shard_projection.py)
-  if (rc == HSRANS_OK && parts > 1 && parts <= kMaxLaunchParts && !(getenv("HSRANS_SHARD_ONE_LAUNCH") && atoi(getenv("HSRANS_SHARD_ONE_LAUNCH")) == 0))
+  if (rc == HSRANS_OK && parts > 1 && parts <= kMaxLaunchParts && s->tuning.shard_one_launch)
   {
     int can_wait = 0;
     (void)hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, ctx->device);

@@ -102,14 +102,14 @@ extern "C++" int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_si
     if (h.flags & kPlanHasHist)
     {
       const uint16_t *counts = (const uint16_t *)(plan + plan_hist_off(h.n_chains, h.n_pieces, h.states));
-      TableChoice tc = choose_table(h.bits, h.states, h.interval == 0);
+      TableChoice tc = choose_table(d->tuning, h.bits, h.states, h.interval == 0);
       if (tc.dual)
       {
         // k_decode_dual reads the two neighbouring chains of a wave through ONE 32-bit window of the stream: a pair whose words
         // could span 4 GiB (a multi-GiB stream indexed for very few chains, e.g. by hsrans_plan_thin) goes one chain per wave
         for (uint32_t a = 0; a < h.n_chains && tc.dual; a += 2)
           if ((a + 2 < h.n_chains ? pc[a + 2].words_off : h.stream_len) - pc[a].words_off >= 0xFFFF0000ull)
-            tc = choose_table(h.bits, h.states, false);
+            tc = choose_table(d->tuning, h.bits, h.states, false);
       }
       uint32_t mode = tc.mode;
       if (mode == 3 || mode == 5)
@@ -333,7 +333,7 @@ static void dplan_blocks_from_device_groups(hsrans_dplan *d, hipStream_t s)
         continue;
       if ((g.flags & kGroupFill) || !(g.flags & kGroupMergeable) || g.begin != next || g.piece0 != g.begin)
       {
-        if (getenv("HSRANS_DEALT_TRACE"))
+        if (d->tuning.dealt_trace)
           fprintf(stderr, "hsrans dealt: group %zu of %zu: flags %x begin %u count %u piece0 %u, expected begin %u\n", k, groups.size(), g.flags, g.begin, g.count, g.piece0, next);
         return;
       }
@@ -386,6 +386,7 @@ extern "C++" int dplan_arena(hsrans_dplan *d, const DplanRegions &r, hipStream_t
 
 extern "C++" void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_groups, uint64_t spread_min_block, hipStream_t s)
 {
+  d->tuning = read_tuning(); // (as a fill takes them)
   d->hdr = h;
   d->plan_bytes = (size_t)plan_size(h.n_chains, h.n_pieces, h.states, h.flags);
   d->out_hi = h.decoded_len; // a plan written on the device covers the whole stream and the whole output
@@ -416,7 +417,7 @@ extern "C++" hsrans_dplan *dplan_new(hsrans_ctx *ctx)
   if (d == nullptr)
     return nullptr;
   d->ctx = ctx;
-  if (getenv("HSRANS_DEBUG_STAMPS") && hipMalloc((void **)&d->d_stamps, kStampWaves * 8 * 8) == hipSuccess)
+  if (d->tuning.debug_stamps && hipMalloc((void **)&d->d_stamps, kStampWaves * 8 * 8) == hipSuccess)
     (void)hipMemset(d->d_stamps, 0, kStampWaves * 8 * 8);
   return d;
 }
@@ -446,43 +447,28 @@ extern "C++" int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stre
     kp.n_groups = d->n_groups;
     kp.groups_lean = d->groups_lean ? 1 : 0;
     kp.spread = d->groups_lean ? d->spread_min_block : 0;
-    // (measured at 2^30 bytes, two runs each on one box: 0 -> 0.447-0.450 ms, 300 -> 0.440, 500 -> 0.440-0.445, 700 -> 0.447-0.451, 1000 -> 0.452-0.455)
-    kp.group_prio = getenv("HSRANS_GROUP_PRIO") != nullptr ? (uint32_t)atoi(getenv("HSRANS_GROUP_PRIO")) : 350;
-    // HSRANS_GROUP_PRIO_CLASS: ten per-mille values, see KParams::group_prio_class (tuning; tools/group_prio_probe.py)
-    kp.group_prio_class[9] = 0xFFFF;
-    if (const char *e = getenv("HSRANS_GROUP_PRIO_CLASS"))
-    {
-      uint32_t v[10], n = 0;
-      for (const char *p = e; n < 10 && *p; n++)
-      {
-        v[n] = (uint32_t)strtoul(p, (char **)&p, 10);
-        if (*p == ',')
-          p++;
-      }
-      if (n == 10)
-        for (uint32_t k = 0; k < 10; k++)
-          kp.group_prio_class[k] = (uint16_t)(v[k] > 1000 ? 1000 : v[k]);
-    }
+    kp.group_prio = d->tuning.group_prio;
+    memcpy(kp.group_prio_class, d->tuning.group_prio_class, sizeof(kp.group_prio_class));
     // (requesting a round's records and first chunks before its table build: measured, no gain — the other workgroups of the CU
     // fill the gap either way — so off unless asked for)
     // dynamic group order: this launch's own ticket counter (the counter sets of the persistent launches, one head of each used)
-    if (d->d_counters != nullptr && getenv("HSRANS_GROUP_STATIC") == nullptr)
+    if (d->d_counters != nullptr && !d->tuning.group_static)
       kp.group_tickets = d->d_counters + (size_t)(d->epoch.fetch_add(1, std::memory_order_relaxed) % kCounterSets) * kDynQueues * kDynQueueStride;
   }
   // lean grouped plans of coded blocks: the host-dealt one-round launch where the plan suits it (dealt once per weight set)
   const DealtTable *dealt = nullptr;
   if (d->n_groups && d->groups_lean && d->block_begin.size() >= 2 && (d->hdr.bits <= 11 || d->hdr.bits == 13 || d->hdr.bits == 14) && d->hdr.states == 64 &&
-      !(d->hdr.bits >= 13 && getenv("HSRANS_DEALT_WIDE") != nullptr && atoi(getenv("HSRANS_DEALT_WIDE")) == 0)) // (HSRANS_DEALT_WIDE=0: 13 / 14 bits keep the grouped launch: comparison)
+      (d->hdr.bits <= 11 || d->tuning.dealt_wide))
   {
     uint32_t w8[8];
     const uint64_t total_groups = (d->out_hi - d->out_lo) / 64; // (what THIS plan's chains decode: a rank's slice of a sharded stream, not the stream)
-    dealt_weights_now(d->ctx->geom, total_groups / ((uint64_t)spread_grid(d->ctx->geom) * 16), d->hdr.bits, w8);
+    dealt_weights_now(d->tuning, d->ctx->geom, total_groups / ((uint64_t)spread_grid(d->ctx->geom) * 16), d->hdr.bits, w8);
     if (d->dealt_state == 0 || memcmp(w8, d->dealt_weights, sizeof(w8)) != 0)
-      d->dealt_state = deal_shares(d->ctx->geom, d->block_begin.data(), (uint32_t)d->block_begin.size() - 1, d->hdr.n_chains, total_groups, d->hdr.bits, &d->dealt, d->dealt_weights) ? 1 : -1;
+      d->dealt_state = deal_shares(d->tuning, d->ctx->geom, d->block_begin.data(), (uint32_t)d->block_begin.size() - 1, d->hdr.n_chains, total_groups, d->hdr.bits, &d->dealt, d->dealt_weights) ? 1 : -1;
     if (d->dealt_state == 1)
       dealt = &d->dealt;
   }
-  if (getenv("HSRANS_DEALT_TRACE"))
+  if (d->tuning.dealt_trace)
     fprintf(stderr, "hsrans dealt: groups %u lean %d blocks %zu bits %u chains %u state %d\n", d->n_groups, (int)d->groups_lean, d->block_begin.size(), d->hdr.bits, d->hdr.n_chains, d->dealt_state);
   if (part_words != nullptr)
   {
@@ -491,9 +477,9 @@ extern "C++" int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stre
       return HSRANS_E_ARG;
     kp.parts = *part_words;
     PartPlan pp{(uint32_t)d->part_ends.size(), d->part_ends.data(), d->part_units.data(), d->part_cum.data()};
-    return launch_decode(kp, d->hdr, d->ctx->geom, s, &d->info, &pp, dealt, d->dealt_weights) == hipSuccess ? HSRANS_OK : HSRANS_E_HIP;
+    return launch_decode(d->tuning, kp, d->hdr, d->ctx->geom, s, &d->info, &pp, dealt, d->dealt_weights) == hipSuccess ? HSRANS_OK : HSRANS_E_HIP;
   }
-  return launch_decode(kp, d->hdr, d->ctx->geom, s, &d->info, nullptr, dealt, d->dealt_weights) == hipSuccess ? HSRANS_OK : HSRANS_E_HIP;
+  return launch_decode(d->tuning, kp, d->hdr, d->ctx->geom, s, &d->info, nullptr, dealt, d->dealt_weights) == hipSuccess ? HSRANS_OK : HSRANS_E_HIP;
 }
 
 extern "C++" int dplan_create(hsrans_ctx *ctx, const uint8_t *plan, size_t plan_size, const std::vector<uint32_t> *part_ends, hsrans_dplan **out_dplan)

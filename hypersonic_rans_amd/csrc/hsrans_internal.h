@@ -25,6 +25,7 @@ struct hsrans_ctx
   int device = 0;
   char name[256] = {};
   DeviceGeom geom{};     // CU count / LDS of THIS context's device (nothing about a device is process-global)
+  Tuning tuning = read_tuning(); // the switches as they were at hsrans_ctx_create: what the context's calls that make no object of their own use
   bool enc_prepared = false;
   bool enc_raw_prepared = false;
   bool enc_chain_prepared = false;
@@ -75,6 +76,7 @@ inline uint64_t next_dplan_uid()
 struct DplanState
 {
   uint64_t uid = next_dplan_uid(); // (a refill is another plan)
+  Tuning tuning = read_tuning();   // the switches as they were at this fill or dplan_adopt: what the plan's launches use
   PlanHeader hdr{};
   size_t plan_bytes = 0;
   // regions of d_arena (dplan_arena): not freed one by one
@@ -122,7 +124,7 @@ struct hsrans_dplan : DplanState
   LaunchInfo info{};
 };
 
-// a fresh device plan of ctx (with the stamps buffer when HSRANS_DEBUG_STAMPS is set); null when out of memory
+// a fresh device plan of ctx (with the stamps buffer when HSRANS_DEBUG_STAMPS is set: Tuning::debug_stamps); null when out of memory
 hsrans_dplan *dplan_new(hsrans_ctx *ctx);
 // hsrans_dplan_create; part_ends (may be null): the chains [part_ends[k - 1], part_ends[k]) are the sub-runs of a sharded decode
 // (hsrans_comm.cpp), and the group list is tagged with them.  *out_dplan's part_units is empty when the plan is of a kind no one-launch kernel takes.
@@ -202,6 +204,7 @@ inline bool read_header(const uint8_t *plan, size_t size, PlanHeader *h)
 struct hsrans_batch
 {
   hsrans_ctx *ctx = nullptr;
+  Tuning tuning = read_tuning(); // (at hsrans_dplan_batch_create: the shapes and weights of its launches)
   std::vector<hsrans_dplan *> members;
   struct DirectLaunch
   {

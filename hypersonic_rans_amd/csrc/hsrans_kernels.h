@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "hsrans_plan.h"
+#include "hsrans_tuning.h"
 
 namespace hsrans
 {
@@ -219,7 +220,7 @@ struct BatchGroupShape
   uint32_t grid, waves, lds;
   uint16_t group_cum[2][17];
 };
-BatchGroupShape batch_grouped_shape(const struct DeviceGeom &dg, uint32_t bits, uint32_t n_groups, uint64_t n_chains);
+BatchGroupShape batch_grouped_shape(const Tuning &tn, const struct DeviceGeom &dg, uint32_t bits, uint32_t n_groups, uint64_t n_chains);
 hipError_t launch_batch_grouped(const BatchGroupParams &bp, const BatchGroupShape &shape, hipStream_t stream);
 
 constexpr uint32_t kBatchDirect = 0, kBatchPair = 1, kBatchDualPack = 2, kBatchDualRank = 3; // which kernel a shared launch runs
@@ -254,11 +255,11 @@ struct DeviceGeom
   uint32_t set_weights[4][8];
 };
 // the per-mille chain lengths of the 8 wave classes for a 64-state one-chain-per-wave launch whose runs average run_groups
-void direct_weights_for(const DeviceGeom &dg, uint64_t run_groups, uint32_t out[8]);
+void direct_weights_for(const Tuning &tn, const DeviceGeom &dg, uint64_t run_groups, uint32_t out[8]);
 
 // the launch all members of a batch of 64-state plans with 8-byte tables (bits <= 12) share; max_bits = the widest member
 // (total_groups: all members' groups together — the class weights follow the launch's mean run length; 0 = the default set)
-BatchShape batch_direct_shape(const DeviceGeom &dg, uint32_t max_bits, uint64_t total_groups = 0, uint32_t states = 64);
+BatchShape batch_direct_shape(const Tuning &tn, const DeviceGeom &dg, uint32_t max_bits, uint64_t total_groups = 0, uint32_t states = 64);
 hipError_t launch_batch_direct(const BatchParams &bp, const BatchShape &shape, hipStream_t stream);
 
 // a launch's shape as it follows from plan header + device (launch_shape)
@@ -310,8 +311,6 @@ __host__ __device__ inline uint32_t spread_share_begin(uint32_t n_chains, uint32
   const uint64_t cum = b <= fh ? (uint64_t)b * w1 : (uint64_t)fh * w1 + (uint64_t)(b - fh) * w2;
   return (uint32_t)((uint64_t)n_chains * cum / total);
 }
-// the longest share of a launch on this device (0 = the plan is too small or too large for the launch)
-uint32_t spread_longest_share(const DeviceGeom &dg, uint64_t n_chains);
 
 struct IndexArgs
 {
@@ -333,16 +332,15 @@ hipError_t launch_index_assemble(const IndexArgs &a, hipStream_t stream);
 hipError_t launch_stream_checksum(const uint8_t *d_stream, uint64_t stream_len, uint64_t *d_sum, hipStream_t stream);
 
 DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
-LaunchShape launch_shape(const PlanHeader &h, const DeviceGeom &dg, bool persistent, uint32_t table_mode, uint32_t n_groups, bool index_pass, bool direct, bool dual);
+LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, bool persistent, uint32_t table_mode, uint32_t n_groups, bool index_pass, bool direct, bool dual);
 struct TableChoice
 {
   uint32_t mode; // 0: none (the kernel builds its own), else kMode* of the host-built table
   bool dual;     // two chains per wave (k_decode_dual)
 };
-TableChoice choose_table(uint32_t bits, uint32_t states, bool direct);
+TableChoice choose_table(const Tuning &tn, uint32_t bits, uint32_t states, bool direct);
 // chain boundaries (in groups) of the direct launch: one chain per resident wave, sized by class weight; see hsrans_kernels.hip
-size_t direct_boundaries(const DeviceGeom &dg, uint32_t states, uint32_t bits, uint64_t total_groups, uint64_t *out, size_t cap);
-bool table_spill(); // HSRANS_TABLE_SPILL: leave host-built tables in global memory (comparison only)
+size_t direct_boundaries(const Tuning &tn, const DeviceGeom &dg, uint32_t states, uint32_t bits, uint64_t total_groups, uint64_t *out, size_t cap);
 // host-side builder of the bits >= 13 coarse/fine decode table (layout: kModeCoarse in hsrans_kernels.hip); returns entries written
 size_t build_rank_table(const uint16_t counts[256], uint32_t bits, uint2 *out, size_t capacity_entries);
 size_t rank_table_entries(uint32_t bits);
@@ -366,16 +364,16 @@ struct PartPlan
 };
 // `dealt` (may be null): the plan's shares for k_decode_dealt, from deal_shares with this device's current weights; the launcher takes that
 // kernel when it is given (the caller has checked the plan: lean grouped, 64 states, <= 11 bits, no single-symbol blocks)
-hipError_t launch_decode(const KParams &kp, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts = nullptr,
+hipError_t launch_decode(const Tuning &tn, const KParams &kp, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts = nullptr,
                          const DealtTable *dealt = nullptr, const uint32_t *dealt_weights = nullptr /* the 8 class weights `dealt` was made with */);
 // The dealing of k_decode_dealt: block k = chains [block_begin[k], block_begin[k + 1]) (n_blocks + 1 entries, the last = n_chains), every one a coded
 // block of single-piece mergeable chains.  Workgroup shares by age-class weight (the one-chain-per-wave launch's, this device's own once
 // calibrated), each cut back where it would reach into a third block.  false: the plan does not suit the launch (too few chains for the
 // device's waves, shares that would have to span more than two blocks, a share beyond 65,535 chains).  weights_out: the 8 class weights used
 // (the caller's cache key: a calibration changes them).
-bool deal_shares(const DeviceGeom &dg, const uint32_t *block_begin, uint32_t n_blocks, uint32_t n_chains, uint64_t total_groups, uint32_t bits, DealtTable *out,
+bool deal_shares(const Tuning &tn, const DeviceGeom &dg, const uint32_t *block_begin, uint32_t n_blocks, uint32_t n_chains, uint64_t total_groups, uint32_t bits, DealtTable *out,
                  uint32_t weights_out[8]);
-void dealt_weights_now(const DeviceGeom &dg, uint64_t run_groups, uint32_t bits, uint32_t weights_out[8]); // run_groups: groups per wave of the launch, on average
+void dealt_weights_now(const Tuning &tn, const DeviceGeom &dg, uint64_t run_groups, uint32_t bits, uint32_t weights_out[8]); // run_groups: groups per wave of the launch, on average
 
 } // namespace hsrans
 

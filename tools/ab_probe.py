@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A/B of library builds / tuning environments IN ONE PROCESS on the SAME device buffers (between processes the rotated 100 MB
 decode moves by +-3 us on one box, with no change at all: where the driver puts the pages decides; tools/rot_probe.py saw 37.5 and
-42.9 us for one and the same library).  Every variant is its own dlopen of a library file (its tuning environment is read when
-it loads) with its own context and device plans; the stream bytes do not depend on the index, so the streams and the output
+42.9 us for one and the same library).  Every variant is its own dlopen of a library file with its own context and device plans,
+made under the variant's tuning environment (a context and a device plan read it when they are made); the stream bytes do not depend on the index, so the streams and the output
 buffers are shared.  Windows of `--window` launches alternate between the variants, `--rounds` times.
 
     python tools/ab_probe.py --variant base --variant other:lib/variants/libhsrans_hip_other.so:HSRANS_DIRECT_WEIGHTS=1400,1330,1240,1130,960,810,640,490
@@ -72,14 +72,14 @@ for spec in a.variant:
     lib = parts[1] if len(parts) > 1 and parts[1] else "lib/libhsrans_hip.so"
     lib = lib if os.path.isabs(lib) else os.path.join(ROOT, "hypersonic_rans_amd", lib)
     env = dict(kv.split("=", 1) for kv in re.split(r",(?=[A-Z][A-Z0-9_]*=)", parts[2])) if len(parts) > 2 and parts[2] else {}  # (values may hold commas: weight lists)
-    # a private copy of the file: dlopen of one path twice would give the SAME library instance (one set of tuning globals)
+    # a private copy of the file: dlopen of one path twice would give the SAME library instance
     private = os.path.join(tmpdir, f"{tag}.so")
     shutil.copy(lib, private)
     saved = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     os.environ["HSRANS_LIB"] = private
     api._LIB = None
-    ctx = H.Context(0)  # loads `private` and reads the tuning environment
+    ctx = H.Context(0)  # loads `private`; the context and the plans below read the tuning environment
     cal = ctx.calibrate(bits=bits) if a.calibrate else None
     groups = H.index_boundaries(S, bits, n, ctx) if (a.container == "raw" and a.index == "wave") else None
     dplans = []
@@ -117,8 +117,6 @@ for spec in a.variant:
 
 
 def window(v, pick):
-    saved = {k: os.environ.get(k) for k in v["env"]}  # (some knobs are read at every launch: the variant's environment is in force while it runs)
-    os.environ.update(v["env"])
     ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ea.record()
     for t in range(a.window):
@@ -126,11 +124,6 @@ def window(v, pick):
         v["ctx"].decode_device(v["dplans"][k], d_in[k], d_out[k], stream_length=lens[k])
     eb.record()
     torch.cuda.synchronize()
-    for k, val in saved.items():
-        if val is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = val
     return round(ea.elapsed_time(eb) / a.window * 1e3, 2)
 
 

@@ -105,10 +105,16 @@ check("serial")
 report = {"size": n, "pairs": P, "states": S, "bits": bits, "index": a.index, "batch_index": a.batch_index, "calibration": cal, "rounds": []}
 weights = None
 for it in range(a.fit + 1):
+    ictx = ctx
     if weights is not None:
         os.environ["HSRANS_BATCH_WEIGHTS"] = ",".join(str(int(w)) for w in weights)
+        # a context reads HSRANS_BATCH_WEIGHTS when it is made, so this round's boundaries come from a fresh one (with the variable set,
+        # the batch's class lengths are the variable's whatever a calibration fitted); the batch made below reads it too
+        ictx = H.Context(0) if a.batch_index else ctx
     if a.batch_index:
-        bplans = [ctx.make_device_plan(ctx.index_build_at(H.RAW, S, bits, streams[k], H.index_boundaries_batch(S, bits, [n] * P, k, ctx))) for k in range(P)]
+        bplans = [ctx.make_device_plan(ctx.index_build_at(H.RAW, S, bits, streams[k], H.index_boundaries_batch(S, bits, [n] * P, k, ictx))) for k in range(P)]
+        if ictx is not ctx:
+            ictx.close()
         batch = ctx.make_batch(bplans)
     else:
         batch = ctx.make_batch(dplans)

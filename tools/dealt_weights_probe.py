@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Class lengths for the host-dealt launch at 13 / 14 bits (k_decode_dealt_rank): HSRANS_DEALT_WEIGHTS is read at every dealing, so one
-process times several sets on the same buffers (100 MB mt_, 256 KiB blocks, G = 16, four copies rotated), every set twice.
+"""Class lengths for the host-dealt launch at 13 / 14 bits (k_decode_dealt_rank): HSRANS_DEALT_WEIGHTS is read when a device plan is made,
+so one process times several sets, a plan for each, on the same buffers (100 MB mt_, 256 KiB blocks, G = 16, four copies rotated), every set twice.
     python tools/dealt_weights_probe.py > profiles/rNN_dealt_weights_14bit.txt"""
 import os, sys, json, time
 sys.path.insert(0, "/root/repo" if os.path.exists("/root/repo/bench.py") else ".")
@@ -34,6 +34,8 @@ for bits in (14, 13):
         for w in ("", "1192,1159,1120,1072,976,907,829,745", "1100,1075,1050,1020,975,950,920,900", "1300,1250,1180,1100,980,860,720,610", "1250,1200,1150,1080,1000,900,780,650", "1000,1000,1000,1000,1000,1000,1000,1000"):
             if w: os.environ["HSRANS_DEALT_WEIGHTS"] = w
             else: os.environ.pop("HSRANS_DEALT_WEIGHTS", None)
+            m2, dplan = ctx.encode_device(H.MT, 64, bits, d_in, enc, block_size=1 << 18, index_interval=16, want_plan=True)  # (the same stream bytes)
+            assert m2 == m
             us = timed(rot)
             ok = ctx.status(dplan) == 0 and all(bool(torch.equal(o, d_in)) for o in outs)
             print(bits, rnd, w or "calibrated", round(us, 2), dplan.launch_info()["spread"], ok, flush=True)

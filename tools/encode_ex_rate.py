@@ -42,18 +42,22 @@ def device_ms(fn):
 
 
 def stamps_of(fn):
-    """the HSRANS_DEBUG_STAMPS line one call prints to stderr (fd 2, captured in-process)"""
+    """the HSRANS_DEBUG_STAMPS line one call fn(context) prints to stderr (fd 2, captured in-process), on a fresh context: a context
+    reads the switch when it is made"""
     os.environ["HSRANS_DEBUG_STAMPS"] = "1"
+    try:
+        c = H.Context(0)
+    finally:
+        del os.environ["HSRANS_DEBUG_STAMPS"]
     with tempfile.TemporaryFile(mode="w+b") as f:
         sys.stderr.flush()
         saved = os.dup(2)
         os.dup2(f.fileno(), 2)
         try:
-            fn()
+            fn(c)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
-            del os.environ["HSRANS_DEBUG_STAMPS"]
         f.seek(0)
         text = f.read().decode(errors="replace")
     m = re.search(r"blocks (\d+)\s+units (\d+)\s+summaries ([\d.]+) us\s+walk ([\d.]+) us\s+chain\+gather ([\d.]+) us", text)
@@ -68,7 +72,7 @@ for kind in ("config2", "nonstationary"):
     raw_ms = device_ms(lambda: ctx.encode_device_raw(S, BITS, d_in, d_raw, index_groups=groups, want_plan=True))
     for cont, name in ((H.BLOCK, "block_"), (H.MT, "mt_")):
         d_out = torch.empty(H.capacity(cont, S, n), dtype=torch.uint8, device="cuda")
-        call = lambda: ctx.encode_device_ex(cont, S, BITS, d_in, d_out, index_groups=groups, want_plan=True)  # noqa: E731
+        call = lambda c=ctx: c.encode_device_ex(cont, S, BITS, d_in, d_out, index_groups=groups, want_plan=True)  # noqa: E731
         ms = device_ms(call)
         st = stamps_of(call)
         t0 = time.perf_counter()

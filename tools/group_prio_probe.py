@@ -3,8 +3,8 @@
 each scheduling class decode at raised instruction priority (s_setprio)?  A SIMD serves its oldest wave first; in a grouped launch
 every workgroup gets a whole block whatever its age, so the older workgroup of a CU is done long before the younger one, which then
 has the CU to itself at half the occupancy.  HSRANS_GROUP_PRIO_CLASS = ten per-mille values (KParams::group_prio_class: eight classes
-for evenly split groups, two grid halves for class-weighted ones) is read at every launch, so one process tries them all on the same
-buffers, alternating, rotated over COPIES (stream, output) pairs.
+for evenly split groups, two grid halves for class-weighted ones) is read when a device plan is made, so one process tries them all, a
+plan for each, on the same buffers, alternating, rotated over COPIES (stream, output) pairs.
 
     python tools/group_prio_probe.py --size 134217728 --block 262144 --interval 256 64 32"""
 import argparse
@@ -84,6 +84,8 @@ for interval in args.interval:
                 os.environ.pop("HSRANS_GROUP_PRIO_CLASS", None)
             else:
                 os.environ["HSRANS_GROUP_PRIO_CLASS"] = cfg
+            m2, dplan = ctx.encode_device(H.MT, 64, args.bits, d_in, enc, block_size=args.block, index_interval=interval, want_plan=True)  # (the same stream bytes)
+            assert m2 == m
             us = timed(rotated)
             info = dplan.launch_info()
             ok = ctx.status(dplan) == 0 and all(bool(torch.equal(o, d_in)) for o in outs)

@@ -33,6 +33,16 @@ class EncodeOpts(ctypes.Structure):
                 ("reserved", _u32), ("index_groups", _vp), ("n_index_groups", _sz)]
 
 
+class EncodeMember(ctypes.Structure):
+    """hsrans_encode_member: one stream of hsrans_encode_device_batch"""
+    _fields_ = [("container", _i), ("states", _i), ("bits", _u32), ("block_size", _u32), ("d_in", _vp), ("length", _sz), ("d_out", _vp),
+                ("out_capacity", _sz), ("hist", _vp), ("index_interval", _u32), ("index_groups", _vp), ("n_index_groups", _sz), ("stream_length", _sz)]
+
+
+class EncodeBatchStats(ctypes.Structure):
+    _fields_ = [(n, _u32) for n in ("launches", "raw_members", "mt_members", "mt_blocks")]
+
+
 class Calibration(ctypes.Structure):
     _fields_ = [("class_weights", _u32 * 8), ("class_finish_us_last_iteration", ctypes.c_double * 8), ("last_wave_us_before", ctypes.c_double),
                 ("last_wave_us_after", ctypes.c_double), ("class_spread_us_before", ctypes.c_double), ("class_spread_us_after", ctypes.c_double),
@@ -226,6 +236,8 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_block_choices.argtypes = [_i, _i, _u32, _vp, _sz, _u32, _vp, _sz]
     L.hsrans_block_choices_device.restype = _sz
     L.hsrans_block_choices_device.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz, _vp]
+    L.hsrans_encode_device_batch.restype = _i
+    L.hsrans_encode_device_batch.argtypes = [_vp, ctypes.POINTER(EncodeMember), _u32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(EncodeBatchStats)]
     L.hsrans_encode_device_ex.restype = _sz
     L.hsrans_encode_device_ex.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(Hist), ctypes.POINTER(EncodeOpts), _vp, ctypes.POINTER(_vp)]
     L.hsrans_index_build.restype = _sz
@@ -963,6 +975,53 @@ class Context:
         if want_device_plan and indexed:
             out.append(DevicePlan(self, h))
         return out[0] if len(out) == 1 else tuple(out)
+
+    def encode_device_batch(self, members, want_plans: bool = False, stream: torch.cuda.Stream | None = None, stats: dict | None = None):
+        """Many streams in one call (hsrans_encode_device_batch): member k is ``(container, states, bits, d_in, d_out)`` or
+        ``(container, states, bits, d_in, d_out, options)`` with ``options`` a dict of ``block_size`` (mt_; default 2^16),
+        ``index_interval``, ``hist`` (raw: a Hist), ``index_groups`` (raw) and ``length`` (default ``d_in.numel()``).  Each member gets
+        what its single call (``encode_device_raw`` / ``encode_device``) gives.  Returns the stream lengths, or ``(lengths, plans)``
+        with ``want_plans`` (a DevicePlan or None per member: raw members have one only with an index).  ``stats``: filled with
+        hsrans_encode_batch_stats.  Raises HsransError naming the first failed member; the error carries ``code``, ``lengths``
+        and ``plans`` (what the members that did not fail got)."""
+        K = len(members)
+        arr = (EncodeMember * max(K, 1))()
+        keep = []  # (the hists and group lists must outlive the call)
+        dev = None
+        for k, m in enumerate(members):
+            container, states, bits, d_in, d_out = m[:5]
+            o = dict(m[5]) if len(m) > 5 and m[5] is not None else {}
+            unknown = set(o) - {"block_size", "index_interval", "hist", "index_groups", "length"}
+            if unknown:
+                raise HsransError(f"encode_device_batch: member {k}: unknown options {sorted(unknown)}")
+            dev = d_in.device if dev is None else dev
+            e = arr[k]
+            e.container, e.states, e.bits = container, states, bits
+            e.block_size = o.get("block_size", 1 << 16 if container == MT else 0)
+            e.d_in, e.length = d_in.data_ptr(), int(o.get("length", d_in.numel()))
+            e.d_out, e.out_capacity = d_out.data_ptr(), d_out.numel()
+            e.index_interval = o.get("index_interval", 0)
+            if o.get("hist") is not None:
+                keep.append(o["hist"])
+                e.hist = ctypes.addressof(o["hist"])
+            if o.get("index_groups") is not None:
+                g = np.ascontiguousarray(o["index_groups"], dtype=np.uint64)
+                keep.append(g)
+                e.index_groups, e.n_index_groups = (g.ctypes.data if g.size else None), g.size
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        handles = (_vp * max(K, 1))()
+        st = EncodeBatchStats()
+        rc = self.L.hsrans_encode_device_batch(self.handle, arr, K, ctypes.c_void_p(s.cuda_stream), handles if want_plans else None, ctypes.byref(st))
+        if stats is not None:
+            stats.update({n: getattr(st, n) for n, _ in EncodeBatchStats._fields_})
+        lengths = [int(arr[k].stream_length) for k in range(K)]
+        plans = [DevicePlan(self, _vp(handles[k])) if want_plans and handles[k] else None for k in range(K)]
+        if rc != 0:
+            failed = [k for k in range(K) if lengths[k] == 0]
+            err = HsransError(f"hsrans_encode_device_batch failed with code {rc}" + (f": member {failed[0]} failed" if failed and rc != 2 else ""))
+            err.code, err.lengths, err.plans = rc, lengths, plans
+            raise err
+        return (lengths, plans) if want_plans else lengths
 
     def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
                              stream: torch.cuda.Stream | None = None) -> np.ndarray:

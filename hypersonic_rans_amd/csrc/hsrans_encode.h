@@ -78,6 +78,37 @@ hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream, bool *pr
 // asynchronous on `stream`: K_plan (needs ep.plan, ep.n_chains; after launch_encode's results are known)
 hipError_t launch_encode_plan(const EncParams &ep, hipStream_t stream);
 
+// mt_ streams of up to this many blocks: K_gather adds up the image sizes itself, beyond it K_scan runs first
+constexpr uint32_t kEncSelfScanBlocks = 4096;
+
+// ---- batches (hsrans_encode_device_batch): one workgroup of a batched launch works on block / part `index` (of `count`) of member `member`
+struct EncTask
+{
+  uint32_t member, index, count;
+};
+// what launch_encode_batch launches, every array in device memory.  Raw members are as launch_encode_raw's EncParams (raw_counts: 256
+// counts of their own inside `zero`), mt_ members as launch_encode's (raw_counts: their per-block counts; fits: a device word).
+struct EncBatch
+{
+  const EncParams *params;     // [members]
+  const EncTask *raw_parts;    // histogram and copy workgroups of the raw members: {member, part, parts}
+  uint32_t n_raw_parts;
+  const uint32_t *raw_members; // coding wavefronts: n_raw64 members of 64 states, then n_raw32 of 32
+  uint32_t n_raw64, n_raw32;
+  uint8_t *const *raw_headers; // [members]: where k_copy_images_batch puts a raw member's stream header for its plan, or null
+  const EncTask *mt_blocks;    // every block of the mt_ members: {member, block, 0}, n_mt64_blocks of 64-state members first
+  uint32_t n_mt64_blocks, n_mt32_blocks;
+  const uint32_t *scan_members; // mt_ members of more blocks than k_gather_images adds up itself: K_scan's
+  uint32_t n_scan;
+  void *zero;                  // zeroed first (one memset): every member's result words and the raw members' counts
+  size_t zero_bytes;
+};
+// asynchronous on `stream`: memset -> K_hist (raw), K_hist (mt_) -> K_raw per state count -> K_enc per state count -> [K_scan] -> K_gather
+// -> K_copy; each kind launched once for all members, none for a kind no member needs.  *launches += the kernels launched
+hipError_t launch_encode_batch(const EncBatch &batch, hipStream_t stream, bool *prepared, uint32_t *launches);
+// asynchronous on `stream`: K_plan over `tasks` (the mt_ blocks); members whose EncParams::plan is null are skipped
+hipError_t launch_encode_plan_batch(const EncParams *params, const EncTask *tasks, uint32_t n_tasks, hipStream_t stream, uint32_t *launches);
+
 } // namespace hsrans
 
 #endif // HSRANS_ENCODE_H

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <utility>
 
 #include "hsrans_encode.h"
 #include "hsrans_kernels.h"
@@ -1093,7 +1094,8 @@ __global__ void __launch_bounds__(64 * kWavesPerWG) k_encode_blocks(EncParams ep
 // ---- raw streams: K_hist (wide) -> K_raw (one wavefront) -> K_copy (wide) -----------------------------------------------
 // byte counts of the whole input into counts[256] (zeroed by the launcher): per-workgroup LDS histograms (the sub-histogram layout
 // of the block encoder), one global atomic per symbol and workgroup
-__global__ void __launch_bounds__(256) k_raw_histogram(const uint8_t *in, uint64_t n, uint32_t *counts)
+// (workgroup `wg` of `n_wg` that share the input: the body of k_raw_histogram and of k_raw_histogram_batch)
+__device__ __forceinline__ void raw_histogram_body(const uint8_t *in, uint64_t n, uint32_t *counts, uint32_t wg, uint32_t n_wg)
 {
   constexpr uint32_t kSubStride = 257; // dwords between copies: copy c of symbol s sits in bank (c + s) % 32, not all in bank s % 32
   __shared__ uint32_t sub[kSubHists * kSubStride];
@@ -1101,7 +1103,7 @@ __global__ void __launch_bounds__(256) k_raw_histogram(const uint8_t *in, uint64
     sub[k] = 0;
   __syncthreads();
   uint32_t *mine = sub + (threadIdx.x & (kSubHists - 1)) * kSubStride;
-  for (uint64_t off = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16; off < n; off += (uint64_t)gridDim.x * 4096)
+  for (uint64_t off = ((uint64_t)wg * 256 + threadIdx.x) * 16; off < n; off += (uint64_t)n_wg * 4096)
   {
     const uint4 d = load16_guarded(in, off, n);
     const uint32_t w[4] = {d.x, d.y, d.z, d.w};
@@ -1116,11 +1118,12 @@ __global__ void __launch_bounds__(256) k_raw_histogram(const uint8_t *in, uint64
   if (v)
     atomicAdd(&counts[threadIdx.x], v);
 }
+__global__ void __launch_bounds__(256) k_raw_histogram(const uint8_t *in, uint64_t n, uint32_t *counts) { raw_histogram_body(in, n, counts, blockIdx.x, gridDim.x); }
 
 // byte counts of every block of an mt_ encode, a workgroup per block: counts[b][256].  The coding wavefront used to count its own
 // block (33 us of its ~270 at 64 KiB, 130 us at 256 KiB: 64 lanes of LDS atomics); 256 threads per block and every CU at it take
 // a few microseconds for the whole input, and the block is in L2 when the coding wavefront reads it again.
-__global__ void __launch_bounds__(256) k_block_histograms(EncParams ep, uint32_t *counts)
+__device__ __forceinline__ void block_histograms_body(EncParams ep, const uint32_t b, uint32_t *counts)
 {
   // 32 copies of the histogram, copy = lane & 31, laid out [symbol][copy]: a lane's counter is ALWAYS in bank (lane & 31), whatever the
   // symbol, so the 32 lanes the LDS serves at a time never meet in a bank (the [copy][symbol] layout of round 4, copies 257 dwords apart,
@@ -1130,7 +1133,6 @@ __global__ void __launch_bounds__(256) k_block_histograms(EncParams ep, uint32_t
   // 27.3 us with 24, 26.5 us with 16: it is the atomics, not the tail of the grid)
   constexpr uint32_t kCopies = 32;
   __shared__ uint32_t sub[256 * kCopies];
-  const uint32_t b = blockIdx.x;
   const uint64_t begin = (uint64_t)b * ep.block;
   const uint64_t end = b + 1 == ep.n_blocks ? ep.n : begin + ep.block;
   for (uint32_t k = threadIdx.x; k < 256 * kCopies; k += 256)
@@ -1173,6 +1175,7 @@ __global__ void __launch_bounds__(256) k_block_histograms(EncParams ep, uint32_t
     v += sub[threadIdx.x * kCopies + ((threadIdx.x + c) & (kCopies - 1))];
   counts[(uint64_t)b * 256 + threadIdx.x] = v;
 }
+__global__ void __launch_bounds__(256) k_block_histograms(EncParams ep, uint32_t *counts) { block_histograms_body(ep, blockIdx.x, counts); }
 
 // the unit summaries of the block walk (hsrans_host.h UnitSummary: counts[256], run_len, run_sym, fresh_cost; 1040 bytes), a workgroup per unit
 // of ep.block symbols: k_block_histograms' counting, and per thread the highest position whose byte differs from the unit's last
@@ -1324,7 +1327,7 @@ __device__ __forceinline__ uint64_t wg_exclusive_scan(uint64_t v, uint64_t *wave
   return before + incl - v;
 }
 
-__global__ void __launch_bounds__(1024) k_scan_images(EncParams ep)
+__device__ __forceinline__ void scan_images_body(EncParams ep)
 {
   __shared__ uint64_t wave_tot[16];
   uint64_t bytes_before = 16; // file header
@@ -1378,14 +1381,15 @@ __global__ void __launch_bounds__(1024) k_scan_images(EncParams ep)
     }
   }
 }
+__global__ void __launch_bounds__(1024) k_scan_images(EncParams ep) { scan_images_body(ep); }
 
 // ---- K_plan: the sidecar plan of the stream (hsrans_plan.h), one wavefront per block --------------------------------
 // Writes exactly what the host encoder emits for the same layout (hsrans_host.cpp encode(), "sidecar plan"): single-piece
 // chains in output order — per coded block one chain from the block header's states plus one per checkpoint, per
 // single-symbol block one fill chain — and the Group records of the grouped decode launch (one group per block).
-__global__ void __launch_bounds__(64) k_plan_blocks(EncParams ep)
+__device__ __forceinline__ void plan_blocks_body(EncParams ep, const uint32_t b)
 {
-  const uint32_t b = blockIdx.x, lane = threadIdx.x, S = ep.S;
+  const uint32_t lane = threadIdx.x, S = ep.S;
   const uint32_t nc = ep.n_chains;
   uint32_t *chain_first = (uint32_t *)(ep.plan + plan_chain_first_off());
   Piece *pieces = (Piece *)(ep.plan + plan_pieces_off(nc));
@@ -1465,6 +1469,7 @@ __global__ void __launch_bounds__(64) k_plan_blocks(EncParams ep)
     ((Group *)ep.groups)[(uint64_t)b * ep.group_split + lane] = g;
   }
 }
+__global__ void __launch_bounds__(64) k_plan_blocks(EncParams ep) { plan_blocks_body(ep, blockIdx.x); }
 
 // ---- K_gather: one workgroup per block image; source and destination are only 2-byte aligned -------------------------
 struct __attribute__((packed, aligned(2))) U128a2
@@ -1486,11 +1491,10 @@ __device__ __forceinline__ uint64_t wg_sum(uint64_t v, uint64_t *slot)
 // Up to this many blocks, every workgroup of K_gather adds up the image sizes in front of its own block itself (n / 256 loads per
 // thread out of L2, two reductions) and the scan kernel with its launch is not run at all: K_scan is one workgroup's worth of latency
 // (13.5 us at 1,526 blocks) on the path of every encode.  Beyond it the reads grow with the square of the block count: K_scan again.
-constexpr uint32_t kSelfScanBlocks = 4096;
+constexpr uint32_t kSelfScanBlocks = kEncSelfScanBlocks;
 
-__global__ void __launch_bounds__(256) k_gather_images(EncParams ep)
+__device__ __forceinline__ void gather_images_body(EncParams ep, const uint32_t b)
 {
-  const uint32_t b = blockIdx.x;
   const uint64_t bytes = ep.image_bytes[b];
   uint64_t off;
   if (ep.n_blocks <= kSelfScanBlocks)
@@ -1570,24 +1574,26 @@ __global__ void __launch_bounds__(256) k_gather_images(EncParams ep)
   for (uint64_t k = head + body * 16 + threadIdx.x * 2; k < bytes; k += 512)
     *(uint16_t *)(dst + k) = *(const uint16_t *)(src + k);
 }
+__global__ void __launch_bounds__(256) k_gather_images(EncParams ep) { gather_images_body(ep, blockIdx.x); }
 
-// the one image of a raw encode (the whole stream), copied by the whole grid
-__global__ void __launch_bounds__(256) k_copy_image(EncParams ep)
+// the one image of a raw encode (the whole stream), copied by workgroups wg of n_wg (k_copy_image: the whole grid)
+__device__ __forceinline__ void copy_image_body(EncParams ep, const uint32_t wg, const uint32_t n_wg)
 {
   if (ep.result[1] == 0)
     return;
   const uint64_t bytes = ep.image_bytes[0];
   const uint8_t *src = ep.scratch + ep.slot_bytes - bytes; // 2-byte aligned; ep.out is 16-byte aligned
   const uint64_t body = bytes / 16;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < body; i += (uint64_t)gridDim.x * 256)
+  for (uint64_t i = (uint64_t)wg * 256 + threadIdx.x; i < body; i += (uint64_t)n_wg * 256)
   {
     const U128a2 v = *(const U128a2 *)(src + i * 16);
     *(uint4 *)(ep.out + i * 16) = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
   }
-  if (blockIdx.x == 0)
+  if (wg == 0)
     for (uint64_t i = body * 16 + threadIdx.x * 2; i < bytes; i += 512)
       *(uint16_t *)(ep.out + i) = *(const uint16_t *)(src + i);
 }
+__global__ void __launch_bounds__(256) k_copy_image(EncParams ep) { copy_image_body(ep, blockIdx.x, gridDim.x); }
 
 // ---- chain encodes: block_ / mt_ streams whose coder states run through every block ----------------------------------------
 // The reference carries the states from block to block (mt_rANS32x64_16w_encode.cpp:220-222, the block_ encoders alike), so the
@@ -1668,6 +1674,83 @@ __global__ void __launch_bounds__(256) k_gather_chain(EncParams ep)
   if (part + 1 == parts)
     for (uint64_t k = head + body * 16 + threadIdx.x * 2; k < bytes; k += 512)
       *(uint16_t *)(dst + k) = *(const uint16_t *)(src + k);
+}
+
+// ---- batches (hsrans_encode_device_batch): many independent streams, one launch per kernel kind ---------------------------
+// Every member has an EncParams of its own in device memory (its slots, result words and checkpoints carved out of the context's
+// buffers by the host); a workgroup finds its member — and the block or part of it — in a task list.  The members' parameters are
+// read before anything is stored, so the compiler takes them with scalar loads (what a kernel argument costs) and the per-wave work
+// is the single calls' own code: encode_body and the bodies above.
+template <uint32_t S>
+__global__ void __launch_bounds__(64) k_encode_raw_batch(const EncParams *__restrict__ params, const uint32_t *__restrict__ members)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  const EncParams ep = params[members[blockIdx.x]];
+  encode_body<S, true, kChunkFew>(ep, 0, *(WaveLdsT<kChunkFew> *)lds_raw, lane_id());
+}
+
+template <uint32_t S, uint32_t CHUNK>
+__global__ void __launch_bounds__(64) k_encode_blocks_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ tasks)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  const EncTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  encode_body<S, false, CHUNK>(ep, t.index, *(WaveLdsT<CHUNK> *)lds_raw, lane_id());
+}
+
+// raw members: part t.index of t.count workgroups counts the member's bytes into its raw_counts (zeroed by the launcher)
+__global__ void __launch_bounds__(256) k_raw_histogram_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ parts)
+{
+  const EncTask t = parts[blockIdx.x];
+  const EncParams ep = params[t.member];
+  raw_histogram_body(ep.in, ep.n, const_cast<uint32_t *>(ep.raw_counts), t.index, t.count);
+}
+
+// mt_ members: block t.index of member t.member
+__global__ void __launch_bounds__(256) k_block_histograms_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ tasks)
+{
+  const EncTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  block_histograms_body(ep, t.index, const_cast<uint32_t *>(ep.raw_counts));
+}
+
+// mt_ members of more than kSelfScanBlocks blocks, one workgroup each
+__global__ void __launch_bounds__(1024) k_scan_images_batch(const EncParams *__restrict__ params, const uint32_t *__restrict__ members)
+{
+  const EncParams ep = params[members[blockIdx.x]];
+  scan_images_body(ep);
+}
+
+__global__ void __launch_bounds__(256) k_gather_images_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ tasks)
+{
+  const EncTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  gather_images_body(ep, t.index);
+}
+
+// raw members: part t.index of t.count workgroups copies the member's image; part 0 also puts the stream header (counts, final states)
+// at headers[member] when that is not null, where the host fetches every member's header and checkpoints with one copy
+__global__ void __launch_bounds__(256) k_copy_images_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ parts, uint8_t *const *__restrict__ headers)
+{
+  const EncTask t = parts[blockIdx.x];
+  const EncParams ep = params[t.member];
+  uint8_t *header = headers[t.member];
+  copy_image_body(ep, t.index, t.count);
+  if (t.index != 0 || header == nullptr || ep.result[1] == 0)
+    return;
+  const uint8_t *src = ep.scratch + ep.slot_bytes - ep.image_bytes[0]; // (2-byte aligned)
+  for (uint32_t i = threadIdx.x * 2; i < 16 + 512 + 4 * ep.S; i += 512)
+    *(uint16_t *)(header + i) = *(const uint16_t *)(src + i);
+}
+
+// mt_ members that asked for a plan (ep.plan set by the host once the chain counts are known); the others' blocks return at once
+__global__ void __launch_bounds__(64) k_plan_blocks_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ tasks)
+{
+  const EncTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  if (ep.plan == nullptr)
+    return;
+  plan_blocks_body(ep, t.index);
 }
 
 } // namespace
@@ -1800,6 +1883,112 @@ hipError_t launch_encode_plan(const EncParams &ep, hipStream_t stream)
 {
   (void)hipGetLastError();
   hipLaunchKernelGGL(k_plan_blocks, dim3(ep.n_blocks), dim3(64), 0, stream, ep);
+  return hipGetLastError();
+}
+
+
+hipError_t launch_encode_batch(const EncBatch &bt, hipStream_t stream, bool *prepared_flag, uint32_t *launches)
+{
+  bool local = false;
+  bool &prepared = prepared_flag ? *prepared_flag : local;
+  const size_t lds_few = sizeof(WaveLdsT<kChunkFew>), lds_many = sizeof(WaveLdsT<kChunkMany>);
+  if (!prepared)
+  {
+    const std::pair<const void *, size_t> kernels[] = {{(const void *)k_encode_raw_batch<64>, lds_few},
+                                                       {(const void *)k_encode_raw_batch<32>, lds_few},
+                                                       {(const void *)k_encode_blocks_batch<64, kChunkFew>, lds_few},
+                                                       {(const void *)k_encode_blocks_batch<32, kChunkFew>, lds_few},
+                                                       {(const void *)k_encode_blocks_batch<64, kChunkMany>, lds_many},
+                                                       {(const void *)k_encode_blocks_batch<32, kChunkMany>, lds_many}};
+    for (const auto &k : kernels)
+    {
+      const hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second);
+      if (e != hipSuccess)
+        return e;
+    }
+    prepared = true;
+  }
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    cus = 1;
+  const uint32_t n_raw = bt.n_raw64 + bt.n_raw32, n_mt = bt.n_mt64_blocks + bt.n_mt32_blocks;
+  // the chunk variant from all mt_ blocks of the batch, as launch_encode picks it from one stream's
+  const bool few = n_mt <= 11u * (uint32_t)cus;
+  uint32_t n = 0;
+  (void)hipGetLastError(); // (sticky per thread)
+  if (bt.zero_bytes != 0)
+  {
+    const hipError_t e = hipMemsetAsync(bt.zero, 0, bt.zero_bytes, stream);
+    if (e != hipSuccess)
+      return e;
+  }
+  if (n_raw != 0)
+    {
+      hipLaunchKernelGGL(k_raw_histogram_batch, dim3(bt.n_raw_parts), dim3(256), 0, stream, bt.params, bt.raw_parts);
+      n++;
+    }
+  if (n_mt != 0)
+    {
+      hipLaunchKernelGGL(k_block_histograms_batch, dim3(n_mt), dim3(256), 0, stream, bt.params, bt.mt_blocks);
+      n++;
+    }
+  if (bt.n_raw64 != 0)
+    {
+      hipLaunchKernelGGL(k_encode_raw_batch<64>, dim3(bt.n_raw64), dim3(64), lds_few, stream, bt.params, bt.raw_members);
+      n++;
+    }
+  if (bt.n_raw32 != 0)
+    {
+      hipLaunchKernelGGL(k_encode_raw_batch<32>, dim3(bt.n_raw32), dim3(64), lds_few, stream, bt.params, bt.raw_members + bt.n_raw64);
+      n++;
+    }
+  const EncTask *mt32 = bt.mt_blocks + bt.n_mt64_blocks;
+  if (bt.n_mt64_blocks != 0 && few)
+    {
+      hipLaunchKernelGGL((k_encode_blocks_batch<64, kChunkFew>), dim3(bt.n_mt64_blocks), dim3(64), lds_few, stream, bt.params, bt.mt_blocks);
+      n++;
+    }
+  else if (bt.n_mt64_blocks != 0)
+    {
+      hipLaunchKernelGGL((k_encode_blocks_batch<64, kChunkMany>), dim3(bt.n_mt64_blocks), dim3(64), lds_many, stream, bt.params, bt.mt_blocks);
+      n++;
+    }
+  if (bt.n_mt32_blocks != 0 && few)
+    {
+      hipLaunchKernelGGL((k_encode_blocks_batch<32, kChunkFew>), dim3(bt.n_mt32_blocks), dim3(64), lds_few, stream, bt.params, mt32);
+      n++;
+    }
+  else if (bt.n_mt32_blocks != 0)
+    {
+      hipLaunchKernelGGL((k_encode_blocks_batch<32, kChunkMany>), dim3(bt.n_mt32_blocks), dim3(64), lds_many, stream, bt.params, mt32);
+      n++;
+    }
+  if (bt.n_scan != 0)
+    {
+      hipLaunchKernelGGL(k_scan_images_batch, dim3(bt.n_scan), dim3(1024), 0, stream, bt.params, bt.scan_members);
+      n++;
+    }
+  if (n_mt != 0)
+    {
+      hipLaunchKernelGGL(k_gather_images_batch, dim3(n_mt), dim3(256), 0, stream, bt.params, bt.mt_blocks);
+      n++;
+    }
+  if (n_raw != 0)
+    {
+      hipLaunchKernelGGL(k_copy_images_batch, dim3(bt.n_raw_parts), dim3(256), 0, stream, bt.params, bt.raw_parts, bt.raw_headers);
+      n++;
+    }
+  if (launches)
+    *launches += n;
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_plan_batch(const EncParams *params, const EncTask *tasks, uint32_t n_tasks, hipStream_t stream, uint32_t *launches)
+{
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_plan_blocks_batch, dim3(n_tasks), dim3(64), 0, stream, params, tasks);
+  if (launches)
+    *launches += 1;
   return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@ struct hsrans_ctx
   bool enc_prepared = false;
   bool enc_raw_prepared = false;
   bool enc_chain_prepared = false;
+  bool enc_batch_prepared = false;
   std::mutex lock; // guards the staging buffers of the host-pointer entries
   std::mutex stream_lock; // creation of pipe_streams (hsrans_hpipe_create may run under `lock` or without it)
   hipStream_t stream = nullptr;

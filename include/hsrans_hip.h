@@ -429,6 +429,59 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
                                 uint32_t index_interval, const uint64_t *index_groups, size_t n_index_groups, uint8_t *plan_out, size_t plan_capacity,
                                 size_t *plan_size, void *hip_stream, hsrans_dplan **out_dplan);
 
+/* Many independent streams encoded on the GPU at once: the encode-side twin of hsrans_decode_device_batch.
+ *
+ * Member equivalence.  Member k gets exactly what it would get from its single call on `hip_stream`: the same stream bytes at d_out,
+ * the same stream_length, and in out_dplans[k] (when out_dplans != NULL) the device plan that call returns in *out_dplan (NULL where
+ * it returns none).
+ *   HSRANS_RAW: hsrans_encode_device_raw(ctx, states, bits, d_in, length, d_out, out_capacity, hist, index_interval, index_groups,
+ *               n_index_groups, NULL, 0, NULL, hip_stream, out_dplans ? &p : NULL) — a plan only with an index (interval or groups).
+ *   HSRANS_MT:  hsrans_encode_device(ctx, HSRANS_MT, states, bits, d_in, length, d_out, out_capacity, block_size, index_interval,
+ *               hip_stream, out_dplans ? &p : NULL) — fixed blocks of block_size symbols, each from fresh states.
+ * Mixing.  Raw and mt_ members, 32 and 64 states and every bit width may share one call; count is 1..65,536.
+ * Validation before launch.  Every member is checked with its single call's rules before anything is launched; besides, no two
+ * members' output ranges [d_out, d_out + out_capacity) may overlap, and no output range may overlap any member's input range
+ * [d_in, d_in + length).  hist, index_groups and n_index_groups belong to HSRANS_RAW members (NULL / 0 otherwise), block_size to
+ * HSRANS_MT members (0 for raw).  HSRANS_BLOCK members, mt_ members with carried states or adaptive blocks (block_size 0) and anything
+ * else a check refuses: HSRANS_E_ARG, nothing launched, no output byte changed, every stream_length 0.
+ * Failure on the device.  The only one: a raw member whose caller hist gives no slot to a byte that occurs.  That member gets
+ * stream_length 0 and a NULL plan; the others complete; the call returns HSRANS_E_DEVICE.  (HSRANS_E_HIP: the runtime failed.)
+ * Synchronisation.  Synchronises hip_stream: every output is complete on return (twice when mt_ plans are made: their chain counts
+ * are needed before the plans are written on the device; and once more per mt_ plan with checkpoints, whose group list is read back
+ * as the single call reads it).
+ * Launch count.  Independent of count: each kernel kind launches at most once per (kind, state count, chunk variant) present —
+ * the raw histograms, the mt_ block histograms, the raw coding wavefronts per state count, the mt_ coding wavefronts per state count
+ * (one chunk variant for the whole batch, chosen from its total block count), the mt_ size scan (only for members of more than 4,096
+ * blocks), the mt_ gather, the raw image copy, and the mt_ plans (only when asked for): at most 10 kernels, plus one memset and the
+ * copies of the members' parameters and results.  stats->launches counts the kernels.
+ * Host work per member: its validation and parameter record; with out_dplans, per raw member with an index its plan is assembled on
+ * the host (as the single call does) and uploaded by hsrans_dplan_create (one device allocation), and per mt_ member one plan
+ * allocation, one memset and one header upload; raw members' headers and checkpoints come down in one copy for all of them.
+ * The members' scratch (slots, result words, checkpoints) is carved out of the context's encode buffers, which grow to the sum over
+ * all members: a raw member needs about 2 x length, an mt_ member 2 x block_size per block.  Calls on one context are serialised.
+ * Limits: the single calls' (raw length <= 2^31 - 2^16), and fewer than 2^24 mt_ blocks and 2^24 raw 64 KiB parts in one call. */
+typedef struct hsrans_encode_member
+{
+  int container, states;       /* HSRANS_RAW or HSRANS_MT (fixed, independent blocks); 32 or 64 */
+  uint32_t bits;               /* 10..15 */
+  uint32_t block_size;         /* HSRANS_MT: symbols per block, multiple of 64; HSRANS_RAW: must be 0 */
+  const void *d_in;            /* device, 16-byte aligned */
+  size_t length;
+  void *d_out;                 /* device, 16-byte aligned, out_capacity >= hsrans_capacity(container, states, length) */
+  size_t out_capacity;
+  const hsrans_hist *hist;     /* HSRANS_RAW only, may be NULL (as hsrans_encode_device_raw) */
+  uint32_t index_interval;     /* checkpoints for the member's plan, multiple of 4, 0 = none */
+  const uint64_t *index_groups; /* HSRANS_RAW only (e.g. hsrans_index_boundaries_batch) */
+  size_t n_index_groups;
+  size_t stream_length;        /* out: bytes written to d_out, 0 = this member failed */
+} hsrans_encode_member;
+typedef struct hsrans_encode_batch_stats
+{
+  uint32_t launches, raw_members, mt_members, mt_blocks;
+} hsrans_encode_batch_stats;
+int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member *members, uint32_t count, void *hip_stream, hsrans_dplan **out_dplans,
+                               hsrans_encode_batch_stats *stats);
+
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one
  * sequential wavefront), HSRANS_MT (one wavefront per block) and HSRANS_BLOCK (one sequential wavefront that also reports

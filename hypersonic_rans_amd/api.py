@@ -258,6 +258,8 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_hpipe_destroy.argtypes = [_vp]
     L.hsrans_decode_host_pipelined.restype = _sz
     L.hsrans_decode_host_pipelined.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _u32]
+    L.hsrans_encode_host_pipelined.restype = _sz
+    L.hsrans_encode_host_pipelined.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(EncodeOpts), _u32]
     L.hsrans_host_register.restype = _i
     L.hsrans_host_register.argtypes = [_vp, _vp, _sz]
     L.hsrans_host_unregister.restype = _i
@@ -1051,6 +1053,30 @@ class Context:
         plan = _u8(plan)
         return self.L.hsrans_decode_host_pipelined(self.handle, container, states, bits, stream.data_ptr(), stream.numel(), out.data_ptr(), out.numel(),
                                                    _p(plan), plan.size, n_slices)
+
+    def encode_host_pipelined(self, states: int, bits: int, host_in, host_out, block_size: int = 1 << 16, index_interval: int = 0,
+                              n_slices: int = 0):
+        """mt_ encode (independent fixed-size blocks) of host bytes into a host buffer on the GPU, the PCIe legs overlapped
+        (hsrans_encode_host_pipelined; twin of :meth:`decode_host_pipelined`).  ``host_in`` / ``host_out``: torch CPU uint8 tensors
+        (ideally pinned) or numpy arrays; ``host_out`` needs ``capacity(MT, states, len(host_in))`` bytes.  Returns ``(length, plan)``,
+        ``plan`` a numpy array when ``index_interval`` is set, else None."""
+        def addr(a):
+            if isinstance(a, torch.Tensor):
+                if a.is_cuda or a.dtype != torch.uint8 or not a.is_contiguous():
+                    raise HsransError("encode_host_pipelined takes contiguous uint8 CPU tensors")
+                return a.data_ptr(), a.numel()
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous):
+                raise HsransError("encode_host_pipelined takes contiguous uint8 numpy arrays")
+            return a.ctypes.data, a.size
+        p_in, n_in = addr(host_in)
+        p_out, n_out = addr(host_out)
+        plan = np.zeros(max(self.L.hsrans_plan_capacity(MT, states, n_in, index_interval, block_size) if index_interval else 1, 1), np.uint8)
+        opts = EncodeOpts(block_size, index_interval, plan.ctypes.data if index_interval else None, plan.size if index_interval else 0, 0,
+                          ENC_INDEPENDENT_BLOCKS, 0, None, 0)
+        n = self.L.hsrans_encode_host_pipelined(self.handle, MT, states, bits, p_in, n_in, p_out, n_out, ctypes.byref(opts), n_slices)
+        if n == 0:
+            raise HsransError("hsrans_encode_host_pipelined failed")
+        return n, (plan[: opts.plan_size].copy() if index_interval else None)
 
     def index_build(self, container: int, states: int, bits: int, stream, index_interval: int) -> np.ndarray:
         stream = _u8(stream)

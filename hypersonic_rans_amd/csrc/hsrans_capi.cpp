@@ -234,6 +234,8 @@ void hsrans_ctx_destroy(hsrans_ctx *ctx)
     (void)hipHostFree(ctx->h_pin);
   if (ctx->h_enc_result)
     (void)hipHostFree(ctx->h_enc_result);
+  if (ctx->h_pipe_result)
+    (void)hipHostFree(ctx->h_pipe_result);
   for (hipStream_t st : ctx->pipe_streams)
     if (st)
       (void)hipStreamDestroy(st);

@@ -78,6 +78,23 @@ hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream, bool *pr
 // asynchronous on `stream`: K_plan (needs ep.plan, ep.n_chains; after launch_encode's results are known)
 hipError_t launch_encode_plan(const EncParams &ep, hipStream_t stream);
 
+// ---- host pipeline (hsrans_encode_host_pipelined): one stream encoded slice by slice, a slice = a run of whole blocks ----
+// Where the stream stands after the slices so far, in device memory; {16, 0, 0, 0} before the first
+struct EncCarry
+{
+  uint64_t bytes_before;  // stream bytes so far (the 16-byte file header included)
+  uint64_t chains_before; // plan chains so far
+  uint64_t coded_blocks;  // blocks that are not single-symbol blocks
+  uint64_t last_hist;     // position of the counts of the last such block
+};
+// asynchronous on `stream`: K_hist -> K_enc (launch_encode's) -> K_scan (carried) -> K_gather (carried).  ep describes the slice
+// (ep.in its first byte, ep.n its length, ep.n_blocks its blocks; the per-block arrays start at its first block), ep.out its staging
+// buffer (the images packed from byte 0); result[0..4] as launch_encode's, absolute, result[5] the stream position of the slice's first
+// byte.  heads: or null, 16 + 4 S bytes per block of what k_plan_blocks reads of the images (launch_encode_plan_carried)
+hipError_t launch_encode_slice(const EncParams &ep, EncCarry *carry, bool last_slice, uint8_t *heads, hipStream_t stream, bool *prepared);
+// asynchronous on `stream`: K_plan over the whole stream after its last slice, the images' heads at ep.scratch (launch_encode_slice's)
+hipError_t launch_encode_plan_carried(const EncParams &ep, hipStream_t stream);
+
 // mt_ streams of up to this many blocks: K_gather adds up the image sizes itself, beyond it K_scan runs first
 constexpr uint32_t kEncSelfScanBlocks = 4096;
 

@@ -1327,11 +1327,18 @@ __device__ __forceinline__ uint64_t wg_exclusive_scan(uint64_t v, uint64_t *wave
   return before + incl - v;
 }
 
-__device__ __forceinline__ void scan_images_body(EncParams ep)
+// CARRIED (hsrans_encode_host_pipelined): the blocks are one slice of a longer stream.  The stream position, chain count, coded-block
+// count and last histogram position come in through *carry and leave through it, so that image_off / chain_off are the absolute ones
+// of the whole stream; result[5] is the slice's first byte.  The file header is not written (the caller writes it after the last
+// slice), and a slice that is not the stream's last gives its last coded block the skip of a block with a successor (encode_body
+// took it for the stream's last block).
+template <bool CARRIED = false>
+__device__ __forceinline__ void scan_images_body(EncParams ep, EncCarry *carry = nullptr, uint32_t last_slice = 1)
 {
   __shared__ uint64_t wave_tot[16];
-  uint64_t bytes_before = 16; // file header
-  uint64_t chains_before = 0, coded_blocks = 0, last_hist = 0;
+  uint64_t bytes_before = CARRIED ? carry->bytes_before : 16; // file header
+  uint64_t chains_before = CARRIED ? carry->chains_before : 0, coded_blocks = CARRIED ? carry->coded_blocks : 0, last_hist = 0;
+  const uint64_t slice_base = bytes_before;
   constexpr uint64_t kNone = ~(uint64_t)0;
   uint64_t my_last = kNone; // highest non-single block this thread has seen
   for (uint32_t base = 0; base < ep.n_blocks; base += 1024)
@@ -1358,7 +1365,7 @@ __device__ __forceinline__ void scan_images_body(EncParams ep)
   // any thread's candidate will do when there is exactly one coded block (the only case the value is used in)
   __shared__ uint64_t hist_s;
   if (threadIdx.x == 0)
-    hist_s = 0;
+    hist_s = CARRIED ? carry->last_hist : 0;
   __syncthreads();
   if (my_last != kNone)
     atomicMax((unsigned long long *)&hist_s, (unsigned long long)my_last);
@@ -1367,26 +1374,53 @@ __device__ __forceinline__ void scan_images_body(EncParams ep)
   if (threadIdx.x == 0)
   {
     const uint64_t total = bytes_before;
-    ep.result[0] = total;
-    ep.result[1] = total <= ep.out_cap ? 1 : 0;
-    if (ep.fits)
-      *ep.fits = total <= ep.out_cap ? 1 : 0;
-    ep.result[2] = chains_before;
-    ep.result[3] = coded_blocks;
-    ep.result[4] = last_hist;
-    if (total <= ep.out_cap)
+    if constexpr (CARRIED)
     {
-      ((uint64_t *)ep.out)[0] = ep.n;
-      ((uint64_t *)ep.out)[1] = total;
+      const uint32_t b = ep.n_blocks - 1;
+      const uint64_t bytes = ep.image_bytes[b];
+      if (last_slice == 0 && bytes != 8)
+      {
+        U64a2 *skip = (U64a2 *)(ep.scratch + (uint64_t)(b + 1) * ep.slot_bytes - bytes + 8);
+        skip->v = skip->v + 1;
+      }
+      carry->bytes_before = total;
+      carry->chains_before = chains_before;
+      carry->coded_blocks = coded_blocks;
+      carry->last_hist = last_hist;
+      ep.result[0] = total;
+      ep.result[1] = 1;
+      ep.result[2] = chains_before;
+      ep.result[3] = coded_blocks;
+      ep.result[4] = last_hist;
+      ep.result[5] = slice_base;
+    }
+    else
+    {
+      ep.result[0] = total;
+      ep.result[1] = total <= ep.out_cap ? 1 : 0;
+      if (ep.fits)
+        *ep.fits = total <= ep.out_cap ? 1 : 0;
+      ep.result[2] = chains_before;
+      ep.result[3] = coded_blocks;
+      ep.result[4] = last_hist;
+      if (total <= ep.out_cap)
+      {
+        ((uint64_t *)ep.out)[0] = ep.n;
+        ((uint64_t *)ep.out)[1] = total;
+      }
     }
   }
 }
 __global__ void __launch_bounds__(1024) k_scan_images(EncParams ep) { scan_images_body(ep); }
+__global__ void __launch_bounds__(1024) k_scan_images_carried(EncParams ep, EncCarry *carry, uint32_t last_slice) { scan_images_body<true>(ep, carry, last_slice); }
 
 // ---- K_plan: the sidecar plan of the stream (hsrans_plan.h), one wavefront per block --------------------------------
 // Writes exactly what the host encoder emits for the same layout (hsrans_host.cpp encode(), "sidecar plan"): single-piece
 // chains in output order — per coded block one chain from the block header's states plus one per checkpoint, per
 // single-symbol block one fill chain — and the Group records of the grouped decode launch (one group per block).
+// HEADS (hsrans_encode_host_pipelined): the images are gone from ep.scratch by the time the plan is written; what the plan reads of
+// them — a coded block's first 16 + 4 S bytes, a single-symbol block's 8-byte marker — was kept by K_gather at ep.scratch + b (16 + 4 S).
+template <bool HEADS = false>
 __device__ __forceinline__ void plan_blocks_body(EncParams ep, const uint32_t b)
 {
   const uint32_t lane = threadIdx.x, S = ep.S;
@@ -1402,7 +1436,7 @@ __device__ __forceinline__ void plan_blocks_body(EncParams ep, const uint32_t b)
   const uint64_t header = 16 + 4 * (uint64_t)S + 512;
   const uint64_t hist_off = at + 16 + 4 * (uint64_t)S;
   const uint64_t whole_file = ep.n / S; // whole groups of the file (rANS32x64_16w.cpp:220)
-  const uint8_t *image = ep.scratch + (uint64_t)(b + 1) * ep.slot_bytes - bytes;
+  const uint8_t *image = HEADS ? ep.scratch + (uint64_t)b * (16 + 4 * (uint64_t)S) : ep.scratch + (uint64_t)(b + 1) * ep.slot_bytes - bytes;
   if (b == 0 && lane == 0)
     chain_first[nc] = nc;
   for (uint32_t k = lane; k < count; k += 64)
@@ -1470,6 +1504,7 @@ __device__ __forceinline__ void plan_blocks_body(EncParams ep, const uint32_t b)
   }
 }
 __global__ void __launch_bounds__(64) k_plan_blocks(EncParams ep) { plan_blocks_body(ep, blockIdx.x); }
+__global__ void __launch_bounds__(64) k_plan_blocks_carried(EncParams ep) { plan_blocks_body<true>(ep, blockIdx.x); }
 
 // ---- K_gather: one workgroup per block image; source and destination are only 2-byte aligned -------------------------
 struct __attribute__((packed, aligned(2))) U128a2
@@ -1493,11 +1528,27 @@ __device__ __forceinline__ uint64_t wg_sum(uint64_t v, uint64_t *slot)
 // (13.5 us at 1,526 blocks) on the path of every encode.  Beyond it the reads grow with the square of the block count: K_scan again.
 constexpr uint32_t kSelfScanBlocks = kEncSelfScanBlocks;
 
-__device__ __forceinline__ void gather_images_body(EncParams ep, const uint32_t b)
+// CARRIED (hsrans_encode_host_pipelined): K_scan has run (k_scan_images_carried); the slice's images go to ep.out + (image_off[b] -
+// image_off[0]), the slice's own staging buffer, and with `heads` each block's first 16 + 4 S bytes (all of a single-symbol block's 8)
+// also to heads + b (16 + 4 S), for the plan written after the last slice (k_plan_blocks_carried)
+template <bool CARRIED = false>
+__device__ __forceinline__ void gather_images_body(EncParams ep, const uint32_t b, uint8_t *heads = nullptr)
 {
   const uint64_t bytes = ep.image_bytes[b];
   uint64_t off;
-  if (ep.n_blocks <= kSelfScanBlocks)
+  if constexpr (CARRIED)
+  {
+    off = ep.image_off[b] - ep.image_off[0];
+    if (heads != nullptr)
+    {
+      const uint64_t keep = 16 + 4 * (uint64_t)ep.S;
+      const uint8_t *src = ep.scratch + (uint64_t)(b + 1) * ep.slot_bytes - bytes;
+      uint8_t *dst = heads + (uint64_t)b * keep;
+      for (uint64_t i = threadIdx.x * 2; i < (bytes < keep ? bytes : keep); i += 512)
+        *(uint16_t *)(dst + i) = *(const uint16_t *)(src + i);
+    }
+  }
+  else if (ep.n_blocks <= kSelfScanBlocks)
   {
     __shared__ uint64_t red[5][4];
     uint64_t before = 0, total = 0, chains_before = 0, chains = 0, coded = 0;
@@ -1575,6 +1626,7 @@ __device__ __forceinline__ void gather_images_body(EncParams ep, const uint32_t 
     *(uint16_t *)(dst + k) = *(const uint16_t *)(src + k);
 }
 __global__ void __launch_bounds__(256) k_gather_images(EncParams ep) { gather_images_body(ep, blockIdx.x); }
+__global__ void __launch_bounds__(256) k_gather_images_carried(EncParams ep, uint8_t *heads) { gather_images_body<true>(ep, blockIdx.x, heads); }
 
 // the one image of a raw encode (the whole stream), copied by workgroups wg of n_wg (k_copy_image: the whole grid)
 __device__ __forceinline__ void copy_image_body(EncParams ep, const uint32_t wg, const uint32_t n_wg)
@@ -1771,7 +1823,10 @@ uint64_t encode_slot_bytes(uint64_t block, uint32_t S)
   return (need + 511) / 512 * 512; // (a multiple of the encoder's flush segment)
 }
 
-hipError_t launch_encode(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
+namespace
+{
+// K_hist -> K_enc of launch_encode and launch_encode_slice (the launches queued; errors are read by the caller)
+hipError_t launch_encode_blocks(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
 {
   bool local = false;
   bool &prepared = prepared_flag ? *prepared_flag : local;
@@ -1807,9 +1862,28 @@ hipError_t launch_encode(const EncParams &ep, hipStream_t stream, bool *prepared
     hipLaunchKernelGGL((k_encode_blocks<32, kChunkFew>), dim3(grid), dim3(64 * kWavesPerWG), lds, stream, ep);
   else
     hipLaunchKernelGGL((k_encode_blocks<32, kChunkMany>), dim3(grid), dim3(64 * kWavesPerWG), lds, stream, ep);
+  return hipSuccess;
+}
+} // namespace
+
+hipError_t launch_encode(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
+{
+  const hipError_t e = launch_encode_blocks(ep, stream, prepared_flag);
+  if (e != hipSuccess)
+    return e;
   if (ep.n_blocks > kSelfScanBlocks)
     hipLaunchKernelGGL(k_scan_images, dim3(1), dim3(1024), 0, stream, ep);
   hipLaunchKernelGGL(k_gather_images, dim3(ep.n_blocks), dim3(256), 0, stream, ep);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_slice(const EncParams &ep, EncCarry *carry, bool last_slice, uint8_t *heads, hipStream_t stream, bool *prepared_flag)
+{
+  const hipError_t e = launch_encode_blocks(ep, stream, prepared_flag);
+  if (e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(k_scan_images_carried, dim3(1), dim3(1024), 0, stream, ep, carry, last_slice ? 1u : 0u);
+  hipLaunchKernelGGL(k_gather_images_carried, dim3(ep.n_blocks), dim3(256), 0, stream, ep, heads);
   return hipGetLastError();
 }
 
@@ -1883,6 +1957,13 @@ hipError_t launch_encode_plan(const EncParams &ep, hipStream_t stream)
 {
   (void)hipGetLastError();
   hipLaunchKernelGGL(k_plan_blocks, dim3(ep.n_blocks), dim3(64), 0, stream, ep);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_plan_carried(const EncParams &ep, hipStream_t stream)
+{
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_plan_blocks_carried, dim3(ep.n_blocks), dim3(64), 0, stream, ep);
   return hipGetLastError();
 }
 

@@ -62,6 +62,8 @@ struct hsrans_ctx
   uint64_t *h_enc_result = nullptr; // page-locked, device-mapped: hsrans_encode_device's kernels write their result words straight into it (no copy kernel, no second launch gap); under `lock`
   uint8_t *h_pin = nullptr; // page-locked staging of hsrans_decode_device_indexing (checkpoints down, plan blob up); under `lock`
   size_t h_pin_cap = 0;
+  uint8_t *h_pipe_result = nullptr; // page-locked, device-mapped: hsrans_encode_host_pipelined's carry start and per-slice result words; under `lock`
+  size_t h_pipe_result_cap = 0;
 };
 
 // every device plan (and every refill of one) has a number of its own: what hsrans_queue keys its cached batches by — an address can come back
@@ -186,6 +188,25 @@ inline bool grow_pinned(uint8_t **p, size_t *cap, size_t need)
   *cap = 0;
   const size_t want = need + need / 4 + 65536;
   if (hipHostMalloc((void **)p, want, hipHostMallocDefault) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return false;
+  }
+  *cap = want;
+  return true;
+}
+
+// page-locked and mapped into the device's address space (hipHostGetDevicePointer)
+inline bool grow_pinned_mapped(uint8_t **p, size_t *cap, size_t need)
+{
+  if (need <= *cap)
+    return true;
+  if (*p)
+    (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need + need / 4 + 4096;
+  if (hipHostMalloc((void **)p, want, hipHostMallocMapped) != hipSuccess)
   {
     (void)hipGetLastError();
     return false;

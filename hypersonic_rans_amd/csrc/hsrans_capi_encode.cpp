@@ -1,5 +1,6 @@
 // hsrans_capi_encode.cpp — GPU encoder entries: hsrans_encode_device (mt_, one wavefront per block), hsrans_encode_device_raw,
-// hsrans_encode_device_ex (every format hsrans_encode_ex writes).
+// hsrans_encode_device_ex (every format hsrans_encode_ex writes); and the host side the batch and the host pipeline share with the
+// single calls (declared in hsrans_internal.h): argument rules and shapes, per-block arrays, plan assembly, kernel setup.
 // Part of the C ABI of libhsrans_hip.so (include/hsrans_hip.h); split out of hsrans_capi.cpp in round 5 by concern.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -18,6 +19,7 @@
 #include "hsrans_host.h"
 #include "hsrans_cpu.h"
 #include "hsrans_encode.h"
+#include "hsrans_index_groups.h"
 #include "hsrans_kernels.h"
 
 using namespace hsrans;
@@ -86,6 +88,172 @@ size_t copy_choices(const std::vector<BlockSpan> &spans, hsrans_block_choice *ou
 }
 } // namespace
 
+bool encoder_ready(hsrans_ctx *ctx)
+{
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return false;
+  if (!ctx->encoder_prepared && prepare_encode_kernels() == hipSuccess)
+    ctx->encoder_prepared = true;
+  return ctx->encoder_prepared;
+}
+
+EncParams EncShape::params(const void *d_in, void *d_out, size_t out_capacity) const
+{
+  EncParams ep{};
+  ep.S = S;
+  ep.bits = bits;
+  ep.in = (const uint8_t *)d_in;
+  ep.n = n;
+  ep.out = (uint8_t *)d_out;
+  ep.out_cap = out_capacity;
+  ep.block = block;
+  ep.n_blocks = n_blocks;
+  ep.slot_bytes = slot_bytes;
+  ep.interval = interval;
+  ep.max_ck = max_ck;
+  return ep;
+}
+
+bool raw_shape(int states, uint32_t bits, size_t length, size_t out_capacity, const hsrans_hist *hist, uint32_t index_interval, const uint64_t *index_groups,
+               size_t n_index_groups, bool plan, EncShape *sh)
+{
+  EncShape r;
+  r.listed = index_groups != nullptr && n_index_groups != 0;
+  if (!valid_codec(HSRANS_RAW, states, bits) || length == 0 || length > 0x7FFF0000ull || index_interval % 4 != 0 || // (byte offsets inside the slot are 32-bit)
+      out_capacity < capacity(HSRANS_RAW, states, length) || (r.listed && (n_index_groups > 0x7FFFFFFFull || !index_groups_valid(index_groups, n_index_groups))))
+    return false;
+  if (hist != nullptr)
+  {
+    uint32_t sum = 0;
+    for (int k = 0; k < 256; k++)
+      sum += hist->symbolCount[k];
+    if (sum != (1u << bits))
+      return false;
+  }
+  r.S = (uint32_t)states;
+  r.bits = bits;
+  r.n = r.block = length;
+  r.want_plan = plan && (r.listed || index_interval != 0);
+  // checkpoints the pass will record: interval -> group (k + 1) * interval; list -> the entries below the last whole group
+  const uint64_t whole_groups = length / r.S;
+  if (r.want_plan && r.listed)
+    while (r.n_ck < n_index_groups && index_groups[r.n_ck] < whole_groups)
+      r.n_ck++;
+  else if (r.want_plan)
+    r.n_ck = whole_groups >= 1 ? (size_t)((whole_groups - 1) / index_interval) : 0;
+  r.slot_bytes = encode_slot_bytes(length, r.S);
+  r.interval = r.want_plan && !r.listed ? index_interval : 0;
+  r.max_ck = (uint32_t)r.n_ck;
+  r.ck_slots = r.n_ck ? r.n_ck : 1;
+  *sh = r;
+  return true;
+}
+
+bool mt_shape(int states, uint32_t bits, size_t length, size_t out_capacity, uint32_t block_size, uint32_t index_interval, bool plan, EncShape *sh)
+{
+  if (!valid_codec(HSRANS_MT, states, bits) || length == 0 || block_size == 0 || block_size % 64 != 0 || block_size > (1u << 30) || index_interval % 4 != 0 ||
+      out_capacity < capacity(HSRANS_MT, states, length)) // (same contract as the host encoders)
+    return false;
+  EncShape r;
+  r.S = (uint32_t)states;
+  r.bits = bits;
+  r.n = length;
+  r.block = block_size;
+  r.n_blocks = encode_block_count(length, block_size, r.S);
+  if (r.n_blocks == 0)
+    return false;
+  r.slot_bytes = encode_slot_bytes(block_size, r.S);
+  r.interval = plan ? index_interval : 0; // checkpoints only serve the plan
+  r.max_ck = r.interval ? (block_size / r.S - 1) / r.interval : 0;
+  r.ck_slots = (size_t)r.n_blocks * (r.max_ck ? r.max_ck : 1);
+  *sh = r;
+  return true;
+}
+
+size_t mt_block_arrays_bytes(uint32_t n_blocks) { return ((size_t)n_blocks * 24 + 15) / 16 * 16 + 16 + (size_t)n_blocks * 1024; }
+
+void mt_block_arrays(EncParams *ep, uint8_t *at)
+{
+  const size_t nb = ep->n_blocks;
+  ep->image_bytes = (uint64_t *)at;
+  ep->image_off = ep->image_bytes + nb;
+  ep->chain_count = (uint32_t *)(ep->image_off + nb);
+  ep->chain_off = ep->chain_count + nb;
+  ep->fits = (uint64_t *)(at + (nb * 24 + 15) / 16 * 16);
+  ep->raw_counts = (const uint32_t *)(ep->fits + 2);
+}
+
+bool mt_result_header(const EncParams &ep, const uint64_t *result, PlanHeader *h)
+{
+  if (result[2] == 0 || result[2] > 0xFFFFFFFFull)
+    return false;
+  *h = mt_plan_header(ep.S, ep.bits, ep.n, result[0], (uint32_t)result[2]);
+  h->shared_hist = result[3] == 1 ? 1 : 0; // exactly one block with a histogram (hsrans_host.cpp PlanBuilder::serialize)
+  h->aux_off = h->shared_hist ? result[4] : 0;
+  h->interval = ep.interval;
+  return true;
+}
+
+namespace
+{
+// the plan is decoded by the grouped launch (blocks with checkpoints), for which K_plan writes the group list
+bool mt_grouped(const EncParams &ep, const PlanHeader &h) { return ep.interval != 0 && ep.n_blocks < h.n_chains; }
+} // namespace
+
+hsrans_dplan *mt_plan_begin(hsrans_ctx *ctx, EncParams *ep, const uint64_t *result, PlanHeader *h, hipStream_t s)
+{
+  hsrans_dplan *d = mt_result_header(*ep, result, h) ? dplan_new(ctx) : nullptr;
+  if (d == nullptr)
+    return nullptr;
+  const bool grouped = mt_grouped(*ep, *h);
+  // few large blocks: every block's chains in parts (every coded block but the last has max_ck + 1 chains; at most 64 parts a block)
+  ep->group_split = grouped ? group_parts_of(ep->max_ck + 1, std::min(group_parts_max(ctx->geom, ep->n_blocks), 64u)) : 1;
+  // ONE device allocation for the status word, the ticket counters of the dynamic group order (as dplan_fill; without them the launch
+  // falls back to the static order), the plan and the group list, one memset over the first three, one synchronisation (round 4:
+  // up to four hipMalloc, three memsets, three synchronisations — 0.14 ms on top of a 0.2 ms encode)
+  DplanRegions r;
+  r.counters = grouped;
+  r.plan = (size_t)plan_size(h->n_chains, h->n_pieces, h->states, 0);
+  r.groups = grouped ? (size_t)ep->n_blocks * ep->group_split * sizeof(Group) : 0;
+  r.zero = kZeroThroughPlan;
+  if (dplan_arena(d, r, s) != HSRANS_OK || hipMemcpyAsync(d->d_plan, h, sizeof(*h), hipMemcpyHostToDevice, s) != hipSuccess)
+  {
+    hsrans_dplan_destroy(d);
+    return nullptr;
+  }
+  ep->plan = d->d_plan;
+  ep->groups = d->d_groups;
+  ep->n_chains = h->n_chains;
+  return d;
+}
+
+void mt_plan_adopt(hsrans_dplan *d, const EncParams &ep, const PlanHeader &h, hipStream_t s)
+{
+  dplan_adopt(d, h, mt_grouped(ep, h) ? ep.n_blocks * ep.group_split : 0, ep.max_ck + 1, s);
+}
+
+size_t raw_plan(hsrans_ctx *ctx, const EncShape &sh, uint64_t total, const uint64_t *index_groups, const uint8_t *header, const uint32_t *ck_states,
+                const uint32_t *ck_pos, uint8_t *plan_out, size_t plan_capacity, size_t *plan_size, hsrans_dplan **out_dplan)
+{
+  std::vector<uint64_t> ck_group(sh.n_ck), ck_wfe(sh.n_ck);
+  for (size_t k = 0; k < sh.n_ck; k++)
+  {
+    ck_group[k] = sh.listed ? index_groups[k] : (uint64_t)(k + 1) * sh.interval;
+    ck_wfe[k] = ck_pos[k];
+  }
+  std::vector<uint8_t> own(plan_out ? 0 : plan_capacity_chains(HSRANS_RAW, (int)sh.S, sh.n, sh.n_ck, 0));
+  uint8_t *blob = plan_out ? plan_out : own.data();
+  const size_t psize = raw_plan_from_checkpoints((int)sh.S, sh.bits, sh.n, total, (const uint16_t *)(header + 16), (const uint32_t *)(header + 16 + 512), sh.n_ck,
+                                                 ck_group.data(), ck_wfe.data(), ck_states, sh.interval, blob, plan_out ? plan_capacity : own.size());
+  if (psize == 0)
+    return 0;
+  if (plan_size)
+    *plan_size = psize;
+  if (out_dplan != nullptr && hsrans_dplan_create(ctx, blob, psize, out_dplan) != HSRANS_OK)
+    return 0;
+  return psize;
+}
+
 extern "C"
 {
 
@@ -135,67 +303,22 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
     *out_dplan = nullptr;
   if (plan_size)
     *plan_size = 0;
-  if (ctx == nullptr || !valid_codec(HSRANS_RAW, states, bits) || d_in == nullptr || d_out == nullptr || length == 0)
+  EncShape sh;
+  if (ctx == nullptr || !device_io_ok(d_in, d_out) || (plan_out != nullptr && plan_size == nullptr) ||
+      !raw_shape(states, bits, length, out_capacity, hist, index_interval, index_groups, n_index_groups, plan_out != nullptr || out_dplan != nullptr, &sh))
     return 0;
-  if (length > 0x7FFF0000ull || index_interval % 4 != 0 || ((uintptr_t)d_in & 15) != 0 || ((uintptr_t)d_out & 15) != 0) // (byte offsets inside the slot are 32-bit)
-    return 0;
-  if (out_capacity < capacity(HSRANS_RAW, states, length))
-    return 0;
-  const uint32_t S = (uint32_t)states;
-  const bool listed = index_groups != nullptr && n_index_groups != 0;
-  const bool want_plan = (plan_out != nullptr || out_dplan != nullptr) && (listed || index_interval != 0);
-  if (plan_out != nullptr && plan_size == nullptr)
-    return 0;
-  if (listed)
-  {
-    if (n_index_groups > 0x7FFFFFFFull)
-      return 0;
-    for (size_t k = 0; k < n_index_groups; k++) // (the host encoder's rule)
-      if (index_groups[k] == 0 || (index_groups[k] % 4) != 0 || (k > 0 && index_groups[k] <= index_groups[k - 1]))
-        return 0;
-  }
-  if (hist != nullptr)
-  {
-    uint32_t sum = 0;
-    for (int k = 0; k < 256; k++)
-      sum += hist->symbolCount[k];
-    if (sum != (1u << bits))
-      return 0;
-  }
-  const uint64_t whole_groups = length / S;
-  // checkpoints the pass will record: interval -> group (k + 1) * interval; list -> the entries below the last whole group
-  size_t n_ck = 0;
-  std::vector<uint32_t> groups32;
-  if (want_plan && listed)
-  {
-    while (n_ck < n_index_groups && index_groups[n_ck] < whole_groups)
-      n_ck++;
-    groups32.resize(n_ck);
-    for (size_t k = 0; k < n_ck; k++)
-      groups32[k] = (uint32_t)index_groups[k];
-  }
-  else if (want_plan)
-    n_ck = whole_groups >= 1 ? (size_t)((whole_groups - 1) / index_interval) : 0;
-  EncParams ep{};
-  ep.S = S;
-  ep.bits = bits;
-  ep.n = length;
-  ep.block = length;
-  ep.n_blocks = 1;
-  ep.slot_bytes = encode_slot_bytes(length, S);
-  ep.interval = want_plan && !listed ? index_interval : 0;
-  ep.max_ck = (uint32_t)n_ck;
+  const size_t n_ck = sh.n_ck;
+  std::vector<uint32_t> groups32(sh.want_plan && sh.listed ? n_ck : 0);
+  for (size_t k = 0; k < groups32.size(); k++)
+    groups32[k] = (uint32_t)index_groups[k];
+  EncParams ep = sh.params(d_in, d_out, out_capacity);
   std::lock_guard<std::mutex> guard(ctx->lock);
-  if (hipSetDevice(ctx->device) != hipSuccess)
+  if (!encoder_ready(ctx))
     return 0;
   const size_t meta_bytes = (2 + kEncResultWords + 4) * 8 + 256 * 4 + 256 * 2 + n_ck * 4 + 64;
-  const size_t ck_slots = n_ck ? n_ck : 1;
   if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, ep.slot_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta_bytes) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck_slots * ((size_t)S * 4 + 4)))
+      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, sh.ck_slots * ((size_t)sh.S * 4 + 4)))
     return 0;
-  ep.in = (const uint8_t *)d_in;
-  ep.out = (uint8_t *)d_out;
-  ep.out_cap = out_capacity;
   ep.scratch = ctx->d_enc_scratch;
   ep.image_bytes = (uint64_t *)ctx->d_enc_meta;
   ep.image_off = ep.image_bytes + 1;
@@ -206,10 +329,10 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
   uint32_t *d_groups = (uint32_t *)(d_given + 256);
   ep.raw_counts = d_counts;
   ep.given_counts = hist ? d_given : nullptr;
-  ep.ck_groups = want_plan && listed && n_ck ? d_groups : nullptr;
-  ep.n_ck_groups = ep.ck_groups ? (uint32_t)n_ck : 0;
+  ep.ck_groups = groups32.empty() ? nullptr : d_groups;
+  ep.n_ck_groups = (uint32_t)groups32.size();
   ep.ck_states = (uint32_t *)ctx->d_enc_ck;
-  ep.ck_pos = ep.ck_states + ck_slots * S;
+  ep.ck_pos = ep.ck_states + sh.ck_slots * sh.S;
   hipStream_t s = (hipStream_t)hip_stream;
   uint64_t result[kEncResultWords] = {};
   bool ok = true;
@@ -217,8 +340,7 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
     ok = hipMemcpyAsync(d_given, hist->symbolCount, 512, hipMemcpyHostToDevice, s) == hipSuccess;
   if (ok && ep.ck_groups)
     ok = hipMemcpyAsync(d_groups, groups32.data(), n_ck * 4, hipMemcpyHostToDevice, s) == hipSuccess;
-  ok = ok && launch_encode_raw(ep, d_counts, s, &ctx->enc_raw_prepared) == hipSuccess &&
-       hipMemcpyAsync(result, ep.result, sizeof(result), hipMemcpyDeviceToHost, s) == hipSuccess;
+  ok = ok && launch_encode_raw(ep, d_counts, s) == hipSuccess && hipMemcpyAsync(result, ep.result, sizeof(result), hipMemcpyDeviceToHost, s) == hipSuccess;
   if (hipStreamSynchronize(s) != hipSuccess || !ok) // (groups32 / *hist may be read until here)
   {
     (void)hipGetLastError();
@@ -233,43 +355,18 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
   if (result[1] != 1 || result[2] != 0)
     return 0;
   const size_t total = (size_t)result[0];
-  if (!want_plan)
+  if (!sh.want_plan)
     return total;
 
   // ---- the sidecar plan: checkpoints and the stream's header come down (2.1 MB for the one-chain-per-wavefront index), the host
-  // assembles exactly what hsrans_encode_ex emits (raw_plan_from_checkpoints is that code) ----
-  const size_t header_bytes = 16 + 512 + 4 * (size_t)S;
-  std::vector<uint8_t> header(header_bytes);
-  std::vector<uint32_t> ck_states(n_ck * S), ck_pos(n_ck);
-  std::vector<uint64_t> ck_group(n_ck), ck_wfe(n_ck);
-  if (hipMemcpy(header.data(), d_out, header_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-      (n_ck && (hipMemcpy(ck_states.data(), ep.ck_states, n_ck * S * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+  // assembles exactly what hsrans_encode_ex emits ----
+  std::vector<uint8_t> header(16 + 512 + 4 * (size_t)sh.S);
+  std::vector<uint32_t> ck_states(n_ck * sh.S), ck_pos(n_ck);
+  if (hipMemcpy(header.data(), d_out, header.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+      (n_ck && (hipMemcpy(ck_states.data(), ep.ck_states, n_ck * sh.S * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                 hipMemcpy(ck_pos.data(), ep.ck_pos, n_ck * 4, hipMemcpyDeviceToHost) != hipSuccess)))
     return 0;
-  for (size_t k = 0; k < n_ck; k++)
-  {
-    ck_group[k] = listed ? index_groups[k] : (uint64_t)(k + 1) * index_interval;
-    ck_wfe[k] = ck_pos[k];
-  }
-  const size_t pcap = plan_capacity_chains(HSRANS_RAW, states, length, n_ck, 0);
-  std::vector<uint8_t> own;
-  uint8_t *blob = plan_out;
-  size_t cap = plan_capacity;
-  if (blob == nullptr)
-  {
-    own.resize(pcap);
-    blob = own.data();
-    cap = own.size();
-  }
-  const size_t psize = raw_plan_from_checkpoints(states, bits, length, total, (const uint16_t *)(header.data() + 16), (const uint32_t *)(header.data() + 16 + 512), n_ck,
-                                                 ck_group.data(), ck_wfe.data(), ck_states.data(), listed ? 0 : index_interval, blob, cap);
-  if (psize == 0)
-    return 0;
-  if (plan_size)
-    *plan_size = psize;
-  if (out_dplan != nullptr && hsrans_dplan_create(ctx, blob, psize, out_dplan) != HSRANS_OK)
-    return 0;
-  return total;
+  return raw_plan(ctx, sh, total, index_groups, header.data(), ck_states.data(), ck_pos.data(), plan_out, plan_capacity, plan_size, out_dplan) ? total : 0;
 }
 
 size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity,
@@ -279,40 +376,22 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
     return hsrans_encode_device_raw(ctx, states, bits, d_in, length, d_out, out_capacity, nullptr, index_interval, nullptr, 0, nullptr, 0, nullptr, hip_stream, out_dplan);
   if (out_dplan)
     *out_dplan = nullptr;
-  if (ctx == nullptr || container != HSRANS_MT || !valid_codec(container, states, bits) || d_in == nullptr || d_out == nullptr || length == 0)
+  EncShape sh;
+  if (ctx == nullptr || container != HSRANS_MT || !device_io_ok(d_in, d_out) ||
+      !mt_shape(states, bits, length, out_capacity, block_size, index_interval, out_dplan != nullptr, &sh))
     return 0;
-  if (block_size == 0 || block_size % 64 != 0 || block_size > (1u << 30) || index_interval % 4 != 0 || ((uintptr_t)d_in & 15) != 0 || ((uintptr_t)d_out & 15) != 0)
-    return 0;
-  if (out_capacity < capacity(container, states, length)) // same contract as the host encoders
-    return 0;
-  EncParams ep{};
-  ep.S = (uint32_t)states;
-  ep.bits = bits;
-  ep.n = length;
-  ep.block = block_size;
-  ep.n_blocks = encode_block_count(length, block_size, ep.S);
-  if (ep.n_blocks == 0)
-    return 0;
-  ep.slot_bytes = encode_slot_bytes(block_size, ep.S);
-  ep.interval = out_dplan ? index_interval : 0; // checkpoints only serve the plan
-  ep.max_ck = ep.interval ? (block_size / ep.S - 1) / ep.interval : 0;
+  EncParams ep = sh.params(d_in, d_out, out_capacity);
   std::lock_guard<std::mutex> guard(ctx->lock);
-  if (hipSetDevice(ctx->device) != hipSuccess)
+  if (!encoder_ready(ctx))
     return 0;
   const bool stamps = ctx->tuning.debug_stamps;
-  const size_t nb = ep.n_blocks;
-  const bool wide_hist = true; // (false: the coding wavefront counts its own block, as in rounds 1-3: 29.5 us per 64 KiB block — one wavefront's LDS atomics — against 23.5 us for the whole input by K_hist; the knob is gone)
-  const size_t meta_bytes = (nb * 2 + kEncResultWords) * 8 + nb * 2 * 4 + (stamps ? nb * 4 * 8 : 0) + 64 + (wide_hist ? nb * 1024 + 16 : 0);
-  const size_t ck_slots = nb * (ep.max_ck ? ep.max_ck : 1);
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, nb * ep.slot_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta_bytes) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck_slots * ((size_t)ep.S * 4 + 4)))
+  const size_t nb = ep.n_blocks, arrays = mt_block_arrays_bytes(ep.n_blocks);
+  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, nb * ep.slot_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, arrays + (stamps ? nb * 4 * 8 : 0)) ||
+      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, sh.ck_slots * ((size_t)sh.S * 4 + 4)))
     return 0;
-  ep.in = (const uint8_t *)d_in;
-  ep.out = (uint8_t *)d_out;
-  ep.out_cap = out_capacity;
   ep.scratch = ctx->d_enc_scratch;
-  ep.image_bytes = (uint64_t *)ctx->d_enc_meta;
-  ep.image_off = ep.image_bytes + nb;
+  mt_block_arrays(&ep, ctx->d_enc_meta);
+  ep.stamps = stamps ? (uint64_t *)(ctx->d_enc_meta + arrays) : nullptr;
   // the result words land in page-locked host memory the kernels write directly (the stream is synchronised before they are read)
   if (ctx->h_enc_result == nullptr && hipHostMalloc((void **)&ctx->h_enc_result, kEncResultWords * 8, hipHostMallocMapped) != hipSuccess)
   {
@@ -323,19 +402,11 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
   if (hipHostGetDevicePointer(&d_result, ctx->h_enc_result, 0) != hipSuccess)
     return 0;
   ep.result = (uint64_t *)d_result;
-  ep.fits = ep.image_off + nb;
-  uint64_t *after = ep.image_off + nb + kEncResultWords; // (the words' old place in the meta buffer stays reserved)
-  ep.stamps = stamps ? after : nullptr;
-  after += stamps ? nb * 4 : 0;
-  ep.chain_count = (uint32_t *)after;
-  ep.chain_off = ep.chain_count + nb;
-  if (wide_hist)
-    ep.raw_counts = (const uint32_t *)(((uintptr_t)(ep.chain_off + nb) + 15) & ~(uintptr_t)15);
   ep.ck_states = (uint32_t *)ctx->d_enc_ck;
-  ep.ck_pos = ep.ck_states + ck_slots * ep.S;
+  ep.ck_pos = ep.ck_states + sh.ck_slots * sh.S;
   hipStream_t s = (hipStream_t)hip_stream;
   uint64_t result[kEncResultWords] = {};
-  if (launch_encode(ep, s, &ctx->enc_prepared) != hipSuccess)
+  if (launch_encode(ep, ctx->geom.num_cus, s) != hipSuccess)
     return 0;
   if (hipStreamSynchronize(s) != hipSuccess)
     return 0;
@@ -374,40 +445,16 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
     return total;
 
   // ---- the stream's plan, written on the device (K_plan), wrapped into a device plan ready for hsrans_decode_device ----
-  if (result[2] == 0 || result[2] > 0xFFFFFFFFull)
-    return 0;
-  hsrans_dplan *d = dplan_new(ctx);
+  PlanHeader h;
+  hsrans_dplan *d = mt_plan_begin(ctx, &ep, result, &h, s);
   if (d == nullptr)
     return 0;
-  PlanHeader h = mt_plan_header(ep.S, bits, length, total, (uint32_t)result[2]);
-  h.shared_hist = result[3] == 1 ? 1 : 0; // exactly one block with a histogram (hsrans_host.cpp PlanBuilder::serialize)
-  h.aux_off = h.shared_hist ? result[4] : 0;
-  h.interval = ep.interval;
-  const bool grouped = ep.interval != 0 && ep.n_blocks < h.n_chains;
-  // few large blocks: every block's chains in parts (every coded block but the last has max_ck + 1 chains; at most 64 parts a block)
-  ep.group_split = grouped ? group_parts_of(ep.max_ck + 1, std::min(group_parts_max(ctx->geom, nb), 64u)) : 1;
-  // ONE device allocation for the status word, the ticket counters of the dynamic group order (as dplan_fill; without them the launch
-  // falls back to the static order), the plan and the group list, one memset over the first three, one synchronisation (round 4:
-  // up to four hipMalloc, three memsets, three synchronisations — 0.14 ms on top of a 0.2 ms encode)
-  DplanRegions r;
-  r.counters = grouped;
-  r.plan = (size_t)plan_size(h.n_chains, h.n_pieces, h.states, 0);
-  r.groups = grouped ? nb * ep.group_split * sizeof(Group) : 0;
-  r.zero = kZeroThroughPlan;
-  bool ok = dplan_arena(d, r, s) == HSRANS_OK && hipMemcpyAsync(d->d_plan, &h, sizeof(h), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (ok)
-  {
-    ep.plan = d->d_plan;
-    ep.groups = d->d_groups;
-    ep.n_chains = h.n_chains;
-    ok = launch_encode_plan(ep, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-  }
-  if (!ok)
+  if (launch_encode_plan(ep, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
   {
     hsrans_dplan_destroy(d);
     return 0;
   }
-  dplan_adopt(d, h, grouped ? ep.n_blocks * ep.group_split : 0, ep.max_ck + 1, s);
+  mt_plan_adopt(d, ep, h, s);
   *out_dplan = d;
   return total;
 }
@@ -435,11 +482,8 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
   const size_t n_ig = ig ? opts->n_index_groups : 0;
   const uint32_t interval = ig ? 0 : (opts ? opts->index_interval : 0);
   const bool want_plan = interval != 0 || ig != nullptr;
-  if (want_plan && ((interval % 4) != 0 || opts->plan_out == nullptr))
+  if ((want_plan && ((interval % 4) != 0 || opts->plan_out == nullptr)) || !index_groups_valid(ig, n_ig))
     return 0;
-  for (size_t k = 0; k < n_ig; k++)
-    if (ig[k] == 0 || (ig[k] % 4) != 0 || (k > 0 && ig[k] <= ig[k - 1]))
-      return 0;
   const bool fixed = opts && opts->block_size != 0;
   const bool independent = opts && (opts->flags & HSRANS_ENC_INDEPENDENT_BLOCKS) != 0;
   if (independent && (container != HSRANS_MT || !fixed))
@@ -475,7 +519,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
     return 0;
 
   std::lock_guard<std::mutex> guard(ctx->lock);
-  if (hipSetDevice(ctx->device) != hipSuccess)
+  if (!encoder_ready(ctx))
     return 0;
   hipStream_t s = (hipStream_t)hip_stream;
   const bool stamps = ctx->tuning.debug_stamps;
@@ -581,7 +625,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
   bool ok = hipMemcpyAsync((void *)ep.chain_blocks, cb.data(), nb * sizeof(ChainBlock), hipMemcpyHostToDevice, s) == hipSuccess &&
             hipMemcpyAsync((void *)ep.given_counts, counts.data(), nb * 512, hipMemcpyHostToDevice, s) == hipSuccess &&
             (ck_list.empty() || hipMemcpyAsync((void *)ep.ck_groups, ck_list.data(), ck_list.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess) &&
-            launch_encode_chain(ep, s, &ctx->enc_chain_prepared) == hipSuccess &&
+            launch_encode_chain(ep, s) == hipSuccess &&
             hipMemcpyAsync(result, ep.result, sizeof(result), hipMemcpyDeviceToHost, s) == hipSuccess;
   if (hipStreamSynchronize(s) != hipSuccess || !ok) // (cb / counts / ck_list may be read until here)
   {

@@ -1,8 +1,9 @@
 // hsrans_capi_encode_batch.cpp — hsrans_encode_device_batch: many independent raw / mt_ streams encoded by one launch per kernel kind.
 // Part of the C ABI of libhsrans_hip.so (include/hsrans_hip.h).  Every member is what its single call (hsrans_encode_device_raw,
-// hsrans_encode_device in hsrans_capi_encode.cpp) would make: the same checks, the same EncParams, the same per-wave code
-// (hsrans_encode.hip encode_body and the bodies of the single calls' kernels); only where the parameters live changes — one record
-// per member in device memory, and a task list that maps each workgroup to its member and block.
+// hsrans_encode_device in hsrans_capi_encode.cpp) would make, through the same code: the same rules and shape (raw_shape, mt_shape), the
+// same per-block arrays (mt_block_arrays), the same plan assembly (raw_plan; mt_plan_begin / mt_plan_adopt around K_plan) and the same
+// per-wave code (hsrans_encode.hip encode_body and the bodies of the single calls' kernels); only where the parameters live changes —
+// one record per member in device memory, and a task list that maps each workgroup to its member and block.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -28,83 +29,26 @@ constexpr uint64_t kRawPartBytes = 1 << 16; // input bytes per workgroup of the 
 constexpr uint32_t kRawMaxParts = 4096;
 constexpr size_t kMaxTasks = (size_t)1 << 24; // mt_ blocks of all members, and raw histogram / copy workgroups
 
-// what the host knows of a member before launch (the single calls' own derivations)
-struct Member
+// what the host knows of a member before launch: its single call's shape, and where the batch puts its parts
+struct Member : EncShape
 {
   bool raw = false;
-  uint32_t S = 0;
-  uint64_t slot_bytes = 0; // per block (raw: the one slot)
-  uint32_t n_blocks = 1;
-  uint32_t interval = 0;   // EncParams::interval
-  uint32_t max_ck = 0;     // EncParams::max_ck
-  size_t ck_slots = 1;
-  // raw
-  bool want_plan = false, listed = false;
-  size_t n_ck = 0;
-  uint32_t parts = 0;
-  // carving
+  uint32_t parts = 0; // raw: histogram / copy workgroups
   size_t scratch_at = 0, ck_at = 0, header_at = 0, given_at = 0, groups_at = 0, meta_at = 0;
 };
 
-// the single calls' argument rules (hsrans_encode_device_raw, hsrans_encode_device), plus the batch's own: fields of the other container unset
+// the single calls' argument rules (raw_shape, mt_shape), plus the batch's own: fields of the other container unset, no range that wraps
 bool check_member(const hsrans_encode_member &m, bool want_dplan, Member *out)
 {
-  Member r;
-  if (!valid_codec(m.container, m.states, m.bits) || m.d_in == nullptr || m.d_out == nullptr || m.length == 0 || m.index_interval % 4 != 0 ||
-      ((uintptr_t)m.d_in & 15) != 0 || ((uintptr_t)m.d_out & 15) != 0 || m.out_capacity < capacity(m.container, m.states, m.length) ||
-      (uintptr_t)m.d_in + m.length < (uintptr_t)m.d_in || (uintptr_t)m.d_out + m.out_capacity < (uintptr_t)m.d_out)
+  if (!device_io_ok(m.d_in, m.d_out) || (uintptr_t)m.d_in + m.length < (uintptr_t)m.d_in || (uintptr_t)m.d_out + m.out_capacity < (uintptr_t)m.d_out)
     return false;
-  r.S = (uint32_t)m.states;
-  if (m.container == HSRANS_RAW)
-  {
-    if (m.block_size != 0 || m.length > 0x7FFF0000ull)
-      return false;
-    r.raw = true;
-    r.listed = m.index_groups != nullptr && m.n_index_groups != 0;
-    if (r.listed)
-    {
-      if (m.n_index_groups > 0x7FFFFFFFull)
-        return false;
-      for (size_t k = 0; k < m.n_index_groups; k++)
-        if (m.index_groups[k] == 0 || (m.index_groups[k] % 4) != 0 || (k > 0 && m.index_groups[k] <= m.index_groups[k - 1]))
-          return false;
-    }
-    if (m.hist != nullptr)
-    {
-      uint32_t sum = 0;
-      for (int k = 0; k < 256; k++)
-        sum += m.hist->symbolCount[k];
-      if (sum != (1u << m.bits))
-        return false;
-    }
-    r.want_plan = want_dplan && (r.listed || m.index_interval != 0);
-    const uint64_t whole_groups = m.length / r.S;
-    if (r.want_plan && r.listed)
-      while (r.n_ck < m.n_index_groups && m.index_groups[r.n_ck] < whole_groups)
-        r.n_ck++;
-    else if (r.want_plan)
-      r.n_ck = whole_groups >= 1 ? (size_t)((whole_groups - 1) / m.index_interval) : 0;
-    r.slot_bytes = encode_slot_bytes(m.length, r.S);
-    r.interval = r.want_plan && !r.listed ? m.index_interval : 0;
-    r.max_ck = (uint32_t)r.n_ck;
-    r.ck_slots = r.n_ck ? r.n_ck : 1;
-    r.parts = (uint32_t)std::min<uint64_t>((m.length + kRawPartBytes - 1) / kRawPartBytes, kRawMaxParts);
-  }
-  else if (m.container == HSRANS_MT)
-  {
-    if (m.block_size == 0 || m.block_size % 64 != 0 || m.block_size > (1u << 30) || m.hist != nullptr || m.index_groups != nullptr || m.n_index_groups != 0)
-      return false;
-    r.n_blocks = encode_block_count(m.length, m.block_size, r.S);
-    if (r.n_blocks == 0)
-      return false;
-    r.slot_bytes = encode_slot_bytes(m.block_size, r.S);
-    r.interval = want_dplan ? m.index_interval : 0; // checkpoints only serve the plan
-    r.max_ck = r.interval ? (m.block_size / r.S - 1) / r.interval : 0;
-    r.ck_slots = (size_t)r.n_blocks * (r.max_ck ? r.max_ck : 1);
-  }
-  else
+  out->raw = m.container == HSRANS_RAW;
+  if (!out->raw)
+    return m.container == HSRANS_MT && m.hist == nullptr && m.index_groups == nullptr && m.n_index_groups == 0 &&
+           mt_shape(m.states, m.bits, m.length, m.out_capacity, m.block_size, m.index_interval, want_dplan, out);
+  if (m.block_size != 0 || !raw_shape(m.states, m.bits, m.length, m.out_capacity, m.hist, m.index_interval, m.index_groups, m.n_index_groups, want_dplan, out))
     return false;
-  *out = r;
+  out->parts = (uint32_t)std::min<uint64_t>((m.length + kRawPartBytes - 1) / kRawPartBytes, kRawMaxParts);
   return true;
 }
 
@@ -128,7 +72,6 @@ bool ranges_disjoint(const hsrans_encode_member *members, uint32_t count)
   return true;
 }
 
-size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 } // namespace
 
 extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member *members, uint32_t count, void *hip_stream, hsrans_dplan **out_dplans,
@@ -200,7 +143,7 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   //       [zeroed: result words (8 per member) | raw counts (256 per raw member)] [per member: image sizes / offsets, chain counts, block counts]
   size_t scratch_bytes = 0, ck_bytes = 0, meta = 0;
   auto take = [](size_t *at, size_t bytes, size_t align) {
-    *at = up(*at, align);
+    *at = (*at + align - 1) / align * align;
     const size_t here = *at;
     *at += bytes;
     return here;
@@ -239,15 +182,11 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   const size_t off_results = take(&meta, (size_t)count * kEncResultWords * 8, 256);
   const size_t off_raw_counts = take(&meta, (size_t)n_raw * 1024, 16);
   const size_t zero_bytes = meta - off_results;
-  for (uint32_t k = 0; k < count; k++)
-  {
-    const size_t nb = mm[k].n_blocks;
-    // mt_: image_bytes, image_off [nb] u64, chain_count, chain_off [nb] u32, fits (16-byte aligned, 16 bytes), block counts [nb][256] u32
-    mm[k].meta_at = take(&meta, mm[k].raw ? 16 : nb * 24 + 32 + nb * 1024, 256);
-  }
+  for (uint32_t k = 0; k < count; k++) // (raw: image_bytes, image_off)
+    mm[k].meta_at = take(&meta, mm[k].raw ? 16 : mt_block_arrays_bytes(mm[k].n_blocks), 256);
 
   std::lock_guard<std::mutex> guard(ctx->lock);
-  if (hipSetDevice(ctx->device) != hipSuccess)
+  if (!encoder_ready(ctx))
     return HSRANS_E_HIP;
   if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, scratch_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta) ||
       !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, std::max<size_t>(ck_bytes, 256)))
@@ -266,18 +205,8 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   {
     const hsrans_encode_member &a = members[k];
     const Member &m = mm[k];
-    EncParams ep{};
-    ep.S = m.S;
-    ep.bits = a.bits;
-    ep.in = (const uint8_t *)a.d_in;
-    ep.n = a.length;
-    ep.out = (uint8_t *)a.d_out;
-    ep.out_cap = a.out_capacity;
+    EncParams ep = m.params(a.d_in, a.d_out, a.out_capacity);
     ep.scratch = ctx->d_enc_scratch + m.scratch_at;
-    ep.slot_bytes = m.slot_bytes;
-    ep.n_blocks = m.n_blocks;
-    ep.interval = m.interval;
-    ep.max_ck = m.max_ck;
     ep.result = (uint64_t *)(d_meta + off_results) + (size_t)k * kEncResultWords;
     ep.ck_states = (uint32_t *)(ctx->d_enc_ck + m.ck_at);
     ep.ck_pos = ep.ck_states + m.ck_slots * m.S;
@@ -285,7 +214,6 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
     headers[k] = nullptr;
     if (m.raw)
     {
-      ep.block = a.length;
       ep.image_bytes = (uint64_t *)own;
       ep.image_off = ep.image_bytes + 1;
       ep.raw_counts = (const uint32_t *)(d_meta + off_raw_counts) + (size_t)raw_slot[k] * 256;
@@ -306,16 +234,7 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
         headers[k] = ctx->d_enc_ck + m.header_at;
     }
     else
-    {
-      const size_t nb = m.n_blocks;
-      ep.block = a.block_size;
-      ep.image_bytes = (uint64_t *)own;
-      ep.image_off = ep.image_bytes + nb;
-      ep.chain_count = (uint32_t *)(ep.image_off + nb);
-      ep.chain_off = ep.chain_count + nb;
-      ep.fits = (uint64_t *)up((uintptr_t)(ep.chain_off + nb), 16);
-      ep.raw_counts = (const uint32_t *)(ep.fits + 2);
-    }
+      mt_block_arrays(&ep, own);
     params[k] = ep;
   }
   memcpy(upload.data() + off_raw_list, raw_list.data(), raw_list.size() * 4);
@@ -344,7 +263,7 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   std::vector<uint64_t> results((size_t)count * kEncResultWords);
   std::vector<uint8_t> raw_down(any_raw_plan ? raw_down_bytes : 0);
   bool ok = hipMemcpyAsync(d_meta, upload.data(), upload_bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
-            launch_encode_batch(bt, s, &ctx->enc_batch_prepared, &launches) == hipSuccess &&
+            launch_encode_batch(bt, ctx->geom.num_cus, s, &launches) == hipSuccess &&
             hipMemcpyAsync(results.data(), d_meta + off_results, results.size() * 8, hipMemcpyDeviceToHost, s) == hipSuccess &&
             (!any_raw_plan || hipMemcpyAsync(raw_down.data(), ctx->d_enc_ck, raw_down_bytes, hipMemcpyDeviceToHost, s) == hipSuccess);
   if (hipStreamSynchronize(s) != hipSuccess || !ok) // (upload may be read until here)
@@ -379,30 +298,15 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
       rc = HSRANS_E_HIP;
   };
 
-  // ---- raw plans: assembled on the host from the headers and checkpoints that came down (raw_plan_from_checkpoints, as the single call) ----
-  std::vector<uint8_t> blob;
-  std::vector<uint64_t> ck_group, ck_wfe;
+  // ---- raw plans: assembled on the host from the headers and checkpoints that came down, as the single call does (raw_plan) ----
   for (uint32_t k : raw_list)
   {
     const Member &m = mm[k];
     if (!fine[k] || !m.want_plan)
       continue;
-    const hsrans_encode_member &a = members[k];
-    const uint8_t *header = raw_down.data() + m.header_at;
     const uint32_t *ck_states = (const uint32_t *)(raw_down.data() + m.ck_at);
-    const uint32_t *ck_pos = ck_states + m.ck_slots * m.S;
-    ck_group.resize(m.n_ck);
-    ck_wfe.resize(m.n_ck);
-    for (size_t i = 0; i < m.n_ck; i++)
-    {
-      ck_group[i] = m.listed ? a.index_groups[i] : (uint64_t)(i + 1) * a.index_interval;
-      ck_wfe[i] = ck_pos[i];
-    }
-    blob.resize(plan_capacity_chains(HSRANS_RAW, a.states, a.length, m.n_ck, 0));
-    const size_t psize = raw_plan_from_checkpoints(a.states, a.bits, a.length, members[k].stream_length, (const uint16_t *)(header + 16),
-                                                   (const uint32_t *)(header + 16 + 512), m.n_ck, ck_group.data(), ck_wfe.data(), ck_states,
-                                                   m.listed ? 0 : a.index_interval, blob.data(), blob.size());
-    if (psize == 0 || hsrans_dplan_create(ctx, blob.data(), psize, &out_dplans[k]) != HSRANS_OK)
+    if (raw_plan(ctx, m, members[k].stream_length, members[k].index_groups, raw_down.data() + m.header_at, ck_states, ck_states + m.ck_slots * m.S, nullptr, 0,
+                 nullptr, &out_dplans[k]) == 0)
       fail_member(k);
   }
 
@@ -410,47 +314,16 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   if (n_mt_members == 0)
     return rc;
   std::vector<PlanHeader> heads(count);
-  std::vector<uint8_t> grouped(count, 0);
   bool any_plan = false;
-  for (uint32_t k = 0; k < count; k++)
+  for (uint32_t k = 0; k < count; k++) // (members without a plan keep EncParams::plan null: their blocks return at once)
   {
-    const Member &m = mm[k];
-    if (m.raw || !fine[k])
+    if (mm[k].raw || !fine[k])
       continue;
-    const uint64_t *r = &results[(size_t)k * kEncResultWords];
-    EncParams &ep = params[k];
-    hsrans_dplan *d = r[2] == 0 || r[2] > 0xFFFFFFFFull ? nullptr : dplan_new(ctx);
-    if (d == nullptr)
-    {
+    out_dplans[k] = mt_plan_begin(ctx, &params[k], &results[(size_t)k * kEncResultWords], &heads[k], s);
+    if (out_dplans[k] == nullptr)
       fail_member(k);
-      continue;
-    }
-    PlanHeader &h = heads[k];
-    h = mt_plan_header(m.S, members[k].bits, members[k].length, members[k].stream_length, (uint32_t)r[2]);
-    h.shared_hist = r[3] == 1 ? 1 : 0; // exactly one block with a histogram (hsrans_host.cpp PlanBuilder::serialize)
-    h.aux_off = h.shared_hist ? r[4] : 0;
-    h.interval = ep.interval;
-    grouped[k] = ep.interval != 0 && ep.n_blocks < h.n_chains;
-    ep.group_split = grouped[k] ? group_parts_of(ep.max_ck + 1, std::min(group_parts_max(ctx->geom, ep.n_blocks), 64u)) : 1;
-    DplanRegions reg;
-    reg.counters = grouped[k];
-    reg.plan = (size_t)plan_size(h.n_chains, h.n_pieces, h.states, 0);
-    reg.groups = grouped[k] ? (size_t)ep.n_blocks * ep.group_split * sizeof(Group) : 0;
-    reg.zero = kZeroThroughPlan;
-    out_dplans[k] = d;
-    if (dplan_arena(d, reg, s) != HSRANS_OK || hipMemcpyAsync(d->d_plan, &h, sizeof(h), hipMemcpyHostToDevice, s) != hipSuccess)
-    {
-      fail_member(k);
-      continue;
-    }
-    ep.plan = d->d_plan;
-    ep.groups = d->d_groups;
-    ep.n_chains = h.n_chains;
-    any_plan = true;
+    any_plan = any_plan || out_dplans[k] != nullptr;
   }
-  for (uint32_t k = 0; k < count; k++) // (members without a plan: their blocks return at once)
-    if (!mm[k].raw && out_dplans[k] == nullptr)
-      params[k].plan = nullptr;
   ok = !any_plan || (hipMemcpyAsync(d_meta + off_params, params, (size_t)count * sizeof(EncParams), hipMemcpyHostToDevice, s) == hipSuccess &&
                      launch_encode_plan_batch(bt.params, bt.mt_blocks, (uint32_t)mt_tasks.size(), s, &launches) == hipSuccess);
   if (hipStreamSynchronize(s) != hipSuccess || !ok) // (heads / params may be read until here)
@@ -465,6 +338,6 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
     stats->launches = launches;
   for (uint32_t k = 0; k < count; k++)
     if (!mm[k].raw && out_dplans[k] != nullptr)
-      dplan_adopt(out_dplans[k], heads[k], grouped[k] ? params[k].n_blocks * params[k].group_split : 0, params[k].max_ck + 1, s);
+      mt_plan_adopt(out_dplans[k], params[k], heads[k], s);
   return rc;
 }

@@ -54,22 +54,14 @@ try
   // plan, when asked for, is written once after the last slice by k_plan_blocks from the block records every slice left on the device.
   if (opts)
     opts->plan_size = 0;
-  if (ctx == nullptr || opts == nullptr || container != HSRANS_MT || !valid_codec(container, states, bits) || in == nullptr || out == nullptr || length == 0)
+  EncShape sh; // (hsrans_encode_device's block rules)
+  if (ctx == nullptr || opts == nullptr || container != HSRANS_MT || in == nullptr || out == nullptr || opts->flags != HSRANS_ENC_INDEPENDENT_BLOCKS ||
+      opts->n_index_groups != 0 || (opts->index_interval != 0 && opts->plan_out == nullptr) ||
+      !mt_shape(states, bits, length, out_capacity, opts->block_size, opts->index_interval, true, &sh))
     return 0;
-  const uint32_t S = (uint32_t)states;
-  const size_t block = opts->block_size;
-  const uint32_t interval = opts->index_interval;
-  if (opts->flags != HSRANS_ENC_INDEPENDENT_BLOCKS || opts->n_index_groups != 0 || block == 0 || block % 64 != 0 || block > (1u << 30) || interval % 4 != 0)
-    return 0;
+  const uint32_t S = sh.S, nb = sh.n_blocks, interval = sh.interval, max_ck = sh.max_ck;
+  const size_t block = sh.block;
   const bool want_plan = interval != 0;
-  if (want_plan && opts->plan_out == nullptr)
-    return 0;
-  if (out_capacity < capacity(container, states, length))
-    return 0;
-  const uint32_t nb = encode_block_count(length, block, S);
-  if (nb == 0)
-    return 0;
-  const uint32_t max_ck = want_plan ? (uint32_t)((block / S - 1) / interval) : 0;
   auto block_end = [&](uint32_t b) { return b + 1 == nb ? length : (size_t)(b + 1) * block; };
   auto chains_of = [&](uint32_t b) -> uint64_t { // a coded block's chains (encode_body: 1 + one per checkpoint)
     const uint64_t whole = (block_end(b) - (size_t)b * block) / S;
@@ -109,7 +101,7 @@ try
     in_slot = std::max(in_slot, block_end(first[k + 1] - 1) - (size_t)first[k] * block);
   }
   in_slot = up256(in_slot);
-  const uint64_t slot_bytes = encode_slot_bytes(block, S);
+  const uint64_t slot_bytes = sh.slot_bytes;
   const size_t stage_slot = up256(most_blocks * slot_bytes); // (an image never outgrows its slot)
   const size_t head_bytes = 16 + 4 * (size_t)S;
   // per-block records of the whole stream (the plan reads them after the last slice), the one slice's counts, the carry, the heads
@@ -120,7 +112,7 @@ try
   constexpr uint32_t kRing = 2; // input and staging slots: slice k reuses slice k-2's once its encode / download is done
 
   std::lock_guard<std::mutex> guard(ctx->lock);
-  if (hipSetDevice(ctx->device) != hipSuccess)
+  if (!encoder_ready(ctx))
     return 0;
   {
     std::lock_guard<std::mutex> sguard(ctx->stream_lock);
@@ -162,7 +154,7 @@ try
   auto down_done = [&](uint32_t k) { return ev[3 * (size_t)k + 2]; };
   ok = ok && hipMemcpyAsync(d_carry, h_res, sizeof(EncCarry), hipMemcpyHostToDevice, enc) == hipSuccess;
 
-  uint64_t total = 0, chains = 0, coded = 0, last_hist = 0;
+  uint64_t last[kEncResultWords] = {}; // the result words of the slice that came in last: the whole stream's once all are in
   // step j queues slice j's upload and encode, then (one slice behind) waits for slice j-1's result words and queues its download:
   // the upload of slice j is in flight while the host waits, and the next upload is queued before it ends
   for (uint32_t j = 0; ok && j <= ns; j++)
@@ -196,7 +188,7 @@ try
       ep.max_ck = max_ck;
       ep.ck_states = g_ck_states + (want_plan && max_ck ? (size_t)b0 * max_ck * S : 0);
       ep.ck_pos = g_ck_pos + (want_plan && max_ck ? (size_t)b0 * max_ck : 0);
-      ok = ok && launch_encode_slice(ep, d_carry, j + 1 == ns, g_heads ? g_heads + (size_t)b0 * head_bytes : nullptr, enc, &ctx->enc_prepared) == hipSuccess &&
+      ok = ok && launch_encode_slice(ep, d_carry, j + 1 == ns, g_heads ? g_heads + (size_t)b0 * head_bytes : nullptr, ctx->geom.num_cus, enc) == hipSuccess &&
            hipEventRecord(enc_done(j), enc) == hipSuccess;
     }
     if (ok && j >= 1)
@@ -207,12 +199,7 @@ try
       const uint64_t end = r[0], base = r[5];
       ok = ok && r[1] == 1 && base >= 16 && end >= base && end <= out_capacity;
       if (ok)
-      {
-        total = end;
-        chains = r[2];
-        coded = r[3];
-        last_hist = r[4];
-      }
+        std::copy(r, r + kEncResultWords, last);
       ok = ok && hipStreamWaitEvent(down, enc_done(k), 0) == hipSuccess &&
            (end == base || hipMemcpyAsync(out + base, ctx->d_out + (k % kRing) * stage_slot, end - base, hipMemcpyDeviceToHost, down) == hipSuccess) &&
            hipEventRecord(down_done(k), down) == hipSuccess;
@@ -223,30 +210,26 @@ try
   size_t psize = 0;
   if (ok && want_plan)
   {
-    ok = chains != 0 && chains <= 0xFFFFFFFFull;
-    h = mt_plan_header(S, bits, length, total, (uint32_t)chains);
-    h.shared_hist = coded == 1 ? 1 : 0; // exactly one block with a histogram (as hsrans_encode_device)
-    h.aux_off = h.shared_hist ? last_hist : 0;
-    h.interval = interval;
+    EncParams ep{};
+    ep.S = S;
+    ep.bits = bits;
+    ep.n = length;
+    ep.block = block;
+    ep.n_blocks = nb;
+    ep.image_bytes = g_bytes;
+    ep.image_off = g_off;
+    ep.chain_count = g_cc;
+    ep.chain_off = g_co;
+    ep.interval = interval;
+    ep.max_ck = max_ck;
+    ep.ck_states = g_ck_states;
+    ep.ck_pos = g_ck_pos;
+    ep.scratch = g_heads;
+    ok = mt_result_header(ep, last, &h); // (as hsrans_encode_device's)
     psize = (size_t)plan_size(h.n_chains, h.n_pieces, S, h.flags);
     ok = ok && psize <= opts->plan_capacity && grow(&ctx->d_plan, &ctx->d_plan_cap, psize);
     if (ok)
     {
-      EncParams ep{};
-      ep.S = S;
-      ep.bits = bits;
-      ep.n = length;
-      ep.block = block;
-      ep.n_blocks = nb;
-      ep.image_bytes = g_bytes;
-      ep.image_off = g_off;
-      ep.chain_count = g_cc;
-      ep.chain_off = g_co;
-      ep.interval = interval;
-      ep.max_ck = max_ck;
-      ep.ck_states = g_ck_states;
-      ep.ck_pos = g_ck_pos;
-      ep.scratch = g_heads;
       ep.plan = ctx->d_plan;
       ep.n_chains = h.n_chains;
       ok = hipMemsetAsync(ctx->d_plan, 0, psize, enc) == hipSuccess && hipMemcpyAsync(ctx->d_plan, &h, sizeof(h), hipMemcpyHostToDevice, enc) == hipSuccess &&
@@ -264,11 +247,11 @@ try
     (void)hipGetLastError();
     return 0;
   }
-  const uint64_t file_header[2] = {(uint64_t)length, total}; // decodedLen | streamLen, once the last slice's end is known
+  const uint64_t file_header[2] = {(uint64_t)length, last[0]}; // decodedLen | streamLen, once the last slice's end is known
   memcpy(out, file_header, 16);
   if (want_plan)
     opts->plan_size = psize;
-  return (size_t)total;
+  return (size_t)last[0];
 }
 catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
 {

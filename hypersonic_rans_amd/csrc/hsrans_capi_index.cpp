@@ -15,6 +15,7 @@
 
 #include "../../include/hsrans_hip.h"
 #include "hsrans_host.h"
+#include "hsrans_index_groups.h"
 #include "hsrans_cpu.h"
 #include "hsrans_encode.h"
 #include "hsrans_kernels.h"
@@ -76,11 +77,8 @@ static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint3
   if (groups != nullptr)
   {
     index_interval = 0;
-    if (n_groups == 0 || n_groups > 0xFFFFFFFFull || container == HSRANS_BLOCK)
+    if (n_groups == 0 || n_groups > 0xFFFFFFFFull || container == HSRANS_BLOCK || !index_groups_valid(groups, n_groups))
       return 0;
-    for (size_t k = 0; k < n_groups; k++)
-      if (groups[k] == 0 || (groups[k] % 4) != 0 || (k > 0 && groups[k] <= groups[k - 1]))
-        return 0;
   }
   uint64_t out_len;
   memcpy(&out_len, in, 8);

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "hsrans_host.h"
+#include "hsrans_index_groups.h"
 
 namespace hsrans
 {
@@ -681,9 +682,8 @@ size_t index_build(int level, uint32_t threads, int container, int states, uint3
 {
   if (in == nullptr || plan_out == nullptr || in_len < 16 || !valid_codec(container, states, bits) || container == HSRANS_BLOCK || groups == nullptr || n_groups == 0)
     return 0;
-  for (size_t k = 0; k < n_groups; k++)
-    if (groups[k] == 0 || (groups[k] % 4) != 0 || (k > 0 && groups[k] <= groups[k - 1]))
-      return 0;
+  if (!index_groups_valid(groups, n_groups))
+    return 0;
   const uint64_t out_len = rd64(in);
   const uint32_t S = (uint32_t)states;
   // The decoded length in the header is untrusted: nothing here is sized by it alone.  The base plan (one chain per block) is

@@ -62,11 +62,13 @@ struct EncParams
 uint32_t encode_block_count(uint64_t n, uint64_t block, uint32_t S); // 0: too many blocks
 uint64_t encode_slot_bytes(uint64_t block, uint32_t S);
 constexpr uint32_t kEncResultWords = 8;
-// asynchronous on `stream`: K_enc, K_scan, K_gather.  `prepared` is the calling context's flag: the dynamic-LDS attribute
-// is per device, so it is raised once per context, not once per process
-hipError_t launch_encode(const EncParams &ep, hipStream_t stream, bool *prepared);
+// raises the dynamic-LDS limit of every encode kernel that needs more than the default, on the current device.  The attribute is per
+// device, so each context calls it once, before its first encode of any kind; the launchers below rely on it
+hipError_t prepare_encode_kernels();
+// asynchronous on `stream`: K_enc, K_scan, K_gather.  cus: the device's CU count (picks the chunk variant)
+hipError_t launch_encode(const EncParams &ep, uint32_t cus, hipStream_t stream);
 // asynchronous on `stream`: [memset + K_hist ->] K_raw -> K_copy.  result[0] stream length, [1] fits out_cap, [2] listed checkpoints not met (0)
-hipError_t launch_encode_raw(const EncParams &ep, uint32_t *d_counts, hipStream_t stream, bool *prepared);
+hipError_t launch_encode_raw(const EncParams &ep, uint32_t *d_counts, hipStream_t stream);
 // asynchronous on `stream`: the unit summaries the block walk reads (hsrans_host.h UnitSummary, kUnitSummaryBytes each) of ep.n_blocks
 // units of ep.block symbols (the last ends at ep.n) into `summaries`; with `log_table` (walk_log_table's, 2^bits + 1 floats, device
 // memory) also every whole unit's fresh_cost, normalised at ep.block symbols
@@ -74,7 +76,7 @@ constexpr uint32_t kUnitSummaryBytes = 1040;
 hipError_t launch_unit_summaries(const EncParams &ep, void *summaries, const float *log_table, hipStream_t stream);
 // asynchronous on `stream`: K_chain (one wavefront, blocks back to front) -> K_gather_chain.  result[0] stream length, [1] fits
 // out_cap, [2] listed checkpoints not met (0); image_off / image_bytes per block
-hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream, bool *prepared);
+hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream);
 // asynchronous on `stream`: K_plan (needs ep.plan, ep.n_chains; after launch_encode's results are known)
 hipError_t launch_encode_plan(const EncParams &ep, hipStream_t stream);
 
@@ -91,7 +93,7 @@ struct EncCarry
 // (ep.in its first byte, ep.n its length, ep.n_blocks its blocks; the per-block arrays start at its first block), ep.out its staging
 // buffer (the images packed from byte 0); result[0..4] as launch_encode's, absolute, result[5] the stream position of the slice's first
 // byte.  heads: or null, 16 + 4 S bytes per block of what k_plan_blocks reads of the images (launch_encode_plan_carried)
-hipError_t launch_encode_slice(const EncParams &ep, EncCarry *carry, bool last_slice, uint8_t *heads, hipStream_t stream, bool *prepared);
+hipError_t launch_encode_slice(const EncParams &ep, EncCarry *carry, bool last_slice, uint8_t *heads, uint32_t cus, hipStream_t stream);
 // asynchronous on `stream`: K_plan over the whole stream after its last slice, the images' heads at ep.scratch (launch_encode_slice's)
 hipError_t launch_encode_plan_carried(const EncParams &ep, hipStream_t stream);
 
@@ -122,7 +124,7 @@ struct EncBatch
 };
 // asynchronous on `stream`: memset -> K_hist (raw), K_hist (mt_) -> K_raw per state count -> K_enc per state count -> [K_scan] -> K_gather
 // -> K_copy; each kind launched once for all members, none for a kind no member needs.  *launches += the kernels launched
-hipError_t launch_encode_batch(const EncBatch &batch, hipStream_t stream, bool *prepared, uint32_t *launches);
+hipError_t launch_encode_batch(const EncBatch &batch, uint32_t cus, hipStream_t stream, uint32_t *launches);
 // asynchronous on `stream`: K_plan over `tasks` (the mt_ blocks); members whose EncParams::plan is null are skipped
 hipError_t launch_encode_plan_batch(const EncParams *params, const EncTask *tasks, uint32_t n_tasks, hipStream_t stream, uint32_t *launches);
 

@@ -1823,32 +1823,40 @@ uint64_t encode_slot_bytes(uint64_t block, uint32_t S)
   return (need + 511) / 512 * 512; // (a multiple of the encoder's flush segment)
 }
 
+hipError_t prepare_encode_kernels()
+{
+  const size_t lds_few = sizeof(WaveLdsT<kChunkFew>), lds_many = sizeof(WaveLdsT<kChunkMany>);
+  const std::pair<const void *, size_t> kernels[] = {{(const void *)k_encode_blocks<64, kChunkFew>, lds_few * kWavesPerWG},
+                                                     {(const void *)k_encode_blocks<32, kChunkFew>, lds_few * kWavesPerWG},
+                                                     {(const void *)k_encode_blocks<64, kChunkMany>, lds_many * kWavesPerWG},
+                                                     {(const void *)k_encode_blocks<32, kChunkMany>, lds_many * kWavesPerWG},
+                                                     {(const void *)k_encode_raw<64>, lds_few},
+                                                     {(const void *)k_encode_raw<32>, lds_few},
+                                                     {(const void *)k_encode_chain<64>, lds_few},
+                                                     {(const void *)k_encode_chain<32>, lds_few},
+                                                     {(const void *)k_encode_raw_batch<64>, lds_few},
+                                                     {(const void *)k_encode_raw_batch<32>, lds_few},
+                                                     {(const void *)k_encode_blocks_batch<64, kChunkFew>, lds_few},
+                                                     {(const void *)k_encode_blocks_batch<32, kChunkFew>, lds_few},
+                                                     {(const void *)k_encode_blocks_batch<64, kChunkMany>, lds_many},
+                                                     {(const void *)k_encode_blocks_batch<32, kChunkMany>, lds_many}};
+  for (const auto &k : kernels)
+  {
+    const hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second);
+    if (e != hipSuccess)
+      return e;
+  }
+  return hipSuccess;
+}
+
 namespace
 {
 // K_hist -> K_enc of launch_encode and launch_encode_slice (the launches queued; errors are read by the caller)
-hipError_t launch_encode_blocks(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
+void launch_encode_blocks(const EncParams &ep, uint32_t cus, hipStream_t stream)
 {
-  bool local = false;
-  bool &prepared = prepared_flag ? *prepared_flag : local;
   const size_t lds_few = sizeof(WaveLdsT<kChunkFew>) * kWavesPerWG, lds_many = sizeof(WaveLdsT<kChunkMany>) * kWavesPerWG;
-  if (!prepared)
-  {
-    hipError_t e = hipFuncSetAttribute((const void *)k_encode_blocks<64, kChunkFew>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_few);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)k_encode_blocks<32, kChunkFew>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_few);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)k_encode_blocks<64, kChunkMany>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_many);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)k_encode_blocks<32, kChunkMany>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_many);
-    if (e != hipSuccess)
-      return e;
-    prepared = true;
-  }
   // few blocks: all resident at once with the large chunks too (11 workgroups of 13.25 KiB per CU: the LDS is handed out in pieces)
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 1;
-  const bool few = ep.n_blocks <= 11u * (uint32_t)cus * kWavesPerWG;
+  const bool few = ep.n_blocks <= 11u * cus * kWavesPerWG;
   const size_t lds = few ? lds_few : lds_many;
   const uint32_t grid = (ep.n_blocks + kWavesPerWG - 1) / kWavesPerWG;
   (void)hipGetLastError(); // (sticky per thread)
@@ -1862,45 +1870,29 @@ hipError_t launch_encode_blocks(const EncParams &ep, hipStream_t stream, bool *p
     hipLaunchKernelGGL((k_encode_blocks<32, kChunkFew>), dim3(grid), dim3(64 * kWavesPerWG), lds, stream, ep);
   else
     hipLaunchKernelGGL((k_encode_blocks<32, kChunkMany>), dim3(grid), dim3(64 * kWavesPerWG), lds, stream, ep);
-  return hipSuccess;
 }
 } // namespace
 
-hipError_t launch_encode(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
+hipError_t launch_encode(const EncParams &ep, uint32_t cus, hipStream_t stream)
 {
-  const hipError_t e = launch_encode_blocks(ep, stream, prepared_flag);
-  if (e != hipSuccess)
-    return e;
+  launch_encode_blocks(ep, cus, stream);
   if (ep.n_blocks > kSelfScanBlocks)
     hipLaunchKernelGGL(k_scan_images, dim3(1), dim3(1024), 0, stream, ep);
   hipLaunchKernelGGL(k_gather_images, dim3(ep.n_blocks), dim3(256), 0, stream, ep);
   return hipGetLastError();
 }
 
-hipError_t launch_encode_slice(const EncParams &ep, EncCarry *carry, bool last_slice, uint8_t *heads, hipStream_t stream, bool *prepared_flag)
+hipError_t launch_encode_slice(const EncParams &ep, EncCarry *carry, bool last_slice, uint8_t *heads, uint32_t cus, hipStream_t stream)
 {
-  const hipError_t e = launch_encode_blocks(ep, stream, prepared_flag);
-  if (e != hipSuccess)
-    return e;
+  launch_encode_blocks(ep, cus, stream);
   hipLaunchKernelGGL(k_scan_images_carried, dim3(1), dim3(1024), 0, stream, ep, carry, last_slice ? 1u : 0u);
   hipLaunchKernelGGL(k_gather_images_carried, dim3(ep.n_blocks), dim3(256), 0, stream, ep, heads);
   return hipGetLastError();
 }
 
-hipError_t launch_encode_raw(const EncParams &ep, uint32_t *d_counts, hipStream_t stream, bool *prepared_flag)
+hipError_t launch_encode_raw(const EncParams &ep, uint32_t *d_counts, hipStream_t stream)
 {
-  bool local = false;
-  bool &prepared = prepared_flag ? *prepared_flag : local;
   const size_t lds = sizeof(WaveLdsT<kChunkFew>);
-  if (!prepared)
-  {
-    hipError_t e = hipFuncSetAttribute((const void *)k_encode_raw<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)k_encode_raw<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-      return e;
-    prepared = true;
-  }
   (void)hipGetLastError();
   {
     // (also with the caller's histogram: the coding wavefront checks that every symbol that occurs has a slot in it)
@@ -1928,20 +1920,9 @@ hipError_t launch_unit_summaries(const EncParams &ep, void *summaries, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream, bool *prepared_flag)
+hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream)
 {
-  bool local = false;
-  bool &prepared = prepared_flag ? *prepared_flag : local;
   const size_t lds = sizeof(WaveLdsT<kChunkFew>);
-  if (!prepared)
-  {
-    hipError_t e = hipFuncSetAttribute((const void *)k_encode_chain<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)k_encode_chain<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess)
-      return e;
-    prepared = true;
-  }
   (void)hipGetLastError();
   if (ep.S == 64)
     hipLaunchKernelGGL(k_encode_chain<64>, dim3(1), dim3(64), lds, stream, ep);
@@ -1968,33 +1949,12 @@ hipError_t launch_encode_plan_carried(const EncParams &ep, hipStream_t stream)
 }
 
 
-hipError_t launch_encode_batch(const EncBatch &bt, hipStream_t stream, bool *prepared_flag, uint32_t *launches)
+hipError_t launch_encode_batch(const EncBatch &bt, uint32_t cus, hipStream_t stream, uint32_t *launches)
 {
-  bool local = false;
-  bool &prepared = prepared_flag ? *prepared_flag : local;
   const size_t lds_few = sizeof(WaveLdsT<kChunkFew>), lds_many = sizeof(WaveLdsT<kChunkMany>);
-  if (!prepared)
-  {
-    const std::pair<const void *, size_t> kernels[] = {{(const void *)k_encode_raw_batch<64>, lds_few},
-                                                       {(const void *)k_encode_raw_batch<32>, lds_few},
-                                                       {(const void *)k_encode_blocks_batch<64, kChunkFew>, lds_few},
-                                                       {(const void *)k_encode_blocks_batch<32, kChunkFew>, lds_few},
-                                                       {(const void *)k_encode_blocks_batch<64, kChunkMany>, lds_many},
-                                                       {(const void *)k_encode_blocks_batch<32, kChunkMany>, lds_many}};
-    for (const auto &k : kernels)
-    {
-      const hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second);
-      if (e != hipSuccess)
-        return e;
-    }
-    prepared = true;
-  }
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 1;
-  const uint32_t n_raw = bt.n_raw64 + bt.n_raw32, n_mt = bt.n_mt64_blocks + bt.n_mt32_blocks;
+  const uint32_t n_mt = bt.n_mt64_blocks + bt.n_mt32_blocks;
   // the chunk variant from all mt_ blocks of the batch, as launch_encode picks it from one stream's
-  const bool few = n_mt <= 11u * (uint32_t)cus;
+  const bool few = n_mt <= 11u * cus;
   uint32_t n = 0;
   (void)hipGetLastError(); // (sticky per thread)
   if (bt.zero_bytes != 0)
@@ -2003,62 +1963,31 @@ hipError_t launch_encode_batch(const EncBatch &bt, hipStream_t stream, bool *pre
     if (e != hipSuccess)
       return e;
   }
-  if (n_raw != 0)
-    {
-      hipLaunchKernelGGL(k_raw_histogram_batch, dim3(bt.n_raw_parts), dim3(256), 0, stream, bt.params, bt.raw_parts);
-      n++;
-    }
-  if (n_mt != 0)
-    {
-      hipLaunchKernelGGL(k_block_histograms_batch, dim3(n_mt), dim3(256), 0, stream, bt.params, bt.mt_blocks);
-      n++;
-    }
-  if (bt.n_raw64 != 0)
-    {
-      hipLaunchKernelGGL(k_encode_raw_batch<64>, dim3(bt.n_raw64), dim3(64), lds_few, stream, bt.params, bt.raw_members);
-      n++;
-    }
-  if (bt.n_raw32 != 0)
-    {
-      hipLaunchKernelGGL(k_encode_raw_batch<32>, dim3(bt.n_raw32), dim3(64), lds_few, stream, bt.params, bt.raw_members + bt.n_raw64);
-      n++;
-    }
+  // one launch of `kernel` over `grid` workgroups when that is not 0
+  auto launch = [&](auto kernel, uint32_t grid, uint32_t threads, size_t lds, auto... args) {
+    if (grid == 0)
+      return;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, args...);
+    n++;
+  };
   const EncTask *mt32 = bt.mt_blocks + bt.n_mt64_blocks;
-  if (bt.n_mt64_blocks != 0 && few)
-    {
-      hipLaunchKernelGGL((k_encode_blocks_batch<64, kChunkFew>), dim3(bt.n_mt64_blocks), dim3(64), lds_few, stream, bt.params, bt.mt_blocks);
-      n++;
-    }
-  else if (bt.n_mt64_blocks != 0)
-    {
-      hipLaunchKernelGGL((k_encode_blocks_batch<64, kChunkMany>), dim3(bt.n_mt64_blocks), dim3(64), lds_many, stream, bt.params, bt.mt_blocks);
-      n++;
-    }
-  if (bt.n_mt32_blocks != 0 && few)
-    {
-      hipLaunchKernelGGL((k_encode_blocks_batch<32, kChunkFew>), dim3(bt.n_mt32_blocks), dim3(64), lds_few, stream, bt.params, mt32);
-      n++;
-    }
-  else if (bt.n_mt32_blocks != 0)
-    {
-      hipLaunchKernelGGL((k_encode_blocks_batch<32, kChunkMany>), dim3(bt.n_mt32_blocks), dim3(64), lds_many, stream, bt.params, mt32);
-      n++;
-    }
-  if (bt.n_scan != 0)
-    {
-      hipLaunchKernelGGL(k_scan_images_batch, dim3(bt.n_scan), dim3(1024), 0, stream, bt.params, bt.scan_members);
-      n++;
-    }
-  if (n_mt != 0)
-    {
-      hipLaunchKernelGGL(k_gather_images_batch, dim3(n_mt), dim3(256), 0, stream, bt.params, bt.mt_blocks);
-      n++;
-    }
-  if (n_raw != 0)
-    {
-      hipLaunchKernelGGL(k_copy_images_batch, dim3(bt.n_raw_parts), dim3(256), 0, stream, bt.params, bt.raw_parts, bt.raw_headers);
-      n++;
-    }
+  launch(k_raw_histogram_batch, bt.n_raw_parts, 256, 0, bt.params, bt.raw_parts);
+  launch(k_block_histograms_batch, n_mt, 256, 0, bt.params, bt.mt_blocks);
+  launch(k_encode_raw_batch<64>, bt.n_raw64, 64, lds_few, bt.params, bt.raw_members);
+  launch(k_encode_raw_batch<32>, bt.n_raw32, 64, lds_few, bt.params, bt.raw_members + bt.n_raw64);
+  if (few)
+  {
+    launch(k_encode_blocks_batch<64, kChunkFew>, bt.n_mt64_blocks, 64, lds_few, bt.params, bt.mt_blocks);
+    launch(k_encode_blocks_batch<32, kChunkFew>, bt.n_mt32_blocks, 64, lds_few, bt.params, mt32);
+  }
+  else
+  {
+    launch(k_encode_blocks_batch<64, kChunkMany>, bt.n_mt64_blocks, 64, lds_many, bt.params, bt.mt_blocks);
+    launch(k_encode_blocks_batch<32, kChunkMany>, bt.n_mt32_blocks, 64, lds_many, bt.params, mt32);
+  }
+  launch(k_scan_images_batch, bt.n_scan, 1024, 0, bt.params, bt.scan_members);
+  launch(k_gather_images_batch, n_mt, 256, 0, bt.params, bt.mt_blocks);
+  launch(k_copy_images_batch, bt.n_raw_parts, 256, 0, bt.params, bt.raw_parts, bt.raw_headers);
   if (launches)
     *launches += n;
   return hipGetLastError();

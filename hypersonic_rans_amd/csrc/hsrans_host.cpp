@@ -9,6 +9,7 @@
 //   mt_    : u64 decodedLen | u64 streamLen | { u64 size ; u64 skip ; u32 state[S] ; u16 count[256] ; words }...
 //            next header = &state[0] + 2*(skip+1) bytes                                  (mt_rANS32x64_16w_encode.cpp:266-298)
 #include "hsrans_host.h"
+#include "hsrans_index_groups.h"
 
 #include <math.h>
 #include <string.h>
@@ -549,9 +550,8 @@ size_t encode(int container, int states, uint32_t bits, const uint8_t *in, size_
   const bool want_plan = interval != 0 || ig != nullptr;
   if (want_plan && ((interval % 4) != 0 || opts->plan_out == nullptr))
     return 0;
-  for (size_t k = 0; k < ig_left; k++)
-    if (ig[k] == 0 || (ig[k] % 4) != 0 || (k > 0 && ig[k] <= ig[k - 1]))
-      return 0;
+  if (!index_groups_valid(ig, ig_left))
+    return 0;
   auto wanted = [&](uint64_t g) { // is group g a checkpoint?  (called with descending g)
     if (interval != 0)
       return g % interval == 0;

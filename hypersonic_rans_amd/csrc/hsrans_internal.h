@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/hsrans_hip.h"
+#include "hsrans_encode.h"
 #include "hsrans_kernels.h"
 
 using namespace hsrans;
@@ -26,10 +27,7 @@ struct hsrans_ctx
   char name[256] = {};
   DeviceGeom geom{};     // CU count / LDS of THIS context's device (nothing about a device is process-global)
   Tuning tuning = read_tuning(); // the switches as they were at hsrans_ctx_create: what the context's calls that make no object of their own use
-  bool enc_prepared = false;
-  bool enc_raw_prepared = false;
-  bool enc_chain_prepared = false;
-  bool enc_batch_prepared = false;
+  bool encoder_prepared = false; // prepare_encode_kernels has run for this context (encoder_ready: on its first encode, so a context that never encodes never loads the encoder)
   std::mutex lock; // guards the staging buffers of the host-pointer entries
   std::mutex stream_lock; // creation of pipe_streams (hsrans_hpipe_create may run under `lock` or without it)
   hipStream_t stream = nullptr;
@@ -49,7 +47,7 @@ struct hsrans_ctx
   uint8_t *d_plan = nullptr;
   size_t d_plan_cap = 0;
   uint32_t *d_status = nullptr;
-  uint8_t *d_enc_scratch = nullptr; // hsrans_encode_device: block images, then {image_bytes, image_off, result}
+  uint8_t *d_enc_scratch = nullptr; // the GPU encoders' block images (slots)
   size_t d_enc_scratch_cap = 0;
   uint8_t *d_enc_meta = nullptr;
   size_t d_enc_meta_cap = 0;
@@ -268,6 +266,53 @@ int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stream_length, vo
 // part_words: a sharded decode's sub-runs in this one launch (completion words, sequence number; hsrans_comm.cpp)
 int dplan_launch_ranges(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_window, size_t window_offset, size_t window_length, void *d_out, size_t out_offset,
                         size_t out_length, void *hip_stream, const PartArgs *part_words);
+
+// ---- the GPU encoder's host side (hsrans_capi_encode.cpp): what hsrans_encode_device_raw, hsrans_encode_device, hsrans_encode_device_batch
+// and hsrans_encode_host_pipelined share, so that a batch member gets exactly what its single call would ----
+
+// under ctx->lock: the context's device made current and, on the context's first encode of any kind, prepare_encode_kernels run
+bool encoder_ready(hsrans_ctx *ctx);
+inline bool device_io_ok(const void *d_in, const void *d_out) // a device encode's input and output: set and 16-byte aligned
+{
+  return d_in != nullptr && d_out != nullptr && ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out & 15) == 0;
+}
+// what an encode of one raw or mt_ stream derives from its arguments before anything is launched
+struct EncShape
+{
+  uint32_t S = 0, bits = 0;
+  uint64_t n = 0, block = 0; // input bytes; symbols per block (raw: n)
+  uint32_t n_blocks = 1;
+  uint64_t slot_bytes = 0;   // per block (raw: the one slot)
+  uint32_t interval = 0;     // EncParams::interval
+  uint32_t max_ck = 0;       // EncParams::max_ck
+  size_t ck_slots = 1;       // checkpoint slots of the whole stream
+  // raw only
+  bool listed = false;    // checkpoints at the caller's groups rather than every `interval`
+  bool want_plan = false; // a plan was asked for and the stream gets checkpoints
+  size_t n_ck = 0;        // checkpoints the pass records
+  EncParams params(const void *d_in, void *d_out, size_t out_capacity) const; // the fields above, the input and the output
+};
+// the rules of a raw encode (hsrans_encode_device_raw's) but the pointers'; plan: a plan is asked for
+bool raw_shape(int states, uint32_t bits, size_t length, size_t out_capacity, const hsrans_hist *hist, uint32_t index_interval, const uint64_t *index_groups,
+               size_t n_index_groups, bool plan, EncShape *sh);
+// the rules of an mt_ encode in blocks of block_size symbols (hsrans_encode_device's) but the pointers'; plan: a plan is asked for (checkpoints only serve it)
+bool mt_shape(int states, uint32_t bits, size_t length, size_t out_capacity, uint32_t block_size, uint32_t index_interval, bool plan, EncShape *sh);
+// an mt_ stream's per-block arrays, laid out at `at` (16-byte aligned) for ep->n_blocks blocks: image_bytes, image_off [nb] u64, chain_count,
+// chain_off [nb] u32, fits (16 bytes, 16-byte aligned), raw_counts [nb][256] u32 (16-byte aligned)
+size_t mt_block_arrays_bytes(uint32_t n_blocks);
+void mt_block_arrays(EncParams *ep, uint8_t *at);
+// the header of an mt_ stream's plan from its encode's result words (EncParams::result) and ep's S, bits, n and interval; false: no plan in them
+bool mt_result_header(const EncParams &ep, const uint64_t *result, PlanHeader *h);
+// the device plan K_plan writes for an mt_ encode: its header (mt_result_header), the group split (ep->group_split), the plan object with the
+// header copied in on `s`, and ep->plan / groups / n_chains pointed at it; null on failure.  *h must live until `s` is synchronised.
+hsrans_dplan *mt_plan_begin(hsrans_ctx *ctx, EncParams *ep, const uint64_t *result, PlanHeader *h, hipStream_t s);
+// after K_plan (and `s` synchronised): the plan object takes over what the device wrote
+void mt_plan_adopt(hsrans_dplan *d, const EncParams &ep, const PlanHeader &h, hipStream_t s);
+// a raw encode's plan (what hsrans_encode_ex emits) from what came down: the stream's first 16 + 512 + 4 S bytes and the checkpoints' states and
+// positions, at sh's listed groups (index_groups) or every sh.interval.  Into plan_out (null: a buffer of its own); then *plan_size and, with
+// out_dplan, a device plan of it.  Returns the plan's size, 0 on failure.
+size_t raw_plan(hsrans_ctx *ctx, const EncShape &sh, uint64_t total, const uint64_t *index_groups, const uint8_t *header, const uint32_t *ck_states,
+                const uint32_t *ck_pos, uint8_t *plan_out, size_t plan_capacity, size_t *plan_size, hsrans_dplan **out_dplan);
 
 // a page-locked, device-mapped host range: the address the GPU reaches it at, else null (hsrans_capi.cpp)
 uint8_t *device_view_of_host(const void *ptr, size_t bytes);

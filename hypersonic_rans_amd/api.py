@@ -54,6 +54,16 @@ class LaunchInfo(ctypes.Structure):
                [("class_weights", _u32 * 8), ("dynamic_groups", _u32), ("spread", _u32)]
 
 
+class PlanKind(ctypes.Structure):
+    _fields_ = [(n, _u32) for n in ("container", "states", "bits", "flags")] + [("decoded_len", ctypes.c_uint64)] + \
+               [(n, _u32) for n in ("n_chains", "n_pieces", "shared_hist", "interval")]
+
+
+class LaunchFacts(ctypes.Structure):
+    _fields_ = [(n, _u32) for n in ("persistent", "table_mode", "dual", "n_groups", "groups_lean", "spread_min_block", "tickets", "index_pass", "single_valid",
+                                    "single_ring_entries", "calibrating", "parts", "n_parts", "dealt")]
+
+
 class BatchInfo(ctypes.Structure):
     _fields_ = [(n, _u32) for n in ("members", "launches", "direct_members", "solo_members", "grouped_members", "reserved", "grid", "block", "lds_bytes")] + \
                [("class_weights", _u32 * 8), ("imbalance", ctypes.c_double)]
@@ -179,6 +189,8 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_queue_pending.argtypes = [_vp]
     L.hsrans_queue_stats.restype = _i
     L.hsrans_queue_stats.argtypes = [_vp, ctypes.POINTER(QueueStats)]
+    L.hsrans_launch_choice.restype = _i
+    L.hsrans_launch_choice.argtypes = [_vp, ctypes.POINTER(PlanKind), ctypes.POINTER(LaunchFacts), ctypes.POINTER(LaunchInfo), ctypes.c_char_p, ctypes.c_size_t]
     L.hsrans_dealt_shares.restype = _i
     L.hsrans_dealt_shares.argtypes = [_vp, _u32, _vp, _u32, _u32, ctypes.c_uint64, _vp, _vp]
     L.hsrans_batch_deal.restype = ctypes.c_double
@@ -497,6 +509,22 @@ def dealt_shares(block_begin, total_groups: int, ctx: "Context | None" = None, b
     if rc < 0:
         raise HsransError("hsrans_dealt_shares: bad arguments")
     return rc == 1, begin, split
+
+
+def launch_choice(plan: dict, ctx: "Context | None" = None, **facts):
+    """hsrans_launch_choice: (kernel name, launch_info dict) of the single-plan decode launch a plan of these header fields (``plan``: PlanKind's
+    fields, 0 where left out) and launch facts (LaunchFacts' fields as keywords) would get; raises NotImplementedError / ValueError where the
+    launcher refuses it as not supported / as an invalid value."""
+    info, name = LaunchInfo(), ctypes.create_string_buffer(128)
+    rc = load_library().hsrans_launch_choice(ctx.handle if ctx is not None else None, ctypes.byref(PlanKind(**plan)), ctypes.byref(LaunchFacts(**facts)), ctypes.byref(info),
+                                             name, len(name))
+    if rc == 1:
+        raise NotImplementedError("hsrans_launch_choice: no kernel takes this launch")
+    if rc == 2:
+        raise ValueError("hsrans_launch_choice: the launcher refuses these values")
+    if rc != 0:
+        raise HsransError("hsrans_launch_choice: bad arguments")
+    return name.value.decode(), {n: (list(getattr(info, n)) if n == "class_weights" else getattr(info, n)) for n, _ in LaunchInfo._fields_}
 
 
 def index_boundaries_batch(states: int, bits: int, decoded_sizes, member: int, ctx: "Context | None" = None) -> np.ndarray:

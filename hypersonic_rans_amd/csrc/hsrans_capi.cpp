@@ -514,25 +514,66 @@ int hsrans_dplan_status(hsrans_ctx *ctx, hsrans_dplan *d, void *hip_stream)
   return HSRANS_E_DEVICE;
 }
 
+static void export_launch_info(const LaunchInfo &in, hsrans_launch_info *info)
+{
+  info->grid = in.grid;
+  info->block = in.block;
+  info->lds_bytes = in.lds_bytes;
+  info->waves_per_block = in.waves_per_block;
+  info->chains = in.chains;
+  info->shared_table = in.shared_table;
+  info->walk = in.walk;
+  info->two_level = in.two_level;
+  info->table_mode = in.table_mode;
+  info->chains_per_wave = in.chains_per_wave;
+  for (int k = 0; k < 8; k++)
+    info->class_weights[k] = in.class_weights[k];
+  info->dynamic_groups = in.dynamic_groups;
+  info->spread = in.spread;
+}
+
 int hsrans_dplan_launch_info(const hsrans_dplan *d, hsrans_launch_info *info)
 {
   if (d == nullptr || info == nullptr)
     return HSRANS_E_ARG;
-  info->grid = d->info.grid;
-  info->block = d->info.block;
-  info->lds_bytes = d->info.lds_bytes;
-  info->waves_per_block = d->info.waves_per_block;
-  info->chains = d->info.chains;
-  info->shared_table = d->info.shared_table;
-  info->walk = d->info.walk;
-  info->two_level = d->info.two_level;
-  info->table_mode = d->info.table_mode;
-  info->chains_per_wave = d->info.chains_per_wave;
-  for (int k = 0; k < 8; k++)
-    info->class_weights[k] = d->info.class_weights[k];
-  info->dynamic_groups = d->info.dynamic_groups;
-  info->spread = d->info.spread;
+  export_launch_info(d->info, info);
   return HSRANS_OK;
+}
+
+int hsrans_launch_choice(const hsrans_ctx *ctx, const hsrans_plan_kind *plan, const hsrans_launch_facts *facts, hsrans_launch_info *info, char *kernel_name, size_t name_capacity)
+{
+  if (plan == nullptr || facts == nullptr || info == nullptr || kernel_name == nullptr || !valid_codec((int)plan->container, (int)plan->states, plan->bits))
+    return -1;
+  const DeviceGeom dg = ctx ? ctx->geom : default_geom();
+  const Tuning tn = ctx ? ctx->tuning : read_tuning();
+  PlanHeader h{};
+  h.container = plan->container, h.states = plan->states, h.bits = plan->bits, h.flags = plan->flags;
+  h.decoded_len = plan->decoded_len;
+  h.n_chains = plan->n_chains, h.n_pieces = plan->n_pieces, h.shared_hist = plan->shared_hist, h.interval = plan->interval;
+  LaunchFacts f;
+  f.persistent = facts->persistent != 0;
+  f.table_mode = facts->table_mode;
+  f.interval = plan->interval;
+  f.dual = facts->dual != 0;
+  f.n_groups = facts->n_groups;
+  f.groups_lean = facts->groups_lean != 0;
+  f.spread_min_block = facts->spread_min_block;
+  f.index_pass = facts->index_pass != 0;
+  f.single_valid = facts->single_valid != 0;
+  f.single_ring_entries = facts->single_ring_entries;
+  f.calibrating = facts->calibrating != 0;
+  f.tickets = facts->tickets != 0;
+  f.parts = facts->parts != 0;
+  f.n_parts = facts->n_parts;
+  f.dealt = facts->dealt != 0;
+  if (f.dealt) // (the class weights dplan_launch deals such a plan with)
+    dealt_weights_now(tn, dg, plan->decoded_len / 64 / ((uint64_t)spread_grid(dg) * 16), plan->bits, f.dealt_weights);
+  const LaunchChoice c = choose_launch(tn, h, dg, f);
+  if (c.error != hipSuccess)
+    return c.error == hipErrorNotSupported ? 1 : 2;
+  export_launch_info(launch_info_of(c, h.n_chains), info);
+  snprintf(kernel_name, name_capacity, "%s", hsrans::kernel_name(c.kernel));
+  return 0;
 }
 
 int hsrans_dealt_shares(const hsrans_ctx *ctx, uint32_t bits, const uint32_t *block_begin, uint32_t n_blocks, uint32_t n_chains, uint64_t total_groups,

@@ -152,7 +152,11 @@ static int calibrate_impl(hsrans_ctx *ctx, uint32_t bits, uint32_t iterations, u
       PlanHeader h{};
       h.states = 64, h.bits = bits, h.shared_hist = 1, h.n_chains = 1u << 30;
       const TableChoice tc = choose_table(ctx->tuning, bits, 64, true);
-      const LaunchShape L = launch_shape(ctx->tuning, h, ctx->geom, true, tc.mode, 0, false, true, tc.dual);
+      LaunchFacts f;
+      f.persistent = true;
+      f.table_mode = tc.mode;
+      f.dual = tc.dual;
+      const LaunchShape L = launch_shape(ctx->tuning, h, ctx->geom, f);
       if (L.dual || L.waves != 16 || L.grid <= ctx->geom.num_cus) // not the launch shape the classes are defined for: nothing to fit
       {
         rc = HSRANS_E_ARG;

@@ -457,8 +457,7 @@ extern "C++" int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stre
   }
   // lean grouped plans of coded blocks: the host-dealt one-round launch where the plan suits it (dealt once per weight set)
   const DealtTable *dealt = nullptr;
-  if (d->n_groups && d->groups_lean && d->block_begin.size() >= 2 && (d->hdr.bits <= 11 || d->hdr.bits == 13 || d->hdr.bits == 14) && d->hdr.states == 64 &&
-      (d->hdr.bits <= 11 || d->tuning.dealt_wide))
+  if (d->block_begin.size() >= 2 && dealt_eligible(d->tuning, d->hdr, d->ctx->geom, launch_facts(kp, nullptr, nullptr)))
   {
     uint32_t w8[8];
     const uint64_t total_groups = (d->out_hi - d->out_lo) / 64; // (what THIS plan's chains decode: a rank's slice of a sharded stream, not the stream)

@@ -271,6 +271,70 @@ struct LaunchShape
   uint32_t weights[8]; // per-mille run length of the 8 wave classes
 };
 
+// What decides a launch besides the plan header, the device and the tuning: scalars only.  launch_facts reads them off a KParams, so
+// every caller of launch_decode describes its launch the same way; hsrans_launch_choice takes them as they are (tests, planning).
+struct LaunchFacts
+{
+  bool persistent = false;       // a kPlanMergeable plan: PersistentArgs is filled
+  uint32_t table_mode = 0;       // ... its host-built decode table (kMode*); 0: the kernel builds its own
+  uint32_t interval = 0;         // ... uniform chains of this many groups; 0: chains of any length, one (run) per wave
+  bool dual = false;             // ... two chains per wave (choose_table)
+  uint32_t n_groups = 0;         // grouped plan (block_/mt_ with checkpoints): its groups; 0: none
+  bool groups_lean = false;      // ... 64 states, every group a mergeable run or fills only
+  uint32_t spread_min_block = 0; // ... KParams::spread
+  bool index_pass = false;       // the launch records checkpoints (hsrans_capi_index.cpp)
+  bool single_valid = false;     // one chain of one rANS piece (SingleArgs::valid)
+  uint32_t single_ring_entries = 0;
+  bool calibrating = false;      // hsrans_ctx_calibrate's launches: per-wave finish times
+  bool tickets = false;          // grouped: the launch has a ticket counter
+  bool parts = false;            // a rank's sub-runs in one launch (PartPlan) ...
+  uint32_t n_parts = 0;          // ... so many: 1 .. kMaxLaunchParts, anything else is refused
+  bool dealt = false;            // the plan has a valid dealing (deal_shares) ...
+  uint32_t dealt_weights[8] = {}; // ... made with these class weights
+};
+
+// one value per kernel instantiation a single-plan decode launch can run (the table in hsrans_kernels.hip: name + launch)
+enum KernelId : uint32_t
+{
+  kKDecodePrivate,                   // + mode (kModePack .. kModeTwoLevel): k_decode<mode, false>
+  kKDecodeShared = kKDecodePrivate + 3, // + mode (kModePack .. kModeSpill): k_decode<mode, true>
+  kKDual = kKDecodeShared + 6,       // + 1: the rank table
+  kKPersist = kKDual + 2,            // + 1: the rank table
+  kKDirect = kKPersist + 2,          // + mode (kModePack .. kModeSpill)
+  kKCalibrate = kKDirect + 6,
+  kKGrouped,                         // + mode (kModePack .. kModeRank): k_decode_grouped<mode, false>
+  kKGroupedLean = kKGrouped + 5,     // + mode - kModeTwoLevel (.. kModeRank): <mode, true>
+  kKGroupedParts = kKGroupedLean + 3, // + mode - kModePack64 (.. kModeRank): <mode, true, true>
+  kKSpread = kKGroupedParts + 2,     // + 1: PARTS
+  kKDealtNt = kKSpread + 2,          // k_decode_dealt<false, false>
+  kKDealt,                           // <true, false>
+  kKDealtParts,                      // <true, true>
+  kKDealtRank,                       // + 2 * (bits - 13) + PARTS: k_decode_dealt_rank<bits, PARTS>
+  kKSingle = kKDealtRank + 4,
+  kKernelCount
+};
+
+// the static shares of a uniform-interval launch (PersistentArgs' fields of the same names)
+struct StaticShares
+{
+  uint32_t static_per_wave, run_len[8], class_off[8], wg_chains[2], half_base[2], static_total;
+};
+
+// Which kernel a single-plan launch runs and how: everything launch_decode needs that is not a pointer.
+struct LaunchChoice
+{
+  hipError_t error;      // hipSuccess, or what launch_decode returns without launching anything
+  KernelId kernel;
+  uint32_t grid, waves, lds; // of the launch (the spread and dealt launches have their own, not the shape's)
+  LaunchShape shape;     // (weights: what the launch's shares were sized with — the dealing's for k_decode_dealt)
+  uint32_t spread;       // LaunchInfo::spread: 0, 1 = k_decode_spread, 2 = k_decode_dealt
+  bool dynamic_groups;   // grouped: groups behind the first round go by ticket
+  uint16_t cum[2][17];   // grouped / spread: KParams::group_cum; dealt: DealtParams::cum
+  StaticShares shares;   // uniform-interval launches
+  uint32_t run_chains;   // one-chain-per-wave launches: PersistentArgs::run_chains
+  uint32_t gap_chains;   // dealt: DealtParams::gap_chains
+};
+
 // K2: device-side walk of an mt_ stream's header chain (mt_rANS32x64_16w_decode.cpp:41-96), the device twin of the host
 // planner.  Pass 1 (k_mt_chase, one wavefront) follows the chain with one 16-byte read per block and lists the blocks;
 // pass 2 (k_mt_fill, one wavefront per block) writes the plan blob.
@@ -332,7 +396,7 @@ hipError_t launch_index_assemble(const IndexArgs &a, hipStream_t stream);
 hipError_t launch_stream_checksum(const uint8_t *d_stream, uint64_t stream_len, uint64_t *d_sum, hipStream_t stream);
 
 DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
-LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, bool persistent, uint32_t table_mode, uint32_t n_groups, bool index_pass, bool direct, bool dual);
+LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f); // (reads persistent, table_mode, interval, dual, n_groups, index_pass)
 struct TableChoice
 {
   uint32_t mode; // 0: none (the kernel builds its own), else kMode* of the host-built table
@@ -349,12 +413,20 @@ uint32_t pack64_max_bits();
 // per device (call with the device current): raise the dynamic-LDS limit of every kernel variant to the gfx950 maximum
 // (160 KiB) and report the device's geometry
 hipError_t prepare_kernels(DeviceGeom *geom);
-// asynchronous on `stream` of the current device; no allocation, no synchronisation (graph-capturable)
+// A single-plan decode launch is decided in ONE place, choose_launch: a pure function of the tuning, the plan header, the device and the
+// LaunchFacts — no pointer, no HIP call, nothing written — that names the kernel (KernelId), its grid, workgroup and LDS, and the scalars
+// the kernel's parameters still need.  It is also where the launch is refused: `parts` with n == 0 or n > kMaxLaunchParts and shares a
+// uniform-interval launch cannot address are hipErrorInvalidValue, `parts` with a kernel that cannot count them (plans without groups,
+// groups that are not lean, tables other than the 8-byte and the rank table) hipErrorNotSupported.
+LaunchChoice choose_launch(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f);
+// whether k_decode_dealt can take the plan at all (lean grouped, single-piece chains, 64 states, <= 11 bits or 13 / 14 bits with
+// Tuning::dealt_wide, no index pass, two workgroups' LDS per CU): choose_launch's test, and dplan_launch's for whether dealing is worth doing
+bool dealt_eligible(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f);
+LaunchInfo launch_info_of(const LaunchChoice &c, uint32_t chains); // what hsrans_dplan_launch_info reports of the launch
+const char *kernel_name(KernelId k); // as rocprofv3 --kernel-trace prints it, without return type and parameter list
 // `parts` (may be null): the launch decodes a rank's sub-runs and publishes a completion word per sub-run (PartArgs).  In: n,
-// chain_end[], group_units[k] = groups of the plan's group list that overlap part k.  The launcher picks the kernel, works out how
-// many units of that kernel overlap each part, adds them to cum[k] (the running total over all launches of this plan: the
-// counters on the device are never reset) and hands the kernel cum[] as its targets.  Only plans the grouped (64 states, lean) or
-// the spread kernel takes: hipErrorNotSupported otherwise, nothing launched.
+// chain_end[], group_units[k] = groups of the plan's group list that overlap part k, cum[k] = the units counted into part k by all
+// launches of this plan so far (the counters on the device are never reset).
 struct PartPlan
 {
   uint32_t n;
@@ -362,10 +434,14 @@ struct PartPlan
   const uint32_t *group_units;
   uint32_t *cum;
 };
-// `dealt` (may be null): the plan's shares for k_decode_dealt, from deal_shares with this device's current weights; the launcher takes that
-// kernel when it is given (the caller has checked the plan: lean grouped, 64 states, <= 11 bits, no single-symbol blocks)
+LaunchFacts launch_facts(const KParams &kp, const PartPlan *parts, const uint32_t *dealt_weights /* null: no valid dealing */);
+// asynchronous on `stream` of the current device; no allocation, no synchronisation (graph-capturable).
+// facts (launch_facts) -> choice (choose_launch) -> the launch-dependent kernel parameters -> one launch through the kernel table ->
+// *info from the choice.  `dealt` + `dealt_weights` (both or neither): the plan's shares for k_decode_dealt and the class weights
+// they were dealt with (deal_shares).  `parts`: the units of the chosen kernel that overlap each part become its targets, cum[k] + units;
+// cum[] itself moves only once the launch has been queued (hipSuccess), so a refused launch leaves host and device totals in step.
 hipError_t launch_decode(const Tuning &tn, const KParams &kp, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts = nullptr,
-                         const DealtTable *dealt = nullptr, const uint32_t *dealt_weights = nullptr /* the 8 class weights `dealt` was made with */);
+                         const DealtTable *dealt = nullptr, const uint32_t *dealt_weights = nullptr);
 // The dealing of k_decode_dealt: block k = chains [block_begin[k], block_begin[k + 1]) (n_blocks + 1 entries, the last = n_chains), every one a coded
 // block of single-piece mergeable chains.  Workgroup shares by age-class weight (the one-chain-per-wave launch's, this device's own once
 // calibrated), each cut back where it would reach into a third block.  false: the plan does not suit the launch (too few chains for the

@@ -33,7 +33,7 @@
 //   kernels_dual.h      k_decode_dual      two chains per wave (13-15 bits)
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
 //   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device
-// This file: the host side — tuning constants, launch shapes, hsrans_index_boundaries' chain lengths, launch_decode.
+// This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -54,6 +54,10 @@
 #include "kernels_batch.h"
 #include "kernels_single.h"
 #include "kernels_walk.h"
+
+#include <array>
+#include <type_traits>
+#include <vector>
 
 namespace hsrans
 {
@@ -98,22 +102,74 @@ hipError_t launch_mt_fill(const uint8_t *d_stream, uint64_t stream_len, uint32_t
 // the tuning switches are a Tuning (hsrans_tuning.h) that every launch path is handed; the one constant left is exported
 static constexpr uint32_t g_pack64_max_bits = 14; // widest histogram decoded with the 8-byte-per-slot shared table (knob removed in round 5: settled)
 
-typedef void (*KernelFn)(KParams);
-static KernelFn kernel_for(int mode, bool shared)
+// The kernel table: every instantiation a single-plan decode launch can run (KernelId), its name as a kernel trace prints it, and its launch.
+// choose_launch picks the row, prepare_kernels raises every row's LDS limit, launch_decode launches through it: the one launch site.
+struct KernelEntry
 {
-  switch (mode * 2 + (shared ? 1 : 0))
-  {
-  case 0: return k_decode<kModePack, false>;
-  case 1: return k_decode<kModePack, true>;
-  case 2: return k_decode<kModePackM1, false>;
-  case 3: return k_decode<kModePackM1, true>;
-  case 4: return k_decode<kModeTwoLevel, false>;
-  case 5: return k_decode<kModeTwoLevel, true>;
-  case 8: case 9: return k_decode<kModeRank, true>;
-  case 10: case 11: return k_decode<kModeSpill, true>;
-  default: return k_decode<kModePack64, true>;
-  }
+  const char *name;
+  const void *fn;
+  void (*launch)(const LaunchChoice &c, hipStream_t stream, const KParams &kp, const DealtParams &dp, const DealtTable *dt);
+};
+template <auto K>
+static void launch_thunk(const LaunchChoice &c, hipStream_t stream, const KParams &kp, const DealtParams &dp, const DealtTable *dt)
+{
+  const auto go = [&](const auto &...args) { hipLaunchKernelGGL(K, dim3(c.grid), dim3(c.waves * 64), c.lds, stream, args...); };
+  if constexpr (std::is_invocable_v<decltype(K), KParams>)
+    go(kp);
+  else
+    go(dp, *dt); // (k_decode_dealt*: its own parameters + the dealing)
 }
+template <auto K>
+static KernelEntry entry(const char *name)
+{
+  return {name, (const void *)K, launch_thunk<K>};
+}
+static const std::array<KernelEntry, kKernelCount> g_kernels = [] {
+  std::array<KernelEntry, kKernelCount> t{};
+  // (rows in the order the kernels have always been instantiated, which is the order of the compiler's resource report, build/hsrans_kernels.remarks)
+  t[kKCalibrate] = entry<k_calibrate>("hsrans::k_calibrate");
+  t[kKSingle] = entry<k_decode_single>("hsrans::k_decode_single");
+  t[kKDecodePrivate + kModePack] = entry<k_decode<kModePack, false>>("hsrans::k_decode<0, false>");
+  t[kKDecodeShared + kModePack] = entry<k_decode<kModePack, true>>("hsrans::k_decode<0, true>");
+  t[kKDecodePrivate + kModePackM1] = entry<k_decode<kModePackM1, false>>("hsrans::k_decode<1, false>");
+  t[kKDecodeShared + kModePackM1] = entry<k_decode<kModePackM1, true>>("hsrans::k_decode<1, true>");
+  t[kKDecodePrivate + kModeTwoLevel] = entry<k_decode<kModeTwoLevel, false>>("hsrans::k_decode<2, false>");
+  t[kKDecodeShared + kModeTwoLevel] = entry<k_decode<kModeTwoLevel, true>>("hsrans::k_decode<2, true>");
+  t[kKDecodeShared + kModeRank] = entry<k_decode<kModeRank, true>>("hsrans::k_decode<4, true>");
+  t[kKDecodeShared + kModeSpill] = entry<k_decode<kModeSpill, true>>("hsrans::k_decode<5, true>");
+  t[kKDecodeShared + kModePack64] = entry<k_decode<kModePack64, true>>("hsrans::k_decode<3, true>");
+  t[kKPersist] = entry<k_decode_persist<kModePack64>>("hsrans::k_decode_persist<3>");
+  t[kKPersist + 1] = entry<k_decode_persist<kModeRank>>("hsrans::k_decode_persist<4>");
+  t[kKDual] = entry<k_decode_dual<kModePack64>>("hsrans::k_decode_dual<3>");
+  t[kKDual + 1] = entry<k_decode_dual<kModeRank>>("hsrans::k_decode_dual<4>");
+  t[kKDirect + kModePack] = entry<k_decode_direct<kModePack>>("hsrans::k_decode_direct<0>");
+  t[kKDirect + kModePackM1] = entry<k_decode_direct<kModePackM1>>("hsrans::k_decode_direct<1>");
+  t[kKDirect + kModeTwoLevel] = entry<k_decode_direct<kModeTwoLevel>>("hsrans::k_decode_direct<2>");
+  t[kKDirect + kModePack64] = entry<k_decode_direct<kModePack64>>("hsrans::k_decode_direct<3>");
+  t[kKDirect + kModeRank] = entry<k_decode_direct<kModeRank>>("hsrans::k_decode_direct<4>");
+  t[kKDirect + kModeSpill] = entry<k_decode_direct<kModeSpill>>("hsrans::k_decode_direct<5>");
+  t[kKGrouped + kModePack] = entry<k_decode_grouped<kModePack, false>>("hsrans::k_decode_grouped<0, false, false>");
+  t[kKGrouped + kModePackM1] = entry<k_decode_grouped<kModePackM1, false>>("hsrans::k_decode_grouped<1, false, false>");
+  t[kKGrouped + kModeTwoLevel] = entry<k_decode_grouped<kModeTwoLevel, false>>("hsrans::k_decode_grouped<2, false, false>");
+  t[kKGrouped + kModePack64] = entry<k_decode_grouped<kModePack64, false>>("hsrans::k_decode_grouped<3, false, false>");
+  t[kKGroupedLean] = entry<k_decode_grouped<kModeTwoLevel, true>>("hsrans::k_decode_grouped<2, true, false>");
+  t[kKGroupedLean + 1] = entry<k_decode_grouped<kModePack64, true>>("hsrans::k_decode_grouped<3, true, false>");
+  t[kKGrouped + kModeRank] = entry<k_decode_grouped<kModeRank, false>>("hsrans::k_decode_grouped<4, false, false>");
+  t[kKGroupedLean + 2] = entry<k_decode_grouped<kModeRank, true>>("hsrans::k_decode_grouped<4, true, false>");
+  t[kKSpread] = entry<k_decode_spread<kModePack64>>("hsrans::k_decode_spread<3, false>");
+  t[kKGroupedParts] = entry<k_decode_grouped<kModePack64, true, true>>("hsrans::k_decode_grouped<3, true, true>");
+  t[kKGroupedParts + 1] = entry<k_decode_grouped<kModeRank, true, true>>("hsrans::k_decode_grouped<4, true, true>");
+  t[kKSpread + 1] = entry<k_decode_spread<kModePack64, true>>("hsrans::k_decode_spread<3, true>");
+  t[kKDealt] = entry<k_decode_dealt<true, false>>("hsrans::k_decode_dealt<true, false>");
+  t[kKDealtNt] = entry<k_decode_dealt<false, false>>("hsrans::k_decode_dealt<false, false>");
+  t[kKDealtParts] = entry<k_decode_dealt<true, true>>("hsrans::k_decode_dealt<true, true>");
+  t[kKDealtRank] = entry<k_decode_dealt_rank<13, false>>("hsrans::k_decode_dealt_rank<13u, false>");
+  t[kKDealtRank + 1] = entry<k_decode_dealt_rank<13, true>>("hsrans::k_decode_dealt_rank<13u, true>");
+  t[kKDealtRank + 2] = entry<k_decode_dealt_rank<14, false>>("hsrans::k_decode_dealt_rank<14u, false>");
+  t[kKDealtRank + 3] = entry<k_decode_dealt_rank<14, true>>("hsrans::k_decode_dealt_rank<14u, true>");
+  return t;
+}();
+const char *kernel_name(KernelId k) { return g_kernels[k].name; }
 
 uint32_t pack64_max_bits() { return g_pack64_max_bits; }
 
@@ -181,25 +237,13 @@ hipError_t prepare_kernels(DeviceGeom *geom)
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
     geom->num_cus = (uint32_t)cus;
-  for (int mode = 0; mode < 6; mode++)
-    for (int shared = 0; shared < 2; shared++)
-    {
-      const hipError_t e = hipFuncSetAttribute((const void *)kernel_for(mode, shared != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geom->max_lds);
-      if (e != hipSuccess)
-        return e;
-    }
-  for (const void *fn : {(const void *)k_decode_single, (const void *)k_decode_persist<kModePack64>, (const void *)k_decode_persist<kModeRank>, (const void *)k_calibrate,
-                         (const void *)k_decode_dual<kModePack64>, (const void *)k_decode_dual<kModeRank>, (const void *)k_decode_direct<kModePack>, (const void *)k_decode_direct<kModePackM1>,
-                         (const void *)k_decode_direct<kModeTwoLevel>, (const void *)k_decode_direct<kModePack64>, (const void *)k_decode_direct<kModeRank>, (const void *)k_decode_direct<kModeSpill>,
-                         (const void *)k_decode_grouped<kModePack, false>, (const void *)k_decode_grouped<kModePackM1, false>, (const void *)k_decode_grouped<kModeTwoLevel, false>,
-                         (const void *)k_decode_grouped<kModePack64, false>, (const void *)k_decode_grouped<kModeTwoLevel, true>, (const void *)k_decode_grouped<kModePack64, true>,
-                         (const void *)k_decode_grouped<kModeRank, false>, (const void *)k_decode_grouped<kModeRank, true>, (const void *)k_decode_spread<kModePack64>,
-                         (const void *)k_decode_grouped<kModePack64, true, true>, (const void *)k_decode_grouped<kModeRank, true, true>, (const void *)k_decode_spread<kModePack64, true>,
-                         (const void *)k_decode_dealt<true, false>, (const void *)k_decode_dealt<false, false>, (const void *)k_decode_dealt<true, true>,
-                         (const void *)k_decode_dealt_rank<13, false>, (const void *)k_decode_dealt_rank<13, true>, (const void *)k_decode_dealt_rank<14, false>,
-                         (const void *)k_decode_dealt_rank<14, true>, (const void *)k_decode_batch<kModePack64>, (const void *)k_decode_grouped_batch<kModePack64>,
-                         (const void *)k_decode_batch_pair<kModePack64>, (const void *)k_decode_batch_dual<kModePack64>, (const void *)k_decode_batch_dual<kModeRank>,
-                         (const void *)k_calibrate_batch})
+  std::vector<const void *> fns;
+  for (const KernelEntry &k : g_kernels)
+    fns.push_back(k.fn);
+  for (const void *fn : {(const void *)k_decode_batch<kModePack64>, (const void *)k_decode_grouped_batch<kModePack64>, (const void *)k_decode_batch_pair<kModePack64>,
+                         (const void *)k_decode_batch_dual<kModePack64>, (const void *)k_decode_batch_dual<kModeRank>, (const void *)k_calibrate_batch})
+    fns.push_back(fn);
+  for (const void *fn : fns)
   {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geom->max_lds);
     if (e != hipSuccess)
@@ -331,10 +375,11 @@ bool deal_shares(const Tuning &tn, const DeviceGeom &dg, const uint32_t *block_b
 }
 
 // Everything about a launch that follows from the plan header and the device alone (no pointers): the table layout, the
-// workgroup shape and the grid.  launch_decode uses it; direct_boundaries uses it to size one chain per resident wave.
-LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, bool persistent, uint32_t table_mode, uint32_t n_groups, bool index_pass, bool direct,
-                         bool dual)
+// workgroup shape and the grid.  choose_launch starts from it; direct_boundaries uses it to size one chain per resident wave.
+LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f)
 {
+  const bool persistent = f.persistent, index_pass = f.index_pass, direct = persistent && f.interval == 0, dual = persistent && f.dual;
+  const uint32_t table_mode = persistent ? f.table_mode : 0, n_groups = f.n_groups;
   LaunchShape L{};
   const bool walk = (h.flags & kPlanWalk) != 0;
   const bool grouped = n_groups != 0 && !index_pass;
@@ -460,7 +505,11 @@ size_t direct_boundaries(const Tuning &tn, const DeviceGeom &dg, uint32_t states
   h.shared_hist = 1;
   h.n_chains = 1u << 30; // "many": the full machine
   const TableChoice tc = choose_table(tn, bits, states, true);
-  const LaunchShape L = launch_shape(tn, h, dg, true, tc.mode, 0, false, true, tc.dual);
+  LaunchFacts f;
+  f.persistent = true;
+  f.table_mode = tc.mode;
+  f.dual = tc.dual;
+  const LaunchShape L = launch_shape(tn, h, dg, f);
   const uint32_t runs_per_wave = (states == 32 || L.dual) ? 2 : 1;
   const uint64_t W = (uint64_t)L.grid * L.waves;
   uint64_t chains = W * runs_per_wave;
@@ -517,7 +566,11 @@ BatchShape batch_direct_shape(const Tuning &tn, const DeviceGeom &dg, uint32_t m
   // 13-15 bits (64 states): k_decode_dual's shape — one 16-wave workgroup per CU, two chains per wave, the 8-byte table at 13 bits,
   // the rank table at 14 / 15 — and its class lengths
   const bool wide = states == 64 && max_bits >= 13;
-  const LaunchShape L = launch_shape(tn, h, dg, true, wide && max_bits >= 14 ? kModeRank : kModePack64, 0, false, true, wide);
+  LaunchFacts f;
+  f.persistent = true;
+  f.table_mode = wide && max_bits >= 14 ? kModeRank : kModePack64;
+  f.dual = wide;
+  const LaunchShape L = launch_shape(tn, h, dg, f);
   BatchShape b{};
   b.kind = states == 32 ? kBatchPair : !wide ? kBatchDirect : max_bits >= 14 ? kBatchDualRank : kBatchDualPack;
   b.grid = L.grid;
@@ -574,7 +627,9 @@ BatchGroupShape batch_grouped_shape(const Tuning &tn, const DeviceGeom &dg, uint
   h.states = 64;
   h.bits = bits;
   h.n_chains = n_chains > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n_chains;
-  const LaunchShape L = launch_shape(tn, h, dg, false, 0, n_groups, false, false, false);
+  LaunchFacts f;
+  f.n_groups = n_groups;
+  const LaunchShape L = launch_shape(tn, h, dg, f);
   BatchGroupShape b{};
   b.grid = L.grid;
   b.waves = L.waves;
@@ -590,182 +645,145 @@ hipError_t launch_batch_grouped(const BatchGroupParams &bp, const BatchGroupShap
   return hipGetLastError();
 }
 
-static hipError_t launch_dealt(const Tuning &tn, const KParams &kp, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts, const DealtTable &dt,
-                               const uint32_t *w8)
+static uint32_t dealt_lds(uint32_t bits) // 16 rings + two tables (rank tables from 13 bits on) + 2 KiB
 {
-  DealtParams dp{};
-  dp.stream = kp.stream;
-  dp.stream_len = kp.stream_len;
-  dp.stream_lo = kp.stream_lo;
-  dp.out = kp.out;
-  dp.out_cap = kp.out_cap;
-  dp.pieces = (const Piece *)(kp.plan + plan_pieces_off(h.n_chains));
-  dp.states = (const uint32_t *)(kp.plan + plan_states_off(h.n_chains, h.n_chains));
-  dp.status = kp.status;
-  dp.stamps = kp.stamps;
-  dp.n_chains = h.n_chains;
-  dp.bits = h.bits;
-  const uint32_t grid = spread_grid(dg);
-  cum_from_weights(w8, dp.cum); // (the weights the shares were dealt with)
-  // a second prologue costs Tuning::dealt_gap_groups groups of decoding
-  const uint64_t per_chain = h.interval ? h.interval : h.n_chains ? (uint64_t)h.decoded_len / 64 / h.n_chains : 0; // groups per chain: the index interval (a sliced plan keeps the stream's header)
-  dp.gap_chains = per_chain ? (uint32_t)((tn.dealt_gap_groups + per_chain / 2) / per_chain) : 0;
-  const bool rank = h.bits >= 13; // (13 / 14 bits: two rank tables, k_decode_dealt_rank)
-  const uint32_t lds = kSpreadWaves * kFastRingBytes + 2 * table_bytes_for(rank ? kModeRank : kModePack64, h.bits) + 2048;
-  if (parts != nullptr)
-  {
-    dp.parts = kp.parts;
-    dp.parts.n = parts->n;
-    uint32_t begin = 0;
-    for (uint32_t k = 0; k < parts->n; k++)
-    {
-      const uint32_t end = parts->chain_end[k];
-      uint32_t units = 0; // workgroups whose share overlaps part k (run_dealt counts itself by the same rule)
-      for (uint32_t b = 0; b < grid && end > begin; b++)
-        units += dt.begin[b + 1] > dt.begin[b] && dt.begin[b] < end && dt.begin[b + 1] > begin ? 1 : 0;
-      dp.parts.chain_end[k] = end;
-      dp.parts.target[k] = (parts->cum[k] += units);
-      begin = end > begin ? end : begin;
-    }
-  }
-  if (info)
-  {
-    *info = LaunchInfo{};
-    info->grid = grid;
-    info->block = kSpreadWaves * 64;
-    info->lds_bytes = lds;
-    info->waves_per_block = kSpreadWaves;
-    info->chains = h.n_chains;
-    info->shared_table = 1;
-    info->table_mode = (uint32_t)(rank ? kModeRank : kModePack64);
-    info->chains_per_wave = 1;
-    for (uint32_t k = 0; k < 8; k++)
-      info->class_weights[k] = w8[k];
-    info->spread = 2;
-  }
-  (void)hipGetLastError();
-  if (rank && h.bits == 13 && parts != nullptr)
-    hipLaunchKernelGGL((k_decode_dealt_rank<13, true>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  else if (rank && h.bits == 13)
-    hipLaunchKernelGGL((k_decode_dealt_rank<13, false>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  else if (rank && parts != nullptr)
-    hipLaunchKernelGGL((k_decode_dealt_rank<14, true>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  else if (rank)
-    hipLaunchKernelGGL((k_decode_dealt_rank<14, false>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  else if (parts != nullptr)
-    hipLaunchKernelGGL((k_decode_dealt<true, true>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  else if (tn.dealt_wt)
-    hipLaunchKernelGGL((k_decode_dealt<true, false>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  else
-    hipLaunchKernelGGL((k_decode_dealt<false, false>), dim3(grid), dim3(kSpreadWaves * 64), lds, stream, dp, dt);
-  return hipGetLastError();
+  return kSpreadWaves * kFastRingBytes + 2 * table_bytes_for(bits >= 13 ? kModeRank : kModePack64, bits) + 2048;
 }
 
-hipError_t launch_decode(const Tuning &tn, const KParams &kp_in, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts, const DealtTable *dealt,
-                         const uint32_t *dealt_weights)
+bool dealt_eligible(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f)
 {
-  KParams kp = kp_in;
-  if (parts != nullptr && (parts->n == 0 || parts->n > kMaxLaunchParts))
-    return hipErrorInvalidValue;
-  if (dealt != nullptr && dealt_weights != nullptr && kp.groups != nullptr && kp.groups_lean && kp.ckpt_interval == 0 && kp.ckpt_groups == nullptr && h.states == 64 &&
-      (h.bits <= 11 || h.bits == 13 || h.bits == 14) && h.n_pieces == h.n_chains &&
-      2 * (kSpreadWaves * kFastRingBytes + 2 * table_bytes_for(h.bits >= 13 ? kModeRank : kModePack64, h.bits) + 2048) <= dg.max_lds)
-    return launch_dealt(tn, kp, h, dg, stream, info, parts, *dealt, dealt_weights);
-  const bool persistent = kp.pa.pieces != nullptr;
-  const bool index_pass = kp.ckpt_interval != 0 || kp.ckpt_groups != nullptr;
-  const LaunchShape L = launch_shape(tn, h, dg, persistent, persistent && kp.pa.table != nullptr ? kp.pa.table_mode : 0, kp.groups != nullptr ? kp.n_groups : 0, index_pass, persistent && kp.pa.interval == 0, persistent && kp.pa.dual != 0);
-  const bool grouped = kp.groups != nullptr && !index_pass;
-  const uint32_t waves = L.waves, grid = L.grid;
-  kp.private_pair = L.private_pair;
+  return f.n_groups != 0 && f.groups_lean && !f.index_pass && h.states == 64 && (h.bits <= 11 || h.bits == 13 || h.bits == 14) && (h.bits <= 11 || tn.dealt_wide) &&
+         h.n_pieces == h.n_chains && 2 * dealt_lds(h.bits) <= dg.max_lds;
+}
 
-  if (grouped)
-    group_cum_of(L, kp.group_cum);
-  if (persistent && kp.pa.interval != 0)
+LaunchFacts launch_facts(const KParams &kp, const PartPlan *parts, const uint32_t *dealt_weights)
+{
+  LaunchFacts f;
+  f.persistent = kp.pa.pieces != nullptr;
+  f.table_mode = kp.pa.table != nullptr ? kp.pa.table_mode : 0;
+  f.interval = kp.pa.interval;
+  f.dual = kp.pa.dual != 0;
+  f.n_groups = kp.groups != nullptr ? kp.n_groups : 0;
+  f.groups_lean = kp.groups_lean != 0;
+  f.spread_min_block = kp.spread;
+  f.index_pass = kp.ckpt_interval != 0 || kp.ckpt_groups != nullptr;
+  f.single_valid = kp.single.valid != 0;
+  f.single_ring_entries = kp.single.ring_entries;
+  f.calibrating = kp.finish != nullptr;
+  f.tickets = kp.group_tickets != nullptr;
+  f.parts = parts != nullptr;
+  f.n_parts = parts != nullptr ? parts->n : 0;
+  f.dealt = dealt_weights != nullptr;
+  if (f.dealt)
+    memcpy(f.dealt_weights, dealt_weights, sizeof(f.dealt_weights));
+  return f;
+}
+
+// a uniform-interval launch's static shares: the chains split over the waves by class weight; what rounding leaves goes through the queues.
+// false: shares the kernel cannot address
+static bool static_shares(const PlanHeader &h, const LaunchShape &L, uint32_t interval, StaticShares *st)
+{
+  const uint64_t W = (uint64_t)L.grid * L.waves;
+  // 32-state streams: two runs per wave (run_persistent_pair)
+  st->static_per_wave = (uint32_t)((uint64_t)h.n_chains / (h.states == 32 ? 2 * W : W));
+  const uint32_t first_half = (L.grid + 1) / 2, second_half = L.grid - first_half;
+  const uint32_t per_class = L.waves >= 4 ? L.waves / 4 : 1, classes = L.waves / per_class;
+  const uint32_t runs_per_wave = h.states == 32 ? 2 : 1; // run_persistent_pair decodes two runs side by side
+  uint32_t longest = 0;
+  for (uint32_t hf = 0; hf < 2; hf++)
   {
-    // static share: the chains split over the waves by class weight; what rounding leaves goes through the queues
-    const uint64_t W = (uint64_t)grid * waves;
-    // 32-state streams: two runs per wave (run_persistent_pair)
-    kp.pa.static_per_wave = (uint32_t)((uint64_t)h.n_chains / (h.states == 32 ? 2 * W : W));
-    const uint32_t first_half = (grid + 1) / 2, second_half = grid - first_half;
-    const uint32_t per_class = waves >= 4 ? waves / 4 : 1, classes = waves / per_class;
-    const uint32_t runs_per_wave = h.states == 32 ? 2 : 1; // run_persistent_pair decodes two runs side by side
-    uint32_t longest = 0;
-    for (uint32_t hf = 0; hf < 2; hf++)
+    uint32_t off = 0;
+    for (uint32_t k = 0; k < 4; k++)
     {
-      uint32_t off = 0;
-      for (uint32_t k = 0; k < 4; k++)
-      {
-        kp.pa.run_len[hf * 4 + k] = k < classes ? (uint32_t)((uint64_t)h.n_chains * L.weights[hf * 4 + k] / (1000 * W * runs_per_wave)) : 0;
-        kp.pa.class_off[hf * 4 + k] = off;
-        off += kp.pa.run_len[hf * 4 + k] * per_class * runs_per_wave;
-        longest = kp.pa.run_len[hf * 4 + k] > longest ? kp.pa.run_len[hf * 4 + k] : longest;
-      }
-      kp.pa.wg_chains[hf] = off;
+      st->run_len[hf * 4 + k] = k < classes ? (uint32_t)((uint64_t)h.n_chains * L.weights[hf * 4 + k] / (1000 * W * runs_per_wave)) : 0;
+      st->class_off[hf * 4 + k] = off;
+      off += st->run_len[hf * 4 + k] * per_class * runs_per_wave;
+      longest = st->run_len[hf * 4 + k] > longest ? st->run_len[hf * 4 + k] : longest;
     }
-    kp.pa.half_base[0] = 0;
-    kp.pa.half_base[1] = first_half * kp.pa.wg_chains[0];
-    kp.pa.static_total = first_half * kp.pa.wg_chains[0] + second_half * kp.pa.wg_chains[1];
-    if (kp.pa.static_total > h.n_chains) // weights sum to <= 8000 by construction; belt and braces
-      return hipErrorInvalidValue;
-    // a merged run is read through one 32-bit window of the stream (at most one 16-bit word per symbol)
-    if ((uint64_t)(longest ? longest : 1) * kp.pa.interval * h.states * 2 >= 0xFFFF0000ull)
-      return hipErrorInvalidValue;
+    st->wg_chains[hf] = off;
   }
-  if (persistent && kp.pa.interval == 0)
+  st->half_base[0] = 0;
+  st->half_base[1] = first_half * st->wg_chains[0];
+  st->static_total = first_half * st->wg_chains[0] + second_half * st->wg_chains[1];
+  if (st->static_total > h.n_chains) // weights sum to <= 8000 by construction; belt and braces
+    return false;
+  // a merged run is read through one 32-bit window of the stream (at most one 16-bit word per symbol)
+  return (uint64_t)(longest ? longest : 1) * interval * h.states * 2 < 0xFFFF0000ull;
+}
+
+LaunchChoice choose_launch(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f)
+{
+  LaunchChoice c{};
+  c.error = hipSuccess;
+  if (f.parts && (f.n_parts == 0 || f.n_parts > kMaxLaunchParts))
+  {
+    c.error = hipErrorInvalidValue;
+    return c;
+  }
+  if (f.dealt && dealt_eligible(tn, h, dg, f))
+  {
+    // the host-dealt one-round launch (kernels_dealt.h): 13 / 14 bits with two rank tables, a kernel per width
+    const bool rank = h.bits >= 13;
+    c.kernel = rank ? KernelId(kKDealtRank + 2 * (h.bits - 13) + (f.parts ? 1 : 0)) : f.parts ? kKDealtParts : tn.dealt_wt ? kKDealt : kKDealtNt;
+    c.grid = c.shape.grid = spread_grid(dg);
+    c.waves = c.shape.waves = kSpreadWaves;
+    c.lds = c.shape.lds = dealt_lds(h.bits);
+    c.shape.mode = rank ? kModeRank : kModePack64;
+    c.shape.shared = true;
+    memcpy(c.shape.weights, f.dealt_weights, sizeof(c.shape.weights));
+    c.spread = 2;
+    cum_from_weights(f.dealt_weights, c.cum); // (the weights the shares were dealt with)
+    // a second prologue costs Tuning::dealt_gap_groups groups of decoding
+    const uint64_t per_chain = h.interval ? h.interval : h.n_chains ? (uint64_t)h.decoded_len / 64 / h.n_chains : 0; // groups per chain: the index interval (a sliced plan keeps the stream's header)
+    c.gap_chains = per_chain ? (uint32_t)((tn.dealt_gap_groups + per_chain / 2) / per_chain) : 0;
+    return c;
+  }
+  const LaunchShape &L = c.shape = launch_shape(tn, h, dg, f);
+  const bool grouped = f.n_groups != 0 && !f.index_pass;
+  c.grid = L.grid;
+  c.waves = L.waves;
+  c.lds = L.lds;
+  if (grouped)
+    group_cum_of(L, c.cum);
+  if (f.persistent && f.interval != 0 && !static_shares(h, L, f.interval, &c.shares))
+  {
+    c.error = hipErrorInvalidValue;
+    return c;
+  }
+  if (f.persistent && f.interval == 0)
   {
     // one-chain-per-wave launches: the plan's chains as W runs of consecutive chains (run_direct); 32-state and two-chain launches keep their own dealing
-    const uint64_t W = (uint64_t)grid * waves;
-    kp.pa.run_chains = h.states == 64 && !L.dual ? (uint32_t)((h.n_chains + W - 1) / W) : 1;
+    const uint64_t W = (uint64_t)L.grid * L.waves;
+    c.run_chains = h.states == 64 && !L.dual ? (uint32_t)((h.n_chains + W - 1) / W) : 1;
   }
-  if (kp.single.valid && !index_pass && tn.single_fast)
+  if (f.single_valid && !f.index_pass && tn.single_fast)
   {
     // one chain of one piece (a raw stream without an index): the two-wave latency kernel
-    const uint32_t lds = (8u << h.bits) + (kp.single.ring_entries + kSingleMirror) * 16 + 64;
-    if (info)
-    {
-      *info = LaunchInfo{};
-      info->grid = 1;
-      info->block = 128;
-      info->lds_bytes = lds;
-      info->waves_per_block = 2;
-      info->chains = 1;
-      info->table_mode = kModePack64;
-      info->chains_per_wave = 1;
-    }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_decode_single, dim3(1), dim3(128), lds, stream, kp);
-    return hipGetLastError();
+    c.kernel = kKSingle;
+    c.shape = LaunchShape{};
+    c.shape.mode = kModePack64;
+    c.grid = c.shape.grid = 1;
+    c.waves = c.shape.waves = 2;
+    c.lds = c.shape.lds = (8u << h.bits) + (f.single_ring_entries + kSingleMirror) * 16 + 64;
+    return c;
   }
-  KernelFn fn = kernel_for(L.mode, L.shared);
+  const bool wide_table = L.mode == kModePack64 || L.mode == kModeRank; // what k_decode_dual, k_decode_persist and the PARTS kernels are built for
   if (L.dual)
-    fn = L.mode == kModeRank ? (KernelFn)k_decode_dual<kModeRank> : (KernelFn)k_decode_dual<kModePack64>;
-  else if (persistent && kp.pa.interval != 0 && L.shared && (L.mode == kModePack64 || L.mode == kModeRank) && kp.pa.table != nullptr && !index_pass)
-    fn = L.mode == kModeRank ? (KernelFn)k_decode_persist<kModeRank> : (KernelFn)k_decode_persist<kModePack64>;
-
+    c.kernel = KernelId(kKDual + (L.mode == kModeRank ? 1 : 0));
+  else if (f.persistent && f.interval != 0 && L.shared && wide_table && f.table_mode != 0 && !f.index_pass)
+    c.kernel = KernelId(kKPersist + (L.mode == kModeRank ? 1 : 0));
   else if (grouped && L.shared)
-    switch (L.mode)
-    {
-    case kModePack: fn = k_decode_grouped<kModePack, false>; break;
-    case kModePackM1: fn = k_decode_grouped<kModePackM1, false>; break;
-    case kModeTwoLevel: fn = kp.groups_lean ? k_decode_grouped<kModeTwoLevel, true> : k_decode_grouped<kModeTwoLevel, false>; break;
-    case kModeRank: fn = kp.groups_lean ? k_decode_grouped<kModeRank, true> : k_decode_grouped<kModeRank, false>; break;
-    default: fn = kp.groups_lean ? k_decode_grouped<kModePack64, true> : k_decode_grouped<kModePack64, false>; break;
-    }
-  else if (persistent && kp.pa.interval == 0 && L.shared)
-    switch (L.mode)
-    {
-    case kModePack: fn = k_decode_direct<kModePack>; break;
-    case kModePackM1: fn = k_decode_direct<kModePackM1>; break;
-    case kModeTwoLevel: fn = k_decode_direct<kModeTwoLevel>; break;
-    case kModeRank: fn = k_decode_direct<kModeRank>; break;
-    case kModeSpill: fn = k_decode_direct<kModeSpill>; break;
-    default: fn = kp.finish != nullptr && h.states == 64 ? (KernelFn)k_calibrate : (KernelFn)k_decode_direct<kModePack64>; break;
-    }
-  // grouped plans with few, large blocks (kp.spread: the fewest chains of a block, where the host found the plan eligible): every
+  {
+    const int m = L.mode == kModeSpill ? kModePack64 : L.mode;
+    c.kernel = f.groups_lean && m >= kModeTwoLevel ? KernelId(kKGroupedLean + m - kModeTwoLevel) : KernelId(kKGrouped + m);
+  }
+  else if (f.persistent && f.interval == 0 && L.shared)
+    c.kernel = L.mode == kModePack64 && f.calibrating && h.states == 64 ? kKCalibrate : KernelId(kKDirect + L.mode);
+  else
+    c.kernel = L.shared || L.mode >= kModePack64 ? KernelId(kKDecodeShared + L.mode) : KernelId(kKDecodePrivate + L.mode);
+  // grouped plans with few, large blocks (spread_min_block: the fewest chains of a block, where the host found the plan eligible): every
   // resident workgroup takes its share of ALL chains and builds the one or two tables it needs (kernels_spread.h)
-  uint32_t launch_grid = grid, launch_waves = waves, launch_lds = L.lds;
-  bool spread = false;
-  if (grouped && L.shared && kp.spread != 0 && kp.groups_lean && L.mode == kModePack64 && tn.spread)
+  if (grouped && L.shared && f.spread_min_block != 0 && f.groups_lean && L.mode == kModePack64 && tn.spread)
   {
     uint16_t spread_cum[2][17];
     // k_decode_spread's wave weights: the one-chain-per-wave launch's (the device's own once calibrated); one snapshot, the same weights
@@ -773,71 +791,139 @@ hipError_t launch_decode(const Tuning &tn, const KParams &kp_in, const PlanHeade
     cum_from_weights(dg.have_direct_weights ? dg.direct_weights : tn.direct_weights, spread_cum);
     const uint32_t longest = spread_longest_share_of(dg, h.n_chains, spread_cum);
     const uint32_t slds = kSpreadWaves * kFastRingBytes + 2 * table_bytes_for(kModePack64, h.bits) + (kSpreadMaxShare + 1) * (uint32_t)sizeof(Piece);
-    if (longest != 0 && longest < kp.spread && 2 * slds <= dg.max_lds) // (a share shorter than every block touches at most two)
+    if (longest != 0 && longest < f.spread_min_block && 2 * slds <= dg.max_lds) // (a share shorter than every block touches at most two)
     {
-      spread = true;
-      fn = k_decode_spread<kModePack64>;
-      launch_grid = spread_grid(dg);
-      launch_waves = kSpreadWaves;
-      launch_lds = slds;
-      memcpy(kp.group_cum, spread_cum, sizeof(kp.group_cum));
+      c.spread = 1;
+      c.kernel = kKSpread;
+      c.grid = spread_grid(dg);
+      c.waves = kSpreadWaves;
+      c.lds = slds;
+      memcpy(c.cum, spread_cum, sizeof(c.cum));
+    }
+  }
+  if (f.parts)
+  {
+    // a rank's sub-runs in one launch: only the kernels that count their units into the sub-runs (PartArgs)
+    if (c.spread)
+      c.kernel = KernelId(kKSpread + 1);
+    else if (grouped && L.shared && f.groups_lean && wide_table)
+      c.kernel = KernelId(kKGroupedParts + L.mode - kModePack64);
+    else
+      c.error = hipErrorNotSupported;
+  }
+  c.dynamic_groups = grouped && !c.spread && f.tickets && f.n_groups > L.grid;
+  return c;
+}
+
+LaunchInfo launch_info_of(const LaunchChoice &c, uint32_t chains)
+{
+  LaunchInfo info{};
+  info.grid = c.grid;
+  info.block = c.waves * 64;
+  info.lds_bytes = c.lds;
+  info.waves_per_block = c.waves;
+  info.chains = chains;
+  info.shared_table = c.shape.shared;
+  info.walk = c.shape.walk;
+  info.two_level = c.shape.mode == kModeTwoLevel;
+  info.table_mode = (uint32_t)c.shape.mode;
+  info.chains_per_wave = c.shape.dual ? 2 : 1;
+  for (uint32_t k = 0; k < 8; k++)
+    info.class_weights[k] = c.shape.weights[k];
+  info.dynamic_groups = c.dynamic_groups ? 1 : 0;
+  info.spread = c.spread;
+  return info;
+}
+
+// The targets of a sub-run launch: part k is complete once cum[k] + units[k] units have counted themselves into it, units[k] = the launch's
+// units that overlap the part.  A unit of the spread and dealt launches is a workgroup's share of the chains, [share_begin(b),
+// share_begin(b + 1)) for b < grid (the kernels count themselves by the same rule); grid == 0: the grouped launch, whose units are the plan's
+// groups (PartPlan::group_units).
+template <typename ShareBegin>
+static void part_targets(const PartPlan &parts, uint32_t grid, ShareBegin share_begin, PartArgs *out, uint32_t units[kMaxLaunchParts])
+{
+  out->n = parts.n;
+  uint32_t begin = 0;
+  for (uint32_t k = 0; k < parts.n; k++)
+  {
+    const uint32_t end = parts.chain_end[k];
+    units[k] = grid ? 0 : parts.group_units[k];
+    for (uint32_t b = 0; b < grid && end > begin; b++)
+    {
+      const uint32_t c0 = share_begin(b), c1 = share_begin(b + 1);
+      units[k] += c1 > c0 && c0 < end && c1 > begin ? 1 : 0;
+    }
+    out->chain_end[k] = end;
+    out->target[k] = parts.cum[k] + units[k];
+    begin = end > begin ? end : begin;
+  }
+}
+
+hipError_t launch_decode(const Tuning &tn, const KParams &kp_in, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts, const DealtTable *dealt,
+                         const uint32_t *dealt_weights)
+{
+  const LaunchChoice c = choose_launch(tn, h, dg, launch_facts(kp_in, parts, dealt != nullptr ? dealt_weights : nullptr));
+  if (c.error != hipSuccess)
+    return c.error;
+  KParams kp = kp_in;
+  DealtParams dp; // (k_decode_dealt's own parameters: filled for that launch only)
+  uint32_t units[kMaxLaunchParts];
+  if (c.spread == 2)
+  {
+    dp = DealtParams{};
+    dp.stream = kp.stream;
+    dp.stream_len = kp.stream_len;
+    dp.stream_lo = kp.stream_lo;
+    dp.out = kp.out;
+    dp.out_cap = kp.out_cap;
+    dp.pieces = (const Piece *)(kp.plan + plan_pieces_off(h.n_chains));
+    dp.states = (const uint32_t *)(kp.plan + plan_states_off(h.n_chains, h.n_chains));
+    dp.status = kp.status;
+    dp.stamps = kp.stamps;
+    dp.n_chains = h.n_chains;
+    dp.bits = h.bits;
+    memcpy(dp.cum, c.cum, sizeof(dp.cum));
+    dp.gap_chains = c.gap_chains;
+    if (parts != nullptr)
+    {
+      dp.parts = kp.parts;
+      part_targets(*parts, c.grid, [&](uint32_t b) { return dealt->begin[b]; }, &dp.parts, units);
+    }
+  }
+  else
+  {
+    kp.private_pair = c.shape.private_pair;
+    if (kp.groups != nullptr && kp.ckpt_interval == 0 && kp.ckpt_groups == nullptr) // (grouped and spread launches)
+      memcpy(kp.group_cum, c.cum, sizeof(kp.group_cum));
+    if (kp.pa.pieces != nullptr && kp.pa.interval != 0)
+    {
+      kp.pa.static_per_wave = c.shares.static_per_wave;
+      memcpy(kp.pa.run_len, c.shares.run_len, sizeof(kp.pa.run_len));
+      memcpy(kp.pa.class_off, c.shares.class_off, sizeof(kp.pa.class_off));
+      memcpy(kp.pa.wg_chains, c.shares.wg_chains, sizeof(kp.pa.wg_chains));
+      memcpy(kp.pa.half_base, c.shares.half_base, sizeof(kp.pa.half_base));
+      kp.pa.static_total = c.shares.static_total;
+    }
+    if (kp.pa.pieces != nullptr && kp.pa.interval == 0)
+      kp.pa.run_chains = c.run_chains;
+    if (c.spread == 1)
+    {
       kp.pa.n_chains = h.n_chains; // (single-piece chains: n_pieces == n_chains)
       kp.pa.S = h.states;
       kp.pa.bits = h.bits;
     }
-  }
-  if (parts != nullptr)
-  {
-    // a rank's sub-runs in one launch: only the kernels that count their units into the sub-runs (PartArgs)
-    if (spread)
-      fn = k_decode_spread<kModePack64, true>;
-    else if (grouped && L.shared && kp.groups_lean && L.mode == kModePack64)
-      fn = k_decode_grouped<kModePack64, true, true>;
-    else if (grouped && L.shared && kp.groups_lean && L.mode == kModeRank)
-      fn = k_decode_grouped<kModeRank, true, true>;
-    else
-      return hipErrorNotSupported;
-    kp.parts.n = parts->n;
-    uint32_t begin = 0;
-    for (uint32_t k = 0; k < parts->n; k++)
-    {
-      const uint32_t end = parts->chain_end[k];
-      uint32_t units = parts->group_units[k];
-      if (spread) // workgroups whose share of the chains overlaps part k (run_spread counts itself by the same rule)
-      {
-        units = 0;
-        for (uint32_t b = 0; b < launch_grid && end > begin; b++)
-        {
-          const uint32_t c0 = spread_share_begin(h.n_chains, b, launch_grid, kp.group_cum[0][launch_waves], kp.group_cum[1][launch_waves]);
-          const uint32_t c1 = spread_share_begin(h.n_chains, b + 1, launch_grid, kp.group_cum[0][launch_waves], kp.group_cum[1][launch_waves]);
-          units += c1 > c0 && c0 < end && c1 > begin ? 1 : 0;
-        }
-      }
-      kp.parts.chain_end[k] = end;
-      kp.parts.target[k] = (parts->cum[k] += units);
-      begin = end > begin ? end : begin;
-    }
+    if (parts != nullptr)
+      part_targets(*parts, c.spread ? c.grid : 0, [&](uint32_t b) { return spread_share_begin(h.n_chains, b, c.grid, c.cum[0][c.waves], c.cum[1][c.waves]); }, &kp.parts, units);
   }
   if (info)
-  {
-    info->grid = launch_grid;
-    info->block = launch_waves * 64;
-    info->lds_bytes = launch_lds;
-    info->waves_per_block = launch_waves;
-    info->chains = h.n_chains;
-    info->shared_table = L.shared;
-    info->walk = L.walk;
-    info->two_level = L.mode == kModeTwoLevel;
-    info->table_mode = (uint32_t)L.mode;
-    info->chains_per_wave = L.dual ? 2 : 1;
-    for (uint32_t k = 0; k < 8; k++)
-      info->class_weights[k] = L.weights[k];
-    info->dynamic_groups = grouped && !spread && kp.group_tickets != nullptr && kp.n_groups > grid ? 1 : 0;
-    info->spread = spread ? 1 : 0;
-  }
+    *info = launch_info_of(c, h.n_chains);
   (void)hipGetLastError(); // (sticky per thread: an earlier failed call — e.g. an allocation a hostile stream asked for — is not this launch's error)
-  hipLaunchKernelGGL(fn, dim3(launch_grid), dim3(launch_waves * 64), launch_lds, stream, kp);
-  return hipGetLastError();
+  g_kernels[c.kernel].launch(c, stream, kp, dp, dealt);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess && parts != nullptr) // (only now: a launch that was refused has counted nothing on the device)
+    for (uint32_t k = 0; k < parts->n; k++)
+      parts->cum[k] += units[k];
+  return e;
 }
 
 } // namespace hsrans

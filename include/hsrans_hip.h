@@ -587,6 +587,35 @@ int hsrans_dealt_shares(const hsrans_ctx *ctx, uint32_t bits /* the class length
                         const uint32_t *block_begin, uint32_t n_blocks, uint32_t n_chains, uint64_t total_groups, uint32_t *begin_out /* [513] */,
                         uint16_t *split_out /* [512] */);
 
+/* Which kernel a single-plan decode launch of a plan would run, and with what geometry, without a device (tests, planning): the launcher's
+ * own decision (choose_launch in csrc/hsrans_kernels.hip), on the MI355X defaults (ctx != NULL: that context's device and switches).
+ * `plan`: the plan-header fields that matter.  `facts`: what the launcher otherwise reads off the device plan it is handed.
+ * Returns 0 and fills *info and kernel_name (the demangled name as a kernel trace prints it, without return type and parameter list,
+ * e.g. "hsrans::k_decode_direct<3>"); 1: the launch would be refused as not supported, 2: as an invalid value (nothing is filled in);
+ * < 0 on bad arguments. */
+typedef struct hsrans_plan_kind
+{
+  uint32_t container, states, bits, flags; /* flags: 1 walk, 2 mergeable, 4 carries its histogram */
+  uint64_t decoded_len;
+  uint32_t n_chains, n_pieces, shared_hist, interval;
+} hsrans_plan_kind;
+typedef struct hsrans_launch_facts
+{
+  uint32_t persistent;          /* a mergeable plan (raw with an index): chains of plan->interval groups, or of any length (0) */
+  uint32_t table_mode, dual;    /* ... its host-built decode table (hsrans_launch_info.table_mode; 0: none) and two chains per wave */
+  uint32_t n_groups;            /* block_/mt_ plan with checkpoints: its groups (a block, or a part of one); 0: none */
+  uint32_t groups_lean;         /* ... 64 states, every group a run of single-piece chains or a single-symbol block */
+  uint32_t spread_min_block;    /* ... the fewest chains of a coded block that is neither first nor last; 0: k_decode_spread cannot take the plan */
+  uint32_t tickets;             /* ... the launch has a ticket counter for the groups behind the first round */
+  uint32_t index_pass;          /* the launch records checkpoints */
+  uint32_t single_valid, single_ring_entries; /* one chain of one rANS piece (a raw stream without an index) and its ring size */
+  uint32_t calibrating;         /* hsrans_ctx_calibrate's launches */
+  uint32_t parts, n_parts;      /* a sharded decode's sub-runs in one launch, and how many */
+  uint32_t dealt;               /* the plan has a valid dealing (hsrans_dealt_shares returned 1) */
+} hsrans_launch_facts;
+int hsrans_launch_choice(const hsrans_ctx *ctx /* may be NULL: MI355X defaults, as hsrans_dealt_shares */, const hsrans_plan_kind *plan, const hsrans_launch_facts *facts,
+                         hsrans_launch_info *info, char *kernel_name, size_t name_capacity);
+
 /* diagnostics: with HSRANS_DEBUG_STAMPS=1 in the environment every wavefront of a persistent / direct launch records
  * s_memtime stamps {entry, table built, stream ready, done, static share done} in 8 slots; copies up to capacity_u64 values to
  * `out`, returns the count */

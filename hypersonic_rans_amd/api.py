@@ -83,6 +83,14 @@ class ShardedInfo(ctypes.Structure):
                 ("one_launch", _u32), ("reserved", _u32)]
 
 
+class Range(ctypes.Structure):  # hsrans_range
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64)]
+
+
+class GatherTask(ctypes.Structure):  # hsrans_gather_task
+    _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("dst_delta", ctypes.c_int64)]
+
+
 COMM_ID_BYTES = 128
 SHARD_DECODE_ONLY, SHARD_DECODE_AND_EXCHANGE, SHARD_EXCHANGE_ONLY = 0, 1, 2
 
@@ -189,6 +197,12 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_queue_pending.argtypes = [_vp]
     L.hsrans_queue_stats.restype = _i
     L.hsrans_queue_stats.argtypes = [_vp, ctypes.POINTER(QueueStats)]
+    L.hsrans_decode_device_gather.restype = _i
+    L.hsrans_decode_device_gather.argtypes = [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp]
+    L.hsrans_gather_segment.restype = ctypes.c_uint64
+    L.hsrans_gather_segment.argtypes = [ctypes.c_uint64, _u32, _u32, _u32]
+    L.hsrans_gather_tasks.restype = _sz
+    L.hsrans_gather_tasks.argtypes = [ctypes.c_uint64, _u32, _u32, _u32, _vp, _u32, _vp, _sz]
     L.hsrans_launch_choice.restype = _i
     L.hsrans_launch_choice.argtypes = [_vp, ctypes.POINTER(PlanKind), ctypes.POINTER(LaunchFacts), ctypes.POINTER(LaunchInfo), ctypes.c_char_p, ctypes.c_size_t]
     L.hsrans_dealt_shares.restype = _i
@@ -552,6 +566,31 @@ def shard_layout(plan, world: int, parts: int = 1, weights=None):
     return out, [(int(windows[2 * r]), int(windows[2 * r + 1])) for r in range(world)]
 
 
+def _ranges_array(ranges) -> np.ndarray:
+    """(N, 3) uint64, C-contiguous: the memory layout of hsrans_range[N]"""
+    arr = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 3))
+    return arr
+
+
+def gather_segment(decoded_len: int, n_chains: int, states: int, interval: int) -> int:
+    """hsrans_gather_segment: the segment length L a gather's ranges are cut at (absolute multiples of it); 0 for n_chains == 0."""
+    return int(load_library().hsrans_gather_segment(decoded_len, n_chains, states, interval))
+
+
+def gather_tasks(decoded_len: int, n_chains: int, states: int, interval: int, ranges, capacity: int | None = None) -> np.ndarray:
+    """hsrans_gather_tasks: the one-wave tasks ``ranges`` ((N, 3) uint64 or a list of (offset, length, dst_offset)) are cut into, as an
+    (M, 3) array of (begin, end, dst_delta) (dst_delta as uint64, modulo 2^64).  Pure host arithmetic; an empty array for invalid input.
+    ``capacity``: write at most so many tasks (the C call's protocol: the array then holds min(capacity, M) rows)."""
+    L = load_library()
+    arr = _ranges_array(ranges)
+    n = L.hsrans_gather_tasks(decoded_len, n_chains, states, interval, _p(arr) if arr.size else None, arr.shape[0], None, 0)
+    rows = n if capacity is None else min(n, capacity)
+    out = np.zeros((rows, 3), np.uint64)
+    if rows:
+        L.hsrans_gather_tasks(decoded_len, n_chains, states, interval, _p(arr), arr.shape[0], _p(out), rows)
+    return out
+
+
 def batch_deal(chain_starts, grid: int = 512, waves: int = 16, weights=None):
     """hsrans_batch_deal: how one launch's wave slots would be dealt to members whose chains start at ``chain_starts[m]`` (groups,
     ascending, last entry = the member's total).  Returns (imbalance, slots[grid * waves, 4] = member, first chain, end chain, flags)."""
@@ -903,6 +942,22 @@ class Context:
                                                 out_offset, out_length, ctypes.c_void_p(s.cuda_stream))
         if rc != 0:
             raise HsransError(f"hsrans_decode_device_ranges failed with code {rc}")
+
+    def decode_device_gather(self, dplan: DevicePlan, d_stream: torch.Tensor, ranges, d_dst: torch.Tensor, stream_length: int | None = None,
+                             stream: torch.cuda.Stream | None = None):
+        """Byte ranges of a stream that stays compressed on the GPU, one launch (hsrans_decode_device_gather): for every row
+        (offset, length, dst_offset) of ``ranges`` ((N, 3) uint64 or a list of triples) the decoded bytes [offset, offset + length) land at
+        d_dst[dst_offset:]; no other byte of ``d_dst`` is written.  Asynchronous on ``stream`` (default: torch's current stream); ``ranges`` is
+        read before the call returns.  Destinations that overlap are the caller's responsibility.  Raises HsransError (``.code``: 2 bad
+        argument or range, 3 a plan without entry points or a wrong stream length)."""
+        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
+        arr = _ranges_array(ranges)
+        rc = self.L.hsrans_decode_device_gather(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                                _p(arr) if arr.size else None, arr.shape[0], d_dst.data_ptr(), d_dst.numel(), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_gather failed with code {rc}")
+            err.code = rc
+            raise err
 
     # -- K independent streams, one launch -------------------------------------------------------------------------
     def make_batch(self, dplans) -> Batch:

@@ -236,6 +236,13 @@ void hsrans_ctx_destroy(hsrans_ctx *ctx)
     (void)hipHostFree(ctx->h_enc_result);
   if (ctx->h_pipe_result)
     (void)hipHostFree(ctx->h_pipe_result);
+  if (ctx->d_gather)
+    (void)hipFree(ctx->d_gather);
+  if (ctx->h_gather)
+    (void)hipHostFree(ctx->h_gather);
+  for (hipEvent_t ev : ctx->gather_ev)
+    if (ev)
+      (void)hipEventDestroy(ev);
   for (hipStream_t st : ctx->pipe_streams)
     if (st)
       (void)hipStreamDestroy(st);

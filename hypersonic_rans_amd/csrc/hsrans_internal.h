@@ -60,6 +60,14 @@ struct hsrans_ctx
   uint64_t *h_enc_result = nullptr; // page-locked, device-mapped: hsrans_encode_device's kernels write their result words straight into it (no copy kernel, no second launch gap); under `lock`
   uint8_t *h_pin = nullptr; // page-locked staging of hsrans_decode_device_indexing (checkpoints down, plan blob up); under `lock`
   size_t h_pin_cap = 0;
+  // hsrans_decode_device_gather's task lists (hsrans_capi_gather.cpp), under `lock`: a page-locked host buffer and its device twin, used as
+  // two halves by region; gather_ev[k] = the last launch that read half k
+  uint8_t *d_gather = nullptr, *h_gather = nullptr;
+  size_t d_gather_cap = 0, h_gather_cap = 0, gather_cursor = 0;
+  hipEvent_t gather_ev[2] = {nullptr, nullptr};
+  bool gather_ev_used[2] = {false, false}, gather_have_last = false;
+  hipStream_t gather_last_stream = nullptr;
+  uint32_t gather_last_half = 0;
   uint8_t *h_pipe_result = nullptr; // page-locked, device-mapped: hsrans_encode_host_pipelined's carry start and per-slice result words; under `lock`
   size_t h_pipe_result_cap = 0;
 };

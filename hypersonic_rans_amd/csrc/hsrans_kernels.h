@@ -395,6 +395,40 @@ hipError_t launch_index_assemble(const IndexArgs &a, hipStream_t stream);
 // 64-bit fingerprint of d_stream[0, stream_len) into *d_sum (16-byte aligned stream; asynchronous: memset + one launch)
 hipError_t launch_stream_checksum(const uint8_t *d_stream, uint64_t stream_len, uint64_t *d_sum, hipStream_t stream);
 
+// ---- byte ranges of one stream in one launch (kernels_gather.h, hsrans_capi_gather.cpp) --------------------------------------
+// one wave's work: decoded bytes [begin, end) of the stream go to GatherParams::dst + byte + dst_delta
+struct GatherTask // == hsrans_gather_task (include/hsrans_hip.h)
+{
+  uint64_t begin, end;
+  int64_t dst_delta;
+};
+static_assert(sizeof(GatherTask) == 24, "GatherTask layout");
+struct GatherParams
+{
+  const uint8_t *stream; // device, 16-byte aligned
+  uint64_t stream_len;
+  uint8_t *dst; // device, any alignment
+  const uint8_t *plan;
+  uint32_t *status;
+  const GatherTask *tasks; // device
+  uint32_t n_tasks;
+  // shared-table launches only: the plan's host-built table, the counts it was made from and where the stream keeps them
+  const uint2 *table;
+  const uint16_t *hist_copy;
+  uint64_t hist_off;
+};
+struct GatherShape
+{
+  int mode;    // decode-table layout (kMode*)
+  bool shared; // one LDS table per workgroup, copied from the plan's host-built table; else a table per wave, built from the pieces' histograms
+  uint32_t waves, lds, grid;
+};
+// the launch of n_tasks tasks on a plan: table_mode = the plan's host-built table (PersistentArgs::table_mode; 0: it has none).  The table
+// layout is the one the plan decodes with: its host-built table's, else what launch_shape gives a plan whose waves build their own.
+GatherShape gather_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t n_tasks);
+// asynchronous on `stream`; one launch
+hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipStream_t stream);
+
 DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
 LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f); // (reads persistent, table_mode, interval, dual, n_groups, index_pass)
 struct TableChoice

@@ -33,6 +33,7 @@
 //   kernels_dual.h      k_decode_dual      two chains per wave (13-15 bits)
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
 //   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device
+//   kernels_gather.h    k_gather           byte ranges of one stream: one wave per task, entered at the chain that holds its first byte
 // This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,6 +55,7 @@
 #include "kernels_batch.h"
 #include "kernels_single.h"
 #include "kernels_walk.h"
+#include "kernels_gather.h"
 
 #include <array>
 #include <type_traits>
@@ -229,6 +231,24 @@ size_t build_rank_table(const uint16_t counts[256], uint32_t bits, uint2 *out, s
   return cumul == (1u << bits) ? rank_table_entries(bits) : 0;
 }
 
+// hsrans_decode_device_gather's kernels: a table per wave in the three layouts waves build for themselves, one table per workgroup in the
+// three layouts the host builds (choose_table)
+struct GatherKernel
+{
+  int mode;
+  bool shared;
+  const void *fn;
+  void (*launch)(const GatherParams &gp, const GatherShape &shape, hipStream_t stream);
+};
+template <int MODE, bool SHARED>
+static GatherKernel gather_entry()
+{
+  return {MODE, SHARED, (const void *)k_gather<MODE, SHARED>,
+          [](const GatherParams &gp, const GatherShape &shape, hipStream_t stream) { hipLaunchKernelGGL((k_gather<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, gp); }};
+}
+static const GatherKernel g_gather_kernels[] = {gather_entry<kModePack, false>(),  gather_entry<kModePackM1, false>(), gather_entry<kModeTwoLevel, false>(),
+                                                gather_entry<kModePack64, true>(), gather_entry<kModeRank, true>(),    gather_entry<kModeSpill, true>()};
+
 // per device (the CURRENT device): dynamic-LDS limit of every kernel variant, CU count
 hipError_t prepare_kernels(DeviceGeom *geom)
 {
@@ -243,6 +263,8 @@ hipError_t prepare_kernels(DeviceGeom *geom)
   for (const void *fn : {(const void *)k_decode_batch<kModePack64>, (const void *)k_decode_grouped_batch<kModePack64>, (const void *)k_decode_batch_pair<kModePack64>,
                          (const void *)k_decode_batch_dual<kModePack64>, (const void *)k_decode_batch_dual<kModeRank>, (const void *)k_calibrate_batch})
     fns.push_back(fn);
+  for (const GatherKernel &g : g_gather_kernels)
+    fns.push_back(g.fn);
   for (const void *fn : fns)
   {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geom->max_lds);
@@ -924,6 +946,50 @@ hipError_t launch_decode(const Tuning &tn, const KParams &kp_in, const PlanHeade
     for (uint32_t k = 0; k < parts->n; k++)
       parts->cum[k] += units[k];
   return e;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_gather's launch: a function of its own, beside choose_launch / launch_decode and touching neither
+// ---------------------------------------------------------------------------------------------------------------
+GatherShape gather_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t n_tasks)
+{
+  GatherShape g{};
+  g.shared = table_mode != 0;
+  if (g.shared)
+    g.mode = (int)table_mode; // what choose_table gave the plan when it was filled
+  else
+  {
+    // the layout launch_shape gives a plan whose waves build their own tables
+    PlanHeader hp = h;
+    hp.shared_hist = 0;
+    hp.flags &= ~kPlanWalk;
+    g.mode = launch_shape(tn, hp, dg, LaunchFacts{}).mode;
+  }
+  const uint32_t table_bytes = table_bytes_for(g.mode, h.bits);
+  const uint32_t wave_bytes = g.shared ? kWaveRingBytes : kWaveRingBytes + ((table_bytes + 15) & ~15u);
+  const uint32_t fixed = g.shared ? table_bytes : 0;
+  // few tasks: smaller workgroups, so that they reach more CUs (a task is one wave's work whatever the workgroup)
+  uint32_t waves = g.shared ? 16 : 4;
+  while (waves > 1 && (waves * wave_bytes + fixed > (g.shared ? dg.max_lds : dg.max_lds / 2) || (waves > (g.shared ? 4u : 1u) && (n_tasks + waves - 1) / waves < 2 * dg.num_cus)))
+    waves /= 2;
+  g.waves = waves;
+  g.lds = waves * wave_bytes + fixed;
+  g.grid = (n_tasks + waves - 1) / waves;
+  return g;
+}
+
+hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipStream_t stream)
+{
+  if (shape.grid == 0 || shape.lds > 160 * 1024)
+    return hipErrorInvalidValue;
+  for (const GatherKernel &g : g_gather_kernels)
+    if (g.mode == shape.mode && g.shared == shape.shared)
+    {
+      (void)hipGetLastError();
+      g.launch(gp, shape, stream);
+      return hipGetLastError();
+    }
+  return hipErrorNotSupported;
 }
 
 } // namespace hsrans

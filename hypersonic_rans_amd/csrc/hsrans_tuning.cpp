@@ -85,6 +85,8 @@ Tuning read_tuning()
   t.debug_stamps = set("HSRANS_DEBUG_STAMPS");
   t.hpipe_trace = set("HSRANS_HPIPE_TRACE");
   t.indexing_trace = set("HSRANS_INDEXING_TRACE");
+  if (set("HSRANS_GATHER_MIN_SEGMENT") && atoi(e) >= 64 && atoi(e) <= (1 << 30))
+    t.gather_min_segment = (uint32_t)atoi(e);
   return t;
 }
 

@@ -77,6 +77,7 @@ struct Tuning
   bool debug_stamps = false;          // HSRANS_DEBUG_STAMPS: per-wave time stamps (diagnostic library) and the encoders' phase times
   bool hpipe_trace = false;           // HSRANS_HPIPE_TRACE: per-slice timeline of a host pipeline on stderr
   bool indexing_trace = false;        // HSRANS_INDEXING_TRACE: phase times of an indexing decode on stderr
+  uint32_t gather_min_segment = 0;    // HSRANS_GATHER_MIN_SEGMENT: floor of a gather task's segment in decoded bytes, 64 .. 2^30 (0: kGatherMinSegment; tools/gather_rate.py sweeps it), read per device plan
 };
 
 // the switches as the environment sets them now (about 3 us)

@@ -1,0 +1,259 @@
+// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather) — gather_groups, gather_tail, run_gather, k_gather.
+// Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the host-side launcher).
+//
+// One wavefront = one task (GatherTask: decoded bytes [begin, end) of the stream, destination = GatherParams::dst + byte + dst_delta).  The
+// wave finds the last chain that starts at or before `begin` (binary search over the chains' first output bytes), enters it at its
+// start states and decodes forward, chain after chain, until `end`: groups in front of `begin` are decoded and dropped, everything
+// else is stored clipped to the task, and nothing outside [begin, end) is ever written.
+#ifndef HSRANS_KERNELS_GATHER_H
+#define HSRANS_KERNELS_GATHER_H
+
+namespace hsrans
+{
+
+// ring_advance for a loop that may not store at all: the wait that holds whatever else the wave has issued.  Younger than the request for
+// chunk k + 1 are the requests for k + 2 .. k + HSRANS_RING_AHEAD (and perhaps a mirror: stricter), so "all but AHEAD - 1 done" implies it.
+__device__ __forceinline__ void gather_advance(const StreamWin &sw, Ring &r, const WaveCtx &c)
+{
+  if ((r.cur >> (r.clog - 1)) > r.k)
+  {
+    r.k++;
+    ring_request(sw, r, c, r.k + HSRANS_RING_AHEAD);
+    if (HSRANS_RING_AHEAD == 3)
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+  }
+}
+
+// `steps` whole groups of a piece whose next symbol is decoded byte o, clipped to [begin, end); stops behind the group that holds
+// end - 1 (the wave has nothing more to decode then: its states are left mid-piece).  c.out is the task's destination of decoded byte 0.
+//   in front of begin     decoded, nothing stored (the non-storing form of run_groups_impl's loop)
+//   wholly inside         4 groups -> in-quad transpose -> one dword per lane, where the destination of the piece's groups is 4-byte
+//                         aligned; else a byte per lane and group
+//   the edges             a byte per lane under the lane's own test begin <= byte < end
+template <int MODE, bool FULL>
+__device__ __forceinline__ void gather_groups(uint32_t &x, const StreamWin &sw, Ring &r, const WaveCtx &c, uint64_t &o_ref, uint32_t steps, uint64_t begin, uint64_t end)
+{
+  uint64_t o = uni64(o_ref);
+  const uint32_t S = FULL ? 64 : c.S;
+  const bool act = FULL || c.lane < S;
+  const unsigned long long act_mask = FULL ? ~0ull : __builtin_amdgcn_ballot_w64(act);
+  constexpr uint32_t kSymByte = (MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) ? 3 : 0;
+
+  if (o + S <= begin)
+  {
+    const uint64_t in_front = groups_of(S, begin - o);
+    uint32_t skip = in_front < steps ? (uint32_t)in_front : steps;
+    steps -= skip;
+    o += (uint64_t)skip * S;
+    for (; skip >= 4; skip -= 4)
+    {
+      group_step<MODE, FULL>(x, r, c, act_mask);
+      group_step<MODE, FULL>(x, r, c, act_mask);
+      group_step<MODE, FULL>(x, r, c, act_mask);
+      group_step<MODE, FULL>(x, r, c, act_mask);
+      gather_advance(sw, r, c);
+    }
+    for (; skip > 0; skip--)
+      group_step<MODE, FULL>(x, r, c, act_mask);
+    gather_advance(sw, r, c);
+  }
+
+  const OutLanes ol = out_lanes(c.lane, S);
+  const uint32_t p = lane_to_byte(c.lane);
+  const bool aligned = uni((uint32_t)((uintptr_t)c.out + o) & 3u) == 0; // (S is a multiple of 4: the same for every group of the piece)
+  while (steps > 0 && o < end)
+  {
+    if (aligned && steps >= 4 && o >= begin && o + 4 * S <= end)
+    {
+      const uint32_t e0 = group_step<MODE, FULL>(x, r, c, act_mask);
+      const uint32_t e1 = group_step<MODE, FULL>(x, r, c, act_mask);
+      const uint32_t e2 = group_step<MODE, FULL>(x, r, c, act_mask);
+      const uint32_t e3 = group_step<MODE, FULL>(x, r, c, act_mask);
+      const uint32_t acc = pack4<kSymByte>(e0, e1, e2, e3, ol);
+      if (act)
+        HSRANS_STORE_U32((uint32_t *)(c.out + o + ol.store_off), acc);
+      o += 4 * S;
+      steps -= 4;
+    }
+    else
+    {
+      const uint32_t e = group_step<MODE, FULL>(x, r, c, act_mask);
+      const uint64_t b = o + p;
+      if (act && b >= begin && b < end)
+        c.out[b] = (uint8_t)(e >> (8 * kSymByte));
+      o += S;
+      steps--;
+    }
+    gather_advance(sw, r, c);
+  }
+  o_ref = o;
+}
+
+// the final masked group of a piece (run_tail), clipped
+template <int MODE>
+__device__ __forceinline__ void gather_tail(uint32_t &x, Ring &r, const WaveCtx &c, uint64_t o, uint32_t tail, uint64_t begin, uint64_t end)
+{
+  const uint32_t p = lane_to_byte(c.lane);
+  const bool act = c.lane < c.S && p < tail;
+  const uint32_t e = group_step<MODE, false>(x, r, c, __builtin_amdgcn_ballot_w64(act));
+  const uint64_t b = o + p;
+  if (act && b >= begin && b < end)
+    c.out[b] = (uint8_t)(e >> ((MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) ? 24 : 0));
+}
+
+// the task of one wave.  SHARED: c.table holds the plan's one table already.
+template <int MODE, bool SHARED>
+__device__ void run_gather(WaveCtx &c, const PlanView &pv, const GatherParams &gp, uint32_t task)
+{
+  const uint64_t begin = uni64(gp.tasks[task].begin), end = uni64(gp.tasks[task].end);
+  c.out = gp.dst + (int64_t)uni64((uint64_t)gp.tasks[task].dst_delta);
+  const uint32_t n_chains = uni(pv.hdr->n_chains);
+  if (begin >= end || n_chains == 0)
+    return;
+  // the last chain whose first output byte is <= begin (chain 0 where there is none: a plan that starts later writes nothing in front of itself)
+  uint32_t lo = 0, hi = n_chains;
+  while (hi - lo > 1)
+  {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (uni64(pv.pieces[uni(pv.chain_first[mid])].out_off) <= begin)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  uint32_t x = 0;
+  uint64_t have_hist = ~(uint64_t)0, o = 0;
+  bool live = false; // the ring stands right behind the last whole group of the piece before, whose decoding ended at output byte o
+  StreamWin sw;
+  Ring r;
+  ring_bind(r, c.rings, 9, false);
+  for (uint32_t chain = lo; chain < n_chains; chain++)
+  {
+    const uint32_t first = uni(pv.chain_first[chain]), last = uni(pv.chain_first[chain + 1]);
+    for (uint32_t pi = first; pi < last; pi++)
+    {
+      const Piece *pc = pv.pieces + pi;
+      const uint32_t flags = uni(pc->flags);
+      const uint64_t out_off = uni64(pc->out_off);
+      if (out_off >= end) // (pieces ascend in the output: nothing behind this one is the task's)
+        return;
+      if (flags & kPieceFill)
+      {
+        if (flags & kPieceChainStart)
+          x = c.lane < c.S ? pv.states[(uint64_t)uni(pc->state_idx) * c.S + c.lane] : 0;
+        const uint64_t f_end = out_off + uni64(pc->fill_len);
+        const uint64_t f0 = out_off > begin ? out_off : begin, f1 = f_end < end ? f_end : end;
+        if (f0 < f1)
+          wave_fill(c, f0, f1 - f0, (uint32_t)uni64(pc->hist_off) & 0xFF);
+        live = false;
+        continue;
+      }
+      const uint64_t hist_off = uni64(pc->hist_off), words_off = uni64(pc->words_off);
+      // a chain that starts exactly where this wave stands — same histogram, next output byte, next stream word — is the checkpoint of the
+      // states the wave already holds: it decodes on without a new prologue (what kPlanMergeable promises of a whole plan, found per chain here)
+      const bool cont = live && flags == kPieceChainStart && (SHARED || hist_off == have_hist) && out_off == o && words_off == ring_pos(sw, r);
+      if (!cont)
+      {
+        if (flags & kPieceChainStart)
+          x = c.lane < c.S ? pv.states[(uint64_t)uni(pc->state_idx) * c.S + c.lane] : 0;
+        if (!SHARED && hist_off != have_hist)
+        {
+          if (uni(build_table<MODE, false>(c, hist_off, c.lane, 64) ? 1u : 0u) == 0) // (the same on every lane; said so, for the window and ring below live across this exit)
+            return;
+          have_hist = hist_off;
+        }
+        ring_init(sw, r, c, words_off, x);
+      }
+      o = out_off;
+      if (c.S == 64)
+        gather_groups<MODE, true>(x, sw, r, c, o, uni(pc->steps), begin, end);
+      else
+        gather_groups<MODE, false>(x, sw, r, c, o, uni(pc->steps), begin, end);
+      if (o >= end)
+        return;
+      const uint32_t tail = uni(pc->tail);
+      if (tail != 0)
+        gather_tail<MODE>(x, r, c, o, tail, begin, end);
+      live = tail == 0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the kernel: blockDim.x = 64 * waves; wave w of block b runs task b * waves + w
+// LDS: SHARED  -> [waves x ring][table] (the rank table first, as k_decode has it);   otherwise -> [waves x ring][waves x table]
+// ---------------------------------------------------------------------------------------------------------------
+template <int MODE, bool SHARED>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_gather(GatherParams gp)
+{
+  extern __shared__ u32x4 smem_v[];
+  uint8_t *smem = (uint8_t *)smem_v;
+
+  const PlanView pv = plan_view(gp.plan);
+  const uint32_t waves = blockDim.x >> 6;
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const uint32_t bits = pv.hdr->bits;
+  const uint32_t table_bytes = table_bytes_for(MODE, bits);
+
+  WaveCtx c;
+  c.stream = gp.stream;
+  c.stream_len = gp.stream_len;
+  c.stream_lo = 0;
+  c.out = gp.dst;
+  c.out_cap = 0; // (not used: every store of this kernel is tested against its task)
+  c.status = gp.status;
+  c.bits = bits;
+  c.S = pv.hdr->states;
+  c.lane = threadIdx.x & 63;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
+  const uint32_t task = blockIdx.x * waves + wave;
+
+  if (SHARED)
+  {
+    uint8_t *ring0 = table_first_mode(MODE) ? smem + table_bytes : smem;
+    c.rings = ring0 + wave * kWaveRingBytes;
+    c.table = table_first_mode(MODE) ? smem : smem + waves * kWaveRingBytes;
+    c.table_b = c.table;
+    c.gtable = gp.table;
+    c.scratch_cnt = (uint16_t *)ring0;
+    c.scratch_cum = (uint16_t *)(ring0 + 512);
+    // the host-built table: one coalesced 16-byte load + LDS store per thread (none for the table that stays in global memory), while the
+    // launch's first wave checks that the stream carries the histogram it was built from (run_persistent)
+    const uint32_t entries = table_bytes / 8;
+    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
+      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(gp.table + i);
+    if (blockIdx.x == 0 && threadIdx.x < 64)
+    {
+      bool same = HSRANS_HIST_IN_RANGE(c, gp.hist_off);
+      if (same)
+      {
+        const uint64_t mine = *(const uint64_t *)(gp.hist_copy + 4 * c.lane);
+        uint64_t theirs = 0;
+        for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
+          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + gp.hist_off + 8 * c.lane + 2 * b);
+        same = mine == theirs;
+      }
+      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
+        atomicOr(c.status, kStatusBadHist);
+    }
+    __syncthreads();
+  }
+  else
+  {
+    const uint32_t table_stride = (table_bytes + 15) & ~15u;
+    c.rings = smem + wave * kWaveRingBytes; // all rings first: they stay kRingBytes-aligned
+    c.table = smem + waves * kWaveRingBytes + wave * table_stride;
+    c.table_b = c.table;
+    c.gtable = nullptr;
+    c.scratch_cnt = (uint16_t *)c.rings;
+    c.scratch_cum = (uint16_t *)(c.rings + 512);
+  }
+  if (task < gp.n_tasks)
+    run_gather<MODE, SHARED>(c, pv, gp, task);
+}
+
+} // namespace hsrans
+
+#endif // HSRANS_KERNELS_GATHER_H

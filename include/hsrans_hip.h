@@ -202,6 +202,59 @@ int hsrans_decode_device_window(hsrans_ctx *ctx, hsrans_dplan *dplan, const void
  * sender side of the gather in src/mt_rANS32x64_16w_decode.cpp:217-220's fan-out, one GPU per run of blocks. */
 int hsrans_decode_device_ranges(hsrans_ctx *ctx, hsrans_dplan *dplan, const void *d_window, size_t window_offset, size_t window_length, void *d_out_window,
                                 size_t out_offset, size_t out_length, void *hip_stream);
+/* ------------------------------------------------------------------------------------------------------------
+ * Random access: byte ranges of a stream that stays compressed in device memory, ONE launch.
+ * For every r < count the decoded bytes [ranges[r].offset, + ranges[r].length) of the stream land at
+ * (uint8_t *)d_dst + ranges[r].dst_offset; no other byte of d_dst is written.  Only the chains that cover the ranges are
+ * decoded: a range is cut into tasks (hsrans_gather_tasks), one wavefront each, and a wave enters the stream at the last
+ * chain that starts at or before its task — found on the device, in the device plan; no host copy of the plan is needed —
+ * decodes and drops what lies in front of its first byte, stores the rest clipped to the task and stops at its end.
+ *   - asynchronous on hip_stream.  `ranges` (host memory) is read before the call returns: the caller may reuse it.
+ *     Gathers of one context are ordered among themselves (a gather on another stream waits for the one before it:
+ *     they share the context's task buffer).
+ *   - d_stream 16-byte aligned, as everywhere.  d_dst and every dst_offset: ANY alignment.  Where a task's destination
+ *     is 4-byte aligned against its source (address of d_dst + dst_offset - offset a multiple of 4) whole groups are
+ *     stored as words; otherwise, and at a task's first and last group, as bytes.
+ *   - ranges may overlap in the source.  Destinations that overlap are the caller's responsibility: which range's
+ *     bytes end up in the overlap is unspecified (the bytes of the two ranges differ in general).
+ *   - a malformed histogram / header sets the plan's status word as in every decode launch (hsrans_dplan_status).
+ * Plans: every plan of planned chains — raw with an index (uniform interval, or hsrans_index_boundaries' device-shaped
+ * one), mt_ with and without checkpoints (single-symbol blocks included), block_ with checkpoints, 32 / 64 states,
+ * 10-15 bits, made on the host or written on the device (hsrans_encode_device(..., out_dplan),
+ * hsrans_decode_device_indexing).  A raw stream WITHOUT an index is one chain: every task is correct and decodes from
+ * the stream's first byte.  Plans with a host-built table decode with it (one LDS copy per workgroup), all others build
+ * a table per wave from the histogram of the piece they enter.
+ * Cost model: a wave decodes its task plus, in front of it, at most the bytes of ONE chain (the distance from the
+ * chain's start to the task's first byte) — nothing for tasks that start on a checkpoint.
+ * Returns HSRANS_E_ARG: a null handle or pointer, a plan of another context, a misaligned d_stream, a range with
+ *   offset + length beyond the plan's decoded bytes or dst_offset + length beyond dst_capacity (nothing is launched);
+ * HSRANS_E_FORMAT: a plan without entry points (a block_ stream without checkpoints: its blocks are found by walking
+ *   the stream), stream_length != the plan's stream length;
+ * HSRANS_OK with nothing launched: count == 0 or only empty ranges. */
+typedef struct hsrans_range
+{
+  uint64_t offset, length, dst_offset;
+} hsrans_range; /* 24 bytes */
+int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *dplan, const void *d_stream, size_t stream_length, const hsrans_range *ranges /* host */,
+                                uint32_t count, void *d_dst, size_t dst_capacity, void *hip_stream);
+/* The host-side cut of that call, a pure function (no GPU; for tests and planning, as hsrans_shard_layout and
+ * hsrans_launch_choice): one task = one wavefront's work.  Every range is cut at the ABSOLUTE multiples of a segment
+ * length L (hsrans_gather_segment): where the plan has a uniform checkpoint interval (PlanHeader::interval, in groups)
+ * the base length is interval * states, so tasks start on checkpoints; otherwise the mean chain length
+ * ceil(decoded_len / n_chains) rounded up to a multiple of `states`.  L is the smallest multiple of the base that is
+ * >= the floor (4096 bytes), so short chains are taken several at a time and a task is never tiny.  Empty ranges give no
+ * task; the tasks of a range tile it in order and share dst_delta = dst_offset - offset.
+ * Returns the tasks the ranges need and writes at most `capacity` of them (out may be NULL when capacity is 0);
+ * 0 for a null `ranges` with count > 0, a range beyond decoded_len, n_chains == 0 or states == 0. */
+typedef struct hsrans_gather_task
+{
+  uint64_t begin, end; /* decoded bytes [begin, end) ... */
+  int64_t dst_delta;   /* ... go to d_dst + byte + dst_delta */
+} hsrans_gather_task; /* 24 bytes */
+uint64_t hsrans_gather_segment(uint64_t decoded_len, uint32_t n_chains, uint32_t states, uint32_t interval /* 0 = none */);
+size_t hsrans_gather_tasks(uint64_t decoded_len, uint32_t n_chains, uint32_t states, uint32_t interval /* 0 = none */, const hsrans_range *ranges,
+                           uint32_t count, hsrans_gather_task *out, size_t capacity);
+
 /* Plan an mt_ stream that only exists in device memory: the header chain (src/mt_rANS32x64_16w_decode.cpp:166-227) is
  * followed by a device kernel; synchronises `hip_stream` twice (chain count, then the finished plan). HSRANS_MT only. */
 int hsrans_dplan_create_from_device_stream(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_stream, size_t stream_length,

@@ -199,6 +199,10 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_queue_stats.argtypes = [_vp, ctypes.POINTER(QueueStats)]
     L.hsrans_decode_device_gather.restype = _i
     L.hsrans_decode_device_gather.argtypes = [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp]
+    L.hsrans_gather_workspace_bytes.restype = _sz
+    L.hsrans_gather_workspace_bytes.argtypes = [_u32]
+    L.hsrans_decode_device_gather_indirect.restype = _i
+    L.hsrans_decode_device_gather_indirect.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
     L.hsrans_gather_segment.restype = ctypes.c_uint64
     L.hsrans_gather_segment.argtypes = [ctypes.c_uint64, _u32, _u32, _u32]
     L.hsrans_gather_tasks.restype = _sz
@@ -575,6 +579,11 @@ def _ranges_array(ranges) -> np.ndarray:
 def gather_segment(decoded_len: int, n_chains: int, states: int, interval: int) -> int:
     """hsrans_gather_segment: the segment length L a gather's ranges are cut at (absolute multiples of it); 0 for n_chains == 0."""
     return int(load_library().hsrans_gather_segment(decoded_len, n_chains, states, interval))
+
+
+def gather_workspace_bytes(max_count: int) -> int:
+    """hsrans_gather_workspace_bytes: the device workspace a decode_device_gather_indirect of up to ``max_count`` ranges needs."""
+    return int(load_library().hsrans_gather_workspace_bytes(max_count))
 
 
 def gather_tasks(decoded_len: int, n_chains: int, states: int, interval: int, ranges, capacity: int | None = None) -> np.ndarray:
@@ -958,6 +967,39 @@ class Context:
             err = HsransError(f"hsrans_decode_device_gather failed with code {rc}")
             err.code = rc
             raise err
+
+    def decode_device_gather_indirect(self, dplan: DevicePlan, d_stream: torch.Tensor, d_ranges: torch.Tensor, d_dst: torch.Tensor, count: torch.Tensor | None = None,
+                                      max_count: int | None = None, workspace: torch.Tensor | None = None, stream_length: int | None = None,
+                                      stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """decode_device_gather for ranges that are on the GPU (hsrans_decode_device_gather_indirect): ``d_ranges`` is a contiguous CUDA
+        tensor (N, 3) of int64 / uint64 rows (offset, length, dst_offset), ``count`` a CUDA int32 / uint32 scalar tensor with the number of
+        rows in use (None: ``max_count``, itself N when None).  Both are read when the launch runs, not here: nothing is copied to the host,
+        nothing is waited for, and the call can be captured into a graph.  ``workspace``: a CUDA uint8 tensor of at least
+        gather_workspace_bytes(max_count) bytes that no other call in flight uses; allocated here when None.  Returns the workspace.
+        Raises HsransError (``.code``) for what the host can check; a range or count only the device can refuse leaves ``d_dst`` untouched
+        and is reported by ``status(dplan)`` (5)."""
+        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
+        if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == 3 and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
+            raise TypeError("d_ranges: a contiguous CUDA tensor (N, 3) of int64 or uint64")
+        if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
+            raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
+        if max_count is None:
+            max_count = d_ranges.shape[0]
+        if max_count > d_ranges.shape[0]:
+            raise ValueError("max_count is larger than d_ranges")
+        if workspace is None:
+            with torch.cuda.stream(s):
+                workspace = torch.empty(gather_workspace_bytes(max_count), dtype=torch.uint8, device=d_stream.device)
+        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace: a contiguous CUDA uint8 tensor")
+        rc = self.L.hsrans_decode_device_gather_indirect(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                                         d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count, d_dst.data_ptr(), d_dst.numel(),
+                                                         workspace.data_ptr(), workspace.numel(), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_gather_indirect failed with code {rc}")
+            err.code = rc
+            raise err
+        return workspace
 
     # -- K independent streams, one launch -------------------------------------------------------------------------
     def make_batch(self, dplans) -> Batch:

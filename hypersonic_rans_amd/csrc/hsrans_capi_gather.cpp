@@ -1,6 +1,8 @@
 // hsrans_decode_device_gather (include/hsrans_hip.h): byte ranges of one stream in one launch — the host-side cut of the ranges into
 // one-wave tasks (hsrans_gather_tasks, a pure function), the argument checks, the context's task buffer and the launch (k_gather,
 // kernels_gather.h, through launch_gather in hsrans_kernels.hip).
+// hsrans_decode_device_gather_indirect: the same for ranges that are in device memory — no cut, no task buffer and no lock here: the
+// device cuts (k_gather_cut, k_gather_ranges through launch_gather_ranges), the caller brings the workspace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -14,7 +16,8 @@ using namespace hsrans;
 
 #include "hsrans_internal.h"
 
-static_assert(sizeof(hsrans_range) == 24 && sizeof(hsrans_gather_task) == 24 && sizeof(GatherTask) == sizeof(hsrans_gather_task), "gather ABI layout");
+static_assert(sizeof(hsrans_range) == 24 && sizeof(hsrans_gather_task) == 24 && sizeof(GatherTask) == sizeof(hsrans_gather_task) && sizeof(GatherRange) == sizeof(hsrans_range),
+              "gather ABI layout");
 
 // The floor of a task's segment length, in decoded bytes.  A task costs its wave a prologue (chain search, start states, perhaps a table
 // build, the first stream chunks) whatever its length, so segments far below a few KiB are mostly prologue; segments far above it leave
@@ -179,6 +182,58 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
   ctx->gather_last_stream = s;
   ctx->gather_last_half = hf;
   ctx->gather_cursor += need;
+  return HSRANS_OK;
+}
+
+size_t hsrans_gather_workspace_bytes(uint32_t max_count)
+{
+  // k_gather_cut's header words, then first_task[0 .. max_count]
+  return ((size_t)kGatherWsFirst * 4 + ((size_t)max_count + 1) * 4 + 255) & ~(size_t)255;
+}
+
+int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_stream, size_t stream_length, const hsrans_range *d_ranges, const uint32_t *d_count,
+                                         uint32_t max_count, void *d_dst, size_t dst_capacity, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+  if (ctx == nullptr || d == nullptr || d_stream == nullptr || d_dst == nullptr || d_ranges == nullptr || d_workspace == nullptr || d->ctx != ctx)
+    return HSRANS_E_ARG;
+  if (((uintptr_t)d_stream & 15) != 0 || ((uintptr_t)d_ranges & 7) != 0 || ((uintptr_t)d_count & 3) != 0 || ((uintptr_t)d_workspace & 255) != 0 ||
+      workspace_bytes < hsrans_gather_workspace_bytes(max_count))
+    return HSRANS_E_ARG;
+  const PlanHeader &h = d->hdr;
+  if ((h.flags & kPlanWalk) || h.n_chains == 0 || stream_length != h.stream_len)
+    return HSRANS_E_FORMAT;
+  if (max_count == 0)
+    return HSRANS_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return HSRANS_E_HIP;
+
+  GatherCutParams cp{};
+  cp.ranges = (const GatherRange *)d_ranges;
+  cp.count = d_count;
+  cp.max_count = max_count;
+  cp.segment = segment_for(d->tuning.gather_min_segment ? d->tuning.gather_min_segment : kGatherMinSegment, h.decoded_len, h.n_chains, h.states, h.interval);
+  cp.decoded_len = h.decoded_len;
+  cp.out_lo = d->out_lo;
+  cp.out_hi = d->out_hi;
+  cp.dst_capacity = dst_capacity;
+  cp.workspace = (uint32_t *)d_workspace;
+  cp.status = d->d_status;
+  GatherParams gp{};
+  gp.stream = (const uint8_t *)d_stream;
+  gp.stream_len = stream_length;
+  gp.dst = (uint8_t *)d_dst;
+  gp.plan = d->d_plan;
+  gp.status = d->d_status;
+  const uint32_t table_mode = d->pa.table != nullptr ? d->pa.table_mode : 0;
+  gp.table = d->pa.table;
+  gp.hist_copy = d->pa.hist_copy;
+  gp.hist_off = d->pa.hist_off;
+  const GatherShape shape = gather_ranges_shape(d->tuning, h, ctx->geom, table_mode, max_count, dst_capacity, cp.segment);
+  if (launch_gather_ranges(gp, cp, shape, (hipStream_t)hip_stream) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
   return HSRANS_OK;
 }
 

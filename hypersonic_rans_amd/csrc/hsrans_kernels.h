@@ -429,6 +429,40 @@ GatherShape gather_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom
 // asynchronous on `stream`; one launch
 hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipStream_t stream);
 
+// ---- the same for ranges in device memory (hsrans_decode_device_gather_indirect): k_gather_cut, then k_gather_ranges ------------
+struct GatherRange // == hsrans_range (include/hsrans_hip.h)
+{
+  uint64_t offset, length, dst_offset;
+};
+static_assert(sizeof(GatherRange) == 24, "GatherRange layout");
+// the workspace, in uint32 words: what k_gather_cut leaves for k_gather_ranges
+constexpr uint32_t kGatherWsTotal = 0;  // tasks of the launch; 0 where a range or the count was refused
+constexpr uint32_t kGatherWsCount = 1;  // ranges in use: *count, or max_count
+constexpr uint32_t kGatherWsFirst = 64; // first_task[0 .. count]: the tasks in front of range r (byte 256 of the workspace on)
+struct GatherCutParams
+{
+  const GatherRange *ranges; // device, [max_count]
+  const uint32_t *count;     // device or null (= max_count)
+  uint32_t max_count;
+  uint64_t segment; // the task length L (hsrans_gather_segment's rule), > 0
+  uint64_t decoded_len, out_lo, out_hi, dst_capacity; // what a range is checked against
+  uint32_t *workspace;
+  uint32_t *status;
+};
+struct GatherRangesParams
+{
+  const GatherRange *ranges;
+  const uint32_t *workspace;
+  uint64_t segment;
+  uint32_t segment_shift; // log2(segment) where it is a power of two, else 0: offset / segment without a division
+};
+// the launch shape for ranges only the device knows.  The grid is sized from what the host does know — no more tasks can have
+// destinations of their own than max_count + dst_capacity / segment — and capped at the waves the device holds at once; the kernel
+// strides over the tasks, so a total above either bound still finishes.
+GatherShape gather_ranges_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t max_count, uint64_t dst_capacity, uint64_t segment);
+// asynchronous on `stream`; two launches, nothing else (capturable)
+hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &cp, const GatherShape &shape, hipStream_t stream);
+
 DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
 LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f); // (reads persistent, table_mode, interval, dual, n_groups, index_pass)
 struct TableChoice

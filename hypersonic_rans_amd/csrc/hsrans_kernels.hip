@@ -34,6 +34,7 @@
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
 //   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device
 //   kernels_gather.h    k_gather           byte ranges of one stream: one wave per task, entered at the chain that holds its first byte
+//                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks
 // This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +58,7 @@
 #include "kernels_walk.h"
 #include "kernels_gather.h"
 
+#include <algorithm>
 #include <array>
 #include <type_traits>
 #include <vector>
@@ -239,12 +241,18 @@ struct GatherKernel
   bool shared;
   const void *fn;
   void (*launch)(const GatherParams &gp, const GatherShape &shape, hipStream_t stream);
+  const void *fn_ranges; // k_gather_ranges of the same table layout
+  void (*launch_ranges)(const GatherParams &gp, const GatherRangesParams &rp, const GatherShape &shape, hipStream_t stream);
 };
 template <int MODE, bool SHARED>
 static GatherKernel gather_entry()
 {
   return {MODE, SHARED, (const void *)k_gather<MODE, SHARED>,
-          [](const GatherParams &gp, const GatherShape &shape, hipStream_t stream) { hipLaunchKernelGGL((k_gather<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, gp); }};
+          [](const GatherParams &gp, const GatherShape &shape, hipStream_t stream) { hipLaunchKernelGGL((k_gather<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, gp); },
+          (const void *)k_gather_ranges<MODE, SHARED>,
+          [](const GatherParams &gp, const GatherRangesParams &rp, const GatherShape &shape, hipStream_t stream) {
+            hipLaunchKernelGGL((k_gather_ranges<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, gp, rp);
+          }};
 }
 static const GatherKernel g_gather_kernels[] = {gather_entry<kModePack, false>(),  gather_entry<kModePackM1, false>(), gather_entry<kModeTwoLevel, false>(),
                                                 gather_entry<kModePack64, true>(), gather_entry<kModeRank, true>(),    gather_entry<kModeSpill, true>()};
@@ -264,7 +272,10 @@ hipError_t prepare_kernels(DeviceGeom *geom)
                          (const void *)k_decode_batch_dual<kModePack64>, (const void *)k_decode_batch_dual<kModeRank>, (const void *)k_calibrate_batch})
     fns.push_back(fn);
   for (const GatherKernel &g : g_gather_kernels)
+  {
     fns.push_back(g.fn);
+    fns.push_back(g.fn_ranges);
+  }
   for (const void *fn : fns)
   {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geom->max_lds);
@@ -987,6 +998,45 @@ hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipSt
     {
       (void)hipGetLastError();
       g.launch(gp, shape, stream);
+      return hipGetLastError();
+    }
+  return hipErrorNotSupported;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_gather_indirect's launch.  Table layout, waves per workgroup and LDS are gather_shape's for the most tasks the
+// call can have; the grid is that bound too, capped at the workgroups the device holds at once (LDS and 32 waves per CU: the
+// shared-table kernels run 8 waves per SIMD, the others are bound by their LDS), so every workgroup is resident from the start.
+// How k_gather_ranges deals the tasks to its waves: a static stride (task t of wave w, workgroup b: w * grid + b, + grid * waves, ...).
+// The alternative, a ticket counter in the workspace that k_gather_cut resets, has not been measured yet; the stride is what ships.
+// ---------------------------------------------------------------------------------------------------------------
+GatherShape gather_ranges_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t max_count, uint64_t dst_capacity, uint64_t segment)
+{
+  const uint64_t most = (uint64_t)max_count + (segment ? dst_capacity / segment : 0);
+  GatherShape g = gather_shape(tn, h, dg, table_mode, (uint32_t)std::min<uint64_t>(most, 0x7FFFFFFFu));
+  const uint32_t per_cu = std::max(1u, std::min(g.lds ? dg.max_lds / g.lds : 32u, 32u / g.waves));
+  g.grid = std::max(1u, std::min(g.grid, dg.num_cus * per_cu));
+  return g;
+}
+
+hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &cp, const GatherShape &shape, hipStream_t stream)
+{
+  if (shape.grid == 0 || shape.lds > 160 * 1024 || cp.segment == 0)
+    return hipErrorInvalidValue;
+  GatherRangesParams rp{};
+  rp.ranges = cp.ranges;
+  rp.workspace = cp.workspace;
+  rp.segment = cp.segment;
+  rp.segment_shift = (cp.segment & (cp.segment - 1)) == 0 ? (uint32_t)__builtin_ctzll(cp.segment) : 0; // (a segment of 1 byte divides as it is)
+  for (const GatherKernel &g : g_gather_kernels)
+    if (g.mode == shape.mode && g.shared == shape.shared)
+    {
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(k_gather_cut, dim3(1), dim3(1024), 0, stream, cp);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess)
+        return e;
+      g.launch_ranges(gp, rp, shape, stream);
       return hipGetLastError();
     }
   return hipErrorNotSupported;

@@ -74,6 +74,7 @@ __host__ __device__ inline uint64_t plan_size(uint32_t n_chains, uint32_t n_piec
 constexpr uint32_t kStatusBadHist = 1;   // counts do not sum to 1 << bits (hist.cpp:308-324 returns false)
 constexpr uint32_t kStatusBadBlock = 2;  // block end not a multiple of S (block_…decode.cpp:76-77)
 constexpr uint32_t kStatusOutOfRange = 4; // a header / fill points outside the buffers
+constexpr uint32_t kStatusBadRange = 8;   // hsrans_decode_device_gather_indirect: a range or count the device refused (k_gather_cut); nothing was gathered
 
 } // namespace hsrans
 

@@ -1,4 +1,4 @@
-// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather) — gather_groups, gather_tail, run_gather, k_gather.
+// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather, hsrans_decode_device_gather_indirect) — gather_groups, gather_tail, run_gather, k_gather, k_gather_cut, k_gather_ranges.
 // Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the host-side launcher).
 //
 // One wavefront = one task (GatherTask: decoded bytes [begin, end) of the stream, destination = GatherParams::dst + byte + dst_delta).  The
@@ -103,12 +103,12 @@ __device__ __forceinline__ void gather_tail(uint32_t &x, Ring &r, const WaveCtx 
     c.out[b] = (uint8_t)(e >> ((MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) ? 24 : 0));
 }
 
-// the task of one wave.  SHARED: c.table holds the plan's one table already.
+// the task of one wave: decoded bytes [begin, end) go to dst + byte + dst_delta (all three wave-uniform).  SHARED: c.table holds the
+// plan's one table already.  A wave may run task after task: nothing but the table of a SHARED launch is carried from one to the next.
 template <int MODE, bool SHARED>
-__device__ void run_gather(WaveCtx &c, const PlanView &pv, const GatherParams &gp, uint32_t task)
+__device__ void run_gather(WaveCtx &c, const PlanView &pv, uint8_t *dst, uint64_t begin, uint64_t end, int64_t dst_delta)
 {
-  const uint64_t begin = uni64(gp.tasks[task].begin), end = uni64(gp.tasks[task].end);
-  c.out = gp.dst + (int64_t)uni64((uint64_t)gp.tasks[task].dst_delta);
+  c.out = dst + dst_delta;
   const uint32_t n_chains = uni(pv.hdr->n_chains);
   if (begin >= end || n_chains == 0)
     return;
@@ -180,35 +180,26 @@ __device__ void run_gather(WaveCtx &c, const PlanView &pv, const GatherParams &g
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// the kernel: blockDim.x = 64 * waves; wave w of block b runs task b * waves + w
-// LDS: SHARED  -> [waves x ring][table] (the rank table first, as k_decode has it);   otherwise -> [waves x ring][waves x table]
-// ---------------------------------------------------------------------------------------------------------------
+// what k_gather and k_gather_ranges do before their first task: the wave's context and, in a SHARED launch, the workgroup's table
 template <int MODE, bool SHARED>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_gather(GatherParams gp)
+__device__ __forceinline__ void gather_setup(WaveCtx &c, const PlanView &pv, const GatherParams &gp, uint8_t *smem)
 {
-  extern __shared__ u32x4 smem_v[];
-  uint8_t *smem = (uint8_t *)smem_v;
-
-  const PlanView pv = plan_view(gp.plan);
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   const uint32_t bits = pv.hdr->bits;
   const uint32_t table_bytes = table_bytes_for(MODE, bits);
 
-  WaveCtx c;
   c.stream = gp.stream;
   c.stream_len = gp.stream_len;
   c.stream_lo = 0;
   c.out = gp.dst;
-  c.out_cap = 0; // (not used: every store of this kernel is tested against its task)
+  c.out_cap = 0; // (not used: every store of these kernels is tested against its task)
   c.status = gp.status;
   c.bits = bits;
   c.S = pv.hdr->states;
   c.lane = threadIdx.x & 63;
   asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
   asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
-  const uint32_t task = blockIdx.x * waves + wave;
 
   if (SHARED)
   {
@@ -250,8 +241,143 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_g
     c.scratch_cnt = (uint16_t *)c.rings;
     c.scratch_cum = (uint16_t *)(c.rings + 512);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the kernel: blockDim.x = 64 * waves; wave w of block b runs task b * waves + w
+// LDS: SHARED  -> [waves x ring][table] (the rank table first, as k_decode has it);   otherwise -> [waves x ring][waves x table]
+// ---------------------------------------------------------------------------------------------------------------
+template <int MODE, bool SHARED>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_gather(GatherParams gp)
+{
+  extern __shared__ u32x4 smem_v[];
+  const PlanView pv = plan_view(gp.plan);
+  WaveCtx c;
+  gather_setup<MODE, SHARED>(c, pv, gp, (uint8_t *)smem_v);
+  const uint32_t task = blockIdx.x * (blockDim.x >> 6) + uni(threadIdx.x >> 6);
   if (task < gp.n_tasks)
-    run_gather<MODE, SHARED>(c, pv, gp, task);
+    run_gather<MODE, SHARED>(c, pv, gp.dst, uni64(gp.tasks[task].begin), uni64(gp.tasks[task].end), (int64_t)uni64((uint64_t)gp.tasks[task].dst_delta));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_gather_indirect: the ranges are in device memory and are read when the launch runs.  Two kernels, queued back to
+// back: k_gather_cut checks the ranges and counts their tasks, k_gather_ranges runs them.
+// Workspace (uint32 words; GatherWs* in hsrans_kernels.h): [0] the task total, 0 where anything was refused; [1] the ranges in use;
+// from word kGatherWsFirst on first_task[0 .. n], the exclusive prefix of the ranges' task counts.
+// ---------------------------------------------------------------------------------------------------------------
+// One workgroup of 1024 threads, a range per thread and round.  The checks are the host entry's (hsrans_decode_device_gather), done
+// without a sum that can wrap; one range that fails them, a count above max_count or a total of 2^31 or more refuses the whole call:
+// the total is written as 0 and kStatusBadRange set.
+__global__ void __launch_bounds__(1024) k_gather_cut(GatherCutParams cp)
+{
+  __shared__ uint64_t wave_sum[16];
+  __shared__ uint32_t any_bad;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t *first_task = cp.workspace + kGatherWsFirst;
+  uint32_t n = cp.count != nullptr ? *cp.count : cp.max_count;
+  bool bad = n > cp.max_count;
+  if (bad)
+    n = 0;
+  if (threadIdx.x == 0)
+    any_bad = 0;
+  __syncthreads();
+  uint64_t carry = 0; // tasks of the rounds before this one (the same on every thread)
+  for (uint32_t r0 = 0; r0 < n; r0 += 1024)
+  {
+    const uint32_t r = r0 + threadIdx.x;
+    uint64_t tasks = 0;
+    if (r < n)
+    {
+      const uint64_t offset = cp.ranges[r].offset, length = cp.ranges[r].length, dst_offset = cp.ranges[r].dst_offset;
+      if (offset > cp.decoded_len || length > cp.decoded_len - offset || dst_offset > cp.dst_capacity || length > cp.dst_capacity - dst_offset ||
+          (length != 0 && (offset < cp.out_lo || offset + length > cp.out_hi)))
+        bad = true;
+      else if (length != 0)
+        tasks = (offset + length - 1) / cp.segment - offset / cp.segment + 1;
+      if (tasks >= (1ull << 31)) // (so that no sum below can wrap)
+      {
+        bad = true;
+        tasks = 0;
+      }
+    }
+    // inclusive scan: inside the wave, then over the 16 waves' sums
+    uint64_t incl = tasks;
+    for (uint32_t d = 1; d < 64; d *= 2)
+    {
+      const uint64_t below = __shfl_up(incl, d, 64);
+      if (lane >= d)
+        incl += below;
+    }
+    __syncthreads(); // (wave_sum of the round before has been read)
+    if (lane == 63)
+      wave_sum[wave] = incl;
+    __syncthreads();
+    uint64_t before = carry, round = 0;
+    for (uint32_t w = 0; w < 16; w++)
+    {
+      const uint64_t v = wave_sum[w];
+      before += w < wave ? v : 0;
+      round += v;
+    }
+    // (a prefix of 2^31 or more is refused below: what the low words then hold is never read)
+    if (r < n)
+      first_task[r] = (uint32_t)(before + incl - tasks);
+    carry += round;
+    if (carry >= (1ull << 31))
+    {
+      bad = true;
+      carry = 1ull << 31;
+    }
+  }
+  if (bad)
+    any_bad = 1; // (benign race: every writer stores 1)
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    const bool refuse = any_bad != 0;
+    first_task[n] = (uint32_t)carry;
+    cp.workspace[kGatherWsTotal] = refuse ? 0 : (uint32_t)carry;
+    cp.workspace[kGatherWsCount] = n;
+    if (refuse)
+      atomicOr(cp.status, kStatusBadRange);
+  }
+}
+
+// blockDim.x = 64 * waves, any grid: wave w of block b runs tasks w * gridDim.x + b, + gridDim.x * waves, ... below the total that
+// k_gather_cut left — neighbouring tasks go to different workgroups, so a total far below the grid's waves still spreads over the CUs
+// (the grid is sized from max_count and dst_capacity, not from the ranges: gather_ranges_shape).  LDS as k_gather.
+// (100 SGPRs: the loop keeps its own uniforms beside a task's; occupancy is the same 8 waves per SIMD)
+template <int MODE, bool SHARED>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(100))) k_gather_ranges(GatherParams gp, GatherRangesParams rp)
+{
+  extern __shared__ u32x4 smem_v[];
+  const uint32_t total = uni(rp.workspace[kGatherWsTotal]);
+  if (blockIdx.x >= total) // (wave 0's first task is the workgroup's lowest: nothing for any of its waves, the table copy included)
+    return;
+  const PlanView pv = plan_view(gp.plan);
+  WaveCtx c;
+  gather_setup<MODE, SHARED>(c, pv, gp, (uint8_t *)smem_v);
+  const uint32_t n = uni(rp.workspace[kGatherWsCount]);
+  const uint32_t *first_task = rp.workspace + kGatherWsFirst;
+  const uint32_t stride = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t t = uni(threadIdx.x >> 6) * gridDim.x + blockIdx.x; t < total; t += stride)
+  {
+    // the range of task t: the last r with first_task[r] <= t (ranges without tasks share their successor's entry and are passed over)
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1)
+    {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (uni(first_task[mid]) <= t)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    const uint64_t offset = uni64(rp.ranges[lo].offset), stop = offset + uni64(rp.ranges[lo].length), dst_offset = uni64(rp.ranges[lo].dst_offset);
+    const uint64_t first_seg = rp.segment_shift != 0 ? offset >> rp.segment_shift : uni64(offset / rp.segment);
+    const uint64_t cut = (first_seg + (t - uni(first_task[lo]))) * rp.segment;
+    const uint64_t begin = cut > offset ? cut : offset, end = cut + rp.segment < stop ? cut + rp.segment : stop;
+    run_gather<MODE, SHARED>(c, pv, gp.dst, begin, end, (int64_t)(dst_offset - offset));
+  }
 }
 
 } // namespace hsrans

@@ -149,7 +149,7 @@ size_t hsrans_index_build_host(int level, uint32_t threads, int container, int s
 #define HSRANS_E_ARG 2
 #define HSRANS_E_FORMAT 3   /* malformed stream / plan (the reference's "return 0" cases) */
 #define HSRANS_E_HIP 4
-#define HSRANS_E_DEVICE 5   /* the kernel reported a malformed histogram / block header */
+#define HSRANS_E_DEVICE 5   /* the kernel reported a malformed histogram / block header, or refused the ranges of a gather_indirect */
 
 int hsrans_ctx_create(int device, hsrans_ctx **out_ctx);
 void hsrans_ctx_destroy(hsrans_ctx *ctx);
@@ -254,6 +254,36 @@ typedef struct hsrans_gather_task
 uint64_t hsrans_gather_segment(uint64_t decoded_len, uint32_t n_chains, uint32_t states, uint32_t interval /* 0 = none */);
 size_t hsrans_gather_tasks(uint64_t decoded_len, uint32_t n_chains, uint32_t states, uint32_t interval /* 0 = none */, const hsrans_range *ranges,
                            uint32_t count, hsrans_gather_task *out, size_t capacity);
+/* ------------------------------------------------------------------------------------------------------------
+ * The same gather for ranges that are in DEVICE memory — an index lookup, a page table, the output of another kernel —
+ * with no host round trip: n = d_count ? *d_count : max_count, and for the ranges d_ranges[0 .. n) the result is byte
+ * for byte that of hsrans_decode_device_gather with the same ranges (same segment length L, hence the same tasks
+ * hsrans_gather_tasks reports; same alignment rules; no other byte of d_dst is written).
+ *   - asynchronous on hip_stream: two kernel launches and nothing else — no allocation, no synchronisation, no lock,
+ *     no host read of device memory, no use of the context's task buffer.  The call can be captured into a graph.
+ *   - d_ranges and *d_count are read when the launch RUNS, not when it is queued: a replayed graph gathers whatever
+ *     they hold then.  Rows of d_ranges from n on are never read.
+ *   - d_workspace: hsrans_gather_workspace_bytes(max_count) bytes of device memory, 256-byte aligned, contents
+ *     irrelevant.  It belongs to one call in flight at a time; calls with different workspaces are independent of each
+ *     other whatever streams they are on (the host-ranges entry orders the gathers of a context; this one does not).
+ *   - the launch shape cannot depend on the ranges: the grid is sized from max_count and dst_capacity (no more tasks
+ *     than max_count + dst_capacity / L have destinations of their own), capped at the waves the device holds at once,
+ *     and the waves stride over the tasks, so any task total finishes.  Pass the dst_capacity the ranges can really
+ *     address: a much larger one only starts workgroups that find nothing to do.
+ * What only the device can see is checked there, all or nothing: *d_count > max_count, a range beyond the plan's decoded
+ * bytes (or outside what a sliced plan decodes), dst_offset + length beyond dst_capacity, any 64-bit overflow in these
+ * sums, a task total of 2^31 or more.  Then the call gathers NOTHING — not one byte of d_dst is written — and sets bit 8
+ * of the plan's status word: hsrans_dplan_status returns HSRANS_E_DEVICE once and clears it, as for the other bits.
+ * Returns HSRANS_E_ARG: a null handle or pointer (d_count may be NULL), a plan of another context, d_stream not 16-byte,
+ *   d_ranges not 8-byte, d_count not 4-byte or d_workspace not 256-byte aligned, workspace_bytes too small;
+ * HSRANS_E_FORMAT: as hsrans_decode_device_gather;
+ * HSRANS_OK with nothing queued: max_count == 0.
+ * hsrans_gather_workspace_bytes: a pure function; > 0 and a multiple of 256 for every max_count. */
+size_t hsrans_gather_workspace_bytes(uint32_t max_count);
+int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *dplan, const void *d_stream, size_t stream_length,
+                                         const hsrans_range *d_ranges /* DEVICE, 8-byte aligned */, const uint32_t *d_count /* DEVICE, or NULL = max_count */,
+                                         uint32_t max_count, void *d_dst, size_t dst_capacity, void *d_workspace /* DEVICE, 256-byte aligned */,
+                                         size_t workspace_bytes, void *hip_stream);
 
 /* Plan an mt_ stream that only exists in device memory: the header chain (src/mt_rANS32x64_16w_decode.cpp:166-227) is
  * followed by a device kernel; synchronises `hip_stream` twice (chain count, then the finished plan). HSRANS_MT only. */

@@ -11,7 +11,15 @@ Per case one JSON line with
                 rounded outward to chain boundaries), host clock around all ranges including the final synchronisation
 --segments 1024,2048,...: the same gather with other floors of the task length (HSRANS_GATHER_MIN_SEGMENT, read when a device plan is
 made) on the 1 % / 4 KiB and 10 % / 64 KiB cases — the table kGatherMinSegment was chosen from.
-Run on the GPU box: python tools/gather_rate.py --out profiles/r10_gather_rate.jsonl --segments 1024,2048,4096,8192,16384"""
+--indirect: instead of all that, the 1 % / 4 KiB and 10 % / 64 KiB cases through hsrans_decode_device_gather_indirect, beside the host-ranges
+entry in the same process.  Per case one JSON line with
+  host_us            decode_device_gather as above (ranges in host memory; the parent's path)
+  indirect_us        decode_device_gather_indirect with the ranges already on the device (k_gather_cut + k_gather_ranges), measured the same way
+  graph_us           the same call captured once per set into a graph, the graphs replayed in rotation
+  host_clock_*_us    wall clock per gather for ranges that START on the device, everything waited for: the device-to-host copy of the
+                     ranges + synchronisation + decode_device_gather (roundtrip), against the one indirect call (indirect)
+Run on the GPU box: python tools/gather_rate.py --out profiles/r10_gather_rate.jsonl --segments 1024,2048,4096,8192,16384
+                    python tools/gather_rate.py --indirect --out profiles/r11_gather_indirect_rate.jsonl"""
 import argparse
 import json
 import os
@@ -30,6 +38,7 @@ ap.add_argument("--size", type=int, default=100_000_000)
 ap.add_argument("--sets", type=int, default=4)
 ap.add_argument("--iters", type=int, default=24)
 ap.add_argument("--segments", default="")
+ap.add_argument("--indirect", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 ctx = H.Context(0)
@@ -135,7 +144,72 @@ def run_case(container, m, plan, d_streams, dplan, length, fraction, packing, rn
     return rec
 
 
+def run_indirect_case(container, m, plan, d_streams, dplan, length, fraction, packing, rng):
+    ranges, size, base = make_ranges(rng, length, fraction, packing)
+    count = int(len(ranges))
+    backs = [torch.zeros(size + 16, dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
+    dsts = [b[base:base + size] for b in backs]
+    d_ranges = torch.from_numpy(ranges.view(np.int64)).cuda()
+    d_count = torch.tensor(count, dtype=torch.int32, device="cuda")
+    spaces = [torch.empty(H.gather_workspace_bytes(count), dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
+    host = lambda k: ctx.decode_device_gather(dplan, d_streams[k % args.sets], ranges, dsts[k % args.sets], stream_length=m)
+    indirect = lambda k: ctx.decode_device_gather_indirect(dplan, d_streams[k % args.sets], d_ranges, dsts[k % args.sets], count=d_count, workspace=spaces[k % args.sets],
+                                                           stream_length=m)
+    rec = {"container": container, "range_bytes": length, "fraction": fraction, "ranges": count, "dst": packing,
+           "tasks": int(H.gather_tasks(N, H.plan_chain_count(plan), S, INTERVAL, ranges).shape[0])}
+    rec["host_us"] = round(event_us(host, args.iters), 2)
+    check(ranges, dsts[0])
+    for d in dsts:
+        d.zero_()
+    rec["indirect_us"] = round(event_us(indirect, args.iters), 2)
+    check(ranges, dsts[0])
+    # one graph per set (its stream, destination and workspace are baked in; the ranges and the count are read at every replay)
+    graphs = []
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    for k in range(args.sets):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                ctx.decode_device_gather_indirect(dplan, d_streams[k], d_ranges, dsts[k], count=d_count, workspace=spaces[k], stream_length=m, stream=side)
+        graphs.append(g)
+    torch.cuda.synchronize()
+    for d in dsts:
+        d.zero_()
+    rec["graph_us"] = round(event_us(lambda k: graphs[k % args.sets].replay(), args.iters), 2)
+    check(ranges, dsts[0])
+    assert ctx.status(dplan) == 0
+    rec["indirect_over_host"] = round(rec["indirect_us"] / rec["host_us"], 3)
+    rec["graph_over_host"] = round(rec["graph_us"] / rec["host_us"], 3)
+
+    # ranges that start on the device, by the host's clock, every gather waited for
+    def roundtrip(k):
+        ctx.decode_device_gather(dplan, d_streams[k % args.sets], d_ranges.cpu().numpy().view(np.uint64), dsts[k % args.sets], stream_length=m)
+        torch.cuda.synchronize()
+
+    def direct(k):
+        indirect(k)
+        torch.cuda.synchronize()
+
+    for name, fn in (("host_clock_roundtrip_us", roundtrip), ("host_clock_indirect_us", direct)):
+        for k in range(args.sets):
+            fn(k)
+        t0 = time.perf_counter()
+        for k in range(args.iters):
+            fn(k)
+        rec[name] = round((time.perf_counter() - t0) * 1e6 / args.iters, 1)
+    return rec
+
+
 rng = np.random.default_rng(10)
+if args.indirect:
+    for container in ("raw", "mt_"):
+        m, plan, d_streams = make_stream(container)
+        dplan = ctx.make_device_plan(plan)
+        for length, fraction in ((4096, 0.01), (65536, 0.1)):
+            for packing in ("aligned", "packed"):
+                emit(run_indirect_case(container, m, plan, d_streams, dplan, length, fraction, packing, np.random.default_rng(length)))
+    sys.exit(0)
 for container in ("raw", "mt_"):
     m, plan, d_streams = make_stream(container)
     dplan = ctx.make_device_plan(plan)

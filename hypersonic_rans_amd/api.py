@@ -91,6 +91,23 @@ class GatherTask(ctypes.Structure):  # hsrans_gather_task
     _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("dst_delta", ctypes.c_int64)]
 
 
+class MemberRange(ctypes.Structure):  # hsrans_member_range
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("member", _u32), ("reserved", _u32)]
+
+
+class GatherMember(ctypes.Structure):  # hsrans_gather_member
+    _fields_ = [("decoded_len", ctypes.c_uint64), ("n_chains", _u32), ("states", _u32), ("interval", _u32), ("kind", _u32)]
+
+
+class GatherBatchTask(ctypes.Structure):  # hsrans_gather_batch_task
+    _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("dst_delta", ctypes.c_int64), ("member", _u32), ("reserved", _u32)]
+
+
+class GatherSetInfo(ctypes.Structure):  # hsrans_gather_set_info_t
+    _fields_ = [("members", _u32), ("launches", _u32)] + \
+               [(n, _u32 * 6) for n in ("kind_members", "kind_tasks", "kind_entries", "kind_grid", "kind_waves", "kind_lds_bytes")]
+
+
 COMM_ID_BYTES = 128
 SHARD_DECODE_ONLY, SHARD_DECODE_AND_EXCHANGE, SHARD_EXCHANGE_ONLY = 0, 1, 2
 
@@ -203,6 +220,18 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_gather_workspace_bytes.argtypes = [_u32]
     L.hsrans_decode_device_gather_indirect.restype = _i
     L.hsrans_decode_device_gather_indirect.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
+    L.hsrans_gather_set_create.restype = _i
+    L.hsrans_gather_set_create.argtypes = [_vp, _vp, _vp, _vp, _u32, _vp]
+    L.hsrans_gather_set_destroy.restype = None
+    L.hsrans_gather_set_destroy.argtypes = [_vp]
+    L.hsrans_decode_device_gather_batch.restype = _i
+    L.hsrans_decode_device_gather_batch.argtypes = [_vp, _vp, _vp, _u32, _vp, _sz, _vp]
+    L.hsrans_gather_set_status.restype = _i
+    L.hsrans_gather_set_status.argtypes = [_vp, _vp, _vp, _vp]
+    L.hsrans_gather_set_info.restype = _i
+    L.hsrans_gather_set_info.argtypes = [_vp, _vp]
+    L.hsrans_gather_batch_tasks.restype = _sz
+    L.hsrans_gather_batch_tasks.argtypes = [_vp, _u32, _vp, _u32, _u32, _u32, _vp, _sz]
     L.hsrans_gather_segment.restype = ctypes.c_uint64
     L.hsrans_gather_segment.argtypes = [ctypes.c_uint64, _u32, _u32, _u32]
     L.hsrans_gather_tasks.restype = _sz
@@ -600,6 +629,35 @@ def gather_tasks(decoded_len: int, n_chains: int, states: int, interval: int, ra
     return out
 
 
+def _member_ranges_array(ranges) -> np.ndarray:
+    """rows (member, offset, length, dst_offset) -> hsrans_member_range[N] as a structured array (reserved = 0)"""
+    rows = np.asarray(ranges, dtype=np.uint64).reshape(-1, 4)
+    if rows.size and int(rows[:, 0].max()) > 0xFFFFFFFF:
+        raise ValueError("member does not fit 32 bits")
+    arr = np.zeros(rows.shape[0], np.dtype([("offset", "<u8"), ("length", "<u8"), ("dst_offset", "<u8"), ("member", "<u4"), ("reserved", "<u4")]))
+    arr["member"], arr["offset"], arr["length"], arr["dst_offset"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3]
+    return arr
+
+
+def gather_batch_tasks(members, ranges, kind: int, waves: int, capacity: int | None = None) -> np.ndarray:
+    """hsrans_gather_batch_tasks: the entries of the launch of one ``kind`` (0..5; 3..5: one table per workgroup, the entries sorted by member
+    and every member's run padded to a multiple of ``waves``) for ``members`` (rows (decoded_len, n_chains, states, interval, kind)) and
+    ``ranges`` (rows (member, offset, length, dst_offset)), as an (M, 4) uint64 array of (begin, end, dst_delta modulo 2^64, member).  Pure
+    host arithmetic; an empty array for invalid input.  ``capacity``: as gather_tasks."""
+    L = load_library()
+    rows = np.asarray(members, dtype=np.uint64).reshape(-1, 5)
+    mem = np.zeros(rows.shape[0], np.dtype([("decoded_len", "<u8"), ("n_chains", "<u4"), ("states", "<u4"), ("interval", "<u4"), ("kind", "<u4")]))
+    for k, name in enumerate(mem.dtype.names):
+        mem[name] = rows[:, k]
+    arr = _member_ranges_array(ranges)
+    n = L.hsrans_gather_batch_tasks(_p(mem) if mem.size else None, mem.shape[0], _p(arr) if arr.size else None, arr.shape[0], kind, waves, None, 0)
+    rows_out = n if capacity is None else min(n, capacity)
+    out = np.zeros(rows_out, np.dtype([("begin", "<u8"), ("end", "<u8"), ("dst_delta", "<u8"), ("member", "<u4"), ("reserved", "<u4")]))
+    if rows_out:
+        L.hsrans_gather_batch_tasks(_p(mem), mem.shape[0], _p(arr), arr.shape[0], kind, waves, _p(out), rows_out)
+    return np.stack([out["begin"], out["end"], out["dst_delta"], out["member"].astype(np.uint64)], axis=1) if rows_out else np.zeros((0, 4), np.uint64)
+
+
 def batch_deal(chain_starts, grid: int = 512, waves: int = 16, weights=None):
     """hsrans_batch_deal: how one launch's wave slots would be dealt to members whose chains start at ``chain_starts[m]`` (groups,
     ascending, last entry = the member's total).  Returns (imbalance, slots[grid * waves, 4] = member, first chain, end chain, flags)."""
@@ -637,6 +695,30 @@ class Batch:
     def close(self):
         if self.handle:
             load_library().hsrans_dplan_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GatherSet:
+    """hsrans_gather_set: K device plans bound to their compressed streams (Context.make_gather_set / Context.decode_device_gather_batch)."""
+
+    def __init__(self, ctx: "Context", handle, dplans, d_streams):
+        self.ctx, self.handle, self.dplans, self.d_streams = ctx, handle, list(dplans), list(d_streams)  # (keeps the plans and the streams alive)
+
+    def info(self) -> dict:
+        """members, members per kind, and of the last gather: launches and per kind tasks, entries (tasks + padding), grid, waves, LDS bytes"""
+        info = GatherSetInfo()
+        load_library().hsrans_gather_set_info(self.handle, ctypes.byref(info))
+        return {n: (list(getattr(info, n)) if n.startswith("kind_") else getattr(info, n)) for n, _ in GatherSetInfo._fields_}
+
+    def close(self):
+        if self.handle:
+            load_library().hsrans_gather_set_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1000,6 +1082,47 @@ class Context:
             err.code = rc
             raise err
         return workspace
+
+    def make_gather_set(self, dplans, d_streams, stream_lengths=None) -> GatherSet:
+        """Binds K device plans to their streams (hsrans_gather_set_create): member k = dplans[k] over the CUDA uint8 tensor d_streams[k]
+        (16-byte aligned; ``stream_lengths[k]`` bytes of it, default all).  The set keeps the plans and the tensors alive.  Raises HsransError
+        (``.code``: 2 a bad argument or a misaligned stream, 3 a plan without entry points or a wrong stream length)."""
+        dplans, d_streams = list(dplans), list(d_streams)
+        K = len(dplans)
+        if len(d_streams) != K:
+            raise ValueError("one stream per device plan")
+        pa = (ctypes.c_void_p * K)(*[d.handle.value if isinstance(d.handle, ctypes.c_void_p) else d.handle for d in dplans])
+        sp = (ctypes.c_void_p * K)(*[t.data_ptr() for t in d_streams])
+        sl = (ctypes.c_size_t * K)(*[(t.numel() if stream_lengths is None else int(stream_lengths[k])) for k, t in enumerate(d_streams)])
+        h = _vp()
+        rc = self.L.hsrans_gather_set_create(self.handle, pa, sp, sl, K, ctypes.byref(h))
+        if rc != 0:
+            err = HsransError(f"hsrans_gather_set_create failed with code {rc}")
+            err.code = rc
+            raise err
+        return GatherSet(self, h, dplans, d_streams)
+
+    def decode_device_gather_batch(self, gset: GatherSet, ranges, d_dst: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """Byte ranges of many streams that stay compressed on the GPU, one launch per table layout (hsrans_decode_device_gather_batch): for
+        every row (member, offset, length, dst_offset) of ``ranges`` ((N, 4) uint64 or a list of such rows) the decoded bytes
+        [offset, offset + length) of that member land at d_dst[dst_offset:]; no other byte of ``d_dst`` is written — byte for byte what one
+        decode_device_gather per member gives.  Asynchronous on ``stream`` (default: torch's current stream); ``ranges`` is read before the
+        call returns.  Raises HsransError (``.code``: 2 a bad member, range or destination; nothing was launched)."""
+        s = stream if stream is not None else torch.cuda.current_stream(d_dst.device)
+        arr = _member_ranges_array(ranges)
+        rc = self.L.hsrans_decode_device_gather_batch(self.handle, gset.handle, _p(arr) if arr.size else None, arr.shape[0], d_dst.data_ptr(), d_dst.numel(),
+                                                      ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_gather_batch failed with code {rc}")
+            err.code = rc
+            raise err
+
+    def gather_set_status(self, gset: GatherSet, stream: torch.cuda.Stream | None = None) -> list:
+        """hsrans_gather_set_status: synchronises ``stream`` and returns every member's status (0, or 5: its kernel found a malformed histogram)"""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        codes = (ctypes.c_int * len(gset.dplans))()
+        self.L.hsrans_gather_set_status(self.handle, gset.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        return list(codes)
 
     # -- K independent streams, one launch -------------------------------------------------------------------------
     def make_batch(self, dplans) -> Batch:

@@ -3,6 +3,7 @@
 // kernels_gather.h, through launch_gather in hsrans_kernels.hip).
 // hsrans_decode_device_gather_indirect: the same for ranges that are in device memory — no cut, no task buffer and no lock here: the
 // device cuts (k_gather_cut, k_gather_ranges through launch_gather_ranges), the caller brings the workspace.
+// gather_region_*: the context's task buffer as regions, shared with hsrans_decode_device_gather_batch (hsrans_capi_gather_batch.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -73,6 +74,73 @@ static size_t cut_tasks(uint64_t L, uint64_t decoded_len, const hsrans_range *ra
   return n;
 }
 
+// (the floor: the compiled-in one unless the plan was made under HSRANS_GATHER_MIN_SEGMENT, the sweep's knob)
+uint64_t gather_segment_of(const hsrans_dplan *d)
+{
+  const PlanHeader &h = d->hdr;
+  return segment_for(d->tuning.gather_min_segment ? d->tuning.gather_min_segment : kGatherMinSegment, h.decoded_len, h.n_chains, h.states, h.interval);
+}
+
+// The task buffers — page-locked on the host, so that the copy really is asynchronous, and on the device — belong to the context and are
+// used as two halves, call after call taking the next region: a queued gather's tasks are never overwritten under it.  Before a half is
+// entered again the last launch that used it is waited for (a wait that only happens when the device is more than half a buffer of task
+// lists behind).
+int gather_region_take(hsrans_ctx *ctx, size_t need, GatherRegion *region)
+{
+  for (int k = 0; k < 2; k++)
+    if (ctx->gather_ev[k] == nullptr && hipEventCreateWithFlags(&ctx->gather_ev[k], hipEventDisableTiming) != hipSuccess)
+      return HSRANS_E_HIP;
+  if (2 * need > ctx->d_gather_cap || 2 * need > ctx->h_gather_cap)
+  {
+    for (int k = 0; k < 2; k++) // (nothing queued may still be reading what is about to be freed)
+      if (ctx->gather_ev_used[k] && hipEventSynchronize(ctx->gather_ev[k]) != hipSuccess)
+        return HSRANS_E_HIP;
+    const size_t want = 2 * need > (256u << 10) ? 2 * need : (256u << 10);
+    if (!grow(&ctx->d_gather, &ctx->d_gather_cap, want) || !grow_pinned(&ctx->h_gather, &ctx->h_gather_cap, want))
+      return HSRANS_E_HIP;
+    ctx->gather_cursor = 0;
+    ctx->gather_ev_used[0] = ctx->gather_ev_used[1] = false;
+  }
+  const size_t half = ((ctx->d_gather_cap < ctx->h_gather_cap ? ctx->d_gather_cap : ctx->h_gather_cap) / 2) & ~(size_t)255;
+  uint32_t hf = ctx->gather_cursor >= half ? 1 : 0;
+  if (ctx->gather_cursor - hf * half + need > half)
+  {
+    hf ^= 1;
+    ctx->gather_cursor = hf * half;
+  }
+  // (a region never straddles the halves, so a half is always entered at its first byte)
+  if (ctx->gather_cursor == hf * half && ctx->gather_ev_used[hf] && hipEventSynchronize(ctx->gather_ev[hf]) != hipSuccess)
+    return HSRANS_E_HIP;
+  region->host = ctx->h_gather + ctx->gather_cursor;
+  region->dev = ctx->d_gather + ctx->gather_cursor;
+  region->half = hf;
+  region->bytes = need;
+  return HSRANS_OK;
+}
+
+// the event of a half's last launch stands for every launch before it
+int gather_region_order(hsrans_ctx *ctx, hipStream_t s)
+{
+  if (ctx->gather_have_last && ctx->gather_last_stream != s && hipStreamWaitEvent(s, ctx->gather_ev[ctx->gather_last_half], 0) != hipSuccess)
+    return HSRANS_E_HIP;
+  return HSRANS_OK;
+}
+
+int gather_region_commit(hsrans_ctx *ctx, const GatherRegion &region, hipStream_t s)
+{
+  if (hipEventRecord(ctx->gather_ev[region.half], s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  ctx->gather_ev_used[region.half] = true;
+  ctx->gather_have_last = true;
+  ctx->gather_last_stream = s;
+  ctx->gather_last_half = region.half;
+  ctx->gather_cursor += region.bytes;
+  return HSRANS_OK;
+}
+
 extern "C"
 {
 
@@ -110,8 +178,7 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
     return HSRANS_E_FORMAT;
   if (!any)
     return HSRANS_OK;
-  // (the floor: the compiled-in one unless the plan was made under HSRANS_GATHER_MIN_SEGMENT, the sweep's knob)
-  const uint64_t L = segment_for(d->tuning.gather_min_segment ? d->tuning.gather_min_segment : kGatherMinSegment, h.decoded_len, h.n_chains, h.states, h.interval);
+  const uint64_t L = gather_segment_of(d);
   const size_t n_tasks = cut_tasks(L, h.decoded_len, ranges, count, nullptr, 0);
   if (n_tasks == 0 || n_tasks > 0x7FFFFFFFu)
     return HSRANS_E_ARG;
@@ -119,43 +186,16 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
 
-  // The task list goes up with one stream-ordered copy in front of the launch.  Its buffers — page-locked on the host, so that the copy
-  // really is asynchronous, and on the device — belong to the context and are used as two halves, call after call taking the next region:
-  // a queued gather's tasks are never overwritten under it.  Before a half is entered again the last launch that used it is waited for
-  // (a wait that only happens when the device is more than half a buffer of task lists behind).
+  // The task list goes up with one stream-ordered copy in front of the launch, through a region of the context's task buffers
   std::lock_guard<std::mutex> lk(ctx->lock);
-  const size_t need = (n_tasks * sizeof(GatherTask) + 255) & ~(size_t)255;
-  for (int k = 0; k < 2; k++)
-    if (ctx->gather_ev[k] == nullptr && hipEventCreateWithFlags(&ctx->gather_ev[k], hipEventDisableTiming) != hipSuccess)
-      return HSRANS_E_HIP;
-  if (2 * need > ctx->d_gather_cap || 2 * need > ctx->h_gather_cap)
-  {
-    for (int k = 0; k < 2; k++) // (nothing queued may still be reading what is about to be freed)
-      if (ctx->gather_ev_used[k] && hipEventSynchronize(ctx->gather_ev[k]) != hipSuccess)
-        return HSRANS_E_HIP;
-    const size_t want = 2 * need > (256u << 10) ? 2 * need : (256u << 10);
-    if (!grow(&ctx->d_gather, &ctx->d_gather_cap, want) || !grow_pinned(&ctx->h_gather, &ctx->h_gather_cap, want))
-      return HSRANS_E_HIP;
-    ctx->gather_cursor = 0;
-    ctx->gather_ev_used[0] = ctx->gather_ev_used[1] = false;
-  }
-  const size_t half = ((ctx->d_gather_cap < ctx->h_gather_cap ? ctx->d_gather_cap : ctx->h_gather_cap) / 2) & ~(size_t)255;
-  uint32_t hf = ctx->gather_cursor >= half ? 1 : 0;
-  if (ctx->gather_cursor - hf * half + need > half)
-  {
-    hf ^= 1;
-    ctx->gather_cursor = hf * half;
-  }
-  // (a region never straddles the halves, so a half is always entered at its first byte)
-  if (ctx->gather_cursor == hf * half && ctx->gather_ev_used[hf] && hipEventSynchronize(ctx->gather_ev[hf]) != hipSuccess)
-    return HSRANS_E_HIP;
-  hsrans_gather_task *h_tasks = (hsrans_gather_task *)(ctx->h_gather + ctx->gather_cursor);
-  uint8_t *d_tasks = ctx->d_gather + ctx->gather_cursor;
+  GatherRegion region;
+  const int rc = gather_region_take(ctx, (n_tasks * sizeof(GatherTask) + 255) & ~(size_t)255, &region);
+  if (rc != HSRANS_OK)
+    return rc;
+  hsrans_gather_task *h_tasks = (hsrans_gather_task *)region.host;
   if (cut_tasks(L, h.decoded_len, ranges, count, h_tasks, n_tasks) != n_tasks)
     return HSRANS_E_ARG;
-  // gathers of one context form one chain on the device, whatever streams they are queued on: the event of a half's last launch then
-  // stands for every launch before it
-  if (ctx->gather_have_last && ctx->gather_last_stream != s && hipStreamWaitEvent(s, ctx->gather_ev[ctx->gather_last_half], 0) != hipSuccess)
+  if (gather_region_order(ctx, s) != HSRANS_OK)
     return HSRANS_E_HIP;
 
   GatherParams gp{};
@@ -164,25 +204,19 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
   gp.dst = (uint8_t *)d_dst;
   gp.plan = d->d_plan;
   gp.status = d->d_status;
-  gp.tasks = (const GatherTask *)d_tasks;
+  gp.tasks = (const GatherTask *)region.dev;
   gp.n_tasks = (uint32_t)n_tasks;
   const uint32_t table_mode = d->pa.table != nullptr ? d->pa.table_mode : 0;
   gp.table = d->pa.table;
   gp.hist_copy = d->pa.hist_copy;
   gp.hist_off = d->pa.hist_off;
   const GatherShape shape = gather_shape(d->tuning, h, ctx->geom, table_mode, gp.n_tasks);
-  if (hipMemcpyAsync(d_tasks, h_tasks, n_tasks * sizeof(GatherTask), hipMemcpyHostToDevice, s) != hipSuccess || launch_gather(gp, shape, s) != hipSuccess ||
-      hipEventRecord(ctx->gather_ev[hf], s) != hipSuccess)
+  if (hipMemcpyAsync(region.dev, h_tasks, n_tasks * sizeof(GatherTask), hipMemcpyHostToDevice, s) != hipSuccess || launch_gather(gp, shape, s) != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
   }
-  ctx->gather_ev_used[hf] = true;
-  ctx->gather_have_last = true;
-  ctx->gather_last_stream = s;
-  ctx->gather_last_half = hf;
-  ctx->gather_cursor += need;
-  return HSRANS_OK;
+  return gather_region_commit(ctx, region, s);
 }
 
 size_t hsrans_gather_workspace_bytes(uint32_t max_count)
@@ -211,7 +245,7 @@ int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *d, const
   cp.ranges = (const GatherRange *)d_ranges;
   cp.count = d_count;
   cp.max_count = max_count;
-  cp.segment = segment_for(d->tuning.gather_min_segment ? d->tuning.gather_min_segment : kGatherMinSegment, h.decoded_len, h.n_chains, h.states, h.interval);
+  cp.segment = gather_segment_of(d);
   cp.decoded_len = h.decoded_len;
   cp.out_lo = d->out_lo;
   cp.out_hi = d->out_hi;

@@ -322,6 +322,26 @@ void mt_plan_adopt(hsrans_dplan *d, const EncParams &ep, const PlanHeader &h, hi
 size_t raw_plan(hsrans_ctx *ctx, const EncShape &sh, uint64_t total, const uint64_t *index_groups, const uint8_t *header, const uint32_t *ck_states,
                 const uint32_t *ck_pos, uint8_t *plan_out, size_t plan_capacity, size_t *plan_size, hsrans_dplan **out_dplan);
 
+// ---- what the host-ranges gathers share (hsrans_capi_gather.cpp): hsrans_decode_device_gather and hsrans_decode_device_gather_batch ----
+// the segment length L a gather of d cuts its ranges at: hsrans_gather_segment's rule with the plan's floor (HSRANS_GATHER_MIN_SEGMENT
+// when the plan was made, else the compiled-in one)
+uint64_t gather_segment_of(const hsrans_dplan *d);
+// A region of the context's task buffers (ctx->h_gather, its device twin), under ctx->lock.  The buffers are used as two halves, call
+// after call taking the next region: a queued gather's tasks are never overwritten under it.  gather_region_take grows the buffers
+// where `need` (a multiple of 256) asks for it and waits for the last launch that used a half before the half is entered again; the
+// caller fills `host`, calls gather_region_order, queues the copy to `dev` and its launches on `s`, then gather_region_commit.
+struct GatherRegion
+{
+  uint8_t *host = nullptr, *dev = nullptr;
+  uint32_t half = 0;
+  size_t bytes = 0;
+};
+int gather_region_take(hsrans_ctx *ctx, size_t need, GatherRegion *region);
+// gathers of one context form one chain on the device, whatever streams they are queued on: `s` waits for the gather before it
+int gather_region_order(hsrans_ctx *ctx, hipStream_t s);
+// records the region's event behind the launches on `s` and moves the cursor; HSRANS_E_HIP: nothing is recorded, the region is free again
+int gather_region_commit(hsrans_ctx *ctx, const GatherRegion &region, hipStream_t s);
+
 // a page-locked, device-mapped host range: the address the GPU reaches it at, else null (hsrans_capi.cpp)
 uint8_t *device_view_of_host(const void *ptr, size_t bytes);
 // hsrans_decode_device_indexing's body; have_lock: the caller holds ctx->lock already (hsrans_capi_index.cpp)

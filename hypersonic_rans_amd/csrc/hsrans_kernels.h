@@ -463,6 +463,45 @@ GatherShape gather_ranges_shape(const Tuning &tn, const PlanHeader &h, const Dev
 // asynchronous on `stream`; two launches, nothing else (capturable)
 hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &cp, const GatherShape &shape, hipStream_t stream);
 
+// ---- byte ranges of many streams, one launch per table layout (hsrans_decode_device_gather_batch): k_gather_set ------------------
+// what a wave needs of the member its task belongs to: uploaded once per gather set, one record per member
+struct GatherSetMember
+{
+  const uint8_t *plan; // the member's plan blob (device)
+  uint32_t *status;    // ... and its status word
+  const uint8_t *stream; // device, 16-byte aligned
+  uint64_t stream_len;
+  // members with a host-built table: the table, the counts it was made from and where the stream keeps them
+  const uint2 *table;
+  const uint16_t *hist_copy;
+  uint64_t hist_off;
+  uint64_t segment, decoded_len, out_lo, out_hi; // the member's task length L and what its ranges are checked against (the host's cut; no kernel reads them)
+  uint32_t states, bits;
+};
+static_assert(sizeof(GatherSetMember) == 96, "GatherSetMember layout");
+struct GatherSetTask // == hsrans_gather_batch_task (include/hsrans_hip.h)
+{
+  uint64_t begin, end;
+  int64_t dst_delta;
+  uint32_t member, reserved;
+};
+static_assert(sizeof(GatherSetTask) == 32, "GatherSetTask layout");
+struct GatherSetParams
+{
+  const GatherSetMember *members; // device
+  const GatherSetTask *tasks;     // device: the launch's entries, wave w of workgroup b runs entry b * waves + w
+  uint32_t n_tasks;
+  uint8_t *dst; // device, any alignment
+  uint32_t table_bytes; // the largest table among the kind's members: what the LDS layout leaves room for per workgroup (shared) or wave (a multiple of 16)
+};
+// the LDS a decode table of layout `mode` takes at `bits`, rounded up to 16 bytes (0: the layout that stays in global memory)
+uint32_t gather_table_bytes(int mode, uint32_t bits);
+// the launch of n_tasks tasks of one kind (mode, shared): waves per workgroup and LDS by gather_shape's rule for table_bytes, the kind's
+// largest table; the grid is that of n_tasks entries (a launch whose entries are padded is given its own by the caller)
+GatherShape gather_set_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t n_tasks);
+// asynchronous on `stream`; one launch
+hipError_t launch_gather_set(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream);
+
 DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
 LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f); // (reads persistent, table_mode, interval, dual, n_groups, index_pass)
 struct TableChoice

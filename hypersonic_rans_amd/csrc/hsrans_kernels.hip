@@ -34,7 +34,7 @@
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
 //   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device
 //   kernels_gather.h    k_gather           byte ranges of one stream: one wave per task, entered at the chain that holds its first byte
-//                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks
+//                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks; k_gather_set   byte ranges of many streams: every task names its member, one launch per table layout
 // This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -243,6 +243,8 @@ struct GatherKernel
   void (*launch)(const GatherParams &gp, const GatherShape &shape, hipStream_t stream);
   const void *fn_ranges; // k_gather_ranges of the same table layout
   void (*launch_ranges)(const GatherParams &gp, const GatherRangesParams &rp, const GatherShape &shape, hipStream_t stream);
+  const void *fn_set; // k_gather_set of the same table layout
+  void (*launch_set)(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream);
 };
 template <int MODE, bool SHARED>
 static GatherKernel gather_entry()
@@ -252,6 +254,10 @@ static GatherKernel gather_entry()
           (const void *)k_gather_ranges<MODE, SHARED>,
           [](const GatherParams &gp, const GatherRangesParams &rp, const GatherShape &shape, hipStream_t stream) {
             hipLaunchKernelGGL((k_gather_ranges<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, gp, rp);
+          },
+          (const void *)k_gather_set<MODE, SHARED>,
+          [](const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream) {
+            hipLaunchKernelGGL((k_gather_set<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, sp);
           }};
 }
 static const GatherKernel g_gather_kernels[] = {gather_entry<kModePack, false>(),  gather_entry<kModePackM1, false>(), gather_entry<kModeTwoLevel, false>(),
@@ -275,6 +281,7 @@ hipError_t prepare_kernels(DeviceGeom *geom)
   {
     fns.push_back(g.fn);
     fns.push_back(g.fn_ranges);
+    fns.push_back(g.fn_set);
   }
   for (const void *fn : fns)
   {
@@ -962,6 +969,20 @@ hipError_t launch_decode(const Tuning &tn, const KParams &kp_in, const PlanHeade
 // ---------------------------------------------------------------------------------------------------------------
 // hsrans_decode_device_gather's launch: a function of its own, beside choose_launch / launch_decode and touching neither
 // ---------------------------------------------------------------------------------------------------------------
+// waves per workgroup, LDS and grid of g's layout for n_tasks tasks and a table of table_bytes
+static void gather_waves(GatherShape &g, const DeviceGeom &dg, uint32_t table_bytes, uint32_t n_tasks)
+{
+  const uint32_t wave_bytes = g.shared ? kWaveRingBytes : kWaveRingBytes + ((table_bytes + 15) & ~15u);
+  const uint32_t fixed = g.shared ? table_bytes : 0;
+  // few tasks: smaller workgroups, so that they reach more CUs (a task is one wave's work whatever the workgroup)
+  uint32_t waves = g.shared ? 16 : 4;
+  while (waves > 1 && (waves * wave_bytes + fixed > (g.shared ? dg.max_lds : dg.max_lds / 2) || (waves > (g.shared ? 4u : 1u) && (n_tasks + waves - 1) / waves < 2 * dg.num_cus)))
+    waves /= 2;
+  g.waves = waves;
+  g.lds = waves * wave_bytes + fixed;
+  g.grid = (n_tasks + waves - 1) / waves;
+}
+
 GatherShape gather_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t n_tasks)
 {
   GatherShape g{};
@@ -976,16 +997,18 @@ GatherShape gather_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom
     hp.flags &= ~kPlanWalk;
     g.mode = launch_shape(tn, hp, dg, LaunchFacts{}).mode;
   }
-  const uint32_t table_bytes = table_bytes_for(g.mode, h.bits);
-  const uint32_t wave_bytes = g.shared ? kWaveRingBytes : kWaveRingBytes + ((table_bytes + 15) & ~15u);
-  const uint32_t fixed = g.shared ? table_bytes : 0;
-  // few tasks: smaller workgroups, so that they reach more CUs (a task is one wave's work whatever the workgroup)
-  uint32_t waves = g.shared ? 16 : 4;
-  while (waves > 1 && (waves * wave_bytes + fixed > (g.shared ? dg.max_lds : dg.max_lds / 2) || (waves > (g.shared ? 4u : 1u) && (n_tasks + waves - 1) / waves < 2 * dg.num_cus)))
-    waves /= 2;
-  g.waves = waves;
-  g.lds = waves * wave_bytes + fixed;
-  g.grid = (n_tasks + waves - 1) / waves;
+  gather_waves(g, dg, table_bytes_for(g.mode, h.bits), n_tasks);
+  return g;
+}
+
+uint32_t gather_table_bytes(int mode, uint32_t bits) { return (table_bytes_for(mode, bits) + 15) & ~15u; }
+
+GatherShape gather_set_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t n_tasks)
+{
+  GatherShape g{};
+  g.mode = mode;
+  g.shared = shared;
+  gather_waves(g, dg, table_bytes, n_tasks);
   return g;
 }
 
@@ -998,6 +1021,21 @@ hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipSt
     {
       (void)hipGetLastError();
       g.launch(gp, shape, stream);
+      return hipGetLastError();
+    }
+  return hipErrorNotSupported;
+}
+
+// hsrans_decode_device_gather_batch's launch of one kind: k_gather_set of the kind's table layout
+hipError_t launch_gather_set(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream)
+{
+  if (shape.grid == 0 || shape.lds > 160 * 1024 || sp.n_tasks == 0 || (uint64_t)shape.grid * shape.waves < sp.n_tasks || (sp.table_bytes & 15) != 0)
+    return hipErrorInvalidValue;
+  for (const GatherKernel &g : g_gather_kernels)
+    if (g.mode == shape.mode && g.shared == shape.shared)
+    {
+      (void)hipGetLastError();
+      g.launch_set(sp, shape, stream);
       return hipGetLastError();
     }
   return hipErrorNotSupported;

@@ -1,4 +1,4 @@
-// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather, hsrans_decode_device_gather_indirect) — gather_groups, gather_tail, run_gather, k_gather, k_gather_cut, k_gather_ranges.
+// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather, hsrans_decode_device_gather_indirect), and of many streams in one launch per table layout (hsrans_decode_device_gather_batch) — gather_groups, gather_tail, run_gather, k_gather, k_gather_cut, k_gather_ranges, k_gather_set.
 // Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the host-side launcher).
 //
 // One wavefront = one task (GatherTask: decoded bytes [begin, end) of the stream, destination = GatherParams::dst + byte + dst_delta).  The
@@ -378,6 +378,93 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(100))) k_
     const uint64_t begin = cut > offset ? cut : offset, end = cut + rp.segment < stop ? cut + rp.segment : stop;
     run_gather<MODE, SHARED>(c, pv, gp.dst, begin, end, (int64_t)(dst_offset - offset));
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_gather_batch: the tasks of many streams (the members of a gather set) whose gathers use one table layout, in one
+// launch.  Every entry names its member; the wave takes stream, plan, status word, states and bits from the member's record (all
+// wave-uniform) instead of from the launch's parameters, then runs its task as k_gather does.
+// blockDim.x = 64 * waves; wave w of block b runs entry b * waves + w.
+// SHARED: the host has sorted the entries by member and padded every member's run to a multiple of `waves` (hsrans_gather_batch_tasks),
+// so a workgroup serves one member — that of its first entry — and copies that member's host-built table; the first workgroup of a
+// member's run (the one before it serves another member, or there is none) checks that the member's stream carries the histogram the
+// table was built from, as workgroup 0 of k_gather does.
+// LDS as k_gather, with room for the largest table among the launch's members (sp.table_bytes) where k_gather has the plan's.
+// ---------------------------------------------------------------------------------------------------------------
+template <int MODE, bool SHARED>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(100))) k_gather_set(GatherSetParams sp)
+{
+  extern __shared__ u32x4 smem_v[];
+  uint8_t *smem = (uint8_t *)smem_v;
+  const uint32_t waves = blockDim.x >> 6;
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const uint32_t first = blockIdx.x * waves; // (< n_tasks: the grid is sized from the entries)
+  const uint32_t entry = first + wave;
+  if (!SHARED && entry >= sp.n_tasks) // (SHARED: the entries fill whole workgroups, and every wave must reach the barrier)
+    return;
+  const GatherSetTask *task = sp.tasks + (SHARED && entry >= sp.n_tasks ? first : entry);
+  const uint32_t member = uni(SHARED ? sp.tasks[first].member : task->member);
+  const GatherSetMember *rec = sp.members + member;
+  const PlanView pv = plan_view((const uint8_t *)uni64((uint64_t)(uintptr_t)rec->plan));
+  const uint32_t bits = uni(rec->bits);
+
+  WaveCtx c;
+  c.stream = (const uint8_t *)uni64((uint64_t)(uintptr_t)rec->stream);
+  c.stream_len = uni64(rec->stream_len);
+  c.stream_lo = 0;
+  c.out = sp.dst;
+  c.out_cap = 0; // (not used: every store of these kernels is tested against its task)
+  c.status = (uint32_t *)uni64((uint64_t)(uintptr_t)rec->status);
+  c.bits = bits;
+  c.S = uni(rec->states);
+  c.lane = threadIdx.x & 63;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
+
+  if (SHARED)
+  {
+    const uint2 *table = (const uint2 *)uni64((uint64_t)(uintptr_t)rec->table);
+    uint8_t *ring0 = table_first_mode(MODE) ? smem + sp.table_bytes : smem;
+    c.rings = ring0 + wave * kWaveRingBytes;
+    c.table = table_first_mode(MODE) ? smem : smem + waves * kWaveRingBytes;
+    c.table_b = c.table;
+    c.gtable = table;
+    c.scratch_cnt = (uint16_t *)ring0;
+    c.scratch_cum = (uint16_t *)(ring0 + 512);
+    // the member's host-built table: one coalesced 16-byte load + LDS store per thread (gather_setup)
+    const uint32_t entries = table_bytes_for(MODE, bits) / 8;
+    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
+      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(table + i);
+    if (threadIdx.x < 64 && (first == 0 || uni(sp.tasks[first - 1].member) != member))
+    {
+      const uint64_t hist_off = uni64(rec->hist_off);
+      const uint16_t *hist_copy = (const uint16_t *)uni64((uint64_t)(uintptr_t)rec->hist_copy);
+      bool same = HSRANS_HIST_IN_RANGE(c, hist_off);
+      if (same)
+      {
+        const uint64_t mine = *(const uint64_t *)(hist_copy + 4 * c.lane);
+        uint64_t theirs = 0;
+        for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
+          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + hist_off + 8 * c.lane + 2 * b);
+        same = mine == theirs;
+      }
+      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
+        atomicOr(c.status, kStatusBadHist);
+    }
+    __syncthreads();
+    if (entry >= sp.n_tasks)
+      return;
+  }
+  else
+  {
+    c.rings = smem + wave * kWaveRingBytes; // all rings first: they stay kRingBytes-aligned
+    c.table = smem + waves * kWaveRingBytes + wave * sp.table_bytes;
+    c.table_b = c.table;
+    c.gtable = nullptr;
+    c.scratch_cnt = (uint16_t *)c.rings;
+    c.scratch_cum = (uint16_t *)(c.rings + 512);
+  }
+  run_gather<MODE, SHARED>(c, pv, sp.dst, uni64(task->begin), uni64(task->end), (int64_t)uni64((uint64_t)task->dst_delta));
 }
 
 } // namespace hsrans

@@ -284,6 +284,77 @@ int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *dplan, c
                                          const hsrans_range *d_ranges /* DEVICE, 8-byte aligned */, const uint32_t *d_count /* DEVICE, or NULL = max_count */,
                                          uint32_t max_count, void *d_dst, size_t dst_capacity, void *d_workspace /* DEVICE, 256-byte aligned */,
                                          size_t workspace_bytes, void *hip_stream);
+/* ------------------------------------------------------------------------------------------------------------
+ * Byte ranges of MANY streams that stay compressed in device memory: a gather set binds `count` device plans to their
+ * streams once, and one call then fetches ranges of any of them — for every r < count the decoded bytes
+ * [ranges[r].offset, + ranges[r].length) of member ranges[r].member land at (uint8_t *)d_dst + ranges[r].dst_offset; no
+ * other byte of d_dst is written.  Byte for byte what one hsrans_decode_device_gather per member gives with that
+ * member's ranges, all into the same d_dst: every member is cut at the segment length L of its single call (a plan
+ * made under HSRANS_GATHER_MIN_SEGMENT included), hence into the tasks hsrans_gather_tasks reports for it; the alignment
+ * rules and the caller's responsibility for overlapping destinations are the single call's.
+ *   - members: d_streams[k] (16-byte aligned, stream_lengths[k] == the plan's stream length) belongs to member k from
+ *     hsrans_gather_set_create on; a member cannot be rebound.  A device plan may be a member of any number of sets, may
+ *     appear twice in one set and stays usable alone (a gather keeps no per-launch state in a plan).  The plans must
+ *     outlive the set and must not be refilled while it exists.  One record per member is uploaded, once, here.
+ *   - launches: a member's kind is the decode-table layout its single gather uses — 0..2 a table per wave (bits <= 11,
+ *     12, >= 13), 3..5 the plan's host-built table, one copy per workgroup — and a call makes ONE launch per kind that
+ *     has tasks: at most six, whatever the number of members or ranges.  In the launches of kinds 3..5 a workgroup
+ *     serves one member (hsrans_gather_batch_tasks).
+ *   - asynchronous on hip_stream; `ranges` (host memory) is read before the call returns.  The task lists go through the
+ *     context's task buffer: gathers of one context, single and batch alike, are ordered among themselves.
+ *   - a malformed histogram sets the status word of THAT member's plan; hsrans_gather_set_status synchronises
+ *     hip_stream once, fills member_status[members] (may be NULL) with each member's hsrans_dplan_status and returns
+ *     the first that is not HSRANS_OK (a plan that is a member twice reports the same code for both).
+ * hsrans_gather_set_create returns HSRANS_E_ARG: a null pointer, count == 0 or > 65,536, a plan of another context, a
+ *   misaligned stream; HSRANS_E_FORMAT: a plan without entry points, stream_lengths[k] != the plan's stream length.
+ * hsrans_decode_device_gather_batch returns HSRANS_E_ARG, nothing launched and nothing uploaded: member >= the set's
+ *   members or reserved != 0, a range beyond the member's decoded bytes (or outside what a sliced plan decodes),
+ *   dst_offset + length beyond dst_capacity, a null `ranges` with count > 0, 2^31 or more tasks;
+ *   HSRANS_OK with nothing launched: count == 0 or only empty ranges. */
+typedef struct hsrans_gather_set hsrans_gather_set;
+typedef struct hsrans_member_range
+{
+  uint64_t offset, length, dst_offset;
+  uint32_t member, reserved; /* reserved: 0 */
+} hsrans_member_range; /* 32 bytes */
+typedef struct hsrans_gather_set_info_t
+{
+  uint32_t members;
+  uint32_t launches;         /* of the last hsrans_decode_device_gather_batch on the set (0: none yet, or it had nothing to do) */
+  uint32_t kind_members[6];  /* members per kind */
+  /* the last call, per kind: its tasks, the entries of its launch (tasks + padding), and the launch's shape */
+  uint32_t kind_tasks[6], kind_entries[6], kind_grid[6], kind_waves[6], kind_lds_bytes[6];
+} hsrans_gather_set_info_t;
+int hsrans_gather_set_create(hsrans_ctx *ctx, hsrans_dplan *const *dplans, const void *const *d_streams, const size_t *stream_lengths,
+                             uint32_t count /* 1 .. 65,536 */, hsrans_gather_set **out_set);
+void hsrans_gather_set_destroy(hsrans_gather_set *set);
+int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, const hsrans_member_range *ranges /* host */, uint32_t count,
+                                      void *d_dst, size_t dst_capacity, void *hip_stream);
+int hsrans_gather_set_status(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip_stream, int *member_status /* [members] or NULL */);
+int hsrans_gather_set_info(const hsrans_gather_set *set, hsrans_gather_set_info_t *info);
+/* The host-side cut of that call, a pure function (no GPU): the task list of ONE kind's launch, in launch order — wave w
+ * of workgroup b runs entry b * waves + w.  Every range is cut exactly as hsrans_gather_tasks cuts it for its member
+ * (decoded_len, n_chains, states, interval), and the member's number stands beside each task.
+ *   kinds 0..2 (a table per wave): the tasks of the ranges whose member is of `kind`, in range order.
+ *   kinds 3..5 (one table per workgroup): the same tasks stable-sorted by member, each member's run padded with empty
+ *     tasks (begin == end == 0, the same member) up to a multiple of `waves`: every workgroup serves exactly one member.
+ *     A member without tasks contributes no entry.
+ * Returns the entries of the launch and writes at most `capacity` of them (out may be NULL when capacity is 0); 0 for a
+ * null pointer with a count > 0, a range beyond its member's decoded_len, member >= n_members, kind > 5, waves == 0, a
+ * range that is not empty on a member with n_chains == 0 or states == 0. */
+typedef struct hsrans_gather_member
+{
+  uint64_t decoded_len;
+  uint32_t n_chains, states, interval, kind; /* kind 0..5; 3..5 = shared table */
+} hsrans_gather_member; /* 24 bytes */
+typedef struct hsrans_gather_batch_task
+{
+  uint64_t begin, end;
+  int64_t dst_delta;
+  uint32_t member, reserved;
+} hsrans_gather_batch_task; /* 32 bytes */
+size_t hsrans_gather_batch_tasks(const hsrans_gather_member *members, uint32_t n_members, const hsrans_member_range *ranges, uint32_t count,
+                                 uint32_t kind, uint32_t waves, hsrans_gather_batch_task *out, size_t capacity);
 
 /* Plan an mt_ stream that only exists in device memory: the header chain (src/mt_rANS32x64_16w_decode.cpp:166-227) is
  * followed by a device kernel; synchronises `hip_stream` twice (chain count, then the finished plan). HSRANS_MT only. */

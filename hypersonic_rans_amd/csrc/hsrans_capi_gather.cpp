@@ -4,6 +4,9 @@
 // hsrans_decode_device_gather_indirect: the same for ranges that are in device memory — no cut, no task buffer and no lock here: the
 // device cuts (k_gather_cut, k_gather_ranges through launch_gather_ranges), the caller brings the workspace.
 // gather_region_*: the context's task buffer as regions, shared with hsrans_decode_device_gather_batch (hsrans_capi_gather_batch.cpp).
+// What all three entries do alike is written once: the rules of a range (gather_range_ok, gather_range_tasks: hsrans_kernels.h, the
+// device's too) and the plan test, the fill of a GatherSource and the cut of a range at multiples of L (gather_plan_ok,
+// gather_source_of, gather_cut_range: hsrans_internal.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -55,23 +58,35 @@ static size_t cut_tasks(uint64_t L, uint64_t decoded_len, const hsrans_range *ra
   if (L == 0 || (ranges == nullptr && count > 0) || (out == nullptr && capacity > 0))
     return 0;
   for (uint32_t r = 0; r < count; r++)
-    if (ranges[r].offset > decoded_len || ranges[r].length > decoded_len - ranges[r].offset)
+    if (!gather_extent_ok(ranges[r].offset, ranges[r].length, decoded_len))
       return 0;
   size_t n = 0;
   for (uint32_t r = 0; r < count; r++)
   {
-    const uint64_t stop = ranges[r].offset + ranges[r].length;
     const int64_t delta = (int64_t)(ranges[r].dst_offset - ranges[r].offset); // (modulo 2^64: the device adds it back the same way)
-    for (uint64_t b = ranges[r].offset; b < stop;)
-    {
-      const uint64_t cut = (b / L + 1) * L, e = cut < stop ? cut : stop;
+    gather_cut_range(ranges[r].offset, ranges[r].length, L, [&](uint64_t b, uint64_t e) {
       if (n < capacity)
         out[n] = hsrans_gather_task{b, e, delta};
       n++;
-      b = e;
-    }
+    });
   }
   return n;
+}
+
+// the launch parameters of a gather of d over the stream at d_stream into d_dst, all but the tasks
+static GatherParams gather_params_of(const hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_dst)
+{
+  const GatherSource gs = gather_source_of(d, d_stream, stream_length);
+  GatherParams gp{};
+  gp.stream = gs.stream;
+  gp.stream_len = gs.stream_len;
+  gp.dst = (uint8_t *)d_dst;
+  gp.plan = gs.plan;
+  gp.status = gs.status;
+  gp.table = gs.table;
+  gp.hist_copy = gs.hist_copy;
+  gp.hist_off = gs.hist_off;
+  return gp;
 }
 
 // (the floor: the compiled-in one unless the plan was made under HSRANS_GATHER_MIN_SEGMENT, the sweep's knob)
@@ -167,14 +182,11 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
   for (uint32_t r = 0; r < count; r++)
   {
     const hsrans_range &g = ranges[r];
-    if (g.offset > h.decoded_len || g.length > h.decoded_len - g.offset || g.dst_offset > dst_capacity || g.length > dst_capacity - g.dst_offset)
-      return HSRANS_E_ARG;
-    // (a slice of a plan decodes only part of the output: bytes none of its chains writes cannot be asked for)
-    if (g.length != 0 && (g.offset < d->out_lo || g.offset + g.length > d->out_hi))
+    if (!gather_range_ok(g.offset, g.length, g.dst_offset, h.decoded_len, d->out_lo, d->out_hi, dst_capacity))
       return HSRANS_E_ARG;
     any = any || g.length != 0;
   }
-  if ((h.flags & kPlanWalk) || h.n_chains == 0 || stream_length != h.stream_len)
+  if (!gather_plan_ok(d, stream_length))
     return HSRANS_E_FORMAT;
   if (!any)
     return HSRANS_OK;
@@ -198,19 +210,10 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
   if (gather_region_order(ctx, s) != HSRANS_OK)
     return HSRANS_E_HIP;
 
-  GatherParams gp{};
-  gp.stream = (const uint8_t *)d_stream;
-  gp.stream_len = stream_length;
-  gp.dst = (uint8_t *)d_dst;
-  gp.plan = d->d_plan;
-  gp.status = d->d_status;
+  GatherParams gp = gather_params_of(d, d_stream, stream_length, d_dst);
   gp.tasks = (const GatherTask *)region.dev;
   gp.n_tasks = (uint32_t)n_tasks;
-  const uint32_t table_mode = d->pa.table != nullptr ? d->pa.table_mode : 0;
-  gp.table = d->pa.table;
-  gp.hist_copy = d->pa.hist_copy;
-  gp.hist_off = d->pa.hist_off;
-  const GatherShape shape = gather_shape(d->tuning, h, ctx->geom, table_mode, gp.n_tasks);
+  const GatherShape shape = gather_shape(d->tuning, h, ctx->geom, gather_table_mode(d), gp.n_tasks);
   if (hipMemcpyAsync(region.dev, h_tasks, n_tasks * sizeof(GatherTask), hipMemcpyHostToDevice, s) != hipSuccess || launch_gather(gp, shape, s) != hipSuccess)
   {
     (void)hipGetLastError();
@@ -234,7 +237,7 @@ int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *d, const
       workspace_bytes < hsrans_gather_workspace_bytes(max_count))
     return HSRANS_E_ARG;
   const PlanHeader &h = d->hdr;
-  if ((h.flags & kPlanWalk) || h.n_chains == 0 || stream_length != h.stream_len)
+  if (!gather_plan_ok(d, stream_length))
     return HSRANS_E_FORMAT;
   if (max_count == 0)
     return HSRANS_OK;
@@ -252,17 +255,8 @@ int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *d, const
   cp.dst_capacity = dst_capacity;
   cp.workspace = (uint32_t *)d_workspace;
   cp.status = d->d_status;
-  GatherParams gp{};
-  gp.stream = (const uint8_t *)d_stream;
-  gp.stream_len = stream_length;
-  gp.dst = (uint8_t *)d_dst;
-  gp.plan = d->d_plan;
-  gp.status = d->d_status;
-  const uint32_t table_mode = d->pa.table != nullptr ? d->pa.table_mode : 0;
-  gp.table = d->pa.table;
-  gp.hist_copy = d->pa.hist_copy;
-  gp.hist_off = d->pa.hist_off;
-  const GatherShape shape = gather_ranges_shape(d->tuning, h, ctx->geom, table_mode, max_count, dst_capacity, cp.segment);
+  const GatherParams gp = gather_params_of(d, d_stream, stream_length, d_dst);
+  const GatherShape shape = gather_ranges_shape(d->tuning, h, ctx->geom, gather_table_mode(d), max_count, dst_capacity, cp.segment);
   if (launch_gather_ranges(gp, cp, shape, (hipStream_t)hip_stream) != hipSuccess)
   {
     (void)hipGetLastError();

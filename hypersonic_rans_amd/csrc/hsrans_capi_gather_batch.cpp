@@ -2,7 +2,8 @@
 // (device plans bound to their streams, one uploaded record per member), the host-side cut of the ranges into one kind's entries
 // (hsrans_gather_batch_tasks, a pure function), the argument checks and the launches (k_gather_set, kernels_gather.h, through
 // launch_gather_set in hsrans_kernels.hip).  The task lists go through the context's task buffer as hsrans_decode_device_gather's do
-// (gather_region_*, hsrans_capi_gather.cpp).
+// (gather_region_*, hsrans_capi_gather.cpp); range rules, plan test, the member's GatherSource and the cut of a range are the single
+// call's own functions (hsrans_kernels.h, hsrans_internal.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -46,14 +47,13 @@ static bool count_tasks(const hsrans_gather_member *members, uint32_t n_members,
   for (uint32_t r = 0; r < count; r++)
   {
     const hsrans_member_range &g = ranges[r];
-    if (g.member >= n_members || g.offset > members[g.member].decoded_len || g.length > members[g.member].decoded_len - g.offset)
+    if (g.member >= n_members || !gather_extent_ok(g.offset, g.length, members[g.member].decoded_len))
       return false;
     if (g.length == 0)
       continue;
-    const uint64_t L = segment[g.member];
-    if (L == 0)
+    if (segment[g.member] == 0)
       return false;
-    tasks[g.member] += (g.offset + g.length - 1) / L - g.offset / L + 1;
+    tasks[g.member] += gather_range_tasks(g.offset, g.length, segment[g.member]);
   }
   return true;
 }
@@ -82,17 +82,13 @@ static size_t cut_batch(const hsrans_gather_member *members, uint32_t n_members,
     const hsrans_member_range &g = ranges[r];
     if (members[g.member].kind != kind)
       continue;
-    const uint64_t L = segment[g.member], stop = g.offset + g.length;
     const int64_t delta = (int64_t)(g.dst_offset - g.offset); // (modulo 2^64: the device adds it back the same way)
     uint64_t &pos = shared ? at[g.member] : n;
-    for (uint64_t b = g.offset; b < stop;)
-    {
-      const uint64_t cut = (b / L + 1) * L, e = cut < stop ? cut : stop;
+    gather_cut_range(g.offset, g.length, segment[g.member], [&](uint64_t b, uint64_t e) {
       if (pos < capacity)
         out[pos] = hsrans_gather_batch_task{b, e, delta, g.member, 0};
       pos++;
-      b = e;
-    }
+    });
   }
   if (!shared)
     return (size_t)n;
@@ -137,11 +133,8 @@ int hsrans_gather_set_create(hsrans_ctx *ctx, hsrans_dplan *const *dplans, const
     if (dplans[k] == nullptr || dplans[k]->ctx != ctx || d_streams[k] == nullptr || ((uintptr_t)d_streams[k] & 15) != 0)
       return HSRANS_E_ARG;
   for (uint32_t k = 0; k < count; k++)
-  {
-    const PlanHeader &h = dplans[k]->hdr;
-    if ((h.flags & kPlanWalk) || h.n_chains == 0 || stream_lengths[k] != h.stream_len)
+    if (!gather_plan_ok(dplans[k], stream_lengths[k]))
       return HSRANS_E_FORMAT;
-  }
   hsrans_gather_set *set = new (std::nothrow) hsrans_gather_set;
   if (set == nullptr)
     return HSRANS_E_HIP;
@@ -157,8 +150,7 @@ int hsrans_gather_set_create(hsrans_ctx *ctx, hsrans_dplan *const *dplans, const
     const hsrans_dplan *d = dplans[k];
     const PlanHeader &h = d->hdr;
     // the member's kind: the table layout its single gather uses (gather_shape's decision, whatever the task count)
-    const uint32_t table_mode = d->pa.table != nullptr ? d->pa.table_mode : 0;
-    const GatherShape shape = gather_shape(d->tuning, h, ctx->geom, table_mode, 1);
+    const GatherShape shape = gather_shape(d->tuning, h, ctx->geom, gather_table_mode(d), 1);
     if (shape.mode < 0 || shape.mode >= (int)kGatherKinds || shape.shared != (shape.mode >= 3))
     {
       delete set;
@@ -174,13 +166,7 @@ int hsrans_gather_set_create(hsrans_ctx *ctx, hsrans_dplan *const *dplans, const
     if (table_bytes > set->kind_table_bytes[kind])
       set->kind_table_bytes[kind] = table_bytes;
     GatherSetMember &rec = recs[k];
-    rec.plan = d->d_plan;
-    rec.status = d->d_status;
-    rec.stream = (const uint8_t *)d_streams[k];
-    rec.stream_len = stream_lengths[k];
-    rec.table = d->pa.table;
-    rec.hist_copy = d->pa.hist_copy;
-    rec.hist_off = d->pa.hist_off;
+    rec.src = gather_source_of(d, d_streams[k], stream_lengths[k]);
     rec.segment = set->segment[k];
     rec.decoded_len = h.decoded_len;
     rec.out_lo = d->out_lo;
@@ -222,11 +208,7 @@ int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, c
     const hsrans_member_range &g = ranges[r];
     if (g.member >= n_members || g.reserved != 0)
       return HSRANS_E_ARG;
-    const uint64_t decoded_len = set->members[g.member].decoded_len;
-    if (g.offset > decoded_len || g.length > decoded_len - g.offset || g.dst_offset > dst_capacity || g.length > dst_capacity - g.dst_offset)
-      return HSRANS_E_ARG;
-    // (a slice of a plan decodes only part of the output: bytes none of its chains writes cannot be asked for)
-    if (g.length != 0 && (g.offset < set->out_lo[g.member] || g.offset + g.length > set->out_hi[g.member]))
+    if (!gather_range_ok(g.offset, g.length, g.dst_offset, set->members[g.member].decoded_len, set->out_lo[g.member], set->out_hi[g.member], dst_capacity))
       return HSRANS_E_ARG;
     any = any || g.length != 0;
   }

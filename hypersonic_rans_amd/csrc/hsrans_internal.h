@@ -326,6 +326,30 @@ size_t raw_plan(hsrans_ctx *ctx, const EncShape &sh, uint64_t total, const uint6
 // the segment length L a gather of d cuts its ranges at: hsrans_gather_segment's rule with the plan's floor (HSRANS_GATHER_MIN_SEGMENT
 // when the plan was made, else the compiled-in one)
 uint64_t gather_segment_of(const hsrans_dplan *d);
+// whether d can be gathered from over a stream of stream_length bytes: it has entry points (no walk plan, at least one chain) and is that stream's
+inline bool gather_plan_ok(const hsrans_dplan *d, size_t stream_length)
+{
+  return !(d->hdr.flags & hsrans::kPlanWalk) && d->hdr.n_chains != 0 && stream_length == d->hdr.stream_len;
+}
+// what the gather kernels need of d bound to the stream at d_stream (the table fields are null / 0 for a plan without a host-built table)
+inline hsrans::GatherSource gather_source_of(const hsrans_dplan *d, const void *d_stream, size_t stream_length)
+{
+  return hsrans::GatherSource{d->d_plan, d->d_status, (const uint8_t *)d_stream, stream_length, d->pa.table, d->pa.hist_copy, d->pa.hist_off};
+}
+// the table layout d's gathers use, as gather_shape takes it: that of its host-built table, 0 where its waves build their own
+inline uint32_t gather_table_mode(const hsrans_dplan *d) { return d->pa.table != nullptr ? d->pa.table_mode : 0; }
+// task(begin, end) for every one-wave task of decoded bytes [offset, offset + length): the range cut at the absolute multiples of L (> 0)
+template <typename Task>
+inline void gather_cut_range(uint64_t offset, uint64_t length, uint64_t L, Task &&task)
+{
+  const uint64_t stop = offset + length;
+  for (uint64_t b = offset; b < stop;)
+  {
+    const uint64_t cut = (b / L + 1) * L, e = cut < stop ? cut : stop;
+    task(b, e);
+    b = e;
+  }
+}
 // A region of the context's task buffers (ctx->h_gather, its device twin), under ctx->lock.  The buffers are used as two halves, call
 // after call taking the next region: a queued gather's tasks are never overwritten under it.  gather_region_take grows the buffers
 // where `need` (a multiple of 256) asks for it and waits for the last launch that used a half before the half is entered again; the

@@ -403,6 +403,22 @@ struct GatherTask // == hsrans_gather_task (include/hsrans_hip.h)
   int64_t dst_delta;
 };
 static_assert(sizeof(GatherTask) == 24, "GatherTask layout");
+// what a gather wave needs of one planned stream, filled on the host from a device plan and the stream it is bound to (gather_source_of):
+// the head of a gather set's member record (k_gather_set); k_gather and k_gather_ranges put it together from their parameters
+struct GatherSource
+{
+  const uint8_t *plan; // the plan blob (device)
+  uint32_t *status;    // ... and its status word
+  const uint8_t *stream; // device, 16-byte aligned
+  uint64_t stream_len;
+  // plans with a host-built table (shared-table launches) only: the table, the counts it was made from and where the stream keeps them
+  const uint2 *table;
+  const uint16_t *hist_copy;
+  uint64_t hist_off;
+};
+static_assert(sizeof(GatherSource) == 56, "GatherSource layout");
+// (flat, in this order: with the GatherSource embedded k_gather<3, true> took 18.4 instead of 17.5 us per launch in tools/gather_batch_rate.py's
+// single-call leg — the order decides which parameters the kernel loads together, and when)
 struct GatherParams
 {
   const uint8_t *stream; // device, 16-byte aligned
@@ -417,6 +433,19 @@ struct GatherParams
   const uint16_t *hist_copy;
   uint64_t hist_off;
 };
+// The rules of a range, once for the host entries and for k_gather_cut; none forms a sum that can wrap.
+// [offset, offset + length) lies inside [0, extent): a range against its stream's decoded length, its destination against dst_capacity
+__host__ __device__ inline bool gather_extent_ok(uint64_t offset, uint64_t length, uint64_t extent) { return offset <= extent && length <= extent - offset; }
+// ... and a range that has bytes asks only for bytes the plan's chains write, [out_lo, out_hi) (a slice of a plan decodes part of the output)
+__host__ __device__ inline bool gather_range_ok(uint64_t offset, uint64_t length, uint64_t dst_offset, uint64_t decoded_len, uint64_t out_lo, uint64_t out_hi, uint64_t dst_capacity)
+{
+  return gather_extent_ok(offset, length, decoded_len) && gather_extent_ok(dst_offset, length, dst_capacity) && (length == 0 || (offset >= out_lo && offset + length <= out_hi));
+}
+// the one-wave tasks of a range that is cut at the absolute multiples of the segment length (> 0)
+__host__ __device__ inline uint64_t gather_range_tasks(uint64_t offset, uint64_t length, uint64_t segment)
+{
+  return length == 0 ? 0 : (offset + length - 1) / segment - offset / segment + 1;
+}
 struct GatherShape
 {
   int mode;    // decode-table layout (kMode*)
@@ -467,14 +496,7 @@ hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &c
 // what a wave needs of the member its task belongs to: uploaded once per gather set, one record per member
 struct GatherSetMember
 {
-  const uint8_t *plan; // the member's plan blob (device)
-  uint32_t *status;    // ... and its status word
-  const uint8_t *stream; // device, 16-byte aligned
-  uint64_t stream_len;
-  // members with a host-built table: the table, the counts it was made from and where the stream keeps them
-  const uint2 *table;
-  const uint16_t *hist_copy;
-  uint64_t hist_off;
+  GatherSource src;
   uint64_t segment, decoded_len, out_lo, out_hi; // the member's task length L and what its ranges are checked against (the host's cut; no kernel reads them)
   uint32_t states, bits;
 };

@@ -1012,33 +1012,42 @@ GatherShape gather_set_shape(const DeviceGeom &dg, int mode, bool shared, uint32
   return g;
 }
 
-hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipStream_t stream)
+// the kernels of a launch shape; null with *why set where the shape cannot be launched (no grid, more LDS than a CU has) or names no table layout
+static const GatherKernel *gather_kernel_for(const GatherShape &shape, hipError_t *why)
 {
+  *why = hipErrorInvalidValue;
   if (shape.grid == 0 || shape.lds > 160 * 1024)
-    return hipErrorInvalidValue;
+    return nullptr;
   for (const GatherKernel &g : g_gather_kernels)
     if (g.mode == shape.mode && g.shared == shape.shared)
-    {
-      (void)hipGetLastError();
-      g.launch(gp, shape, stream);
-      return hipGetLastError();
-    }
-  return hipErrorNotSupported;
+      return &g;
+  *why = hipErrorNotSupported;
+  return nullptr;
+}
+
+hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipStream_t stream)
+{
+  hipError_t e;
+  const GatherKernel *g = gather_kernel_for(shape, &e);
+  if (g == nullptr)
+    return e;
+  (void)hipGetLastError();
+  g->launch(gp, shape, stream);
+  return hipGetLastError();
 }
 
 // hsrans_decode_device_gather_batch's launch of one kind: k_gather_set of the kind's table layout
 hipError_t launch_gather_set(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream)
 {
-  if (shape.grid == 0 || shape.lds > 160 * 1024 || sp.n_tasks == 0 || (uint64_t)shape.grid * shape.waves < sp.n_tasks || (sp.table_bytes & 15) != 0)
+  if (sp.n_tasks == 0 || (uint64_t)shape.grid * shape.waves < sp.n_tasks || (sp.table_bytes & 15) != 0)
     return hipErrorInvalidValue;
-  for (const GatherKernel &g : g_gather_kernels)
-    if (g.mode == shape.mode && g.shared == shape.shared)
-    {
-      (void)hipGetLastError();
-      g.launch_set(sp, shape, stream);
-      return hipGetLastError();
-    }
-  return hipErrorNotSupported;
+  hipError_t e;
+  const GatherKernel *g = gather_kernel_for(shape, &e);
+  if (g == nullptr)
+    return e;
+  (void)hipGetLastError();
+  g->launch_set(sp, shape, stream);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1059,25 +1068,24 @@ GatherShape gather_ranges_shape(const Tuning &tn, const PlanHeader &h, const Dev
 
 hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &cp, const GatherShape &shape, hipStream_t stream)
 {
-  if (shape.grid == 0 || shape.lds > 160 * 1024 || cp.segment == 0)
+  if (cp.segment == 0)
     return hipErrorInvalidValue;
+  hipError_t e;
+  const GatherKernel *g = gather_kernel_for(shape, &e);
+  if (g == nullptr)
+    return e;
   GatherRangesParams rp{};
   rp.ranges = cp.ranges;
   rp.workspace = cp.workspace;
   rp.segment = cp.segment;
   rp.segment_shift = (cp.segment & (cp.segment - 1)) == 0 ? (uint32_t)__builtin_ctzll(cp.segment) : 0; // (a segment of 1 byte divides as it is)
-  for (const GatherKernel &g : g_gather_kernels)
-    if (g.mode == shape.mode && g.shared == shape.shared)
-    {
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(k_gather_cut, dim3(1), dim3(1024), 0, stream, cp);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess)
-        return e;
-      g.launch_ranges(gp, rp, shape, stream);
-      return hipGetLastError();
-    }
-  return hipErrorNotSupported;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_gather_cut, dim3(1), dim3(1024), 0, stream, cp);
+  e = hipGetLastError();
+  if (e != hipSuccess)
+    return e;
+  g->launch_ranges(gp, rp, shape, stream);
+  return hipGetLastError();
 }
 
 } // namespace hsrans

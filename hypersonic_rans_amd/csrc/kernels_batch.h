@@ -58,6 +58,7 @@ __device__ __forceinline__ void run_batch_pair(const WaveCtx &c, const KParams &
   pair_bind<MODE>(ra, rb, c);
   if (check_hist && threadIdx.x < 64)
   {
+    // (check_hist_copy<false>, written out: the call moves two instructions of k_decode_batch_pair)
     bool same = HSRANS_HIST_IN_RANGE(c, pa.hist_off);
     if (same)
     {
@@ -125,19 +126,7 @@ __device__ __forceinline__ void run_batch_dual(const WaveCtx &c, const KParams &
     for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
       *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
     if (check_hist && threadIdx.x < 64)
-    {
-      bool same = HSRANS_HIST_IN_RANGE(c, pa.hist_off);
-      if (same)
-      {
-        const uint64_t mine = *(const uint64_t *)(pa.hist_copy + 4 * c.lane);
-        uint64_t theirs = 0;
-        for (int b = 3; b >= 0; b--)
-          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + pa.hist_off + 8 * c.lane + 2 * b);
-        same = mine == theirs;
-      }
-      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-        atomicOr(c.status, kStatusBadHist);
-    }
+      check_hist_copy<false>(c, pa.hist_copy, pa.hist_off);
   }
   if (ch >= end || ch >= pa.n_chains)
   {

@@ -537,6 +537,27 @@ __device__ __forceinline__ void pack64_from_marks(uint2 *tab, const uint16_t *cn
   }
 }
 
+// A host-built table was made from the plan's copy of the histogram (hist_copy): one whole wave — the caller picks it, the first of the
+// launch or of a member — checks that the stream really carries those counts at hist_off, four per lane, and raises the status where it
+// does not (as a failed sum check).  WINDOW: a window launch may lack the histogram (it lies below stream_lo): nothing to compare.
+// (hist_copy and hist_off by reference: a call site passes fields of its kernel parameters, and they are then loaded where the written-out
+// block loaded them — by value six decode kernels' instruction sequences change)
+template <bool WINDOW>
+__device__ __forceinline__ void check_hist_copy(const WaveCtx &c, const uint16_t *const &hist_copy, const uint64_t &hist_off)
+{
+  bool same = HSRANS_HIST_IN_RANGE(c, hist_off) || (WINDOW && hist_off + 512 <= c.stream_lo);
+  if (same && (!WINDOW || hist_off >= c.stream_lo))
+  {
+    const uint64_t mine = *(const uint64_t *)(hist_copy + 4 * c.lane);
+    uint64_t theirs = 0;
+    for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
+      theirs = (theirs << 16) | *(const uint16_t *)(c.stream + hist_off + 8 * c.lane + 2 * b);
+    same = mine == theirs;
+  }
+  if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
+    atomicOr(c.status, kStatusBadHist);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // decode table build (hist.cpp:291-306 make_dec_pack_hist, :356-384 inplace_make_hist_dec2, :308-324 the sum check)
 // `tid`/`nthreads` = the threads that share this table (one wave, or the whole workgroup); SYNC() orders their LDS traffic.

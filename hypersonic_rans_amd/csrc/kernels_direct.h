@@ -75,19 +75,7 @@ __device__ __forceinline__ void run_direct_span(const WaveCtx &c, const KParams 
         *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
     }
     if (check_hist && threadIdx.x < 64)
-    {
-      bool same = HSRANS_HIST_IN_RANGE(c, pa.hist_off) || pa.hist_off + 512 <= c.stream_lo; // (a window launch may lack the histogram: nothing to compare)
-      if (same && pa.hist_off >= c.stream_lo)
-      {
-        const uint64_t mine = *(const uint64_t *)(pa.hist_copy + 4 * c.lane);
-        uint64_t theirs = 0;
-        for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
-          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + pa.hist_off + 8 * c.lane + 2 * b);
-        same = mine == theirs;
-      }
-      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-        atomicOr(c.status, kStatusBadHist);
-    }
+      check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
     if (MODE != kModeSpill)
       __syncthreads();
     if (HSRANS_STAMPS(kp))
@@ -183,19 +171,7 @@ __device__ void run_direct_pair(const WaveCtx &c, const KParams &kp, uint32_t wa
     build_table<MODE, true>(c, pa.hist_off, threadIdx.x, blockDim.x);
   bool table_pending = host_table && MODE != kModeSpill;
   if (host_table && blockIdx.x == 0 && threadIdx.x < 64)
-  {
-    bool same = HSRANS_HIST_IN_RANGE(c, pa.hist_off) || pa.hist_off + 512 <= c.stream_lo; // (a window launch may lack the histogram: nothing to compare)
-    if (same && pa.hist_off >= c.stream_lo)
-    {
-      const uint64_t mine = *(const uint64_t *)(pa.hist_copy + 4 * c.lane);
-      uint64_t theirs = 0;
-      for (int b = 3; b >= 0; b--)
-        theirs = (theirs << 16) | *(const uint16_t *)(c.stream + pa.hist_off + 8 * c.lane + 2 * b);
-      same = mine == theirs;
-    }
-    if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-      atomicOr(c.status, kStatusBadHist);
-  }
+    check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
   auto copy_table = [&]() {
     const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
     for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)

@@ -1,10 +1,13 @@
-// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather, hsrans_decode_device_gather_indirect), and of many streams in one launch per table layout (hsrans_decode_device_gather_batch) — gather_groups, gather_tail, run_gather, k_gather, k_gather_cut, k_gather_ranges, k_gather_set.
+// kernels_gather.h — Random access: arbitrary byte ranges of one planned stream in one launch (hsrans_decode_device_gather, hsrans_decode_device_gather_indirect), and of many streams in one launch per table layout (hsrans_decode_device_gather_batch) — gather_groups, gather_tail, run_gather, gather_setup, k_gather, k_gather_cut, k_gather_ranges, k_gather_set.
 // Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the host-side launcher).
 //
 // One wavefront = one task (GatherTask: decoded bytes [begin, end) of the stream, destination = GatherParams::dst + byte + dst_delta).  The
 // wave finds the last chain that starts at or before `begin` (binary search over the chains' first output bytes), enters it at its
 // start states and decodes forward, chain after chain, until `end`: groups in front of `begin` are decoded and dropped, everything
 // else is stored clipped to the task, and nothing outside [begin, end) is ever written.
+// The three task kernels differ only in where a wave finds its task and its stream: each fills a GatherSource (from the launch's
+// parameters, or from a gather set's member record), calls the one gather_setup and then run_gather.  The rules of a range
+// (gather_range_ok, gather_range_tasks: hsrans_kernels.h) are the host entries' own functions, used by k_gather_cut as they stand.
 #ifndef HSRANS_KERNELS_GATHER_H
 #define HSRANS_KERNELS_GATHER_H
 
@@ -180,23 +183,25 @@ __device__ void run_gather(WaveCtx &c, const PlanView &pv, uint8_t *dst, uint64_
   }
 }
 
-// what k_gather and k_gather_ranges do before their first task: the wave's context and, in a SHARED launch, the workgroup's table
+// what every gather kernel does before its first task: the wave's context and, in a SHARED launch, the workgroup's table.  gs, bits and
+// states are wave-uniform, wave is the wave's number in its workgroup.  table_bytes: the table the LDS is laid out for (the plan's own;
+// in a launch over many plans their largest), for a table per wave a multiple of 16.
+// check_hist (SHARED; true in the workgroup's first wave at most, and gs.hist_copy / gs.hist_off are read there only): the wave checks
+// that the stream carries the histogram the table was built from.
+// A SHARED launch ends in a barrier: every wave of the workgroup comes here.
 template <int MODE, bool SHARED>
-__device__ __forceinline__ void gather_setup(WaveCtx &c, const PlanView &pv, const GatherParams &gp, uint8_t *smem)
+__device__ __forceinline__ void gather_setup(WaveCtx &c, const GatherSource &gs, uint32_t bits, uint32_t states, uint32_t wave, uint32_t table_bytes, bool check_hist, uint8_t *smem)
 {
   const uint32_t waves = blockDim.x >> 6;
-  const uint32_t wave = uni(threadIdx.x >> 6);
-  const uint32_t bits = pv.hdr->bits;
-  const uint32_t table_bytes = table_bytes_for(MODE, bits);
 
-  c.stream = gp.stream;
-  c.stream_len = gp.stream_len;
+  c.stream = gs.stream;
+  c.stream_len = gs.stream_len;
   c.stream_lo = 0;
-  c.out = gp.dst;
-  c.out_cap = 0; // (not used: every store of these kernels is tested against its task)
-  c.status = gp.status;
+  c.out = nullptr; // (run_gather sets it, task by task)
+  c.out_cap = 0;   // (not used: every store of these kernels is tested against its task)
+  c.status = gs.status;
   c.bits = bits;
-  c.S = pv.hdr->states;
+  c.S = states;
   c.lane = threadIdx.x & 63;
   asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
   asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
@@ -207,40 +212,36 @@ __device__ __forceinline__ void gather_setup(WaveCtx &c, const PlanView &pv, con
     c.rings = ring0 + wave * kWaveRingBytes;
     c.table = table_first_mode(MODE) ? smem : smem + waves * kWaveRingBytes;
     c.table_b = c.table;
-    c.gtable = gp.table;
+    c.gtable = gs.table;
     c.scratch_cnt = (uint16_t *)ring0;
     c.scratch_cum = (uint16_t *)(ring0 + 512);
-    // the host-built table: one coalesced 16-byte load + LDS store per thread (none for the table that stays in global memory), while the
-    // launch's first wave checks that the stream carries the histogram it was built from (run_persistent)
-    const uint32_t entries = table_bytes / 8;
+    // the host-built table: one coalesced 16-byte load + LDS store per thread (none for the table that stays in global memory)
+    const uint32_t entries = table_bytes_for(MODE, bits) / 8;
     for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(gp.table + i);
-    if (blockIdx.x == 0 && threadIdx.x < 64)
-    {
-      bool same = HSRANS_HIST_IN_RANGE(c, gp.hist_off);
-      if (same)
-      {
-        const uint64_t mine = *(const uint64_t *)(gp.hist_copy + 4 * c.lane);
-        uint64_t theirs = 0;
-        for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
-          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + gp.hist_off + 8 * c.lane + 2 * b);
-        same = mine == theirs;
-      }
-      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-        atomicOr(c.status, kStatusBadHist);
-    }
+      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(gs.table + i);
+    if (check_hist)
+      check_hist_copy<false>(c, gs.hist_copy, gs.hist_off);
     __syncthreads();
   }
   else
   {
-    const uint32_t table_stride = (table_bytes + 15) & ~15u;
     c.rings = smem + wave * kWaveRingBytes; // all rings first: they stay kRingBytes-aligned
-    c.table = smem + waves * kWaveRingBytes + wave * table_stride;
+    c.table = smem + waves * kWaveRingBytes + wave * table_bytes;
     c.table_b = c.table;
     c.gtable = nullptr;
     c.scratch_cnt = (uint16_t *)c.rings;
     c.scratch_cum = (uint16_t *)(c.rings + 512);
   }
+}
+
+// k_gather's and k_gather_ranges': one plan, whose header says bits and states; the launch's first workgroup checks the histogram
+template <int MODE, bool SHARED>
+__device__ __forceinline__ void gather_setup(WaveCtx &c, const PlanView &pv, const GatherParams &gp, uint8_t *smem)
+{
+  const uint32_t bits = pv.hdr->bits;
+  const GatherSource gs{gp.plan, gp.status, gp.stream, gp.stream_len, gp.table, gp.hist_copy, gp.hist_off};
+  const uint32_t table_bytes = table_bytes_for(MODE, bits);
+  gather_setup<MODE, SHARED>(c, gs, bits, pv.hdr->states, uni(threadIdx.x >> 6), SHARED ? table_bytes : (table_bytes + 15) & ~15u, blockIdx.x == 0 && threadIdx.x < 64, smem);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -265,8 +266,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_g
 // Workspace (uint32 words; GatherWs* in hsrans_kernels.h): [0] the task total, 0 where anything was refused; [1] the ranges in use;
 // from word kGatherWsFirst on first_task[0 .. n], the exclusive prefix of the ranges' task counts.
 // ---------------------------------------------------------------------------------------------------------------
-// One workgroup of 1024 threads, a range per thread and round.  The checks are the host entry's (hsrans_decode_device_gather), done
-// without a sum that can wrap; one range that fails them, a count above max_count or a total of 2^31 or more refuses the whole call:
+// One workgroup of 1024 threads, a range per thread and round.  The checks and the task count are the host entry's (gather_range_ok,
+// gather_range_tasks: hsrans_kernels.h); one range that fails them, a count above max_count or a total of 2^31 or more refuses the whole call:
 // the total is written as 0 and kStatusBadRange set.
 __global__ void __launch_bounds__(1024) k_gather_cut(GatherCutParams cp)
 {
@@ -289,11 +290,10 @@ __global__ void __launch_bounds__(1024) k_gather_cut(GatherCutParams cp)
     if (r < n)
     {
       const uint64_t offset = cp.ranges[r].offset, length = cp.ranges[r].length, dst_offset = cp.ranges[r].dst_offset;
-      if (offset > cp.decoded_len || length > cp.decoded_len - offset || dst_offset > cp.dst_capacity || length > cp.dst_capacity - dst_offset ||
-          (length != 0 && (offset < cp.out_lo || offset + length > cp.out_hi)))
+      if (!gather_range_ok(offset, length, dst_offset, cp.decoded_len, cp.out_lo, cp.out_hi, cp.dst_capacity))
         bad = true;
-      else if (length != 0)
-        tasks = (offset + length - 1) / cp.segment - offset / cp.segment + 1;
+      else
+        tasks = gather_range_tasks(offset, length, cp.segment);
       if (tasks >= (1ull << 31)) // (so that no sum below can wrap)
       {
         bad = true;
@@ -395,75 +395,34 @@ template <int MODE, bool SHARED>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(100))) k_gather_set(GatherSetParams sp)
 {
   extern __shared__ u32x4 smem_v[];
-  uint8_t *smem = (uint8_t *)smem_v;
   const uint32_t waves = blockDim.x >> 6;
-  const uint32_t wave = uni(threadIdx.x >> 6);
   const uint32_t first = blockIdx.x * waves; // (< n_tasks: the grid is sized from the entries)
+  const uint32_t wave = uni(threadIdx.x >> 6);
   const uint32_t entry = first + wave;
-  if (!SHARED && entry >= sp.n_tasks) // (SHARED: the entries fill whole workgroups, and every wave must reach the barrier)
+  if (!SHARED && entry >= sp.n_tasks) // (SHARED: the entries fill whole workgroups, and every wave must reach gather_setup's barrier)
     return;
   const GatherSetTask *task = sp.tasks + (SHARED && entry >= sp.n_tasks ? first : entry);
   const uint32_t member = uni(SHARED ? sp.tasks[first].member : task->member);
   const GatherSetMember *rec = sp.members + member;
-  const PlanView pv = plan_view((const uint8_t *)uni64((uint64_t)(uintptr_t)rec->plan));
-  const uint32_t bits = uni(rec->bits);
-
-  WaveCtx c;
-  c.stream = (const uint8_t *)uni64((uint64_t)(uintptr_t)rec->stream);
-  c.stream_len = uni64(rec->stream_len);
-  c.stream_lo = 0;
-  c.out = sp.dst;
-  c.out_cap = 0; // (not used: every store of these kernels is tested against its task)
-  c.status = (uint32_t *)uni64((uint64_t)(uintptr_t)rec->status);
-  c.bits = bits;
-  c.S = uni(rec->states);
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
-
+  GatherSource gs{};
+  gs.stream = (const uint8_t *)uni64((uint64_t)(uintptr_t)rec->src.stream);
+  gs.stream_len = uni64(rec->src.stream_len);
+  gs.plan = (const uint8_t *)uni64((uint64_t)(uintptr_t)rec->src.plan);
+  gs.status = (uint32_t *)uni64((uint64_t)(uintptr_t)rec->src.status);
+  // the first wave of the first workgroup of a member's run checks the histogram
+  const bool check_hist = SHARED && threadIdx.x < 64 && (first == 0 || uni(sp.tasks[first - 1].member) != member);
   if (SHARED)
+    gs.table = (const uint2 *)uni64((uint64_t)(uintptr_t)rec->src.table);
+  if (check_hist)
   {
-    const uint2 *table = (const uint2 *)uni64((uint64_t)(uintptr_t)rec->table);
-    uint8_t *ring0 = table_first_mode(MODE) ? smem + sp.table_bytes : smem;
-    c.rings = ring0 + wave * kWaveRingBytes;
-    c.table = table_first_mode(MODE) ? smem : smem + waves * kWaveRingBytes;
-    c.table_b = c.table;
-    c.gtable = table;
-    c.scratch_cnt = (uint16_t *)ring0;
-    c.scratch_cum = (uint16_t *)(ring0 + 512);
-    // the member's host-built table: one coalesced 16-byte load + LDS store per thread (gather_setup)
-    const uint32_t entries = table_bytes_for(MODE, bits) / 8;
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(table + i);
-    if (threadIdx.x < 64 && (first == 0 || uni(sp.tasks[first - 1].member) != member))
-    {
-      const uint64_t hist_off = uni64(rec->hist_off);
-      const uint16_t *hist_copy = (const uint16_t *)uni64((uint64_t)(uintptr_t)rec->hist_copy);
-      bool same = HSRANS_HIST_IN_RANGE(c, hist_off);
-      if (same)
-      {
-        const uint64_t mine = *(const uint64_t *)(hist_copy + 4 * c.lane);
-        uint64_t theirs = 0;
-        for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
-          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + hist_off + 8 * c.lane + 2 * b);
-        same = mine == theirs;
-      }
-      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-        atomicOr(c.status, kStatusBadHist);
-    }
-    __syncthreads();
-    if (entry >= sp.n_tasks)
-      return;
+    gs.hist_copy = (const uint16_t *)uni64((uint64_t)(uintptr_t)rec->src.hist_copy);
+    gs.hist_off = uni64(rec->src.hist_off);
   }
-  else
-  {
-    c.rings = smem + wave * kWaveRingBytes; // all rings first: they stay kRingBytes-aligned
-    c.table = smem + waves * kWaveRingBytes + wave * sp.table_bytes;
-    c.table_b = c.table;
-    c.gtable = nullptr;
-    c.scratch_cnt = (uint16_t *)c.rings;
-    c.scratch_cum = (uint16_t *)(c.rings + 512);
-  }
+  const PlanView pv = plan_view(gs.plan);
+  WaveCtx c;
+  gather_setup<MODE, SHARED>(c, gs, uni(rec->bits), uni(rec->states), wave, sp.table_bytes, check_hist, (uint8_t *)smem_v);
+  if (SHARED && entry >= sp.n_tasks)
+    return;
   run_gather<MODE, SHARED>(c, pv, sp.dst, uni64(task->begin), uni64(task->end), (int64_t)uni64((uint64_t)task->dst_delta));
 }
 

@@ -72,19 +72,7 @@ __device__ void run_persistent(const WaveCtx &c, const KParams &kp, uint32_t wav
     for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
       *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
     if (blockIdx.x == 0 && threadIdx.x < 64)
-    {
-      bool same = HSRANS_HIST_IN_RANGE(c, pa.hist_off) || pa.hist_off + 512 <= c.stream_lo; // (a window launch may lack the histogram: nothing to compare)
-      if (same && pa.hist_off >= c.stream_lo)
-      {
-        const uint64_t mine = *(const uint64_t *)(pa.hist_copy + 4 * c.lane);
-        uint64_t theirs = 0;
-        for (int b = 3; b >= 0; b--) // stream offsets are only 2-byte aligned
-          theirs = (theirs << 16) | *(const uint16_t *)(c.stream + pa.hist_off + 8 * c.lane + 2 * b);
-        same = mine == theirs;
-      }
-      if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-        atomicOr(c.status, kStatusBadHist);
-    }
+      check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
     __syncthreads();
   }
   if (HSRANS_STAMPS(kp))
@@ -206,19 +194,7 @@ __device__ void run_persistent_pair(const WaveCtx &c, const KParams &kp, uint32_
   };
 
   if (host_table && blockIdx.x == 0 && threadIdx.x < 64)
-  {
-    bool same = HSRANS_HIST_IN_RANGE(c, pa.hist_off) || pa.hist_off + 512 <= c.stream_lo; // (a window launch may lack the histogram: nothing to compare)
-    if (same && pa.hist_off >= c.stream_lo)
-    {
-      const uint64_t mine = *(const uint64_t *)(pa.hist_copy + 4 * c.lane);
-      uint64_t theirs = 0;
-      for (int b = 3; b >= 0; b--)
-        theirs = (theirs << 16) | *(const uint16_t *)(c.stream + pa.hist_off + 8 * c.lane + 2 * b);
-      same = mine == theirs;
-    }
-    if (__builtin_amdgcn_ballot_w64(!same) != 0 && c.lane == 0)
-      atomicOr(c.status, kStatusBadHist);
-  }
+    check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
   if (q0 != 0)
     run(c_first, c_first + q0, c_first + 2 * q0, host_table);
   else if (host_table)

@@ -242,3 +242,18 @@ def test_gathers_on_two_streams(gpu_ctx, datasets):
             want[int(dst):int(dst + length)] = data[int(off):int(off + length)]
         assert np.array_equal(d_dst.cpu().numpy(), want)
     assert gpu_ctx.status(dplan) == 0
+
+
+def test_altered_histogram_sets_the_status_and_the_plans_table_decodes(gpu_ctx):
+    """A stream that does not carry the histogram the plan's host-built table was made from (one count flipped in the device copy):
+    the first workgroup's first wave compares the stream's counts with the plan's copy and raises the status, reported once; the
+    workgroups decode with the plan's own table, which the stream's counts never enter, so the gathered bytes are still the input's."""
+    data = synth.enwik8_shaped(300_011, seed=21)
+    s, plan = _encode(gpu_ctx, "raw32", 64, 11, data)
+    dplan = gpu_ctx.make_device_plan(plan)
+    bad = _upload(s)
+    bad[int(H.api.plan_tables(plan)[2][0]["hist_off"]) + 40] ^= 0x5A  # one count of the histogram every piece of this plan decodes with
+    assert sum(gpu_ctx.make_gather_set([dplan], [bad], [s.size]).info()["kind_members"][3:]) == 1  # a kind with a host-built table
+    _gather_and_check(gpu_ctx, dplan, bad, s.size, data, [(1000, 4096), (150_001, 4096), (data.size - 4096, 4096)], "gaps", check_status=False)
+    assert gpu_ctx.status(dplan) != 0
+    assert gpu_ctx.status(dplan) == 0  # (reported once, then cleared)

@@ -3,13 +3,14 @@ the caller wants them, and nowhere else, in one launch per table layout.  Expect
 data[member][offset : offset + length].  Every gather writes into a buffer filled with 0xCC that has 4 KiB of canary in front of and
 behind the destination (and, in the 'gaps' layout, between the ranges); the WHOLE buffer is compared, so a byte written outside a range —
 or taken from the wrong member: every member holds other bytes — fails the case; every member's status must stay 0.
-(A corrupted histogram reaching the right member's status word is not tested here: tests/test_gpu_gather.py has no such case to follow.)"""
+A member whose stream does not carry its plan's histogram has its own tests at the end: that member's status says so, no other's."""
 import numpy as np
 import pytest
 import torch
 
 import hypersonic_rans_amd as H
 from hypersonic_rans_amd import synth
+from test_gpu_gather import _encode, _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -21,33 +22,6 @@ CANARY = 4096
 # (container, states, bits); the last one is a raw stream without an index: one chain
 MEMBERS = (("raw32", 64, 11), ("raw32", 64, 12), ("raw32", 32, 12), ("rawdev", 64, 14), ("raw32", 64, 15), ("mt", 64, 11), ("mt32", 64, 12), ("mt", 32, 14),
            ("block32", 64, 15), ("raw", 64, 11))
-
-
-def _upload(stream):
-    return torch.from_numpy(np.concatenate([stream, np.zeros((-stream.size) % 16, np.uint8)])).cuda()
-
-
-def _encode(ctx, kind, states, bits, data):
-    if kind == "raw32":
-        s, plan = H.encode(H.RAW, states, bits, data, index_interval=32)
-    elif kind == "rawdev":
-        s, plan = H.encode(H.RAW, states, bits, data, index_groups=H.index_boundaries(states, bits, data.size, ctx))
-    elif kind == "raw":
-        s = H.encode(H.RAW, states, bits, data)
-        plan = H.plan_build(H.RAW, states, bits, s)
-    elif kind == "mt":
-        s = H.encode(H.MT, states, bits, data, block_size=BLOCK)
-        plan = H.plan_build(H.MT, states, bits, s)
-    elif kind == "mt32":
-        s, plan = H.encode(H.MT, states, bits, data, block_size=BLOCK, index_interval=32)
-    elif kind == "block32":
-        s, plan = H.encode(H.BLOCK, states, bits, data, index_interval=32)
-    elif kind == "block":
-        s = H.encode(H.BLOCK, states, bits, data)
-        plan = H.plan_build(H.BLOCK, states, bits, s)
-    else:
-        raise AssertionError(kind)
-    return s, plan
 
 
 class _Set:
@@ -83,7 +57,7 @@ def ten(gpu_ctx):
     return _Set(gpu_ctx)
 
 
-def _layout(src, packing, base_align=0):
+def _layout(src, packing, base_align=0):  # (test_gpu_gather's has no member column)
     """(member, offset, length) triples -> (N, 4) rows (member, offset, length, dst_offset) and the buffer size.  packing: 'packed' = back to
     back behind the front canary (most destinations misaligned against their source); 'aligned' = every dst_offset congruent to its offset
     modulo 4 (gaps of < 4 bytes); 'gaps' = 4 KiB of canary between ranges."""
@@ -311,3 +285,51 @@ def test_two_sets_on_two_streams(gpu_ctx, ten):
         assert np.array_equal(d_dst.cpu().numpy(), _want(data, ranges, size))
     assert np.array_equal(d_single.cpu().numpy(), ten.data[0][100:50_100])
     assert gpu_ctx.gather_set_status(first) == [0] * len(MEMBERS) and gpu_ctx.gather_set_status(second) == [0] * len(order)
+
+
+def _first_hist_off(plan):
+    """where the stream keeps the counts the plan's first piece decodes with"""
+    return int(H.api.plan_tables(plan)[2][0]["hist_off"])
+
+
+def _altered_member(ctx, kind, states, bits, seed):
+    """(data, stream length, the good device copy of the stream, one with a count of its first histogram flipped, device plan)"""
+    data = synth.nonstationary(N, seed=seed).copy()
+    s, plan = _encode(ctx, kind, states, bits, data)
+    bad = _upload(s)
+    bad[_first_hist_off(plan) + 40] ^= 0x5A
+    return data, s.size, _upload(s), bad, ctx.make_device_plan(plan)
+
+
+def test_altered_histogram_reaches_its_members_status_only(gpu_ctx):
+    """three members with host-built tables, the middle one over a stream whose histogram is not its plan's: the first workgroup of that
+    member's run raises that member's status, reported once; the others' statuses stay 0 and every member's bytes are right"""
+    ms = [_altered_member(gpu_ctx, "raw32", 64, 11, 70 + k) for k in range(3)]
+    gset = gpu_ctx.make_gather_set([m[4] for m in ms], [ms[0][2], ms[1][3], ms[2][2]], [m[1] for m in ms])
+    assert sum(gset.info()["kind_members"][3:]) == 3
+    ranges, size = _layout([(0, 1000, 4096), (1, 150_001, 4096), (2, N - 4096, 4096)], "gaps")
+    d_dst = torch.full((size,), 0xCC, dtype=torch.uint8, device="cuda")
+    gpu_ctx.decode_device_gather_batch(gset, ranges, d_dst)
+    torch.cuda.synchronize()
+    codes = gpu_ctx.gather_set_status(gset)
+    assert codes[0] == 0 and codes[2] == 0 and codes[1] != 0, codes
+    # (member 1's workgroups decode with its plan's own table, which the stream's counts never enter: its bytes are the input's too)
+    assert np.array_equal(d_dst.cpu().numpy(), _want([m[0] for m in ms], ranges, size))
+    assert gpu_ctx.gather_set_status(gset) == [0, 0, 0]  # (reported once, then cleared, like hsrans_dplan_status)
+
+
+def test_altered_histogram_of_a_member_that_builds_its_table(gpu_ctx):
+    """a member whose waves build their table from the stream's counts (MEMBERS' mt_ 64 x 11): the altered count breaks the sum, the wave
+    raises the member's status and returns before it writes anything; the member beside it is untouched by that"""
+    good, other = _altered_member(gpu_ctx, "raw32", 64, 11, 80), _altered_member(gpu_ctx, "mt", 64, 11, 81)
+    gset = gpu_ctx.make_gather_set([good[4], other[4]], [good[2], other[3]], [good[1], other[1]])
+    info = gset.info()
+    assert sum(info["kind_members"][:3]) == 1 and sum(info["kind_members"][3:]) == 1, info
+    ranges, size = _layout([(0, 1000, 4096), (1, 1000, 4096)], "gaps")  # (member 1's range lies in its first block: the altered counts)
+    d_dst = torch.full((size,), 0xCC, dtype=torch.uint8, device="cuda")
+    gpu_ctx.decode_device_gather_batch(gset, ranges, d_dst)
+    torch.cuda.synchronize()
+    codes = gpu_ctx.gather_set_status(gset)
+    assert codes[0] == 0 and codes[1] != 0, codes
+    assert np.array_equal(d_dst.cpu().numpy(), _want([good[0]], ranges[:1], size))  # member 0's bytes, and 0xCC everywhere else
+    assert gpu_ctx.gather_set_status(gset) == [0, 0]

@@ -230,6 +230,14 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_gather_set_status.argtypes = [_vp, _vp, _vp, _vp]
     L.hsrans_gather_set_info.restype = _i
     L.hsrans_gather_set_info.argtypes = [_vp, _vp]
+    L.hsrans_gather_batch_workspace_bytes.restype = _sz
+    L.hsrans_gather_batch_workspace_bytes.argtypes = [_u32, _u32]
+    L.hsrans_decode_device_gather_batch_indirect.restype = _i
+    L.hsrans_decode_device_gather_batch_indirect.argtypes = [_vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
+    L.hsrans_gather_set_refused.restype = _i
+    L.hsrans_gather_set_refused.argtypes = [_vp, _vp, _vp]
+    L.hsrans_gather_set_indirect_info.restype = _i
+    L.hsrans_gather_set_indirect_info.argtypes = [_vp, _u32, _sz, _vp]
     L.hsrans_gather_batch_tasks.restype = _sz
     L.hsrans_gather_batch_tasks.argtypes = [_vp, _u32, _vp, _u32, _u32, _u32, _vp, _sz]
     L.hsrans_gather_segment.restype = ctypes.c_uint64
@@ -615,6 +623,12 @@ def gather_workspace_bytes(max_count: int) -> int:
     return int(load_library().hsrans_gather_workspace_bytes(max_count))
 
 
+def gather_batch_workspace_bytes(members: int, max_count: int) -> int:
+    """hsrans_gather_batch_workspace_bytes: the device workspace a decode_device_gather_batch_indirect of up to ``max_count`` ranges on a
+    gather set of ``members`` members needs; 0 for members == 0 or above 65,536."""
+    return int(load_library().hsrans_gather_batch_workspace_bytes(members, max_count))
+
+
 def gather_tasks(decoded_len: int, n_chains: int, states: int, interval: int, ranges, capacity: int | None = None) -> np.ndarray:
     """hsrans_gather_tasks: the one-wave tasks ``ranges`` ((N, 3) uint64 or a list of (offset, length, dst_offset)) are cut into, as an
     (M, 3) array of (begin, end, dst_delta) (dst_delta as uint64, modulo 2^64).  Pure host arithmetic; an empty array for invalid input.
@@ -714,6 +728,16 @@ class GatherSet:
         """members, members per kind, and of the last gather: launches and per kind tasks, entries (tasks + padding), grid, waves, LDS bytes"""
         info = GatherSetInfo()
         load_library().hsrans_gather_set_info(self.handle, ctypes.byref(info))
+        return {n: (list(getattr(info, n)) if n.startswith("kind_") else getattr(info, n)) for n, _ in GatherSetInfo._fields_}
+
+    def indirect_info(self, max_count: int, dst_capacity: int) -> dict:
+        """hsrans_gather_set_indirect_info: what a decode_device_gather_batch_indirect of up to ``max_count`` ranges into ``dst_capacity``
+        bytes will launch — members, members per kind, the launches behind the cut and per kind grid, waves and LDS bytes (tasks and
+        entries are 0: only the device knows them).  Pure host arithmetic."""
+        info = GatherSetInfo()
+        rc = load_library().hsrans_gather_set_indirect_info(self.handle, max_count, dst_capacity, ctypes.byref(info))
+        if rc != 0:
+            raise HsransError(f"hsrans_gather_set_indirect_info failed with code {rc}")
         return {n: (list(getattr(info, n)) if n.startswith("kind_") else getattr(info, n)) for n, _ in GatherSetInfo._fields_}
 
     def close(self):
@@ -1116,6 +1140,45 @@ class Context:
             err = HsransError(f"hsrans_decode_device_gather_batch failed with code {rc}")
             err.code = rc
             raise err
+
+    def decode_device_gather_batch_indirect(self, gset: GatherSet, d_ranges: torch.Tensor, d_dst: torch.Tensor, count: torch.Tensor | None = None,
+                                            max_count: int | None = None, workspace: torch.Tensor | None = None,
+                                            stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """decode_device_gather_batch for ranges that are on the GPU (hsrans_decode_device_gather_batch_indirect): ``d_ranges`` is a
+        contiguous CUDA tensor (N, 4) of int64 / uint64 rows (offset, length, dst_offset, member) — the memory layout of
+        hsrans_member_range: ``member`` is the low 32 bits of the fourth column, the high 32 bits are ``reserved`` and must be 0 —
+        ``count`` a CUDA int32 / uint32 scalar tensor with the number of rows in use (None: ``max_count``, itself N when None).  Both are
+        read when the launches run, not here: nothing is copied to the host, nothing is waited for, and the call can be captured into a
+        graph.  ``workspace``: a CUDA uint8 tensor of at least gather_batch_workspace_bytes(members, max_count) bytes that no other call in
+        flight uses; allocated here when None.  Returns the workspace.  Raises HsransError (``.code``) for what the host can check; a row or
+        count only the device can refuse leaves ``d_dst`` untouched and is reported by ``gather_set_refused(gset)`` (5)."""
+        s = stream if stream is not None else torch.cuda.current_stream(d_dst.device)
+        if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == 4 and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
+            raise TypeError("d_ranges: a contiguous CUDA tensor (N, 4) of int64 or uint64")
+        if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
+            raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
+        if max_count is None:
+            max_count = d_ranges.shape[0]
+        if max_count > d_ranges.shape[0]:
+            raise ValueError("max_count is larger than d_ranges")
+        if workspace is None:
+            with torch.cuda.stream(s):
+                workspace = torch.empty(gather_batch_workspace_bytes(len(gset.dplans), max_count), dtype=torch.uint8, device=d_dst.device)
+        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace: a contiguous CUDA uint8 tensor")
+        rc = self.L.hsrans_decode_device_gather_batch_indirect(self.handle, gset.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
+                                                               d_dst.data_ptr(), d_dst.numel(), workspace.data_ptr(), workspace.numel(), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_gather_batch_indirect failed with code {rc}")
+            err.code = rc
+            raise err
+        return workspace
+
+    def gather_set_refused(self, gset: GatherSet, stream: torch.cuda.Stream | None = None) -> int:
+        """hsrans_gather_set_refused: synchronises ``stream`` and returns 5 once where a decode_device_gather_batch_indirect on the set was
+        refused on the device since the last look, else 0"""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return int(self.L.hsrans_gather_set_refused(self.handle, gset.handle, ctypes.c_void_p(s.cuda_stream)))
 
     def gather_set_status(self, gset: GatherSet, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_gather_set_status: synchronises ``stream`` and returns every member's status (0, or 5: its kernel found a malformed histogram)"""

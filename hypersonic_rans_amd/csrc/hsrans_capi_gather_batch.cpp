@@ -4,6 +4,9 @@
 // launch_gather_set in hsrans_kernels.hip).  The task lists go through the context's task buffer as hsrans_decode_device_gather's do
 // (gather_region_*, hsrans_capi_gather.cpp); range rules, plan test, the member's GatherSource and the cut of a range are the single
 // call's own functions (hsrans_kernels.h, hsrans_internal.h).
+// hsrans_decode_device_gather_batch_indirect: the same for ranges that are in device memory — no cut, no task buffer and no lock here: the
+// device checks, sorts and cuts (k_set_cut, then one k_set_ranges per kind that has members, through launch_gather_set_ranges), the caller
+// brings the workspace, and what the device refuses lands in a status word of the set's own (hsrans_gather_set_refused).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -20,11 +23,11 @@ using namespace hsrans;
 
 #include "hsrans_internal.h"
 
-static_assert(sizeof(hsrans_member_range) == 32 && sizeof(hsrans_gather_batch_task) == 32 && sizeof(hsrans_gather_member) == 24 &&
+static_assert(sizeof(GatherSetRange) == sizeof(hsrans_member_range) && sizeof(hsrans_member_range) == 32 && sizeof(hsrans_gather_batch_task) == 32 && sizeof(hsrans_gather_member) == 24 &&
                   sizeof(GatherSetTask) == sizeof(hsrans_gather_batch_task),
               "gather batch ABI layout");
 
-constexpr uint32_t kGatherKinds = 6;        // k_gather_set's instantiations: kind = decode-table layout (kMode*), 3..5 with one table per workgroup
+// (kGatherKinds, hsrans_kernels.h: k_gather_set's instantiations — kind = decode-table layout (kMode*), 3..5 with one table per workgroup)
 constexpr uint32_t kGatherSetMaxMembers = 65536;
 
 struct hsrans_gather_set
@@ -37,6 +40,11 @@ struct hsrans_gather_set
   GatherSetMember *d_members = nullptr;
   uint32_t kind_members[kGatherKinds] = {};
   uint32_t kind_table_bytes[kGatherKinds] = {}; // the largest table among the kind's members, a multiple of 16
+  // hsrans_decode_device_gather_batch_indirect: a member's position is its place in kind-major order (members sorted by kind, then index)
+  uint32_t *d_position = nullptr;               // [members] the position of member m
+  uint32_t *d_refused = nullptr;                // the set's own status word (kStatusBadRange: k_set_cut refused a call); no member plan's word is involved
+  uint32_t kind_first[kGatherKinds + 1] = {};   // the first position of each kind ([6] = members)
+  uint64_t kind_min_segment[kGatherKinds] = {}; // the smallest segment among the kind's members that can be cut (0: none can)
   hsrans_gather_set_info_t last{};              // the last call's part of hsrans_gather_set_info (under ctx->lock)
 };
 
@@ -173,10 +181,26 @@ int hsrans_gather_set_create(hsrans_ctx *ctx, hsrans_dplan *const *dplans, const
     rec.out_hi = d->out_hi;
     rec.states = h.states;
     rec.bits = h.bits;
+    if (set->segment[k] != 0 && (set->kind_min_segment[kind] == 0 || set->segment[k] < set->kind_min_segment[kind]))
+      set->kind_min_segment[kind] = set->segment[k];
+  }
+  // positions: kind-major, inside a kind by member index
+  std::vector<uint32_t> position(count, 0);
+  for (uint32_t kind = 0; kind < kGatherKinds; kind++)
+    set->kind_first[kind + 1] = set->kind_first[kind] + set->kind_members[kind];
+  {
+    uint32_t next[kGatherKinds];
+    for (uint32_t kind = 0; kind < kGatherKinds; kind++)
+      next[kind] = set->kind_first[kind];
+    for (uint32_t k = 0; k < count; k++)
+      position[k] = next[set->members[k].kind]++;
   }
   // the records go up once, here (a synchronous copy: they are in place when the call returns)
   if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&set->d_members, count * sizeof(GatherSetMember)) != hipSuccess ||
-      hipMemcpy(set->d_members, recs.data(), count * sizeof(GatherSetMember), hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy(set->d_members, recs.data(), count * sizeof(GatherSetMember), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMalloc((void **)&set->d_position, (size_t)count * sizeof(uint32_t)) != hipSuccess ||
+      hipMemcpy(set->d_position, position.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMalloc((void **)&set->d_refused, sizeof(uint32_t)) != hipSuccess || hipMemset(set->d_refused, 0, sizeof(uint32_t)) != hipSuccess)
   {
     (void)hipGetLastError();
     hsrans_gather_set_destroy(set);
@@ -193,6 +217,10 @@ void hsrans_gather_set_destroy(hsrans_gather_set *set)
     return;
   if (set->d_members != nullptr)
     (void)hipFree(set->d_members);
+  if (set->d_position != nullptr)
+    (void)hipFree(set->d_position);
+  if (set->d_refused != nullptr)
+    (void)hipFree(set->d_refused);
   delete set;
 }
 
@@ -321,6 +349,98 @@ int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, c
       return rc_commit;
   }
   return failed ? HSRANS_E_HIP : HSRANS_OK;
+}
+
+// the launches of an indirect call on the set: one shape per kind that has members (grid 0 elsewhere), from what the host knows
+static void indirect_shapes(const hsrans_gather_set *set, uint32_t max_count, size_t dst_capacity, GatherShape shapes[kGatherKinds])
+{
+  for (uint32_t k = 0; k < kGatherKinds; k++)
+  {
+    shapes[k] = GatherShape{};
+    if (set->kind_members[k] != 0)
+      shapes[k] = gather_set_ranges_shape(set->ctx->geom, (int)k, k >= 3, set->kind_table_bytes[k], max_count, dst_capacity, set->kind_min_segment[k], set->kind_members[k]);
+  }
+}
+
+size_t hsrans_gather_batch_workspace_bytes(uint32_t members, uint32_t max_count)
+{
+  if (members == 0 || members > kGatherSetMaxMembers)
+    return 0;
+  return (size_t)gather_set_ws(members, max_count).words * 4;
+}
+
+int hsrans_gather_set_indirect_info(const hsrans_gather_set *set, uint32_t max_count, size_t dst_capacity, hsrans_gather_set_info_t *info)
+{
+  if (set == nullptr || info == nullptr)
+    return HSRANS_E_ARG;
+  *info = hsrans_gather_set_info_t{};
+  info->members = (uint32_t)set->members.size();
+  GatherShape shapes[kGatherKinds];
+  indirect_shapes(set, max_count, dst_capacity, shapes);
+  for (uint32_t k = 0; k < kGatherKinds; k++)
+  {
+    info->kind_members[k] = set->kind_members[k];
+    if (set->kind_members[k] == 0 || max_count == 0)
+      continue;
+    info->launches++;
+    info->kind_grid[k] = shapes[k].grid;
+    info->kind_waves[k] = shapes[k].waves;
+    info->kind_lds_bytes[k] = shapes[k].lds;
+  }
+  return HSRANS_OK;
+}
+
+int hsrans_decode_device_gather_batch_indirect(hsrans_ctx *ctx, hsrans_gather_set *set, const hsrans_member_range *d_ranges, const uint32_t *d_count, uint32_t max_count, void *d_dst,
+                                               size_t dst_capacity, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+  if (ctx == nullptr || set == nullptr || d_ranges == nullptr || d_dst == nullptr || d_workspace == nullptr || set->ctx != ctx)
+    return HSRANS_E_ARG;
+  const uint32_t n_members = (uint32_t)set->members.size();
+  if (((uintptr_t)d_ranges & 7) != 0 || ((uintptr_t)d_count & 3) != 0 || ((uintptr_t)d_workspace & 255) != 0 ||
+      workspace_bytes < hsrans_gather_batch_workspace_bytes(n_members, max_count))
+    return HSRANS_E_ARG;
+  if (max_count == 0)
+    return HSRANS_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return HSRANS_E_HIP;
+
+  GatherShape shapes[kGatherKinds];
+  indirect_shapes(set, max_count, dst_capacity, shapes);
+  GatherSetCutParams cp{};
+  cp.ranges = (const GatherSetRange *)d_ranges;
+  cp.count = d_count;
+  cp.max_count = max_count;
+  cp.n_members = n_members;
+  cp.members = set->d_members;
+  cp.position = set->d_position;
+  cp.dst_capacity = dst_capacity;
+  cp.workspace = (uint32_t *)d_workspace;
+  cp.status = set->d_refused;
+  for (uint32_t k = 0; k <= kGatherKinds; k++)
+    cp.kind_first[k] = set->kind_first[k];
+  for (uint32_t k = 0; k < kGatherKinds; k++)
+    cp.kind_waves[k] = shapes[k].waves;
+  if (launch_gather_set_ranges(cp, (uint8_t *)d_dst, shapes, set->kind_table_bytes, (hipStream_t)hip_stream) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  return HSRANS_OK;
+}
+
+int hsrans_gather_set_refused(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip_stream)
+{
+  if (ctx == nullptr || set == nullptr || set->ctx != ctx)
+    return HSRANS_E_ARG;
+  uint32_t status = 0xFFFFFFFF;
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (hipMemcpyAsync(&status, set->d_refused, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  if (status == 0)
+    return HSRANS_OK;
+  if (hipMemsetAsync(set->d_refused, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  return HSRANS_E_DEVICE;
 }
 
 int hsrans_gather_set_status(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip_stream, int *member_status)

@@ -497,7 +497,7 @@ hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &c
 struct GatherSetMember
 {
   GatherSource src;
-  uint64_t segment, decoded_len, out_lo, out_hi; // the member's task length L and what its ranges are checked against (the host's cut; no kernel reads them)
+  uint64_t segment, decoded_len, out_lo, out_hi; // the member's task length L and what its ranges are checked against (the host's cut, and k_set_cut / k_set_ranges)
   uint32_t states, bits;
 };
 static_assert(sizeof(GatherSetMember) == 96, "GatherSetMember layout");
@@ -523,6 +523,73 @@ uint32_t gather_table_bytes(int mode, uint32_t bits);
 GatherShape gather_set_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t n_tasks);
 // asynchronous on `stream`; one launch
 hipError_t launch_gather_set(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream);
+
+// ---- the same for ranges in device memory (hsrans_decode_device_gather_batch_indirect): k_set_cut, then k_set_ranges per kind ----
+struct GatherSetRange // == hsrans_member_range (include/hsrans_hip.h)
+{
+  uint64_t offset, length, dst_offset;
+  uint32_t member, reserved;
+};
+static_assert(sizeof(GatherSetRange) == 32, "GatherSetRange layout");
+constexpr uint32_t kGatherKinds = 6; // the table layouts (kMode*): 0..2 a table per wave, 3..5 one per workgroup
+// The workspace, in uint32 words: what k_set_cut leaves for the k_set_ranges launches.  A member's position is its place in kind-major
+// order (members sorted by kind, then member index), so every kind owns a run of positions, of perm slots, of tasks and of units.
+//   header     kSetWsTasks + k: tasks of kind k;  kSetWsUnits + k: units of kind k (3..5);  kSetWsSlot + k, k = 0..6: the first perm slot
+//              of kind k (6: all slots);  kSetWsCount: ranges in use.  Every total is 0 where the call was refused.
+//   slot_first [members + 1]    the perm slots in front of position p (while the ranges are counted: the ranges of p that have tasks)
+//   unit_first [members + 1]    the units in front of position p (while the ranges are counted: the tasks of p); a unit is `waves`
+//                               consecutive tasks of one member of a shared kind
+//   cursor     [members]        where the scatter stands in p's slots
+//   perm       [max_count]      the ranges that have tasks, by position
+//   first_task [max_count + 1]  the tasks in front of perm slot s, over all kinds
+constexpr uint32_t kSetWsTasks = 0, kSetWsUnits = 8, kSetWsSlot = 16, kSetWsCount = 24, kSetWsHeader = 64;
+struct GatherSetWs
+{
+  uint64_t slot_first, unit_first, cursor, perm, first_task, words; // word offsets into the workspace (each a multiple of 64: 256 bytes), and its size
+};
+__host__ __device__ inline GatherSetWs gather_set_ws(uint32_t members, uint32_t max_count)
+{
+  const uint64_t per_pos = ((uint64_t)members + 1 + 63) & ~(uint64_t)63, per_range = ((uint64_t)max_count + 1 + 63) & ~(uint64_t)63;
+  GatherSetWs w{};
+  w.slot_first = kSetWsHeader;
+  w.unit_first = w.slot_first + per_pos;
+  w.cursor = w.unit_first + per_pos;
+  w.perm = w.cursor + per_pos;
+  w.first_task = w.perm + per_range;
+  w.words = w.first_task + per_range;
+  return w;
+}
+struct GatherSetCutParams
+{
+  const GatherSetRange *ranges; // device, [max_count]
+  const uint32_t *count;        // device or null (= max_count)
+  uint32_t max_count, n_members;
+  const GatherSetMember *members; // device: a range is checked against its member's record and cut at its segment
+  const uint32_t *position;       // device, [n_members]: the member's position
+  uint64_t dst_capacity;
+  uint32_t *workspace;
+  uint32_t *status;                      // the set's own word
+  uint32_t kind_first[kGatherKinds + 1]; // the first position of kind k ([6] = n_members)
+  uint32_t kind_waves[kGatherKinds];     // waves per workgroup of kind k's launch (3..5: the length of a unit)
+};
+struct GatherSetRangesParams
+{
+  const GatherSetRange *ranges;
+  const uint32_t *workspace;
+  const GatherSetMember *members;
+  uint8_t *dst;
+  uint32_t max_count, n_members;
+  uint32_t kind, pos_lo, pos_hi; // the launch's kind and its positions [pos_lo, pos_hi)
+  uint32_t table_bytes;          // as GatherSetParams::table_bytes
+};
+// the launch shape of one kind for ranges only the device knows: layout, waves and LDS are gather_set_shape's for the most tasks the kind
+// can have — max_count + dst_capacity / min_segment (the kind's smallest member segment; 0: no member can have a task) have destinations
+// of their own, gather_ranges_shape's bound — the shared kinds add one unit of padding per member that can be named; the grid is capped at
+// the workgroups the device holds at once, and the kernels loop
+GatherShape gather_set_ranges_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t max_count, uint64_t dst_capacity, uint64_t min_segment,
+                                    uint32_t kind_members);
+// asynchronous on `stream`; one k_set_cut and one k_set_ranges per kind whose shape has a grid, nothing else (capturable)
+hipError_t launch_gather_set_ranges(const GatherSetCutParams &cp, uint8_t *dst, const GatherShape shapes[kGatherKinds], const uint32_t table_bytes[kGatherKinds], hipStream_t stream);
 
 DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
 LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f); // (reads persistent, table_mode, interval, dual, n_groups, index_pass)

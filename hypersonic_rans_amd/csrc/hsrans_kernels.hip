@@ -34,7 +34,7 @@
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
 //   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device
 //   kernels_gather.h    k_gather           byte ranges of one stream: one wave per task, entered at the chain that holds its first byte
-//                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks; k_gather_set   byte ranges of many streams: every task names its member, one launch per table layout
+//                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks; k_gather_set   byte ranges of many streams: every task names its member, one launch per table layout; k_set_cut, k_set_ranges   the same for ranges in device memory
 // This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -245,6 +245,8 @@ struct GatherKernel
   void (*launch_ranges)(const GatherParams &gp, const GatherRangesParams &rp, const GatherShape &shape, hipStream_t stream);
   const void *fn_set; // k_gather_set of the same table layout
   void (*launch_set)(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream);
+  const void *fn_set_ranges; // k_set_ranges of the same table layout
+  void (*launch_set_ranges)(const GatherSetRangesParams &rp, const GatherShape &shape, hipStream_t stream);
 };
 template <int MODE, bool SHARED>
 static GatherKernel gather_entry()
@@ -258,6 +260,10 @@ static GatherKernel gather_entry()
           (const void *)k_gather_set<MODE, SHARED>,
           [](const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream) {
             hipLaunchKernelGGL((k_gather_set<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, sp);
+          },
+          (const void *)k_set_ranges<MODE, SHARED>,
+          [](const GatherSetRangesParams &rp, const GatherShape &shape, hipStream_t stream) {
+            hipLaunchKernelGGL((k_set_ranges<MODE, SHARED>), dim3(shape.grid), dim3(shape.waves * 64), shape.lds, stream, rp);
           }};
 }
 static const GatherKernel g_gather_kernels[] = {gather_entry<kModePack, false>(),  gather_entry<kModePackM1, false>(), gather_entry<kModeTwoLevel, false>(),
@@ -282,6 +288,7 @@ hipError_t prepare_kernels(DeviceGeom *geom)
     fns.push_back(g.fn);
     fns.push_back(g.fn_ranges);
     fns.push_back(g.fn_set);
+    fns.push_back(g.fn_set_ranges);
   }
   for (const void *fn : fns)
   {
@@ -1086,6 +1093,60 @@ hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &c
     return e;
   g->launch_ranges(gp, rp, shape, stream);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_gather_batch_indirect's launches: gather_ranges_shape's reasoning, kind by kind.  A shared kind's workgroup serves
+// whole units (`waves` consecutive tasks of one member), so its grid is counted in units: those of the most tasks the kind can have and
+// one more per member that can be named, each member's last unit being partly empty.
+// ---------------------------------------------------------------------------------------------------------------
+GatherShape gather_set_ranges_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t max_count, uint64_t dst_capacity, uint64_t min_segment,
+                                    uint32_t kind_members)
+{
+  const uint64_t most = std::min<uint64_t>((uint64_t)max_count + (min_segment ? dst_capacity / min_segment : 0), 0x7FFFFFFFu);
+  GatherShape g = gather_set_shape(dg, mode, shared, table_bytes, (uint32_t)most);
+  const uint64_t padding = shared ? std::min(kind_members, max_count) : 0;
+  const uint32_t per_cu = std::max(1u, std::min(g.lds ? dg.max_lds / g.lds : 32u, 32u / g.waves));
+  g.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g.grid + padding, (uint64_t)dg.num_cus * per_cu));
+  return g;
+}
+
+hipError_t launch_gather_set_ranges(const GatherSetCutParams &cp, uint8_t *dst, const GatherShape shapes[kGatherKinds], const uint32_t table_bytes[kGatherKinds], hipStream_t stream)
+{
+  const GatherKernel *kernels[kGatherKinds] = {};
+  for (uint32_t k = 0; k < kGatherKinds; k++)
+  {
+    if (cp.kind_first[k] == cp.kind_first[k + 1])
+      continue;
+    hipError_t e;
+    kernels[k] = gather_kernel_for(shapes[k], &e);
+    if (kernels[k] == nullptr)
+      return e;
+    if (shapes[k].mode != (int)k || (table_bytes[k] & 15) != 0 || cp.kind_waves[k] != shapes[k].waves)
+      return hipErrorInvalidValue;
+  }
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_set_cut, dim3(1), dim3(1024), 0, stream, cp);
+  hipError_t e = hipGetLastError();
+  for (uint32_t k = 0; k < kGatherKinds && e == hipSuccess; k++)
+  {
+    if (kernels[k] == nullptr)
+      continue;
+    GatherSetRangesParams rp{};
+    rp.ranges = cp.ranges;
+    rp.workspace = cp.workspace;
+    rp.members = cp.members;
+    rp.dst = dst;
+    rp.max_count = cp.max_count;
+    rp.n_members = cp.n_members;
+    rp.kind = k;
+    rp.pos_lo = cp.kind_first[k];
+    rp.pos_hi = cp.kind_first[k + 1];
+    rp.table_bytes = table_bytes[k];
+    kernels[k]->launch_set_ranges(rp, shapes[k], stream);
+    e = hipGetLastError();
+  }
+  return e;
 }
 
 } // namespace hsrans

@@ -332,7 +332,48 @@ int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, c
                                       void *d_dst, size_t dst_capacity, void *hip_stream);
 int hsrans_gather_set_status(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip_stream, int *member_status /* [members] or NULL */);
 int hsrans_gather_set_info(const hsrans_gather_set *set, hsrans_gather_set_info_t *info);
-/* The host-side cut of that call, a pure function (no GPU): the task list of ONE kind's launch, in launch order — wave w
+/* ------------------------------------------------------------------------------------------------------------
+ * The same gather for ranges that are in DEVICE memory — a page-table lookup, a router, a sampler — with no host
+ * round trip: n = d_count ? *d_count : max_count, and for the rows d_ranges[0 .. n) the bytes written to d_dst are those
+ * hsrans_decode_device_gather_batch writes for the same rows in host memory (every member cut at its own segment
+ * length L; same alignment rules; overlapping destinations unspecified; no other byte of d_dst is written).
+ *   - asynchronous on hip_stream: kernel launches and nothing else — no allocation, no synchronisation, no lock, no
+ *     host read of device memory, no use of the context's task buffer; set->last is not written, so
+ *     hsrans_gather_set_info keeps describing the last host-ranges call.  The call can be captured into a graph.
+ *   - d_ranges and *d_count are read when the launches RUN: a replayed graph gathers whatever they hold then.  Rows of
+ *     d_ranges from n on are never read.
+ *   - launches: one cut launch (one workgroup: it checks the rows, sorts them by member and counts their tasks), then
+ *     one launch per kind that has MEMBERS, whatever the ranges: at most seven kernels in a line.  In the launches of
+ *     kinds 3..5 a workgroup serves whole units — `waves` consecutive tasks of one member — and reloads its table only
+ *     where the member changes.  The grids are sized from what the host knows: per kind no more tasks than
+ *     max_count + dst_capacity / (the kind's smallest member L) have destinations of their own; capped at the
+ *     workgroups the device holds at once, and the kernels loop, so any total finishes.  Pass the dst_capacity the
+ *     ranges can really address.
+ *   - d_workspace: hsrans_gather_batch_workspace_bytes(the set's members, max_count) bytes of device memory, 256-byte
+ *     aligned, contents irrelevant.  It belongs to one call in flight; calls with different workspaces on one set are
+ *     independent of each other whatever streams they are on.
+ * What only the device can see is checked there, all or nothing: *d_count > max_count, member >= the set's members,
+ * reserved != 0, a range beyond its member's decoded bytes (or outside what a sliced plan decodes), dst_offset + length
+ * beyond dst_capacity, any 64-bit overflow in these sums, a task total of 2^31 or more.  Then the call gathers NOTHING
+ * — not one byte of d_dst is written — and sets bit 8 of a status word the SET owns (no member plan's word is touched):
+ * hsrans_gather_set_refused synchronises hip_stream, returns HSRANS_E_DEVICE once and clears the word, else HSRANS_OK.
+ * A malformed histogram still reaches the status word of that member's plan only (hsrans_gather_set_status).
+ * Returns HSRANS_E_ARG, nothing queued: a null handle or pointer (d_count may be NULL), a set of another context,
+ *   d_ranges not 8-byte, d_count not 4-byte or d_workspace not 256-byte aligned, workspace_bytes too small;
+ * HSRANS_OK with nothing queued: max_count == 0.
+ * hsrans_gather_batch_workspace_bytes: a pure function; > 0 and a multiple of 256 for members in 1 .. 65,536 and every
+ *   max_count, non-decreasing in both; 0 for members == 0 or > 65,536.
+ * hsrans_gather_set_indirect_info: a pure function of the set, max_count and dst_capacity (no device call) — members
+ *   and kind_members, launches = the launches behind the cut, kind_grid / kind_waves / kind_lds_bytes = the shapes the
+ *   entry will use (it computes them through the same function); kind_tasks and kind_entries are 0: only the device
+ *   knows them. */
+size_t hsrans_gather_batch_workspace_bytes(uint32_t members, uint32_t max_count);
+int hsrans_decode_device_gather_batch_indirect(hsrans_ctx *ctx, hsrans_gather_set *set, const hsrans_member_range *d_ranges /* DEVICE, 8-byte aligned */,
+                                               const uint32_t *d_count /* DEVICE, or NULL = max_count */, uint32_t max_count, void *d_dst, size_t dst_capacity,
+                                               void *d_workspace /* DEVICE, 256-byte aligned */, size_t workspace_bytes, void *hip_stream);
+int hsrans_gather_set_refused(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip_stream);
+int hsrans_gather_set_indirect_info(const hsrans_gather_set *set, uint32_t max_count, size_t dst_capacity, hsrans_gather_set_info_t *info);
+/* The host-side cut of hsrans_decode_device_gather_batch, a pure function (no GPU): the task list of ONE kind's launch, in launch order — wave w
  * of workgroup b runs entry b * waves + w.  Every range is cut exactly as hsrans_gather_tasks cuts it for its member
  * (decoded_len, n_chains, states, interval), and the member's number stands beside each task.
  *   kinds 0..2 (a table per wave): the tasks of the ranges whose member is of `kind`, in range order.

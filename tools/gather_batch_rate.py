@@ -8,7 +8,13 @@ Per case one JSON line with
   batch_us         one decode_device_gather_batch call, measured the same way
   single_spread_us / batch_spread_us   the interquartile range of the repetitions: the run-to-run spread of each leg
   batch_over_single   the ratio of the medians;  launches: what the batch call queued
-Run on the GPU box: python tools/gather_batch_rate.py --out profiles/r12_gather_batch_rate.jsonl"""
+Run on the GPU box: python tools/gather_batch_rate.py --out profiles/r12_gather_batch_rate.jsonl
+--indirect: the same rows with three other legs — the host-ranges batch call (the yardstick), hsrans_decode_device_gather_batch_indirect
+with the ranges already in device memory, and that call captured once and replayed from a graph — rotated leg by leg within a repetition
+(the starting leg moves on by one every repetition).  Per case one JSON line with batch_us / indirect_us / graph_us (medians), the three
+*_spread_us (interquartile ranges), indirect_over_batch and graph_over_batch.  What the host-ranges leg pays and the others do not: the
+cut on the CPU and the upload of the task lists; what it is spared: the device-side cut and the table reloads of a workgroup that serves
+several members.  python tools/gather_batch_rate.py --indirect --out profiles/r13_gather_batch_indirect_rate.jsonl"""
 import argparse
 import json
 import os
@@ -28,6 +34,7 @@ ap.add_argument("--sets", type=int, default=4)
 ap.add_argument("--reps", type=int, default=24)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--out", default=None)
+ap.add_argument("--indirect", action="store_true")
 args = ap.parse_args()
 assert args.reps >= 20 and args.warmup >= 5
 ctx = H.Context(0)
@@ -106,6 +113,8 @@ def run_case(container, K, fraction, datas, lengths, plans, sets, gsets):
     torch.cuda.synchronize()
     check(0)
     assert ctx.gather_set_status(gsets[0]) == [0] * K
+    if args.indirect:
+        return run_indirect(container, K, fraction, ranges, pos, dsts, gsets, batch, check)
     t_single, t_batch = [], []
     for r in range(args.warmup + args.reps):
         q = r % args.sets
@@ -122,6 +131,56 @@ def run_case(container, K, fraction, datas, lengths, plans, sets, gsets):
            "single_min_us": round(min(t_single), 2), "batch_min_us": round(min(t_batch), 2)}
     rec["batch_over_single"] = round(rec["batch_us"] / rec["single_us"], 4)
     rec["batch_not_slower"] = bool(rec["batch_us"] <= rec["single_us"] + rec["single_spread_us"])
+    return rec
+
+
+def run_indirect(container, K, fraction, ranges, size, dsts, gsets, batch, check):
+    """the three legs of --indirect over the rows `ranges` (member, offset, length, dst_offset)"""
+    rows = np.stack([ranges[:, 1], ranges[:, 2], ranges[:, 3], ranges[:, 0]], axis=1).astype(np.int64)
+    d_rows = [torch.from_numpy(rows).cuda() for _ in range(args.sets)]
+    d_count = torch.tensor(len(rows), dtype=torch.int32, device="cuda")
+    workspaces = [torch.empty(H.gather_batch_workspace_bytes(K, len(rows)), dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
+
+    def indirect(q):
+        ctx.decode_device_gather_batch_indirect(gsets[q], d_rows[q], dsts[q], count=d_count, workspace=workspaces[q])
+
+    graphs = []
+    side = torch.cuda.Stream()
+    for q in range(args.sets):
+        g = torch.cuda.CUDAGraph()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                ctx.decode_device_gather_batch_indirect(gsets[q], d_rows[q], dsts[q], count=d_count, workspace=workspaces[q], stream=side)
+        graphs.append(g)
+    torch.cuda.synchronize()
+    for leg in (indirect, lambda q: graphs[q].replay()):
+        leg(0)
+        torch.cuda.synchronize()
+        check(0)
+    assert ctx.gather_set_status(gsets[0]) == [0] * K and ctx.gather_set_refused(gsets[0]) == 0
+    legs = (("batch", batch), ("indirect", indirect), ("graph", lambda q: graphs[q].replay()))
+    times = {name: [] for name, _ in legs}
+    for r in range(args.warmup + args.reps):
+        q = r % args.sets
+        for j in range(3):
+            name, fn = legs[(r + j) % 3]
+            t = timed(lambda: fn(q))
+            if r >= args.warmup:
+                times[name].append(t)
+    iqr = lambda t: float(np.percentile(t, 75) - np.percentile(t, 25))
+    batch(0)
+    torch.cuda.synchronize()
+    host, info = gsets[0].info(), gsets[0].indirect_info(len(rows), size)
+    rec = {"container": container, "streams": K, "stream_bytes": N, "fraction": fraction, "range_bytes": RANGE, "ranges": int(len(rows)),
+           "tasks": int(sum(host["kind_tasks"])), "launches": info["launches"], "grid": info["kind_grid"], "waves": info["kind_waves"], "reps": args.reps,
+           "sets": args.sets}
+    for name, _ in legs:
+        rec[name + "_us"] = round(float(np.median(times[name])), 2)
+        rec[name + "_spread_us"] = round(iqr(times[name]), 2)
+        rec[name + "_min_us"] = round(min(times[name]), 2)
+    rec["indirect_over_batch"] = round(rec["indirect_us"] / rec["batch_us"], 4)
+    rec["graph_over_batch"] = round(rec["graph_us"] / rec["batch_us"], 4)
     return rec
 
 

@@ -979,7 +979,7 @@ class Context:
         return r, out[:out_capacity]
 
     def host_index_chains(self) -> int:
-        """chains of the index decode_host keeps from its last plan-less call on an mt_/raw stream (0 = none)"""
+        """chains of the index decode_host keeps from its last plan-less call on an mt_, block_ or raw stream of >= 1 MiB (0 = none)"""
         return int(self.L.hsrans_ctx_host_index_chains(self.handle))
 
     def decode(self, container: int, states: int, bits: int, stream, plan=None) -> np.ndarray:
@@ -1001,7 +1001,9 @@ class Context:
 
     def make_device_plan_from_stream(self, container: int, states: int, bits: int, d_stream: torch.Tensor, stream_length: int,
                                      out_capacity: int, stream: torch.cuda.Stream | None = None) -> DevicePlan:
-        """mt_ only: the header chain is walked on the GPU (no host copy of the stream needed)."""
+        """A plan for a stream that only exists in device memory.  mt_: the header chain is walked on the GPU.  block_: the walk plan
+        (one wavefront follows the inline headers), made from the stream's first 16 + 4 * states bytes; :meth:`decode_device_indexing`
+        turns it into a plan with checkpoints.  Raw streams are refused (plan_build needs their header only)."""
         s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
         h = _vp()
         rc = self.L.hsrans_dplan_create_from_device_stream(self.handle, container, states, bits, d_stream.data_ptr(), stream_length, out_capacity,
@@ -1029,7 +1031,9 @@ class Context:
     def decode_device_indexing(self, dplan: DevicePlan, d_stream: torch.Tensor, d_out: torch.Tensor, index_interval: int,
                                stream: torch.cuda.Stream | None = None, stream_length: int | None = None) -> DevicePlan:
         """First decode of a stream without an index: fills ``d_out`` and returns the plan with a checkpoint every
-        ``index_interval`` groups for the later decodes (hsrans_decode_device_indexing; synchronises ``stream``)."""
+        ``index_interval`` groups for the later decodes (hsrans_decode_device_indexing; synchronises ``stream``).  ``dplan``: a raw or mt_
+        base plan, or a block_ stream's walk plan (``make_device_plan_from_stream(BLOCK, ...)`` or ``make_device_plan(plan_build(BLOCK, ...))``).
+        Raises HsransError; for a block_ stream with more than ``decoded_len / 4096 + 16`` blocks (code 3) ``d_out`` is complete all the same."""
         s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
         h = _vp()
         rc = self.L.hsrans_decode_device_indexing(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,

@@ -289,7 +289,9 @@ try
   // missing index once: the first call's decode records checkpoints (hsrans_decode_device_indexing) and the plan it leaves is kept
   // in the context; later calls on the same bytes launch it.  "The same bytes" is checked on ALL of them: the stream is uploaded
   // anyway, a wide kernel fingerprints it there, and the decode that ran beside it only counts when the fingerprint matches.
-  const bool cacheable = plan == nullptr && (container == HSRANS_MT || container == HSRANS_RAW) && in_length >= 16 && !ctx->tuning.host_index_cache_off;
+  // (block_ streams too: the one wavefront that walks their inline headers records them, and the indexed plan is assembled on the device behind it)
+  const bool cacheable = plan == nullptr && (container == HSRANS_MT || container == HSRANS_RAW || container == HSRANS_BLOCK) && in_length >= 16 &&
+                         !ctx->tuning.host_index_cache_off;
   const uint64_t codec_key = (uint64_t)container | ((uint64_t)states << 8) | ((uint64_t)bits << 16) | (1ull << 32);
   if (cacheable)
   {

@@ -59,6 +59,50 @@ static void add_interval_chains(PlanBuilder &pb, const PlanHeader &h, const uint
   }
 }
 
+// The chains of a block_ stream's plan with a checkpoint every `index_interval` groups, from what the walk that recorded them left: block b's
+// {header position, output offset, header word} in blocks[3b .. 3b+2], the states it was entered with in bstates[b * S ..], and the
+// checkpoints (slot = absolute group / interval).  One fill chain per single-symbol block, one chain per block start and per checkpoint
+// inside a coded block.  false: no plan (a tail behind a trailing single-symbol block).  k_walk_index_fill writes the same on the device.
+static bool walk_index_chains(PlanBuilder &pb, uint32_t S, uint64_t out_len, uint32_t index_interval, uint32_t n_blocks, const uint64_t *blocks,
+                              const uint32_t *bstates, const uint32_t *ck_states, const uint64_t *ck_words)
+{
+  const uint64_t whole_file = out_len / S; // whole groups of the file (block_rANS32x64_16w_decode.cpp:82-88)
+  const uint64_t tail = out_len - whole_file * S;
+  for (uint32_t b = 0; b < n_blocks; b++)
+  {
+    const uint64_t pos = blocks[3 * (size_t)b], at = blocks[3 * (size_t)b + 1], hdr = blocks[3 * (size_t)b + 2];
+    const bool last = b + 1 == n_blocks;
+    if (hdr >> 63)
+    {
+      Piece p{};
+      p.out_off = at;
+      p.hist_off = (hdr >> 54) & 0xFF;
+      p.fill_len = hdr & (((uint64_t)1 << 54) - 1);
+      p.flags = kPieceChainStart | kPieceFill;
+      pb.add_chain(p, nullptr);
+      if (last && at + p.fill_len < out_len) // a tail behind a single-symbol block has no histogram
+        return false;
+      continue;
+    }
+    const uint64_t g0 = at / S;
+    const uint64_t g1 = std::min<uint64_t>((at + hdr + S - 1) / S, whole_file); // the decoder stops at the last whole group
+    const uint64_t T = g1 > g0 ? g1 - g0 : 0;
+    for (uint64_t g = 0; g < T || g == 0; g += index_interval)
+    {
+      Piece p{};
+      p.hist_off = pos + 8;
+      p.out_off = at + g * S;
+      const uint64_t slot = (g0 + g) / index_interval;
+      p.words_off = g == 0 ? pos + 8 + 512 : ck_words[slot];
+      const uint64_t steps = T - g < index_interval ? T - g : index_interval;
+      p.steps = (uint32_t)steps;
+      p.tail = (uint16_t)(last && g + steps >= T ? tail : 0);
+      pb.add_chain(p, g == 0 ? &bstates[(size_t)b * S] : &ck_states[slot * S]);
+    }
+  }
+  return true;
+}
+
 static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint32_t bits, const uint8_t *in, size_t in_length, uint32_t index_interval,
                                const uint64_t *groups, size_t n_groups, uint8_t *plan_out, size_t plan_capacity)
 {
@@ -190,41 +234,7 @@ static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint3
       if (hipMemcpy(blocks.data(), d_walk_blocks, blocks.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
           hipMemcpy(bstates.data(), d_walk_states, bstates.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
         break;
-      const uint64_t whole_file = out_len / S; // whole groups of the file (block_rANS32x64_16w_decode.cpp:82-88)
-      const uint64_t tail = out_len - whole_file * S;
-      bool ok = true;
-      for (uint32_t b = 0; b < n_blocks && ok; b++)
-      {
-        const uint64_t pos = blocks[3 * (size_t)b], at = blocks[3 * (size_t)b + 1], hdr = blocks[3 * (size_t)b + 2];
-        const bool last = b + 1 == n_blocks;
-        if (hdr >> 63)
-        {
-          Piece p{};
-          p.out_off = at;
-          p.hist_off = (hdr >> 54) & 0xFF;
-          p.fill_len = hdr & (((uint64_t)1 << 54) - 1);
-          p.flags = kPieceChainStart | kPieceFill;
-          pb.add_chain(p, nullptr);
-          ok = !(last && at + p.fill_len < out_len); // a tail behind a single-symbol block has no histogram
-          continue;
-        }
-        const uint64_t g0 = at / S;
-        const uint64_t g1 = std::min<uint64_t>((at + hdr + S - 1) / S, whole_file); // the decoder stops at the last whole group
-        const uint64_t T = g1 > g0 ? g1 - g0 : 0;
-        for (uint64_t g = 0; g < T || g == 0; g += index_interval)
-        {
-          Piece p{};
-          p.hist_off = pos + 8;
-          p.out_off = at + g * S;
-          const uint64_t slot = (g0 + g) / index_interval;
-          p.words_off = g == 0 ? pos + 8 + 512 : ck_words[slot];
-          const uint64_t steps = T - g < index_interval ? T - g : index_interval;
-          p.steps = (uint32_t)steps;
-          p.tail = (uint16_t)(last && g + steps >= T ? tail : 0);
-          pb.add_chain(p, g == 0 ? &bstates[(size_t)b * S] : &ck_states[slot * S]);
-        }
-      }
-      if (!ok)
+      if (!walk_index_chains(pb, S, out_len, index_interval, n_blocks, blocks.data(), bstates.data(), ck_states.data(), ck_words.data()))
         break;
     }
     else if (groups != nullptr)
@@ -307,11 +317,152 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
   return 0;
 }
 
+// hsrans_decode_device_indexing for a block_ stream's walk plan (d: kPlanWalk, one chain, no checkpoints; the arguments are checked).  The one
+// wavefront that walks the inline headers decodes into the caller's d_out and records block headers, entry states and checkpoints; behind it,
+// on the same stream, k_walk_index_count / k_walk_index_fill write the indexed plan and its group list into the new plan's arena, which also
+// holds the walk's records.  A few result words come back; one synchronisation.  HSRANS_INDEX_ASSEMBLE_ON_HOST=1: the records come down and
+// walk_index_chains + hsrans_dplan_create make the same plan.
+static int decode_walk_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity,
+                                uint32_t index_interval, hipStream_t s, hsrans_dplan **indexed, bool have_lock)
+{
+  const PlanHeader &h = d->hdr;
+  const uint32_t S = h.states;
+  const uint64_t n_ck = h.decoded_len / S / index_interval + 2;
+  // room for blocks of >= 4 KiB on average, as hsrans_index_build has it; a stream with more gets no plan
+  const uint64_t max_blocks = h.decoded_len / 4096 + 16, max_chains = max_blocks + n_ck, max_groups = max_blocks + max_chains / kGroupPartChains + 16;
+  if (max_chains > 0xFFFFFFF0u)
+    return HSRANS_E_FORMAT;
+  std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer belongs to the context)
+  if (!have_lock)
+    guard.lock();
+  const size_t st_bytes = (size_t)n_ck * S * 4, wd_bytes = (size_t)n_ck * 8;
+  const size_t off_bytes = ((size_t)max_blocks * 8 + 15) / 16 * 16, blk_bytes = (size_t)max_blocks * 24, bst_bytes = (size_t)max_blocks * S * 4;
+  if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, st_bytes + wd_bytes))
+    return HSRANS_E_HIP;
+  hsrans_dplan *nd = dplan_new(ctx);
+  if (nd == nullptr)
+    return HSRANS_E_HIP;
+  DplanRegions r;
+  r.counters = true;
+  r.plan = (size_t)plan_size((uint32_t)max_chains, (uint32_t)max_chains, S, 0);
+  r.groups = (size_t)max_groups * sizeof(Group);
+  r.scratch = 256 + off_bytes + blk_bytes + bst_bytes; // result words and the walk's block count, chain and group offsets, the walk's records
+  r.zero = kZeroAll;
+  uint8_t *scratch = nullptr;
+  if (dplan_arena(nd, r, s, &scratch) != HSRANS_OK)
+  {
+    hsrans_dplan_destroy(nd);
+    return HSRANS_E_HIP;
+  }
+  uint64_t *d_result = (uint64_t *)scratch;
+  uint32_t *d_walk_count = (uint32_t *)(scratch + 128);
+  uint64_t *d_walk_blocks = (uint64_t *)(scratch + 256 + off_bytes);
+  uint32_t *d_walk_states = (uint32_t *)(scratch + 256 + off_bytes + blk_bytes);
+  KParams kp{};
+  kp.stream = (const uint8_t *)d_stream;
+  kp.stream_len = stream_length;
+  kp.out = (uint8_t *)d_out;
+  kp.out_cap = out_capacity;
+  kp.plan = d->d_plan;
+  kp.status = d->d_status;
+  kp.ckpt_states = (uint32_t *)ctx->d_enc_ck;
+  kp.ckpt_words = (uint64_t *)(ctx->d_enc_ck + st_bytes);
+  kp.ckpt_interval = index_interval;
+  kp.walk_blocks = d_walk_blocks;
+  kp.walk_states = d_walk_states;
+  kp.walk_count = d_walk_count;
+  kp.walk_max_blocks = (uint32_t)max_blocks;
+  uint32_t status = 0xFFFFFFFF;
+  auto fail = [&](int rc) { // (nothing queued here may still be running when the call returns, whatever failed)
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    hsrans_dplan_destroy(nd);
+    return rc;
+  };
+  // the walk set a status bit (a bad histogram / header): reported and cleared like hsrans_dplan_status does
+  auto device_error = [&] { return hipMemsetAsync(d->d_status, 0, 4, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? HSRANS_E_DEVICE : HSRANS_E_HIP; };
+  if (launch_decode(ctx->tuning, kp, h, ctx->geom, s, nullptr) != hipSuccess)
+    return fail(HSRANS_E_HIP);
+
+  if (ctx->tuning.index_assemble_on_host)
+  {
+    uint32_t n_blocks = 0;
+    if (!grow_pinned(&ctx->h_pin, &ctx->h_pin_cap, st_bytes + wd_bytes + blk_bytes + bst_bytes) ||
+        hipMemcpyAsync(&n_blocks, d_walk_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return fail(HSRANS_E_HIP);
+    if (status != 0)
+      return fail(device_error());
+    if (n_blocks == 0 || n_blocks > max_blocks)
+      return fail(HSRANS_E_FORMAT);
+    uint32_t *ck_states = (uint32_t *)ctx->h_pin, *bstates = (uint32_t *)(ctx->h_pin + st_bytes + wd_bytes + blk_bytes);
+    uint64_t *ck_words = (uint64_t *)(ctx->h_pin + st_bytes), *blocks = (uint64_t *)(ctx->h_pin + st_bytes + wd_bytes);
+    if (hipMemcpyAsync(ck_states, kp.ckpt_states, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(ck_words, kp.ckpt_words, wd_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(blocks, d_walk_blocks, (size_t)n_blocks * 24, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(bstates, d_walk_states, (size_t)n_blocks * S * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return fail(HSRANS_E_HIP);
+    hsrans_dplan_destroy(nd); // (it only lent its arena to the walk's records)
+    PlanBuilder pb;
+    pb.begin((int)h.container, (int)S, h.bits, h.decoded_len, h.stream_len);
+    pb.reserve((size_t)n_blocks + n_ck);
+    pb.hdr.interval = index_interval;
+    if (!walk_index_chains(pb, S, h.decoded_len, index_interval, n_blocks, blocks, bstates, ck_states, ck_words))
+      return HSRANS_E_FORMAT;
+    std::vector<uint8_t> plan(pb.serialized_size());
+    const size_t plan_bytes = pb.serialize(plan.data(), plan.size());
+    return plan_bytes == 0 ? HSRANS_E_FORMAT : hsrans_dplan_create(ctx, plan.data(), plan_bytes, indexed);
+  }
+
+  WalkIndexArgs wa{};
+  wa.base = d->d_plan;
+  wa.walk_count = d_walk_count;
+  wa.walk_blocks = d_walk_blocks;
+  wa.walk_states = d_walk_states;
+  wa.ck_states = kp.ckpt_states;
+  wa.ck_words = kp.ckpt_words;
+  wa.S = S;
+  wa.interval = index_interval;
+  wa.max_blocks = (uint32_t)max_blocks;
+  wa.max_chains = (uint32_t)max_chains;
+  wa.max_groups = (uint32_t)max_groups;
+  wa.parts_want = kGroupPartsPerCU * ctx->geom.num_cus;
+  wa.decoded_len = h.decoded_len;
+  wa.stream_len = h.stream_len;
+  wa.chain_off = (uint32_t *)(scratch + 256);
+  wa.group_off = wa.chain_off + max_blocks;
+  wa.result = d_result;
+  wa.plan = nd->d_plan;
+  wa.groups = (Group *)nd->d_groups;
+  uint64_t res[9] = {}; // WalkIndexArgs::result
+  if (launch_index_assemble_walk(wa, s) != hipSuccess || hipMemcpyAsync(res, d_result, sizeof(res), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return fail(HSRANS_E_HIP);
+  if (status != 0)
+    return fail(device_error());
+  if (res[6] != 0 || res[0] == 0 || res[0] > max_chains || res[5] > max_groups) // the block list overflowed, a tail behind a single-symbol block, no room
+    return fail(HSRANS_E_FORMAT);
+  PlanHeader hn = h;
+  hn.flags = 0;
+  hn.n_chains = hn.n_pieces = (uint32_t)res[0];
+  hn.interval = index_interval;
+  hn.shared_hist = res[1] == 1 ? 1 : 0;
+  hn.aux_off = hn.shared_hist ? res[2] : 0;
+  dplan_adopt(nd, hn, res[8] != 0 ? (uint32_t)res[5] : 0, res[3], s);
+  if (ctx->tuning.indexing_trace)
+    fprintf(stderr, "hsrans_decode_device_indexing: block_ on the device: %llu blocks, %llu chains, %llu groups, %zu plan bytes\n", (unsigned long long)res[4],
+            (unsigned long long)res[0], (unsigned long long)res[5], nd->plan_bytes);
+  *indexed = nd;
+  return HSRANS_OK;
+}
+
 // The first decode of a stream that came without an index (a reference-emitted mt_ stream planned by hsrans_plan_build or on the
 // device by hsrans_dplan_create_from_device_stream: one chain per block, most wave slots empty) also RECORDS the coder states and
 // the read cursor every `index_interval` groups — two stores per checkpoint on a pass that is latency-bound anyway — and returns
 // the plan with those checkpoints for every later decode of the same stream.  The stream never leaves device memory; the plan
-// blob (chain table, a few MB) is assembled on the host as in hsrans_index_build, whose result it equals byte for byte.
+// blob (chain table, a few MB) equals hsrans_index_build's byte for byte: mt_ and block_ plans are assembled on the device behind the pass,
+// raw plans on the host.  A block_ stream comes with its walk plan (hsrans_plan_build, or hsrans_dplan_create_from_device_stream from the
+// stream's head): decode_walk_indexing.
 int hsrans_decode_device_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity,
                                   uint32_t index_interval, void *hip_stream, hsrans_dplan **indexed)
 {
@@ -329,14 +480,17 @@ try
   if (((uintptr_t)d_stream & 15) != 0 || ((uintptr_t)d_out & 3) != 0 || index_interval == 0 || (index_interval % 4) != 0)
     return HSRANS_E_ARG;
   const PlanHeader &h = d->hdr;
-  // base plans only: one single-piece chain per block (raw: one chain), no inline-header walk (block_ streams: hsrans_index_build)
-  if ((h.flags & kPlanWalk) || h.n_pieces != h.n_chains || h.interval != 0 || d->d_plan == nullptr || d->plan_bytes == 0)
+  // base plans only: one single-piece chain per block (raw: one chain), or a block_ stream's walk plan (one chain that follows the inline headers)
+  const bool walk = (h.flags & kPlanWalk) != 0;
+  if (h.n_pieces != h.n_chains || h.interval != 0 || d->d_plan == nullptr || d->plan_bytes == 0 || (walk && (h.container != HSRANS_BLOCK || h.n_chains != 1)))
     return HSRANS_E_ARG;
   if (stream_length < h.stream_len || out_capacity < h.decoded_len)
     return HSRANS_E_FORMAT;
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
+  if (walk)
+    return decode_walk_indexing(ctx, d, d_stream, stream_length, d_out, out_capacity, index_interval, s, indexed, have_lock);
   const bool trace = ctx->tuning.indexing_trace;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

@@ -527,11 +527,31 @@ int hsrans_dplan_create_from_device_stream(hsrans_ctx *ctx, int container, int s
   if (ctx == nullptr || out_dplan == nullptr || d_stream == nullptr)
     return HSRANS_E_ARG;
   *out_dplan = nullptr;
-  if (container != HSRANS_MT || !valid_codec(container, states, bits) || ((uintptr_t)d_stream & 15) != 0)
+  if ((container != HSRANS_MT && container != HSRANS_BLOCK) || !valid_codec(container, states, bits) || ((uintptr_t)d_stream & 15) != 0)
     return HSRANS_E_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
+  if (container == HSRANS_BLOCK)
+  try
+  {
+    // a block_ stream's inline headers are only found by decoding: its plan is the walk plan, and the host planner makes that from the
+    // stream's head alone — the two lengths and the start states, 16 + 4 * states bytes — with the checks hsrans_plan_build makes
+    const size_t head_bytes = 16 + 4 * (size_t)states;
+    if (stream_length < head_bytes)
+      return HSRANS_E_FORMAT;
+    uint8_t head[16 + 4 * 64];
+    if (hipMemcpyAsync(head, d_stream, head_bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return HSRANS_E_HIP;
+    std::vector<uint8_t> plan;
+    if (!plan_build_vec(container, states, bits, head, stream_length, out_capacity, &plan)) // (reads no byte behind the head of a block_ stream)
+      return HSRANS_E_FORMAT;
+    return hsrans_dplan_create(ctx, plan.data(), plan.size(), out_dplan);
+  }
+  catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+  {
+    return HSRANS_E_HIP;
+  }
   WalkResult *d_res = nullptr;
   uint64_t *d_blocks = nullptr;
   WalkResult res{};

@@ -160,8 +160,7 @@ PlanHeader mt_plan_header(uint32_t states, uint32_t bits, uint64_t decoded_len, 
 // each is cut into up to this many parts of >= kGroupPartChains chains (hsrans_kernels.h group_parts_of: the rule and what was measured); 1 = no cut
 inline uint32_t group_parts_max(const DeviceGeom &geom, size_t n_groups)
 {
-  const size_t want = (size_t)kGroupPartsPerCU * geom.num_cus;
-  return n_groups != 0 && n_groups < want ? (uint32_t)((want + n_groups - 1) / n_groups) : 1;
+  return group_parts_max_of((uint64_t)kGroupPartsPerCU * geom.num_cus, n_groups);
 }
 
 constexpr size_t kStampWaves = 16384;

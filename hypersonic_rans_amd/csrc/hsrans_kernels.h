@@ -362,6 +362,11 @@ __host__ __device__ inline uint32_t group_parts_of(uint32_t chains, uint32_t k_m
   const uint32_t k = by_size < k_max ? by_size : k_max;
   return k < 1 ? 1 : k;
 }
+// ... and the most parts a group is cut into in a plan of n_groups groups on a device that wants `want` of them (kGroupPartsPerCU per CU); 1 = no cut
+__host__ __device__ inline uint32_t group_parts_max_of(uint64_t want, uint64_t n_groups)
+{
+  return n_groups != 0 && n_groups < want ? (uint32_t)((want + n_groups - 1) / n_groups) : 1;
+}
 
 // k_decode_spread (kernels_spread.h): G = two 16-wave workgroups per CU; workgroup b's share of the plan's N chains starts at
 // spread_share_begin(b): the first half of the grid weighs w1 per workgroup, the second half w2 (the sums of their waves' age-class
@@ -392,6 +397,30 @@ struct IndexArgs
   uint64_t stream_len;
 };
 hipError_t launch_index_assemble(const IndexArgs &a, hipStream_t stream);
+// The same for a block_ stream, from what the recording walk left (KParams::walk_*): the plan hsrans_index_build(HSRANS_BLOCK) makes
+// and the group list dplan_fill derives from it.  The block count is only known on the device: every buffer is sized by the host's bounds.
+struct WalkIndexArgs
+{
+  const uint8_t *base;         // the walk plan's blob (device): container, states, bits and lengths come from its header
+  const uint32_t *walk_count;  // blocks recorded; max_blocks + 1: the list overflowed
+  const uint64_t *walk_blocks; // [3b .. 3b+2] = {header position, output offset, header word}
+  const uint32_t *walk_states; // [b * S]: coder states on entry to block b
+  const uint32_t *ck_states;   // as IndexArgs
+  const uint64_t *ck_words;
+  uint32_t S, interval;
+  uint32_t max_blocks, max_chains, max_groups; // what walk_blocks, the plan blob and `groups` have room for
+  uint32_t parts_want;         // kGroupPartsPerCU x CUs (group_parts_max_of)
+  uint64_t decoded_len, stream_len;
+  uint32_t *chain_off;         // [max_blocks] first chain of block b in the new plan (k_walk_index_count)
+  uint32_t *group_off;         // [max_blocks] first group of block b
+  // [0] chains, [1] coded blocks, [2] the last one's histogram offset, [3] fewest chains of a coded block that is neither the first nor the
+  // last (0xFFFFFFFF: none), [4] blocks, [5] groups, [6] 0 or why there is no plan (1: block list, 2: tail behind a single-symbol block,
+  // 3: more chains / groups than there is room for), [7] parts a group is cut into at most, [8] 1: grouped launch (fewer groups than chains)
+  uint64_t *result;
+  uint8_t *plan;               // the new plan blob (zeroed, sized for max_chains)
+  Group *groups;               // [max_groups], zeroed
+};
+hipError_t launch_index_assemble_walk(const WalkIndexArgs &a, hipStream_t stream);
 // 64-bit fingerprint of d_stream[0, stream_len) into *d_sum (16-byte aligned stream; asynchronous: memset + one launch)
 hipError_t launch_stream_checksum(const uint8_t *d_stream, uint64_t stream_len, uint64_t *d_sum, hipStream_t stream);
 

@@ -32,7 +32,7 @@
 //   kernels_generic.h   k_decode           mt_ without index, block_ header walk, index-build passes
 //   kernels_dual.h      k_decode_dual      two chains per wave (13-15 bits)
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
-//   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device
+//   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device; k_index_count / k_index_fill, k_walk_index_count / k_walk_index_fill   the indexed plan behind a first decode (mt_, block_)
 //   kernels_gather.h    k_gather           byte ranges of one stream: one wave per task, entered at the chain that holds its first byte
 //                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks; k_gather_set   byte ranges of many streams: every task names its member, one launch per table layout; k_set_cut, k_set_ranges   the same for ranges in device memory
 // This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
@@ -79,6 +79,15 @@ hipError_t launch_index_assemble(const IndexArgs &a, hipStream_t stream)
   (void)hipGetLastError();
   hipLaunchKernelGGL(k_index_count, dim3(1), dim3(1024), 0, stream, a);
   hipLaunchKernelGGL(k_index_fill, dim3(a.n_base), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_assemble_walk(const WalkIndexArgs &a, hipStream_t stream)
+{
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_walk_index_count, dim3(1), dim3(1024), 0, stream, a);
+  // (the block count is on the device: wavefronts stride over the blocks there are, or leave)
+  hipLaunchKernelGGL(k_walk_index_fill, dim3(a.max_blocks < 2048 ? (a.max_blocks ? a.max_blocks : 1) : 2048), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -87,22 +87,22 @@ __device__ void run_block_walk(const WaveCtx &c, const PlanView &pv, const KPara
     hdr = uni64(hdr);
     if (kp.ckpt_interval != 0) // index-build pass: where this block starts and the states the decoder enters it with
     {
-      if (n_blocks >= kp.walk_max_blocks)
+      // a full list ends the recording, not the decode: walk_count stays at walk_max_blocks + 1 ("no plan") and the output is still complete
+      if (n_blocks < kp.walk_max_blocks)
       {
         if (c.lane == 0)
-          atomicOr(c.status, kStatusOutOfRange);
-        return;
+        {
+          kp.walk_blocks[3 * (uint64_t)n_blocks] = pos;
+          kp.walk_blocks[3 * (uint64_t)n_blocks + 1] = i;
+          kp.walk_blocks[3 * (uint64_t)n_blocks + 2] = hdr;
+          kp.walk_count[0] = n_blocks + 1;
+        }
+        if (c.lane < S)
+          kp.walk_states[(uint64_t)n_blocks * S + c.lane] = x;
+        n_blocks++;
       }
-      if (c.lane == 0)
-      {
-        kp.walk_blocks[3 * (uint64_t)n_blocks] = pos;
-        kp.walk_blocks[3 * (uint64_t)n_blocks + 1] = i;
-        kp.walk_blocks[3 * (uint64_t)n_blocks + 2] = hdr;
-        kp.walk_count[0] = n_blocks + 1;
-      }
-      if (c.lane < S)
-        kp.walk_states[(uint64_t)n_blocks * S + c.lane] = x;
-      n_blocks++;
+      else if (c.lane == 0)
+        kp.walk_count[0] = kp.walk_max_blocks + 1;
     }
     pos += 8;
     if (hdr >> 63)

@@ -1,4 +1,4 @@
-// kernels_walk.h — K2: the mt_ header chain followed on the device — k_mt_chase, k_mt_fill.
+// kernels_walk.h — K2: the mt_ header chain followed on the device — k_mt_chase, k_mt_fill; the indexed plan assembled behind a first decode — k_index_count, k_index_fill (mt_), k_walk_index_count, k_walk_index_fill (block_).
 // Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the host-side launcher).
 #ifndef HSRANS_KERNELS_WALK_H
 #define HSRANS_KERNELS_WALK_H
@@ -171,13 +171,37 @@ __device__ __forceinline__ uint32_t index_chains_of(const Piece &bp, uint32_t in
   return bp.steps == 0 ? 1 : (bp.steps + interval - 1) / interval; // (add_interval_chains: g = 0, interval, ... < steps; at least g = 0)
 }
 
+// One value per thread of a 1024-thread workgroup -> its exclusive prefix, continued from call to call through *carry (LDS: zeroed by the
+// caller, one barrier before the first call; the running total afterwards).  Every thread of the workgroup calls it.
+__device__ __forceinline__ uint32_t wg_scan_1024(uint32_t v, uint32_t *wave_tot, uint32_t *carry)
+{
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t incl = v;
+  for (int d = 1; d < 64; d <<= 1)
+  {
+    const uint32_t o = __shfl_up(incl, d, 64);
+    if ((int)lane >= d)
+      incl += o;
+  }
+  if (lane == 63)
+    wave_tot[wave] = incl;
+  __syncthreads();
+  uint32_t before = *carry;
+  for (uint32_t w = 0; w < wave; w++)
+    before += wave_tot[w];
+  __syncthreads();
+  if (threadIdx.x == 1023)
+    *carry = before + incl;
+  __syncthreads();
+  return before + incl - v;
+}
+
 __global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
 {
   __shared__ uint32_t wave_tot[16];
   __shared__ uint32_t carry_s;
   const uint32_t *cf0 = (const uint32_t *)(a.base + plan_chain_first_off());
   const Piece *pc0 = (const Piece *)(a.base + plan_pieces_off(a.n_base));
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0)
     carry_s = 0;
   __syncthreads();
@@ -199,25 +223,9 @@ __global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
           atomicMax((unsigned long long *)&a.result[3], ~(unsigned long long)v);
       }
     }
-    uint32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1)
-    {
-      const uint32_t o = __shfl_up(incl, d, 64);
-      if ((int)lane >= d)
-        incl += o;
-    }
-    if (lane == 63)
-      wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (uint32_t w = 0; w < wave; w++)
-      before += wave_tot[w];
+    const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
     if (ch < a.n_base)
-      a.chain_off[ch] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023)
-      carry_s = before + incl;
-    __syncthreads();
+      a.chain_off[ch] = off;
   }
   if (threadIdx.x == 0)
     a.result[0] = carry_s;
@@ -313,6 +321,226 @@ __global__ void __launch_bounds__(64) k_index_fill(IndexArgs a)
       g.words_end = words_end;
     }
     a.groups[(uint64_t)ch * a.group_split + lane] = g;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same for a block_ stream, from the records of the walk that has just decoded it (run_block_walk with ckpt_interval != 0): byte for
+// byte the plan hsrans_index_build(HSRANS_BLOCK) returns (walk_index_chains in hsrans_capi_index.cpp + PlanBuilder::serialize) and the
+// group list dplan_fill derives from that plan — one group per coded block, cut into parts where there are few (group_parts_of), one
+// per run of single-symbol blocks.  The block count is read here, not on the host: the grids are sized by the host's bound.
+//   k_walk_index_count   one workgroup: chains and groups per block, their exclusive scans, the totals and header facts -> result[]
+//   k_walk_index_fill    one wavefront per block (striding): header, chain table, pieces, start states, groups
+// ---------------------------------------------------------------------------------------------------------------
+struct WalkBlock
+{
+  uint64_t pos, at, hdr;
+  uint64_t T;     // whole groups the block decodes (clipped at the file's last whole group)
+  uint32_t count; // its chains
+  bool fill;
+};
+__device__ __forceinline__ WalkBlock walk_block_of(const WalkIndexArgs &a, uint32_t b)
+{
+  WalkBlock w;
+  w.pos = a.walk_blocks[3 * (uint64_t)b];
+  w.at = a.walk_blocks[3 * (uint64_t)b + 1];
+  w.hdr = a.walk_blocks[3 * (uint64_t)b + 2];
+  w.fill = (w.hdr >> 63) != 0;
+  const uint64_t whole_file = a.decoded_len / a.S, g0 = w.at / a.S, e = (w.at + w.hdr + a.S - 1) / a.S, g1 = e < whole_file ? e : whole_file;
+  w.T = !w.fill && g1 > g0 ? g1 - g0 : 0;
+  w.count = w.T == 0 ? 1 : (uint32_t)((w.T + a.interval - 1) / a.interval); // (g = 0, interval, ... < T; at least g = 0)
+  return w;
+}
+// groups block b opens before any is cut: a coded block one, a run of single-symbol blocks one at its first block
+__device__ __forceinline__ uint32_t walk_block_leads(const WalkIndexArgs &a, uint32_t b, bool fill)
+{
+  return !fill || b == 0 || !(a.walk_blocks[3 * (uint64_t)(b - 1) + 2] >> 63) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
+{
+  __shared__ uint32_t wave_tot[16];
+  __shared__ uint32_t carry_s, coded_s, first_s, last_s, fewest_s, bad_s, lead_s;
+  __shared__ unsigned long long hist_s;
+  const uint32_t n = a.walk_count[0];
+  if (n == 0 || n > a.max_blocks) // (uniform: the walk recorded nothing, or more blocks than the list holds)
+  {
+    if (threadIdx.x == 0)
+      a.result[6] = 1;
+    return;
+  }
+  if (threadIdx.x == 0)
+  {
+    carry_s = coded_s = last_s = bad_s = lead_s = 0;
+    first_s = fewest_s = 0xFFFFFFFFu;
+    hist_s = 0;
+  }
+  __syncthreads();
+  for (uint32_t base = 0; base < n; base += 1024)
+  {
+    const uint32_t b = base + threadIdx.x;
+    uint32_t v = 0;
+    if (b < n)
+    {
+      const WalkBlock w = walk_block_of(a, b);
+      v = w.count;
+      atomicAdd(&lead_s, walk_block_leads(a, b, w.fill));
+      if (w.fill)
+      {
+        if (b + 1 == n && w.at + (w.hdr & (((uint64_t)1 << 54) - 1)) < a.decoded_len) // a tail behind a single-symbol block has no histogram
+          bad_s = 2;
+      }
+      else
+      {
+        atomicAdd(&coded_s, 1u);
+        atomicMin(&first_s, b);
+        atomicMax(&last_s, b);
+        atomicMax(&hist_s, (unsigned long long)(w.pos + 8)); // (exactly one coded block: the plan's chains share its table — PlanBuilder::serialize)
+      }
+    }
+    const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
+    if (b < n)
+      a.chain_off[b] = off;
+  }
+  const uint32_t total = carry_s, lead = lead_s;
+  // dplan_fill: groups only where there are fewer than chains, cut into parts where there are few
+  const bool grouped = lead < total;
+  const uint32_t k_max = grouped ? group_parts_max_of(a.parts_want, lead) : 1;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    carry_s = 0;
+  __syncthreads();
+  for (uint32_t base = 0; base < n; base += 1024)
+  {
+    const uint32_t b = base + threadIdx.x;
+    uint32_t v = 0;
+    if (b < n)
+    {
+      const WalkBlock w = walk_block_of(a, b);
+      v = w.fill ? walk_block_leads(a, b, true) : group_parts_of(w.count, k_max);
+      if (!w.fill && b != first_s && b != last_s) // (k_decode_spread's condition, as dplan_fill has it)
+        atomicMin(&fewest_s, w.count);
+    }
+    const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
+    if (b < n)
+      a.group_off[b] = off;
+  }
+  if (threadIdx.x == 0)
+  {
+    const uint32_t n_groups = carry_s;
+    a.result[0] = total;
+    a.result[1] = coded_s;
+    a.result[2] = hist_s;
+    a.result[3] = fewest_s;
+    a.result[4] = n;
+    a.result[5] = n_groups;
+    a.result[6] = bad_s ? bad_s : total > a.max_chains || n_groups > a.max_groups ? 3 : 0;
+    a.result[7] = k_max;
+    a.result[8] = grouped ? 1 : 0;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_walk_index_fill(WalkIndexArgs a)
+{
+  if (a.result[6] != 0) // no plan: the host reads the word and fails the call
+    return;
+  const uint32_t lane = threadIdx.x, S = a.S;
+  const uint32_t nc = (uint32_t)a.result[0], n = (uint32_t)a.result[4], k_max = (uint32_t)a.result[7];
+  const bool grouped = a.result[8] != 0;
+  uint32_t *chain_first = (uint32_t *)(a.plan + plan_chain_first_off());
+  Piece *pieces = (Piece *)(a.plan + plan_pieces_off(nc));
+  uint32_t *states = (uint32_t *)(a.plan + plan_states_off(nc, nc));
+  const uint64_t tail = a.decoded_len - a.decoded_len / S * S;
+  if (blockIdx.x == 0 && lane == 0)
+  {
+    PlanHeader h = *(const PlanHeader *)a.base; // container, states, bits, lengths: the walk plan's
+    h.flags = 0;
+    h.n_chains = h.n_pieces = nc;
+    h.interval = a.interval;
+    h.shared_hist = a.result[1] == 1 ? 1 : 0;
+    h.aux_off = h.shared_hist ? a.result[2] : 0;
+    *(PlanHeader *)a.plan = h;
+    chain_first[nc] = nc;
+  }
+  for (uint32_t b = blockIdx.x; b < n; b += gridDim.x)
+  {
+    const WalkBlock w = walk_block_of(a, b);
+    const bool last = b + 1 == n;
+    const uint32_t c0 = a.chain_off[b], count = w.count;
+    const uint64_t g_abs0 = w.at / S;
+    for (uint32_t k = lane; k < count; k += 64)
+    {
+      Piece p{};
+      if (w.fill)
+      {
+        p.out_off = w.at;
+        p.hist_off = (w.hdr >> 54) & 0xFF;
+        p.fill_len = w.hdr & (((uint64_t)1 << 54) - 1);
+        p.flags = kPieceFill;
+      }
+      else
+      {
+        const uint64_t g = (uint64_t)k * a.interval;
+        p.hist_off = w.pos + 8;
+        p.out_off = w.at + g * S;
+        p.words_off = k == 0 ? w.pos + 8 + 512 : a.ck_words[(g_abs0 + g) / a.interval];
+        const uint64_t steps = w.T - g < a.interval ? w.T - g : a.interval;
+        p.steps = (uint32_t)steps;
+        p.tail = (uint16_t)(last && g + steps >= w.T ? tail : 0);
+      }
+      p.flags |= kPieceChainStart;
+      p.state_idx = c0 + k;
+      pieces[c0 + k] = p;
+      chain_first[c0 + k] = c0 + k;
+    }
+    for (uint32_t k = 0; k < count; k++)
+      if (lane < S)
+      {
+        uint32_t v = 0;
+        if (!w.fill)
+          v = k == 0 ? a.walk_states[(uint64_t)b * S + lane] : a.ck_states[((g_abs0 + (uint64_t)k * a.interval) / a.interval) * S + lane];
+        states[(uint64_t)(c0 + k) * S + lane] = v;
+      }
+    if (!grouped || !walk_block_leads(a, b, w.fill))
+      continue;
+    // the group's words end where the next coded block's histogram begins (as dplan_fill has it), or at the stream's end
+    uint64_t words_end = a.stream_len;
+    uint32_t run = 1; // a single-symbol block: the blocks of its run
+    for (uint32_t nx = b + 1; nx < n; nx++)
+    {
+      if (!(a.walk_blocks[3 * (uint64_t)nx + 2] >> 63))
+      {
+        words_end = a.walk_blocks[3 * (uint64_t)nx] + 8;
+        break;
+      }
+      run++; // (every block passed here is a single-symbol one: behind a run's first block, the rest of its run)
+    }
+    const uint32_t g0 = a.group_off[b];
+    if (w.fill)
+    {
+      if (lane == 0)
+      {
+        Group g{};
+        g.begin = g.piece0 = c0;
+        g.count = run;
+        g.flags = kGroupFill;
+        g.words_end = words_end;
+        a.groups[g0] = g;
+      }
+      continue;
+    }
+    const uint32_t parts = group_parts_of(count, k_max);
+    for (uint32_t part = lane; part < parts; part += 64)
+    {
+      const uint32_t lo = (uint32_t)((uint64_t)count * part / parts), hi = (uint32_t)((uint64_t)count * (part + 1) / parts);
+      Group g{};
+      g.begin = g.piece0 = c0 + lo;
+      g.count = hi - lo;
+      g.flags = kGroupMergeable;
+      g.hist_off = w.pos + 8;
+      g.words_end = hi < count ? a.ck_words[(g_abs0 + (uint64_t)hi * a.interval) / a.interval] : words_end; // (the next part's first words_off)
+      a.groups[g0 + part] = g;
+    }
   }
 }
 

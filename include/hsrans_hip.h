@@ -160,7 +160,7 @@ uint32_t hsrans_ctx_host_index_chains(hsrans_ctx *ctx);
 /* Host-pointer drop-in for decodeFunc (src/main.cpp:149): H2D, plan, launch, D2H.  Replaces
  * rANS32x{32,64}_16w_decode_*_N, block_rANS32x{32,64}_16w_decode_N, mt_rANS32x{32,64}_16w_decode[_mt]_N.
  * Returns the decoded length, 0 on failure. `plan` may be NULL (derived from the stream).
- * With plan == NULL, mt_ and raw streams of >= 1 MiB leave an index behind: the first call's decode records checkpoints (as
+ * With plan == NULL, mt_, block_ and raw streams of >= 1 MiB leave an index behind: the first call's decode records checkpoints (as
  * hsrans_decode_device_indexing) and the context keeps the plan; a later call with the same `in`, in_length and codec launches it
  * — but only counts when the stream's first 128 bytes (compared on the host) and a 64-bit fingerprint of ALL stream bytes, computed on
  * the device beside the decode, equal the first call's (otherwise the call starts over; other bytes at the same address cost one
@@ -168,7 +168,7 @@ uint32_t hsrans_ctx_host_index_chains(hsrans_ctx *ctx);
  * the same allocation), where a false match needs a 2^-64 coincidence; bytes crafted to collide with it would decode with the previous
  * stream's checkpoints — memory-safe (every read stays inside in_length) but wrong.  Callers that decode hostile streams through this
  * entry switch the cache off (HSRANS_HOST_INDEX_CACHE_OFF=1) or pass their own plan.  A loop over one file (src/main.cpp:860-889) thus runs the indexed kernels from its second iteration:
- * 100 MB mt_: 0.24 -> 0.06 ms of kernel per call; raw: 125 ms -> 0.04 ms (a raw stream's index comes from the host SIMD decoder's
+ * 100 MB mt_: 0.24 -> 0.06 ms of kernel per call; block_: 153 ms (one wavefront walks the inline headers) -> 0.09 ms; raw: 125 ms -> 0.04 ms (a raw stream's index comes from the host SIMD decoder's
  * pass, ~30 ms for 100 MB, during the first call — the one host-side step of this entry; HSRANS_HIP_STRICT=1: from the wavefront that
  * decodes the stream instead, ~125 ms once).  HSRANS_HOST_INDEX_CACHE_OFF=1 disables the cache: every call decodes what the stream alone
  * allows (a raw stream: one wavefront, k_decode_single). */
@@ -398,7 +398,11 @@ size_t hsrans_gather_batch_tasks(const hsrans_gather_member *members, uint32_t n
                                  uint32_t kind, uint32_t waves, hsrans_gather_batch_task *out, size_t capacity);
 
 /* Plan an mt_ stream that only exists in device memory: the header chain (src/mt_rANS32x64_16w_decode.cpp:166-227) is
- * followed by a device kernel; synchronises `hip_stream` twice (chain count, then the finished plan). HSRANS_MT only. */
+ * followed by a device kernel; synchronises `hip_stream` twice (chain count, then the finished plan).
+ * HSRANS_BLOCK: the inline headers are only found by decoding, so the plan is the walk plan hsrans_plan_build makes — from the stream's
+ * first 16 + 4 * states bytes, which are copied down (one synchronisation), with hsrans_plan_build's checks of the lengths against
+ * stream_length and out_capacity; hsrans_decode_device_indexing turns it into a plan with entry points.  HSRANS_RAW: HSRANS_E_ARG
+ * (hsrans_plan_build needs nothing but the header either: copy it down). */
 int hsrans_dplan_create_from_device_stream(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_stream, size_t stream_length,
                                            size_t out_capacity, void *hip_stream, hsrans_dplan **out_dplan);
 /* copies the plan blob a dplan holds in device memory back to the host (inspection / tests); returns its size, 0 on error */
@@ -561,11 +565,17 @@ int hsrans_sharded_status(hsrans_sharded *sharded, void *hip_stream); /* as hsra
 
 /* First decode of a stream that came WITHOUT an index (e.g. a reference-emitted mt_ stream: one chain per block,
  * src/mt_rANS32x64_16w_decode.cpp:137-265 decodes it with one thread per block): decodes like hsrans_decode_device with
- * `dplan` (from hsrans_plan_build + hsrans_dplan_create, or from hsrans_dplan_create_from_device_stream; HSRANS_RAW and
- * HSRANS_MT, no checkpoints yet) and records the coder states and read cursor every `index_interval` groups (multiple of 4)
- * on the way.  *indexed receives a device plan with those checkpoints (the blob hsrans_index_build would return for the
- * same stream and interval) for every later decode of the same stream.  Synchronises `hip_stream`.  d_out is complete on
- * return.  HSRANS_E_DEVICE: the pass found a malformed stream (status cleared), *indexed is NULL. */
+ * `dplan` (from hsrans_plan_build + hsrans_dplan_create, or from hsrans_dplan_create_from_device_stream; HSRANS_RAW,
+ * HSRANS_MT and HSRANS_BLOCK, no checkpoints yet) and records the coder states and read cursor every `index_interval` groups
+ * (multiple of 4) on the way.  *indexed receives a device plan with those checkpoints (the blob hsrans_index_build would return
+ * for the same stream and interval) for every later decode of the same stream.  Synchronises `hip_stream`.  d_out is complete on
+ * return.  HSRANS_E_DEVICE: the pass found a malformed stream (status cleared), *indexed is NULL, d_out is unspecified.
+ * A block_ stream comes with its walk plan: the one wavefront that follows the inline headers (block_rANS32x64_16w_decode.cpp:47-123)
+ * also records every block header and the states it enters the block with, and the plan — one chain per block and per checkpoint —
+ * and its group list are assembled on the device behind it.  HSRANS_E_FORMAT with d_out COMPLETE and *indexed NULL: the stream
+ * holds more than decoded_len / 4096 + 16 blocks, or ends in a single-symbol block with a partial group behind it — the cases in
+ * which hsrans_index_build returns 0; decode it with the walk plan.  HSRANS_INDEX_ASSEMBLE_ON_HOST=1 (read at hsrans_ctx_create):
+ * the records come down and the host writes the same blob (mt_ and block_; the comparison path). */
 int hsrans_decode_device_indexing(hsrans_ctx *ctx, hsrans_dplan *dplan, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity,
                                   uint32_t index_interval, void *hip_stream, hsrans_dplan **indexed);
 

@@ -1,0 +1,18 @@
+"""Build-time guard for the kernels that assemble a block_ stream's indexed plan on the device behind its first decode
+(hsrans_decode_device_indexing on a walk plan): k_walk_index_count and k_walk_index_fill, from the compiler's resource report as
+tests/test_kernel_resources.py reads it.  Both are in the code object, once each, and neither spills to scratch; their registers are
+reported as built (one workgroup and one wavefront per block of small kernels: nothing bounds their occupancy)."""
+import pytest
+
+from test_kernel_resources import _report
+
+KERNELS = ("k_walk_index_count", "k_walk_index_fill")
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_in_the_code_object_without_scratch(kernel):
+    found = [r for name, r in _report("hsrans_kernels").items() if kernel in name]
+    assert len(found) == 1, (kernel, len(found))
+    r = found[0]
+    print("%s: %d VGPRs, %d SGPRs, %d waves/SIMD, %d bytes of LDS" % (kernel, r["VGPRs"], r["TotalSGPRs"], r["Occupancy [waves/SIMD]"], r["LDS Size [bytes/block]"]))
+    assert r["ScratchSize [bytes/lane]"] == 0, (kernel, r)

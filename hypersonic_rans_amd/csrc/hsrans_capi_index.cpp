@@ -10,6 +10,7 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -29,88 +30,138 @@ using namespace hsrans;
 extern "C"
 {
 
-// The chains of a plan with a checkpoint every `index_interval` groups (absolute group numbers: slot = group / interval), given
-// the base plan (one single-piece chain per block) and what a recording decode pass left at the checkpoints
-static void add_interval_chains(PlanBuilder &pb, const PlanHeader &h, const uint32_t *cf0, const Piece *pc0, const uint32_t *st0, uint32_t index_interval,
-                                const uint32_t *ck_states, const uint64_t *ck_words)
+// Where the blocks of an index come from: a base plan's single-piece chains (raw, mt_), or the records of the walk over a block_ stream —
+// block b's {header position, output offset, header word} in blocks[3b .. 3b+2] and the states it was entered with in bstates[b * S ..]
+struct IndexSource
 {
-  const uint32_t S = h.states;
-  for (uint32_t ch = 0; ch < h.n_chains; ch++)
-  {
-    const Piece &bp = pc0[cf0[ch]];
-    if (bp.flags & kPieceFill)
-    {
-      pb.add_chain(bp, nullptr);
-      continue;
-    }
-    const uint64_t T = bp.steps, g_abs0 = bp.out_off / S;
-    for (uint64_t g = 0; g < T || g == 0; g += index_interval)
-    {
-      Piece p{};
-      p.hist_off = bp.hist_off;
-      p.out_off = bp.out_off + g * S;
-      const uint64_t slot = (g_abs0 + g) / index_interval;
-      p.words_off = g == 0 ? bp.words_off : ck_words[slot];
-      const uint64_t steps = T - g < index_interval ? T - g : index_interval;
-      p.steps = (uint32_t)steps;
-      p.tail = (uint16_t)(g + steps == T ? bp.tail : 0);
-      pb.add_chain(p, g == 0 ? st0 + (size_t)bp.state_idx * S : &ck_states[slot * S]);
-    }
-  }
+  uint32_t n_blocks;
+  const uint32_t *cf0, *st0; // base plan
+  const Piece *pc0;
+  const uint64_t *blocks; // walk records (null: a base plan)
+  const uint32_t *bstates;
+  uint64_t decoded_len;
+};
+static IndexSource source_of_plan(const uint8_t *base, const PlanHeader &h)
+{
+  return {h.n_chains, (const uint32_t *)(base + plan_chain_first_off()), (const uint32_t *)(base + plan_states_off(h.n_chains, h.n_pieces)),
+          (const Piece *)(base + plan_pieces_off(h.n_chains)), nullptr, nullptr, h.decoded_len};
 }
 
-// The chains of a block_ stream's plan with a checkpoint every `index_interval` groups, from what the walk that recorded them left: block b's
-// {header position, output offset, header word} in blocks[3b .. 3b+2], the states it was entered with in bstates[b * S ..], and the
-// checkpoints (slot = absolute group / interval).  One fill chain per single-symbol block, one chain per block start and per checkpoint
-// inside a coded block.  false: no plan (a tail behind a trailing single-symbol block).  k_walk_index_fill writes the same on the device.
-static bool walk_index_chains(PlanBuilder &pb, uint32_t S, uint64_t out_len, uint32_t index_interval, uint32_t n_blocks, const uint64_t *blocks,
-                              const uint32_t *bstates, const uint32_t *ck_states, const uint64_t *ck_words)
+// The chains of a plan with a checkpoint every `interval` groups, given what a recording pass left at the checkpoints (slot = absolute
+// group / interval): one fill chain per single-symbol block, one chain per block start and per checkpoint inside a coded block (IndexBlock,
+// hsrans_kernels.h: the fill kernels write the same on the device).  false: no plan (a tail behind a trailing single-symbol block).
+static bool add_interval_chains(PlanBuilder &pb, const IndexSource &src, uint32_t interval, const uint32_t *ck_states, const uint64_t *ck_words)
 {
-  const uint64_t whole_file = out_len / S; // whole groups of the file (block_rANS32x64_16w_decode.cpp:82-88)
-  const uint64_t tail = out_len - whole_file * S;
-  for (uint32_t b = 0; b < n_blocks; b++)
+  const uint32_t S = pb.hdr.states;
+  for (uint32_t b = 0; b < src.n_blocks; b++)
   {
-    const uint64_t pos = blocks[3 * (size_t)b], at = blocks[3 * (size_t)b + 1], hdr = blocks[3 * (size_t)b + 2];
-    const bool last = b + 1 == n_blocks;
-    if (hdr >> 63)
-    {
-      Piece p{};
-      p.out_off = at;
-      p.hist_off = (hdr >> 54) & 0xFF;
-      p.fill_len = hdr & (((uint64_t)1 << 54) - 1);
-      p.flags = kPieceChainStart | kPieceFill;
-      pb.add_chain(p, nullptr);
-      if (last && at + p.fill_len < out_len) // a tail behind a single-symbol block has no histogram
-        return false;
-      continue;
-    }
-    const uint64_t g0 = at / S;
-    const uint64_t g1 = std::min<uint64_t>((at + hdr + S - 1) / S, whole_file); // the decoder stops at the last whole group
-    const uint64_t T = g1 > g0 ? g1 - g0 : 0;
-    for (uint64_t g = 0; g < T || g == 0; g += index_interval)
-    {
-      Piece p{};
-      p.hist_off = pos + 8;
-      p.out_off = at + g * S;
-      const uint64_t slot = (g0 + g) / index_interval;
-      p.words_off = g == 0 ? pos + 8 + 512 : ck_words[slot];
-      const uint64_t steps = T - g < index_interval ? T - g : index_interval;
-      p.steps = (uint32_t)steps;
-      p.tail = (uint16_t)(last && g + steps >= T ? tail : 0);
-      pb.add_chain(p, g == 0 ? &bstates[(size_t)b * S] : &ck_states[slot * S]);
-    }
+    const bool last = b + 1 == src.n_blocks;
+    const uint64_t *rec = src.blocks ? src.blocks + 3 * (size_t)b : nullptr;
+    const Piece *bp = rec ? nullptr : &src.pc0[src.cf0[b]];
+    const IndexBlock blk = rec ? index_block_of_walk(rec[0], rec[1], rec[2], src.decoded_len, S, last) : index_block_of_piece(*bp, S, last);
+    const uint32_t *entry = rec ? src.bstates + (size_t)b * S : src.st0 + (size_t)bp->state_idx * S;
+    if (rec && index_block_ends_short(blk, src.decoded_len))
+      return false;
+    for (uint32_t k = 0, n = index_block_chains(blk, interval); k < n; k++)
+      pb.add_chain(index_chain_piece(blk, S, interval, k, ck_words, 0), index_chain_states(blk, S, interval, k, entry, ck_states));
   }
   return true;
 }
 
+// ---- what every recording pass shares ------------------------------------------------------------------------------------------------
+// What a recording pass writes besides the output: checkpoint states and read cursors, and for a block_ walk the block records, the states
+// on entry to each block and the block count.  Byte counts of the first four.
+struct PassBytes
+{
+  size_t st, wd, blk, bst;
+  size_t all() const { return st + wd + blk + bst; }
+};
+struct PassBuffers // device
+{
+  uint32_t *ck_states;
+  uint64_t *ck_words;
+  uint64_t *walk_blocks; // null: not a walk
+  uint32_t *walk_states, *walk_count;
+  uint32_t max_blocks;
+};
+static PassBytes pass_bytes(uint64_t n_ck, uint32_t S, uint64_t max_blocks) { return {(size_t)n_ck * S * 4, (size_t)n_ck * 8, (size_t)max_blocks * 24, (size_t)max_blocks * S * 4}; }
+// room for blocks of >= 4 KiB on average (the reference's smallest block is 32 KiB, block_rANS32x64_16w_encode.cpp:21-39); a stream with more gets no plan
+static uint64_t walk_max_blocks(uint64_t decoded_len) { return decoded_len / 4096 + 16; }
+
+// The pass: the base plan (blob and status word on the device, header h) decodes d_stream into d_out and records {states, read cursor} every
+// `interval` groups, or (interval 0) at the n_groups ascending groups of d_groups; a walk plan also records its blocks.
+static hipError_t launch_recording_pass(hsrans_ctx *ctx, const uint8_t *d_plan, uint32_t *d_status, const PlanHeader &h, const void *d_stream, size_t stream_length,
+                                        void *d_out, size_t out_capacity, uint32_t interval, const uint64_t *d_groups, uint32_t n_groups, const PassBuffers &b, hipStream_t s)
+{
+  KParams kp{};
+  kp.stream = (const uint8_t *)d_stream;
+  kp.stream_len = stream_length;
+  kp.out = (uint8_t *)d_out;
+  kp.out_cap = out_capacity;
+  kp.plan = d_plan;
+  kp.status = d_status;
+  kp.ckpt_states = b.ck_states;
+  kp.ckpt_words = b.ck_words;
+  kp.ckpt_interval = interval;
+  kp.ckpt_groups = d_groups;
+  kp.n_ckpt_groups = n_groups;
+  kp.walk_blocks = b.walk_blocks;
+  kp.walk_states = b.walk_states;
+  kp.walk_count = b.walk_count;
+  kp.walk_max_blocks = b.max_blocks;
+  PlanHeader hl = h;
+  if (!(h.flags & kPlanWalk))
+    hl.shared_hist = 0; // private tables: every chain of the pass builds its own (raw has one chain, mt_ one per block)
+  return launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr);
+}
+
+// The status word a pass left, once it is on the host: non-zero (a bad histogram / header) is reported and cleared like hsrans_dplan_status does
+static int pass_status_rc(uint32_t status, uint32_t *d_status, hipStream_t s)
+{
+  if (status == 0)
+    return HSRANS_OK;
+  return hipMemsetAsync(d_status, 0, 4, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? HSRANS_E_DEVICE : HSRANS_E_HIP;
+}
+
+// What a recording walk left, brought down to host_ck [checkpoint states | cursors] and host_walk [blocks | entry states] (sized by pbytes):
+// the count and the status word first, then as many blocks and entry states as there are and the checkpoints, with one more synchronisation
+static int download_walk_records(const PassBuffers &b, const PassBytes &pbytes, uint32_t S, uint32_t *d_status, uint8_t *host_ck, uint8_t *host_walk, uint32_t *n_blocks,
+                                 hipStream_t s)
+{
+  uint32_t status = 0xFFFFFFFF;
+  *n_blocks = 0;
+  if (hipMemcpyAsync(n_blocks, b.walk_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  if (status != 0)
+    return pass_status_rc(status, d_status, s);
+  if (*n_blocks == 0 || *n_blocks > b.max_blocks)
+    return HSRANS_E_FORMAT;
+  if (hipMemcpyAsync(host_ck, b.ck_states, pbytes.st, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(host_ck + pbytes.st, b.ck_words, pbytes.wd, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(host_walk, b.walk_blocks, (size_t)*n_blocks * 24, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(host_walk + pbytes.blk, b.walk_states, (size_t)*n_blocks * S * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  return HSRANS_OK;
+}
+// ... and the plan's chains from that copy
+static bool add_walk_chains(PlanBuilder &pb, const PassBytes &pbytes, const uint8_t *host_ck, const uint8_t *host_walk, uint32_t n_blocks, uint32_t interval)
+{
+  const IndexSource src{n_blocks, nullptr, nullptr, nullptr, (const uint64_t *)host_walk, (const uint32_t *)(host_walk + pbytes.blk), pb.hdr.decoded_len};
+  return add_interval_chains(pb, src, interval, (const uint32_t *)host_ck, (const uint64_t *)(host_ck + pbytes.st));
+}
+
+static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
 static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint32_t bits, const uint8_t *in, size_t in_length, uint32_t index_interval,
                                const uint64_t *groups, size_t n_groups, uint8_t *plan_out, size_t plan_capacity)
 {
-  // One pass over an existing stream that records {states, read cursor} every `index_interval` groups inside every rANS
-  // piece of the stream's own plan (raw: one sequential wavefront; mt_: one wavefront per block, in parallel); the
-  // checkpoints then become additional chains.  A block_ stream is one chain with inline headers (the position of a block's
-  // header is only known once the block before it is decoded): the single wavefront that walks it also reports every block
-  // header it meets and the states it enters the block with, and the plan gets one chain per block plus the checkpoints.
+  // One pass over an existing stream that records {states, read cursor} every `index_interval` groups inside every rANS piece of the
+  // stream's own plan; the checkpoints then become additional chains.  raw: one dependent chain, indexed on the host (below).  mt_: one
+  // wavefront per block, in parallel.  A block_ stream is one chain with inline headers (the position of a block's header is only known
+  // once the block before it is decoded): the single wavefront that walks it also reports every block header it meets and the states it
+  // enters the block with, and the plan gets one chain per block plus the checkpoints.
   if (ctx == nullptr || in == nullptr || plan_out == nullptr || !valid_codec(container, states, bits))
     return 0;
   // checkpoints every index_interval groups, or (groups != nullptr) at explicit ascending group indices
@@ -133,9 +184,7 @@ static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint3
   const size_t base_size = base.size();
   PlanHeader h;
   memcpy(&h, base.data(), sizeof(h));
-  const uint32_t *cf0 = (const uint32_t *)(base.data() + plan_chain_first_off());
-  const Piece *pc0 = (const Piece *)(base.data() + plan_pieces_off(h.n_chains));
-  const uint32_t *st0 = (const uint32_t *)(base.data() + plan_states_off(h.n_chains, h.n_pieces));
+  const IndexSource src = source_of_plan(base.data(), h);
   const uint32_t S = (uint32_t)states;
   const bool walk = (h.flags & kPlanWalk) != 0;
   if (!walk && h.n_pieces != h.n_chains) // the planner only produces single-piece chains for raw and mt_
@@ -149,7 +198,7 @@ static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint3
     std::vector<uint64_t> own;
     if (groups == nullptr)
     {
-      const uint64_t T = h.n_pieces == 1 ? pc0[0].steps : 0;
+      const uint64_t T = h.n_pieces == 1 ? src.pc0[0].steps : 0;
       for (uint64_t g = index_interval; g < T; g += index_interval)
         own.push_back(g);
       if (own.empty())
@@ -159,137 +208,74 @@ static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint3
                             plan_capacity, groups ? 0 : index_interval);
   }
   const uint64_t n_ck = groups ? n_groups : out_len / S / index_interval + 2;
-  // block_: room for blocks of >= 4 KiB on average (the reference's smallest block is 32 KiB, block_rANS32x64_16w_encode.cpp:21-39)
-  const uint64_t max_blocks = walk ? out_len / 4096 + 16 : 0;
+  const uint64_t max_blocks = walk ? std::min<uint64_t>(walk_max_blocks(out_len), 0xFFFFFFFFull) : 0;
+  const PassBytes pbytes = pass_bytes(n_ck, S, max_blocks);
 
   std::lock_guard<std::mutex> guard(ctx->lock);
   if (hipSetDevice(ctx->device) != hipSuccess)
     return 0;
-  const size_t in_pad = (in_length + 15) / 16 * 16;
+  const size_t in_pad = up16(in_length);
   if (!grow(&ctx->d_in, &ctx->d_in_cap, in_pad) || !grow(&ctx->d_out, &ctx->d_out_cap, (size_t)out_len + 16) || !grow(&ctx->d_plan, &ctx->d_plan_cap, base_size))
     return 0;
-  uint32_t *d_ck_states = nullptr;
-  uint64_t *d_ck_words = nullptr, *d_groups = nullptr;
-  uint64_t *d_walk_blocks = nullptr;
-  uint32_t *d_walk_states = nullptr, *d_walk_count = nullptr;
+  // one region for what the pass records, for this call only: [checkpoint states | cursors | the caller's groups | blocks | entry states | block count]
+  const size_t off_wd = up16(pbytes.st), off_groups = off_wd + up16(pbytes.wd), off_blk = off_groups + up16(groups ? n_groups * 8 : 0), off_bst = off_blk + up16(pbytes.blk);
+  const size_t off_count = off_bst + up16(pbytes.bst);
+  uint8_t *d_rec = nullptr;
+  if (hipMalloc((void **)&d_rec, off_count + 16) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return 0;
+  }
+  const PassBuffers pass{(uint32_t *)d_rec, (uint64_t *)(d_rec + off_wd), walk ? (uint64_t *)(d_rec + off_blk) : nullptr, walk ? (uint32_t *)(d_rec + off_bst) : nullptr,
+                         walk ? (uint32_t *)(d_rec + off_count) : nullptr, (uint32_t)max_blocks};
+  uint64_t *d_groups = groups ? (uint64_t *)(d_rec + off_groups) : nullptr;
   size_t result = 0;
   hipStream_t s = ctx->stream;
-  std::vector<uint32_t> ck_states(n_ck * S);
-  std::vector<uint64_t> ck_words(n_ck);
-  uint32_t status = 0xFFFFFFFF;
+  std::vector<uint8_t> host_ck(pbytes.st + pbytes.wd);                        // the records on the host: [checkpoint states | cursors]
+  std::unique_ptr<uint8_t[]> host_walk(new uint8_t[pbytes.blk + pbytes.bst]); // ... and the walk's [blocks | entry states]
+  const uint32_t *ck_states = (const uint32_t *)host_ck.data();
+  const uint64_t *ck_words = (const uint64_t *)(host_ck.data() + pbytes.st);
   do
   {
-    if (hipMalloc((void **)&d_ck_states, n_ck * S * 4) != hipSuccess || hipMalloc((void **)&d_ck_words, n_ck * 8) != hipSuccess)
+    if (groups && hipMemcpyAsync(d_groups, groups, n_groups * 8, hipMemcpyHostToDevice, s) != hipSuccess)
       break;
-    if (groups && (hipMalloc((void **)&d_groups, n_groups * 8) != hipSuccess || hipMemcpyAsync(d_groups, groups, n_groups * 8, hipMemcpyHostToDevice, s) != hipSuccess))
-      break;
-    if (walk && (hipMalloc((void **)&d_walk_blocks, max_blocks * 24) != hipSuccess || hipMalloc((void **)&d_walk_states, max_blocks * S * 4) != hipSuccess ||
-                 hipMalloc((void **)&d_walk_count, 4) != hipSuccess || hipMemsetAsync(d_walk_count, 0, 4, s) != hipSuccess))
-      break;
-    if (hipMemcpyAsync(ctx->d_in, in, in_length, hipMemcpyHostToDevice, s) != hipSuccess ||
+    if (hipMemsetAsync(d_rec + off_count, 0, 16, s) != hipSuccess || hipMemcpyAsync(ctx->d_in, in, in_length, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(ctx->d_plan, base.data(), base_size, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(ctx->d_status, 0, 4, s) != hipSuccess)
       break;
-    KParams kp{};
-    kp.stream = ctx->d_in;
-    kp.stream_len = in_length;
-    kp.out = ctx->d_out;
-    kp.out_cap = out_len;
-    kp.plan = ctx->d_plan;
-    kp.status = ctx->d_status;
-    kp.ckpt_states = d_ck_states;
-    kp.ckpt_words = d_ck_words;
-    kp.ckpt_interval = index_interval;
-    kp.ckpt_groups = d_groups;
-    kp.n_ckpt_groups = (uint32_t)(groups ? n_groups : 0);
-    kp.walk_blocks = d_walk_blocks;
-    kp.walk_states = d_walk_states;
-    kp.walk_count = d_walk_count;
-    kp.walk_max_blocks = (uint32_t)(max_blocks > 0xFFFFFFFFull ? 0xFFFFFFFFull : max_blocks);
-    PlanHeader hl = h;
-    hl.shared_hist = 0; // private tables: every chain of the pass builds its own (raw has one chain, mt_ one per block)
-    if (launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr) != hipSuccess)
-      break;
-    if (hipMemcpyAsync(ck_states.data(), d_ck_states, n_ck * S * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(ck_words.data(), d_ck_words, n_ck * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&status, ctx->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      break;
-    if (status != 0)
+    if (launch_recording_pass(ctx, ctx->d_plan, ctx->d_status, h, ctx->d_in, in_length, ctx->d_out, out_len, index_interval, d_groups, (uint32_t)(groups ? n_groups : 0), pass,
+                              s) != hipSuccess)
       break;
     PlanBuilder pb;
     pb.begin(container, states, bits, out_len, in_length);
     pb.hdr.interval = index_interval;
-    if (container == HSRANS_RAW)
-    {
-      uint16_t counts[256];
-      memcpy(counts, in + pc0[0].hist_off, 512);
-      pb.set_hist(counts);
-    }
     if (walk)
     {
       uint32_t n_blocks = 0;
-      if (hipMemcpy(&n_blocks, d_walk_count, 4, hipMemcpyDeviceToHost) != hipSuccess || n_blocks == 0 || n_blocks > max_blocks)
+      if (download_walk_records(pass, pbytes, S, ctx->d_status, host_ck.data(), host_walk.get(), &n_blocks, s) != HSRANS_OK ||
+          !add_walk_chains(pb, pbytes, host_ck.data(), host_walk.get(), n_blocks, index_interval))
         break;
-      std::vector<uint64_t> blocks((size_t)n_blocks * 3);
-      std::vector<uint32_t> bstates((size_t)n_blocks * S);
-      if (hipMemcpy(blocks.data(), d_walk_blocks, blocks.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(bstates.data(), d_walk_states, bstates.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        break;
-      if (!walk_index_chains(pb, S, out_len, index_interval, n_blocks, blocks.data(), bstates.data(), ck_states.data(), ck_words.data()))
-        break;
-    }
-    else if (groups != nullptr)
-    {
-      size_t k = 0; // next boundary
-      for (uint32_t ch = 0; ch < h.n_chains; ch++)
-      {
-        const Piece &bp = pc0[cf0[ch]];
-        if (bp.flags & kPieceFill)
-        {
-          pb.add_chain(bp, nullptr);
-          continue;
-        }
-        const uint64_t T = bp.steps, g0 = bp.out_off / S;
-        while (k < n_groups && groups[k] <= g0)
-          k++;
-        uint64_t g = 0; // groups of this piece already assigned to chains
-        const uint32_t *st = st0 + (size_t)bp.state_idx * S;
-        uint64_t words = bp.words_off;
-        while (true)
-        {
-          const bool more = k < n_groups && groups[k] < g0 + T;
-          const uint64_t g_next = more ? groups[k] - g0 : T;
-          Piece p{};
-          p.hist_off = bp.hist_off;
-          p.out_off = bp.out_off + g * S;
-          p.words_off = words;
-          p.steps = (uint32_t)(g_next - g);
-          p.tail = (uint16_t)(more ? 0 : bp.tail);
-          pb.add_chain(p, st);
-          if (!more)
-            break;
-          st = &ck_states[k * S];
-          words = ck_words[k];
-          g = g_next;
-          k++;
-        }
-      }
     }
     else
-      add_interval_chains(pb, h, cf0, pc0, st0, index_interval, ck_states.data(), ck_words.data());
+    {
+      uint32_t status = 0xFFFFFFFF;
+      if (hipMemcpyAsync(host_ck.data(), pass.ck_states, pbytes.st, hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipMemcpyAsync(host_ck.data() + pbytes.st, pass.ck_words, pbytes.wd, hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipMemcpyAsync(&status, ctx->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
+          pass_status_rc(status, ctx->d_status, s) != HSRANS_OK)
+        break;
+      if (groups != nullptr)
+        add_group_chains(pb, h, src.cf0, src.pc0, src.st0, groups, n_groups, ck_states, ck_words);
+      else
+        add_interval_chains(pb, src, index_interval, ck_states, ck_words);
+    }
     result = pb.serialize(plan_out, plan_capacity);
   } while (false);
-  if (d_ck_states)
-    (void)hipFree(d_ck_states);
-  if (d_ck_words)
-    (void)hipFree(d_ck_words);
-  if (d_groups)
-    (void)hipFree(d_groups);
-  if (d_walk_blocks)
-    (void)hipFree(d_walk_blocks);
-  if (d_walk_states)
-    (void)hipFree(d_walk_states);
-  if (d_walk_count)
-    (void)hipFree(d_walk_count);
+  if (result == 0)
+  {
+    (void)hipStreamSynchronize(s); // nothing queued above may still be using the region when it is freed
+    (void)hipGetLastError();
+  }
+  (void)hipFree(d_rec);
   return result;
 }
 
@@ -317,97 +303,114 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
   return 0;
 }
 
+// ---- what both device assemblies share ----------------------------------------------------------------------------------------------
+// The checkpoint buffers of a first decode: the context's (the GPU encoder's, kept and grown; under ctx->lock), not fresh allocations
+static bool context_checkpoints(hsrans_ctx *ctx, const PassBytes &pbytes, PassBuffers *b)
+{
+  if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, pbytes.st + pbytes.wd))
+    return false;
+  b->ck_states = (uint32_t *)ctx->d_enc_ck;
+  b->ck_words = (uint64_t *)(ctx->d_enc_ck + pbytes.st);
+  return true;
+}
+
+// The plan a device assembly writes, with room for max_chains chains and max_groups groups.  Its arena's scratch: the assembly's IndexResult
+// (and at +128 a walk's block count), from +256 `off_words` chain / group offsets, behind them (16-byte aligned) `extra` bytes.  null: no memory
+constexpr size_t kAssemblyCount = 128, kAssemblyOffsets = 256;
+static hsrans_dplan *assembly_plan(hsrans_ctx *ctx, uint32_t S, uint32_t max_chains, size_t max_groups, size_t off_words, size_t extra, hipStream_t s, uint8_t **scratch)
+{
+  hsrans_dplan *nd = dplan_new(ctx);
+  if (nd == nullptr)
+    return nullptr;
+  DplanRegions r;
+  r.counters = true;
+  r.plan = (size_t)plan_size(max_chains, max_chains, S, 0);
+  r.groups = max_groups * sizeof(Group);
+  r.scratch = kAssemblyOffsets + up16(off_words * 4) + extra;
+  r.zero = kZeroAll;
+  if (dplan_arena(nd, r, s, scratch) != HSRANS_OK)
+  {
+    hsrans_dplan_destroy(nd);
+    return nullptr;
+  }
+  return nd;
+}
+
+// Behind the pass and the assembly kernels (`queued`: all of them were): what the count kernel left comes back with the base plan d's status
+// word, is checked against the bounds, and nd takes over the plan the device wrote.  One synchronisation — nothing queued may still be running
+// when this returns, whatever failed; on failure nd is destroyed.
+static int finish_assembly(hsrans_dplan *d, hsrans_dplan *nd, bool queued, const IndexResult *d_result, uint32_t interval, uint32_t min_chains, uint32_t max_chains,
+                           uint32_t max_groups, hipStream_t s, IndexResult *r)
+{
+  uint32_t status = 0xFFFFFFFF;
+  const bool ok = queued && hipMemcpyAsync(r, d_result, sizeof(*r), hipMemcpyDeviceToHost, s) == hipSuccess &&
+                  hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+  const bool synced = hipStreamSynchronize(s) == hipSuccess;
+  int rc = ok && synced ? pass_status_rc(status, d->d_status, s) : HSRANS_E_HIP;
+  // no plan: IndexResult::error, no chains, or more chains / groups than the arena has room for
+  if (rc == HSRANS_OK && (r->error != 0 || r->chains < min_chains || r->chains > max_chains || r->groups > max_groups))
+    rc = HSRANS_E_FORMAT;
+  if (rc != HSRANS_OK)
+  {
+    (void)hipGetLastError();
+    hsrans_dplan_destroy(nd);
+    return rc;
+  }
+  PlanHeader hn = d->hdr;
+  hn.flags = 0;
+  hn.n_chains = hn.n_pieces = r->chains;
+  hn.interval = interval;
+  hn.shared_hist = r->coded == 1 ? 1 : 0;
+  hn.aux_off = hn.shared_hist ? r->hist_off : 0;
+  dplan_adopt(nd, hn, r->groups, r->fewest, s); // (kIndexNoFewest is the largest spread_min_block a plan keeps)
+  return HSRANS_OK;
+}
+
 // hsrans_decode_device_indexing for a block_ stream's walk plan (d: kPlanWalk, one chain, no checkpoints; the arguments are checked).  The one
 // wavefront that walks the inline headers decodes into the caller's d_out and records block headers, entry states and checkpoints; behind it,
 // on the same stream, k_walk_index_count / k_walk_index_fill write the indexed plan and its group list into the new plan's arena, which also
-// holds the walk's records.  A few result words come back; one synchronisation.  HSRANS_INDEX_ASSEMBLE_ON_HOST=1: the records come down and
-// walk_index_chains + hsrans_dplan_create make the same plan.
+// holds the walk's records.  HSRANS_INDEX_ASSEMBLE_ON_HOST=1: the records come down and add_interval_chains + hsrans_dplan_create make the same plan.
 static int decode_walk_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity,
                                 uint32_t index_interval, hipStream_t s, hsrans_dplan **indexed, bool have_lock)
 {
   const PlanHeader &h = d->hdr;
   const uint32_t S = h.states;
   const uint64_t n_ck = h.decoded_len / S / index_interval + 2;
-  // room for blocks of >= 4 KiB on average, as hsrans_index_build has it; a stream with more gets no plan
-  const uint64_t max_blocks = h.decoded_len / 4096 + 16, max_chains = max_blocks + n_ck, max_groups = max_blocks + max_chains / kGroupPartChains + 16;
+  const uint64_t max_blocks = walk_max_blocks(h.decoded_len), max_chains = max_blocks + n_ck, max_groups = max_blocks + max_chains / kGroupPartChains + 16;
   if (max_chains > 0xFFFFFFF0u)
     return HSRANS_E_FORMAT;
   std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer belongs to the context)
   if (!have_lock)
     guard.lock();
-  const size_t st_bytes = (size_t)n_ck * S * 4, wd_bytes = (size_t)n_ck * 8;
-  const size_t off_bytes = ((size_t)max_blocks * 8 + 15) / 16 * 16, blk_bytes = (size_t)max_blocks * 24, bst_bytes = (size_t)max_blocks * S * 4;
-  if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, st_bytes + wd_bytes))
+  const PassBytes pbytes = pass_bytes(n_ck, S, max_blocks);
+  PassBuffers pass{};
+  if (!context_checkpoints(ctx, pbytes, &pass))
     return HSRANS_E_HIP;
-  hsrans_dplan *nd = dplan_new(ctx);
+  uint8_t *scratch = nullptr;
+  hsrans_dplan *nd = assembly_plan(ctx, S, (uint32_t)max_chains, (size_t)max_groups, 2 * (size_t)max_blocks, pbytes.blk + pbytes.bst, s, &scratch);
   if (nd == nullptr)
     return HSRANS_E_HIP;
-  DplanRegions r;
-  r.counters = true;
-  r.plan = (size_t)plan_size((uint32_t)max_chains, (uint32_t)max_chains, S, 0);
-  r.groups = (size_t)max_groups * sizeof(Group);
-  r.scratch = 256 + off_bytes + blk_bytes + bst_bytes; // result words and the walk's block count, chain and group offsets, the walk's records
-  r.zero = kZeroAll;
-  uint8_t *scratch = nullptr;
-  if (dplan_arena(nd, r, s, &scratch) != HSRANS_OK)
-  {
-    hsrans_dplan_destroy(nd);
-    return HSRANS_E_HIP;
-  }
-  uint64_t *d_result = (uint64_t *)scratch;
-  uint32_t *d_walk_count = (uint32_t *)(scratch + 128);
-  uint64_t *d_walk_blocks = (uint64_t *)(scratch + 256 + off_bytes);
-  uint32_t *d_walk_states = (uint32_t *)(scratch + 256 + off_bytes + blk_bytes);
-  KParams kp{};
-  kp.stream = (const uint8_t *)d_stream;
-  kp.stream_len = stream_length;
-  kp.out = (uint8_t *)d_out;
-  kp.out_cap = out_capacity;
-  kp.plan = d->d_plan;
-  kp.status = d->d_status;
-  kp.ckpt_states = (uint32_t *)ctx->d_enc_ck;
-  kp.ckpt_words = (uint64_t *)(ctx->d_enc_ck + st_bytes);
-  kp.ckpt_interval = index_interval;
-  kp.walk_blocks = d_walk_blocks;
-  kp.walk_states = d_walk_states;
-  kp.walk_count = d_walk_count;
-  kp.walk_max_blocks = (uint32_t)max_blocks;
-  uint32_t status = 0xFFFFFFFF;
-  auto fail = [&](int rc) { // (nothing queued here may still be running when the call returns, whatever failed)
-    (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    hsrans_dplan_destroy(nd);
-    return rc;
-  };
-  // the walk set a status bit (a bad histogram / header): reported and cleared like hsrans_dplan_status does
-  auto device_error = [&] { return hipMemsetAsync(d->d_status, 0, 4, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? HSRANS_E_DEVICE : HSRANS_E_HIP; };
-  if (launch_decode(ctx->tuning, kp, h, ctx->geom, s, nullptr) != hipSuccess)
-    return fail(HSRANS_E_HIP);
+  uint32_t *d_offsets = (uint32_t *)(scratch + kAssemblyOffsets);
+  pass.walk_count = (uint32_t *)(scratch + kAssemblyCount);
+  pass.walk_blocks = (uint64_t *)(scratch + kAssemblyOffsets + up16(2 * (size_t)max_blocks * 4));
+  pass.walk_states = (uint32_t *)((uint8_t *)pass.walk_blocks + pbytes.blk);
+  pass.max_blocks = (uint32_t)max_blocks;
+  const bool passed = launch_recording_pass(ctx, d->d_plan, d->d_status, h, d_stream, stream_length, d_out, out_capacity, index_interval, nullptr, 0, pass, s) == hipSuccess;
 
-  if (ctx->tuning.index_assemble_on_host)
+  if (passed && ctx->tuning.index_assemble_on_host)
   {
     uint32_t n_blocks = 0;
-    if (!grow_pinned(&ctx->h_pin, &ctx->h_pin_cap, st_bytes + wd_bytes + blk_bytes + bst_bytes) ||
-        hipMemcpyAsync(&n_blocks, d_walk_count, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return fail(HSRANS_E_HIP);
-    if (status != 0)
-      return fail(device_error());
-    if (n_blocks == 0 || n_blocks > max_blocks)
-      return fail(HSRANS_E_FORMAT);
-    uint32_t *ck_states = (uint32_t *)ctx->h_pin, *bstates = (uint32_t *)(ctx->h_pin + st_bytes + wd_bytes + blk_bytes);
-    uint64_t *ck_words = (uint64_t *)(ctx->h_pin + st_bytes), *blocks = (uint64_t *)(ctx->h_pin + st_bytes + wd_bytes);
-    if (hipMemcpyAsync(ck_states, kp.ckpt_states, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(ck_words, kp.ckpt_words, wd_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(blocks, d_walk_blocks, (size_t)n_blocks * 24, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(bstates, d_walk_states, (size_t)n_blocks * S * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return fail(HSRANS_E_HIP);
+    const int rc = grow_pinned(&ctx->h_pin, &ctx->h_pin_cap, pbytes.all()) ? download_walk_records(pass, pbytes, S, d->d_status, ctx->h_pin, ctx->h_pin + pbytes.st + pbytes.wd, &n_blocks, s) : HSRANS_E_HIP;
+    if (rc != HSRANS_OK)
+      (void)hipStreamSynchronize(s), (void)hipGetLastError(); // (nothing queued here may still be running when the call returns, whatever failed)
     hsrans_dplan_destroy(nd); // (it only lent its arena to the walk's records)
+    if (rc != HSRANS_OK)
+      return rc;
     PlanBuilder pb;
     pb.begin((int)h.container, (int)S, h.bits, h.decoded_len, h.stream_len);
     pb.reserve((size_t)n_blocks + n_ck);
     pb.hdr.interval = index_interval;
-    if (!walk_index_chains(pb, S, h.decoded_len, index_interval, n_blocks, blocks, bstates, ck_states, ck_words))
+    if (!add_walk_chains(pb, pbytes, ctx->h_pin, ctx->h_pin + pbytes.st + pbytes.wd, n_blocks, index_interval))
       return HSRANS_E_FORMAT;
     std::vector<uint8_t> plan(pb.serialized_size());
     const size_t plan_bytes = pb.serialize(plan.data(), plan.size());
@@ -416,11 +419,11 @@ static int decode_walk_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
 
   WalkIndexArgs wa{};
   wa.base = d->d_plan;
-  wa.walk_count = d_walk_count;
-  wa.walk_blocks = d_walk_blocks;
-  wa.walk_states = d_walk_states;
-  wa.ck_states = kp.ckpt_states;
-  wa.ck_words = kp.ckpt_words;
+  wa.walk_count = pass.walk_count;
+  wa.walk_blocks = pass.walk_blocks;
+  wa.walk_states = pass.walk_states;
+  wa.ck_states = pass.ck_states;
+  wa.ck_words = pass.ck_words;
   wa.S = S;
   wa.interval = index_interval;
   wa.max_blocks = (uint32_t)max_blocks;
@@ -429,29 +432,17 @@ static int decode_walk_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
   wa.parts_want = kGroupPartsPerCU * ctx->geom.num_cus;
   wa.decoded_len = h.decoded_len;
   wa.stream_len = h.stream_len;
-  wa.chain_off = (uint32_t *)(scratch + 256);
-  wa.group_off = wa.chain_off + max_blocks;
-  wa.result = d_result;
+  wa.chain_off = d_offsets;
+  wa.group_off = d_offsets + max_blocks;
+  wa.result = (IndexResult *)scratch;
   wa.plan = nd->d_plan;
   wa.groups = (Group *)nd->d_groups;
-  uint64_t res[9] = {}; // WalkIndexArgs::result
-  if (launch_index_assemble_walk(wa, s) != hipSuccess || hipMemcpyAsync(res, d_result, sizeof(res), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return fail(HSRANS_E_HIP);
-  if (status != 0)
-    return fail(device_error());
-  if (res[6] != 0 || res[0] == 0 || res[0] > max_chains || res[5] > max_groups) // the block list overflowed, a tail behind a single-symbol block, no room
-    return fail(HSRANS_E_FORMAT);
-  PlanHeader hn = h;
-  hn.flags = 0;
-  hn.n_chains = hn.n_pieces = (uint32_t)res[0];
-  hn.interval = index_interval;
-  hn.shared_hist = res[1] == 1 ? 1 : 0;
-  hn.aux_off = hn.shared_hist ? res[2] : 0;
-  dplan_adopt(nd, hn, res[8] != 0 ? (uint32_t)res[5] : 0, res[3], s);
+  IndexResult res{};
+  const int rc = finish_assembly(d, nd, passed && launch_index_assemble_walk(wa, s) == hipSuccess, wa.result, index_interval, 1, (uint32_t)max_chains, (uint32_t)max_groups, s, &res);
+  if (rc != HSRANS_OK)
+    return rc;
   if (ctx->tuning.indexing_trace)
-    fprintf(stderr, "hsrans_decode_device_indexing: block_ on the device: %llu blocks, %llu chains, %llu groups, %zu plan bytes\n", (unsigned long long)res[4],
-            (unsigned long long)res[0], (unsigned long long)res[5], nd->plan_bytes);
+    fprintf(stderr, "hsrans_decode_device_indexing: block_ on the device: %u blocks, %u chains, %u groups, %zu plan bytes\n", res.blocks, res.chains, res.groups, nd->plan_bytes);
   *indexed = nd;
   return HSRANS_OK;
 }
@@ -497,143 +488,75 @@ try
   const auto t0 = now();
   const uint32_t S = h.states;
   const uint64_t n_ck = h.decoded_len / S / index_interval + 2;
+  std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer and the staging belong to the context)
+  if (!have_lock)
+    guard.lock();
+  const PassBytes pbytes = pass_bytes(n_ck, S, 0);
+  PassBuffers pass{};
+  if (!context_checkpoints(ctx, pbytes, &pass))
+    return HSRANS_E_HIP;
+  const uint32_t max_chains = (uint32_t)std::min<uint64_t>((uint64_t)h.n_chains + n_ck, 0xFFFFFFF0u);
   // mt_ streams (one single-piece chain per block, histograms in the stream): the indexed plan is assembled ON THE DEVICE behind the
-  // recording pass — one allocation, three launches, one synchronisation; nothing but two words comes back to the host
-  // (HSRANS_INDEX_ASSEMBLE_ON_HOST=1: round 3's path — checkpoints down, blob built by one core, blob up — still what raw plans take)
+  // recording pass — one allocation, three launches, one synchronisation; nothing but an IndexResult comes back to the host
+  // (HSRANS_INDEX_ASSEMBLE_ON_HOST=1: checkpoints down, blob built by one core, blob up — still what raw plans take)
   if (h.container == HSRANS_MT && (h.flags & (kPlanWalk | kPlanHasHist | kPlanMergeable)) == 0 && !ctx->tuning.index_assemble_on_host)
   {
-    std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer belongs to the context)
-    if (!have_lock)
-      guard.lock();
-    const uint64_t max_chains64 = std::min<uint64_t>((uint64_t)h.n_chains + n_ck, 0xFFFFFFF0u);
-    const uint32_t max_chains = (uint32_t)max_chains64;
-    const size_t st_bytes = (size_t)n_ck * S * 4, wd_bytes = (size_t)n_ck * 8;
-    if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, st_bytes + wd_bytes))
-      return HSRANS_E_HIP;
     const uint32_t nb = h.n_chains;
     // few large blocks: every block's chains in parts (at most 64 parts a block), as dplan_fill
     const uint32_t group_split = group_parts_of((uint32_t)std::min<uint64_t>(n_ck / nb + 1, 0xFFFFFFFFu), std::min(group_parts_max(ctx->geom, nb), 64u));
-    hsrans_dplan *nd = dplan_new(ctx);
+    uint8_t *scratch = nullptr;
+    hsrans_dplan *nd = assembly_plan(ctx, S, max_chains, (size_t)nb * group_split, nb, 0, s, &scratch);
     if (nd == nullptr)
       return HSRANS_E_HIP;
-    DplanRegions r;
-    r.counters = true;
-    r.plan = (size_t)plan_size(max_chains, max_chains, S, 0);
-    r.groups = (size_t)nb * group_split * sizeof(Group);
-    r.scratch = 256 + (size_t)nb * 4; // the assembly's result words, then its chain offsets
-    r.zero = kZeroAll;
-    uint8_t *scratch = nullptr;
-    if (dplan_arena(nd, r, s, &scratch) != HSRANS_OK)
-    {
-      hsrans_dplan_destroy(nd);
-      return HSRANS_E_HIP;
-    }
-    uint64_t *d_result = (uint64_t *)scratch;
-    uint32_t *d_chain_off = (uint32_t *)(scratch + 256);
-    KParams kp{};
-    kp.stream = (const uint8_t *)d_stream;
-    kp.stream_len = stream_length;
-    kp.out = (uint8_t *)d_out;
-    kp.out_cap = out_capacity;
-    kp.plan = d->d_plan;
-    kp.status = d->d_status;
-    kp.ckpt_states = (uint32_t *)ctx->d_enc_ck;
-    kp.ckpt_words = (uint64_t *)(ctx->d_enc_ck + st_bytes);
-    kp.ckpt_interval = index_interval;
-    PlanHeader hl = h;
-    hl.shared_hist = 0; // private tables, as in hsrans_index_build's pass
     IndexArgs ia{};
     ia.base = d->d_plan;
     ia.n_base = nb;
     ia.S = S;
     ia.interval = index_interval;
-    ia.ck_states = kp.ckpt_states;
-    ia.ck_words = kp.ckpt_words;
-    ia.chain_off = d_chain_off;
-    ia.result = d_result;
+    ia.ck_states = pass.ck_states;
+    ia.ck_words = pass.ck_words;
+    ia.chain_off = (uint32_t *)(scratch + kAssemblyOffsets);
+    ia.result = (IndexResult *)scratch;
     ia.plan = nd->d_plan;
     ia.max_chains = max_chains;
     ia.groups = (Group *)nd->d_groups;
     ia.group_split = group_split;
     ia.stream_len = h.stream_len;
-    uint32_t status = 0xFFFFFFFF;
-    uint64_t counted[4] = {}; // chains in all, blocks with a histogram, the (one) histogram's offset, fewest chains of a coded block but the last
-    const uint64_t &total = counted[0];
-    const bool ok = launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr) == hipSuccess &&
-                    launch_index_assemble(ia, s) == hipSuccess && hipMemcpyAsync(counted, d_result, sizeof(counted), hipMemcpyDeviceToHost, s) == hipSuccess &&
-                    hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
-    const bool synced = hipStreamSynchronize(s) == hipSuccess; // (nothing queued above may still be running when this returns, whatever failed)
-    int rc = ok && synced ? HSRANS_OK : HSRANS_E_HIP;
-    if (rc == HSRANS_OK && status != 0) // the pass found a bad histogram / header: reported and cleared like hsrans_dplan_status does
-      rc = hipMemsetAsync(d->d_status, 0, 4, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? HSRANS_E_DEVICE : HSRANS_E_HIP;
-    if (rc == HSRANS_OK && (total < nb || total > max_chains))
-      rc = HSRANS_E_FORMAT;
+    const bool queued = launch_recording_pass(ctx, d->d_plan, d->d_status, h, d_stream, stream_length, d_out, out_capacity, index_interval, nullptr, 0, pass, s) == hipSuccess &&
+                        launch_index_assemble(ia, s) == hipSuccess;
+    IndexResult res{};
+    const int rc = finish_assembly(d, nd, queued, ia.result, index_interval, nb, max_chains, nb * group_split, s, &res);
     if (rc != HSRANS_OK)
-    {
-      (void)hipGetLastError();
-      hsrans_dplan_destroy(nd);
       return rc;
-    }
-    PlanHeader hn = h;
-    hn.n_chains = hn.n_pieces = (uint32_t)total;
-    hn.interval = index_interval;
-    hn.shared_hist = counted[1] == 1 ? 1 : 0;
-    hn.aux_off = hn.shared_hist ? counted[2] : 0;
-    // (total == nb: no checkpoint fell inside any block — one chain per block, the ungrouped launch; counted[3]: ~(the fewest chains of a
-    // coded block that is not the last), 0 = there is none)
-    dplan_adopt(nd, hn, total > nb ? nb * group_split : 0, counted[3] == 0 ? ~0ull : ~counted[3], s);
     if (trace)
-      fprintf(stderr, "hsrans_decode_device_indexing: on the device: %.3f ms in all (%llu chains, %zu plan bytes)\n", ms(t0, now()), (unsigned long long)total, nd->plan_bytes);
+      fprintf(stderr, "hsrans_decode_device_indexing: on the device: %.3f ms in all (%u chains, %zu plan bytes)\n", ms(t0, now()), res.chains, nd->plan_bytes);
     *indexed = nd;
     return HSRANS_OK;
   }
   // page-locked staging (kept by the context): [checkpoint states | cursors | base plan] down, then the new plan blob up —
   // from pageable memory these copies (12.5 MB of states each way for 100 MB at 32 groups) took 15 ms, the decode 0.25
-  std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock);
-  if (!have_lock)
-    guard.lock();
-  const size_t st_bytes = (size_t)n_ck * S * 4, wd_bytes = (size_t)n_ck * 8, base_bytes = (d->plan_bytes + 15) / 16 * 16;
-  const size_t new_cap = (size_t)plan_size((uint32_t)std::min<uint64_t>(h.n_chains + n_ck, 0xFFFFFFF0u), (uint32_t)std::min<uint64_t>(h.n_chains + n_ck, 0xFFFFFFF0u), S, kPlanHasHist);
-  if (!grow_pinned(&ctx->h_pin, &ctx->h_pin_cap, st_bytes + wd_bytes + base_bytes + new_cap))
+  const size_t base_bytes = up16(d->plan_bytes);
+  const size_t new_cap = (size_t)plan_size(max_chains, max_chains, S, kPlanHasHist);
+  if (!grow_pinned(&ctx->h_pin, &ctx->h_pin_cap, pbytes.all() + base_bytes + new_cap))
     return HSRANS_E_HIP;
   uint32_t *ck_states = (uint32_t *)ctx->h_pin;
-  uint64_t *ck_words = (uint64_t *)(ctx->h_pin + st_bytes);
-  uint8_t *base = ctx->h_pin + st_bytes + wd_bytes;
+  uint64_t *ck_words = (uint64_t *)(ctx->h_pin + pbytes.st);
+  uint8_t *base = ctx->h_pin + pbytes.all();
   uint8_t *plan = base + base_bytes;
   size_t plan_bytes = 0;
-  // (the checkpoints land in the context's checkpoint buffer — the GPU encoder's, kept and grown — not in fresh allocations)
-  if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, st_bytes + wd_bytes))
-    return HSRANS_E_HIP;
-  uint32_t *d_ck_states = (uint32_t *)ctx->d_enc_ck;
-  uint64_t *d_ck_words = (uint64_t *)(ctx->d_enc_ck + st_bytes);
   int rc = HSRANS_E_HIP;
   do
   {
-    KParams kp{};
-    kp.stream = (const uint8_t *)d_stream;
-    kp.stream_len = stream_length;
-    kp.out = (uint8_t *)d_out;
-    kp.out_cap = out_capacity;
-    kp.plan = d->d_plan;
-    kp.status = d->d_status;
-    kp.ckpt_states = d_ck_states;
-    kp.ckpt_words = d_ck_words;
-    kp.ckpt_interval = index_interval;
-    PlanHeader hl = h;
-    hl.shared_hist = 0; // private tables, as in hsrans_index_build's pass
     uint32_t status = 0xFFFFFFFF;
-    if (launch_decode(ctx->tuning, kp, hl, ctx->geom, s, nullptr) != hipSuccess ||
+    if (launch_recording_pass(ctx, d->d_plan, d->d_status, h, d_stream, stream_length, d_out, out_capacity, index_interval, nullptr, 0, pass, s) != hipSuccess ||
         hipMemcpyAsync(base, d->d_plan, d->plan_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(ck_states, d_ck_states, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(ck_words, d_ck_words, wd_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(ck_states, pass.ck_states, pbytes.st, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(ck_words, pass.ck_words, pbytes.wd, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
       break;
     const auto t1 = now();
-    if (status != 0) // the pass found a bad histogram / header: reported and cleared like hsrans_dplan_status does
-    {
-      rc = hipMemsetAsync(d->d_status, 0, 4, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? HSRANS_E_DEVICE : HSRANS_E_HIP;
+    if ((rc = pass_status_rc(status, d->d_status, s)) != HSRANS_OK)
       break;
-    }
     PlanHeader hb;
     if (!read_header(base, d->plan_bytes, &hb) || hb.n_chains != h.n_chains || hb.n_pieces != h.n_pieces || hb.states != h.states ||
         !plan_validate(base, d->plan_bytes, h.stream_len, h.decoded_len))
@@ -651,8 +574,7 @@ try
       memcpy(counts, base + plan_hist_off(hb.n_chains, hb.n_pieces, hb.states), 512);
       pb.set_hist(counts);
     }
-    add_interval_chains(pb, hb, (const uint32_t *)(base + plan_chain_first_off()), (const Piece *)(base + plan_pieces_off(hb.n_chains)),
-                        (const uint32_t *)(base + plan_states_off(hb.n_chains, hb.n_pieces)), index_interval, ck_states, ck_words);
+    add_interval_chains(pb, source_of_plan(base, hb), index_interval, ck_states, ck_words);
     const auto t2 = now();
     plan_bytes = pb.serialize(plan, new_cap);
     rc = plan_bytes == 0 ? HSRANS_E_FORMAT : HSRANS_OK;

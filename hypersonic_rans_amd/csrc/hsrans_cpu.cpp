@@ -719,40 +719,7 @@ size_t index_build(int level, uint32_t threads, int container, int states, uint3
     memcpy(counts, in + pc0[0].hist_off, 512);
     pb.set_hist(counts);
   }
-  size_t k = 0;
-  for (uint32_t ch = 0; ch < h.n_chains; ch++)
-  {
-    const Piece &bp = pc0[cf0[ch]];
-    if (bp.flags & kPieceFill)
-    {
-      pb.add_chain(bp, nullptr);
-      continue;
-    }
-    const uint64_t T = bp.steps, g0 = bp.out_off / S;
-    while (k < n_groups && groups[k] <= g0)
-      k++;
-    uint64_t g = 0;
-    const uint32_t *st = st0 + (size_t)bp.state_idx * S;
-    uint64_t words = bp.words_off;
-    while (true)
-    {
-      const bool more = k < n_groups && groups[k] < g0 + T;
-      const uint64_t g_next = more ? groups[k] - g0 : T;
-      Piece p{};
-      p.hist_off = bp.hist_off;
-      p.out_off = bp.out_off + g * S;
-      p.words_off = words;
-      p.steps = (uint32_t)(g_next - g);
-      p.tail = (uint16_t)(more ? 0 : bp.tail);
-      pb.add_chain(p, st);
-      if (!more)
-        break;
-      st = &ck_states[k * S];
-      words = ck_words[k];
-      g = g_next;
-      k++;
-    }
-  }
+  add_group_chains(pb, h, cf0, pc0, st0, groups, n_groups, ck_states.data(), ck_words.data());
   return pb.serialize(plan_out, plan_cap);
 }
 

@@ -10,6 +10,7 @@
 //            next header = &state[0] + 2*(skip+1) bytes                                  (mt_rANS32x64_16w_encode.cpp:266-298)
 #include "hsrans_host.h"
 #include "hsrans_index_groups.h"
+#include "hsrans_kernels.h"
 
 #include <math.h>
 #include <string.h>
@@ -882,6 +883,44 @@ void PlanBuilder::add_piece(const Piece &p)
   Piece q = p;
   q.flags &= (uint16_t)~kPieceChainStart;
   pieces.push_back(q);
+}
+
+// The chains of a raw / mt_ base plan (header h, tables cf0 / pc0 / st0: one single-piece chain per block) cut at the explicit ascending
+// `groups`, given what a recording decode left there: checkpoint k = {ck_states[k * S ..], ck_words[k]} at absolute group groups[k].  A group
+// on a block's first group adds no chain.
+void add_group_chains(PlanBuilder &pb, const PlanHeader &h, const uint32_t *cf0, const Piece *pc0, const uint32_t *st0, const uint64_t *groups, size_t n_groups,
+                      const uint32_t *ck_states, const uint64_t *ck_words)
+{
+  const uint32_t S = h.states;
+  size_t k = 0; // next boundary
+  for (uint32_t ch = 0; ch < h.n_chains; ch++)
+  {
+    const Piece &bp = pc0[cf0[ch]];
+    const IndexBlock blk = index_block_of_piece(bp, S, ch + 1 == h.n_chains);
+    if (blk.fill)
+    {
+      pb.add_chain(index_sub_piece(blk, S, 0, blk.T, blk.words_off, 0), nullptr);
+      continue;
+    }
+    const uint64_t g0 = blk.g0;
+    while (k < n_groups && groups[k] <= g0)
+      k++;
+    uint64_t g = 0; // groups of this block already assigned to chains
+    const uint32_t *st = st0 + (size_t)bp.state_idx * S;
+    uint64_t words = blk.words_off;
+    while (true)
+    {
+      const bool more = k < n_groups && groups[k] < g0 + blk.T;
+      const uint64_t g_next = more ? groups[k] - g0 : blk.T;
+      pb.add_chain(index_sub_piece(blk, S, g, g_next - g, words, 0), st);
+      if (!more)
+        break;
+      st = &ck_states[k * S];
+      words = ck_words[k];
+      g = g_next;
+      k++;
+    }
+  }
 }
 
 void PlanBuilder::set_hist(const uint16_t counts[256])

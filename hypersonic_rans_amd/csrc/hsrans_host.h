@@ -97,6 +97,10 @@ struct PlanBuilder
   size_t serialize(uint8_t *out, size_t cap); // fills shared_hist / aux_off, returns bytes or 0
 };
 
+// the chains of a raw / mt_ base plan cut at explicit ascending groups (checkpoint k of a recording decode: ck_states[k * S ..], ck_words[k])
+void add_group_chains(PlanBuilder &pb, const PlanHeader &h, const uint32_t *cf0, const Piece *pc0, const uint32_t *st0, const uint64_t *groups, size_t n_groups,
+                      const uint32_t *ck_states, const uint64_t *ck_words);
+
 // plan derived from the stream alone (mirrors the control flow of the reference decoders; see hsrans_host.cpp)
 size_t plan_build(int container, int states, uint32_t bits, const uint8_t *stream, size_t stream_len, size_t out_cap, uint8_t *plan_out, size_t plan_cap);
 bool plan_build_vec(int container, int states, uint32_t bits, const uint8_t *stream, size_t stream_len, size_t out_cap, std::vector<uint8_t> *plan);

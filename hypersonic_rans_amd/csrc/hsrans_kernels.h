@@ -368,6 +368,112 @@ __host__ __device__ inline uint32_t group_parts_max_of(uint64_t want, uint64_t n
   return n_groups != 0 && n_groups < want ? (uint32_t)((want + n_groups - 1) / n_groups) : 1;
 }
 
+// ---- the chains of an indexed plan: a block of T groups gets one chain per checkpoint -----------------------------------------------
+// One rule for the host (hsrans_index_build, hsrans_decode_device_indexing's host assembly, cpu::index_build) and for the device
+// (k_index_fill, k_walk_index_fill).  A block as the rule sees it:
+struct IndexBlock
+{
+  uint64_t hist_off;  // its histogram in the stream; a single-symbol block: the symbol
+  uint64_t words_off; // the read cursor at its first group
+  uint64_t out_off;   // its first output byte
+  uint64_t g0;        // ... as a group of the file (out_off / S)
+  uint64_t fill_len;  // a single-symbol block: its bytes
+  uint64_t T;         // whole groups it decodes
+  uint32_t tail;      // symbols of the masked group behind them
+  bool fill, last;    // a single-symbol block; the plan's last block
+};
+// ... from a base plan's piece (raw, mt_: one single-piece chain per block)
+__host__ __device__ inline IndexBlock index_block_of_piece(const Piece &bp, uint32_t S, bool last)
+{
+  IndexBlock b{};
+  b.hist_off = bp.hist_off;
+  b.words_off = bp.words_off;
+  b.out_off = bp.out_off;
+  b.g0 = bp.out_off / S;
+  b.fill_len = bp.fill_len;
+  b.T = bp.steps;
+  b.tail = bp.tail;
+  b.fill = (bp.flags & kPieceFill) != 0;
+  b.last = last;
+  return b;
+}
+// ... from a record of the walk over a block_ stream {header position, output offset, header word}: a coded block stops at the file's last
+// whole group (block_rANS32x64_16w_decode.cpp:82-88), and the file's tail belongs to the last block
+__host__ __device__ inline IndexBlock index_block_of_walk(uint64_t pos, uint64_t at, uint64_t hdr, uint64_t decoded_len, uint32_t S, bool last)
+{
+  IndexBlock b{};
+  b.out_off = at;
+  b.g0 = at / S;
+  b.fill = (hdr >> 63) != 0;
+  b.last = last;
+  if (b.fill)
+  {
+    b.hist_off = (hdr >> 54) & 0xFF;
+    b.fill_len = hdr & (((uint64_t)1 << 54) - 1);
+    return b;
+  }
+  b.hist_off = pos + 8;
+  b.words_off = pos + 8 + 512;
+  const uint64_t whole_file = decoded_len / S, e = (at + hdr + S - 1) / S, g1 = e < whole_file ? e : whole_file;
+  b.T = g1 > b.g0 ? g1 - b.g0 : 0;
+  b.tail = last ? (uint32_t)(decoded_len - whole_file * S) : 0;
+  return b;
+}
+// a tail behind a trailing single-symbol block has no histogram: no plan
+__host__ __device__ inline bool index_block_ends_short(const IndexBlock &b, uint64_t decoded_len) { return b.last && b.fill && b.out_off + b.fill_len < decoded_len; }
+// its chains with a checkpoint every `interval` groups: group 0, interval, ... < T; at least group 0
+__host__ __device__ inline uint32_t index_block_chains(const IndexBlock &b, uint32_t interval)
+{
+  return b.fill || b.T == 0 ? 1 : (uint32_t)((b.T + interval - 1) / interval);
+}
+// the checkpoint slot of its chain k: absolute group / interval, the group being g0 + k * interval
+__host__ __device__ inline uint64_t index_chain_slot(const IndexBlock &b, uint32_t interval, uint64_t k) { return b.g0 / interval + k; }
+// groups [g, g + steps) of the block as the one piece of chain `chain` of a plan, reading from words_off; the tail rides on the piece that
+// ends the block
+__host__ __device__ inline Piece index_sub_piece(const IndexBlock &b, uint32_t S, uint64_t g, uint64_t steps, uint64_t words_off, uint32_t chain)
+{
+  Piece p{};
+  p.hist_off = b.hist_off;
+  p.out_off = b.out_off + g * S;
+  p.words_off = words_off;
+  p.fill_len = b.fill_len;
+  p.steps = (uint32_t)steps;
+  p.tail = (uint16_t)(g + steps >= b.T ? b.tail : 0);
+  p.flags = (uint16_t)(kPieceChainStart | (b.fill ? kPieceFill : 0));
+  p.state_idx = chain;
+  return p;
+}
+// the piece of its chain k, chain `chain` of the plan (ck_words[slot]: the read cursor a recording pass left at the checkpoint)
+__host__ __device__ inline Piece index_chain_piece(const IndexBlock &b, uint32_t S, uint32_t interval, uint32_t k, const uint64_t *ck_words, uint32_t chain)
+{
+  const uint64_t g = b.fill ? 0 : (uint64_t)k * interval, left = b.T - g; // (a single-symbol block: its one chain is the whole block)
+  uint64_t words_off = b.words_off;
+  if (g != 0)
+    words_off = ck_words[index_chain_slot(b, interval, k)];
+  return index_sub_piece(b, S, g, b.fill || left < interval ? left : interval, words_off, chain);
+}
+// the S states chain k starts from: those the block is entered with, or the checkpoint's (ck_states[slot * S]); null: none (a fill, zeros)
+__host__ __device__ inline const uint32_t *index_chain_states(const IndexBlock &b, uint32_t S, uint32_t interval, uint32_t k, const uint32_t *entry, const uint32_t *ck_states)
+{
+  return b.fill ? nullptr : k == 0 ? entry : ck_states + index_chain_slot(b, interval, k) * S;
+}
+// part `part` of `parts` of its `count` chains as a group of its own: chains [lo, hi), words up to the next part's first cursor (the last
+// part: block_words_end)
+struct IndexPart
+{
+  uint32_t lo, hi;
+  uint64_t words_end;
+};
+__host__ __device__ inline IndexPart index_block_part(const IndexBlock &b, uint32_t interval, uint32_t count, uint32_t part, uint32_t parts, const uint64_t *ck_words,
+                                                      uint64_t block_words_end)
+{
+  IndexPart r;
+  r.lo = (uint32_t)((uint64_t)count * part / parts);
+  r.hi = (uint32_t)((uint64_t)count * (part + 1) / parts);
+  r.words_end = r.hi < count ? ck_words[index_chain_slot(b, interval, r.hi)] : block_words_end;
+  return r;
+}
+
 // k_decode_spread (kernels_spread.h): G = two 16-wave workgroups per CU; workgroup b's share of the plan's N chains starts at
 // spread_share_begin(b): the first half of the grid weighs w1 per workgroup, the second half w2 (the sums of their waves' age-class
 // weights).  A share's piece records are kept in LDS: at most kSpreadMaxShare chains.
@@ -381,6 +487,20 @@ __host__ __device__ inline uint32_t spread_share_begin(uint32_t n_chains, uint32
   return (uint32_t)((uint64_t)n_chains * cum / total);
 }
 
+// what the count kernels leave for the fill kernels and the host (in the new plan's arena: zeroed)
+constexpr uint32_t kIndexNoFewest = 0xFFFFFFFFu;
+struct IndexResult
+{
+  uint32_t chains;   // chains of the new plan
+  uint32_t blocks;   // blocks they come from
+  uint32_t coded;    // ... of them with a histogram: exactly one, and the plan's chains share its table (PlanBuilder::serialize)
+  uint32_t fewest;   // fewest chains of a coded inner block (k_decode_spread's condition), kIndexNoFewest: there is none.  mt_: inner = not the
+                     // last block; block_: neither the first nor the last coded block (as dplan_fill has it)
+  uint64_t hist_off; // the last coded block's histogram
+  uint32_t groups;   // groups of the grouped launch; 0: one chain per wave, no group list
+  uint32_t parts;    // block_: parts a group is cut into at most
+  uint32_t error;    // 0, or why there is no plan (1: the walk's block list, 2: a tail behind a single-symbol block, 3: more chains / groups than there is room for)
+};
 struct IndexArgs
 {
   const uint8_t *base;       // base plan blob (device): one single-piece chain per mt_ block
@@ -389,7 +509,7 @@ struct IndexArgs
   const uint32_t *ck_states; // [slot * S]: coder states at absolute group slot * interval
   const uint64_t *ck_words;  // [slot]: absolute stream byte of the read cursor there
   uint32_t *chain_off;       // [n_base] first chain of block b in the new plan (k_index_count)
-  uint64_t *result;          // [0] chains of the new plan
+  IndexResult *result;
   uint8_t *plan;             // the new plan blob (zeroed, sized for max_chains)
   uint32_t max_chains;
   Group *groups;             // [n_base * group_split] or null
@@ -413,10 +533,7 @@ struct WalkIndexArgs
   uint64_t decoded_len, stream_len;
   uint32_t *chain_off;         // [max_blocks] first chain of block b in the new plan (k_walk_index_count)
   uint32_t *group_off;         // [max_blocks] first group of block b
-  // [0] chains, [1] coded blocks, [2] the last one's histogram offset, [3] fewest chains of a coded block that is neither the first nor the
-  // last (0xFFFFFFFF: none), [4] blocks, [5] groups, [6] 0 or why there is no plan (1: block list, 2: tail behind a single-symbol block,
-  // 3: more chains / groups than there is room for), [7] parts a group is cut into at most, [8] 1: grouped launch (fewer groups than chains)
-  uint64_t *result;
+  IndexResult *result;
   uint8_t *plan;               // the new plan blob (zeroed, sized for max_chains)
   Group *groups;               // [max_groups], zeroed
 };

@@ -158,19 +158,12 @@ __global__ void __launch_bounds__(64) k_mt_fill(const uint8_t *in, uint64_t in_l
 // The indexed plan of a stream whose first decode has just recorded its checkpoints (hsrans_decode_device_indexing), assembled
 // ON THE DEVICE: the base plan (one single-piece chain per mt_ block), the states and read cursors the recording pass left every
 // `interval` groups (slot = absolute group / interval) -> the plan with one chain per block start and per checkpoint inside the
-// blocks, byte for byte what the host writes for the same input (hsrans_capi.cpp add_interval_chains + PlanBuilder::serialize),
-// plus the Group records of the grouped launch.  (Round 3 brought 7.5-15 MB of checkpoints down to the host, assembled the blob
-// on one core and sent it up again: 0.8 ms of the first decode's 1.3-2.5 ms.)
-//   k_index_count   one workgroup: chains per block, their exclusive scan -> chain_off[], total -> result[0]
+// blocks, plus the Group records of the grouped launch.  The chains of a block are the host's own rule (IndexBlock, hsrans_kernels.h).
+// (Round 3 brought 7.5-15 MB of checkpoints down to the host, assembled the blob on one core and sent it up again: 0.8 ms of the
+// first decode's 1.3-2.5 ms.)
+//   k_index_count   one workgroup: chains per block, their exclusive scan -> chain_off[], the totals and header facts -> *result
 //   k_index_fill    one wavefront per block: header, chain table, pieces, start states, groups
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t index_chains_of(const Piece &bp, uint32_t interval)
-{
-  if (bp.flags & kPieceFill)
-    return 1;
-  return bp.steps == 0 ? 1 : (bp.steps + interval - 1) / interval; // (add_interval_chains: g = 0, interval, ... < steps; at least g = 0)
-}
-
 // One value per thread of a 1024-thread workgroup -> its exclusive prefix, continued from call to call through *carry (LDS: zeroed by the
 // caller, one barrier before the first call; the running total afterwards).  Every thread of the workgroup calls it.
 __device__ __forceinline__ uint32_t wg_scan_1024(uint32_t v, uint32_t *wave_tot, uint32_t *carry)
@@ -196,14 +189,71 @@ __device__ __forceinline__ uint32_t wg_scan_1024(uint32_t v, uint32_t *wave_tot,
   return before + incl - v;
 }
 
+// what one wavefront writes for a block both ways: the new plan's header (the base plan's container, states, bits and lengths), ...
+__device__ __forceinline__ void index_write_header(const uint8_t *base, uint8_t *plan, const IndexResult &r, uint32_t interval)
+{
+  const PlanHeader &hb = *(const PlanHeader *)base;
+  PlanHeader h{}; // (flags: none)
+  for (int i = 0; i < 8; i++)
+    h.magic[i] = hb.magic[i];
+  h.container = hb.container;
+  h.states = hb.states;
+  h.bits = hb.bits;
+  h.decoded_len = hb.decoded_len;
+  h.stream_len = hb.stream_len;
+  h.n_chains = h.n_pieces = r.chains;
+  h.interval = interval;
+  h.shared_hist = r.coded == 1 ? 1 : 0; // (plans K2 wrote leave these two clear even for a single block)
+  h.aux_off = h.shared_hist ? r.hist_off : 0;
+  *(PlanHeader *)plan = h;
+  ((uint32_t *)(plan + plan_chain_first_off()))[r.chains] = r.chains;
+}
+// ... and the block's `count` chains from chain c0 on: chain table, pieces, start states (entry: those the block is entered with)
+__device__ __forceinline__ void index_write_chains(const IndexBlock &blk, uint32_t S, uint32_t interval, uint32_t c0, uint32_t count, const uint32_t *entry,
+                                                   const uint32_t *ck_states, const uint64_t *ck_words, uint8_t *plan, uint32_t nc)
+{
+  const uint32_t lane = threadIdx.x;
+  uint32_t *chain_first = (uint32_t *)(plan + plan_chain_first_off());
+  Piece *pieces = (Piece *)(plan + plan_pieces_off(nc));
+  uint32_t *states = (uint32_t *)(plan + plan_states_off(nc, nc));
+  for (uint32_t k = lane; k < count; k += 64)
+  {
+    pieces[c0 + k] = index_chain_piece(blk, S, interval, k, ck_words, c0 + k);
+    chain_first[c0 + k] = c0 + k;
+  }
+  for (uint32_t k = 0; k < count; k++)
+    if (lane < S)
+    {
+      const uint32_t *st = index_chain_states(blk, S, interval, k, entry, ck_states);
+      states[(uint64_t)(c0 + k) * S + lane] = st ? st[lane] : 0;
+    }
+}
+// chains [begin, begin + count) as a group
+__device__ __forceinline__ Group index_group(uint32_t begin, uint32_t count, uint32_t flags, uint64_t hist_off, uint64_t words_end)
+{
+  return Group{begin, count, flags, begin, hist_off, words_end};
+}
+// part `part` of `parts` of a coded block's chains as a group
+__device__ __forceinline__ Group index_part_group(const IndexBlock &blk, uint32_t interval, uint32_t c0, uint32_t count, uint32_t part, uint32_t parts,
+                                                  const uint64_t *ck_words, uint64_t words_end)
+{
+  const IndexPart r = index_block_part(blk, interval, count, part, parts, ck_words, words_end);
+  return index_group(c0 + r.lo, r.hi - r.lo, kGroupMergeable, blk.hist_off, r.words_end);
+}
+
 __global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
 {
   __shared__ uint32_t wave_tot[16];
-  __shared__ uint32_t carry_s;
+  __shared__ uint32_t carry_s, coded_s, fewest_s;
+  __shared__ unsigned long long hist_s;
   const uint32_t *cf0 = (const uint32_t *)(a.base + plan_chain_first_off());
   const Piece *pc0 = (const Piece *)(a.base + plan_pieces_off(a.n_base));
   if (threadIdx.x == 0)
-    carry_s = 0;
+  {
+    carry_s = coded_s = 0;
+    fewest_s = kIndexNoFewest;
+    hist_s = 0;
+  }
   __syncthreads();
   for (uint32_t base = 0; base < a.n_base; base += 1024)
   {
@@ -211,16 +261,14 @@ __global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
     uint32_t v = 0;
     if (ch < a.n_base)
     {
-      const Piece bp = pc0[cf0[ch]];
-      v = index_chains_of(bp, a.interval);
-      if (!(bp.flags & kPieceFill)) // blocks with a histogram: when there is exactly one, the plan's chains share its table
-      {                             // (PlanBuilder::serialize: shared_hist = every non-fill piece has the same hist_off; mt_ blocks never share one)
-        atomicAdd((unsigned long long *)&a.result[1], 1ull);
-        atomicMax((unsigned long long *)&a.result[2], (unsigned long long)bp.hist_off);
-        // [3]: the fewest chains of a coded block that is not the plan's last chain (k_decode_spread's condition); stored as ~min so
-        // that the zeroed word means "none seen" (= any number will do)
-        if (ch + 1 < a.n_base)
-          atomicMax((unsigned long long *)&a.result[3], ~(unsigned long long)v);
+      const IndexBlock blk = index_block_of_piece(pc0[cf0[ch]], a.S, ch + 1 == a.n_base);
+      v = index_block_chains(blk, a.interval);
+      if (!blk.fill) // (mt_ blocks never share a histogram)
+      {
+        atomicAdd(&coded_s, 1u);
+        atomicMax(&hist_s, (unsigned long long)blk.hist_off);
+        if (!blk.last)
+          atomicMin(&fewest_s, v);
       }
     }
     const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
@@ -228,67 +276,36 @@ __global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
       a.chain_off[ch] = off;
   }
   if (threadIdx.x == 0)
-    a.result[0] = carry_s;
+  {
+    IndexResult r{};
+    r.chains = carry_s;
+    r.blocks = a.n_base;
+    r.coded = coded_s;
+    r.fewest = fewest_s;
+    r.hist_off = hist_s;
+    r.groups = r.chains > a.n_base ? a.n_base * a.group_split : 0; // (one chain per block: no checkpoint fell inside any, the ungrouped launch)
+    *a.result = r;
+  }
 }
 
 __global__ void __launch_bounds__(64) k_index_fill(IndexArgs a)
 {
   const uint32_t ch = blockIdx.x, lane = threadIdx.x, S = a.S;
-  const uint32_t nc = (uint32_t)a.result[0];
-  if (nc > a.max_chains) // (the host sized the blob for max_chains: it reads result[0] and fails the call)
+  const IndexResult r = *a.result;
+  if (r.chains > a.max_chains) // (the host sized the blob for max_chains: it reads the result and fails the call)
     return;
   const uint32_t *cf0 = (const uint32_t *)(a.base + plan_chain_first_off());
   const Piece *pc0 = (const Piece *)(a.base + plan_pieces_off(a.n_base));
   const uint32_t *st0 = (const uint32_t *)(a.base + plan_states_off(a.n_base, a.n_base));
-  uint32_t *chain_first = (uint32_t *)(a.plan + plan_chain_first_off());
-  Piece *pieces = (Piece *)(a.plan + plan_pieces_off(nc));
-  uint32_t *states = (uint32_t *)(a.plan + plan_states_off(nc, nc));
   const Piece bp = pc0[cf0[ch]];
-  const bool fill = (bp.flags & kPieceFill) != 0;
-  const uint32_t c0 = a.chain_off[ch], count = index_chains_of(bp, a.interval);
+  const IndexBlock blk = index_block_of_piece(bp, S, ch + 1 == a.n_base);
+  const uint32_t c0 = a.chain_off[ch], count = index_block_chains(blk, a.interval);
   if (ch == 0 && lane == 0)
-  {
-    PlanHeader h = *(const PlanHeader *)a.base; // container, states, bits, lengths: the base plan's
-    h.n_chains = h.n_pieces = nc;
-    h.interval = a.interval;
-    h.shared_hist = a.result[1] == 1 ? 1 : 0; // (plans K2 wrote leave these two clear even for a single block)
-    h.aux_off = h.shared_hist ? a.result[2] : 0;
-    *(PlanHeader *)a.plan = h;
-    chain_first[nc] = nc;
-  }
-  const uint64_t T = bp.steps, g_abs0 = bp.out_off / S;
-  for (uint32_t k = lane; k < count; k += 64)
-  {
-    Piece p{};
-    if (fill)
-      p = bp;
-    else
-    {
-      const uint64_t g = (uint64_t)k * a.interval;
-      const uint64_t slot = (g_abs0 + g) / a.interval;
-      p.hist_off = bp.hist_off;
-      p.out_off = bp.out_off + g * S;
-      p.words_off = k == 0 ? bp.words_off : a.ck_words[slot];
-      const uint64_t steps = T - g < a.interval ? T - g : a.interval;
-      p.steps = (uint32_t)steps;
-      p.tail = (uint16_t)(g + steps == T ? bp.tail : 0);
-    }
-    p.flags |= kPieceChainStart;
-    p.state_idx = c0 + k;
-    pieces[c0 + k] = p;
-    chain_first[c0 + k] = c0 + k;
-  }
-  for (uint32_t k = 0; k < count; k++)
-    if (lane < S)
-    {
-      uint32_t v = 0;
-      if (!fill)
-        v = k == 0 ? st0[(uint64_t)bp.state_idx * S + lane] : a.ck_states[((g_abs0 + (uint64_t)k * a.interval) / a.interval) * S + lane];
-      states[(uint64_t)(c0 + k) * S + lane] = v;
-    }
+    index_write_header(a.base, a.plan, r, a.interval);
+  index_write_chains(blk, S, a.interval, c0, count, st0 + (uint64_t)bp.state_idx * S, a.ck_states, a.ck_words, a.plan, r.chains);
   if (a.groups != nullptr && lane < a.group_split)
   {
-    // the block's words end at the next rANS block's histogram (as hsrans_capi.cpp dplan_fill has it), or at the stream's end
+    // the block's words end at the next rANS block's histogram (as dplan_fill has it), or at the stream's end
     uint64_t words_end = a.stream_len;
     for (uint32_t nx = ch + 1; nx < a.n_base; nx++)
     {
@@ -299,57 +316,27 @@ __global__ void __launch_bounds__(64) k_index_fill(IndexArgs a)
         break;
       }
     }
-    const uint32_t by_size = group_parts_of(count, a.group_split);
-    const uint32_t parts = fill || by_size < 1 ? 1 : by_size;
-    Group g{};
-    g.flags = fill ? kGroupFill : kGroupMergeable;
-    g.hist_off = fill ? 0 : bp.hist_off;
-    if (lane < parts)
-    {
-      const uint32_t lo = (uint32_t)((uint64_t)count * lane / parts), hi = (uint32_t)((uint64_t)count * (lane + 1) / parts);
-      g.begin = c0 + lo;
-      g.piece0 = c0 + lo;
-      g.count = hi - lo;
-      g.words_end = hi < count ? a.ck_words[(g_abs0 + (uint64_t)hi * a.interval) / a.interval] : words_end;
-    }
+    // (padded: group_split slots a block; those behind its parts, and all but the first of a single-symbol block, are empty fills)
+    const uint32_t parts = blk.fill ? 1 : group_parts_of(count, a.group_split);
+    Group *slot = &a.groups[(uint64_t)ch * a.group_split + lane];
+    if (lane < parts && !blk.fill)
+      *slot = index_part_group(blk, a.interval, c0, count, lane, parts, a.ck_words, words_end);
     else
-    {
-      g.begin = c0;
-      g.piece0 = c0;
-      g.count = 0;
-      g.flags = kGroupFill;
-      g.words_end = words_end;
-    }
-    a.groups[(uint64_t)ch * a.group_split + lane] = g;
+      *slot = index_group(c0, lane < parts ? count : 0, kGroupFill, blk.fill ? 0 : blk.hist_off, words_end);
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same for a block_ stream, from the records of the walk that has just decoded it (run_block_walk with ckpt_interval != 0): byte for
-// byte the plan hsrans_index_build(HSRANS_BLOCK) returns (walk_index_chains in hsrans_capi_index.cpp + PlanBuilder::serialize) and the
-// group list dplan_fill derives from that plan — one group per coded block, cut into parts where there are few (group_parts_of), one
-// per run of single-symbol blocks.  The block count is read here, not on the host: the grids are sized by the host's bound.
-//   k_walk_index_count   one workgroup: chains and groups per block, their exclusive scans, the totals and header facts -> result[]
+// The same for a block_ stream, from the records of the walk that has just decoded it (run_block_walk with ckpt_interval != 0): the plan
+// hsrans_index_build(HSRANS_BLOCK) returns and the group list dplan_fill derives from that plan — one group per coded block, cut into
+// parts where there are few (group_parts_of), one per run of single-symbol blocks.  The block count is read here, not on the host: the
+// grids are sized by the host's bound.
+//   k_walk_index_count   one workgroup: chains and groups per block, their exclusive scans, the totals and header facts -> *result
 //   k_walk_index_fill    one wavefront per block (striding): header, chain table, pieces, start states, groups
 // ---------------------------------------------------------------------------------------------------------------
-struct WalkBlock
+__device__ __forceinline__ IndexBlock walk_index_block(const WalkIndexArgs &a, uint32_t b, uint32_t n)
 {
-  uint64_t pos, at, hdr;
-  uint64_t T;     // whole groups the block decodes (clipped at the file's last whole group)
-  uint32_t count; // its chains
-  bool fill;
-};
-__device__ __forceinline__ WalkBlock walk_block_of(const WalkIndexArgs &a, uint32_t b)
-{
-  WalkBlock w;
-  w.pos = a.walk_blocks[3 * (uint64_t)b];
-  w.at = a.walk_blocks[3 * (uint64_t)b + 1];
-  w.hdr = a.walk_blocks[3 * (uint64_t)b + 2];
-  w.fill = (w.hdr >> 63) != 0;
-  const uint64_t whole_file = a.decoded_len / a.S, g0 = w.at / a.S, e = (w.at + w.hdr + a.S - 1) / a.S, g1 = e < whole_file ? e : whole_file;
-  w.T = !w.fill && g1 > g0 ? g1 - g0 : 0;
-  w.count = w.T == 0 ? 1 : (uint32_t)((w.T + a.interval - 1) / a.interval); // (g = 0, interval, ... < T; at least g = 0)
-  return w;
+  return index_block_of_walk(a.walk_blocks[3 * (uint64_t)b], a.walk_blocks[3 * (uint64_t)b + 1], a.walk_blocks[3 * (uint64_t)b + 2], a.decoded_len, a.S, b + 1 == n);
 }
 // groups block b opens before any is cut: a coded block one, a run of single-symbol blocks one at its first block
 __device__ __forceinline__ uint32_t walk_block_leads(const WalkIndexArgs &a, uint32_t b, bool fill)
@@ -366,13 +353,14 @@ __global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
   if (n == 0 || n > a.max_blocks) // (uniform: the walk recorded nothing, or more blocks than the list holds)
   {
     if (threadIdx.x == 0)
-      a.result[6] = 1;
+      a.result->error = 1;
     return;
   }
   if (threadIdx.x == 0)
   {
     carry_s = coded_s = last_s = bad_s = lead_s = 0;
-    first_s = fewest_s = 0xFFFFFFFFu;
+    first_s = 0xFFFFFFFFu;
+    fewest_s = kIndexNoFewest;
     hist_s = 0;
   }
   __syncthreads();
@@ -382,20 +370,17 @@ __global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
     uint32_t v = 0;
     if (b < n)
     {
-      const WalkBlock w = walk_block_of(a, b);
-      v = w.count;
-      atomicAdd(&lead_s, walk_block_leads(a, b, w.fill));
-      if (w.fill)
-      {
-        if (b + 1 == n && w.at + (w.hdr & (((uint64_t)1 << 54) - 1)) < a.decoded_len) // a tail behind a single-symbol block has no histogram
-          bad_s = 2;
-      }
-      else
+      const IndexBlock blk = walk_index_block(a, b, n);
+      v = index_block_chains(blk, a.interval);
+      atomicAdd(&lead_s, walk_block_leads(a, b, blk.fill));
+      if (index_block_ends_short(blk, a.decoded_len))
+        bad_s = 2;
+      if (!blk.fill)
       {
         atomicAdd(&coded_s, 1u);
         atomicMin(&first_s, b);
         atomicMax(&last_s, b);
-        atomicMax(&hist_s, (unsigned long long)(w.pos + 8)); // (exactly one coded block: the plan's chains share its table — PlanBuilder::serialize)
+        atomicMax(&hist_s, (unsigned long long)blk.hist_off);
       }
     }
     const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
@@ -416,10 +401,11 @@ __global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
     uint32_t v = 0;
     if (b < n)
     {
-      const WalkBlock w = walk_block_of(a, b);
-      v = w.fill ? walk_block_leads(a, b, true) : group_parts_of(w.count, k_max);
-      if (!w.fill && b != first_s && b != last_s) // (k_decode_spread's condition, as dplan_fill has it)
-        atomicMin(&fewest_s, w.count);
+      const IndexBlock blk = walk_index_block(a, b, n);
+      const uint32_t count = index_block_chains(blk, a.interval);
+      v = blk.fill ? walk_block_leads(a, b, true) : group_parts_of(count, k_max);
+      if (!blk.fill && b != first_s && b != last_s)
+        atomicMin(&fewest_s, count);
     }
     const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
     if (b < n)
@@ -428,80 +414,33 @@ __global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
   if (threadIdx.x == 0)
   {
     const uint32_t n_groups = carry_s;
-    a.result[0] = total;
-    a.result[1] = coded_s;
-    a.result[2] = hist_s;
-    a.result[3] = fewest_s;
-    a.result[4] = n;
-    a.result[5] = n_groups;
-    a.result[6] = bad_s ? bad_s : total > a.max_chains || n_groups > a.max_groups ? 3 : 0;
-    a.result[7] = k_max;
-    a.result[8] = grouped ? 1 : 0;
+    IndexResult r{};
+    r.chains = total;
+    r.blocks = n;
+    r.coded = coded_s;
+    r.fewest = fewest_s;
+    r.hist_off = hist_s;
+    r.groups = grouped ? n_groups : 0;
+    r.parts = k_max;
+    r.error = bad_s ? bad_s : total > a.max_chains || n_groups > a.max_groups ? 3 : 0;
+    *a.result = r;
   }
 }
 
 __global__ void __launch_bounds__(64) k_walk_index_fill(WalkIndexArgs a)
 {
-  if (a.result[6] != 0) // no plan: the host reads the word and fails the call
+  const IndexResult r = *a.result;
+  if (r.error != 0) // no plan: the host reads the word and fails the call
     return;
-  const uint32_t lane = threadIdx.x, S = a.S;
-  const uint32_t nc = (uint32_t)a.result[0], n = (uint32_t)a.result[4], k_max = (uint32_t)a.result[7];
-  const bool grouped = a.result[8] != 0;
-  uint32_t *chain_first = (uint32_t *)(a.plan + plan_chain_first_off());
-  Piece *pieces = (Piece *)(a.plan + plan_pieces_off(nc));
-  uint32_t *states = (uint32_t *)(a.plan + plan_states_off(nc, nc));
-  const uint64_t tail = a.decoded_len - a.decoded_len / S * S;
+  const uint32_t lane = threadIdx.x, S = a.S, n = r.blocks;
   if (blockIdx.x == 0 && lane == 0)
-  {
-    PlanHeader h = *(const PlanHeader *)a.base; // container, states, bits, lengths: the walk plan's
-    h.flags = 0;
-    h.n_chains = h.n_pieces = nc;
-    h.interval = a.interval;
-    h.shared_hist = a.result[1] == 1 ? 1 : 0;
-    h.aux_off = h.shared_hist ? a.result[2] : 0;
-    *(PlanHeader *)a.plan = h;
-    chain_first[nc] = nc;
-  }
+    index_write_header(a.base, a.plan, r, a.interval);
   for (uint32_t b = blockIdx.x; b < n; b += gridDim.x)
   {
-    const WalkBlock w = walk_block_of(a, b);
-    const bool last = b + 1 == n;
-    const uint32_t c0 = a.chain_off[b], count = w.count;
-    const uint64_t g_abs0 = w.at / S;
-    for (uint32_t k = lane; k < count; k += 64)
-    {
-      Piece p{};
-      if (w.fill)
-      {
-        p.out_off = w.at;
-        p.hist_off = (w.hdr >> 54) & 0xFF;
-        p.fill_len = w.hdr & (((uint64_t)1 << 54) - 1);
-        p.flags = kPieceFill;
-      }
-      else
-      {
-        const uint64_t g = (uint64_t)k * a.interval;
-        p.hist_off = w.pos + 8;
-        p.out_off = w.at + g * S;
-        p.words_off = k == 0 ? w.pos + 8 + 512 : a.ck_words[(g_abs0 + g) / a.interval];
-        const uint64_t steps = w.T - g < a.interval ? w.T - g : a.interval;
-        p.steps = (uint32_t)steps;
-        p.tail = (uint16_t)(last && g + steps >= w.T ? tail : 0);
-      }
-      p.flags |= kPieceChainStart;
-      p.state_idx = c0 + k;
-      pieces[c0 + k] = p;
-      chain_first[c0 + k] = c0 + k;
-    }
-    for (uint32_t k = 0; k < count; k++)
-      if (lane < S)
-      {
-        uint32_t v = 0;
-        if (!w.fill)
-          v = k == 0 ? a.walk_states[(uint64_t)b * S + lane] : a.ck_states[((g_abs0 + (uint64_t)k * a.interval) / a.interval) * S + lane];
-        states[(uint64_t)(c0 + k) * S + lane] = v;
-      }
-    if (!grouped || !walk_block_leads(a, b, w.fill))
+    const IndexBlock blk = walk_index_block(a, b, n);
+    const uint32_t c0 = a.chain_off[b], count = index_block_chains(blk, a.interval);
+    index_write_chains(blk, S, a.interval, c0, count, a.walk_states + (uint64_t)b * S, a.ck_states, a.ck_words, a.plan, r.chains);
+    if (r.groups == 0 || !walk_block_leads(a, b, blk.fill))
       continue;
     // the group's words end where the next coded block's histogram begins (as dplan_fill has it), or at the stream's end
     uint64_t words_end = a.stream_len;
@@ -516,31 +455,15 @@ __global__ void __launch_bounds__(64) k_walk_index_fill(WalkIndexArgs a)
       run++; // (every block passed here is a single-symbol one: behind a run's first block, the rest of its run)
     }
     const uint32_t g0 = a.group_off[b];
-    if (w.fill)
+    if (blk.fill)
     {
       if (lane == 0)
-      {
-        Group g{};
-        g.begin = g.piece0 = c0;
-        g.count = run;
-        g.flags = kGroupFill;
-        g.words_end = words_end;
-        a.groups[g0] = g;
-      }
+        a.groups[g0] = index_group(c0, run, kGroupFill, 0, words_end);
       continue;
     }
-    const uint32_t parts = group_parts_of(count, k_max);
+    const uint32_t parts = group_parts_of(count, r.parts);
     for (uint32_t part = lane; part < parts; part += 64)
-    {
-      const uint32_t lo = (uint32_t)((uint64_t)count * part / parts), hi = (uint32_t)((uint64_t)count * (part + 1) / parts);
-      Group g{};
-      g.begin = g.piece0 = c0 + lo;
-      g.count = hi - lo;
-      g.flags = kGroupMergeable;
-      g.hist_off = w.pos + 8;
-      g.words_end = hi < count ? a.ck_words[(g_abs0 + (uint64_t)hi * a.interval) / a.interval] : words_end; // (the next part's first words_off)
-      a.groups[g0 + part] = g;
-    }
+      a.groups[g0 + part] = index_part_group(blk, a.interval, c0, count, part, parts, a.ck_words, words_end);
   }
 }
 

@@ -572,6 +572,52 @@ def test_first_decode_of_an_unindexed_stream_leaves_the_index_behind(gpu_ctx, re
 
 
 @pytest.mark.parametrize("states", (32, 64))
+def test_index_build_at_explicit_groups_of_an_mt_stream(gpu_ctx, states):
+    """hsrans_index_build_at on the GPU (mt_ is the container that takes this path; raw goes to the host): checkpoints at explicit groups
+    near block starts, on one, inside blocks and next to both ends give the host builder's plan byte for byte, and it decodes."""
+    d = synth.enwik8_shaped(1 << 20)
+    s = H.encode(H.MT, states, 11, d)
+    _, _, pc = H.api.plan_tables(H.plan_build(H.MT, states, 11, s))
+    starts = [int(p["out_off"]) // states for p in pc]
+    steps = [int(p["steps"]) for p in pc]
+    total = d.size // states
+    groups = [4, starts[1] - 4, starts[1], starts[1] + 4, starts[2] + steps[2] // 8 * 4, starts[-1] + 4, total - 4]
+    want = H.api.index_build_host(H.MT, states, 11, s, groups)
+    plan = gpu_ctx.index_build_at(H.MT, states, 11, s, groups)
+    assert np.array_equal(plan, want)
+    assert H.plan_chain_count(plan) == len(starts) + len(groups) - 1  # (the group on a block's first group adds no chain)
+    r, got = gpu_ctx.decode_host(H.MT, states, 11, s, d.size, plan=plan)
+    assert r == d.size and np.array_equal(got, d)
+
+
+@pytest.mark.parametrize("states", (32, 64))
+def test_first_decode_of_an_mt_stream_both_assembly_paths(gpu_ctx, ref, zipf, monkeypatch, states):
+    """hsrans_decode_device_indexing on an mt_ base plan: the plan assembled on the device and the one a context made under
+    HSRANS_INDEX_ASSEMBLE_ON_HOST=1 builds on the host are the same blob (hsrans_index_build's), launch alike and decode to the same bytes."""
+    import torch
+
+    monkeypatch.setenv("HSRANS_INDEX_ASSEMBLE_ON_HOST", "1")
+    host_ctx = H.Context(0)  # (the switch is read when a context is made)
+    monkeypatch.delenv("HSRANS_INDEX_ASSEMBLE_ON_HOST")
+    for bits, n, interval in ((11, 65560, 4), (14, 1 << 20, 64)):
+        s = ref.encode(MT, states, bits, zipf[:n])
+        d_in = torch.from_numpy(np.concatenate([s, np.zeros((-s.size) % 16, np.uint8)])).cuda()
+        want_plan = gpu_ctx.index_build(H.MT, states, bits, s, interval)
+        outs, infos = [], []
+        for ctx in (gpu_ctx, host_ctx):
+            base = ctx.make_device_plan_from_stream(H.MT, states, bits, d_in, s.size, n)
+            first = torch.zeros(n, dtype=torch.uint8, device="cuda")
+            indexed = ctx.decode_device_indexing(base, d_in, first, interval, stream_length=s.size)
+            assert np.array_equal(ctx.read_device_plan(indexed, capacity=want_plan.size + 4096), want_plan)
+            again = torch.zeros(n, dtype=torch.uint8, device="cuda")
+            ctx.decode_device(indexed, d_in, again, stream_length=s.size)
+            assert ctx.status(indexed) == 0 and torch.equal(first, again)
+            outs.append(again.cpu().numpy())
+            infos.append(indexed.launch_info())
+        assert np.array_equal(outs[0], outs[1]) and infos[0] == infos[1]
+
+
+@pytest.mark.parametrize("states", (32, 64))
 def test_index_build_for_block_streams(gpu_ctx, oracle, ref, nonstat, zipf, states):
     """block_ streams are one chain with inline headers: the single wavefront that walks them also reports the headers it meets,
     so one pass turns a stream (ours or the real reference's) into a plan with a chain per block and per checkpoint."""

@@ -1,17 +1,24 @@
-"""The first decode of a block_ stream without an index, and what it leaves behind.  One 100 MB enwik8-shaped input, 64 states, 11 bits,
-adaptive blocks from the host encoder (byte-identical to the reference's stream).  Legs, rotated, wall clock around each call including
-its synchronisation, the decoded bytes compared on every leg of every repetition:
-  device  a  decode_device with the walk plan (one wavefront follows the inline headers)
-          b  decode_device_indexing at interval 64: the same walk, recording; the indexed plan assembled on the device
+"""The first decode of a block_ (or, --container mt, an mt_) stream without an index, and what it leaves behind.  One 100 MB enwik8-shaped
+input, 64 states, 11 bits, adaptive blocks from the host encoder (byte-identical to the reference's stream).  Legs, rotated, wall clock around
+each call including its synchronisation, the decoded bytes compared on every leg of every repetition:
+  device  a  decode_device with the base plan (block_: the walk plan, one wavefront follows the inline headers; mt_: one chain per block,
+             planned on the device)
+          b  decode_device_indexing at interval 64: the same pass, recording; the indexed plan assembled on the device
           c  the same in a context made under HSRANS_INDEX_ASSEMBLE_ON_HOST=1 (records down, blob built by one core, blob up)
           d  decode_device with the plan b left
   host    e  decode_host, first call on the stream (the context's index cache holds another stream's index)
           f  decode_host, later calls
           g  decode_host with plan= the hsrans_index_build blob
-  parent  a, e, f against another build of the library (HSRANS_PARENT_LIB=<path to the parent commit's libhsrans_hip.so>), in the same
+          h  hsrans_index_build at interval 64 from the host copy of the stream
+  parent  a, b, e, f, h against another build of the library (HSRANS_PARENT_LIB=<path to the parent commit's libhsrans_hip.so>), in the same
           rotation: the "before" figures.  Left out when the variable is not set.
+  direct  a, b of THIS build through the same bare ctypes calls the parent legs make (the package's wrappers add some 50 us to a call of
+          a few hundred): what parent a and b compare with.  e, f and h are bare calls for both builds already.
+The two roles are not equal: on mt_ the library in the "parent" role measured 3 % (a), 18 % (b) and 11 % (h) faster than the one under test
+whichever build it was (profiles/r15_first_decode_refactor_mt*.jsonl).  For a comparison of two builds run it a second time with the roles
+swapped (HSRANS_LIB=<parent> HSRANS_PARENT_LIB=<this build>): the builds differ by the square root of the quotient of the two ratios.
 One JSON line per leg (median and quartiles over the repetitions), then one line of ratios.  Run on the GPU box:
-  python tools/block_first_decode.py [--size N] [--reps R] [--out profiles/r14_block_first_decode.jsonl]"""
+  python tools/block_first_decode.py [--container block|mt] [--size N] [--reps R] [--out profiles/r14_block_first_decode.jsonl]"""
 import argparse
 import ctypes
 import json
@@ -29,14 +36,18 @@ from hypersonic_rans_amd import synth
 ap = argparse.ArgumentParser()
 ap.add_argument("--size", type=int, default=100_000_000)
 ap.add_argument("--reps", type=int, default=16)
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r14_block_first_decode.jsonl"))
+ap.add_argument("--container", choices=("block", "mt"), default="block")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r14_%s_first_decode.jsonl" % args.container)
+CONTAINER = H.BLOCK if args.container == "block" else H.MT
 assert args.reps >= 16, "medians and quartiles of at least 16 repetitions"
 n, S, BITS, INTERVAL = args.size, 64, 11, 64
 
 data = synth.enwik8_shaped(n)
-stream = np.ascontiguousarray(H.encode(H.BLOCK, S, BITS, data))
-other = np.ascontiguousarray(H.encode(H.BLOCK, S, BITS, data[: 2 << 20][::-1].copy()))  # another stream of >= 1 MiB: decoding it replaces the cached index
+stream = np.ascontiguousarray(H.encode(CONTAINER, S, BITS, data))
+other = np.ascontiguousarray(H.encode(CONTAINER, S, BITS, data[: 2 << 20][::-1].copy()))  # another stream of >= 1 MiB: decoding it replaces the cached index
 m = stream.size
 d_in = torch.from_numpy(np.concatenate([stream, np.zeros((-m) % 16, np.uint8)])).cuda()
 d_ref = torch.from_numpy(data).cuda()
@@ -47,15 +58,17 @@ ctx = H.Context(0)
 os.environ["HSRANS_INDEX_ASSEMBLE_ON_HOST"] = "1"
 ctx_host_asm = H.Context(0)  # (the switch is read when a context is made)
 del os.environ["HSRANS_INDEX_ASSEMBLE_ON_HOST"]
-walk_blob = H.plan_build(H.BLOCK, S, BITS, stream)
-walk = ctx.make_device_plan_from_stream(H.BLOCK, S, BITS, d_in, m, n)
-walk_c = ctx_host_asm.make_device_plan(walk_blob)
-index_blob = ctx.index_build(H.BLOCK, S, BITS, stream, INTERVAL)
+walk_blob = H.plan_build(CONTAINER, S, BITS, stream)
+walk = ctx.make_device_plan_from_stream(CONTAINER, S, BITS, d_in, m, n)
+walk_c = ctx_host_asm.make_device_plan(walk_blob) if CONTAINER == H.BLOCK else ctx_host_asm.make_device_plan_from_stream(CONTAINER, S, BITS, d_in, m, n)
+index_blob = ctx.index_build(CONTAINER, S, BITS, stream, INTERVAL)
+index_room = np.zeros(index_blob.size + 4096, np.uint8)
 state = {"indexed": None}
 
 
 class Parent:
-    """the few entries the parent legs need, straight through ctypes (the package's classes are bound to the library under test)"""
+    """the few entries the parent legs need, straight through ctypes (the package's classes are bound to the library under test); also
+    made for the library under test itself: the "direct" legs"""
 
     def __init__(self, path):
         L = self.L = ctypes.CDLL(path)
@@ -66,25 +79,40 @@ class Parent:
         L.hsrans_dplan_status.argtypes = [vp, vp, ctypes.POINTER(u32)]
         L.hsrans_decode_host.restype = sz
         L.hsrans_decode_host.argtypes = [vp, i, i, u32, vp, sz, vp, sz, vp, sz]
+        L.hsrans_dplan_create_from_device_stream.argtypes = [vp, i, i, u32, vp, sz, sz, vp, ctypes.POINTER(vp)]
+        L.hsrans_decode_device_indexing.argtypes = [vp, vp, vp, sz, vp, sz, u32, vp, ctypes.POINTER(vp)]
+        L.hsrans_dplan_destroy.restype = None
+        L.hsrans_dplan_destroy.argtypes = [vp]
+        L.hsrans_index_build.restype = sz
+        L.hsrans_index_build.argtypes = [vp, i, i, u32, vp, sz, u32, vp, sz]
         self.ctx, self.walk = vp(), vp()
         assert L.hsrans_ctx_create(0, ctypes.byref(self.ctx)) == 0
-        assert L.hsrans_dplan_create(self.ctx, walk_blob.ctypes.data, walk_blob.size, ctypes.byref(self.walk)) == 0
+        if CONTAINER == H.BLOCK:
+            assert L.hsrans_dplan_create(self.ctx, walk_blob.ctypes.data, walk_blob.size, ctypes.byref(self.walk)) == 0
+        else:
+            assert L.hsrans_dplan_create_from_device_stream(self.ctx, CONTAINER, S, BITS, d_in.data_ptr(), m, n, ctypes.c_void_p(cur), ctypes.byref(self.walk)) == 0
 
     def decode_device(self):
         assert self.L.hsrans_decode_device(self.ctx, self.walk, d_in.data_ptr(), m, d_out.data_ptr(), n, ctypes.c_void_p(cur)) == 0
 
+    def decode_device_indexing(self):
+        indexed = ctypes.c_void_p()
+        assert self.L.hsrans_decode_device_indexing(self.ctx, self.walk, d_in.data_ptr(), m, d_out.data_ptr(), n, INTERVAL, ctypes.c_void_p(cur), ctypes.byref(indexed)) == 0
+        self.L.hsrans_dplan_destroy(indexed)
+
     def decode_host(self, s, out):
-        return self.L.hsrans_decode_host(self.ctx, H.BLOCK, S, BITS, s.ctypes.data, s.size, out.ctypes.data, out.size, None, 0)
+        return self.L.hsrans_decode_host(self.ctx, CONTAINER, S, BITS, s.ctypes.data, s.size, out.ctypes.data, out.size, None, 0)
 
 
 parent = Parent(os.environ["HSRANS_PARENT_LIB"]) if os.environ.get("HSRANS_PARENT_LIB") else None
+direct = Parent(H.lib_path()) if parent is not None else None
 h_out = np.zeros(n, np.uint8)
 h_other = np.zeros(2 << 20, np.uint8)
 L = H.load_library()
 
 
 def host_call(handle_lib, handle, s, out, plan=None):
-    return handle_lib.hsrans_decode_host(handle, H.BLOCK, S, BITS, s.ctypes.data, s.size, out.ctypes.data, out.size, None if plan is None else plan.ctypes.data,
+    return handle_lib.hsrans_decode_host(handle, CONTAINER, S, BITS, s.ctypes.data, s.size, out.ctypes.data, out.size, None if plan is None else plan.ctypes.data,
                                          0 if plan is None else plan.size)
 
 
@@ -112,6 +140,13 @@ def host_leg(lib, handle, plan=None):
     return run
 
 
+def index_leg(lib, handle):
+    def run():
+        got = lib.hsrans_index_build(handle, CONTAINER, S, BITS, stream.ctypes.data, stream.size, INTERVAL, index_room.ctypes.data, index_room.size)
+        assert got == index_blob.size and np.array_equal(index_room[:got], index_blob)
+    return run
+
+
 def evict(lib, handle):
     def run():
         assert host_call(lib, handle, other, h_other) == h_other.size
@@ -119,15 +154,20 @@ def evict(lib, handle):
 
 
 # (name, library, what, un-timed step before it, timed call, where the bytes land)
-LEGS = [("a", "this", "decode_device, walk plan", None, leg_a, "device"),
+LEGS = [("a", "this", "decode_device, base plan", None, leg_a, "device"),
         ("b", "this", "decode_device_indexing, interval 64, assembled on the device", None, leg_b, "device"),
         ("c", "this", "decode_device_indexing, interval 64, HSRANS_INDEX_ASSEMBLE_ON_HOST=1", None, leg_c, "device"),
         ("d", "this", "decode_device, the plan b left", None, leg_d, "device"),
         ("e", "this", "decode_host, first call", evict(L, ctx.handle), host_leg(L, ctx.handle), "host"),
         ("f", "this", "decode_host, later call", None, host_leg(L, ctx.handle), "host"),
-        ("g", "this", "decode_host, plan= the hsrans_index_build blob", None, host_leg(L, ctx.handle, index_blob), "host")]
+        ("g", "this", "decode_host, plan= the hsrans_index_build blob", None, host_leg(L, ctx.handle, index_blob), "host"),
+        ("h", "this", "index_build, interval 64", None, index_leg(L, ctx.handle), None)]
 if parent is not None:
-    LEGS += [("a", "parent", "decode_device, walk plan", None, parent.decode_device, "device"),
+    LEGS += [("a", "direct", "decode_device, base plan", None, direct.decode_device, "device"),
+             ("b", "direct", "decode_device_indexing, interval 64, assembled on the device", None, direct.decode_device_indexing, "device"),
+             ("a", "parent", "decode_device, base plan", None, parent.decode_device, "device"),
+             ("b", "parent", "decode_device_indexing, interval 64, assembled on the device", None, parent.decode_device_indexing, "device"),
+             ("h", "parent", "index_build, interval 64", None, index_leg(parent.L, parent.ctx), None),
              ("e", "parent", "decode_host, first call", evict(parent.L, parent.ctx), lambda: parent.decode_host(stream, h_out) == n or sys.exit("parent decode_host failed"), "host"),
              ("f", "parent", "decode_host, later call", None, lambda: parent.decode_host(stream, h_out) == n or sys.exit("parent decode_host failed"), "host")]
 
@@ -143,14 +183,14 @@ for rep in range(args.reps + 1):  # (the first round warms buffers and code obje
             before()
         if where == "device":
             d_out.zero_()
-        else:
+        elif where == "host":
             h_out[:] = 0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         call()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        assert torch.equal(d_out, d_ref) if where == "device" else np.array_equal(h_out, data), (name, lib)
+        assert where is None or (torch.equal(d_out, d_ref) if where == "device" else np.array_equal(h_out, data)), (name, lib)
         if rep:
             times[(name, lib)].append(dt * 1e3)
 assert ctx.status(walk) == 0 and ctx.status(state["indexed"]) == 0 and ctx.host_index_chains() > 100
@@ -162,7 +202,7 @@ with open(args.out, "w") as f:
         q1, q2, q3 = (float(v) for v in np.percentile(times[(name, lib)], (25, 50, 75)))
         med[(name, lib)] = q2
         line = {"leg": name, "library": lib, "what": what, "median_ms": round(q2, 4), "q1_ms": round(q1, 4), "q3_ms": round(q3, 4), "iqr_ms": round(q3 - q1, 4),
-                "reps": len(times[(name, lib)]), "size": n, "stream": int(m), "states": S, "bits": BITS, "interval": INTERVAL}
+                "reps": len(times[(name, lib)]), "size": n, "stream": int(m), "states": S, "bits": BITS, "interval": INTERVAL, "container": args.container}
         if name == "d":
             line["launch"] = state["indexed"].launch_info()
             line["chains"] = line["launch"]["chains"]
@@ -171,7 +211,8 @@ with open(args.out, "w") as f:
     ratios = {"b_over_a": med[("b", "this")] / med[("a", "this")], "c_over_b": med[("c", "this")] / med[("b", "this")], "d_ms": med[("d", "this")],
               "f_over_g": med[("f", "this")] / med[("g", "this")], "e_over_f": med[("e", "this")] / med[("f", "this")]}
     if parent is not None:
-        ratios.update({"b_over_parent_a": med[("b", "this")] / med[("a", "parent")], "a_over_parent_a": med[("a", "this")] / med[("a", "parent")],
+        ratios.update({"b_over_parent_a": med[("b", "this")] / med[("a", "parent")], "a_over_parent_a": med[("a", "direct")] / med[("a", "parent")],
+                       "b_over_parent_b": med[("b", "direct")] / med[("b", "parent")], "h_over_parent_h": med[("h", "this")] / med[("h", "parent")],
                        "f_over_parent_f": med[("f", "this")] / med[("f", "parent")], "e_over_parent_e": med[("e", "this")] / med[("e", "parent")]})
     line = {"ratios": {k: round(v, 4) for k, v in ratios.items()}, "device": ctx.device_name,
             "note": "wall clock around each call including its synchronisation; legs rotated; medians over the repetitions after one dropped round"}

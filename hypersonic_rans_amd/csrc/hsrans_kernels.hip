@@ -452,14 +452,15 @@ LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom
   const uint32_t table_bytes = table_bytes_for(L.mode, h.bits);
   const uint32_t wave_bytes = kWaveRingBytes + ((table_bytes + 15) & ~15u); // private rings + table
   uint32_t waves, lds, grid;
-  const uint32_t dual_ring = kFastRingBytes;
-  L.dual = dual && L.shared && persistent && (L.mode == kModePack64 || L.mode == kModeRank) && 16 * 2 * dual_ring + table_bytes <= dg.max_lds;
+  // the LDS of a workgroup of `w` waves around one shared table (lds_layout: the kernels place their pointers by the same rule)
+  const auto shared_lds = [&](uint32_t w, uint32_t rings_per_wave = 1, uint32_t extra = 0) { return lds_layout(L.mode, h.bits, w, rings_per_wave, extra).total(); };
+  L.dual = dual && L.shared && persistent && (L.mode == kModePack64 || L.mode == kModeRank) && shared_lds(16, 2) <= dg.max_lds;
   if (L.dual)
   {
     // k_decode_dual: workgroups of 16 waves, two rings per wave, wave w decodes chains 2w and 2w + 1 (12 — two workgroups per CU beside a
     // 16 KiB table — measured slower again in round 5: profiles/r05_table_at_zero_ab.txt)
     waves = 16;
-    lds = waves * 2 * dual_ring + table_bytes;
+    lds = shared_lds(waves, 2);
     const uint32_t per_cu = dg.max_lds / lds ? dg.max_lds / lds : 1;
     L.resident = dg.num_cus * (per_cu * waves > 32 ? 32 / waves : per_cu);
     grid = (h.n_chains + 2 * waves - 1) / (2 * waves);
@@ -468,8 +469,7 @@ LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom
   }
   else if (L.shared)
   {
-    // (k_decode_direct's hand-scheduled loop wants a whole-chunk mirror behind every ring)
-    const uint32_t ring = fast_ring_mode(L.mode) ? kFastRingBytes : kWaveRingBytes;
+    const uint32_t ring = lds_layout(L.mode, h.bits, 1).ring_stride();
     waves = tn.waves_per_wg;
     // Grouped launches (one workgroup per block, round after round): FOUR workgroups of 8 waves per CU instead of two of 16
     // wherever four fit the LDS.  A round is table build + records + first chunks (~12 us in which the workgroup decodes
@@ -478,15 +478,15 @@ LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom
     // is twice as long for the same fixed cost.  Measured at 2^30 bytes: 256 KiB blocks 0.461 -> 0.492 of 8 TB/s, 64 KiB blocks
     // 0.358 -> 0.427 (1 MiB blocks: unchanged).  HSRANS_WAVES_PER_WG still overrides.
     // (only with at least four groups per CU: fewer, e.g. a 100 MB stream in 256 KiB blocks, fill more wave slots as 16-wave workgroups)
-    if (grouped && !tn.waves_per_wg_set && 4 * (8 * ring + table_bytes + 64 + 1024) <= dg.max_lds && n_groups >= 4 * dg.num_cus)
+    if (grouped && !tn.waves_per_wg_set && 4 * shared_lds(8, 1, kGroupedExtra) <= dg.max_lds && n_groups >= 4 * dg.num_cus)
       waves = 8;
-    if (L.mode == kModeRank && waves * ring + table_bytes > dg.max_lds / 2)
+    if (L.mode == kModeRank && shared_lds(waves) > dg.max_lds / 2)
       waves = 12; // 15 bits: 48 KiB of tables + 12 rings = 75 KiB, two workgroups per CU
-    if (waves * ring + table_bytes > dg.max_lds && table_bytes + 4 * ring <= dg.max_lds)
+    if (shared_lds(waves) > dg.max_lds && shared_lds(4) <= dg.max_lds)
       waves = (dg.max_lds - table_bytes) / ring / 4 * 4; // a big table: as many waves as still fit (multiple of 4: one per SIMD)
-    while (waves > 1 && (waves / 2 >= h.n_chains || waves * ring + table_bytes > dg.max_lds))
+    while (waves > 1 && (waves / 2 >= h.n_chains || shared_lds(waves) > dg.max_lds))
       waves /= 2;
-    lds = waves * ring + table_bytes + (grouped ? 64 + 1024 : 0); // (run_grouped's two next-group words and its table-build scratch)
+    lds = shared_lds(waves, 1, grouped ? kGroupedExtra : 0);
     grid = (h.n_chains + waves - 1) / waves;
     if (grouped)
       grid = n_groups;
@@ -988,14 +988,14 @@ hipError_t launch_decode(const Tuning &tn, const KParams &kp_in, const PlanHeade
 // waves per workgroup, LDS and grid of g's layout for n_tasks tasks and a table of table_bytes
 static void gather_waves(GatherShape &g, const DeviceGeom &dg, uint32_t table_bytes, uint32_t n_tasks)
 {
-  const uint32_t wave_bytes = g.shared ? kWaveRingBytes : kWaveRingBytes + ((table_bytes + 15) & ~15u);
-  const uint32_t fixed = g.shared ? table_bytes : 0;
+  // a shared table: lds_layout with plain rings (gather_setup); else every wave has a ring and a table of its own
+  const auto lds_of = [&](uint32_t w) { return g.shared ? lds_layout_gather(g.mode, table_bytes, w).total() : w * (kWaveRingBytes + ((table_bytes + 15) & ~15u)); };
   // few tasks: smaller workgroups, so that they reach more CUs (a task is one wave's work whatever the workgroup)
   uint32_t waves = g.shared ? 16 : 4;
-  while (waves > 1 && (waves * wave_bytes + fixed > (g.shared ? dg.max_lds : dg.max_lds / 2) || (waves > (g.shared ? 4u : 1u) && (n_tasks + waves - 1) / waves < 2 * dg.num_cus)))
+  while (waves > 1 && (lds_of(waves) > (g.shared ? dg.max_lds : dg.max_lds / 2) || (waves > (g.shared ? 4u : 1u) && (n_tasks + waves - 1) / waves < 2 * dg.num_cus)))
     waves /= 2;
   g.waves = waves;
-  g.lds = waves * wave_bytes + fixed;
+  g.lds = lds_of(waves);
   g.grid = (n_tasks + waves - 1) / waves;
 }
 

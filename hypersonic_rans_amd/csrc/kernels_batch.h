@@ -72,9 +72,7 @@ __device__ __forceinline__ void run_batch_pair(const WaveCtx &c, const KParams &
       atomicOr(c.status, kStatusBadHist);
   }
   auto copy_table = [&]() {
-    const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+    copy_host_table<MODE>(c, pa.table);
     __syncthreads();
   };
   if (ch >= end || ch >= pa.n_chains)
@@ -122,9 +120,7 @@ __device__ __forceinline__ void run_batch_dual(const WaveCtx &c, const KParams &
   constexpr uint32_t kDualRing = kFastRingBytes;
   // the host-built table, the first workgroup of the member also checks the histogram it was built from against the stream's
   {
-    const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+    copy_host_table<MODE>(c, pa.table);
     if (check_hist && threadIdx.x < 64)
       check_hist_copy<false>(c, pa.hist_copy, pa.hist_off);
   }
@@ -196,38 +192,15 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(102))) k_
   const kmember_ptr mp = (kmember_ptr)(uintptr_t)(bp.members + member);
   const BatchIO &io = bp.io[member];
   WaveCtx c;
-  c.stream = io.stream;
-  c.stream_len = io.stream_len;
-  c.stream_lo = 0;
-  c.out = io.out;
-  c.out_cap = io.out_cap;
-  c.status = mp->status;
-  c.bits = mp->bits;
-  c.S = 64;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  constexpr uint32_t kDualRing = kFastRingBytes;
-  if (MODE == kModeRank)
+  wave_ctx_begin(c, io.stream, io.stream_len, 0, io.out, io.out_cap, mp->status, mp->bits, 64);
+  if (MODE == kModeRank && !lds_starts_at_zero(smem))
   {
-    if (uni(lds_address(smem)) != 0) // (the hand-scheduled group takes the slot as the rank byte's address)
-    {
-      if (threadIdx.x == 0)
-        atomicOr(c.status, kStatusOutOfRange);
-      return;
-    }
-    c.table = smem;
-    c.rings = smem + table_bytes_for(MODE, c.bits) + wave * 2 * kDualRing;
+    if (threadIdx.x == 0)
+      atomicOr(c.status, kStatusOutOfRange);
+    return;
   }
-  else
-  {
-    c.rings = smem + wave * 2 * kDualRing;
-    c.table = smem + waves * 2 * kDualRing;
-  }
-  c.table_b = c.table;
+  wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, c.bits, waves, 2), wave);
   c.gtable = mp->table;
-  c.scratch_cnt = (uint16_t *)smem;
-  c.scratch_cum = (uint16_t *)(smem + 512);
   KParams kp{};
   kp.pa.pieces = mp->pieces;
   kp.pa.states = mp->states;
@@ -254,23 +227,9 @@ __device__ __forceinline__ void batch_body(const BatchParams &bp)
   const kmember_ptr mp = (kmember_ptr)(uintptr_t)(bp.members + member);
   const BatchIO &io = bp.io[member];
   WaveCtx c;
-  c.stream = io.stream;
-  c.stream_len = io.stream_len;
-  c.stream_lo = 0;
-  c.out = io.out;
-  c.out_cap = io.out_cap;
-  c.status = mp->status;
-  c.bits = mp->bits;
-  c.S = PAIR ? 32 : 64; // (a launch's members share one state count: the host puts 64- and 32-state members into launches of their own)
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  c.rings = smem + wave * kFastRingBytes;
-  c.table = smem + waves * kFastRingBytes;
-  c.table_b = c.table;
+  wave_ctx_begin(c, io.stream, io.stream_len, 0, io.out, io.out_cap, mp->status, mp->bits, PAIR ? 32 : 64);
+  wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, c.bits, waves), wave);
   c.gtable = mp->table;
-  c.scratch_cnt = (uint16_t *)smem;
-  c.scratch_cum = (uint16_t *)(smem + 512);
   // the member's plan in the shape run_direct_span reads it (everything below lands in SGPRs; nothing of `kp` survives as memory)
   KParams kp{};
   kp.pa.pieces = mp->pieces;

@@ -60,6 +60,36 @@ __host__ __device__ constexpr bool fast_ring_mode(int mode) { return mode == kMo
 // ... and the one whose table sits at the START of the workgroup's LDS (address 0: the slot is the address of its rank byte)
 __host__ __device__ constexpr bool table_first_mode(int mode) { return mode == kModeRank; }
 
+// The LDS of a workgroup that shares ONE table, as byte offsets from its start: [waves x rings][table][extra], or with the table
+// first [table][extra][waves x rings].  The launcher sizes the workgroup by total(), the kernels place their pointers by the rest
+// (wave_ctx_lds), so the two cannot drift apart.
+//   rings_per_wave: 2 in the dual kernels (one ring per chain)
+//   extra: bytes behind the table; kGroupedExtra = run_grouped's two next-group words (64 B) and a table-build scratch of its own
+//          (1 KiB, the last of them: a round's first stream chunks are requested before its table is built).  Without extra bytes
+//          the build scratch is wave 0's ring: no request is in flight while a table is built
+//   whole_mirror: every ring carries a whole-chunk mirror (the gather kernels never run the hand-scheduled loops: false)
+//   table_given: the table's size where it is not worked out from mode and bits: a gather over many plans makes room for their largest
+constexpr uint32_t kBuildScratchBytes = 1024; // counts + prefix sums, 512 B each
+constexpr uint32_t kGroupedExtra = 64 + kBuildScratchBytes;
+struct LdsLayout
+{
+  int mode;
+  uint32_t bits, waves, rings_per_wave, extra;
+  bool whole_mirror, given;
+  uint32_t table_given;
+  constexpr uint32_t table_bytes() const { return given ? table_given : table_bytes_for(mode, bits); }
+  constexpr uint32_t ring_stride() const { return rings_per_wave * (whole_mirror ? kFastRingBytes : kWaveRingBytes); } // from one wave's rings to the next wave's
+  constexpr uint32_t rings() const { return table_first_mode(mode) ? table_bytes() + extra : 0; }
+  constexpr uint32_t table() const { return table_first_mode(mode) ? 0 : waves * ring_stride(); }
+  constexpr uint32_t total() const { return waves * ring_stride() + table_bytes() + extra; }
+};
+__host__ __device__ constexpr LdsLayout lds_layout(int mode, uint32_t bits, uint32_t waves, uint32_t rings_per_wave = 1, uint32_t extra = 0)
+{
+  return LdsLayout{mode, bits, waves, rings_per_wave, extra, fast_ring_mode(mode), false, 0};
+}
+// (plain rings: the gather kernels never run the hand-scheduled loops)
+__host__ __device__ constexpr LdsLayout lds_layout_gather(int mode, uint32_t table_bytes, uint32_t waves) { return LdsLayout{mode, 0, waves, 1, 0, false, true, table_bytes}; }
+
 __device__ __forceinline__ uint32_t lds_address(const void *p)
 {
   return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)p;
@@ -182,6 +212,70 @@ struct WaveCtx
   uint16_t *scratch_cnt; // LDS, 512 B each, only live during table builds: they alias a ring that has no request in
   uint16_t *scratch_cum; // flight (build_table is always called before the ring is begun)
 };
+
+// What every kernel's context starts from: where it reads and writes, the histogram's width, the state count.  (k_decode_single has
+// no WaveCtx: its two waves share one hand-laid ring of table entries.)
+__device__ __forceinline__ void wave_ctx_begin(WaveCtx &c, const uint8_t *stream, uint64_t stream_len, uint64_t stream_lo, uint8_t *out, uint64_t out_cap, uint32_t *status, uint32_t bits,
+                                               uint32_t S)
+{
+  c.stream = stream;
+  c.stream_len = stream_len;
+  c.stream_lo = stream_lo;
+  c.out = out;
+  c.out_cap = out_cap;
+  c.status = status;
+  c.bits = bits;
+  c.S = S;
+  c.lane = threadIdx.x & 63;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
+}
+
+// the LDS pointers of wave `wave` in a workgroup laid out by L
+__device__ __forceinline__ void wave_ctx_lds(WaveCtx &c, uint8_t *smem, const LdsLayout &L, uint32_t wave)
+{
+  uint8_t *ring0 = smem + L.rings();
+  c.rings = ring0 + wave * L.ring_stride();
+  c.table = smem + L.table();
+  c.table_b = c.table;
+  // the build scratch: the last of the extra bytes behind the table; without any, wave 0's ring
+  uint8_t *scratch = L.extra ? c.table + L.table_bytes() + (L.extra - kBuildScratchBytes) : ring0;
+  c.scratch_cnt = (uint16_t *)scratch;
+  c.scratch_cum = c.scratch_cnt + kBuildScratchBytes / 4;
+}
+// ... laid out for the kernel's own table (c.bits is set).  (A table in front of the rings: its size is worked out here, with MODE a
+// constant, as the table copy works it out: the compiler then shares the value and the preamble's instructions stay where they were.)
+template <int MODE>
+__device__ __forceinline__ void wave_ctx_lds(WaveCtx &c, uint8_t *smem, const LdsLayout &L, uint32_t wave)
+{
+  if constexpr (table_first_mode(MODE))
+  {
+    LdsLayout G = L;
+    G.given = true;
+    G.table_given = table_bytes_for(MODE, c.bits);
+    wave_ctx_lds(c, smem, G, wave);
+  }
+  else
+    wave_ctx_lds(c, smem, L, wave);
+}
+
+// The dual kernels' hand-scheduled rank group takes the slot as the address of its rank byte: the table must sit at LDS address 0
+// (these kernels have no static LDS).  Elsewhere they would decode garbage silently: they report instead; the host discards the output.
+__device__ __forceinline__ bool lds_starts_at_zero(const uint8_t *smem) { return uni(lds_address(smem)) == 0; }
+
+// the table layouts a host-built table comes in (kModeRank / kModeSpill tables always are host-built); a plan has one where pa.table is set
+// (a constant, not a function of pa: the modes that never have one then lose the branch where they lost it before)
+template <int MODE>
+constexpr bool host_table_mode = MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill;
+// The host-built table into LDS: one coalesced 16-byte load + LDS store per thread and round (nothing for the spilled table: it stays
+// in global memory).  No barrier: the callers have their own, some behind further requests.
+template <int MODE>
+__device__ __forceinline__ void copy_host_table(const WaveCtx &c, const uint2 *table)
+{
+  const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
+  for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
+    *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(table + i);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // stream ring: 4 slots x 512 B per wave, filled by LDS-DMA (buffer_load_dwordx4 ... lds under EXEC = lanes 0..31:

@@ -89,17 +89,7 @@ __device__ __forceinline__ void run_dealt(const DealtParams &dp, const DealtTabl
   uint64_t t_table = 0, t_ready = 0;
 #endif
   WaveCtx c;
-  c.stream = dp.stream;
-  c.stream_len = dp.stream_len;
-  c.stream_lo = dp.stream_lo;
-  c.out = dp.out;
-  c.out_cap = dp.out_cap;
-  c.status = dp.status;
-  c.bits = dp.bits;
-  c.S = 64;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
+  wave_ctx_begin(c, dp.stream, dp.stream_len, dp.stream_lo, dp.out, dp.out_cap, dp.status, dp.bits, 64);
   const uint32_t table_bytes = table_bytes_for(MODE, c.bits);
   // LDS: [waves x ring][table A][table B][build scratch: 2 x (counts + prefix sums)]
   c.rings = smem + wave * kFastRingBytes;
@@ -329,17 +319,7 @@ __device__ __forceinline__ void run_dealt_rank(const DealtParams &dp, const Deal
   const bool two = split < count;
   const uint32_t N = dp.n_chains;
   WaveCtx c;
-  c.stream = dp.stream;
-  c.stream_len = dp.stream_len;
-  c.stream_lo = dp.stream_lo;
-  c.out = dp.out;
-  c.out_cap = dp.out_cap;
-  c.status = dp.status;
-  c.bits = BITS;
-  c.S = 64;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << BITS) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(BITS));
+  wave_ctx_begin(c, dp.stream, dp.stream_len, dp.stream_lo, dp.out, dp.out_cap, dp.status, BITS, 64);
   if (uni(lds_address(smem)) != 0 || dp.bits != BITS) // (the rank loop's addressing; the launcher picks the kernel by the plan's width)
   {
     if (threadIdx.x == 0)

@@ -58,7 +58,7 @@ __device__ __forceinline__ void run_direct_span(const WaveCtx &c, const KParams 
 #if HSRANS_HAVE_STAMPS
   uint32_t diag_wait = 0, diag_store = 0;
 #endif
-  const bool host_table = (MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) && pa.table != nullptr;
+  const bool host_table = host_table_mode<MODE> && pa.table != nullptr;
   if (kp.finish != nullptr && w == 0 && c.lane == 0) // calibration launches: the launch's time zero
     kp.finish[W] = __builtin_amdgcn_s_memrealtime();
   if (!host_table) // the in-kernel build borrows ring space: it has to come before the first stream request
@@ -69,11 +69,7 @@ __device__ __forceinline__ void run_direct_span(const WaveCtx &c, const KParams 
   // (requesting the table BEFORE the piece record, so that its fetch overlaps that round trip, was measured twice: no gain)
   auto fetch_table = [&]() {
     if (MODE != kModeSpill)
-    {
-      const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
-      for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-        *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
-    }
+      copy_host_table<MODE>(c, pa.table);
     if (check_hist && threadIdx.x < 64)
       check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
     if (MODE != kModeSpill)
@@ -166,16 +162,14 @@ __device__ void run_direct_pair(const WaveCtx &c, const KParams &kp, uint32_t wa
   StreamWin sw;
   Ring ra, rb;
   pair_bind<MODE>(ra, rb, c);
-  const bool host_table = (MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) && pa.table != nullptr;
+  const bool host_table = host_table_mode<MODE> && pa.table != nullptr;
   if (!host_table)
     build_table<MODE, true>(c, pa.hist_off, threadIdx.x, blockDim.x);
   bool table_pending = host_table && MODE != kModeSpill;
   if (host_table && blockIdx.x == 0 && threadIdx.x < 64)
     check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
   auto copy_table = [&]() {
-    const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+    copy_host_table<MODE>(c, pa.table);
     __syncthreads();
   };
   // pair (2w, 2w + 1); a plan with more chain pairs than waves: wave w goes on with chains 2 (w + W), ...  One loop, one call site of the decode body
@@ -255,25 +249,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_d
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   WaveCtx c;
-  c.stream = kp.stream;
-  c.stream_len = kp.stream_len;
-  c.stream_lo = kp.stream_lo;
-  c.out = kp.out;
-  c.out_cap = kp.out_cap;
-  c.status = kp.status;
-  c.bits = kp.pa.bits;
-  c.S = kp.pa.S;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  const uint32_t ring_stride = fast_ring_mode(MODE) ? kFastRingBytes : kWaveRingBytes; // (launch_shape sizes the LDS the same way)
-  uint8_t *ring0 = table_first_mode(MODE) ? smem + table_bytes_for(MODE, c.bits) : smem;
-  c.rings = ring0 + wave * ring_stride;
-  c.table = table_first_mode(MODE) ? smem : smem + waves * ring_stride;
-  c.table_b = c.table;
+  wave_ctx_begin(c, kp.stream, kp.stream_len, kp.stream_lo, kp.out, kp.out_cap, kp.status, kp.pa.bits, kp.pa.S);
+  wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, c.bits, waves), wave);
   c.gtable = kp.pa.table;
-  c.scratch_cnt = (uint16_t *)ring0; // wave 0's ring (no request in flight while a table is built)
-  c.scratch_cum = (uint16_t *)(ring0 + 512);
   const uint32_t chain = blockIdx.x * waves + wave;
   if (c.S == 32)
     run_direct_pair<MODE>(c, kp, waves, chain);
@@ -292,23 +270,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_c
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   WaveCtx c;
-  c.stream = kp.stream;
-  c.stream_len = kp.stream_len;
-  c.stream_lo = kp.stream_lo;
-  c.out = kp.out;
-  c.out_cap = kp.out_cap;
-  c.status = kp.status;
-  c.bits = kp.pa.bits;
-  c.S = kp.pa.S;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  c.rings = smem + wave * kFastRingBytes;
-  c.table = smem + waves * kFastRingBytes;
-  c.table_b = c.table;
+  wave_ctx_begin(c, kp.stream, kp.stream_len, kp.stream_lo, kp.out, kp.out_cap, kp.status, kp.pa.bits, kp.pa.S);
+  wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, c.bits, waves), wave);
   c.gtable = kp.pa.table;
-  c.scratch_cnt = (uint16_t *)smem;
-  c.scratch_cum = (uint16_t *)(smem + 512);
   run_direct<MODE>(c, kp, waves, blockIdx.x * waves + wave);
 }
 

@@ -237,39 +237,15 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(102))) k_
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   WaveCtx c;
-  c.stream = kp.stream;
-  c.stream_len = kp.stream_len;
-  c.stream_lo = kp.stream_lo;
-  c.out = kp.out;
-  c.out_cap = kp.out_cap;
-  c.status = kp.status;
-  c.bits = pa.bits;
-  c.S = 64;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  constexpr uint32_t kDualRing = kFastRingBytes; // whole-chunk mirrors for the hand-scheduled loop (launch_shape sizes the LDS the same way)
-  if (MODE == kModeRank)
+  wave_ctx_begin(c, kp.stream, kp.stream_len, kp.stream_lo, kp.out, kp.out_cap, kp.status, pa.bits, 64);
+  if (MODE == kModeRank && !lds_starts_at_zero(smem))
   {
-    // the rank bytes at LDS address 0 (this kernel has no static LDS): the hand-scheduled group uses the slot as the address
-    if (uni(lds_address(smem)) != 0) // (would decode garbage silently: report instead; the host discards the output)
-    {
-      if (threadIdx.x == 0)
-        atomicOr(kp.status, kStatusOutOfRange);
-      return;
-    }
-    c.table = smem;
-    c.rings = smem + table_bytes_for(MODE, c.bits) + wave * 2 * kDualRing;
+    if (threadIdx.x == 0)
+      atomicOr(kp.status, kStatusOutOfRange);
+    return;
   }
-  else
-  {
-    c.rings = smem + wave * 2 * kDualRing;
-    c.table = smem + waves * 2 * kDualRing;
-  }
-  c.table_b = c.table;
+  wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, c.bits, waves, 2), wave);
   c.gtable = pa.table;
-  c.scratch_cnt = (uint16_t *)smem;
-  c.scratch_cum = (uint16_t *)(smem + 512);
   const uint32_t W = gridDim.x * waves;
   const uint32_t w = blockIdx.x * waves + wave;
   const uint64_t t_entry = HSRANS_STAMPS(kp) ? __builtin_amdgcn_s_memrealtime() : 0;
@@ -278,9 +254,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(102))) k_
   // the host-built table (always: the launcher only picks this kernel for plans that carry their histogram)
   bool table_pending = true;
   auto fetch_table = [&]() {
-    const uint32_t entries = table_bytes_for(MODE, c.bits) / 8;
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+    copy_host_table<MODE>(c, pa.table);
     if (blockIdx.x == 0 && threadIdx.x < 64)
       check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
     __syncthreads();
@@ -298,7 +272,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(102))) k_
     StreamWin sw;
     RingD ra, rb;
     ring_bind(ra.r, c.rings, 9, true);
-    ring_bind(rb.r, c.rings + kDualRing, 9, true);
+    ring_bind(rb.r, c.rings + kFastRingBytes, 9, true);
     uint32_t vm = 0; // vector-memory instructions issued from here on (everything older completes before them anyway)
     win_open(sw, c, da.words, have_b ? db.limit : da.limit); // the two chains are neighbours in the stream: one window
     // what the first groups read first (states, chunks 0 and 1 of both rings, the table), the chunks the rings keep ahead and the

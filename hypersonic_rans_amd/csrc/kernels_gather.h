@@ -194,28 +194,15 @@ __device__ __forceinline__ void gather_setup(WaveCtx &c, const GatherSource &gs,
 {
   const uint32_t waves = blockDim.x >> 6;
 
-  c.stream = gs.stream;
-  c.stream_len = gs.stream_len;
-  c.stream_lo = 0;
-  c.out = nullptr; // (run_gather sets it, task by task)
-  c.out_cap = 0;   // (not used: every store of these kernels is tested against its task)
-  c.status = gs.status;
-  c.bits = bits;
-  c.S = states;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
+  // (no output yet: run_gather sets it, task by task; no capacity: every store of these kernels is tested against its task)
+  wave_ctx_begin(c, gs.stream, gs.stream_len, 0, nullptr, 0, gs.status, bits, states);
 
   if (SHARED)
   {
-    uint8_t *ring0 = table_first_mode(MODE) ? smem + table_bytes : smem;
-    c.rings = ring0 + wave * kWaveRingBytes;
-    c.table = table_first_mode(MODE) ? smem : smem + waves * kWaveRingBytes;
-    c.table_b = c.table;
+    wave_ctx_lds(c, smem, lds_layout_gather(MODE, table_bytes, waves), wave);
     c.gtable = gs.table;
-    c.scratch_cnt = (uint16_t *)ring0;
-    c.scratch_cum = (uint16_t *)(ring0 + 512);
     // the host-built table: one coalesced 16-byte load + LDS store per thread (none for the table that stays in global memory)
+    // (copy_host_table, written out: the call changes the instruction sequences of k_gather<4, true> and k_gather_ranges<4, true>)
     const uint32_t entries = table_bytes_for(MODE, bits) / 8;
     for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
       *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(gs.table + i);

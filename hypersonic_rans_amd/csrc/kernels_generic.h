@@ -203,29 +203,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_d
   const uint32_t table_bytes = table_bytes_for(MODE, bits);
 
   WaveCtx c;
-  c.stream = kp.stream;
-  c.stream_len = kp.stream_len;
-  c.stream_lo = kp.stream_lo;
-  c.out = kp.out;
-  c.out_cap = kp.out_cap;
-  c.status = kp.status;
-  c.bits = bits;
-  c.S = pv.hdr->states;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(bits));
+  wave_ctx_begin(c, kp.stream, kp.stream_len, kp.stream_lo, kp.out, kp.out_cap, kp.status, bits, pv.hdr->states);
 
   const uint32_t chain = blockIdx.x * waves + wave;
 
   if (SHARED)
   {
-    const uint32_t ring_stride = fast_ring_mode(MODE) ? kFastRingBytes : kWaveRingBytes; // (launch_shape sizes the LDS the same way)
-    uint8_t *ring0 = table_first_mode(MODE) ? smem + table_bytes : smem;
-    c.rings = ring0 + wave * ring_stride;
-    c.table = table_first_mode(MODE) ? smem : smem + waves * ring_stride;
-    c.table_b = c.table;
-    c.scratch_cnt = (uint16_t *)ring0;         // wave 0's ring (no request in flight while a table is built)
-    c.scratch_cum = (uint16_t *)(ring0 + 512);
+    wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, bits, waves), wave);
     const uint64_t hist_off = pv.hdr->aux_off; // shared plans: the one histogram every chain uses
     c.gtable = kp.pa.table;
     if (kp.pa.pieces != nullptr)

@@ -278,36 +278,19 @@ __device__ void run_grouped(const WaveCtx &c_in, const PlanView &pv_in, const KP
 // The kernel of the grouped launches (block_/mt_ plans with checkpoints: one workgroup per block, run_grouped) — BASELINE config 4's
 // kernel.  A kernel of its own for the same reason as k_decode_direct: inside k_decode<MODE, true> it shared one register
 // allocation with five other launch shapes (two more VGPRs there are the difference between 8 and 7 waves per SIMD).
-// LDS: [waves x ring][table][2 next-group words, 64 B][table-build scratch, 1 KiB].
+// LDS: [waves x ring][table][2 next-group words, 64 B][table-build scratch, 1 KiB], or with the rank table first:
+// [table][next-group words][build scratch][waves x ring] (lds_layout with kGroupedExtra).
 template <int MODE, bool LEAN, bool PARTS = false>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_decode_grouped(KParams kp)
 {
   extern __shared__ u32x4 smem_v[];
-  uint8_t *smem = (uint8_t *)smem_v;
   const PlanView pv = plan_view(kp.plan);
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   WaveCtx c;
-  c.stream = kp.stream;
-  c.stream_len = kp.stream_len;
-  c.stream_lo = kp.stream_lo;
-  c.out = kp.out;
-  c.out_cap = kp.out_cap;
-  c.status = kp.status;
-  c.bits = pv.hdr->bits;
-  c.S = pv.hdr->states;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  const uint32_t ring_stride = fast_ring_mode(MODE) ? kFastRingBytes : kWaveRingBytes; // (launch_shape sizes the LDS the same way)
-  // [rings][table][next-group words][build scratch], or with the table first: [table][next-group words][build scratch][rings]
-  c.rings = (table_first_mode(MODE) ? smem + table_bytes_for(MODE, c.bits) + 64 + 1024 : smem) + wave * ring_stride;
-  c.table = table_first_mode(MODE) ? smem : smem + waves * ring_stride;
-  c.table_b = c.table;
+  wave_ctx_begin(c, kp.stream, kp.stream_len, kp.stream_lo, kp.out, kp.out_cap, kp.status, pv.hdr->bits, pv.hdr->states);
+  wave_ctx_lds(c, (uint8_t *)smem_v, lds_layout(MODE, c.bits, waves, 1, kGroupedExtra), wave);
   c.gtable = nullptr;
-  // the table build's scratch has an area of its own: a round's first stream chunks are requested before its table is built
-  c.scratch_cnt = (uint16_t *)(c.table + table_bytes_for(MODE, c.bits) + 64);
-  c.scratch_cum = c.scratch_cnt + 256;
   run_grouped<MODE, LEAN, false, false, PARTS>(c, pv, kp, waves, wave);
 }
 
@@ -317,28 +300,12 @@ template <int MODE>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_decode_grouped_batch(BatchGroupParams bp)
 {
   extern __shared__ u32x4 smem_v[];
-  uint8_t *smem = (uint8_t *)smem_v;
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   WaveCtx c;
-  c.stream = nullptr; // (set per round from the group's member)
-  c.stream_len = 0;
-  c.stream_lo = 0;
-  c.out = nullptr;
-  c.out_cap = 0;
-  c.status = nullptr;
-  c.bits = bp.bits;
-  c.S = 64;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  const uint32_t ring_stride = fast_ring_mode(MODE) ? kFastRingBytes : kWaveRingBytes;
-  c.rings = smem + wave * ring_stride;
-  c.table = smem + waves * ring_stride;
-  c.table_b = c.table;
+  wave_ctx_begin(c, nullptr, 0, 0, nullptr, 0, nullptr, bp.bits, 64); // (stream, output and status are set per round from the group's member)
+  wave_ctx_lds(c, (uint8_t *)smem_v, lds_layout(MODE, c.bits, waves, 1, kGroupedExtra), wave);
   c.gtable = nullptr;
-  c.scratch_cnt = (uint16_t *)(c.table + table_bytes_for(MODE, c.bits) + 64);
-  c.scratch_cum = c.scratch_cnt + 256;
   KParams kp{}; // (nothing of it is read in the BATCH instantiation but the stamps pointer: null)
   PlanView pv{};
   run_grouped<MODE, true, false, true>(c, pv, kp, waves, wave, &bp);

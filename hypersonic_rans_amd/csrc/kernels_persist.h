@@ -59,7 +59,7 @@ __device__ void run_persistent(const WaveCtx &c, const KParams &kp, uint32_t wav
   const uint32_t cls = half * 4 + wave_in_wg / per_class;
   const uint32_t q0 = pa.run_len[cls];
   const uint32_t c_first = pa.half_base[half] + (blk - half * first_half) * pa.wg_chains[half] + pa.class_off[cls] + (wave_in_wg % per_class) * q0;
-  const bool host_table = (MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) && pa.table != nullptr; // kModeRank / kModeSpill are host-built only
+  const bool host_table = host_table_mode<MODE> && pa.table != nullptr; // kModeRank / kModeSpill are host-built only
   if (!host_table) // the in-kernel build borrows ring space: it has to come before the first stream request
     build_table<MODE, true>(c, pa.hist_off, threadIdx.x, blockDim.x);
   if (q0 != 0)
@@ -68,9 +68,7 @@ __device__ void run_persistent(const WaveCtx &c, const KParams &kp, uint32_t wav
   {
     // the table was built on the host from the plan's histogram copy: one coalesced 16 B load + LDS store per thread,
     // while the first wave checks that the stream really carries that histogram (else: status, as a failed sum check)
-    const uint32_t entries = table_bytes_for(MODE, c.bits) / 8; // (0 for the spilled table: it stays in global memory)
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+    copy_host_table<MODE>(c, pa.table);
     if (blockIdx.x == 0 && threadIdx.x < 64)
       check_hist_copy<true>(c, pa.hist_copy, pa.hist_off);
     __syncthreads();
@@ -142,7 +140,7 @@ __device__ void run_persistent_pair(const WaveCtx &c, const KParams &kp, uint32_
   const uint32_t cls = half * 4 + wave_in_wg / per_class;
   const uint32_t q0 = pa.run_len[cls];
   const uint32_t c_first = pa.half_base[half] + (blk - half * first_half) * pa.wg_chains[half] + pa.class_off[cls] + (wave_in_wg % per_class) * 2 * q0;
-  const bool host_table = (MODE == kModePack64 || MODE == kModeRank || MODE == kModeSpill) && pa.table != nullptr;
+  const bool host_table = host_table_mode<MODE> && pa.table != nullptr;
   if (!host_table)
     build_table<MODE, true>(c, pa.hist_off, threadIdx.x, blockDim.x);
 
@@ -172,9 +170,7 @@ __device__ void run_persistent_pair(const WaveCtx &c, const KParams &kp, uint32_
     {
       // the table was built on the host from the plan's histogram copy: one coalesced 16 B load + LDS store per thread
       // (see run_persistent for the check of the copy against the stream)
-      const uint32_t entries = table_bytes_for(MODE, c.bits) / 8; // (0 for the spilled table)
-      for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-        *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+      copy_host_table<MODE>(c, pa.table);
       __syncthreads();
     }
     ring_ready(x);
@@ -199,9 +195,7 @@ __device__ void run_persistent_pair(const WaveCtx &c, const KParams &kp, uint32_
     run(c_first, c_first + q0, c_first + 2 * q0, host_table);
   else if (host_table)
   {
-    const uint32_t entries = table_bytes_for(MODE, c.bits) / 8; // (0 for the spilled table)
-    for (uint32_t i = threadIdx.x * 2; i < entries; i += blockDim.x * 2)
-      *(u32x4 *)(c.table + (uint64_t)i * 8) = *(const u32x4 *)(pa.table + i);
+    copy_host_table<MODE>(c, pa.table);
     __syncthreads();
   }
 
@@ -235,24 +229,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) k_d
   const uint32_t waves = blockDim.x >> 6;
   const uint32_t wave = uni(threadIdx.x >> 6);
   WaveCtx c;
-  c.stream = kp.stream;
-  c.stream_len = kp.stream_len;
-  c.stream_lo = kp.stream_lo;
-  c.out = kp.out;
-  c.out_cap = kp.out_cap;
-  c.status = kp.status;
-  c.bits = kp.pa.bits;
-  c.S = kp.pa.S;
-  c.lane = threadIdx.x & 63;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_mask) : "s"((1u << c.bits) - 1));
-  asm volatile("v_mov_b32 %0, %1" : "=v"(c.v_bits) : "s"(c.bits));
-  uint8_t *ring0 = table_first_mode(MODE) ? smem + table_bytes_for(MODE, c.bits) : smem;
-  c.rings = ring0 + wave * kFastRingBytes;
-  c.table = table_first_mode(MODE) ? smem : smem + waves * kFastRingBytes;
-  c.table_b = c.table;
+  wave_ctx_begin(c, kp.stream, kp.stream_len, kp.stream_lo, kp.out, kp.out_cap, kp.status, kp.pa.bits, kp.pa.S);
+  wave_ctx_lds<MODE>(c, smem, lds_layout(MODE, c.bits, waves), wave);
   c.gtable = kp.pa.table;
-  c.scratch_cnt = (uint16_t *)ring0;
-  c.scratch_cum = (uint16_t *)(ring0 + 512);
   const uint32_t chain = blockIdx.x * waves + wave;
   if (c.S == 32)
     run_persistent_pair<MODE, true>(c, kp, waves, chain);

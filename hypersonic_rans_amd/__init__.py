@@ -34,9 +34,11 @@ from .api import (  # noqa: F401
     gather_batch_workspace_bytes,
     gather_batch_tasks,
     GatherSet,
+    IndexingMember,
+    IndexingBatchStats,
 )
 
 __all__ = [
     "RAW", "BLOCK", "MT", "Context", "HsransError", "capacity", "encode", "block_choices", "BLOCK_CHOICE", "make_hist", "plan_build", "plan_chain_count",
-    "plan_chain_range", "plan_decoded_length", "plan_slice", "plan_stream_ranges", "plan_thin", "index_boundaries", "batch_deal", "index_boundaries_batch", "gather_segment", "gather_tasks", "gather_workspace_bytes", "gather_batch_workspace_bytes", "gather_batch_tasks", "GatherSet", "lib_path", "load_library",
+    "plan_chain_range", "plan_decoded_length", "plan_slice", "plan_stream_ranges", "plan_thin", "index_boundaries", "batch_deal", "index_boundaries_batch", "gather_segment", "gather_tasks", "gather_workspace_bytes", "gather_batch_workspace_bytes", "gather_batch_tasks", "GatherSet", "IndexingMember", "IndexingBatchStats", "lib_path", "load_library",
 ]

@@ -43,6 +43,16 @@ class EncodeBatchStats(ctypes.Structure):
     _fields_ = [(n, _u32) for n in ("launches", "raw_members", "mt_members", "mt_blocks")]
 
 
+class IndexingMember(ctypes.Structure):
+    """hsrans_indexing_member: one stream of hsrans_decode_device_indexing_batch"""
+    _fields_ = [("dplan", _vp), ("d_stream", _vp), ("stream_length", _sz), ("d_out", _vp), ("out_capacity", _sz), ("index_interval", _u32), ("rc", _i),
+                ("indexed", _vp)]
+
+
+class IndexingBatchStats(ctypes.Structure):
+    _fields_ = [(n, _u32) for n in ("launches", "walk_members", "mt_members", "tasks")]
+
+
 class Calibration(ctypes.Structure):
     _fields_ = [("class_weights", _u32 * 8), ("class_finish_us_last_iteration", ctypes.c_double * 8), ("last_wave_us_before", ctypes.c_double),
                 ("last_wave_us_after", ctypes.c_double), ("class_spread_us_before", ctypes.c_double), ("class_spread_us_after", ctypes.c_double),
@@ -191,6 +201,8 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_decode_device_indexing.restype = _i
     L.hsrans_decode_device_indexing.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _u32, _vp, ctypes.POINTER(_vp)]
     L.hsrans_ctx_calibrate.restype = _i
+    L.hsrans_decode_device_indexing_batch.restype = _i
+    L.hsrans_decode_device_indexing_batch.argtypes = [_vp, ctypes.POINTER(IndexingMember), _u32, _vp, ctypes.POINTER(IndexingBatchStats)]
     L.hsrans_ctx_calibrate.argtypes = [_vp, _u32, _u32, ctypes.POINTER(Calibration)]
     L.hsrans_dplan_batch_create.restype = _i
     L.hsrans_dplan_batch_create.argtypes = [_vp, _vp, _u32, ctypes.POINTER(_vp)]
@@ -1041,6 +1053,50 @@ class Context:
         if rc != 0:
             raise HsransError(f"hsrans_decode_device_indexing failed with code {rc}")
         return DevicePlan(self, h)
+
+    def decode_device_indexing_batch(self, members, stream: torch.cuda.Stream | None = None, stats: dict | None = None):
+        """The first decode of many streams in one call (hsrans_decode_device_indexing_batch): member k is ``(dplan, d_stream, d_out,
+        index_interval)`` or ``(dplan, d_stream, d_out, index_interval, stream_length)`` — a block_ stream's walk plan or an mt_ base
+        plan, uint8 CUDA tensors on one device — and gets what :meth:`decode_device_indexing` gives it.  Returns the list of indexed
+        DevicePlans.  ``stats``: filled with hsrans_indexing_batch_stats.  Raises HsransError when any member failed; the error
+        carries ``code``, ``codes`` (per member) and ``plans`` (a DevicePlan or None per member: what the members that did not
+        fail got).  Synchronises ``stream``."""
+        members = list(members)
+        dev = None
+        for k, m in enumerate(members):
+            if not isinstance(m, (tuple, list)) or len(m) not in (4, 5):
+                raise TypeError(f"decode_device_indexing_batch: member {k}: (dplan, d_stream, d_out, index_interval[, stream_length]) expected")
+            if not isinstance(m[0], DevicePlan):
+                raise TypeError(f"decode_device_indexing_batch: member {k}: a DevicePlan expected")
+            for name, t in (("d_stream", m[1]), ("d_out", m[2])):
+                if not getattr(t, "is_cuda", False) or t.dtype != torch.uint8 or not t.is_contiguous():
+                    raise TypeError(f"decode_device_indexing_batch: member {k}: {name} must be a contiguous uint8 CUDA tensor")
+                dev = t.device if dev is None else dev
+                if t.device != dev:
+                    raise TypeError(f"decode_device_indexing_batch: member {k}: {name} is on {t.device}, the others on {dev}")
+            if not isinstance(m[3], int) or (len(m) == 5 and not isinstance(m[4], int)):
+                raise TypeError(f"decode_device_indexing_batch: member {k}: index_interval and stream_length are integers")
+        K = len(members)
+        arr = (IndexingMember * max(K, 1))()
+        for k, m in enumerate(members):
+            e = arr[k]
+            e.dplan, e.d_stream, e.d_out, e.index_interval = m[0].handle, m[1].data_ptr(), m[2].data_ptr(), m[3]
+            e.stream_length, e.out_capacity = (m[4] if len(m) == 5 else m[1].numel()), m[2].numel()
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        st = IndexingBatchStats()
+        rc = self.L.hsrans_decode_device_indexing_batch(self.handle, arr, K, ctypes.c_void_p(s.cuda_stream), ctypes.byref(st))
+        if stats is not None:
+            stats.update({n: getattr(st, n) for n, _ in IndexingBatchStats._fields_})
+        if rc != 0 and K == 0:
+            raise HsransError(f"hsrans_decode_device_indexing_batch failed with code {rc}")
+        codes = [int(arr[k].rc) for k in range(K)]
+        plans = [DevicePlan(self, _vp(arr[k].indexed)) if arr[k].indexed else None for k in range(K)]
+        if rc != 0:
+            failed = [k for k in range(K) if codes[k] != 0]
+            err = HsransError(f"hsrans_decode_device_indexing_batch failed with code {rc}" + (f": member {failed[0]} failed" if failed and rc not in (2, 4) else ""))
+            err.code, err.codes, err.plans = rc, codes, plans
+            raise err
+        return plans
 
     def decode_device_window(self, dplan: DevicePlan, d_window: torch.Tensor, window_offset: int, window_length: int, d_out: torch.Tensor,
                              stream: torch.cuda.Stream | None = None):

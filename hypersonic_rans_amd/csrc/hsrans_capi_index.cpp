@@ -69,24 +69,7 @@ static bool add_interval_chains(PlanBuilder &pb, const IndexSource &src, uint32_
 }
 
 // ---- what every recording pass shares ------------------------------------------------------------------------------------------------
-// What a recording pass writes besides the output: checkpoint states and read cursors, and for a block_ walk the block records, the states
-// on entry to each block and the block count.  Byte counts of the first four.
-struct PassBytes
-{
-  size_t st, wd, blk, bst;
-  size_t all() const { return st + wd + blk + bst; }
-};
-struct PassBuffers // device
-{
-  uint32_t *ck_states;
-  uint64_t *ck_words;
-  uint64_t *walk_blocks; // null: not a walk
-  uint32_t *walk_states, *walk_count;
-  uint32_t max_blocks;
-};
-static PassBytes pass_bytes(uint64_t n_ck, uint32_t S, uint64_t max_blocks) { return {(size_t)n_ck * S * 4, (size_t)n_ck * 8, (size_t)max_blocks * 24, (size_t)max_blocks * S * 4}; }
-// room for blocks of >= 4 KiB on average (the reference's smallest block is 32 KiB, block_rANS32x64_16w_encode.cpp:21-39); a stream with more gets no plan
-static uint64_t walk_max_blocks(uint64_t decoded_len) { return decoded_len / 4096 + 16; }
+// (PassBytes, PassBuffers, pass_bytes and walk_max_blocks — what a recording pass writes besides the output — are in hsrans_internal.h: the batch's too)
 
 // The pass: the base plan (blob and status word on the device, header h) decodes d_stream into d_out and records {states, read cursor} every
 // `interval` groups, or (interval 0) at the n_groups ascending groups of d_groups; a walk plan also records its blocks.
@@ -151,8 +134,6 @@ static bool add_walk_chains(PlanBuilder &pb, const PassBytes &pbytes, const uint
   const IndexSource src{n_blocks, nullptr, nullptr, nullptr, (const uint64_t *)host_walk, (const uint32_t *)(host_walk + pbytes.blk), pb.hdr.decoded_len};
   return add_interval_chains(pb, src, interval, (const uint32_t *)host_ck, (const uint64_t *)(host_ck + pbytes.st));
 }
-
-static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 static size_t index_build_impl(hsrans_ctx *ctx, int container, int states, uint32_t bits, const uint8_t *in, size_t in_length, uint32_t index_interval,
                                const uint64_t *groups, size_t n_groups, uint8_t *plan_out, size_t plan_capacity)
@@ -314,10 +295,8 @@ static bool context_checkpoints(hsrans_ctx *ctx, const PassBytes &pbytes, PassBu
   return true;
 }
 
-// The plan a device assembly writes, with room for max_chains chains and max_groups groups.  Its arena's scratch: the assembly's IndexResult
-// (and at +128 a walk's block count), from +256 `off_words` chain / group offsets, behind them (16-byte aligned) `extra` bytes.  null: no memory
-constexpr size_t kAssemblyCount = 128, kAssemblyOffsets = 256;
-static hsrans_dplan *assembly_plan(hsrans_ctx *ctx, uint32_t S, uint32_t max_chains, size_t max_groups, size_t off_words, size_t extra, hipStream_t s, uint8_t **scratch)
+// (hsrans_internal.h: the plan a device assembly writes, and its arena's scratch)
+extern "C++" hsrans_dplan *assembly_plan(hsrans_ctx *ctx, uint32_t S, uint32_t max_chains, size_t max_groups, size_t off_words, size_t extra, hipStream_t s, uint8_t **scratch)
 {
   hsrans_dplan *nd = dplan_new(ctx);
   if (nd == nullptr)
@@ -336,19 +315,16 @@ static hsrans_dplan *assembly_plan(hsrans_ctx *ctx, uint32_t S, uint32_t max_cha
   return nd;
 }
 
-// Behind the pass and the assembly kernels (`queued`: all of them were): what the count kernel left comes back with the base plan d's status
-// word, is checked against the bounds, and nd takes over the plan the device wrote.  One synchronisation — nothing queued may still be running
-// when this returns, whatever failed; on failure nd is destroyed.
-static int finish_assembly(hsrans_dplan *d, hsrans_dplan *nd, bool queued, const IndexResult *d_result, uint32_t interval, uint32_t min_chains, uint32_t max_chains,
-                           uint32_t max_groups, hipStream_t s, IndexResult *r)
+// finish_assembly's halves (hsrans_internal.h), to run around one synchronisation
+extern "C++" bool assembly_copy_down(const hsrans_dplan *d, const IndexResult *d_result, hipStream_t s, IndexResult *r, uint32_t *status)
 {
-  uint32_t status = 0xFFFFFFFF;
-  const bool ok = queued && hipMemcpyAsync(r, d_result, sizeof(*r), hipMemcpyDeviceToHost, s) == hipSuccess &&
-                  hipMemcpyAsync(&status, d->d_status, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
-  const bool synced = hipStreamSynchronize(s) == hipSuccess;
-  int rc = ok && synced ? pass_status_rc(status, d->d_status, s) : HSRANS_E_HIP;
+  return hipMemcpyAsync(r, d_result, sizeof(*r), hipMemcpyDeviceToHost, s) == hipSuccess && hipMemcpyAsync(status, d->d_status, 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+}
+extern "C++" int assembly_adopt(const hsrans_dplan *d, hsrans_dplan *nd, int rc, const IndexResult &r, uint32_t interval, uint32_t min_chains, uint32_t max_chains,
+                                uint32_t max_groups, hipStream_t s, const Group *host_groups)
+{
   // no plan: IndexResult::error, no chains, or more chains / groups than the arena has room for
-  if (rc == HSRANS_OK && (r->error != 0 || r->chains < min_chains || r->chains > max_chains || r->groups > max_groups))
+  if (rc == HSRANS_OK && (r.error != 0 || r.chains < min_chains || r.chains > max_chains || r.groups > max_groups))
     rc = HSRANS_E_FORMAT;
   if (rc != HSRANS_OK)
   {
@@ -358,12 +334,96 @@ static int finish_assembly(hsrans_dplan *d, hsrans_dplan *nd, bool queued, const
   }
   PlanHeader hn = d->hdr;
   hn.flags = 0;
-  hn.n_chains = hn.n_pieces = r->chains;
+  hn.n_chains = hn.n_pieces = r.chains;
   hn.interval = interval;
-  hn.shared_hist = r->coded == 1 ? 1 : 0;
-  hn.aux_off = hn.shared_hist ? r->hist_off : 0;
-  dplan_adopt(nd, hn, r->groups, r->fewest, s); // (kIndexNoFewest is the largest spread_min_block a plan keeps)
+  hn.shared_hist = r.coded == 1 ? 1 : 0;
+  hn.aux_off = hn.shared_hist ? r.hist_off : 0;
+  dplan_adopt(nd, hn, r.groups, r.fewest, s, host_groups); // (kIndexNoFewest is the largest spread_min_block a plan keeps)
   return HSRANS_OK;
+}
+
+// Behind the pass and the assembly kernels (`queued`: all of them were): what the count kernel left comes back with the base plan d's status
+// word, is checked against the bounds, and nd takes over the plan the device wrote.  One synchronisation — nothing queued may still be running
+// when this returns, whatever failed; on failure nd is destroyed.
+static int finish_assembly(hsrans_dplan *d, hsrans_dplan *nd, bool queued, const IndexResult *d_result, uint32_t interval, uint32_t min_chains, uint32_t max_chains,
+                           uint32_t max_groups, hipStream_t s, IndexResult *r)
+{
+  uint32_t status = 0xFFFFFFFF;
+  const bool ok = queued && assembly_copy_down(d, d_result, s, r, &status);
+  const bool synced = hipStreamSynchronize(s) == hipSuccess;
+  return assembly_adopt(d, nd, ok && synced ? pass_status_rc(status, d->d_status, s) : HSRANS_E_HIP, *r, interval, min_chains, max_chains, max_groups, s);
+}
+
+// The sizes of a block_ member's first decode, its pass buffers and the arguments of its assembly kernels (hsrans_internal.h)
+extern "C++" bool walk_assembly_sizes(const PlanHeader &h, uint32_t interval, WalkAssemblySizes *z)
+{
+  z->n_ck = pass_checkpoints(h.decoded_len, h.states, interval);
+  z->max_blocks = walk_max_blocks(h.decoded_len);
+  z->max_chains = z->max_blocks + z->n_ck;
+  z->max_groups = z->max_blocks + z->max_chains / kGroupPartChains + 16;
+  z->pbytes = pass_bytes(z->n_ck, h.states, z->max_blocks);
+  return z->max_chains <= 0xFFFFFFF0u;
+}
+extern "C++" void walk_assembly_args(const hsrans_ctx *ctx, const hsrans_dplan *d, const hsrans_dplan *nd, uint8_t *scratch, uint32_t interval, const WalkAssemblySizes &z,
+                                     PassBuffers *pass, WalkIndexArgs *wa)
+{
+  const PlanHeader &h = d->hdr;
+  uint32_t *d_offsets = (uint32_t *)(scratch + kAssemblyOffsets);
+  pass->walk_count = (uint32_t *)(scratch + kAssemblyCount);
+  pass->walk_blocks = (uint64_t *)(scratch + kAssemblyOffsets + up16(2 * (size_t)z.max_blocks * 4));
+  pass->walk_states = (uint32_t *)((uint8_t *)pass->walk_blocks + z.pbytes.blk);
+  pass->max_blocks = (uint32_t)z.max_blocks;
+  *wa = WalkIndexArgs{};
+  wa->base = d->d_plan;
+  wa->walk_count = pass->walk_count;
+  wa->walk_blocks = pass->walk_blocks;
+  wa->walk_states = pass->walk_states;
+  wa->ck_states = pass->ck_states;
+  wa->ck_words = pass->ck_words;
+  wa->S = h.states;
+  wa->interval = interval;
+  wa->max_blocks = (uint32_t)z.max_blocks;
+  wa->max_chains = (uint32_t)z.max_chains;
+  wa->max_groups = (uint32_t)z.max_groups;
+  wa->parts_want = kGroupPartsPerCU * ctx->geom.num_cus;
+  wa->decoded_len = h.decoded_len;
+  wa->stream_len = h.stream_len;
+  wa->chain_off = d_offsets;
+  wa->group_off = d_offsets + z.max_blocks;
+  wa->result = (IndexResult *)scratch;
+  wa->plan = nd->d_plan;
+  wa->groups = (Group *)nd->d_groups;
+}
+// ... and an mt_ member's
+extern "C++" MtAssemblySizes mt_assembly_sizes(const hsrans_ctx *ctx, const PlanHeader &h, uint32_t interval)
+{
+  MtAssemblySizes z{};
+  z.n_ck = pass_checkpoints(h.decoded_len, h.states, interval);
+  z.pbytes = pass_bytes(z.n_ck, h.states, 0);
+  z.max_chains = (uint32_t)std::min<uint64_t>((uint64_t)h.n_chains + z.n_ck, 0xFFFFFFF0u);
+  // at most one group per block, and where there are few every block's chains in parts of >= kGroupPartChains chains (as dplan_fill)
+  z.max_groups = (uint32_t)std::min<uint64_t>((uint64_t)h.n_chains + z.max_chains / kGroupPartChains + 16, 0xFFFFFFF0u);
+  return z;
+}
+extern "C++" void mt_assembly_args(const hsrans_ctx *ctx, const hsrans_dplan *d, const hsrans_dplan *nd, uint8_t *scratch, uint32_t interval, const MtAssemblySizes &z, const PassBuffers &pass,
+                                   IndexArgs *ia)
+{
+  *ia = IndexArgs{};
+  ia->base = d->d_plan;
+  ia->n_base = d->hdr.n_chains;
+  ia->S = d->hdr.states;
+  ia->interval = interval;
+  ia->ck_states = pass.ck_states;
+  ia->ck_words = pass.ck_words;
+  ia->chain_off = (uint32_t *)(scratch + kAssemblyOffsets);
+  ia->group_off = ia->chain_off + d->hdr.n_chains;
+  ia->result = (IndexResult *)scratch;
+  ia->plan = nd->d_plan;
+  ia->max_chains = z.max_chains;
+  ia->max_groups = z.max_groups;
+  ia->groups = (Group *)nd->d_groups;
+  ia->parts_want = kGroupPartsPerCU * ctx->geom.num_cus;
+  ia->stream_len = d->hdr.stream_len;
 }
 
 // hsrans_decode_device_indexing for a block_ stream's walk plan (d: kPlanWalk, one chain, no checkpoints; the arguments are checked).  The one
@@ -375,26 +435,23 @@ static int decode_walk_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
 {
   const PlanHeader &h = d->hdr;
   const uint32_t S = h.states;
-  const uint64_t n_ck = h.decoded_len / S / index_interval + 2;
-  const uint64_t max_blocks = walk_max_blocks(h.decoded_len), max_chains = max_blocks + n_ck, max_groups = max_blocks + max_chains / kGroupPartChains + 16;
-  if (max_chains > 0xFFFFFFF0u)
+  WalkAssemblySizes z;
+  if (!walk_assembly_sizes(h, index_interval, &z))
     return HSRANS_E_FORMAT;
+  const uint64_t n_ck = z.n_ck, max_chains = z.max_chains, max_groups = z.max_groups;
   std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer belongs to the context)
   if (!have_lock)
     guard.lock();
-  const PassBytes pbytes = pass_bytes(n_ck, S, max_blocks);
+  const PassBytes &pbytes = z.pbytes;
   PassBuffers pass{};
   if (!context_checkpoints(ctx, pbytes, &pass))
     return HSRANS_E_HIP;
   uint8_t *scratch = nullptr;
-  hsrans_dplan *nd = assembly_plan(ctx, S, (uint32_t)max_chains, (size_t)max_groups, 2 * (size_t)max_blocks, pbytes.blk + pbytes.bst, s, &scratch);
+  hsrans_dplan *nd = assembly_plan(ctx, S, (uint32_t)max_chains, (size_t)max_groups, 2 * (size_t)z.max_blocks, pbytes.blk + pbytes.bst, s, &scratch);
   if (nd == nullptr)
     return HSRANS_E_HIP;
-  uint32_t *d_offsets = (uint32_t *)(scratch + kAssemblyOffsets);
-  pass.walk_count = (uint32_t *)(scratch + kAssemblyCount);
-  pass.walk_blocks = (uint64_t *)(scratch + kAssemblyOffsets + up16(2 * (size_t)max_blocks * 4));
-  pass.walk_states = (uint32_t *)((uint8_t *)pass.walk_blocks + pbytes.blk);
-  pass.max_blocks = (uint32_t)max_blocks;
+  WalkIndexArgs wa;
+  walk_assembly_args(ctx, d, nd, scratch, index_interval, z, &pass, &wa);
   const bool passed = launch_recording_pass(ctx, d->d_plan, d->d_status, h, d_stream, stream_length, d_out, out_capacity, index_interval, nullptr, 0, pass, s) == hipSuccess;
 
   if (passed && ctx->tuning.index_assemble_on_host)
@@ -417,26 +474,6 @@ static int decode_walk_indexing(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
     return plan_bytes == 0 ? HSRANS_E_FORMAT : hsrans_dplan_create(ctx, plan.data(), plan_bytes, indexed);
   }
 
-  WalkIndexArgs wa{};
-  wa.base = d->d_plan;
-  wa.walk_count = pass.walk_count;
-  wa.walk_blocks = pass.walk_blocks;
-  wa.walk_states = pass.walk_states;
-  wa.ck_states = pass.ck_states;
-  wa.ck_words = pass.ck_words;
-  wa.S = S;
-  wa.interval = index_interval;
-  wa.max_blocks = (uint32_t)max_blocks;
-  wa.max_chains = (uint32_t)max_chains;
-  wa.max_groups = (uint32_t)max_groups;
-  wa.parts_want = kGroupPartsPerCU * ctx->geom.num_cus;
-  wa.decoded_len = h.decoded_len;
-  wa.stream_len = h.stream_len;
-  wa.chain_off = d_offsets;
-  wa.group_off = d_offsets + max_blocks;
-  wa.result = (IndexResult *)scratch;
-  wa.plan = nd->d_plan;
-  wa.groups = (Group *)nd->d_groups;
   IndexResult res{};
   const int rc = finish_assembly(d, nd, passed && launch_index_assemble_walk(wa, s) == hipSuccess, wa.result, index_interval, 1, (uint32_t)max_chains, (uint32_t)max_groups, s, &res);
   if (rc != HSRANS_OK)
@@ -465,18 +502,14 @@ extern "C++" int decode_device_indexing_impl(hsrans_ctx *ctx, hsrans_dplan *d, c
                                        uint32_t index_interval, void *hip_stream, hsrans_dplan **indexed, bool have_lock)
 try
 {
-  if (ctx == nullptr || d == nullptr || d_stream == nullptr || d_out == nullptr || indexed == nullptr || d->ctx != ctx)
+  if (indexed == nullptr)
     return HSRANS_E_ARG;
   *indexed = nullptr;
-  if (((uintptr_t)d_stream & 15) != 0 || ((uintptr_t)d_out & 3) != 0 || index_interval == 0 || (index_interval % 4) != 0)
-    return HSRANS_E_ARG;
+  const int checked = indexing_args_check(ctx, d, d_stream, stream_length, d_out, out_capacity, index_interval);
+  if (checked != HSRANS_OK)
+    return checked;
   const PlanHeader &h = d->hdr;
-  // base plans only: one single-piece chain per block (raw: one chain), or a block_ stream's walk plan (one chain that follows the inline headers)
   const bool walk = (h.flags & kPlanWalk) != 0;
-  if (h.n_pieces != h.n_chains || h.interval != 0 || d->d_plan == nullptr || d->plan_bytes == 0 || (walk && (h.container != HSRANS_BLOCK || h.n_chains != 1)))
-    return HSRANS_E_ARG;
-  if (stream_length < h.stream_len || out_capacity < h.decoded_len)
-    return HSRANS_E_FORMAT;
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
@@ -487,45 +520,32 @@ try
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto t0 = now();
   const uint32_t S = h.states;
-  const uint64_t n_ck = h.decoded_len / S / index_interval + 2;
+  const MtAssemblySizes z = mt_assembly_sizes(ctx, h, index_interval);
+  const uint64_t n_ck = z.n_ck;
   std::unique_lock<std::mutex> guard(ctx->lock, std::defer_lock); // (the checkpoint buffer and the staging belong to the context)
   if (!have_lock)
     guard.lock();
-  const PassBytes pbytes = pass_bytes(n_ck, S, 0);
+  const PassBytes &pbytes = z.pbytes;
   PassBuffers pass{};
   if (!context_checkpoints(ctx, pbytes, &pass))
     return HSRANS_E_HIP;
-  const uint32_t max_chains = (uint32_t)std::min<uint64_t>((uint64_t)h.n_chains + n_ck, 0xFFFFFFF0u);
+  const uint32_t max_chains = z.max_chains;
   // mt_ streams (one single-piece chain per block, histograms in the stream): the indexed plan is assembled ON THE DEVICE behind the
   // recording pass — one allocation, three launches, one synchronisation; nothing but an IndexResult comes back to the host
   // (HSRANS_INDEX_ASSEMBLE_ON_HOST=1: checkpoints down, blob built by one core, blob up — still what raw plans take)
-  if (h.container == HSRANS_MT && (h.flags & (kPlanWalk | kPlanHasHist | kPlanMergeable)) == 0 && !ctx->tuning.index_assemble_on_host)
+  if (indexing_mt_on_device(h) && !ctx->tuning.index_assemble_on_host)
   {
     const uint32_t nb = h.n_chains;
-    // few large blocks: every block's chains in parts (at most 64 parts a block), as dplan_fill
-    const uint32_t group_split = group_parts_of((uint32_t)std::min<uint64_t>(n_ck / nb + 1, 0xFFFFFFFFu), std::min(group_parts_max(ctx->geom, nb), 64u));
     uint8_t *scratch = nullptr;
-    hsrans_dplan *nd = assembly_plan(ctx, S, max_chains, (size_t)nb * group_split, nb, 0, s, &scratch);
+    hsrans_dplan *nd = assembly_plan(ctx, S, max_chains, z.max_groups, 2 * (size_t)nb, 0, s, &scratch);
     if (nd == nullptr)
       return HSRANS_E_HIP;
-    IndexArgs ia{};
-    ia.base = d->d_plan;
-    ia.n_base = nb;
-    ia.S = S;
-    ia.interval = index_interval;
-    ia.ck_states = pass.ck_states;
-    ia.ck_words = pass.ck_words;
-    ia.chain_off = (uint32_t *)(scratch + kAssemblyOffsets);
-    ia.result = (IndexResult *)scratch;
-    ia.plan = nd->d_plan;
-    ia.max_chains = max_chains;
-    ia.groups = (Group *)nd->d_groups;
-    ia.group_split = group_split;
-    ia.stream_len = h.stream_len;
+    IndexArgs ia;
+    mt_assembly_args(ctx, d, nd, scratch, index_interval, z, pass, &ia);
     const bool queued = launch_recording_pass(ctx, d->d_plan, d->d_status, h, d_stream, stream_length, d_out, out_capacity, index_interval, nullptr, 0, pass, s) == hipSuccess &&
                         launch_index_assemble(ia, s) == hipSuccess;
     IndexResult res{};
-    const int rc = finish_assembly(d, nd, queued, ia.result, index_interval, nb, max_chains, nb * group_split, s, &res);
+    const int rc = finish_assembly(d, nd, queued, ia.result, index_interval, nb, max_chains, z.max_groups, s, &res);
     if (rc != HSRANS_OK)
       return rc;
     if (trace)

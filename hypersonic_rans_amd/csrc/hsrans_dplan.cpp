@@ -310,7 +310,7 @@ extern "C++" int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_si
 
 // Plans written on the device (the GPU encoder's, an indexing decode's) have their group list there: a block's parts are consecutive groups of one
 // histogram.  One small copy (32 bytes a group) at plan creation gives k_decode_dealt's dealing the blocks as chain ranges.
-static void dplan_blocks_from_device_groups(hsrans_dplan *d, hipStream_t s)
+static void dplan_blocks_from_device_groups(hsrans_dplan *d, hipStream_t s, const Group *host_groups)
 {
   d->block_begin.clear();
   d->dealt_state = 0;
@@ -319,7 +319,9 @@ static void dplan_blocks_from_device_groups(hsrans_dplan *d, hipStream_t s)
   try
   {
     std::vector<Group> groups(d->n_groups);
-    if (hipMemcpyAsync(groups.data(), d->d_groups, groups.size() * sizeof(Group), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    if (host_groups != nullptr) // (the caller brought them down already)
+      memcpy(groups.data(), host_groups, groups.size() * sizeof(Group));
+    else if (hipMemcpyAsync(groups.data(), d->d_groups, groups.size() * sizeof(Group), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
     {
       (void)hipGetLastError();
       return;
@@ -384,7 +386,7 @@ extern "C++" int dplan_arena(hsrans_dplan *d, const DplanRegions &r, hipStream_t
   return hipMemsetAsync(a, 0, zero, s) == hipSuccess ? HSRANS_OK : HSRANS_E_HIP;
 }
 
-extern "C++" void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_groups, uint64_t spread_min_block, hipStream_t s)
+extern "C++" void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_groups, uint64_t spread_min_block, hipStream_t s, const Group *host_groups)
 {
   d->tuning = read_tuning(); // (as a fill takes them)
   d->hdr = h;
@@ -395,7 +397,7 @@ extern "C++" void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_g
   d->spread_min_block = d->groups_lean ? (uint32_t)std::min<uint64_t>(spread_min_block, 0xFFFFFFFFu) : 0;
   if (n_groups == 0)
     d->d_groups = nullptr, d->d_counters = nullptr;
-  dplan_blocks_from_device_groups(d, s); // (k_decode_dealt's dealing wants the blocks as chain ranges: 32 bytes a group, once)
+  dplan_blocks_from_device_groups(d, s, host_groups); // (k_decode_dealt's dealing wants the blocks as chain ranges: 32 bytes a group, once)
 }
 
 extern "C++" PlanHeader mt_plan_header(uint32_t states, uint32_t bits, uint64_t decoded_len, uint64_t stream_len, uint32_t n_chains)

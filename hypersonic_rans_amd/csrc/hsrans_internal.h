@@ -152,7 +152,8 @@ struct DplanRegions
 int dplan_arena(hsrans_dplan *d, const DplanRegions &r, hipStream_t s, uint8_t **scratch = nullptr);
 // takes over a plan the device wrote into d's arena: its header, its group count (0: ungrouped, groups and counters are dropped) and the fewest
 // chains of a coded block that is not the last; fills block_begin from the group list (synchronises `s` when there is one)
-void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_groups, uint64_t spread_min_block, hipStream_t s);
+// host_groups (may be null): the caller's copy of the first n_groups groups, already on the host — nothing is copied and nothing synchronised
+void dplan_adopt(hsrans_dplan *d, const PlanHeader &h, uint32_t n_groups, uint64_t spread_min_block, hipStream_t s, const Group *host_groups = nullptr);
 // the header of an mt_ plan written on the device (the GPU encoder's, K2's): n_chains single-piece chains
 PlanHeader mt_plan_header(uint32_t states, uint32_t bits, uint64_t decoded_len, uint64_t stream_len, uint32_t n_chains);
 
@@ -364,6 +365,80 @@ int gather_region_take(hsrans_ctx *ctx, size_t need, GatherRegion *region);
 int gather_region_order(hsrans_ctx *ctx, hipStream_t s);
 // records the region's event behind the launches on `s` and moves the cursor; HSRANS_E_HIP: nothing is recorded, the region is free again
 int gather_region_commit(hsrans_ctx *ctx, const GatherRegion &region, hipStream_t s);
+
+// ---- what the first decodes share (hsrans_capi_index.cpp): hsrans_decode_device_indexing and hsrans_decode_device_indexing_batch ----
+inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+// What a recording pass writes besides the output: checkpoint states and read cursors, and for a block_ walk the block records, the states
+// on entry to each block and the block count.  Byte counts of the first four.
+struct PassBytes
+{
+  size_t st, wd, blk, bst;
+  size_t all() const { return st + wd + blk + bst; }
+};
+struct PassBuffers // device
+{
+  uint32_t *ck_states;
+  uint64_t *ck_words;
+  uint64_t *walk_blocks; // null: not a walk
+  uint32_t *walk_states, *walk_count;
+  uint32_t max_blocks;
+};
+inline PassBytes pass_bytes(uint64_t n_ck, uint32_t S, uint64_t max_blocks) { return {(size_t)n_ck * S * 4, (size_t)n_ck * 8, (size_t)max_blocks * 24, (size_t)max_blocks * S * 4}; }
+// room for blocks of >= 4 KiB on average (the reference's smallest block is 32 KiB, block_rANS32x64_16w_encode.cpp:21-39); a stream with more gets no plan
+inline uint64_t walk_max_blocks(uint64_t decoded_len) { return decoded_len / 4096 + 16; }
+// the checkpoints a pass over decoded_len bytes at `interval` groups has room for
+inline uint64_t pass_checkpoints(uint64_t decoded_len, uint32_t S, uint32_t interval) { return decoded_len / S / interval + 2; }
+
+// The argument checks of a first decode (the single call's, and every member's of the batch): HSRANS_OK, HSRANS_E_ARG or HSRANS_E_FORMAT.
+// base plans only: one single-piece chain per block (raw: one chain), or a block_ stream's walk plan (one chain that follows the inline headers)
+inline int indexing_args_check(const hsrans_ctx *ctx, const hsrans_dplan *d, const void *d_stream, size_t stream_length, const void *d_out, size_t out_capacity,
+                               uint32_t index_interval)
+{
+  if (ctx == nullptr || d == nullptr || d_stream == nullptr || d_out == nullptr || d->ctx != ctx)
+    return HSRANS_E_ARG;
+  if (((uintptr_t)d_stream & 15) != 0 || ((uintptr_t)d_out & 3) != 0 || index_interval == 0 || (index_interval % 4) != 0)
+    return HSRANS_E_ARG;
+  const PlanHeader &h = d->hdr;
+  const bool walk = (h.flags & kPlanWalk) != 0;
+  if (h.n_pieces != h.n_chains || h.interval != 0 || d->d_plan == nullptr || d->plan_bytes == 0 || (walk && (h.container != HSRANS_BLOCK || h.n_chains != 1)))
+    return HSRANS_E_ARG;
+  if (stream_length < h.stream_len || out_capacity < h.decoded_len)
+    return HSRANS_E_FORMAT;
+  return HSRANS_OK;
+}
+// whether the first decode with base plan h is assembled on the device behind an mt_ recording pass (else: a walk plan's, or on the host)
+inline bool indexing_mt_on_device(const PlanHeader &h) { return h.container == HSRANS_MT && (h.flags & (kPlanWalk | kPlanHasHist | kPlanMergeable)) == 0; }
+
+// The plan a device assembly writes, with room for max_chains chains and max_groups groups.  Its arena's scratch: the assembly's IndexResult
+// (and at +128 a walk's block count), from +256 `off_words` chain / group offsets, behind them (16-byte aligned) `extra` bytes.  null: no memory
+constexpr size_t kAssemblyCount = 128, kAssemblyOffsets = 256;
+hsrans_dplan *assembly_plan(hsrans_ctx *ctx, uint32_t S, uint32_t max_chains, size_t max_groups, size_t off_words, size_t extra, hipStream_t s, uint8_t **scratch);
+// The sizes of a block_ member's first decode, from its walk plan's header and the interval; false: more chains than a plan holds
+struct WalkAssemblySizes
+{
+  uint64_t n_ck, max_blocks, max_chains, max_groups;
+  PassBytes pbytes;
+};
+bool walk_assembly_sizes(const PlanHeader &h, uint32_t interval, WalkAssemblySizes *z);
+// ... its pass buffers in the new plan's scratch (the checkpoints are the caller's) and the arguments of its assembly kernels
+void walk_assembly_args(const hsrans_ctx *ctx, const hsrans_dplan *d, const hsrans_dplan *nd, uint8_t *scratch, uint32_t interval, const WalkAssemblySizes &z, PassBuffers *pass,
+                        WalkIndexArgs *wa);
+// The sizes and the arguments of an mt_ member's (indexing_mt_on_device)
+struct MtAssemblySizes
+{
+  uint64_t n_ck;
+  uint32_t max_chains, max_groups;
+  PassBytes pbytes;
+};
+MtAssemblySizes mt_assembly_sizes(const hsrans_ctx *ctx, const PlanHeader &h, uint32_t interval);
+void mt_assembly_args(const hsrans_ctx *ctx, const hsrans_dplan *d, const hsrans_dplan *nd, uint8_t *scratch, uint32_t interval, const MtAssemblySizes &z, const PassBuffers &pass, IndexArgs *ia);
+// finish_assembly in two halves, to run around one synchronisation of `s`.  Behind the pass and the assembly kernels: the copy down of what the
+// count kernel left and of the base plan d's status word is queued (false: the runtime refused) ...
+bool assembly_copy_down(const hsrans_dplan *d, const IndexResult *d_result, hipStream_t s, IndexResult *r, uint32_t *status);
+// ... and once `s` is synchronised: rc is what the pass and the copies came to (HSRANS_OK, or why there is no plan); the result is checked
+// against the bounds and nd takes over the plan the device wrote (host_groups: as dplan_adopt).  On failure nd is destroyed.
+int assembly_adopt(const hsrans_dplan *d, hsrans_dplan *nd, int rc, const IndexResult &r, uint32_t interval, uint32_t min_chains, uint32_t max_chains, uint32_t max_groups,
+                   hipStream_t s, const Group *host_groups = nullptr);
 
 // a page-locked, device-mapped host range: the address the GPU reaches it at, else null (hsrans_capi.cpp)
 uint8_t *device_view_of_host(const void *ptr, size_t bytes);

@@ -509,11 +509,12 @@ struct IndexArgs
   const uint32_t *ck_states; // [slot * S]: coder states at absolute group slot * interval
   const uint64_t *ck_words;  // [slot]: absolute stream byte of the read cursor there
   uint32_t *chain_off;       // [n_base] first chain of block b in the new plan (k_index_count)
+  uint32_t *group_off;       // [n_base] first group of block b
   IndexResult *result;
   uint8_t *plan;             // the new plan blob (zeroed, sized for max_chains)
-  uint32_t max_chains;
-  Group *groups;             // [n_base * group_split] or null
-  uint32_t group_split;
+  uint32_t max_chains, max_groups; // what the plan blob and `groups` have room for
+  Group *groups;             // [max_groups], zeroed
+  uint32_t parts_want;       // kGroupPartsPerCU x CUs (group_parts_max_of)
   uint64_t stream_len;
 };
 hipError_t launch_index_assemble(const IndexArgs &a, hipStream_t stream);
@@ -538,6 +539,39 @@ struct WalkIndexArgs
   Group *groups;               // [max_groups], zeroed
 };
 hipError_t launch_index_assemble_walk(const WalkIndexArgs &a, hipStream_t stream);
+
+// ---- the first decode of many streams in one call (kernels_index_batch.h, hsrans_capi_index_batch.cpp) ------------------------------
+// what the recording pass needs of one member: a block_ stream's walk plan or an mt_ base plan, bound to its stream, output and buffers
+struct IndexPassMember
+{
+  const uint8_t *stream; // device, 16-byte aligned
+  uint64_t stream_len;
+  uint8_t *out; // device, 4-byte aligned
+  uint64_t out_cap;
+  const uint8_t *plan;   // the base plan's blob (device)
+  uint32_t *status;      // ... and its status word
+  uint32_t *ck_states;   // KParams::ckpt_states / ckpt_words of this member
+  uint64_t *ck_words;
+  uint64_t *walk_blocks; // KParams::walk_* (null: an mt_ member)
+  uint32_t *walk_states, *walk_count;
+  uint32_t interval, walk_max_blocks;
+};
+static_assert(sizeof(IndexPassMember) == 96, "IndexPassMember layout");
+// one wavefront's work: a walk member's one chain, or chain (block) `chain` of an mt_ member
+struct IndexPassTask
+{
+  uint32_t member, chain;
+};
+constexpr uint32_t kIndexPassModes = 3; // the table layouts waves build for themselves: <= 11 bits, 12 bits, 13-15 bits
+// the layout a recording pass over a plan of `bits` decodes with (launch_shape's rule for private tables)
+int index_pass_mode(uint32_t bits);
+// tasks [0, n_tasks) at d_tasks, all of layout `mode`, the widest histogram among their members max_bits wide: one launch, one wavefront a task
+hipError_t launch_index_pass_batch(int mode, uint32_t max_bits, const IndexPassTask *d_tasks, uint32_t n_tasks, const IndexPassMember *d_members, hipStream_t stream);
+// count and fill for n members' argument structs at d_args; most_blocks: the largest n_base (max_blocks) among them; d_status_of[k]: member
+// k's status word, copied to d_status_out[k] behind the pass
+hipError_t launch_index_assemble_batch(const IndexArgs *d_args, uint32_t n, uint32_t most_blocks, const uint32_t *const *d_status_of, uint32_t *d_status_out, hipStream_t stream);
+hipError_t launch_index_assemble_walk_batch(const WalkIndexArgs *d_args, uint32_t n, uint32_t most_blocks, const uint32_t *const *d_status_of, uint32_t *d_status_out,
+                                            hipStream_t stream);
 // 64-bit fingerprint of d_stream[0, stream_len) into *d_sum (16-byte aligned stream; asynchronous: memset + one launch)
 hipError_t launch_stream_checksum(const uint8_t *d_stream, uint64_t stream_len, uint64_t *d_sum, hipStream_t stream);
 

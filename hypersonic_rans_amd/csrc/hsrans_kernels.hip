@@ -34,6 +34,7 @@
 //   kernels_single.h    k_decode_single    one dependent chain (raw stream without index)
 //   kernels_walk.h      k_mt_chase / k_mt_fill   K2: the mt_ header chain on the device; k_index_count / k_index_fill, k_walk_index_count / k_walk_index_fill   the indexed plan behind a first decode (mt_, block_)
 //   kernels_gather.h    k_gather           byte ranges of one stream: one wave per task, entered at the chain that holds its first byte
+//   kernels_index_batch.h   k_index_pass_batch   the first decode of many streams: one wavefront per walk / mt_ block; k_index_count_batch ... k_walk_index_fill_batch   their plans behind it
 //                       k_gather_cut, k_gather_ranges   the same for ranges in device memory: checked and counted on the device, waves stride over the tasks; k_gather_set   byte ranges of many streams: every task names its member, one launch per table layout; k_set_cut, k_set_ranges   the same for ranges in device memory
 // This file: the host side — the kernel table, launch shapes, hsrans_index_boundaries' chain lengths, choose_launch, launch_decode.
 #include <hip/hip_runtime.h>
@@ -57,6 +58,7 @@
 #include "kernels_single.h"
 #include "kernels_walk.h"
 #include "kernels_gather.h"
+#include "kernels_index_batch.h"
 
 #include <algorithm>
 #include <array>
@@ -88,6 +90,56 @@ hipError_t launch_index_assemble_walk(const WalkIndexArgs &a, hipStream_t stream
   hipLaunchKernelGGL(k_walk_index_count, dim3(1), dim3(1024), 0, stream, a);
   // (the block count is on the device: wavefronts stride over the blocks there are, or leave)
   hipLaunchKernelGGL(k_walk_index_fill, dim3(a.max_blocks < 2048 ? (a.max_blocks ? a.max_blocks : 1) : 2048), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---- hsrans_decode_device_indexing_batch's launches: at most kIndexPassModes of the pass, one count and one fill per kind ----
+int index_pass_mode(uint32_t bits) { return bits >= 13 ? kModeTwoLevel : bits == 12 ? kModePackM1 : kModePack; }
+
+static const void *const g_index_pass_kernels[kIndexPassModes] = {(const void *)k_index_pass_batch<kModePack>, (const void *)k_index_pass_batch<kModePackM1>,
+                                                                  (const void *)k_index_pass_batch<kModeTwoLevel>};
+
+hipError_t launch_index_pass_batch(int mode, uint32_t max_bits, const IndexPassTask *d_tasks, uint32_t n_tasks, const IndexPassMember *d_members, hipStream_t stream)
+{
+  if (mode != index_pass_mode(max_bits) || max_bits > 15 || n_tasks == 0 || n_tasks > 0x7FFFFFFFu)
+    return hipErrorInvalidValue;
+  const uint32_t lds = kWaveRingBytes + ((table_bytes_for(mode, max_bits) + 15) & ~15u); // one wave: ring, then table
+  (void)hipGetLastError();
+  if (mode == kModePack)
+    hipLaunchKernelGGL(k_index_pass_batch<kModePack>, dim3(n_tasks), dim3(64), lds, stream, d_tasks, d_members);
+  else if (mode == kModePackM1)
+    hipLaunchKernelGGL(k_index_pass_batch<kModePackM1>, dim3(n_tasks), dim3(64), lds, stream, d_tasks, d_members);
+  else
+    hipLaunchKernelGGL(k_index_pass_batch<kModeTwoLevel>, dim3(n_tasks), dim3(64), lds, stream, d_tasks, d_members);
+  return hipGetLastError();
+}
+
+// rows of wavefronts per member of a fill launch: as many as the member with the most blocks has, as k_walk_index_fill's at most 2,048, and
+// no more than 2^20 workgroups in all
+static uint32_t index_fill_rows(uint32_t n, uint32_t most_blocks)
+{
+  const uint32_t cap = std::max(1u, std::min(2048u, (1u << 20) / n));
+  return std::max(1u, std::min(most_blocks, cap));
+}
+
+hipError_t launch_index_assemble_batch(const IndexArgs *d_args, uint32_t n, uint32_t most_blocks, const uint32_t *const *d_status_of, uint32_t *d_status_out, hipStream_t stream)
+{
+  if (n == 0 || n > 65536)
+    return hipErrorInvalidValue;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_index_count_batch, dim3(n), dim3(1024), 0, stream, d_args, d_status_of, d_status_out);
+  hipLaunchKernelGGL(k_index_fill_batch, dim3(n, index_fill_rows(n, most_blocks)), dim3(64), 0, stream, d_args);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_assemble_walk_batch(const WalkIndexArgs *d_args, uint32_t n, uint32_t most_blocks, const uint32_t *const *d_status_of, uint32_t *d_status_out,
+                                            hipStream_t stream)
+{
+  if (n == 0 || n > 65536)
+    return hipErrorInvalidValue;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_walk_index_count_batch, dim3(n), dim3(1024), 0, stream, d_args, d_status_of, d_status_out);
+  hipLaunchKernelGGL(k_walk_index_fill_batch, dim3(n, index_fill_rows(n, most_blocks)), dim3(64), 0, stream, d_args);
   return hipGetLastError();
 }
 
@@ -291,6 +343,8 @@ hipError_t prepare_kernels(DeviceGeom *geom)
     fns.push_back(k.fn);
   for (const void *fn : {(const void *)k_decode_batch<kModePack64>, (const void *)k_decode_grouped_batch<kModePack64>, (const void *)k_decode_batch_pair<kModePack64>,
                          (const void *)k_decode_batch_dual<kModePack64>, (const void *)k_decode_batch_dual<kModeRank>, (const void *)k_calibrate_batch})
+    fns.push_back(fn);
+  for (const void *fn : g_index_pass_kernels)
     fns.push_back(fn);
   for (const GatherKernel &g : g_gather_kernels)
   {

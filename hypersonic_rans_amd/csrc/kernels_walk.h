@@ -241,16 +241,28 @@ __device__ __forceinline__ Group index_part_group(const IndexBlock &blk, uint32_
   return index_group(c0 + r.lo, r.hi - r.lo, kGroupMergeable, blk.hist_off, r.words_end);
 }
 
-__global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
+// (the four bodies are device functions of their argument struct: the kernels below hand them their own, by value in the kernel arguments; the
+// batch forms of kernels_index_batch.h hand them member m's, from a table in device memory)
+// groups block ch of an mt_ base plan opens before any is cut: a coded block one, a run of single-symbol blocks one at its first block
+__device__ __forceinline__ uint32_t index_block_leads(const uint32_t *cf0, const Piece *pc0, uint32_t ch, bool fill)
+{
+  return !fill || ch == 0 || !(pc0[cf0[ch - 1]].flags & kPieceFill) ? 1 : 0;
+}
+
+// chains and groups per block, their exclusive scans, the totals and header facts -> *result.  The group list is the one dplan_fill derives
+// from the finished blob: one group per coded block, cut into group_parts_of parts where there are few, one per run of single-symbol blocks,
+// packed; none where there would be as many groups as chains
+__device__ __forceinline__ void index_count(const IndexArgs &a)
 {
   __shared__ uint32_t wave_tot[16];
-  __shared__ uint32_t carry_s, coded_s, fewest_s;
+  __shared__ uint32_t carry_s, coded_s, first_s, last_s, fewest_s, lead_s;
   __shared__ unsigned long long hist_s;
   const uint32_t *cf0 = (const uint32_t *)(a.base + plan_chain_first_off());
   const Piece *pc0 = (const Piece *)(a.base + plan_pieces_off(a.n_base));
   if (threadIdx.x == 0)
   {
-    carry_s = coded_s = 0;
+    carry_s = coded_s = last_s = lead_s = 0;
+    first_s = 0xFFFFFFFFu;
     fewest_s = kIndexNoFewest;
     hist_s = 0;
   }
@@ -263,36 +275,67 @@ __global__ void __launch_bounds__(1024) k_index_count(IndexArgs a)
     {
       const IndexBlock blk = index_block_of_piece(pc0[cf0[ch]], a.S, ch + 1 == a.n_base);
       v = index_block_chains(blk, a.interval);
+      atomicAdd(&lead_s, index_block_leads(cf0, pc0, ch, blk.fill));
       if (!blk.fill) // (mt_ blocks never share a histogram)
       {
         atomicAdd(&coded_s, 1u);
+        atomicMin(&first_s, ch);
+        atomicMax(&last_s, ch);
         atomicMax(&hist_s, (unsigned long long)blk.hist_off);
-        if (!blk.last)
-          atomicMin(&fewest_s, v);
       }
     }
     const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
     if (ch < a.n_base)
       a.chain_off[ch] = off;
   }
+  const uint32_t total = carry_s, lead = lead_s;
+  // dplan_fill: groups only where there are fewer than chains, cut into parts where there are few
+  const bool grouped = lead < total;
+  const uint32_t k_max = grouped ? group_parts_max_of(a.parts_want, lead) : 1;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    carry_s = 0;
+  __syncthreads();
+  for (uint32_t base = 0; base < a.n_base; base += 1024)
+  {
+    const uint32_t ch = base + threadIdx.x;
+    uint32_t v = 0;
+    if (ch < a.n_base)
+    {
+      const IndexBlock blk = index_block_of_piece(pc0[cf0[ch]], a.S, ch + 1 == a.n_base);
+      const uint32_t count = index_block_chains(blk, a.interval);
+      v = blk.fill ? index_block_leads(cf0, pc0, ch, true) : group_parts_of(count, k_max);
+      if (!blk.fill && ch != first_s && ch != last_s)
+        atomicMin(&fewest_s, count);
+    }
+    const uint32_t off = wg_scan_1024(v, wave_tot, &carry_s);
+    if (ch < a.n_base)
+      a.group_off[ch] = off;
+  }
   if (threadIdx.x == 0)
   {
+    const uint32_t n_groups = carry_s;
     IndexResult r{};
-    r.chains = carry_s;
+    r.chains = total;
     r.blocks = a.n_base;
     r.coded = coded_s;
     r.fewest = fewest_s;
     r.hist_off = hist_s;
-    r.groups = r.chains > a.n_base ? a.n_base * a.group_split : 0; // (one chain per block: no checkpoint fell inside any, the ungrouped launch)
+    r.groups = grouped ? n_groups : 0; // (as many groups as chains — no checkpoint fell inside any block: the ungrouped launch)
+    r.parts = k_max;
+    r.error = total > a.max_chains || n_groups > a.max_groups ? 3 : 0;
     *a.result = r;
   }
 }
 
-__global__ void __launch_bounds__(64) k_index_fill(IndexArgs a)
+__global__ void __launch_bounds__(1024) k_index_count(IndexArgs a) { index_count(a); }
+
+// block (base chain) `ch` of the plan, by one wavefront
+__device__ __forceinline__ void index_fill(const IndexArgs &a, uint32_t ch)
 {
-  const uint32_t ch = blockIdx.x, lane = threadIdx.x, S = a.S;
+  const uint32_t lane = threadIdx.x, S = a.S;
   const IndexResult r = *a.result;
-  if (r.chains > a.max_chains) // (the host sized the blob for max_chains: it reads the result and fails the call)
+  if (r.error != 0) // (more chains or groups than the host sized the arena for: it reads the result and fails the call)
     return;
   const uint32_t *cf0 = (const uint32_t *)(a.base + plan_chain_first_off());
   const Piece *pc0 = (const Piece *)(a.base + plan_pieces_off(a.n_base));
@@ -303,28 +346,34 @@ __global__ void __launch_bounds__(64) k_index_fill(IndexArgs a)
   if (ch == 0 && lane == 0)
     index_write_header(a.base, a.plan, r, a.interval);
   index_write_chains(blk, S, a.interval, c0, count, st0 + (uint64_t)bp.state_idx * S, a.ck_states, a.ck_words, a.plan, r.chains);
-  if (a.groups != nullptr && lane < a.group_split)
+  if (a.groups == nullptr || r.groups == 0 || !index_block_leads(cf0, pc0, ch, blk.fill))
+    return;
+  // the group's words end at the next rANS block's histogram (as dplan_fill has it), or at the stream's end
+  uint64_t words_end = a.stream_len;
+  uint32_t run = 1; // a single-symbol block: the blocks of its run
+  for (uint32_t nx = ch + 1; nx < a.n_base; nx++)
   {
-    // the block's words end at the next rANS block's histogram (as dplan_fill has it), or at the stream's end
-    uint64_t words_end = a.stream_len;
-    for (uint32_t nx = ch + 1; nx < a.n_base; nx++)
+    const Piece &q = pc0[cf0[nx]];
+    if (!(q.flags & kPieceFill))
     {
-      const Piece &q = pc0[cf0[nx]];
-      if (!(q.flags & kPieceFill))
-      {
-        words_end = q.hist_off;
-        break;
-      }
+      words_end = q.hist_off;
+      break;
     }
-    // (padded: group_split slots a block; those behind its parts, and all but the first of a single-symbol block, are empty fills)
-    const uint32_t parts = blk.fill ? 1 : group_parts_of(count, a.group_split);
-    Group *slot = &a.groups[(uint64_t)ch * a.group_split + lane];
-    if (lane < parts && !blk.fill)
-      *slot = index_part_group(blk, a.interval, c0, count, lane, parts, a.ck_words, words_end);
-    else
-      *slot = index_group(c0, lane < parts ? count : 0, kGroupFill, blk.fill ? 0 : blk.hist_off, words_end);
+    run++; // (every block passed here is a single-symbol one: behind a run's first block, the rest of its run)
   }
+  const uint32_t g0 = a.group_off[ch];
+  if (blk.fill)
+  {
+    if (lane == 0)
+      a.groups[g0] = index_group(c0, run, kGroupFill, 0, words_end);
+    return;
+  }
+  const uint32_t parts = group_parts_of(count, r.parts);
+  for (uint32_t part = lane; part < parts; part += 64)
+    a.groups[g0 + part] = index_part_group(blk, a.interval, c0, count, part, parts, a.ck_words, words_end);
 }
+
+__global__ void __launch_bounds__(64) k_index_fill(IndexArgs a) { index_fill(a, blockIdx.x); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same for a block_ stream, from the records of the walk that has just decoded it (run_block_walk with ckpt_interval != 0): the plan
@@ -344,7 +393,7 @@ __device__ __forceinline__ uint32_t walk_block_leads(const WalkIndexArgs &a, uin
   return !fill || b == 0 || !(a.walk_blocks[3 * (uint64_t)(b - 1) + 2] >> 63) ? 1 : 0;
 }
 
-__global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
+__device__ __forceinline__ void walk_index_count(const WalkIndexArgs &a)
 {
   __shared__ uint32_t wave_tot[16];
   __shared__ uint32_t carry_s, coded_s, first_s, last_s, fewest_s, bad_s, lead_s;
@@ -427,15 +476,18 @@ __global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a)
   }
 }
 
-__global__ void __launch_bounds__(64) k_walk_index_fill(WalkIndexArgs a)
+__global__ void __launch_bounds__(1024) k_walk_index_count(WalkIndexArgs a) { walk_index_count(a); }
+
+// the wavefronts first, first + stride, ... of `stride` stride over the blocks
+__device__ __forceinline__ void walk_index_fill(const WalkIndexArgs &a, uint32_t first, uint32_t stride)
 {
   const IndexResult r = *a.result;
   if (r.error != 0) // no plan: the host reads the word and fails the call
     return;
   const uint32_t lane = threadIdx.x, S = a.S, n = r.blocks;
-  if (blockIdx.x == 0 && lane == 0)
+  if (first == 0 && lane == 0)
     index_write_header(a.base, a.plan, r, a.interval);
-  for (uint32_t b = blockIdx.x; b < n; b += gridDim.x)
+  for (uint32_t b = first; b < n; b += stride)
   {
     const IndexBlock blk = walk_index_block(a, b, n);
     const uint32_t c0 = a.chain_off[b], count = index_block_chains(blk, a.interval);
@@ -466,6 +518,8 @@ __global__ void __launch_bounds__(64) k_walk_index_fill(WalkIndexArgs a)
       a.groups[g0 + part] = index_part_group(blk, a.interval, c0, count, part, parts, a.ck_words, words_end);
   }
 }
+
+__global__ void __launch_bounds__(64) k_walk_index_fill(WalkIndexArgs a) { walk_index_fill(a, blockIdx.x, gridDim.x); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // 64-bit fingerprint of a stream in device memory (hsrans_decode_host's index cache: the index a first decode left behind may only

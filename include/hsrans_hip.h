@@ -579,6 +579,53 @@ int hsrans_sharded_status(hsrans_sharded *sharded, void *hip_stream); /* as hsra
 int hsrans_decode_device_indexing(hsrans_ctx *ctx, hsrans_dplan *dplan, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity,
                                   uint32_t index_interval, void *hip_stream, hsrans_dplan **indexed);
 
+/* The first decode of many streams that came without an index, in one call: the many-streams form of hsrans_decode_device_indexing.
+ * The walks of different block_ streams, and the blocks of mt_ base plans, are independent: each is one wavefront of one launch.
+ *
+ * Member equivalence.  Member k gets exactly what hsrans_decode_device_indexing(ctx, dplan, d_stream, stream_length, d_out,
+ * out_capacity, index_interval, hip_stream, &indexed) gives it: the same bytes at d_out, the same plan blob byte for byte
+ * (hsrans_dplan_read_plan; hence the blob hsrans_index_build returns), the same group list (hence the same hsrans_dplan_launch_info)
+ * and the same rc.
+ * Mixing.  HSRANS_BLOCK walk plans and HSRANS_MT base plans may share one call, with 32 and 64 states, 10-15 bits and different
+ * intervals.  count is 1..65,536.
+ * Validation before launch.  Every member is checked with the single call's rules before anything is launched or allocated.  Besides:
+ * a dplan appears at most once; no two members' [d_out, d_out + decoded_len) overlap; no output overlaps any member's stream
+ * [d_stream, d_stream + stream_length); a raw member (and an mt_ plan that carries its histogram, which the single call also indexes on
+ * the host) is an argument error here: raw streams are indexed on the host and gain nothing from the batch.  Any violation returns
+ * HSRANS_E_ARG or HSRANS_E_FORMAT as the single call would, with nothing launched, no byte written, every rc set to that code and every
+ * `indexed` NULL.  (NULL ctx or members, count == 0 or > 65,536: HSRANS_E_ARG, members untouched.)
+ * Failure on the device is per member.  A member whose pass sets its status word gets rc = HSRANS_E_DEVICE, indexed = NULL and its
+ * status word cleared.  A member whose walk overflows the block list or ends short gets rc = HSRANS_E_FORMAT, indexed = NULL and d_out
+ * COMPLETE.  In both cases the other members complete normally.  The call returns the first non-OK rc in member order, else HSRANS_OK.
+ * (HSRANS_E_HIP: the runtime failed; every rc is HSRANS_E_HIP.)
+ * Synchronisation.  One hipStreamSynchronize of hip_stream, plus one more only when some member's status word has to be cleared.  All
+ * members' results, status words and (64 states) group lists come down in front of that one synchronisation.
+ * Launch count.  Independent of count: the recording pass launches at most once per private table layout present (<= 11 bits, 12 bits,
+ * 13-15 bits: at most 3), count and fill each at most once per kind (walk, mt_: at most 4); stats->launches <= 7, plus one upload,
+ * one memset and the copies down.  Its tasks (a walk, or one mt_ block) are ordered by descending work: the decoded bytes of a walk, of
+ * an mt_ block its member's average block length.
+ * Host work per member: its validation and parameter records, and one plan allocation with its memset (as the single call).  The
+ * members' checkpoints are carved out of the context's checkpoint buffer, which grows to the sum over all members.
+ * HSRANS_INDEX_ASSEMBLE_ON_HOST=1 (read at hsrans_ctx_create): the single call's body runs member by member behind the same validation
+ * (the comparison path): the same results, stats->launches == 0.  Calls on one context are serialised. */
+typedef struct hsrans_indexing_member
+{
+  hsrans_dplan *dplan;      /* base plan, as hsrans_decode_device_indexing takes it: a block_ walk plan or an mt_ base plan (no checkpoints) */
+  const void *d_stream;     /* device, 16-byte aligned */
+  size_t stream_length;
+  void *d_out;              /* device, 4-byte aligned */
+  size_t out_capacity;
+  uint32_t index_interval;  /* multiple of 4, != 0; members may differ */
+  int rc;                   /* out: what the single call would have returned for this member */
+  hsrans_dplan *indexed;    /* out: the plan with checkpoints, NULL unless rc == HSRANS_OK */
+} hsrans_indexing_member;
+typedef struct hsrans_indexing_batch_stats
+{
+  uint32_t launches, walk_members, mt_members, tasks; /* kernels launched; members by kind; wavefront tasks of the recording pass */
+} hsrans_indexing_batch_stats;
+int hsrans_decode_device_indexing_batch(hsrans_ctx *ctx, hsrans_indexing_member *members, uint32_t count, void *hip_stream,
+                                        hsrans_indexing_batch_stats *stats /* may be NULL */);
+
 /* GPU encoder: mt_ stream with fixed blocks of `block_size` symbols (multiple of 64), each block
  * encoded independently by one wavefront (HSRANS_ENC_INDEPENDENT_BLOCKS layout).  d_in / d_out are device pointers (16-byte
  * aligned); d_out needs hsrans_capacity(HSRANS_MT, states, length) bytes.  Synchronises `hip_stream`; returns the stream

@@ -812,6 +812,34 @@ def test_gpu_encoder_placement_by_either_kernel(gpu_ctx, zipf):
         assert bool((small == 0xA5).all()), (n, block)
 
 
+@pytest.mark.parametrize("states", (32, 64))
+@pytest.mark.parametrize("interval", (0, 4, 32))
+def test_gpu_encoder_small_chunks_with_checkpoints(gpu_ctx, states, interval):
+    """The 2 KiB-chunk instantiations (k_encode_blocks<S, 2048>, chosen above 11 x CUs blocks) on blocks that are more than two chunks
+    and carry checkpoints: 4,160 blocks (beyond the 4,096-block scan limit too) of 6,208 bytes = 97 groups of 64 — one group ahead of
+    the sets, an odd number of sets, four chunks with the last one partial — and a last block 37 bytes longer (a partial last group).
+    With interval 4 a checkpoint follows every set, so chunk change, flush and checkpoint fall on the same set many times a block.
+    Stream and plan == the host encoder's, byte for byte (interval 0: the plan the host builds from its stream, as in
+    test_gpu_encoder_emits_the_host_encoders_plan); the device decode with the returned plan gives the input back."""
+    import torch
+    block = 6208
+    d = synth.zipf_bytes(4160 * block + 37, 1.1, seed=17)
+    if interval:
+        want_stream, want_plan = H.encode(H.MT, states, 11, d, block_size=block, index_interval=interval, independent_blocks=True)
+    else:
+        want_stream = H.encode(H.MT, states, 11, d, block_size=block, independent_blocks=True)
+        want_plan = H.plan_build(H.MT, states, 11, want_stream)
+    d_in = torch.from_numpy(d).cuda()
+    d_out = torch.full((H.capacity(H.MT, states, d.size),), 0x5A, dtype=torch.uint8, device="cuda")
+    m, dplan = gpu_ctx.encode_device(H.MT, states, 11, d_in, d_out, block_size=block, index_interval=interval, want_plan=True)
+    assert m == want_stream.size and np.array_equal(d_out[:m].cpu().numpy(), want_stream), (states, interval)
+    got_plan = gpu_ctx.read_device_plan(dplan)
+    assert got_plan.size == want_plan.size and np.array_equal(got_plan, want_plan), (states, interval, int(np.argmax(got_plan[:want_plan.size] != want_plan)))
+    back = torch.zeros(d.size, dtype=torch.uint8, device="cuda")
+    gpu_ctx.decode_device(dplan, d_out, back, stream_length=m)
+    assert gpu_ctx.status(dplan) == 0 and torch.equal(back, d_in), (states, interval)
+
+
 def test_gpu_encoder_rejects_bad_arguments(gpu_ctx, zipf):
     import torch
     d_in = torch.from_numpy(zipf[:4096].copy()).cuda()

@@ -43,6 +43,17 @@ class EncodeBatchStats(ctypes.Structure):
     _fields_ = [(n, _u32) for n in ("launches", "raw_members", "mt_members", "mt_blocks")]
 
 
+class EncodeExMember(ctypes.Structure):
+    """hsrans_encode_ex_member: one stream of hsrans_encode_device_ex_batch"""
+    _fields_ = [("container", _i), ("states", _i), ("bits", _u32), ("d_in", _vp), ("length", _sz), ("d_out", _vp), ("out_capacity", _sz),
+                ("opts", ctypes.POINTER(EncodeOpts)), ("stream_length", _sz), ("rc", _i)]
+
+
+class EncodeExBatchStats(ctypes.Structure):
+    _fields_ = ([(n, _u32) for n in ("launches", "block_members", "mt_members", "units", "blocks")] +
+                [(n, ctypes.c_double) for n in ("summaries_us", "walk_us", "chain_us", "plans_us")])
+
+
 class IndexingMember(ctypes.Structure):
     """hsrans_indexing_member: one stream of hsrans_decode_device_indexing_batch"""
     _fields_ = [("dplan", _vp), ("d_stream", _vp), ("stream_length", _sz), ("d_out", _vp), ("out_capacity", _sz), ("index_interval", _u32), ("rc", _i),
@@ -317,6 +328,8 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_block_choices_device.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz, _vp]
     L.hsrans_encode_device_batch.restype = _i
     L.hsrans_encode_device_batch.argtypes = [_vp, ctypes.POINTER(EncodeMember), _u32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(EncodeBatchStats)]
+    L.hsrans_encode_device_ex_batch.restype = _i
+    L.hsrans_encode_device_ex_batch.argtypes = [_vp, ctypes.POINTER(EncodeExMember), _u32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(EncodeExBatchStats)]
     L.hsrans_encode_device_ex.restype = _sz
     L.hsrans_encode_device_ex.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(Hist), ctypes.POINTER(EncodeOpts), _vp, ctypes.POINTER(_vp)]
     L.hsrans_index_build.restype = _sz
@@ -1395,6 +1408,70 @@ class Context:
             err.code, err.lengths, err.plans = rc, lengths, plans
             raise err
         return (lengths, plans) if want_plans else lengths
+
+    def encode_device_ex_batch(self, members, want_plans: bool = False, want_device_plans: bool = False, stream: torch.cuda.Stream | None = None,
+                               stats: dict | None = None):
+        """Many block_ / carried-state mt_ streams in one call (hsrans_encode_device_ex_batch): member k is ``(container, states, bits,
+        d_in, d_out)`` or ``(container, states, bits, d_in, d_out, options)`` with ``options`` a dict of ``encode_device_ex``'s keywords
+        ``block_size``, ``independent_blocks``, ``index_interval``, ``index_groups`` and ``length`` (default ``d_in.numel()``).  Each
+        member gets what ``encode_device_ex`` gives it.  Returns the stream lengths, followed by the list of plan blobs (``want_plans``)
+        and/or the list of DevicePlans (``want_device_plans``), with None where a member asked for no index.  ``stats``: filled with
+        hsrans_encode_ex_batch_stats.  Synchronous; the tensors are kept alive until it returns.  Raises HsransError naming the first
+        failed member; the error carries ``code``, ``lengths``, ``rcs``, ``plans`` and ``device_plans`` (what the members that did not
+        fail got)."""
+        K = len(members)
+        arr = (EncodeExMember * max(K, 1))()
+        keep = []  # (tensors, options, group lists and plan buffers must outlive the call)
+        blobs = [None] * K
+        dev = None
+        for k, m in enumerate(members):
+            container, states, bits, d_in, d_out = m[:5]
+            o = dict(m[5]) if len(m) > 5 and m[5] is not None else {}
+            unknown = set(o) - {"block_size", "independent_blocks", "index_interval", "index_groups", "length"}
+            if unknown:
+                raise HsransError(f"encode_device_ex_batch: member {k}: unknown options {sorted(unknown)}")
+            dev = d_in.device if dev is None else dev
+            length = int(o.get("length", d_in.numel()))
+            block_size, index_interval = int(o.get("block_size", 0)), int(o.get("index_interval", 0))
+            groups = np.ascontiguousarray(o["index_groups"], dtype=np.uint64) if o.get("index_groups") is not None else None
+            if groups is not None and groups.size == 0:  # a stream too short for more than one chain (as encode_device_ex)
+                groups, index_interval = None, 4
+            n_groups = 0 if groups is None else groups.size
+            indexed = index_interval != 0 or n_groups != 0
+            if indexed:
+                pcap = (self.L.hsrans_plan_capacity_chains(container, states, length, n_groups, block_size) if n_groups
+                        else self.L.hsrans_plan_capacity(container, states, length, index_interval, block_size))
+                blobs[k] = np.zeros(max(pcap, 1), np.uint8)
+            opts = EncodeOpts(block_size, 0 if n_groups else index_interval, blobs[k].ctypes.data if indexed else None, blobs[k].size if indexed else 0, 0,
+                              ENC_INDEPENDENT_BLOCKS if o.get("independent_blocks") else 0, 0, groups.ctypes.data if n_groups else None, n_groups)
+            keep += [d_in, d_out, groups, opts]
+            e = arr[k]
+            e.container, e.states, e.bits = container, states, bits
+            e.d_in, e.length = d_in.data_ptr(), length
+            e.d_out, e.out_capacity = d_out.data_ptr(), d_out.numel()
+            e.opts = ctypes.pointer(opts)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        handles = (_vp * max(K, 1))()
+        st = EncodeExBatchStats()
+        rc = self.L.hsrans_encode_device_ex_batch(self.handle, arr, K, ctypes.c_void_p(s.cuda_stream), handles if want_device_plans else None, ctypes.byref(st))
+        if stats is not None:
+            stats.update({n: getattr(st, n) for n, _ in EncodeExBatchStats._fields_})
+        lengths = [int(arr[k].stream_length) for k in range(K)]
+        plans = [blobs[k][: arr[k].opts.contents.plan_size].copy() if blobs[k] is not None and lengths[k] else None for k in range(K)]
+        dplans = [DevicePlan(self, _vp(handles[k])) if want_device_plans and handles[k] else None for k in range(K)]
+        del keep
+        if rc != 0:
+            rcs = [int(arr[k].rc) for k in range(K)]
+            failed = [k for k in range(K) if rcs[k] != 0]
+            err = HsransError(f"hsrans_encode_device_ex_batch failed with code {rc}" + (f": member {failed[0]} failed" if failed and len(failed) < K else ""))
+            err.code, err.lengths, err.rcs, err.plans, err.device_plans = rc, lengths, rcs, plans, dplans
+            raise err
+        out = [lengths]
+        if want_plans:
+            out.append(plans)
+        if want_device_plans:
+            out.append(dplans)
+        return out[0] if len(out) == 1 else tuple(out)
 
     def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
                              stream: torch.cuda.Stream | None = None) -> np.ndarray:

@@ -1,4 +1,4 @@
-// enc_batch.h — hsrans_encode_device_batch: the _batch kernels, one launch per kernel kind over many streams.
+// enc_batch.h — hsrans_encode_device_batch and hsrans_encode_device_ex_batch: the _batch kernels, one launch per kernel kind over many streams.
 // Part of the one encoder translation unit hsrans_encode.hip (which includes the parts in dependency order and holds the launchers).
 #ifndef HSRANS_ENC_BATCH_H
 #define HSRANS_ENC_BATCH_H
@@ -83,6 +83,75 @@ __global__ void __launch_bounds__(64) k_plan_blocks_batch(const EncParams *__res
   if (ep.plan == nullptr)
     return;
   plan_blocks_body(ep, t.index);
+}
+
+// ---- batches of chain encodes (hsrans_encode_device_ex_batch): block_ / mt_ streams whose states run through every block -----------
+// What differs between members and a kernel argument cannot carry: where a member's summaries go and which logarithm table its bit
+// width reads — pointer arrays by member, as k_copy_images_batch takes `headers` — and its unit size, ep.block of its own record.
+
+// unit t.index of member t.member into summaries[t.member]
+__global__ void __launch_bounds__(256) k_unit_summaries_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ tasks, uint8_t *const *__restrict__ summaries)
+{
+  const EncTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  uint8_t *mine = summaries[t.member];
+  unit_summaries_body(ep, t.index, mine);
+}
+
+// the adaptive members' whole units: unit t.index of member t.member, with the table of the member's bit width
+__global__ void __launch_bounds__(64) k_unit_costs_batch(const EncParams *__restrict__ params, const EncTask *__restrict__ tasks, uint8_t *const *__restrict__ summaries,
+                                                         const float *const *__restrict__ log_tables)
+{
+  const EncTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  uint8_t *mine = summaries[t.member];
+  const float *table = log_tables[t.member];
+  unit_costs_body(ep, lane_id(), t.index, mine, table);
+}
+
+// A pointer read from a member's record is a generic one, and what is loaded through a generic pointer counts as different from lane
+// to lane: the chain loop reads its block records that way and steers its scalar word cursor by them.  A pointer that is a kernel
+// argument is known to point to device memory; this says the same of the record's.
+template <class T>
+__device__ __forceinline__ T *device_memory(T *p)
+{
+  __attribute__((address_space(1))) T *g = (__attribute__((address_space(1))) T *)p;
+  asm volatile("" : "+s"(g)); // (no instruction: keeps the two casts from being folded into none)
+  return (T *)g;
+}
+__device__ __forceinline__ EncParams chain_params_in_device_memory(EncParams ep)
+{
+  ep.in = device_memory(ep.in);
+  ep.out = device_memory(ep.out);
+  ep.scratch = device_memory(ep.scratch);
+  ep.image_bytes = device_memory(ep.image_bytes);
+  ep.image_off = device_memory(ep.image_off);
+  ep.result = device_memory(ep.result);
+  ep.ck_states = device_memory(ep.ck_states);
+  ep.ck_pos = device_memory(ep.ck_pos);
+  ep.given_counts = device_memory(ep.given_counts);
+  ep.ck_groups = device_memory(ep.ck_groups);
+  ep.chain_blocks = device_memory(ep.chain_blocks);
+  ep.block_states = device_memory(ep.block_states);
+  ep.stamps = device_memory(ep.stamps);
+  return ep;
+}
+
+// one workgroup of one wavefront per member: its whole chain
+template <uint32_t S>
+__global__ void __launch_bounds__(64) k_encode_chain_batch(const EncParams *__restrict__ params, const uint32_t *__restrict__ members)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  const EncParams ep = chain_params_in_device_memory(params[members[blockIdx.x]]);
+  encode_chain_body<S>(ep, *(WaveLdsT<kChunkFew> *)lds_raw, lane_id());
+}
+
+// part t.part of t.parts of image t.block of member t.member
+__global__ void __launch_bounds__(256) k_gather_chain_batch(const EncParams *__restrict__ params, const EncGatherTask *__restrict__ tasks)
+{
+  const EncGatherTask t = tasks[blockIdx.x];
+  const EncParams ep = params[t.member];
+  gather_chain_body(ep, t.block, t.part, t.parts);
 }
 
 } // namespace

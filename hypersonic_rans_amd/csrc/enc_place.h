@@ -97,6 +97,63 @@ __global__ void __launch_bounds__(256) k_block_histograms(EncParams ep, uint32_t
 // the unit summaries of the block walk (hsrans_host.h UnitSummary: counts[256], run_len, run_sym, fresh_cost; 1040 bytes), a workgroup per unit
 // of ep.block symbols: k_block_histograms' counting, and per thread the highest position whose byte differs from the unit's last
 // byte (one compare per byte; the run that ends the unit starts behind the highest of them)
+// (unit `b`: the body of k_unit_summaries_batch, and k_unit_summaries' own text below: called from that kernel it compiles to other code —
+// two instructions more, the rest in another order — and hsrans_encode_device_ex keeps its kernels' code, so the kernel keeps its body)
+__device__ __forceinline__ void unit_summaries_body(const EncParams &ep, const uint32_t b, uint8_t *summaries)
+{
+  constexpr uint32_t kCopies = 32;
+  __shared__ uint32_t sub[256 * kCopies];
+  __shared__ uint32_t differ;
+  const uint64_t begin = (uint64_t)b * ep.block;
+  const uint64_t end = b + 1 == ep.n_blocks ? ep.n : begin + ep.block;
+  const uint32_t last = ep.in[end - 1];
+  for (uint32_t k = threadIdx.x; k < 256 * kCopies; k += 256)
+    sub[k] = 0;
+  if (threadIdx.x == 0)
+    differ = 0;
+  __syncthreads();
+  uint32_t *mine = sub + (threadIdx.x & (kCopies - 1));
+  uint32_t my_differ = 0; // 1 + offset (from begin) of the highest byte seen that is not `last`; 0: none
+  auto count = [&](const uint4 &d, uint64_t off, uint32_t have) {
+    const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++)
+      if (k < have)
+      {
+        const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
+        atomicAdd(&mine[c * kCopies], 1u);
+        my_differ = c != last ? (uint32_t)(off - begin) + k + 1 : my_differ; // (offsets ascend per thread)
+      }
+  };
+  uint64_t off = begin + threadIdx.x * 16;
+  for (; off + 3 * 4096 + 16 <= end; off += 4 * 4096)
+  {
+    uint4 d[4];
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++)
+      d[u] = *(const uint4 *)(ep.in + off + u * 4096);
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++)
+      count(d[u], off + u * 4096, 16);
+  }
+  for (; off < end; off += 4096)
+    count(load16_guarded(ep.in, off, end), off, end - off < 16 ? (uint32_t)(end - off) : 16);
+  if (my_differ)
+    atomicMax(&differ, my_differ);
+  __syncthreads();
+  uint32_t v = 0;
+  for (uint32_t c = 0; c < kCopies; c++)
+    v += sub[threadIdx.x * kCopies + ((threadIdx.x + c) & (kCopies - 1))];
+  uint32_t *out = (uint32_t *)(summaries + (uint64_t)b * kUnitSummaryBytes);
+  out[threadIdx.x] = v;
+  if (threadIdx.x == 0)
+  {
+    out[256] = (uint32_t)(end - begin) - differ;
+    out[257] = last;
+    out[258] = 0; // fresh_cost: k_unit_costs
+    out[259] = 0;
+  }
+}
 __global__ void __launch_bounds__(256) k_unit_summaries(EncParams ep, uint8_t *summaries)
 {
   constexpr uint32_t kCopies = 32;
@@ -165,6 +222,47 @@ struct UnitCostLds
   uint4 table[256];    // (its scratch)
   float prod[256];
 };
+// (unit `u`: the body of k_unit_costs_batch, and k_unit_costs' own text below, kept there for the same reason as k_unit_summaries')
+__device__ __forceinline__ void unit_costs_body(const EncParams &ep, const uint32_t lane, const uint32_t u, uint8_t *summaries, const float *log_table)
+{
+  __shared__ UnitCostLds L;
+  uint32_t *sw = (uint32_t *)(summaries + (uint64_t)u * kUnitSummaryBytes);
+  if ((uint64_t)(u + 1) * ep.block > ep.n)
+  {
+    if (lane == 0)
+      sw[258] = 0;
+    return;
+  }
+  const uint32_t target = 1u << ep.bits;
+  const float factor = (float)target / (float)ep.block;
+  uint32_t raw[4], sc[4], part = 0;
+  for (uint32_t k = 0; k < 4; k++)
+  {
+    raw[k] = sw[lane * 4 + k];
+    const float v = __fmul_rn((float)raw[k], factor);
+    uint32_t c = (uint32_t)(uint16_t)__fadd_rn(v, 0.5f);
+    if (c == 0 && raw[k] != 0)
+      c = 1;
+    sc[k] = c;
+    part += c;
+    L.order[lane * 4 + k] = (c << 8) | (lane * 4 + k);
+  }
+  const uint32_t sum = wave_sum(part);
+  wave_sync();
+  if (sum != target)
+    adjust_counts<true>(L, lane, sc, sum, target);
+  for (uint32_t k = 0; k < 4; k++)
+    L.prod[lane * 4 + k] = raw[k] != 0 ? __fmul_rn((float)raw[k], log_table[sc[k]]) : 0.0f;
+  wave_sync();
+  if (lane == 0)
+  {
+    float cost = (float)(2 * 256 + ep.S * 4 + 8 * 2) * 0.5f;
+    for (uint32_t k = 0; k < 256; k++)
+      if (sw[k] != 0)
+        cost = __fsub_rn(cost, L.prod[k]);
+    ((float *)sw)[258] = cost;
+  }
+}
 __global__ void __launch_bounds__(64) k_unit_costs(EncParams ep, uint8_t *summaries, const float *log_table)
 {
   __shared__ UnitCostLds L;
@@ -561,6 +659,54 @@ __global__ void __launch_bounds__(256) k_copy_image(EncParams ep) { copy_image_b
 // The reference carries the states from block to block (mt_rANS32x64_16w_encode.cpp:220-222, the block_ encoders alike), so the
 // whole input is ONE dependent chain per state: one wavefront codes the blocks back to front (encode_body<CHAIN>), each into a
 // slot of its own, then adds up the image sizes and writes the file header; K_gather_chain moves the images into place.
+// (the body of k_encode_chain_batch: the chain loop, the placement scan and the header write — k_encode_chain's own text below, kept there
+// for the same reason as k_unit_summaries')
+template <uint32_t S>
+__device__ __forceinline__ void encode_chain_body(const EncParams &ep, WaveLdsT<kChunkFew> &L, const uint32_t lane)
+{
+  uint32_t x = 1u << 15;
+  uint32_t ck_left = ep.ck_groups ? ep.n_ck_groups : 0;
+  for (uint32_t b = ep.n_blocks; b-- > 0;)
+  {
+    if (ep.chain_independent)
+      x = 1u << 15;
+    encode_body<S, false, kChunkFew, true>(ep, b, L, lane, &x, &ck_left);
+    wave_sync(); // (the next block rebuilds the table and the rings this one read; its image sizes are read below)
+  }
+  // placement: image b at the file header plus the images in front of it
+  const uint64_t head = 16 + (ep.chain_mt ? 0 : 4 * (uint64_t)S);
+  uint64_t at = head;
+  for (uint32_t base = 0; base < ep.n_blocks; base += 64)
+  {
+    const uint32_t i = base + lane;
+    const uint64_t v = i < ep.n_blocks ? ep.image_bytes[i] : 0;
+    uint64_t incl = v;
+    for (int d = 1; d < 64; d <<= 1)
+    {
+      const uint64_t o = __shfl_up(incl, d, 64);
+      if ((int)lane >= d)
+        incl += o;
+    }
+    if (i < ep.n_blocks)
+      ep.image_off[i] = at + incl - v;
+    at += __shfl(incl, 63, 64);
+  }
+  const uint64_t total = at;
+  const bool fits = total <= ep.out_cap;
+  if (lane == 0)
+  {
+    ep.result[0] = total;
+    ep.result[1] = fits ? 1 : 0;
+    ep.result[2] = ck_left; // (listed checkpoints that were not met: 0 unless the list was not what the host filtered)
+    if (fits)
+    {
+      ((uint64_t *)ep.out)[0] = ep.n;
+      ((uint64_t *)ep.out)[1] = total;
+    }
+  }
+  if (fits && !ep.chain_mt && lane < S) // block_: the states after the first block follow the file header
+    ((uint32_t *)(ep.out + 16))[lane] = x;
+}
 template <uint32_t S>
 __global__ void __launch_bounds__(64) k_encode_chain(EncParams ep)
 {
@@ -611,12 +757,12 @@ __global__ void __launch_bounds__(64) k_encode_chain(EncParams ep)
     ((uint32_t *)(ep.out + 16))[lane] = x;
 }
 
-// copies image b (blockIdx.x) of a chain encode to its place, cut into gridDim.y parts; source and destination are 2-byte aligned
-__global__ void __launch_bounds__(256) k_gather_chain(EncParams ep)
+// copies image b of a chain encode to its place, part `part` of `parts`; source and destination are 2-byte aligned
+// (the body of k_gather_chain — b = blockIdx.x, cut into gridDim.y parts — and of k_gather_chain_batch)
+__device__ __forceinline__ void gather_chain_body(const EncParams &ep, const uint32_t b, const uint32_t part, const uint32_t parts)
 {
   if (ep.result[1] == 0)
     return;
-  const uint32_t b = blockIdx.x, part = blockIdx.y, parts = gridDim.y;
   const uint64_t bytes = ep.image_bytes[b];
   const uint8_t *src = ep.scratch + ep.chain_blocks[b].slot_end - bytes;
   uint8_t *dst = ep.out + ep.image_off[b];
@@ -637,6 +783,7 @@ __global__ void __launch_bounds__(256) k_gather_chain(EncParams ep)
     for (uint64_t k = head + body * 16 + threadIdx.x * 2; k < bytes; k += 512)
       *(uint16_t *)(dst + k) = *(const uint16_t *)(src + k);
 }
+__global__ void __launch_bounds__(256) k_gather_chain(EncParams ep) { gather_chain_body(ep, blockIdx.x, blockIdx.y, gridDim.y); }
 
 } // namespace
 } // namespace hsrans

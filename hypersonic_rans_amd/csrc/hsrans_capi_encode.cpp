@@ -1,6 +1,7 @@
 // hsrans_capi_encode.cpp — GPU encoder entries: hsrans_encode_device (mt_, one wavefront per block), hsrans_encode_device_raw,
 // hsrans_encode_device_ex (every format hsrans_encode_ex writes); and the host side the batch and the host pipeline share with the
-// single calls (declared in hsrans_internal.h): argument rules and shapes, per-block arrays, plan assembly, kernel setup.
+// single calls (declared in hsrans_internal.h): argument rules and shapes, per-block arrays, plan assembly, kernel setup, and the steps
+// of the chain path (ex_route ... chain_plan_finish) that hsrans_encode_device_ex and hsrans_encode_device_ex_batch both run.
 // Part of the C ABI of libhsrans_hip.so (include/hsrans_hip.h); split out of hsrans_capi.cpp in round 5 by concern.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -13,6 +14,7 @@
 #include <chrono>
 #include <mutex>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/hsrans_hip.h"
@@ -32,26 +34,20 @@ namespace
 {
 // the block choice of a chain encode: unit summaries on the device (counts, the run that ends each unit, and for the adaptive policy
 // every unit's own code length), the walk on the host (the host encoder's code).  Caller holds ctx->lock, device set.
-bool device_block_walk(hsrans_ctx *ctx, int container, uint32_t S, uint32_t bits, const void *d_in, size_t length, size_t block, hipStream_t s,
-                       std::vector<BlockSpan> *spans, size_t *n_units_out, double *summaries_us, double *walk_us)
+bool device_block_walk(hsrans_ctx *ctx, ChainJob *job, hipStream_t s, double *summaries_us, double *walk_us)
 {
   const auto t0 = std::chrono::steady_clock::now();
-  const bool fixed = block != 0;
-  const size_t unit = fixed ? block : walk_unit(container, S, bits);
-  const size_t n_units = (length + unit - 1) / unit;
+  if (!chain_units(job))
+    return false;
+  const bool fixed = job->fixed;
+  const size_t n_units = job->n_units;
   std::vector<UnitSummary> units(n_units);
-  std::vector<float> table(fixed ? 0 : (1u << bits) + 1);
+  std::vector<float> table(fixed ? 0 : (1u << job->bits) + 1);
   if (!fixed)
-    walk_log_table(bits, table.data());
-  EncParams ep{};
-  ep.S = S;
-  ep.bits = bits;
-  ep.in = (const uint8_t *)d_in;
-  ep.n = length;
-  ep.block = unit;
-  ep.n_blocks = (uint32_t)n_units;
+    walk_log_table(job->bits, table.data());
+  const EncParams ep = chain_units_params(*job);
   const size_t table_at = (n_units * sizeof(UnitSummary) + 255) & ~(size_t)255;
-  if (n_units > 0xFFFFFFFFull || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, table_at + table.size() * 4))
+  if (!grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, table_at + table.size() * 4))
     return false;
   const float *d_table = fixed ? nullptr : (const float *)(ctx->d_enc_meta + table_at);
   if ((!fixed && hipMemcpyAsync((void *)d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
@@ -62,10 +58,9 @@ bool device_block_walk(hsrans_ctx *ctx, int container, uint32_t S, uint32_t bits
     return false;
   }
   const auto t1 = std::chrono::steady_clock::now();
-  if (!(fixed ? fixed_blocks(length, block, S, bits, units.data(), spans) : reference_blocks(container, length, S, bits, units.data(), spans)))
+  if (!chain_walk(job, units.data()))
     return false;
   const auto t2 = std::chrono::steady_clock::now();
-  *n_units_out = n_units;
   *summaries_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
   *walk_us = std::chrono::duration<double, std::micro>(t2 - t1).count();
   return true;
@@ -87,6 +82,248 @@ size_t copy_choices(const std::vector<BlockSpan> &spans, hsrans_block_choice *ou
   return spans.size();
 }
 } // namespace
+
+ExRoute ex_route(int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity, const hsrans_encode_opts *opts, ChainJob *job)
+{
+  if (!valid_codec(container, states, bits) || d_in == nullptr || d_out == nullptr || length == 0)
+    return kExRefused;
+  if (out_capacity < capacity(container, states, length) || ((uintptr_t)d_in & 15) != 0 || ((uintptr_t)d_out & 15) != 0)
+    return kExRefused;
+  ChainJob j;
+  j.container = container;
+  j.S = (uint32_t)states;
+  j.bits = bits;
+  j.d_in = d_in;
+  j.length = length;
+  j.d_out = d_out;
+  j.out_capacity = out_capacity;
+  j.ig = opts && opts->n_index_groups ? opts->index_groups : nullptr;
+  j.n_ig = j.ig ? opts->n_index_groups : 0;
+  j.interval = j.ig ? 0 : (opts ? opts->index_interval : 0);
+  j.want_plan = j.interval != 0 || j.ig != nullptr;
+  if ((j.want_plan && ((j.interval % 4) != 0 || opts->plan_out == nullptr)) || !index_groups_valid(j.ig, j.n_ig))
+    return kExRefused;
+  j.fixed = opts && opts->block_size != 0;
+  j.independent = opts && (opts->flags & HSRANS_ENC_INDEPENDENT_BLOCKS) != 0;
+  if (j.independent && (container != HSRANS_MT || !j.fixed))
+    return kExRefused;
+  j.block = j.fixed ? opts->block_size : 0;
+  if (j.block % 64 != 0)
+    return kExRefused;
+  *job = std::move(j);
+  if (container == HSRANS_RAW)
+    return kExRaw;
+  if (job->independent && !job->want_plan)
+    return kExBlocks;
+  if (job->independent && job->interval != 0)
+    return kExBlocksPlan;
+  // limits of the one-wavefront pass: byte offsets inside a block's slot are 32-bit (as the raw encoder's; a fixed block longer than the
+  // input is the input: one block); listed checkpoints sit on set boundaries (4 groups) of a block, which fixed blocks of a group count
+  // that is not a multiple of 4 do not keep
+  if (length > 0x7FFF0000ull || (job->ig && job->fixed && (job->block / job->S) % 4 != 0))
+    return kExRefused;
+  return kExChain;
+}
+
+bool chain_units(ChainJob *job)
+{
+  job->unit = job->fixed ? job->block : walk_unit(job->container, job->S, job->bits);
+  job->n_units = (job->length + job->unit - 1) / job->unit;
+  return job->n_units <= 0xFFFFFFFFull;
+}
+
+EncParams chain_units_params(const ChainJob &job)
+{
+  EncParams ep{};
+  ep.S = job.S;
+  ep.bits = job.bits;
+  ep.in = (const uint8_t *)job.d_in;
+  ep.n = job.length;
+  ep.block = job.unit;
+  ep.n_blocks = (uint32_t)job.n_units;
+  return ep;
+}
+
+bool chain_walk(ChainJob *job, const UnitSummary *units)
+{
+  return job->fixed ? fixed_blocks(job->length, job->block, job->S, job->bits, units, &job->spans)
+                    : reference_blocks(job->container, job->length, job->S, job->bits, units, &job->spans);
+}
+
+void chain_prepare(ChainJob *job)
+{
+  const std::vector<BlockSpan> &spans = job->spans;
+  const uint32_t S = job->S, interval = job->interval;
+  const size_t nb = spans.size(), length = job->length;
+  const uint64_t T = length + 1 >= S ? (length - S + 1 + S - 1) / S : 0; // whole groups of the file
+  std::vector<ChainBlock> &cb = job->cb;
+  cb.assign(nb, ChainBlock{});
+  job->counts.assign(nb * 256, 0);
+  uint64_t slot_at = 0, slot_max = 0;
+  uint32_t n_ck = 0;
+  for (size_t b = 0; b < nb; b++)
+  {
+    const BlockSpan &sp = spans[b];
+    ChainBlock &c = cb[b];
+    c.begin = sp.begin;
+    c.end = sp.end;
+    c.slot_bytes = sp.single ? 512 : encode_slot_bytes(sp.end - sp.begin, S);
+    slot_at += c.slot_bytes;
+    slot_max = std::max<uint64_t>(slot_max, c.slot_bytes);
+    c.slot_end = slot_at;
+    c.single = sp.single ? 0x100u | sp.symbol : 0;
+    c.ck_base = n_ck;
+    if (!sp.single)
+    {
+      memcpy(&job->counts[b * 256], sp.hist.symbolCount, 512);
+      const uint64_t whole = (sp.end - sp.begin) / S;
+      if (interval != 0 && whole >= 1)
+        n_ck += (uint32_t)((whole - 1) / interval);
+    }
+  }
+  // listed checkpoints: the entries the host encoder meets (inside a coded block, not its first group, below T), and their blocks
+  std::vector<uint32_t> &ck_list = job->ck_list;
+  std::vector<uint32_t> &ck_block = job->ck_block; // (interval checkpoints too: the block of every checkpoint slot)
+  ck_list.clear();
+  ck_block.clear();
+  if (job->ig)
+  {
+    const uint64_t *ig = job->ig;
+    size_t b = 0;
+    for (size_t k = 0; k < job->n_ig && ig[k] < T; k++)
+    {
+      while (b < nb && (spans[b].end - 1) / S < ig[k])
+        b++;
+      if (b == nb)
+        break;
+      if (!spans[b].single && ig[k] > spans[b].begin / S)
+      {
+        ck_list.push_back((uint32_t)ig[k]);
+        ck_block.push_back((uint32_t)b);
+      }
+    }
+    n_ck = (uint32_t)ck_list.size();
+  }
+  else if (job->want_plan)
+  {
+    ck_block.reserve(n_ck);
+    for (size_t b = 0; b < nb; b++)
+    {
+      const uint32_t next = b + 1 < nb ? cb[b + 1].ck_base : n_ck;
+      for (uint32_t k = cb[b].ck_base; k < next; k++)
+        ck_block.push_back((uint32_t)b);
+    }
+  }
+  job->n_ck = n_ck;
+  job->slot_total = slot_at;
+  job->slot_max = slot_max;
+}
+
+namespace
+{
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+} // namespace
+
+ChainDown chain_down_layout(const ChainJob &job)
+{
+  const size_t nb = job.spans.size();
+  ChainDown d;
+  d.image_bytes = 0;
+  d.image_off = up256(nb * 8);
+  d.result = d.image_off + up256(nb * 8);
+  d.bytes = d.result + 256;
+  return d;
+}
+
+ChainUp chain_up_layout(const ChainJob &job)
+{
+  const size_t nb = job.spans.size();
+  ChainUp u;
+  u.blocks = 0;
+  u.counts = up256(nb * sizeof(ChainBlock));
+  u.list = u.counts + up256(nb * 512);
+  u.bytes = u.list + up256(job.ck_list.size() * 4 + 4);
+  return u;
+}
+
+ChainCk chain_ck_layout(const ChainJob &job)
+{
+  const size_t ck_slots = job.n_ck ? job.n_ck : 1;
+  ChainCk c;
+  c.ck_pos = ck_slots * job.S;
+  c.block_states = c.ck_pos + ck_slots;
+  c.bytes = c.block_states * 4 + (job.want_plan ? job.spans.size() * (size_t)job.S * 4 : 0);
+  return c;
+}
+
+void chain_up_fill(const ChainJob &job, uint8_t *host_up)
+{
+  const ChainUp u = chain_up_layout(job);
+  memcpy(host_up + u.blocks, job.cb.data(), job.cb.size() * sizeof(ChainBlock));
+  memcpy(host_up + u.counts, job.counts.data(), job.counts.size() * 2);
+  if (!job.ck_list.empty())
+    memcpy(host_up + u.list, job.ck_list.data(), job.ck_list.size() * 4);
+}
+
+EncParams chain_params(const ChainJob &job, uint8_t *d_scratch, uint8_t *d_down, uint8_t *d_up, uint8_t *d_ck)
+{
+  const ChainDown down = chain_down_layout(job);
+  const ChainUp up = chain_up_layout(job);
+  const ChainCk ck = chain_ck_layout(job);
+  EncParams ep{};
+  ep.S = job.S;
+  ep.bits = job.bits;
+  ep.in = (const uint8_t *)job.d_in;
+  ep.n = job.length;
+  ep.out = (uint8_t *)job.d_out;
+  ep.out_cap = job.out_capacity;
+  ep.scratch = d_scratch;
+  ep.slot_bytes = job.slot_max;
+  ep.n_blocks = (uint32_t)job.spans.size();
+  ep.image_bytes = (uint64_t *)(d_down + down.image_bytes);
+  ep.image_off = (uint64_t *)(d_down + down.image_off);
+  ep.result = (uint64_t *)(d_down + down.result);
+  ep.chain_blocks = (const ChainBlock *)(d_up + up.blocks);
+  ep.given_counts = (const uint16_t *)(d_up + up.counts);
+  ep.ck_groups = job.ck_list.empty() ? nullptr : (const uint32_t *)(d_up + up.list);
+  ep.n_ck_groups = (uint32_t)job.ck_list.size();
+  ep.interval = job.want_plan ? job.interval : 0;
+  ep.ck_states = (uint32_t *)d_ck;
+  ep.ck_pos = ep.ck_states + ck.ck_pos;
+  ep.block_states = job.want_plan ? ep.ck_states + ck.block_states : nullptr;
+  ep.chain_mt = job.container == HSRANS_MT ? 1 : 0;
+  ep.chain_independent = job.independent ? 1 : 0;
+  return ep;
+}
+
+size_t chain_plan_bytes(const ChainJob &job)
+{
+  // blocks_plan_from_checkpoints: one chain per block and one per checkpoint, every chain a single piece, no histogram copy
+  const uint64_t chains = (uint64_t)job.spans.size() + job.n_ck;
+  return chains > 0xFFFFFFFFull ? ~(size_t)0 : (size_t)plan_size((uint32_t)chains, (uint32_t)chains, job.S, 0);
+}
+
+size_t chain_plan_finish(const ChainJob &job, uint64_t total, const uint64_t *img_bytes, const uint64_t *img_off, const uint32_t *blk_states, const uint32_t *ck_states,
+                         const uint32_t *ck_pos, uint8_t *plan_out, size_t plan_capacity)
+{
+  const std::vector<BlockSpan> &spans = job.spans;
+  const uint32_t S = job.S, n_ck = job.n_ck;
+  const size_t nb = spans.size();
+  const uint64_t counts_at = job.container == HSRANS_MT ? 16 + 4 * (uint64_t)S : 8; // the counts inside a coded block's image
+  std::vector<EncodedBlock> blocks(nb);
+  for (size_t b = 0; b < nb; b++)
+    blocks[b] = EncodedBlock{spans[b].begin, spans[b].end, spans[b].single, spans[b].symbol, total - (img_off[b] + counts_at + 512),
+                             total - (img_off[b] + counts_at), &blk_states[b * S]};
+  std::vector<uint64_t> ck_group(n_ck), ck_wfe(n_ck);
+  for (uint32_t k = 0; k < n_ck; k++)
+  {
+    const uint32_t b = job.ck_block[k];
+    ck_group[k] = job.ig ? job.ck_list[k] : spans[b].begin / S + (uint64_t)(k - job.cb[b].ck_base + 1) * job.interval;
+    ck_wfe[k] = total - (img_off[b] + img_bytes[b]) + ck_pos[k]; // (ck_pos: bytes from the cursor to the end of the block's words)
+  }
+  return blocks_plan_from_checkpoints(job.container, (int)S, job.bits, job.length, total, job.interval, blocks.data(), nb, n_ck, ck_group.data(), ck_wfe.data(), ck_states,
+                                      plan_out, plan_capacity);
+}
 
 bool encoder_ready(hsrans_ctx *ctx)
 {
@@ -282,12 +519,18 @@ size_t hsrans_block_choices_device(hsrans_ctx *ctx, int container, int states, u
   std::lock_guard<std::mutex> guard(ctx->lock);
   if (hipSetDevice(ctx->device) != hipSuccess)
     return 0;
-  std::vector<BlockSpan> spans;
-  size_t n_units = 0;
+  ChainJob job;
+  job.container = container;
+  job.S = (uint32_t)states;
+  job.bits = bits;
+  job.d_in = d_in;
+  job.length = length;
+  job.block = block_size;
+  job.fixed = block_size != 0;
   double a = 0, b = 0;
-  if (!device_block_walk(ctx, container, (uint32_t)states, bits, d_in, length, block_size, (hipStream_t)hip_stream, &spans, &n_units, &a, &b))
+  if (!device_block_walk(ctx, &job, (hipStream_t)hip_stream, &a, &b))
     return 0;
-  return copy_choices(spans, out, capacity);
+  return copy_choices(job.spans, out, capacity);
 }
 
 size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity, const hsrans_hist *hist,
@@ -473,30 +716,20 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
     *out_dplan = nullptr;
   if (opts)
     opts->plan_size = 0;
-  if (ctx == nullptr || !valid_codec(container, states, bits) || d_in == nullptr || d_out == nullptr || length == 0)
+  ChainJob job;
+  const ExRoute route = ctx == nullptr ? kExRefused : ex_route(container, states, bits, d_in, length, d_out, out_capacity, opts, &job);
+  if (route == kExRefused)
     return 0;
-  if (out_capacity < capacity(container, states, length) || ((uintptr_t)d_in & 15) != 0 || ((uintptr_t)d_out & 15) != 0)
-    return 0;
-  const uint32_t S = (uint32_t)states;
-  const uint64_t *ig = opts && opts->n_index_groups ? opts->index_groups : nullptr;
-  const size_t n_ig = ig ? opts->n_index_groups : 0;
-  const uint32_t interval = ig ? 0 : (opts ? opts->index_interval : 0);
-  const bool want_plan = interval != 0 || ig != nullptr;
-  if ((want_plan && ((interval % 4) != 0 || opts->plan_out == nullptr)) || !index_groups_valid(ig, n_ig))
-    return 0;
-  const bool fixed = opts && opts->block_size != 0;
-  const bool independent = opts && (opts->flags & HSRANS_ENC_INDEPENDENT_BLOCKS) != 0;
-  if (independent && (container != HSRANS_MT || !fixed))
-    return 0;
-  const size_t block = fixed ? opts->block_size : 0;
-  if (block % 64 != 0)
-    return 0;
-  if (container == HSRANS_RAW)
+  const uint32_t S = job.S, interval = job.interval;
+  const uint64_t *ig = job.ig;
+  const size_t n_ig = job.n_ig, block = job.block;
+  const bool want_plan = job.want_plan;
+  if (route == kExRaw)
     return hsrans_encode_device_raw(ctx, states, bits, d_in, length, d_out, out_capacity, hist, interval, ig, n_ig, want_plan ? opts->plan_out : nullptr,
                                     want_plan ? opts->plan_capacity : 0, want_plan ? &opts->plan_size : nullptr, hip_stream, want_plan ? out_dplan : nullptr);
-  if (independent && !want_plan)
+  if (route == kExBlocks)
     return hsrans_encode_device(ctx, container, states, bits, d_in, length, d_out, out_capacity, (uint32_t)block, 0, hip_stream, nullptr);
-  if (independent && interval != 0) // the one-wave-per-block launch writes the host encoder's plan on the device (k_plan_blocks): copied back
+  if (route == kExBlocksPlan) // the one-wave-per-block launch writes the host encoder's plan on the device (k_plan_blocks): copied back
   {
     hsrans_dplan *dp = nullptr;
     const size_t total = hsrans_encode_device(ctx, container, states, bits, d_in, length, d_out, out_capacity, (uint32_t)block, interval, hip_stream, &dp);
@@ -512,11 +745,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
       *out_dplan = dp;
     return total;
   }
-  // limits of the one-wavefront pass: byte offsets inside a block's slot are 32-bit (as the raw encoder's; a fixed block longer than the
-  // input is the input: one block); listed checkpoints sit on set boundaries (4 groups) of a block, which fixed blocks of a group count
-  // that is not a multiple of 4 do not keep
-  if (length > 0x7FFF0000ull || (ig && fixed && (block / S) % 4 != 0))
-    return 0;
+  // (kExChain: ex_route has applied the limits of the one-wavefront pass)
 
   std::lock_guard<std::mutex> guard(ctx->lock);
   if (!encoder_ready(ctx))
@@ -525,102 +754,23 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
   const bool stamps = ctx->tuning.debug_stamps;
 
   // ---- a./b. unit summaries on the device, the block walk (the host encoder's) on the host ----
-  std::vector<BlockSpan> spans;
-  size_t n_units = 0;
   double summaries_us = 0, walk_us = 0;
-  if (!device_block_walk(ctx, container, S, bits, d_in, length, block, s, &spans, &n_units, &summaries_us, &walk_us))
+  if (!device_block_walk(ctx, &job, s, &summaries_us, &walk_us))
     return 0;
   const auto t2 = std::chrono::steady_clock::now();
-  const size_t nb = spans.size();
-  const uint64_t T = length + 1 >= S ? (length - S + 1 + S - 1) / S : 0; // whole groups of the file
-  std::vector<ChainBlock> cb(nb);
-  std::vector<uint16_t> counts(nb * 256);
-  uint64_t slot_at = 0, slot_max = 0;
-  uint32_t n_ck = 0;
-  for (size_t b = 0; b < nb; b++)
-  {
-    const BlockSpan &sp = spans[b];
-    ChainBlock &c = cb[b];
-    c.begin = sp.begin;
-    c.end = sp.end;
-    c.slot_bytes = sp.single ? 512 : encode_slot_bytes(sp.end - sp.begin, S);
-    slot_at += c.slot_bytes;
-    slot_max = std::max<uint64_t>(slot_max, c.slot_bytes);
-    c.slot_end = slot_at;
-    c.single = sp.single ? 0x100u | sp.symbol : 0;
-    c.ck_base = n_ck;
-    if (!sp.single)
-    {
-      memcpy(&counts[b * 256], sp.hist.symbolCount, 512);
-      const uint64_t whole = (sp.end - sp.begin) / S;
-      if (interval != 0 && whole >= 1)
-        n_ck += (uint32_t)((whole - 1) / interval);
-    }
-  }
-  // listed checkpoints: the entries the host encoder meets (inside a coded block, not its first group, below T), and their blocks
-  std::vector<uint32_t> ck_list;
-  std::vector<uint32_t> ck_block; // (interval checkpoints too: the block of every checkpoint slot)
-  if (ig)
-  {
-    size_t b = 0;
-    for (size_t k = 0; k < n_ig && ig[k] < T; k++)
-    {
-      while (b < nb && (spans[b].end - 1) / S < ig[k])
-        b++;
-      if (b == nb)
-        break;
-      if (!spans[b].single && ig[k] > spans[b].begin / S)
-      {
-        ck_list.push_back((uint32_t)ig[k]);
-        ck_block.push_back((uint32_t)b);
-      }
-    }
-    n_ck = (uint32_t)ck_list.size();
-  }
-  else if (want_plan)
-  {
-    ck_block.reserve(n_ck);
-    for (size_t b = 0; b < nb; b++)
-    {
-      const uint32_t next = b + 1 < nb ? cb[b + 1].ck_base : n_ck;
-      for (uint32_t k = cb[b].ck_base; k < next; k++)
-        ck_block.push_back((uint32_t)b);
-    }
-  }
+  chain_prepare(&job);
+  const size_t nb = job.spans.size(), n_units = job.n_units;
+  const uint32_t n_ck = job.n_ck;
 
   // ---- c. the chain: one wavefront, blocks back to front; then the images into place ----
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t off_bytes = 0, off_off = up256(nb * 8), off_result = off_off + up256(nb * 8), off_blocks = off_result + 256,
-               off_counts = off_blocks + up256(nb * sizeof(ChainBlock)), off_list = off_counts + up256(nb * 512), meta_bytes = off_list + up256(ck_list.size() * 4 + 4);
-  const size_t ck_slots = n_ck ? n_ck : 1;
-  const size_t states_bytes = want_plan ? nb * (size_t)S * 4 : 0;
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, slot_at) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta_bytes) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck_slots * ((size_t)S * 4 + 4) + states_bytes))
+  const ChainDown down = chain_down_layout(job);
+  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, job.slot_total) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, down.bytes + chain_up_bytes(job)) ||
+      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, chain_ck_bytes(job)))
     return 0;
-  uint8_t *meta = ctx->d_enc_meta;
-  EncParams ep{};
-  ep.S = S;
-  ep.bits = bits;
-  ep.in = (const uint8_t *)d_in;
-  ep.n = length;
-  ep.out = (uint8_t *)d_out;
-  ep.out_cap = out_capacity;
-  ep.scratch = ctx->d_enc_scratch;
-  ep.slot_bytes = slot_max;
-  ep.n_blocks = (uint32_t)nb;
-  ep.image_bytes = (uint64_t *)(meta + off_bytes);
-  ep.image_off = (uint64_t *)(meta + off_off);
-  ep.result = (uint64_t *)(meta + off_result);
-  ep.chain_blocks = (const ChainBlock *)(meta + off_blocks);
-  ep.given_counts = (const uint16_t *)(meta + off_counts);
-  ep.ck_groups = ck_list.empty() ? nullptr : (const uint32_t *)(meta + off_list);
-  ep.n_ck_groups = (uint32_t)ck_list.size();
-  ep.interval = want_plan ? interval : 0;
-  ep.ck_states = (uint32_t *)ctx->d_enc_ck;
-  ep.ck_pos = ep.ck_states + ck_slots * S;
-  ep.block_states = want_plan ? ep.ck_pos + ck_slots : nullptr;
-  ep.chain_mt = container == HSRANS_MT ? 1 : 0;
-  ep.chain_independent = independent ? 1 : 0;
+  const EncParams ep = chain_params(job, ctx->d_enc_scratch, ctx->d_enc_meta, ctx->d_enc_meta + down.bytes, ctx->d_enc_ck);
+  const std::vector<ChainBlock> &cb = job.cb;
+  const std::vector<uint16_t> &counts = job.counts;
+  const std::vector<uint32_t> &ck_list = job.ck_list;
   uint64_t result[kEncResultWords] = {};
   bool ok = hipMemcpyAsync((void *)ep.chain_blocks, cb.data(), nb * sizeof(ChainBlock), hipMemcpyHostToDevice, s) == hipSuccess &&
             hipMemcpyAsync((void *)ep.given_counts, counts.data(), nb * 512, hipMemcpyHostToDevice, s) == hipSuccess &&
@@ -654,20 +804,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
       (n_ck && (hipMemcpy(ck_states.data(), ep.ck_states, (size_t)n_ck * S * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                 hipMemcpy(ck_pos.data(), ep.ck_pos, (size_t)n_ck * 4, hipMemcpyDeviceToHost) != hipSuccess)))
     return 0;
-  const uint64_t counts_at = container == HSRANS_MT ? 16 + 4 * (uint64_t)S : 8; // the counts inside a coded block's image
-  std::vector<EncodedBlock> blocks(nb);
-  for (size_t b = 0; b < nb; b++)
-    blocks[b] = EncodedBlock{spans[b].begin, spans[b].end, spans[b].single, spans[b].symbol, total - (img_off[b] + counts_at + 512),
-                             total - (img_off[b] + counts_at), &blk_states[b * S]};
-  std::vector<uint64_t> ck_group(n_ck), ck_wfe(n_ck);
-  for (uint32_t k = 0; k < n_ck; k++)
-  {
-    const uint32_t b = ck_block[k];
-    ck_group[k] = ig ? ck_list[k] : spans[b].begin / S + (uint64_t)(k - cb[b].ck_base + 1) * interval;
-    ck_wfe[k] = total - (img_off[b] + img_bytes[b]) + ck_pos[k]; // (ck_pos: bytes from the cursor to the end of the block's words)
-  }
-  const size_t psize = blocks_plan_from_checkpoints(container, states, bits, length, total, interval, blocks.data(), nb, n_ck, ck_group.data(), ck_wfe.data(),
-                                                    ck_states.data(), opts->plan_out, opts->plan_capacity);
+  const size_t psize = chain_plan_finish(job, total, img_bytes.data(), img_off.data(), blk_states.data(), ck_states.data(), ck_pos.data(), opts->plan_out, opts->plan_capacity);
   if (psize == 0)
     return 0;
   opts->plan_size = psize;

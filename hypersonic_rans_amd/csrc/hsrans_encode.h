@@ -128,6 +128,28 @@ hipError_t launch_encode_batch(const EncBatch &batch, uint32_t cus, hipStream_t 
 // asynchronous on `stream`: K_plan over `tasks` (the mt_ blocks); members whose EncParams::plan is null are skipped
 hipError_t launch_encode_plan_batch(const EncParams *params, const EncTask *tasks, uint32_t n_tasks, hipStream_t stream, uint32_t *launches);
 
+// ---- batches of chain encodes (hsrans_encode_device_ex_batch) ----
+// parts an image of a chain encode is copied in: about 1 MiB each of the stream's largest slot, so that few large adaptive blocks still spread over the device
+inline uint32_t chain_gather_parts(uint64_t largest_slot_bytes)
+{
+  const uint64_t mib = largest_slot_bytes >> 20;
+  return (uint32_t)(mib < 1 ? 1 : mib > 256 ? 256 : mib);
+}
+// one workgroup of the batched gather copies part `part` (of `parts`) of image `block` of member `member`
+struct EncGatherTask
+{
+  uint32_t member, block, part, parts;
+};
+// asynchronous on `stream`: the unit summaries of many streams, every array in device memory.  params[m]: launch_unit_summaries' EncParams of
+// member m; unit_tasks: {member, unit, 0} for every unit; cost_tasks: the same for the whole units of the members that walk the adaptive policy
+// (none: no launch); summaries[m], log_tables[m]: where member m's summaries go, and walk_log_table's of its bit width (adaptive members)
+hipError_t launch_unit_summaries_batch(const EncParams *params, const EncTask *unit_tasks, uint32_t n_unit_tasks, const EncTask *cost_tasks, uint32_t n_cost_tasks,
+                                       uint8_t *const *summaries, const float *const *log_tables, hipStream_t stream, uint32_t *launches);
+// asynchronous on `stream`: K_chain per state count present — members[0, n64) of 64 states, then n32 of 32, a workgroup of one wavefront
+// each — then one K_gather_chain over `gather`.  params[m]: launch_encode_chain's EncParams of member m
+hipError_t launch_encode_chain_batch(const EncParams *params, const uint32_t *members, uint32_t n64, uint32_t n32, const EncGatherTask *gather, uint32_t n_gather,
+                                     hipStream_t stream, uint32_t *launches);
+
 } // namespace hsrans
 
 #endif // HSRANS_ENCODE_H

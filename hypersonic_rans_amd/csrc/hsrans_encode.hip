@@ -1,4 +1,4 @@
-// The gfx950 encoders (include/hsrans_hip.h: hsrans_encode_device, _raw, _ex, _batch, hsrans_encode_host_pipelined): this file holds the
+// The gfx950 encoders (include/hsrans_hip.h: hsrans_encode_device, _raw, _ex, _batch, _ex_batch, hsrans_encode_host_pipelined): this file holds the
 // launchers; the device code is in the enc_*.h parts included below, in dependency order:
 //   enc_common.h     constants, the coding wavefront's LDS (WaveLdsT), 2-byte-aligned word types, lane / wave helpers, scans and sums
 //   enc_normalise.h  the reference's count normalisation on one wavefront: the heap sort replayed in registers, adjust_counts
@@ -31,7 +31,8 @@
 //            k_scan_images_carried / k_gather_images_carried with the stream position carried from slice to slice, and
 //            k_plan_blocks_carried after the last one
 //   batch    many independent raw and mt_ streams, one launch per kernel kind (hsrans_encode_device_batch): the k_*_batch kernels, which
-//            read their member's parameters from a device table and run the single calls' bodies
+//            read their member's parameters from a device table and run the single calls' bodies; many chain streams likewise
+//            (hsrans_encode_device_ex_batch): k_unit_summaries_batch / k_unit_costs_batch, k_encode_chain_batch<S>, k_gather_chain_batch
 //
 // Every result is byte-identical to the host encoder's (hsrans_host.cpp encode()).
 #include <hip/hip_runtime.h>
@@ -84,7 +85,9 @@ hipError_t prepare_encode_kernels()
                                                      {(const void *)k_encode_blocks_batch<64, kChunkFew>, lds_few},
                                                      {(const void *)k_encode_blocks_batch<32, kChunkFew>, lds_few},
                                                      {(const void *)k_encode_blocks_batch<64, kChunkMany>, lds_many},
-                                                     {(const void *)k_encode_blocks_batch<32, kChunkMany>, lds_many}};
+                                                     {(const void *)k_encode_blocks_batch<32, kChunkMany>, lds_many},
+                                                     {(const void *)k_encode_chain_batch<64>, lds_few},
+                                                     {(const void *)k_encode_chain_batch<32>, lds_few}};
   for (const auto &k : kernels)
   {
     const hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second);
@@ -180,9 +183,55 @@ hipError_t launch_encode_chain(const EncParams &ep, hipStream_t stream)
     hipLaunchKernelGGL(k_encode_chain<64>, dim3(1), dim3(64), lds, stream, ep);
   else
     hipLaunchKernelGGL(k_encode_chain<32>, dim3(1), dim3(64), lds, stream, ep);
-  // parts per image: about 1 MiB each of the largest slot (ep.slot_bytes here), so that few large adaptive blocks still spread over the device
-  const uint32_t parts = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, ep.slot_bytes >> 20));
+  // parts per image: from the largest slot (ep.slot_bytes here)
+  const uint32_t parts = chain_gather_parts(ep.slot_bytes);
   hipLaunchKernelGGL(k_gather_chain, dim3(ep.n_blocks, parts), dim3(256), 0, stream, ep);
+  return hipGetLastError();
+}
+
+hipError_t launch_unit_summaries_batch(const EncParams *params, const EncTask *unit_tasks, uint32_t n_unit_tasks, const EncTask *cost_tasks, uint32_t n_cost_tasks,
+                                       uint8_t *const *summaries, const float *const *log_tables, hipStream_t stream, uint32_t *launches)
+{
+  (void)hipGetLastError();
+  uint32_t n = 0;
+  if (n_unit_tasks != 0)
+  {
+    hipLaunchKernelGGL(k_unit_summaries_batch, dim3(n_unit_tasks), dim3(256), 0, stream, params, unit_tasks, summaries);
+    n++;
+  }
+  if (n_cost_tasks != 0)
+  {
+    hipLaunchKernelGGL(k_unit_costs_batch, dim3(n_cost_tasks), dim3(64), 0, stream, params, cost_tasks, summaries, log_tables);
+    n++;
+  }
+  if (launches)
+    *launches += n;
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_chain_batch(const EncParams *params, const uint32_t *members, uint32_t n64, uint32_t n32, const EncGatherTask *gather, uint32_t n_gather,
+                                     hipStream_t stream, uint32_t *launches)
+{
+  const size_t lds = sizeof(WaveLdsT<kChunkFew>);
+  (void)hipGetLastError();
+  uint32_t n = 0;
+  if (n64 != 0)
+  {
+    hipLaunchKernelGGL(k_encode_chain_batch<64>, dim3(n64), dim3(64), lds, stream, params, members);
+    n++;
+  }
+  if (n32 != 0)
+  {
+    hipLaunchKernelGGL(k_encode_chain_batch<32>, dim3(n32), dim3(64), lds, stream, params, members + n64);
+    n++;
+  }
+  if (n_gather != 0)
+  {
+    hipLaunchKernelGGL(k_gather_chain_batch, dim3(n_gather), dim3(256), 0, stream, params, gather);
+    n++;
+  }
+  if (launches)
+    *launches += n;
   return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 
 #include "../../include/hsrans_hip.h"
 #include "hsrans_encode.h"
+#include "hsrans_host.h"
 #include "hsrans_kernels.h"
 
 using namespace hsrans;
@@ -321,6 +322,79 @@ void mt_plan_adopt(hsrans_dplan *d, const EncParams &ep, const PlanHeader &h, hi
 // out_dplan, a device plan of it.  Returns the plan's size, 0 on failure.
 size_t raw_plan(hsrans_ctx *ctx, const EncShape &sh, uint64_t total, const uint64_t *index_groups, const uint8_t *header, const uint32_t *ck_states,
                 const uint32_t *ck_pos, uint8_t *plan_out, size_t plan_capacity, size_t *plan_size, hsrans_dplan **out_dplan);
+
+// ---- the chain path (hsrans_capi_encode.cpp): what hsrans_encode_device_ex and hsrans_encode_device_ex_batch share, step by step ----
+// where hsrans_encode_device_ex sends its arguments (the context and the histogram aside); kExRefused: it returns 0
+enum ExRoute
+{
+  kExRefused,
+  kExRaw,        // hsrans_encode_device_raw
+  kExBlocks,     // hsrans_encode_device, no plan
+  kExBlocksPlan, // hsrans_encode_device with checkpoints every interval, its plan read back
+  kExChain       // the chain: unit summaries, the host walk, one coding wavefront, the gather
+};
+// One stream on its way through the chain path: the arguments (ex_route), the summaries request (chain_units), the blocks (chain_walk)
+// and what the coding wavefront and the plan need of them (chain_prepare)
+struct ChainJob
+{
+  int container = 0;
+  uint32_t S = 0, bits = 0;
+  const void *d_in = nullptr;
+  size_t length = 0;
+  void *d_out = nullptr;
+  size_t out_capacity = 0;
+  size_t block = 0; // fixed blocks of this many symbols; 0: the adaptive policy
+  bool fixed = false, independent = false, want_plan = false;
+  uint32_t interval = 0; // checkpoints every `interval` groups (0 with listed ones)
+  const uint64_t *ig = nullptr; // listed checkpoints, or null
+  size_t n_ig = 0;
+  size_t unit = 0, n_units = 0; // chain_units: the summaries' unit (the fixed block, or walk_unit) and their number
+  std::vector<BlockSpan> spans; // chain_walk
+  // chain_prepare
+  std::vector<ChainBlock> cb;
+  std::vector<uint16_t> counts;  // [blocks][256]: the normalised counts of the coded blocks
+  std::vector<uint32_t> ck_list; // listed checkpoints the host encoder meets (inside a coded block, not its first group, below the file's whole groups)
+  std::vector<uint32_t> ck_block; // the block of every checkpoint slot
+  uint32_t n_ck = 0;
+  uint64_t slot_total = 0, slot_max = 0; // bytes of all slots, of the largest
+};
+// hsrans_encode_device_ex's refusals, in its order, and its routes; *job gets the arguments as the chain takes them
+ExRoute ex_route(int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity, const hsrans_encode_opts *opts, ChainJob *job);
+// the summaries request: job->unit, job->n_units; false: more units than a launch has workgroups
+bool chain_units(ChainJob *job);
+EncParams chain_units_params(const ChainJob &job); // what the summary kernels read: S, bits, in, n, block = unit, n_blocks = n_units
+// the host walk over the summaries that came down (reference_blocks / fixed_blocks): job->spans
+bool chain_walk(ChainJob *job, const UnitSummary *units);
+// the ChainBlocks, the counts and the interval / listed checkpoint bookkeeping from job->spans
+void chain_prepare(ChainJob *job);
+// A prepared job's device memory.  up (host -> device): blocks, counts, listed checkpoints.  down (device -> host): image sizes, image offsets,
+// result words.  ck: checkpoint states, checkpoint positions and, with a plan, the block states (offsets in 32-bit words).  Regions are 256-byte aligned.
+struct ChainUp
+{
+  size_t blocks, counts, list, bytes;
+};
+struct ChainDown
+{
+  size_t image_bytes, image_off, result, bytes;
+};
+struct ChainCk
+{
+  size_t ck_pos, block_states, bytes;
+};
+ChainUp chain_up_layout(const ChainJob &job);
+ChainDown chain_down_layout(const ChainJob &job);
+ChainCk chain_ck_layout(const ChainJob &job);
+inline size_t chain_up_bytes(const ChainJob &job) { return chain_up_layout(job).bytes; }
+inline size_t chain_down_bytes(const ChainJob &job) { return chain_down_layout(job).bytes; }
+inline size_t chain_ck_bytes(const ChainJob &job) { return chain_ck_layout(job).bytes; }
+void chain_up_fill(const ChainJob &job, uint8_t *host_up); // the up region's content
+// the coding wavefront's and the gather's parameters, the job's regions at the given device addresses
+EncParams chain_params(const ChainJob &job, uint8_t *d_scratch, uint8_t *d_down, uint8_t *d_up, uint8_t *d_ck);
+// the plan's size, known once the job is prepared
+size_t chain_plan_bytes(const ChainJob &job);
+// the plan finish: the device's block and checkpoint records through the host encoder's plan assembly; the plan's size, 0: it does not fit
+size_t chain_plan_finish(const ChainJob &job, uint64_t total, const uint64_t *image_bytes, const uint64_t *image_off, const uint32_t *block_states,
+                         const uint32_t *ck_states, const uint32_t *ck_pos, uint8_t *plan_out, size_t plan_capacity);
 
 // ---- what the host-ranges gathers share (hsrans_capi_gather.cpp): hsrans_decode_device_gather and hsrans_decode_device_gather_batch ----
 // the segment length L a gather of d cuts its ranges at: hsrans_gather_segment's rule with the plan's floor (HSRANS_GATHER_MIN_SEGMENT

@@ -734,6 +734,63 @@ typedef struct hsrans_encode_batch_stats
 int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member *members, uint32_t count, void *hip_stream, hsrans_dplan **out_dplans,
                                hsrans_encode_batch_stats *stats);
 
+/* Many block_ and carried-state mt_ streams encoded on the GPU at once: hsrans_encode_device_ex's chain path for many streams, the
+ * encode-side twin of hsrans_decode_device_indexing_batch.  A stream of these formats is one dependent chain — one wavefront — at
+ * any size; the chains of different streams are independent and run side by side.
+ *
+ * Member equivalence.  Member k gets exactly what hsrans_encode_device_ex(ctx, container, states, bits, d_in, length, d_out,
+ * out_capacity, NULL, opts, hip_stream, out_dplans ? &p : NULL) gives it: the same bytes at d_out, the same returned length in
+ * stream_length, the same blob at opts->plan_out with the same opts->plan_size, and in out_dplans[k] a device plan over that blob
+ * (NULL where the single call returns none: no index asked for).  Stream and plan are byte for byte hsrans_encode_ex's.
+ * Which members.  Those the single call sends to its chain: every HSRANS_BLOCK member; HSRANS_MT with carried states, adaptive
+ * (block_size == 0) or fixed blocks; HSRANS_MT with HSRANS_ENC_INDEPENDENT_BLOCKS and listed checkpoints (index_groups).  HSRANS_RAW
+ * members and independent fixed mt_ blocks with index_interval or with no index belong to hsrans_encode_device_batch and get
+ * HSRANS_E_ARG here, as that call refuses these.  32 and 64 states, every bit width, adaptive and fixed blocks, members with and
+ * without an index may share one call; count is 1..65,536.
+ * Validation before launch.  Every member is checked with hsrans_encode_device_ex's rules (length <= 2^31 - 2^16; index_groups with
+ * fixed blocks need block_size / states to be a multiple of 4; ...).  Besides: no two members' [d_out, d_out + out_capacity) may
+ * overlap, no output may overlap any member's [d_in, d_in + length), and no two members may share an opts object or a plan_out range.
+ * Any violation: HSRANS_E_ARG, nothing launched, no output byte changed, every stream_length 0, every rc HSRANS_E_ARG, every
+ * plan_size 0, every out_dplans[k] NULL.  A NULL ctx or members, count == 0 or count > 65,536: HSRANS_E_ARG (the members are left
+ * untouched where they cannot be read).
+ * Failure after launch is per member.  A member whose plan does not fit plan_capacity — known after its walk — gets rc =
+ * HSRANS_E_ARG, stream_length 0, plan_size 0, a NULL plan, and is left out of the coding launch: its d_out stays untouched.  A member
+ * whose result words report an internal inconsistency gets HSRANS_E_DEVICE.  The others complete.  The call returns the first rc
+ * that is not HSRANS_OK, in member order.  HSRANS_E_HIP: the runtime failed; every rc is HSRANS_E_HIP, and the call returns after
+ * everything it queued has drained.
+ * Synchronisation.  Two hipStreamSynchronize(hip_stream), whatever count: behind the summaries (the host walks need them) and behind
+ * the coding and gather.  The image sizes and offsets, block states, checkpoint states and positions of all members lie next to each
+ * other and come down in front of the second one in two copies; no blocking copy per member.  With out_dplans, each member with an
+ * index costs one hsrans_dplan_create (one allocation, one upload), as the single call does.
+ * Launch count.  Independent of count, at most 5 kernels: the unit summaries (one launch over all (member, unit) tasks), the unit
+ * costs (one over the adaptive members' whole units; none when no member is adaptive or none has a whole unit), the coding wavefronts (one per state count
+ * present: a workgroup of one wavefront per member, the longest first), the gather (one over all (member, block, part) tasks);
+ * plus one upload of the members' records in front of each phase and the copies down.  stats->launches counts the kernels.
+ * Host work.  The block walks run member by member on the calling thread (stats->walk_us).  With HSRANS_DEBUG_STAMPS=1 (read at
+ * hsrans_ctx_create) the call prints one line with its four phase times.
+ * Memory.  The context's encode buffers grow to the sum over all members: slots of about 2 x length each, 1,040 bytes per summary
+ * unit, the per-block records and checkpoints.  Calls on one context are serialised.
+ * Limits: the single call's, and fewer than 2^24 summary units and 2^24 gather workgroups in one call (HSRANS_E_ARG). */
+typedef struct hsrans_encode_ex_member
+{
+  int container, states;      /* HSRANS_BLOCK or HSRANS_MT; 32 or 64 */
+  uint32_t bits;              /* 10..15 */
+  const void *d_in;           /* device, 16-byte aligned */
+  size_t length;
+  void *d_out;                /* device, 16-byte aligned, out_capacity >= hsrans_capacity(container, states, length) */
+  size_t out_capacity;
+  hsrans_encode_opts *opts;   /* as hsrans_encode_device_ex takes it; may be NULL (adaptive blocks, no index); plan_size is set */
+  size_t stream_length;       /* out: bytes written to d_out, 0 = this member failed */
+  int rc;                     /* out: HSRANS_OK, or why stream_length is 0 */
+} hsrans_encode_ex_member;
+typedef struct hsrans_encode_ex_batch_stats
+{
+  uint32_t launches, block_members, mt_members, units, blocks; /* kernels launched; members by container; summary units; coded + single-symbol blocks */
+  double summaries_us, walk_us, chain_us, plans_us;            /* host clock: up to the first synchronisation; the host walks; up to the second; the plans */
+} hsrans_encode_ex_batch_stats;
+int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_member *members, uint32_t count, void *hip_stream,
+                                  hsrans_dplan **out_dplans /* [count] or NULL */, hsrans_encode_ex_batch_stats *stats /* may be NULL */);
+
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one
  * sequential wavefront), HSRANS_MT (one wavefront per block) and HSRANS_BLOCK (one sequential wavefront that also reports

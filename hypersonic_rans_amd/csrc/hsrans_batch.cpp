@@ -140,8 +140,10 @@ try
       G.n_groups = (uint32_t)all.size();
       G.shape = batch_grouped_shape(b->tuning, ctx->geom, bits, G.n_groups, chains);
       const size_t counter_bytes = (size_t)kCounterSets * kDynQueueStride * 8;
-      auto up256g = [](size_t v) { return (v + 255) & ~(size_t)255; };
-      const size_t bytes = up256g(gm.size() * sizeof(GroupMember)) + up256g(all.size() * sizeof(Group)) + counter_bytes;
+      Carve at; // [members | groups | ticket counters]
+      at.take(gm.size() * sizeof(GroupMember));
+      const size_t off_groups = at.take(all.size() * sizeof(Group)), off_tickets = at.take(counter_bytes);
+      const size_t bytes = at.at;
       uint8_t *dev = nullptr;
       if (hipMalloc((void **)&dev, bytes) != hipSuccess)
       {
@@ -149,8 +151,8 @@ try
         return HSRANS_E_HIP;
       }
       G.d_members = (const GroupMember *)dev;
-      G.d_groups = (const Group *)(dev + up256g(gm.size() * sizeof(GroupMember)));
-      G.d_tickets = (unsigned long long *)(dev + up256g(gm.size() * sizeof(GroupMember)) + up256g(all.size() * sizeof(Group)));
+      G.d_groups = (const Group *)(dev + off_groups);
+      G.d_tickets = (unsigned long long *)(dev + off_tickets);
       G.epoch = new (std::nothrow) std::atomic<uint32_t>(0);
       const bool ok = G.epoch != nullptr && hipMemset(dev, 0, bytes) == hipSuccess && hipMemcpy(dev, gm.data(), gm.size() * sizeof(GroupMember), hipMemcpyHostToDevice) == hipSuccess &&
                       hipMemcpy((void *)G.d_groups, all.data(), all.size() * sizeof(Group), hipMemcpyHostToDevice) == hipSuccess;
@@ -185,7 +187,6 @@ try
   std::sort(b->solo.begin(), b->solo.end());
   const size_t n_launches = launch_members.size();
   // one allocation: per launch its member records and its slot table
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
   size_t arena = 0;
   std::vector<std::vector<uint8_t>> host_blobs;
   for (size_t l = 0; l < n_launches; l++)
@@ -243,7 +244,10 @@ try
     for (size_t i = 0; i < L.member_idx.size(); i++)
       b->order_run[L.member_idx[i]] = deal.order_run[i];
     // blobs to upload: members, then slots
-    std::vector<uint8_t> blob(up256(L.member_idx.size() * sizeof(BatchMember)) + up256(deal.slots.size() * sizeof(BatchSlot)));
+    Carve at;
+    at.take(L.member_idx.size() * sizeof(BatchMember));
+    const size_t off_slots = at.take(deal.slots.size() * sizeof(BatchSlot));
+    std::vector<uint8_t> blob(at.close());
     BatchMember *bm = (BatchMember *)blob.data();
     for (size_t i = 0; i < L.member_idx.size(); i++)
     {
@@ -259,7 +263,7 @@ try
       bm[i].bits = d->hdr.bits;
       bm[i].S = d->hdr.states;
     }
-    memcpy(blob.data() + up256(L.member_idx.size() * sizeof(BatchMember)), deal.slots.data(), deal.slots.size() * sizeof(BatchSlot));
+    memcpy(blob.data() + off_slots, deal.slots.data(), deal.slots.size() * sizeof(BatchSlot));
     arena += blob.size();
     host_blobs.push_back(std::move(blob));
     b->direct.push_back(std::move(L));

@@ -130,7 +130,7 @@ static int calibrate_impl(hsrans_ctx *ctx, uint32_t bits, uint32_t iterations, u
     // pair of a set larger than the 256 MB Infinity Cache — a lone launch on warm buffers shows the youngest wave class only
     // 0.3 us late, a launch of a sustained rotation 1.5 us (its prologue loads and its stores are served last), and chains
     // fitted to the former leave that class to finish the rotated launch alone.  (One pair if the device cannot spare 400 MB.)
-    const size_t stream_stride = ((stream_len + 15) / 16 * 16 + 255) / 256 * 256 + 256;
+    const size_t stream_stride = up256(stream_len) + 256;
     uint32_t pairs = copies > 1 ? copies + 2 : 5; // (a batch launch writes `copies` outputs: the next launch's are other buffers)
     if (hipMalloc((void **)&d_stream, pairs * stream_stride) != hipSuccess || hipMalloc((void **)&d_out, pairs * n) != hipSuccess)
     {

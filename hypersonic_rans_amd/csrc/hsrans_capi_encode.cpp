@@ -46,8 +46,10 @@ bool device_block_walk(hsrans_ctx *ctx, ChainJob *job, hipStream_t s, double *su
   if (!fixed)
     walk_log_table(job->bits, table.data());
   const EncParams ep = chain_units_params(*job);
-  const size_t table_at = (n_units * sizeof(UnitSummary) + 255) & ~(size_t)255;
-  if (!grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, table_at + table.size() * 4))
+  Carve meta; // [summaries | logarithm table]
+  meta.take(n_units * sizeof(UnitSummary));
+  const size_t table_at = meta.take(table.size() * 4);
+  if (!grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta.at))
     return false;
   const float *d_table = fixed ? nullptr : (const float *)(ctx->d_enc_meta + table_at);
   if ((!fixed && hipMemcpyAsync((void *)d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
@@ -219,40 +221,39 @@ void chain_prepare(ChainJob *job)
   job->slot_max = slot_max;
 }
 
-namespace
-{
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-} // namespace
-
 ChainDown chain_down_layout(const ChainJob &job)
 {
   const size_t nb = job.spans.size();
+  Carve at;
   ChainDown d;
-  d.image_bytes = 0;
-  d.image_off = up256(nb * 8);
-  d.result = d.image_off + up256(nb * 8);
-  d.bytes = d.result + 256;
+  d.image_bytes = at.take(nb * 8);
+  d.image_off = at.take(nb * 8);
+  d.result = at.take(256);
+  d.bytes = at.at;
   return d;
 }
 
 ChainUp chain_up_layout(const ChainJob &job)
 {
   const size_t nb = job.spans.size();
+  Carve at;
   ChainUp u;
-  u.blocks = 0;
-  u.counts = up256(nb * sizeof(ChainBlock));
-  u.list = u.counts + up256(nb * 512);
-  u.bytes = u.list + up256(job.ck_list.size() * 4 + 4);
+  u.blocks = at.take(nb * sizeof(ChainBlock));
+  u.counts = at.take(nb * 512);
+  u.list = at.take(job.ck_list.size() * 4 + 4);
+  u.bytes = at.close();
   return u;
 }
 
 ChainCk chain_ck_layout(const ChainJob &job)
 {
   const size_t ck_slots = job.n_ck ? job.n_ck : 1;
+  Carve words; // (32-bit words, packed: the states and positions as ck_region lays them, then the block states)
   ChainCk c;
-  c.ck_pos = ck_slots * job.S;
-  c.block_states = c.ck_pos + ck_slots;
-  c.bytes = c.block_states * 4 + (job.want_plan ? job.spans.size() * (size_t)job.S * 4 : 0);
+  words.take(ck_slots * job.S, 1);
+  c.ck_pos = words.take(ck_slots, 1);
+  c.block_states = words.take(job.want_plan ? job.spans.size() * (size_t)job.S : 0, 1);
+  c.bytes = words.at * 4;
   return c;
 }
 
@@ -332,6 +333,26 @@ bool encoder_ready(hsrans_ctx *ctx)
   if (!ctx->encoder_prepared && prepare_encode_kernels() == hipSuccess)
     ctx->encoder_prepared = true;
   return ctx->encoder_prepared;
+}
+
+bool encoder_buffers(hsrans_ctx *ctx, size_t scratch, size_t meta, size_t ck)
+{
+  return grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, scratch) && grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta) &&
+         grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck);
+}
+
+void ck_region(EncParams *ep, uint8_t *at, size_t ck_slots, uint32_t S)
+{
+  ep->ck_states = (uint32_t *)at;
+  ep->ck_pos = ep->ck_states + ck_slots * S;
+}
+
+bool stream_settle(hipStream_t s, bool queued)
+{
+  if (hipStreamSynchronize(s) == hipSuccess && queued)
+    return true;
+  (void)hipGetLastError();
+  return false;
 }
 
 EncParams EncShape::params(const void *d_in, void *d_out, size_t out_capacity) const
@@ -495,6 +516,7 @@ extern "C"
 {
 
 size_t hsrans_block_choices(int container, int states, uint32_t bits, const void *in, size_t length, uint32_t block_size, hsrans_block_choice *out, size_t capacity)
+try
 {
   if ((container != HSRANS_BLOCK && container != HSRANS_MT) || !valid_codec(container, states, bits) || in == nullptr || length == 0 || block_size % 64 != 0)
     return 0;
@@ -509,9 +531,14 @@ size_t hsrans_block_choices(int container, int states, uint32_t bits, const void
     return 0;
   return copy_choices(spans, out, capacity);
 }
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return 0;
+}
 
 size_t hsrans_block_choices_device(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, uint32_t block_size,
                                    hsrans_block_choice *out, size_t capacity, void *hip_stream)
+try
 {
   if (ctx == nullptr || (container != HSRANS_BLOCK && container != HSRANS_MT) || !valid_codec(container, states, bits) || d_in == nullptr || length == 0 ||
       block_size % 64 != 0 || ((uintptr_t)d_in & 15) != 0 || length > 0x7FFF0000ull)
@@ -532,10 +559,15 @@ size_t hsrans_block_choices_device(hsrans_ctx *ctx, int container, int states, u
     return 0;
   return copy_choices(job.spans, out, capacity);
 }
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return 0;
+}
 
 size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity, const hsrans_hist *hist,
                                 uint32_t index_interval, const uint64_t *index_groups, size_t n_index_groups, uint8_t *plan_out, size_t plan_capacity,
                                 size_t *plan_size, void *hip_stream, hsrans_dplan **out_dplan)
+try
 {
   // SURVEY.md §8(f) row 2, the raw half: rANS32x64_16w.cpp:34-166 carries every coder state from the file's last symbol to its
   // first, so the format has work for exactly ONE wavefront (lane j = state j).  What the GPU adds is that input and stream never
@@ -559,8 +591,7 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
   if (!encoder_ready(ctx))
     return 0;
   const size_t meta_bytes = (2 + kEncResultWords + 4) * 8 + 256 * 4 + 256 * 2 + n_ck * 4 + 64;
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, ep.slot_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta_bytes) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, sh.ck_slots * ((size_t)sh.S * 4 + 4)))
+  if (!encoder_buffers(ctx, ep.slot_bytes, meta_bytes, ck_region_bytes(sh.ck_slots, sh.S)))
     return 0;
   ep.scratch = ctx->d_enc_scratch;
   ep.image_bytes = (uint64_t *)ctx->d_enc_meta;
@@ -574,8 +605,7 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
   ep.given_counts = hist ? d_given : nullptr;
   ep.ck_groups = groups32.empty() ? nullptr : d_groups;
   ep.n_ck_groups = (uint32_t)groups32.size();
-  ep.ck_states = (uint32_t *)ctx->d_enc_ck;
-  ep.ck_pos = ep.ck_states + sh.ck_slots * sh.S;
+  ck_region(&ep, ctx->d_enc_ck, sh.ck_slots, sh.S);
   hipStream_t s = (hipStream_t)hip_stream;
   uint64_t result[kEncResultWords] = {};
   bool ok = true;
@@ -584,18 +614,15 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
   if (ok && ep.ck_groups)
     ok = hipMemcpyAsync(d_groups, groups32.data(), n_ck * 4, hipMemcpyHostToDevice, s) == hipSuccess;
   ok = ok && launch_encode_raw(ep, d_counts, s) == hipSuccess && hipMemcpyAsync(result, ep.result, sizeof(result), hipMemcpyDeviceToHost, s) == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (groups32 / *hist may be read until here)
-  {
-    (void)hipGetLastError();
+  if (!stream_settle(s, ok)) // (groups32 / *hist may be read until here)
     return 0;
-  }
   if (ctx->tuning.debug_stamps)
   {
     uint64_t st[4] = {};
     if (hipMemcpy(st, ep.stamps, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess)
       fprintf(stderr, "[hsrans raw encode stamps] us: counts+normalise+table %.1f  rANS pass %.1f\n", (double)(st[2] - st[0]) / 100.0, (double)(st[3] - st[2]) / 100.0);
   }
-  if (result[1] != 1 || result[2] != 0)
+  if (!enc_result_ok(result, true))
     return 0;
   const size_t total = (size_t)result[0];
   if (!sh.want_plan)
@@ -611,9 +638,14 @@ size_t hsrans_encode_device_raw(hsrans_ctx *ctx, int states, uint32_t bits, cons
     return 0;
   return raw_plan(ctx, sh, total, index_groups, header.data(), ck_states.data(), ck_pos.data(), plan_out, plan_capacity, plan_size, out_dplan) ? total : 0;
 }
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return 0;
+}
 
 size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity,
                             uint32_t block_size, uint32_t index_interval, void *hip_stream, hsrans_dplan **out_dplan)
+try
 {
   if (container == HSRANS_RAW) // one wavefront (the format's one dependent chain); block_size has no meaning
     return hsrans_encode_device_raw(ctx, states, bits, d_in, length, d_out, out_capacity, nullptr, index_interval, nullptr, 0, nullptr, 0, nullptr, hip_stream, out_dplan);
@@ -629,8 +661,7 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
     return 0;
   const bool stamps = ctx->tuning.debug_stamps;
   const size_t nb = ep.n_blocks, arrays = mt_block_arrays_bytes(ep.n_blocks);
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, nb * ep.slot_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, arrays + (stamps ? nb * 4 * 8 : 0)) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, sh.ck_slots * ((size_t)sh.S * 4 + 4)))
+  if (!encoder_buffers(ctx, nb * ep.slot_bytes, arrays + (stamps ? nb * 4 * 8 : 0), ck_region_bytes(sh.ck_slots, sh.S)))
     return 0;
   ep.scratch = ctx->d_enc_scratch;
   mt_block_arrays(&ep, ctx->d_enc_meta);
@@ -645,8 +676,7 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
   if (hipHostGetDevicePointer(&d_result, ctx->h_enc_result, 0) != hipSuccess)
     return 0;
   ep.result = (uint64_t *)d_result;
-  ep.ck_states = (uint32_t *)ctx->d_enc_ck;
-  ep.ck_pos = ep.ck_states + sh.ck_slots * sh.S;
+  ck_region(&ep, ctx->d_enc_ck, sh.ck_slots, sh.S);
   hipStream_t s = (hipStream_t)hip_stream;
   uint64_t result[kEncResultWords] = {};
   if (launch_encode(ep, ctx->geom.num_cus, s) != hipSuccess)
@@ -681,7 +711,7 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
       }
     }
   }
-  if (result[1] != 1)
+  if (!enc_result_ok(result, false)) // (word 2 is the chain count)
     return 0;
   const size_t total = (size_t)result[0];
   if (out_dplan == nullptr)
@@ -701,10 +731,15 @@ size_t hsrans_encode_device(hsrans_ctx *ctx, int container, int states, uint32_t
   *out_dplan = d;
   return total;
 }
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return 0;
+}
 
 
 size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint32_t bits, const void *d_in, size_t length, void *d_out, size_t out_capacity,
                                const hsrans_hist *hist, hsrans_encode_opts *opts, void *hip_stream, hsrans_dplan **out_dplan)
+try
 {
   // The device twin of hsrans_encode_ex: same arguments accepted and refused (hsrans_host.cpp encode()), same stream, same plan.
   //   raw                               -> hsrans_encode_device_raw (one wavefront)
@@ -764,8 +799,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
 
   // ---- c. the chain: one wavefront, blocks back to front; then the images into place ----
   const ChainDown down = chain_down_layout(job);
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, job.slot_total) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, down.bytes + chain_up_bytes(job)) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, chain_ck_bytes(job)))
+  if (!encoder_buffers(ctx, job.slot_total, down.bytes + chain_up_bytes(job), chain_ck_bytes(job)))
     return 0;
   const EncParams ep = chain_params(job, ctx->d_enc_scratch, ctx->d_enc_meta, ctx->d_enc_meta + down.bytes, ctx->d_enc_ck);
   const std::vector<ChainBlock> &cb = job.cb;
@@ -777,11 +811,8 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
             (ck_list.empty() || hipMemcpyAsync((void *)ep.ck_groups, ck_list.data(), ck_list.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess) &&
             launch_encode_chain(ep, s) == hipSuccess &&
             hipMemcpyAsync(result, ep.result, sizeof(result), hipMemcpyDeviceToHost, s) == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (cb / counts / ck_list may be read until here)
-  {
-    (void)hipGetLastError();
+  if (!stream_settle(s, ok)) // (cb / counts / ck_list may be read until here)
     return 0;
-  }
   const auto t3 = std::chrono::steady_clock::now();
   if (stamps)
     fprintf(stderr, "[hsrans chain encode] blocks %zu  units %zu  summaries %.1f us  walk %.1f us  chain+gather %.1f us\n", nb, n_units,
@@ -789,7 +820,7 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
             std::chrono::duration<double, std::micro>(t3 - t2).count());
   // result[1] == 0 cannot happen (out_capacity >= hsrans_capacity was checked) and result[2] != 0 only if the host's filtering of the
   // listed checkpoints and the kernel disagree: internal consistency failures, not refusals — d_out may have been written by then
-  if (result[1] != 1 || result[2] != 0)
+  if (!enc_result_ok(result, true))
     return 0;
   const size_t total = (size_t)result[0];
   if (!want_plan)
@@ -811,6 +842,10 @@ size_t hsrans_encode_device_ex(hsrans_ctx *ctx, int container, int states, uint3
   if (out_dplan != nullptr && hsrans_dplan_create(ctx, opts->plan_out, psize, out_dplan) != HSRANS_OK)
     return 0;
   return total;
+}
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return 0;
 }
 
 

@@ -8,9 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
-#include <iterator>
 #include <mutex>
-#include <utility>
 #include <vector>
 
 #include "../../include/hsrans_hip.h"
@@ -52,30 +50,21 @@ bool check_member(const hsrans_encode_member &m, bool want_dplan, Member *out)
   return true;
 }
 
-// no two outputs overlap, no output overlaps an input
-bool ranges_disjoint(const hsrans_encode_member *members, uint32_t count)
+// a member that ends without a stream: no length and no plan (one already made for it is destroyed)
+void fail_member(hsrans_encode_member *members, hsrans_dplan **out_dplans, uint32_t k)
 {
-  std::vector<std::pair<uintptr_t, uintptr_t>> outs(count);
-  for (uint32_t k = 0; k < count; k++)
-    outs[k] = {(uintptr_t)members[k].d_out, (uintptr_t)members[k].d_out + members[k].out_capacity};
-  std::sort(outs.begin(), outs.end());
-  for (uint32_t k = 1; k < count; k++)
-    if (outs[k].first < outs[k - 1].second)
-      return false;
-  for (uint32_t k = 0; k < count; k++) // the outputs are disjoint and sorted, so their ends are too: the last one starting below the input's end decides
+  members[k].stream_length = 0;
+  if (out_dplans != nullptr && out_dplans[k] != nullptr)
   {
-    const uintptr_t lo = (uintptr_t)members[k].d_in, hi = lo + members[k].length;
-    auto it = std::lower_bound(outs.begin(), outs.end(), std::make_pair(hi, (uintptr_t)0));
-    if (it != outs.begin() && std::prev(it)->second > lo)
-      return false;
+    hsrans_dplan_destroy(out_dplans[k]);
+    out_dplans[k] = nullptr;
   }
-  return true;
 }
-
 } // namespace
 
 extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member *members, uint32_t count, void *hip_stream, hsrans_dplan **out_dplans,
                                           hsrans_encode_batch_stats *stats)
+try
 {
   if (stats)
     *stats = hsrans_encode_batch_stats{};
@@ -83,9 +72,9 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
     return HSRANS_E_ARG;
   for (uint32_t k = 0; k < count; k++)
   {
-    members[k].stream_length = 0;
     if (out_dplans)
-      out_dplans[k] = nullptr;
+      out_dplans[k] = nullptr; // (the caller's array may hold anything: nothing to destroy yet)
+    fail_member(members, out_dplans, k);
   }
   if (ctx == nullptr)
     return HSRANS_E_ARG;
@@ -95,8 +84,17 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   for (uint32_t k = 0; k < count; k++)
     if (!check_member(members[k], out_dplans != nullptr, &mm[k]))
       return HSRANS_E_ARG;
-  if (!ranges_disjoint(members, count))
-    return HSRANS_E_ARG;
+  {
+    std::vector<Span> spans; // (raw_shape / mt_shape refuse an empty input and a capacity below hsrans_capacity: no span here is empty)
+    spans.reserve(2 * (size_t)count);
+    for (uint32_t k = 0; k < count; k++)
+    {
+      spans.push_back({(uintptr_t)members[k].d_out, (uintptr_t)members[k].d_out + members[k].out_capacity, true});
+      spans.push_back({(uintptr_t)members[k].d_in, (uintptr_t)members[k].d_in + members[k].length, false});
+    }
+    if (!spans_disjoint(spans))
+      return HSRANS_E_ARG;
+  }
   size_t n_tasks[2] = {0, 0}; // raw histogram / copy workgroups, mt_ blocks (workgroups of 256 threads in one grid: fewer than 2^24)
   for (uint32_t k = 0; k < count; k++)
     n_tasks[mm[k].raw ? 0 : 1] += mm[k].raw ? mm[k].parts : mm[k].n_blocks;
@@ -141,55 +139,48 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   // ---- carving: the context's scratch (slots), checkpoint (raw members', their headers, then mt_ members') and meta buffers ----
   // meta: [upload: params | raw list | raw parts | mt_ tasks | scan list | header pointers | hists | group lists]
   //       [zeroed: result words (8 per member) | raw counts (256 per raw member)] [per member: image sizes / offsets, chain counts, block counts]
-  size_t scratch_bytes = 0, ck_bytes = 0, meta = 0;
-  auto take = [](size_t *at, size_t bytes, size_t align) {
-    *at = (*at + align - 1) / align * align;
-    const size_t here = *at;
-    *at += bytes;
-    return here;
-  };
+  Carve scratch, ck, meta;
   for (uint32_t k = 0; k < count; k++)
   {
-    mm[k].scratch_at = take(&scratch_bytes, (size_t)mm[k].n_blocks * mm[k].slot_bytes, 512);
+    mm[k].scratch_at = scratch.take((size_t)mm[k].n_blocks * mm[k].slot_bytes, 512);
     if (mm[k].raw)
-      mm[k].ck_at = take(&ck_bytes, mm[k].ck_slots * ((size_t)mm[k].S * 4 + 4), 256);
+      mm[k].ck_at = ck.take(ck_region_bytes(mm[k].ck_slots, mm[k].S), 256);
   }
   bool any_raw_plan = false;
   for (uint32_t k = 0; k < count; k++)
     if (mm[k].raw && mm[k].want_plan)
     {
-      mm[k].header_at = take(&ck_bytes, 16 + 512 + 4 * (size_t)mm[k].S, 16);
+      mm[k].header_at = ck.take(16 + 512 + 4 * (size_t)mm[k].S, 16);
       any_raw_plan = true;
     }
-  const size_t raw_down_bytes = ck_bytes; // the raw members' checkpoints and headers: one copy to the host
+  const size_t raw_down_bytes = ck.at; // the raw members' checkpoints and headers: one copy to the host
   for (uint32_t k = 0; k < count; k++)
     if (!mm[k].raw)
-      mm[k].ck_at = take(&ck_bytes, mm[k].ck_slots * ((size_t)mm[k].S * 4 + 4), 256);
+      mm[k].ck_at = ck.take(ck_region_bytes(mm[k].ck_slots, mm[k].S), 256);
 
-  const size_t off_params = take(&meta, (size_t)count * sizeof(EncParams), 256);
-  const size_t off_raw_list = take(&meta, raw_list.size() * 4, 256);
-  const size_t off_raw_parts = take(&meta, raw_parts.size() * sizeof(EncTask), 256);
-  const size_t off_mt_tasks = take(&meta, mt_tasks.size() * sizeof(EncTask), 256);
-  const size_t off_scan = take(&meta, scan_list.size() * 4, 256);
-  const size_t off_headers = take(&meta, (size_t)count * sizeof(uint8_t *), 256);
+  const size_t off_params = meta.take((size_t)count * sizeof(EncParams), 256);
+  const size_t off_raw_list = meta.take(raw_list.size() * 4, 256);
+  const size_t off_raw_parts = meta.take(raw_parts.size() * sizeof(EncTask), 256);
+  const size_t off_mt_tasks = meta.take(mt_tasks.size() * sizeof(EncTask), 256);
+  const size_t off_scan = meta.take(scan_list.size() * 4, 256);
+  const size_t off_headers = meta.take((size_t)count * sizeof(uint8_t *), 256);
   for (uint32_t k = 0; k < count; k++)
     if (mm[k].raw && members[k].hist != nullptr)
-      mm[k].given_at = take(&meta, 512, 16);
+      mm[k].given_at = meta.take(512, 16);
   for (uint32_t k = 0; k < count; k++)
     if (mm[k].raw && mm[k].want_plan && mm[k].listed && mm[k].n_ck)
-      mm[k].groups_at = take(&meta, mm[k].n_ck * 4, 16);
-  const size_t upload_bytes = meta;
-  const size_t off_results = take(&meta, (size_t)count * kEncResultWords * 8, 256);
-  const size_t off_raw_counts = take(&meta, (size_t)n_raw * 1024, 16);
-  const size_t zero_bytes = meta - off_results;
+      mm[k].groups_at = meta.take(mm[k].n_ck * 4, 16);
+  const size_t upload_bytes = meta.at;
+  const size_t off_results = meta.take((size_t)count * kEncResultWords * 8, 256);
+  const size_t off_raw_counts = meta.take((size_t)n_raw * 1024, 16);
+  const size_t zero_bytes = meta.at - off_results;
   for (uint32_t k = 0; k < count; k++) // (raw: image_bytes, image_off)
-    mm[k].meta_at = take(&meta, mm[k].raw ? 16 : mt_block_arrays_bytes(mm[k].n_blocks), 256);
+    mm[k].meta_at = meta.take(mm[k].raw ? 16 : mt_block_arrays_bytes(mm[k].n_blocks), 256);
 
   std::lock_guard<std::mutex> guard(ctx->lock);
   if (!encoder_ready(ctx))
     return HSRANS_E_HIP;
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, scratch_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, std::max<size_t>(ck_bytes, 256)))
+  if (!encoder_buffers(ctx, scratch.at, meta.at, std::max<size_t>(ck.at, 256)))
     return HSRANS_E_HIP;
   uint8_t *const d_meta = ctx->d_enc_meta;
 
@@ -208,8 +199,7 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
     EncParams ep = m.params(a.d_in, a.d_out, a.out_capacity);
     ep.scratch = ctx->d_enc_scratch + m.scratch_at;
     ep.result = (uint64_t *)(d_meta + off_results) + (size_t)k * kEncResultWords;
-    ep.ck_states = (uint32_t *)(ctx->d_enc_ck + m.ck_at);
-    ep.ck_pos = ep.ck_states + m.ck_slots * m.S;
+    ck_region(&ep, ctx->d_enc_ck + m.ck_at, m.ck_slots, m.S);
     uint8_t *own = d_meta + m.meta_at;
     headers[k] = nullptr;
     if (m.raw)
@@ -266,11 +256,8 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
             launch_encode_batch(bt, ctx->geom.num_cus, s, &launches) == hipSuccess &&
             hipMemcpyAsync(results.data(), d_meta + off_results, results.size() * 8, hipMemcpyDeviceToHost, s) == hipSuccess &&
             (!any_raw_plan || hipMemcpyAsync(raw_down.data(), ctx->d_enc_ck, raw_down_bytes, hipMemcpyDeviceToHost, s) == hipSuccess);
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (upload may be read until here)
-  {
-    (void)hipGetLastError();
+  if (!stream_settle(s, ok)) // (upload may be read until here)
     return HSRANS_E_HIP;
-  }
   if (stats)
     stats->launches = launches;
 
@@ -280,7 +267,7 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   for (uint32_t k = 0; k < count; k++)
   {
     const uint64_t *r = &results[(size_t)k * kEncResultWords];
-    fine[k] = r[1] == 1 && (!mm[k].raw || r[2] == 0);
+    fine[k] = enc_result_ok(r, mm[k].raw); // (an mt_ member's word 2 is its chain count)
     if (fine[k])
       members[k].stream_length = (size_t)r[0];
     else
@@ -289,25 +276,20 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
   if (out_dplans == nullptr)
     return rc;
 
-  auto fail_member = [&](uint32_t k) {
-    members[k].stream_length = 0;
-    if (out_dplans[k] != nullptr)
-      hsrans_dplan_destroy(out_dplans[k]);
-    out_dplans[k] = nullptr;
-    if (rc == HSRANS_OK)
-      rc = HSRANS_E_HIP;
-  };
-
   // ---- raw plans: assembled on the host from the headers and checkpoints that came down, as the single call does (raw_plan) ----
   for (uint32_t k : raw_list)
   {
     const Member &m = mm[k];
     if (!fine[k] || !m.want_plan)
       continue;
-    const uint32_t *ck_states = (const uint32_t *)(raw_down.data() + m.ck_at);
-    if (raw_plan(ctx, m, members[k].stream_length, members[k].index_groups, raw_down.data() + m.header_at, ck_states, ck_states + m.ck_slots * m.S, nullptr, 0,
-                 nullptr, &out_dplans[k]) == 0)
-      fail_member(k);
+    EncParams down{}; // (the member's checkpoint region in the host's copy)
+    ck_region(&down, raw_down.data() + m.ck_at, m.ck_slots, m.S);
+    if (raw_plan(ctx, m, members[k].stream_length, members[k].index_groups, raw_down.data() + m.header_at, down.ck_states, down.ck_pos, nullptr, 0, nullptr,
+                 &out_dplans[k]) == 0)
+    {
+      fail_member(members, out_dplans, k);
+      rc = rc == HSRANS_OK ? HSRANS_E_HIP : rc;
+    }
   }
 
   // ---- mt_ plans: written on the device by one K_plan launch over every block of the members, once their chain counts are known ----
@@ -321,18 +303,20 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
       continue;
     out_dplans[k] = mt_plan_begin(ctx, &params[k], &results[(size_t)k * kEncResultWords], &heads[k], s);
     if (out_dplans[k] == nullptr)
-      fail_member(k);
+    {
+      fail_member(members, out_dplans, k);
+      rc = rc == HSRANS_OK ? HSRANS_E_HIP : rc;
+    }
     any_plan = any_plan || out_dplans[k] != nullptr;
   }
   ok = !any_plan || (hipMemcpyAsync(d_meta + off_params, params, (size_t)count * sizeof(EncParams), hipMemcpyHostToDevice, s) == hipSuccess &&
                      launch_encode_plan_batch(bt.params, bt.mt_blocks, (uint32_t)mt_tasks.size(), s, &launches) == hipSuccess);
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (heads / params may be read until here)
+  if (!stream_settle(s, ok)) // (heads / params may be read until here)
   {
-    (void)hipGetLastError();
     for (uint32_t k = 0; k < count; k++)
       if (!mm[k].raw && out_dplans[k] != nullptr)
-        fail_member(k);
-    return rc == HSRANS_OK || rc == HSRANS_E_DEVICE ? HSRANS_E_HIP : rc;
+        fail_member(members, out_dplans, k);
+    return HSRANS_E_HIP; // (whatever rc held: HSRANS_OK, or a member's HSRANS_E_DEVICE / HSRANS_E_HIP)
   }
   if (stats)
     stats->launches = launches;
@@ -340,4 +324,10 @@ extern "C" int hsrans_encode_device_batch(hsrans_ctx *ctx, hsrans_encode_member 
     if (!mm[k].raw && out_dplans[k] != nullptr)
       mt_plan_adopt(out_dplans[k], params[k], heads[k], s);
   return rc;
+}
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI; thrown only after the caller's arrays were reset)
+{
+  for (uint32_t k = 0; k < count; k++)
+    fail_member(members, out_dplans, k);
+  return HSRANS_E_HIP;
 }

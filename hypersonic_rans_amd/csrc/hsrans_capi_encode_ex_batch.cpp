@@ -10,9 +10,7 @@
 
 #include <algorithm>
 #include <chrono>
-#include <iterator>
 #include <mutex>
-#include <utility>
 #include <vector>
 
 #include "../../include/hsrans_hip.h"
@@ -29,49 +27,25 @@ namespace
 constexpr uint32_t kMaxMembers = 65536;
 constexpr size_t kMaxTasks = (size_t)1 << 24; // summary units of all members, and gather workgroups
 
-typedef std::pair<uintptr_t, uintptr_t> Range;
-
-// sorted by start: no two overlap
-bool disjoint(std::vector<Range> *r)
+// a member that ends without a stream: its code, no length, no plan size and no device plan (one already made for it is destroyed)
+void member_fail(hsrans_encode_ex_member *members, hsrans_dplan **out_dplans, uint32_t k, int rc)
 {
-  std::sort(r->begin(), r->end());
-  for (size_t k = 1; k < r->size(); k++)
-    if ((*r)[k].first < (*r)[k - 1].second)
-      return false;
-  return true;
+  members[k].stream_length = 0;
+  members[k].rc = rc;
+  if (members[k].opts)
+    members[k].opts->plan_size = 0;
+  if (out_dplans != nullptr && out_dplans[k] != nullptr)
+  {
+    hsrans_dplan_destroy(out_dplans[k]);
+    out_dplans[k] = nullptr;
+  }
 }
 
-// the batch's own rules: no two outputs overlap, no output overlaps an input, no two members share an opts object or a plan_out range
-bool ranges_disjoint(const hsrans_encode_ex_member *members, uint32_t count, const std::vector<ChainJob> &jobs)
+int all_fail(hsrans_encode_ex_member *members, uint32_t count, hsrans_dplan **out_dplans, int rc)
 {
-  std::vector<Range> outs(count), plans, opts;
   for (uint32_t k = 0; k < count; k++)
-  {
-    const hsrans_encode_ex_member &m = members[k];
-    outs[k] = {(uintptr_t)m.d_out, (uintptr_t)m.d_out + m.out_capacity};
-    if (m.opts != nullptr)
-      opts.push_back({(uintptr_t)m.opts, (uintptr_t)m.opts + sizeof(hsrans_encode_opts)});
-    if (jobs[k].want_plan)
-      plans.push_back({(uintptr_t)m.opts->plan_out, (uintptr_t)m.opts->plan_out + std::max<size_t>(m.opts->plan_capacity, 1)});
-  }
-  if (!disjoint(&outs) || !disjoint(&opts) || !disjoint(&plans))
-    return false;
-  for (uint32_t k = 0; k < count; k++) // the outputs are disjoint and sorted, so their ends are too: the last one starting below the input's end decides
-  {
-    const uintptr_t lo = (uintptr_t)members[k].d_in, hi = lo + members[k].length;
-    auto it = std::lower_bound(outs.begin(), outs.end(), std::make_pair(hi, (uintptr_t)0));
-    if (it != outs.begin() && std::prev(it)->second > lo)
-      return false;
-  }
-  return true;
-}
-
-size_t take(size_t *at, size_t bytes, size_t align)
-{
-  *at = (*at + align - 1) / align * align;
-  const size_t here = *at;
-  *at += bytes;
-  return here;
+    member_fail(members, out_dplans, k, rc);
+  return rc;
 }
 
 double us_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
@@ -82,32 +56,17 @@ double us_between(std::chrono::steady_clock::time_point a, std::chrono::steady_c
 
 extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_member *members, uint32_t count, void *hip_stream, hsrans_dplan **out_dplans,
                                              hsrans_encode_ex_batch_stats *stats)
+try
 {
   if (stats)
     *stats = hsrans_encode_ex_batch_stats{};
   if (members == nullptr || count == 0 || count > kMaxMembers)
     return HSRANS_E_ARG;
-  auto all_fail = [&](int rc) {
-    for (uint32_t k = 0; k < count; k++)
-    {
-      members[k].stream_length = 0;
-      members[k].rc = rc;
-      if (members[k].opts)
-        members[k].opts->plan_size = 0;
-      if (out_dplans)
-      {
-        if (out_dplans[k] != nullptr)
-          hsrans_dplan_destroy(out_dplans[k]);
-        out_dplans[k] = nullptr;
-      }
-    }
-    return rc;
-  };
   if (out_dplans)
     for (uint32_t k = 0; k < count; k++)
-      out_dplans[k] = nullptr;
+      out_dplans[k] = nullptr; // (the caller's array may hold anything: nothing to destroy yet)
   if (ctx == nullptr)
-    return all_fail(HSRANS_E_ARG);
+    return all_fail(members, count, out_dplans, HSRANS_E_ARG);
 
   // ---- every member checked before anything is launched: the single call's rules, then the batch's own ----
   std::vector<ChainJob> jobs(count);
@@ -117,11 +76,29 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
     const hsrans_encode_ex_member &m = members[k];
     if ((uintptr_t)m.d_in + m.length < (uintptr_t)m.d_in || (uintptr_t)m.d_out + m.out_capacity < (uintptr_t)m.d_out ||
         ex_route(m.container, m.states, m.bits, m.d_in, m.length, m.d_out, m.out_capacity, m.opts, &jobs[k]) != kExChain || !chain_units(&jobs[k]))
-      return all_fail(HSRANS_E_ARG);
+      return all_fail(members, count, out_dplans, HSRANS_E_ARG);
     n_unit_tasks += jobs[k].n_units;
   }
-  if (n_unit_tasks >= kMaxTasks || !ranges_disjoint(members, count, jobs))
-    return all_fail(HSRANS_E_ARG);
+  if (n_unit_tasks >= kMaxTasks)
+    return all_fail(members, count, out_dplans, HSRANS_E_ARG);
+  {
+    // the batch's own rules: outputs and inputs by the overlap rule, and no two members share an opts object or a plan_out range
+    // (ex_route refuses an empty input and a capacity below hsrans_capacity: no span here is empty)
+    std::vector<Span> io, opts, plans;
+    io.reserve(2 * (size_t)count);
+    for (uint32_t k = 0; k < count; k++)
+    {
+      const hsrans_encode_ex_member &m = members[k];
+      io.push_back({(uintptr_t)m.d_out, (uintptr_t)m.d_out + m.out_capacity, true});
+      io.push_back({(uintptr_t)m.d_in, (uintptr_t)m.d_in + m.length, false});
+      if (m.opts != nullptr)
+        opts.push_back({(uintptr_t)m.opts, (uintptr_t)m.opts + sizeof(hsrans_encode_opts), true});
+      if (jobs[k].want_plan)
+        plans.push_back({(uintptr_t)m.opts->plan_out, (uintptr_t)m.opts->plan_out + std::max<size_t>(m.opts->plan_capacity, 1), true});
+    }
+    if (!spans_disjoint(io) || !spans_disjoint(opts) || !spans_disjoint(plans))
+      return all_fail(members, count, out_dplans, HSRANS_E_ARG);
+  }
 
   const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = (hipStream_t)hip_stream;
@@ -136,11 +113,12 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
 
   std::lock_guard<std::mutex> guard(ctx->lock);
   if (!encoder_ready(ctx))
-    return all_fail(HSRANS_E_HIP);
+    return all_fail(members, count, out_dplans, HSRANS_E_HIP);
 
   // ---- a. the unit summaries of all members: one launch over the (member, unit) tasks, one over the adaptive members' whole units ----
   // meta: [upload: params | unit tasks | cost tasks | summary pointers | table pointers | one logarithm table per width present] [summaries]
-  size_t meta = 0, table_at[16] = {};
+  Carve meta;
+  size_t table_at[16] = {};
   std::vector<EncTask> unit_tasks, cost_tasks;
   unit_tasks.reserve(n_unit_tasks);
   for (uint32_t k = 0; k < count; k++)
@@ -150,25 +128,25 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
       if (!jobs[k].fixed && (u + 1) * jobs[k].unit <= jobs[k].length) // (a short last unit is never a candidate: its cost stays 0)
         cost_tasks.push_back(EncTask{k, (uint32_t)u, 0});
     }
-  const size_t off_params = take(&meta, (size_t)count * sizeof(EncParams), 256);
-  const size_t off_unit_tasks = take(&meta, unit_tasks.size() * sizeof(EncTask), 256);
-  const size_t off_cost_tasks = take(&meta, cost_tasks.size() * sizeof(EncTask), 256);
-  const size_t off_sum_ptrs = take(&meta, (size_t)count * sizeof(void *), 256);
-  const size_t off_table_ptrs = take(&meta, (size_t)count * sizeof(void *), 256);
+  const size_t off_params = meta.take((size_t)count * sizeof(EncParams), 256);
+  const size_t off_unit_tasks = meta.take(unit_tasks.size() * sizeof(EncTask), 256);
+  const size_t off_cost_tasks = meta.take(cost_tasks.size() * sizeof(EncTask), 256);
+  const size_t off_sum_ptrs = meta.take((size_t)count * sizeof(void *), 256);
+  const size_t off_table_ptrs = meta.take((size_t)count * sizeof(void *), 256);
   bool width_present[16] = {};
   for (uint32_t k = 0; k < count; k++)
     width_present[jobs[k].bits] = width_present[jobs[k].bits] || !jobs[k].fixed;
   for (uint32_t bits = 0; bits < 16; bits++)
     if (width_present[bits])
-      table_at[bits] = take(&meta, (((size_t)1 << bits) + 1) * 4, 256);
-  const size_t upload1_bytes = meta;
-  const size_t off_summaries = take(&meta, 0, 256);
+      table_at[bits] = meta.take((((size_t)1 << bits) + 1) * 4, 256);
+  const size_t upload1_bytes = meta.at;
+  const size_t off_summaries = meta.close();
   std::vector<size_t> sum_at(count);
   for (uint32_t k = 0; k < count; k++)
-    sum_at[k] = take(&meta, jobs[k].n_units * sizeof(UnitSummary), 256);
-  const size_t summaries_bytes = meta - off_summaries;
-  if (!grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta))
-    return all_fail(HSRANS_E_HIP);
+    sum_at[k] = meta.take(jobs[k].n_units * sizeof(UnitSummary), 256);
+  const size_t summaries_bytes = meta.at - off_summaries;
+  if (!grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta.at))
+    return all_fail(members, count, out_dplans, HSRANS_E_HIP);
   uint8_t *d_meta = ctx->d_enc_meta;
   std::vector<uint8_t> upload(upload1_bytes), summaries(summaries_bytes);
   {
@@ -194,26 +172,12 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
                                         (const EncTask *)(d_meta + off_cost_tasks), (uint32_t)cost_tasks.size(), (uint8_t *const *)(d_meta + off_sum_ptrs),
                                         (const float *const *)(d_meta + off_table_ptrs), s, &launches) == hipSuccess &&
             hipMemcpyAsync(summaries.data(), d_meta + off_summaries, summaries_bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (upload may be read until here)
-  {
-    (void)hipGetLastError();
-    return all_fail(HSRANS_E_HIP);
-  }
+  if (!stream_settle(s, ok)) // (upload may be read until here)
+    return all_fail(members, count, out_dplans, HSRANS_E_HIP);
   const auto t1 = std::chrono::steady_clock::now();
 
   // ---- b. the host walks, member by member, and what the chain needs of their blocks; a plan that does not fit leaves its member out ----
   int rc = HSRANS_OK;
-  auto member_fail = [&](uint32_t k, int why) {
-    members[k].stream_length = 0;
-    members[k].rc = why;
-    if (members[k].opts)
-      members[k].opts->plan_size = 0;
-    if (out_dplans && out_dplans[k] != nullptr)
-    {
-      hsrans_dplan_destroy(out_dplans[k]);
-      out_dplans[k] = nullptr;
-    }
-  };
   std::vector<uint32_t> coded; // the members of the coding launch
   for (uint32_t k = 0; k < count; k++)
   {
@@ -221,13 +185,13 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
     members[k].rc = HSRANS_OK;
     if (!chain_walk(&jobs[k], (const UnitSummary *)(summaries.data() + (sum_at[k] - off_summaries))))
     {
-      member_fail(k, HSRANS_E_DEVICE); // (the summaries are inconsistent: not what the device should have written)
+      member_fail(members, out_dplans, k, HSRANS_E_DEVICE); // (the summaries are inconsistent: not what the device should have written)
       continue;
     }
     chain_prepare(&jobs[k]);
     if (jobs[k].want_plan && chain_plan_bytes(jobs[k]) > members[k].opts->plan_capacity)
     {
-      member_fail(k, HSRANS_E_ARG);
+      member_fail(members, out_dplans, k, HSRANS_E_ARG);
       continue;
     }
     coded.push_back(k);
@@ -249,37 +213,36 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
     const uint32_t parts = chain_gather_parts(jobs[k].slot_max);
     n_blocks_all += jobs[k].cb.size();
     if (gather_tasks.size() + jobs[k].cb.size() * parts >= kMaxTasks)
-      return all_fail(HSRANS_E_ARG); // (nothing coded yet: no output byte changed)
+      return all_fail(members, count, out_dplans, HSRANS_E_ARG); // (nothing coded yet: no output byte changed)
     for (uint32_t b = 0; b < jobs[k].cb.size(); b++)
       for (uint32_t p = 0; p < parts; p++)
         gather_tasks.push_back(EncGatherTask{k, b, p, parts});
   }
-  meta = 0;
-  size_t scratch_bytes = 0, ck_bytes = 0;
-  const size_t off_params2 = take(&meta, (size_t)count * sizeof(EncParams), 256);
-  const size_t off_list = take(&meta, coded.size() * 4, 256);
-  const size_t off_gather = take(&meta, gather_tasks.size() * sizeof(EncGatherTask), 256);
+  meta = Carve{};
+  Carve scratch, ck;
+  const size_t off_params2 = meta.take((size_t)count * sizeof(EncParams), 256);
+  const size_t off_list = meta.take(coded.size() * 4, 256);
+  const size_t off_gather = meta.take(gather_tasks.size() * sizeof(EncGatherTask), 256);
   std::vector<size_t> up_at(count), down_at(count), ck_at(count), scratch_at(count);
   for (uint32_t k : coded)
-    up_at[k] = take(&meta, chain_up_bytes(jobs[k]), 256);
-  const size_t upload2_bytes = meta;
-  const size_t off_down = take(&meta, 0, 256);
+    up_at[k] = meta.take(chain_up_bytes(jobs[k]), 256);
+  const size_t upload2_bytes = meta.at;
+  const size_t off_down = meta.close();
   for (uint32_t k : coded)
-    down_at[k] = take(&meta, chain_down_bytes(jobs[k]), 256);
-  const size_t down_bytes = meta - off_down;
+    down_at[k] = meta.take(chain_down_bytes(jobs[k]), 256);
+  const size_t down_bytes = meta.at - off_down;
   for (uint32_t k : coded)
     if (jobs[k].want_plan)
-      ck_at[k] = take(&ck_bytes, chain_ck_bytes(jobs[k]), 256);
-  const size_t ck_down_bytes = ck_bytes;
+      ck_at[k] = ck.take(chain_ck_bytes(jobs[k]), 256);
+  const size_t ck_down_bytes = ck.at;
   for (uint32_t k : coded)
   {
     if (!jobs[k].want_plan)
-      ck_at[k] = take(&ck_bytes, chain_ck_bytes(jobs[k]), 256);
-    scratch_at[k] = take(&scratch_bytes, jobs[k].slot_total, 512);
+      ck_at[k] = ck.take(chain_ck_bytes(jobs[k]), 256);
+    scratch_at[k] = scratch.take(jobs[k].slot_total, 512);
   }
-  if (!grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, scratch_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, std::max<size_t>(ck_bytes, 256)))
-    return all_fail(HSRANS_E_HIP);
+  if (!encoder_buffers(ctx, scratch.at, meta.at, std::max<size_t>(ck.at, 256)))
+    return all_fail(members, count, out_dplans, HSRANS_E_HIP);
   d_meta = ctx->d_enc_meta;
   upload.assign(upload2_bytes, 0);
   std::vector<uint8_t> down(down_bytes), ck_down(ck_down_bytes);
@@ -301,11 +264,8 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
                                   (const EncGatherTask *)(d_meta + off_gather), (uint32_t)gather_tasks.size(), s, &launches) == hipSuccess &&
         hipMemcpyAsync(down.data(), d_meta + off_down, down_bytes, hipMemcpyDeviceToHost, s) == hipSuccess &&
         (ck_down_bytes == 0 || hipMemcpyAsync(ck_down.data(), ctx->d_enc_ck, ck_down_bytes, hipMemcpyDeviceToHost, s) == hipSuccess));
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) // (upload may be read until here)
-  {
-    (void)hipGetLastError();
-    return all_fail(HSRANS_E_HIP);
-  }
+  if (!stream_settle(s, ok)) // (upload may be read until here)
+    return all_fail(members, count, out_dplans, HSRANS_E_HIP);
   const auto t3 = std::chrono::steady_clock::now();
 
   // ---- d. results and plans: what came down through the single call's plan finish ----
@@ -315,9 +275,9 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
     const uint8_t *dn = down.data() + (down_at[k] - off_down);
     const ChainDown at = chain_down_layout(job);
     const uint64_t *result = (const uint64_t *)(dn + at.result);
-    if (result[1] != 1 || result[2] != 0)
+    if (!enc_result_ok(result, true))
     {
-      member_fail(k, HSRANS_E_DEVICE);
+      member_fail(members, out_dplans, k, HSRANS_E_DEVICE);
       continue;
     }
     const size_t total = (size_t)result[0];
@@ -330,14 +290,14 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
                                              ck_states, ck_states + ck.ck_pos, o->plan_out, o->plan_capacity);
       if (psize == 0)
       {
-        member_fail(k, HSRANS_E_ARG);
+        member_fail(members, out_dplans, k, HSRANS_E_ARG);
         continue;
       }
       o->plan_size = psize;
       if (out_dplans != nullptr && hsrans_dplan_create(ctx, o->plan_out, psize, &out_dplans[k]) != HSRANS_OK)
       {
         out_dplans[k] = nullptr;
-        member_fail(k, HSRANS_E_HIP);
+        member_fail(members, out_dplans, k, HSRANS_E_HIP);
         continue;
       }
     }
@@ -359,4 +319,8 @@ extern "C" int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_m
     fprintf(stderr, "[hsrans chain encode batch] members %u  blocks %zu  units %zu  summaries %.1f us  walks %.1f us  chain+gather %.1f us  plans %.1f us\n", count,
             n_blocks_all, n_unit_tasks, us_between(t0, t1), us_between(t1, t2), us_between(t2, t3), us_between(t3, t4));
   return rc;
+}
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI; thrown only after the caller's out_dplans was reset)
+{
+  return all_fail(members, count, out_dplans, HSRANS_E_HIP);
 }

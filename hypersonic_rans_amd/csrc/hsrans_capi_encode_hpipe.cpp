@@ -37,8 +37,6 @@ bool one_symbol(const uint8_t *in, size_t n)
       return false;
   return true;
 }
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 } // namespace
 
 extern "C"
@@ -105,9 +103,11 @@ try
   const size_t stage_slot = up256(most_blocks * slot_bytes); // (an image never outgrows its slot)
   const size_t head_bytes = 16 + 4 * (size_t)S;
   // per-block records of the whole stream (the plan reads them after the last slice), the one slice's counts, the carry, the heads
-  const size_t off_off = up256((size_t)nb * 8), off_cc = off_off + up256((size_t)nb * 8), off_co = off_cc + up256((size_t)nb * 4),
-               off_counts = off_co + up256((size_t)nb * 4), off_carry = off_counts + up256((size_t)most_blocks * 1024),
-               off_heads = off_carry + 256, meta_bytes = off_heads + (want_plan ? (size_t)nb * head_bytes : 0);
+  Carve at;
+  at.take((size_t)nb * 8); // image_bytes
+  const size_t off_off = at.take((size_t)nb * 8), off_cc = at.take((size_t)nb * 4), off_co = at.take((size_t)nb * 4);
+  const size_t off_counts = at.take((size_t)most_blocks * 1024), off_carry = at.take(256), off_heads = at.take(want_plan ? (size_t)nb * head_bytes : 0);
+  const size_t meta_bytes = at.at;
   const size_t ck_slots = want_plan && max_ck ? (size_t)nb * max_ck : 1;
   constexpr uint32_t kRing = 2; // input and staging slots: slice k reuses slice k-2's once its encode / download is done
 
@@ -126,8 +126,7 @@ try
   hipStream_t up = ctx->pipe_streams[0], enc = ctx->pipe_streams[1], down = ctx->pipe_streams[2];
   const size_t result_words = 8 + (size_t)ns * kEncResultWords; // [0, 4): the carry's start; slice k's result words at 8 + 8 k
   if (!grow(&ctx->d_in, &ctx->d_in_cap, kRing * in_slot) || !grow(&ctx->d_out, &ctx->d_out_cap, kRing * stage_slot) ||
-      !grow(&ctx->d_enc_scratch, &ctx->d_enc_scratch_cap, most_blocks * slot_bytes) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, meta_bytes) ||
-      !grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck_slots * ((size_t)S * 4 + 4)) ||
+      !encoder_buffers(ctx, most_blocks * slot_bytes, meta_bytes, ck_region_bytes(ck_slots, S)) ||
       !grow_pinned_mapped(&ctx->h_pipe_result, &ctx->h_pipe_result_cap, result_words * 8))
     return 0;
   uint64_t *h_res = (uint64_t *)ctx->h_pipe_result;
@@ -140,8 +139,9 @@ try
   uint32_t *g_cc = (uint32_t *)(meta + off_cc), *g_co = (uint32_t *)(meta + off_co);
   EncCarry *d_carry = (EncCarry *)(meta + off_carry);
   uint8_t *g_heads = want_plan ? meta + off_heads : nullptr;
-  uint32_t *g_ck_states = (uint32_t *)ctx->d_enc_ck;
-  uint32_t *g_ck_pos = g_ck_states + ck_slots * S;
+  EncParams whole{}; // (the whole stream's checkpoint region: a slice's blocks begin inside it)
+  ck_region(&whole, ctx->d_enc_ck, ck_slots, S);
+  uint32_t *g_ck_states = whole.ck_states, *g_ck_pos = whole.ck_pos;
   memset(h_res, 0, result_words * 8);
   h_res[0] = 16; // EncCarry{16, 0, 0, 0}: the file header comes first
 

@@ -201,7 +201,7 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
   // The task list goes up with one stream-ordered copy in front of the launch, through a region of the context's task buffers
   std::lock_guard<std::mutex> lk(ctx->lock);
   GatherRegion region;
-  const int rc = gather_region_take(ctx, (n_tasks * sizeof(GatherTask) + 255) & ~(size_t)255, &region);
+  const int rc = gather_region_take(ctx, up256(n_tasks * sizeof(GatherTask)), &region);
   if (rc != HSRANS_OK)
     return rc;
   hsrans_gather_task *h_tasks = (hsrans_gather_task *)region.host;
@@ -225,7 +225,7 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
 size_t hsrans_gather_workspace_bytes(uint32_t max_count)
 {
   // k_gather_cut's header words, then first_task[0 .. max_count]
-  return ((size_t)kGatherWsFirst * 4 + ((size_t)max_count + 1) * 4 + 255) & ~(size_t)255;
+  return up256((size_t)kGatherWsFirst * 4 + ((size_t)max_count + 1) * 4);
 }
 
 int hsrans_decode_device_gather_indirect(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_stream, size_t stream_length, const hsrans_range *d_ranges, const uint32_t *d_count,

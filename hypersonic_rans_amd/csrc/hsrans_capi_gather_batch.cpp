@@ -263,7 +263,8 @@ int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, c
     return HSRANS_E_ARG;
   uint64_t kind_tasks[kGatherKinds] = {}, kind_entries[kGatherKinds] = {}, all_entries = 0;
   GatherShape shapes[kGatherKinds] = {};
-  size_t offset[kGatherKinds] = {}, need = 0;
+  size_t offset[kGatherKinds] = {};
+  Carve lists;
   for (uint32_t m = 0; m < n_members; m++)
     kind_tasks[set->members[m].kind] += tasks[m];
   for (uint32_t k = 0; k < kGatherKinds; k++)
@@ -283,9 +284,9 @@ int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, c
     if (all_entries > 0x7FFFFFFFu)
       return HSRANS_E_ARG;
     shapes[k].grid = (uint32_t)((kind_entries[k] + waves - 1) / waves);
-    offset[k] = need;
-    need += ((size_t)kind_entries[k] * sizeof(GatherSetTask) + 255) & ~(size_t)255;
+    offset[k] = lists.take((size_t)kind_entries[k] * sizeof(GatherSetTask));
   }
+  const size_t need = lists.close();
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;

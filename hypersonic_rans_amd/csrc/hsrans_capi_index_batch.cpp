@@ -37,44 +37,12 @@ struct Member
   uint8_t *scratch = nullptr;
 };
 
-struct Span
-{
-  uintptr_t lo, hi;
-  bool out;
-};
-
-// no two outputs [d_out, d_out + decoded_len) overlap, no output overlaps a stream [d_stream, d_stream + stream_length): one sweep over the sorted spans
-bool spans_disjoint(const hsrans_indexing_member *members, uint32_t count)
-{
-  std::vector<Span> spans;
-  spans.reserve(2 * (size_t)count);
-  for (uint32_t k = 0; k < count; k++)
-  {
-    const hsrans_indexing_member &m = members[k];
-    if (m.dplan->hdr.decoded_len != 0)
-      spans.push_back({(uintptr_t)m.d_out, (uintptr_t)m.d_out + (uintptr_t)m.dplan->hdr.decoded_len, true});
-    if (m.stream_length != 0)
-      spans.push_back({(uintptr_t)m.d_stream, (uintptr_t)m.d_stream + m.stream_length, false});
-  }
-  std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.lo != b.lo ? a.lo < b.lo : a.out > b.out; });
-  uintptr_t out_hi = 0, stream_hi = 0; // the furthest end of the outputs / streams that begin at or before this span
-  for (const Span &sp : spans)
-  {
-    if (sp.lo < out_hi || (sp.out && sp.lo < stream_hi))
-      return false;
-    (sp.out ? out_hi : stream_hi) = std::max(sp.out ? out_hi : stream_hi, sp.hi);
-  }
-  return true;
-}
-
 int refuse(hsrans_indexing_member *members, uint32_t count, int rc)
 {
   for (uint32_t k = 0; k < count; k++)
     members[k].rc = rc, members[k].indexed = nullptr;
   return rc;
 }
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 } // namespace
 
@@ -130,7 +98,16 @@ try
     for (uint32_t k = 0; k < count; k++)
       plans[k] = members[k].dplan;
     std::sort(plans.begin(), plans.end());
-    if (std::adjacent_find(plans.begin(), plans.end()) != plans.end() || !spans_disjoint(members, count))
+    // the overlap rule over what the kernels touch: outputs [d_out, d_out + decoded_len) are written, streams [d_stream, d_stream + stream_length) read
+    std::vector<Span> spans;
+    spans.reserve(2 * (size_t)count);
+    for (uint32_t k = 0; k < count; k++)
+    {
+      const hsrans_indexing_member &m = members[k];
+      spans.push_back({(uintptr_t)m.d_out, (uintptr_t)m.d_out + (uintptr_t)m.dplan->hdr.decoded_len, true});
+      spans.push_back({(uintptr_t)m.d_stream, (uintptr_t)m.d_stream + m.stream_length, false});
+    }
+    if (std::adjacent_find(plans.begin(), plans.end()) != plans.end() || !spans_disjoint(spans))
       return refuse(members, count, HSRANS_E_ARG);
   }
 
@@ -186,26 +163,26 @@ try
 
   // ---- memory: the checkpoints of all members out of ctx->d_enc_ck, every member's new plan (its arena also holds a walk's records), the tables
   // the kernels read and the words they leave in ctx->d_enc_meta, the page-locked staging of both in ctx->h_pin ----
-  size_t ck_total = 0;
+  Carve ck;
   for (uint32_t k = 0; k < count; k++)
   {
     const PassBytes &pb = ms[k].walk ? ms[k].wz.pbytes : ms[k].mz.pbytes;
-    ms[k].ck_off = ck_total;
-    ck_total += up256(pb.st + pb.wd);
+    ms[k].ck_off = ck.take(pb.st + pb.wd);
   }
+  const size_t ck_total = ck.close();
   // device: [IndexPassMember x count | tasks | IndexArgs x n_mt | WalkIndexArgs x n_walk | status words' addresses x count] up, [IndexResult x count | status x count] down
-  const size_t off_tasks = up256((size_t)count * sizeof(IndexPassMember)), off_ia = off_tasks + up256((size_t)n_tasks * sizeof(IndexPassTask));
-  const size_t off_wa = off_ia + up256((size_t)n_mt * sizeof(IndexArgs)), off_ptr = off_wa + up256((size_t)n_walk * sizeof(WalkIndexArgs));
-  const size_t up_bytes = off_ptr + up256((size_t)count * sizeof(uint32_t *));
-  const size_t off_res = up_bytes, off_status = off_res + up256((size_t)count * sizeof(IndexResult)), down_bytes = off_status + up256((size_t)count * 4) - off_res;
-  size_t pin_bytes = up_bytes + down_bytes;
+  Carve at; // (the page-locked staging: the same, then the group lists that come down)
+  at.take((size_t)count * sizeof(IndexPassMember));
+  const size_t off_tasks = at.take((size_t)n_tasks * sizeof(IndexPassTask)), off_ia = at.take((size_t)n_mt * sizeof(IndexArgs));
+  const size_t off_wa = at.take((size_t)n_walk * sizeof(WalkIndexArgs)), off_ptr = at.take((size_t)count * sizeof(uint32_t *)), up_bytes = at.close();
+  const size_t off_res = at.take((size_t)count * sizeof(IndexResult)), off_status = at.take((size_t)count * 4), down_bytes = at.close() - off_res;
   for (uint32_t k = 0; k < count; k++)
     if (members[k].dplan->hdr.states == 64 && ms[k].max_groups != 0)
     {
       ms[k].groups_down = true;
-      ms[k].groups_off = pin_bytes;
-      pin_bytes += up256((size_t)ms[k].max_groups * sizeof(Group));
+      ms[k].groups_off = at.take((size_t)ms[k].max_groups * sizeof(Group));
     }
+  const size_t pin_bytes = at.close();
   if (!grow(&ctx->d_enc_ck, &ctx->d_enc_ck_cap, ck_total) || !grow(&ctx->d_enc_meta, &ctx->d_enc_meta_cap, up_bytes + down_bytes) ||
       !grow_pinned(&ctx->h_pin, &ctx->h_pin_cap, pin_bytes))
     return refuse(members, count, HSRANS_E_HIP);
@@ -343,9 +320,8 @@ try
     m.indexed = m.rc == HSRANS_OK ? e.nd : nullptr;
     e.nd = nullptr; // (adopted, or destroyed)
   }
-  if (clear && !(hipStreamSynchronize(s) == hipSuccess && cleared))
+  if (clear && !stream_settle(s, cleared))
   {
-    (void)hipGetLastError();
     for (uint32_t k = 0; k < count; k++)
       if (members[k].rc == HSRANS_E_DEVICE)
         members[k].rc = HSRANS_E_HIP;

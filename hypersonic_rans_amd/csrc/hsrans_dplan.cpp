@@ -367,10 +367,12 @@ static void dplan_blocks_from_device_groups(hsrans_dplan *d, hipStream_t s, cons
 
 extern "C++" int dplan_arena(hsrans_dplan *d, const DplanRegions &r, hipStream_t s, uint8_t **scratch)
 {
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t counter_bytes = r.counters ? (size_t)kCounterSets * kDynQueues * kDynQueueStride * 8 : 0;
-  const size_t off_plan = 256 + up256(counter_bytes), off_table = off_plan + up256(r.plan), off_groups = off_table + up256(r.table);
-  const size_t off_scratch = off_groups + up256(r.groups), end = off_scratch + up256(r.scratch);
+  Carve at;
+  at.take(256); // the status word
+  at.take(counter_bytes);
+  const size_t off_plan = at.take(r.plan), off_table = at.take(r.table), off_groups = at.take(r.groups), off_scratch = at.take(r.scratch);
+  const size_t end = at.close();
   if (!grow(&d->d_arena, &d->d_arena_cap, end))
     return HSRANS_E_HIP;
   uint8_t *a = d->d_arena;

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/hsrans_hip.h"
+#include "hsrans_carve.h"
 #include "hsrans_encode.h"
 #include "hsrans_host.h"
 #include "hsrans_kernels.h"
@@ -285,6 +286,17 @@ inline bool device_io_ok(const void *d_in, const void *d_out) // a device encode
 {
   return d_in != nullptr && d_out != nullptr && ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out & 15) == 0;
 }
+// the context's three encoder buffers, each grown to at least its size: block images (slots), per-call records, checkpoints
+bool encoder_buffers(hsrans_ctx *ctx, size_t scratch, size_t meta, size_t ck);
+// the checkpoint region of an encode with ck_slots slots of S states: [ck_slots][S] states, then ck_slots positions (32-bit words both)
+inline size_t ck_region_bytes(size_t ck_slots, uint32_t S) { return ck_slots * ((size_t)S * 4 + 4); }
+void ck_region(EncParams *ep, uint8_t *at, size_t ck_slots, uint32_t S); // ep->ck_states, ep->ck_pos
+// Synchronises `s` whether or not everything before it was queued (what was queued may still read the caller's host buffers); on a failure of
+// either kind the runtime's sticky error is consumed.  True: all was queued and has run.
+bool stream_settle(hipStream_t s, bool queued);
+// an encode's result words (EncParams::result): word 1, it was coded and fitted d_out; with check_refusal also word 2, the listed checkpoints
+// the pass did not meet, which must be 0.  The one-wavefront-per-block mt_ encodes keep their chain count in word 2: no check_refusal there.
+inline bool enc_result_ok(const uint64_t *result, bool check_refusal) { return result[1] == 1 && (!check_refusal || result[2] == 0); }
 // what an encode of one raw or mt_ stream derives from its arguments before anything is launched
 struct EncShape
 {
@@ -441,7 +453,6 @@ int gather_region_order(hsrans_ctx *ctx, hipStream_t s);
 int gather_region_commit(hsrans_ctx *ctx, const GatherRegion &region, hipStream_t s);
 
 // ---- what the first decodes share (hsrans_capi_index.cpp): hsrans_decode_device_indexing and hsrans_decode_device_indexing_batch ----
-inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 // What a recording pass writes besides the output: checkpoint states and read cursors, and for a block_ walk the block records, the states
 // on entry to each block and the block count.  Byte counts of the first four.
 struct PassBytes

@@ -195,6 +195,8 @@ def test_a_member_that_fails_fails_alone(gpu_ctx, zipf, cases, states):
 
 
 def test_refusals_write_nothing(gpu_ctx, zipf, cases):
+    import torch
+
     c = cases[0]
     a, b = _member(gpu_ctx, c), _member(gpu_ctx, c)
     spare = _member(gpu_ctx, c)[2]
@@ -203,6 +205,12 @@ def test_refusals_write_nothing(gpu_ctx, zipf, cases):
     d_raw = zipf[:300_000]
     s_raw = H.encode(H.RAW, 64, 11, d_raw)
     raw, in_raw = gpu_ctx.make_device_plan(H.plan_build(H.RAW, 64, 11, s_raw)), _upload(s_raw)
+    # one buffer that holds member a's stream at its front and, from byte 16 on, what would be member b's output: a write over a read
+    in_a = _upload(c.s)
+    shared = torch.full((16 + c.n + CANARY,), 0xCC, dtype=torch.uint8, device="cuda")
+    assert in_a.numel() > 16 and in_a.numel() < shared.numel()
+    shared[:in_a.numel()] = in_a
+    shared_before = shared.clone()
 
     def m(base, d_in, out, interval=c.interval, length=c.s.size):
         return (base, d_in, out[:c.n], interval, length)
@@ -211,7 +219,8 @@ def test_refusals_write_nothing(gpu_ctx, zipf, cases):
                           ("two members sharing an output", [m(a[0], a[1], a[2]), m(b[0], b[1], a[2])]),
                           ("an interval of 6", [m(a[0], a[1], a[2]), m(b[0], b[1], b[2], interval=6)]),
                           ("a member that is already indexed", [m(a[0], a[1], a[2]), m(indexed, b[1], b[2])]),
-                          ("a raw base plan", [m(a[0], a[1], a[2]), (raw, in_raw, spare[:d_raw.size], 32, s_raw.size)])):
+                          ("a raw base plan", [m(a[0], a[1], a[2]), (raw, in_raw, spare[:d_raw.size], 32, s_raw.size)]),
+                          ("an output lying over another member's stream", [m(a[0], shared[:in_a.numel()], a[2]), m(b[0], b[1], shared[16:])])):
         stats = {}
         with pytest.raises(H.HsransError) as e:
             gpu_ctx.decode_device_indexing_batch(members, stats=stats)
@@ -219,10 +228,17 @@ def test_refusals_write_nothing(gpu_ctx, zipf, cases):
         assert stats["launches"] == 0, what
         for out in (a[2], b[2], spare):
             assert bool((out == 0xCC).all()), what
+        assert torch.equal(shared, shared_before), what
     # ... and the same members, well formed, go through
     plans = gpu_ctx.decode_device_indexing_batch([m(a[0], a[1], a[2]), m(b[0], b[1], b[2])])
     for (base, d_in, out), p in zip((a, b), plans):
         _check_member(gpu_ctx, c, base, d_in, out, p, single=False)
+    # ... and so do two members, each with a base plan and an output of its own, that read ONE uploaded stream: reads may share
+    p, q = _member(gpu_ctx, c, in_a), _member(gpu_ctx, c, in_a)
+    assert p[1].data_ptr() == q[1].data_ptr() and p[0] is not q[0] and p[2].data_ptr() != q[2].data_ptr()
+    plans = gpu_ctx.decode_device_indexing_batch([m(p[0], in_a, p[2]), m(q[0], in_a, q[2])])
+    for (base, d_in, out), indexed in zip((p, q), plans):
+        _check_member(gpu_ctx, c, base, d_in, out, indexed, single=False)
 
 
 def test_both_assembly_paths(cases, monkeypatch):

@@ -1,7 +1,7 @@
 """hsrans_encode_device_batch against one single call per member: raw and mt_ (64 KiB independent blocks), 64 states, 11 bits, on
 enwik8-shaped data in batches of 32 x 1 MB, 256 x 64 KiB and 8 x 16 MB, without and with plans (raw: the batch-shaped index of
 hsrans_index_boundaries_batch; mt_: a checkpoint every 32 groups).  Both forms are synchronous; the time is a host clock around K single
-calls or around the one batch call, after a warm-up, best and median over --windows windows.  Every member of the batch is checked bit
+calls or around the one batch call, after a warm-up, best, median and interquartile range over --windows windows.  Every member of the batch is checked bit
 for bit (stream and plan) against its single call in the same process first.  Prints one JSON line per case and appends it to --out.
 Run on the GPU box: python tools/encode_batch_rate.py --out profiles/r08_encode_batch_rate.jsonl"""
 import argparse
@@ -34,7 +34,8 @@ def timed(fn):
         t0 = time.perf_counter()
         fn()
         ms.append((time.perf_counter() - t0) * 1e3)
-    return min(ms), float(np.median(ms))
+    q1, med, q3 = np.percentile(ms, (25, 50, 75))
+    return min(ms), float(med), float(q3 - q1)
 
 
 def plan_bytes(p):
@@ -93,14 +94,14 @@ for shape in args.shapes.split(","):
             close(plans)
             close([p for _, p in one])
             # ---- the clock ----
-            s_best, s_med = timed(lambda: close([p for _, p in singles()]))
-            b_best, b_med = timed(lambda: close(batch()[1]))
+            s_best, s_med, s_iqr = timed(lambda: close([p for _, p in singles()]))
+            b_best, b_med, b_iqr = timed(lambda: close(batch()[1]))
             total = K * n
             row = dict(tool="tools/encode_batch_rate.py", codec=f"{name} rANS32x64 16w {BITS}", block_size=BLOCK if container == H.MT else None,
                        members=K, member_bytes=n, plans=with_plans, members_with_plans=sum(p is not None for p in plans),
                        launches=stats["launches"], mt_blocks=stats["mt_blocks"],
-                       stream_bytes=int(sum(lengths)), singles_ms_best=round(s_best, 3), singles_ms_median=round(s_med, 3),
-                       batch_ms_best=round(b_best, 3), batch_ms_median=round(b_med, 3),
+                       stream_bytes=int(sum(lengths)), singles_ms_best=round(s_best, 3), singles_ms_median=round(s_med, 3), singles_ms_iqr=round(s_iqr, 3),
+                       batch_ms_best=round(b_best, 3), batch_ms_median=round(b_med, 3), batch_ms_iqr=round(b_iqr, 3),
                        singles_GB_s_best=round(total / s_best / 1e6, 2), batch_GB_s_best=round(total / b_best / 1e6, 2),
                        batch_GB_s_median=round(total / b_med / 1e6, 2), speedup_best=round(s_best / b_best, 2), speedup_median=round(s_med / b_med, 2),
                        windows=args.windows, checked="bit-exact vs single calls (streams and plans)")

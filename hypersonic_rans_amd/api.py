@@ -129,6 +129,19 @@ class GatherSetInfo(ctypes.Structure):  # hsrans_gather_set_info_t
                [(n, _u32 * 6) for n in ("kind_members", "kind_tasks", "kind_entries", "kind_grid", "kind_waves", "kind_lds_bytes")]
 
 
+PLANES_MAX = 8
+PLANES_STORE_INCOMPRESSIBLE = 1
+
+
+class PlanesDesc(ctypes.Structure):  # hsrans_planes_desc
+    _fields_ = [(n, _u32) for n in ("elem_size", "states", "bits", "block_size", "index_interval", "stored_mask")] + \
+               [("elements", ctypes.c_uint64), ("offset", ctypes.c_uint64 * PLANES_MAX), ("length", ctypes.c_uint64 * PLANES_MAX), ("frame_length", ctypes.c_uint64)]
+
+
+class PlanesInfo(ctypes.Structure):  # hsrans_planes_info_t
+    _fields_ = [(n, _u32) for n in ("coded", "stored", "launches")]
+
+
 COMM_ID_BYTES = 128
 SHARD_DECODE_ONLY, SHARD_DECODE_AND_EXCHANGE, SHARD_EXCHANGE_ONLY = 0, 1, 2
 
@@ -356,6 +369,30 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_host_register.argtypes = [_vp, _vp, _sz]
     L.hsrans_host_unregister.restype = _i
     L.hsrans_host_unregister.argtypes = [_vp, _vp]
+    L.hsrans_planes_capacity.restype = _sz
+    L.hsrans_planes_capacity.argtypes = [_u32, _i, _sz]
+    L.hsrans_planes_workspace_bytes.restype = _sz
+    L.hsrans_planes_workspace_bytes.argtypes = [_u32, _sz]
+    L.hsrans_planes_split.restype = _i
+    L.hsrans_planes_split.argtypes = [_u32, _vp, _sz, _vp]
+    L.hsrans_planes_merge.restype = _i
+    L.hsrans_planes_merge.argtypes = [_u32, _vp, _sz, _vp]
+    L.hsrans_planes_split_device.restype = _i
+    L.hsrans_planes_split_device.argtypes = [_vp, _u32, _vp, _sz, _vp, _vp]
+    L.hsrans_planes_merge_device.restype = _i
+    L.hsrans_planes_merge_device.argtypes = [_vp, _u32, _vp, _sz, _vp, _vp]
+    L.hsrans_encode_device_planes.restype = _sz
+    L.hsrans_encode_device_planes.argtypes = [_vp, _u32, _i, _u32, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, ctypes.POINTER(PlanesDesc), ctypes.POINTER(_vp)]
+    L.hsrans_planes_create.restype = _i
+    L.hsrans_planes_create.argtypes = [_vp, ctypes.POINTER(PlanesDesc), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]
+    L.hsrans_planes_destroy.restype = None
+    L.hsrans_planes_destroy.argtypes = [_vp]
+    L.hsrans_decode_device_planes.restype = _i
+    L.hsrans_decode_device_planes.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
+    L.hsrans_planes_status.restype = _i
+    L.hsrans_planes_status.argtypes = [_vp, _vp, _vp, _vp]
+    L.hsrans_planes_info.restype = _i
+    L.hsrans_planes_info.argtypes = [_vp, ctypes.POINTER(PlanesInfo)]
     _LIB = L
     return L
 
@@ -712,6 +749,41 @@ def batch_deal(chain_starts, grid: int = 512, waves: int = 16, weights=None):
     return float(imb), slots.reshape(-1, 4)
 
 
+def planes_capacity(itemsize: int, states: int, elements: int) -> int:
+    """hsrans_planes_capacity: the bytes of a frame of ``elements`` elements of ``itemsize`` bytes (0: bad arguments)."""
+    return load_library().hsrans_planes_capacity(itemsize, states, elements)
+
+
+def planes_workspace_bytes(itemsize: int, elements: int) -> int:
+    """hsrans_planes_workspace_bytes: the workspace of encode_device_planes / decode_device_planes (0: bad arguments)."""
+    return load_library().hsrans_planes_workspace_bytes(itemsize, elements)
+
+
+def planes_split(array) -> list:
+    """hsrans_planes_split on the host: the byte planes of a contiguous array of 2-, 4- or 8-byte items (plane p = byte p of every
+    item, in memory order), a uint8 array of ``array.size`` bytes each."""
+    a = np.ascontiguousarray(array)
+    planes = [np.empty(a.size, np.uint8) for _ in range(a.itemsize)]
+    ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
+    rc = load_library().hsrans_planes_split(a.itemsize, a.ctypes.data if a.size else ptrs, a.size, ptrs)
+    if rc != 0:
+        raise HsransError(f"hsrans_planes_split failed with code {rc}")
+    return planes
+
+
+def planes_merge(planes, itemsize: int) -> np.ndarray:
+    """hsrans_planes_merge on the host: ``itemsize`` planes of equal length interleaved back into the items' bytes (uint8)."""
+    planes = [_u8(p) for p in planes]
+    if len(planes) != itemsize or any(p.size != planes[0].size for p in planes):
+        raise HsransError("planes_merge: one plane per byte of an item, all of one length")
+    out = np.empty(planes[0].size * itemsize, np.uint8)
+    ptrs = (_vp * itemsize)(*[p.ctypes.data for p in planes])
+    rc = load_library().hsrans_planes_merge(itemsize, ptrs, planes[0].size, out.ctypes.data if out.size else ptrs)
+    if rc != 0:
+        raise HsransError(f"hsrans_planes_merge failed with code {rc}")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU side
 # ---------------------------------------------------------------------------------------------------------------------
@@ -734,6 +806,29 @@ class Batch:
     def close(self):
         if self.handle:
             load_library().hsrans_dplan_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Planes:
+    """hsrans_planes: a frame's descriptor bound to its planes' device plans (Context.make_planes / Context.decode_device_planes)."""
+
+    def __init__(self, ctx: "Context", handle, desc: PlanesDesc, plans):
+        self.ctx, self.handle, self.desc, self.plans = ctx, handle, desc, list(plans)  # (keeps the planes' plans alive)
+
+    def info(self) -> dict:
+        info = PlanesInfo()
+        load_library().hsrans_planes_info(self.handle, ctypes.byref(info))
+        return {n: getattr(info, n) for n, _ in PlanesInfo._fields_}
+
+    def close(self):
+        if self.handle:
+            load_library().hsrans_planes_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1472,6 +1567,92 @@ class Context:
         if want_device_plans:
             out.append(dplans)
         return out[0] if len(out) == 1 else tuple(out)
+
+    # -- multi-byte elements as byte planes ----------------------------------------------------------------------------
+    @staticmethod
+    def _plane_ptrs(d_planes, itemsize: int):
+        d_planes = list(d_planes)
+        if len(d_planes) != itemsize:
+            raise HsransError(f"one plane per byte of an element: {itemsize} planes, not {len(d_planes)}")
+        return (_vp * max(itemsize, 1))(*[t.data_ptr() for t in d_planes])
+
+    def planes_split_device(self, tensor: torch.Tensor, d_planes, elements: int | None = None, stream: torch.cuda.Stream | None = None):
+        """hsrans_planes_split_device: the elements of a contiguous CUDA tensor (2-, 4- or 8-byte items) into ``d_planes`` (one uint8
+        tensor of at least ``elements`` bytes per byte of an item).  Asynchronous on ``stream`` (default: torch's current stream)."""
+        s = stream if stream is not None else torch.cuda.current_stream(tensor.device)
+        W = tensor.element_size()
+        rc = self.L.hsrans_planes_split_device(self.handle, W, tensor.data_ptr(), tensor.numel() if elements is None else elements,
+                                               self._plane_ptrs(d_planes, W), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_planes_split_device failed with code {rc}")
+            err.code = rc
+            raise err
+
+    def planes_merge_device(self, d_planes, out_tensor: torch.Tensor, elements: int | None = None, stream: torch.cuda.Stream | None = None):
+        """hsrans_planes_merge_device: ``d_planes`` interleaved back into the elements of ``out_tensor``.  Asynchronous on ``stream``."""
+        s = stream if stream is not None else torch.cuda.current_stream(out_tensor.device)
+        W = out_tensor.element_size()
+        rc = self.L.hsrans_planes_merge_device(self.handle, W, self._plane_ptrs(d_planes, W), out_tensor.numel() if elements is None else elements,
+                                               out_tensor.data_ptr(), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_planes_merge_device failed with code {rc}")
+            err.code = rc
+            raise err
+
+    def encode_device_planes(self, tensor: torch.Tensor, d_frame: torch.Tensor, d_work: torch.Tensor, states: int = 64, bits: int = 11,
+                             block_size: int = 1 << 16, index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True,
+                             stream: torch.cuda.Stream | None = None):
+        """hsrans_encode_device_planes: a contiguous CUDA tensor whose ``element_size()`` is 2, 4 or 8, taken as bytes, into a frame of
+        byte planes at ``d_frame`` (``planes_capacity`` bytes; ``d_work``: ``planes_workspace_bytes``).  Returns ``(frame_length, desc,
+        plans)``: ``desc`` a PlanesDesc, ``plans`` a DevicePlan per plane (None for a stored plane; all None without ``want_plans``)."""
+        if not tensor.is_contiguous():
+            raise HsransError("encode_device_planes takes a contiguous tensor")
+        s = stream if stream is not None else torch.cuda.current_stream(tensor.device)
+        W = tensor.element_size()
+        desc = PlanesDesc()
+        handles = (_vp * PLANES_MAX)()
+        n = self.L.hsrans_encode_device_planes(self.handle, W, states, bits, tensor.data_ptr(), tensor.numel(), d_frame.data_ptr(), d_frame.numel(), block_size,
+                                               index_interval, PLANES_STORE_INCOMPRESSIBLE if store_incompressible else 0, d_work.data_ptr(), d_work.numel(),
+                                               ctypes.c_void_p(s.cuda_stream), ctypes.byref(desc), handles if want_plans else None)
+        if n == 0:
+            raise HsransError("hsrans_encode_device_planes failed")
+        plans = [DevicePlan(self, _vp(handles[p])) if want_plans and handles[p] else None for p in range(W)]
+        return n, desc, plans
+
+    def make_planes(self, desc: PlanesDesc, plans) -> Planes:
+        """hsrans_planes_create: ``plans[p]`` is plane p's DevicePlan, None exactly for the stored planes."""
+        plans = list(plans)
+        if len(plans) != desc.elem_size:
+            raise HsransError(f"one plan (or None) per plane: {desc.elem_size}, not {len(plans)}")
+        arr = (_vp * PLANES_MAX)(*[None if d is None else (d.handle.value if isinstance(d.handle, ctypes.c_void_p) else d.handle) for d in plans])
+        h = _vp()
+        rc = self.L.hsrans_planes_create(self.handle, ctypes.byref(desc), arr, ctypes.byref(h))
+        if rc != 0:
+            err = HsransError(f"hsrans_planes_create failed with code {rc}")
+            err.code = rc
+            raise err
+        return Planes(self, h, desc, plans)
+
+    def decode_device_planes(self, planes: Planes, d_frame: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                             stream: torch.cuda.Stream | None = None, frame_length: int | None = None):
+        """hsrans_decode_device_planes: the frame at ``d_frame`` back into the elements of ``out_tensor`` (contiguous, as many bytes as
+        were encoded).  Asynchronous on ``stream`` (default: torch's current stream)."""
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes takes a contiguous output tensor")
+        s = stream if stream is not None else torch.cuda.current_stream(d_frame.device)
+        rc = self.L.hsrans_decode_device_planes(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
+                                                out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_planes failed with code {rc}")
+            err.code = rc
+            raise err
+
+    def planes_status(self, planes: Planes, stream: torch.cuda.Stream | None = None) -> list:
+        s = stream if stream is not None else torch.cuda.current_stream()
+        codes = (ctypes.c_int * PLANES_MAX)()
+        self.L.hsrans_planes_status(self.handle, planes.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        return list(codes)[: planes.desc.elem_size]
 
     def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
                              stream: torch.cuda.Stream | None = None) -> np.ndarray:

@@ -1,0 +1,414 @@
+// hsrans_capi_planes.cpp — multi-byte elements coded as byte planes: the element layer over the batch entries.  Part of the C ABI of
+// libhsrans_hip.so (include/hsrans_hip.h).  hsrans_encode_device_planes is one split launch (hsrans_planes.hip), ONE hsrans_encode_device_batch
+// of the planes as mt_ members and, where asked for, a copy over the planes that did not shrink; hsrans_decode_device_planes is
+// hsrans_decode_device_batch of the coded planes and one merge launch behind it.  Both codecs are used as they are, through their public
+// entries: a coded plane is byte for byte what hsrans_encode_device(HSRANS_MT, ...) writes for the plane's bytes.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <new>
+#include <vector>
+
+#include "../../include/hsrans_hip.h"
+#include "hsrans_planes.h"
+
+#include "hsrans_internal.h"
+
+struct hsrans_planes
+{
+  hsrans_ctx *ctx = nullptr;
+  hsrans_planes_desc desc{};
+  hsrans_batch *batch = nullptr;   // over the coded planes; null when every plane is stored
+  std::vector<uint32_t> coded;     // plane of batch member k
+  std::vector<hsrans_dplan *> dplans; // of the coded planes, in batch order
+};
+
+namespace
+{
+constexpr uint32_t kMaxBatchTasks = 1u << 24; // hsrans_encode_device_batch: fewer mt_ blocks than this in one call
+
+bool width_ok(uint32_t W) { return W == 2 || W == 4 || W == 8; }
+bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
+size_t plane_stride(int states, size_t elements) { return up256(capacity(HSRANS_MT, states, elements)); } // a coded plane's room in the frame
+Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
+
+// the planes of a workspace: plane p at p * up256(elements)
+PlanePtrs work_planes(uint32_t W, void *d_work, size_t elements)
+{
+  PlanePtrs pp{};
+  for (uint32_t p = 0; p < W; p++)
+    pp.p[p] = (uint8_t *)d_work + p * up256(elements);
+  return pp;
+}
+
+// the checks of the two kernel entries: W pointers to `elements` bytes each and the element buffer, all 16-byte aligned, none meeting another
+bool kernel_args_ok(uint32_t W, const void *d_elements, size_t elements, const void *const *d_planes, bool planes_written, PlanePtrs *pp)
+{
+  if (!width_ok(W) || !aligned16(d_elements) || d_planes == nullptr || elements == 0 || elements > kPlanesMaxElements)
+    return false;
+  std::vector<Span> spans;
+  spans.push_back(span_of(d_elements, elements * W, !planes_written));
+  for (uint32_t p = 0; p < W; p++)
+  {
+    if (!aligned16(d_planes[p]))
+      return false;
+    pp->p[p] = (uint8_t *)d_planes[p];
+    spans.push_back(span_of(d_planes[p], elements, true)); // (as writes on either side: two planes never share memory)
+  }
+  return spans_disjoint(spans);
+}
+
+void drop_plans(hsrans_dplan **plans, uint32_t W)
+{
+  for (uint32_t p = 0; plans != nullptr && p < W; p++)
+    if (plans[p] != nullptr)
+    {
+      hsrans_dplan_destroy(plans[p]);
+      plans[p] = nullptr;
+    }
+}
+} // namespace
+
+extern "C" size_t hsrans_planes_capacity(uint32_t elem_size, int states, size_t elements)
+{
+  if (!width_ok(elem_size) || (states != 32 && states != 64) || elements == 0)
+    return 0;
+  return elem_size * plane_stride(states, elements);
+}
+
+extern "C" size_t hsrans_planes_workspace_bytes(uint32_t elem_size, size_t elements)
+{
+  if (!width_ok(elem_size) || elements == 0)
+    return 0;
+  return elem_size * up256(elements);
+}
+
+extern "C" int hsrans_planes_split(uint32_t elem_size, const void *in, size_t elements, uint8_t *const *planes)
+{
+  if (!width_ok(elem_size) || in == nullptr || planes == nullptr)
+    return HSRANS_E_ARG;
+  for (uint32_t p = 0; p < elem_size; p++)
+    if (planes[p] == nullptr)
+      return HSRANS_E_ARG;
+  const uint8_t *src = (const uint8_t *)in;
+  for (size_t i = 0; i < elements; i++)
+    for (uint32_t p = 0; p < elem_size; p++)
+      planes[p][i] = src[i * elem_size + p];
+  return HSRANS_OK;
+}
+
+extern "C" int hsrans_planes_merge(uint32_t elem_size, const uint8_t *const *planes, size_t elements, void *out)
+{
+  if (!width_ok(elem_size) || out == nullptr || planes == nullptr)
+    return HSRANS_E_ARG;
+  for (uint32_t p = 0; p < elem_size; p++)
+    if (planes[p] == nullptr)
+      return HSRANS_E_ARG;
+  uint8_t *dst = (uint8_t *)out;
+  for (size_t i = 0; i < elements; i++)
+    for (uint32_t p = 0; p < elem_size; p++)
+      dst[i * elem_size + p] = planes[p][i];
+  return HSRANS_OK;
+}
+
+extern "C" int hsrans_planes_split_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, size_t elements, void *const *d_planes, void *hip_stream)
+try
+{
+  PlanePtrs pp{};
+  if (ctx == nullptr || !kernel_args_ok(elem_size, d_in, elements, (const void *const *)d_planes, true, &pp))
+    return HSRANS_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(elem_size, d_in, elements, pp, (hipStream_t)hip_stream) != hipSuccess)
+    return HSRANS_E_HIP;
+  return HSRANS_OK;
+}
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_merge_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, size_t elements, void *d_out, void *hip_stream)
+try
+{
+  PlanePtrs pp{};
+  if (ctx == nullptr || !kernel_args_ok(elem_size, d_out, elements, d_planes, false, &pp))
+    return HSRANS_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(elem_size, pp, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
+    return HSRANS_E_HIP;
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" size_t hsrans_encode_device_planes(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, size_t elements, void *d_frame,
+                                              size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags, void *d_work, size_t work_bytes,
+                                              void *hip_stream, hsrans_planes_desc *desc, hsrans_dplan **out_dplans)
+try
+{
+  if (desc != nullptr)
+    *desc = hsrans_planes_desc{};
+  if (!width_ok(elem_size))
+    return 0;
+  const uint32_t W = elem_size;
+  for (uint32_t p = 0; out_dplans != nullptr && p < W; p++)
+    out_dplans[p] = nullptr; // (the caller's array may hold anything: nothing to destroy yet)
+  if (ctx == nullptr || desc == nullptr || (flags & ~HSRANS_PLANES_STORE_INCOMPRESSIBLE) != 0 || !aligned16(d_in) || !aligned16(d_frame) || !aligned16(d_work))
+    return 0;
+
+  // ---- everything checked before anything is launched: each plane by its single call's rules (mt_shape), then the call's own ----
+  EncShape sh;
+  if (!(states == 32 || states == 64) || elements == 0 || elements > kPlanesMaxElements)
+    return 0;
+  const size_t stride = plane_stride(states, elements), work_stride = up256(elements);
+  if (!mt_shape(states, bits, elements, stride, block_size, index_interval, out_dplans != nullptr, &sh) || (uint64_t)sh.n_blocks * W >= kMaxBatchTasks)
+    return 0;
+  Carve frame, work; // (the frame and the workspace: W regions each)
+  size_t offset[HSRANS_PLANES_MAX] = {};
+  for (uint32_t p = 0; p < W; p++)
+  {
+    offset[p] = frame.take(stride, 256);
+    work.take(work_stride, 256);
+  }
+  if (frame_capacity < frame.close(256) || work_bytes < work.close(256))
+    return 0;
+  {
+    std::vector<Span> spans{span_of(d_in, elements * W, false), span_of(d_frame, frame_capacity, true), span_of(d_work, work_bytes, true)};
+    if (!spans_disjoint(spans))
+      return 0;
+  }
+
+  hipStream_t s = (hipStream_t)hip_stream;
+  const PlanePtrs pp = work_planes(W, d_work, elements);
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(W, d_in, elements, pp, s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return 0;
+  }
+  // (ctx->lock is not held here: hsrans_encode_device_batch takes it, and it is not recursive)
+  hsrans_encode_member members[HSRANS_PLANES_MAX] = {};
+  for (uint32_t p = 0; p < W; p++)
+  {
+    hsrans_encode_member &m = members[p];
+    m.container = HSRANS_MT;
+    m.states = states;
+    m.bits = bits;
+    m.block_size = block_size;
+    m.d_in = pp.p[p];
+    m.length = elements;
+    m.d_out = (uint8_t *)d_frame + offset[p];
+    m.out_capacity = stride;
+    m.index_interval = index_interval;
+  }
+  if (hsrans_encode_device_batch(ctx, members, W, hip_stream, out_dplans, nullptr) != HSRANS_OK)
+  {
+    drop_plans(out_dplans, W);
+    return 0;
+  }
+
+  // ---- the planes that did not shrink: their bytes instead of their streams ----
+  uint32_t stored = 0;
+  bool copied = true;
+  for (uint32_t p = 0; p < W; p++)
+    if ((flags & HSRANS_PLANES_STORE_INCOMPRESSIBLE) != 0 && members[p].stream_length >= elements)
+    {
+      stored |= 1u << p;
+      copied = copied && hipMemcpyAsync(members[p].d_out, pp.p[p], elements, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    }
+  if (stored != 0 && !stream_settle(s, copied))
+  {
+    drop_plans(out_dplans, W);
+    return 0;
+  }
+
+  desc->elem_size = W;
+  desc->states = (uint32_t)states;
+  desc->bits = bits;
+  desc->block_size = block_size;
+  desc->index_interval = index_interval;
+  desc->stored_mask = stored;
+  desc->elements = elements;
+  for (uint32_t p = 0; p < W; p++)
+  {
+    const bool is_stored = (stored >> p) & 1;
+    desc->offset[p] = offset[p];
+    desc->length[p] = is_stored ? elements : members[p].stream_length;
+    desc->frame_length = offset[p] + desc->length[p];
+    if (is_stored && out_dplans != nullptr && out_dplans[p] != nullptr)
+    {
+      hsrans_dplan_destroy(out_dplans[p]);
+      out_dplans[p] = nullptr;
+    }
+  }
+  return (size_t)desc->frame_length;
+}
+catch (...) // (thrown only after the caller's arrays were reset, or before elem_size was seen to be valid: then they were not touched)
+{
+  if (desc != nullptr)
+    *desc = hsrans_planes_desc{};
+  if (width_ok(elem_size))
+    drop_plans(out_dplans, elem_size);
+  return 0;
+}
+
+extern "C" void hsrans_planes_destroy(hsrans_planes *planes)
+{
+  if (planes == nullptr)
+    return;
+  if (planes->batch != nullptr)
+    hsrans_dplan_batch_destroy(planes->batch);
+  delete planes;
+}
+
+extern "C" int hsrans_planes_create(hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans, hsrans_planes **out_planes)
+try
+{
+  if (out_planes == nullptr)
+    return HSRANS_E_ARG;
+  *out_planes = nullptr;
+  if (ctx == nullptr || desc == nullptr || dplans == nullptr || !width_ok(desc->elem_size) || !valid_codec(HSRANS_MT, (int)desc->states, desc->bits) ||
+      desc->elements == 0 || desc->elements > kPlanesMaxElements || (desc->stored_mask >> desc->elem_size) != 0)
+    return HSRANS_E_ARG;
+  const uint32_t W = desc->elem_size;
+  std::vector<Span> spans;
+  uint64_t end = 0;
+  for (uint32_t p = 0; p < W; p++)
+  {
+    const bool is_stored = (desc->stored_mask >> p) & 1;
+    const hsrans_dplan *d = dplans[p];
+    if ((desc->offset[p] & 15) != 0 || desc->length[p] == 0 || desc->offset[p] + desc->length[p] < desc->offset[p] || is_stored != (d == nullptr))
+      return HSRANS_E_ARG;
+    if (is_stored ? desc->length[p] != desc->elements
+                  : (d->ctx != ctx || d->hdr.decoded_len != desc->elements || d->hdr.stream_len != desc->length[p] || d->hdr.states != desc->states ||
+                     d->hdr.bits != desc->bits))
+      return HSRANS_E_ARG;
+    spans.push_back(Span{(uintptr_t)desc->offset[p], (uintptr_t)(desc->offset[p] + up16(desc->length[p])), true}); // (as writes: no two planes share bytes)
+    end = std::max<uint64_t>(end, desc->offset[p] + desc->length[p]);
+  }
+  if (!spans_disjoint(spans) || desc->frame_length < end)
+    return HSRANS_E_ARG;
+
+  hsrans_planes *pl = new (std::nothrow) hsrans_planes;
+  if (pl == nullptr)
+    return HSRANS_E_HIP;
+  struct Guard // (an exception on its way to the handler below must not leak the object and its batch)
+  {
+    hsrans_planes *pl;
+    bool armed = true;
+    ~Guard()
+    {
+      if (armed)
+        hsrans_planes_destroy(pl);
+    }
+  } guard{pl};
+  pl->ctx = ctx;
+  pl->desc = *desc;
+  for (uint32_t p = 0; p < W; p++)
+    if (dplans[p] != nullptr)
+    {
+      pl->coded.push_back(p);
+      pl->dplans.push_back(dplans[p]);
+    }
+  if (!pl->coded.empty())
+  {
+    const int rc = hsrans_dplan_batch_create(ctx, pl->dplans.data(), (uint32_t)pl->dplans.size(), &pl->batch); // (refuses a plan that appears twice)
+    if (rc != HSRANS_OK)
+      return rc;
+  }
+  guard.armed = false;
+  *out_planes = pl;
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, void *d_out, size_t out_capacity,
+                                           void *d_work, size_t work_bytes, void *hip_stream)
+try
+{
+  if (ctx == nullptr || planes == nullptr || planes->ctx != ctx || !aligned16(d_frame) || !aligned16(d_out) || !aligned16(d_work))
+    return HSRANS_E_ARG;
+  const hsrans_planes_desc &desc = planes->desc;
+  const uint32_t W = desc.elem_size;
+  const size_t elements = (size_t)desc.elements;
+  if (frame_length < desc.frame_length || out_capacity < elements * W || work_bytes < hsrans_planes_workspace_bytes(W, elements))
+    return HSRANS_E_ARG;
+  {
+    std::vector<Span> spans{span_of(d_frame, frame_length, false), span_of(d_out, out_capacity, true), span_of(d_work, work_bytes, true)};
+    if (!spans_disjoint(spans))
+      return HSRANS_E_ARG;
+  }
+  // the merge's sources: a coded plane decoded into the workspace, a stored one where it lies in the frame
+  PlanePtrs src = work_planes(W, d_work, elements);
+  for (uint32_t p = 0; p < W; p++)
+    if ((desc.stored_mask >> p) & 1)
+      src.p[p] = (uint8_t *)d_frame + desc.offset[p];
+  if (planes->batch != nullptr)
+  {
+    const void *streams[HSRANS_PLANES_MAX];
+    void *outs[HSRANS_PLANES_MAX];
+    size_t lengths[HSRANS_PLANES_MAX], caps[HSRANS_PLANES_MAX];
+    for (size_t k = 0; k < planes->coded.size(); k++)
+    {
+      const uint32_t p = planes->coded[k];
+      streams[k] = (const uint8_t *)d_frame + desc.offset[p];
+      lengths[k] = (size_t)desc.length[p];
+      outs[k] = src.p[p];
+      caps[k] = elements;
+    }
+    const int rc = hsrans_decode_device_batch(ctx, planes->batch, streams, lengths, outs, caps, hip_stream);
+    if (rc != HSRANS_OK)
+      return rc;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(W, src, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_status(hsrans_ctx *ctx, hsrans_planes *planes, void *hip_stream, int *plane_status)
+try
+{
+  if (ctx == nullptr || planes == nullptr || planes->ctx != ctx)
+    return HSRANS_E_ARG;
+  for (uint32_t p = 0; plane_status != nullptr && p < planes->desc.elem_size; p++)
+    plane_status[p] = HSRANS_OK;
+  if (planes->batch == nullptr) // (every plane stored: nothing to report, but the call still waits for the stream as the batch's does)
+    return hipSetDevice(ctx->device) == hipSuccess && stream_settle((hipStream_t)hip_stream, true) ? HSRANS_OK : HSRANS_E_HIP;
+  int member_status[HSRANS_PLANES_MAX] = {};
+  const int rc = hsrans_dplan_batch_status(ctx, planes->batch, hip_stream, member_status);
+  for (size_t k = 0; plane_status != nullptr && k < planes->coded.size(); k++)
+    plane_status[planes->coded[k]] = member_status[k];
+  return rc;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_info(const hsrans_planes *planes, hsrans_planes_info_t *info)
+try
+{
+  if (planes == nullptr || info == nullptr)
+    return HSRANS_E_ARG;
+  *info = hsrans_planes_info_t{};
+  info->coded = (uint32_t)planes->coded.size();
+  info->stored = planes->desc.elem_size - info->coded;
+  hsrans_batch_info bi{};
+  if (planes->batch != nullptr && hsrans_dplan_batch_info(planes->batch, &bi) != HSRANS_OK)
+    return HSRANS_E_HIP;
+  info->launches = bi.launches + 1;
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}

@@ -791,6 +791,82 @@ typedef struct hsrans_encode_ex_batch_stats
 int hsrans_encode_device_ex_batch(hsrans_ctx *ctx, hsrans_encode_ex_member *members, uint32_t count, void *hip_stream,
                                   hsrans_dplan **out_dplans /* [count] or NULL */, hsrans_encode_ex_batch_stats *stats /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Multi-byte elements coded as byte planes.  What lies in HBM is mostly tensors of 2-, 4- or 8-byte elements; coded as they lie,
+ * bytes of very different statistics share one histogram (a bf16 value's sign/exponent byte carries ~2.6 bits, its mantissa byte
+ * ~8).  Each byte position coded as a stream of its own never costs entropy (entropy is concave in the histogram) and usually
+ * gains.
+ *
+ * Layout.  An element is W = elem_size bytes, W in {2, 4, 8}.  Plane p is the byte at memory offset p of every element, in
+ * element order: plane[p][i] = in[i * W + p].  Memory order: the library takes no view on endianness or dtype.
+ * A frame is ONE device buffer that holds the W planes at offsets known before encoding:
+ *   offset[p] = p * up256(hsrans_capacity(HSRANS_MT, states, elements))        (up256: rounded up to a multiple of 256)
+ * A plane is coded — an mt_ stream of independent fixed blocks, exactly what hsrans_encode_device(HSRANS_MT, ...) writes for the
+ * plane's bytes — or stored: its `elements` bytes verbatim (stored_mask).
+ * Decision: the descriptor is a host struct and the frame carries no header of its own; keeping or serialising the descriptor is
+ * the caller's business, like the plan blobs.
+ *
+ * The split (elements -> planes) and the merge (planes -> elements) are streaming kernels of their own, in front of the existing
+ * batch encoder and behind the existing batch decoder: neither codec kernel changes, and hsrans_decode_device_planes costs one
+ * pass over the decoded bytes more than hsrans_decode_device_batch of the same plans.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define HSRANS_PLANES_MAX 8
+#define HSRANS_PLANES_STORE_INCOMPRESSIBLE 1u /* flags: a plane whose stream is not shorter than its bytes is stored verbatim */
+typedef struct hsrans_planes_desc
+{
+  uint32_t elem_size, states, bits, block_size, index_interval;
+  uint32_t stored_mask; /* bit p: plane p is stored, not coded */
+  uint64_t elements;
+  uint64_t offset[HSRANS_PLANES_MAX], length[HSRANS_PLANES_MAX]; /* inside the frame; entries >= elem_size are 0 */
+  uint64_t frame_length;                                         /* end of the last plane's data */
+} hsrans_planes_desc;
+/* host arithmetic, no device; 0 on bad arguments (elem_size not 2, 4 or 8; states not 32 or 64; elements 0) */
+size_t hsrans_planes_capacity(uint32_t elem_size, int states, size_t elements); /* the frame's bytes */
+size_t hsrans_planes_workspace_bytes(uint32_t elem_size, size_t elements);      /* elem_size * up256(elements) */
+/* the layout on the host, in plain C++: planes[p] (elements bytes each) <-> in / out (elem_size * elements bytes); HSRANS_OK or HSRANS_E_ARG */
+int hsrans_planes_split(uint32_t elem_size, const void *in, size_t elements, uint8_t *const *planes);
+int hsrans_planes_merge(uint32_t elem_size, const uint8_t *const *planes, size_t elements, void *out);
+/* the two kernels alone.  d_planes: a HOST array of elem_size device pointers.  Asynchronous on `hip_stream`, no allocation, no
+ * synchronisation.  Every pointer is 16-byte aligned; the planes must not overlap each other or the element buffer. */
+int hsrans_planes_split_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, size_t elements, void *const *d_planes, void *hip_stream);
+int hsrans_planes_merge_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, size_t elements, void *d_out, void *hip_stream);
+/* d_in (elem_size * elements bytes) -> a frame at d_frame: one split launch into d_work, ONE hsrans_encode_device_batch of the
+ * elem_size planes as mt_ members, and with HSRANS_PLANES_STORE_INCOMPRESSIBLE a device-to-device copy over every plane whose
+ * stream_length >= elements (exactly this comparison; without the flag nothing is stored).  *desc describes the frame;
+ * out_dplans[p] (when out_dplans != NULL) is plane p's device plan, NULL for a stored plane.  Returns desc->frame_length, 0 on
+ * failure.  Synchronises `hip_stream`, like every encoder here.  A plane that hsrans_encode_device cannot encode (its stream does not
+ * fit hsrans_capacity: uniform bytes in 16 KiB blocks at 10 bits) fails the call, whatever the flags.
+ * Refused before anything is launched or written (0): a NULL ctx, desc or pointer; elem_size not 2, 4 or 8; states not 32 or 64;
+ * bits outside 10..15; block_size 0 or not a multiple of 64; index_interval not a multiple of 4; elements 0 or beyond
+ * hsrans_encode_device's limit; unknown flags; a pointer that is not 16-byte aligned; frame_capacity < hsrans_planes_capacity or
+ * work_bytes < hsrans_planes_workspace_bytes; any intersection among the element buffer, the frame and the workspace. */
+size_t hsrans_encode_device_planes(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, size_t elements, void *d_frame,
+                                   size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags, void *d_work, size_t work_bytes,
+                                   void *hip_stream, hsrans_planes_desc *desc, hsrans_dplan **out_dplans /* [elem_size] or NULL */);
+/* The decode side: a frame's descriptor bound to its planes' device plans.  dplans[p] is NULL exactly for the stored planes; every
+ * other one is a plan of this context over `elements` decoded bytes and length[p] stream bytes with the descriptor's states and
+ * bits, and appears once.  One hsrans_batch is made over the coded planes (none when all are stored).  The dplans must outlive
+ * the object.  The descriptor's offsets may be any multiples of 16 whose ranges [offset, offset + up16(length)) do not overlap
+ * and end within up16(frame_length): a caller may have compacted the frame. */
+typedef struct hsrans_planes hsrans_planes;
+int hsrans_planes_create(hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans, hsrans_planes **out_planes);
+void hsrans_planes_destroy(hsrans_planes *planes);
+/* frame -> d_out (elem_size * elements bytes): hsrans_decode_device_batch of the coded planes into d_work, then ONE merge launch
+ * behind it on the same stream; a stored plane is read by the merge straight from the frame (neither a decode nor a copy).
+ * Asynchronous on `hip_stream`, no allocation, no synchronisation; nothing is launched unless every argument passes (pointers
+ * set and 16-byte aligned; frame_length >= the descriptor's; out_capacity >= elem_size * elements; work_bytes >=
+ * hsrans_planes_workspace_bytes; frame, output and workspace disjoint): HSRANS_E_ARG otherwise. */
+int hsrans_decode_device_planes(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, void *d_out, size_t out_capacity,
+                                void *d_work, size_t work_bytes, void *hip_stream);
+/* hsrans_dplan_batch_status over the coded planes (synchronises `hip_stream`); stored planes report HSRANS_OK */
+int hsrans_planes_status(hsrans_ctx *ctx, hsrans_planes *planes, void *hip_stream, int *plane_status /* [elem_size] or NULL */);
+typedef struct hsrans_planes_info_t
+{
+  uint32_t coded, stored; /* planes */
+  uint32_t launches;      /* kernels of one hsrans_decode_device_planes: the batch's launches + the merge */
+} hsrans_planes_info_t;
+int hsrans_planes_info(const hsrans_planes *planes, hsrans_planes_info_t *info);
+
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one
  * sequential wavefront), HSRANS_MT (one wavefront per block) and HSRANS_BLOCK (one sequential wavefront that also reports

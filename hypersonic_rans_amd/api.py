@@ -142,6 +142,14 @@ class PlanesInfo(ctypes.Structure):  # hsrans_planes_info_t
     _fields_ = [(n, _u32) for n in ("coded", "stored", "launches")]
 
 
+class PlanesGatherInfo(ctypes.Structure):  # hsrans_planes_gather_info_t
+    _fields_ = [(n, _u32) for n in ("coded", "stored", "rows", "merge_tasks", "launches")]
+
+
+class PlanesGatherTask(ctypes.Structure):  # hsrans_planes_gather_task
+    _fields_ = [("src", ctypes.c_uint64), ("work_pos", ctypes.c_uint64), ("dst_delta", ctypes.c_int64), ("lo", _u32), ("hi", _u32)]
+
+
 COMM_ID_BYTES = 128
 SHARD_DECODE_ONLY, SHARD_DECODE_AND_EXCHANGE, SHARD_EXCHANGE_ONLY = 0, 1, 2
 
@@ -393,6 +401,20 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_planes_status.argtypes = [_vp, _vp, _vp, _vp]
     L.hsrans_planes_info.restype = _i
     L.hsrans_planes_info.argtypes = [_vp, ctypes.POINTER(PlanesInfo)]
+    L.hsrans_planes_gather_create.restype = _i
+    L.hsrans_planes_gather_create.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_vp)]
+    L.hsrans_planes_gather_destroy.restype = None
+    L.hsrans_planes_gather_destroy.argtypes = [_vp]
+    L.hsrans_planes_gather_workspace_bytes.restype = _sz
+    L.hsrans_planes_gather_workspace_bytes.argtypes = [_u32, _u32, ctypes.c_uint64]
+    L.hsrans_decode_device_planes_gather.restype = _i
+    L.hsrans_decode_device_planes_gather.argtypes = [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
+    L.hsrans_planes_gather_status.restype = _i
+    L.hsrans_planes_gather_status.argtypes = [_vp, _vp, _vp, _vp]
+    L.hsrans_planes_gather_info.restype = _i
+    L.hsrans_planes_gather_info.argtypes = [_vp, ctypes.POINTER(PlanesGatherInfo)]
+    L.hsrans_planes_gather_tasks.restype = _sz
+    L.hsrans_planes_gather_tasks.argtypes = [_vp, _u32, ctypes.c_uint64, _vp, _sz]
     _LIB = L
     return L
 
@@ -784,6 +806,26 @@ def planes_merge(planes, itemsize: int) -> np.ndarray:
     return out
 
 
+def planes_gather_workspace_bytes(itemsize: int, count: int, total_elements: int) -> int:
+    """hsrans_planes_gather_workspace_bytes: a workspace that takes every decode_device_planes_gather of ``count`` ranges with
+    ``total_elements`` elements in all: itemsize * up256(total_elements + 30 * count) (0: an item size that is not 2, 4 or 8)."""
+    return int(load_library().hsrans_planes_gather_workspace_bytes(itemsize, count, total_elements))
+
+
+def planes_gather_tasks(ranges, elements: int, capacity: int | None = None) -> np.ndarray:
+    """hsrans_planes_gather_tasks: the merge tasks ``ranges`` ((N, 3) uint64 or a list of (offset, length, dst_offset), in elements) of a
+    tensor of ``elements`` elements are cut into, as an (M, 5) uint64 array of (src, work_pos, dst_delta modulo 2^64, lo, hi).  Pure host
+    arithmetic; an empty array for invalid input.  ``capacity``: as gather_tasks."""
+    L = load_library()
+    arr = _ranges_array(ranges)
+    n = L.hsrans_planes_gather_tasks(_p(arr) if arr.size else None, arr.shape[0], elements, None, 0)
+    rows = n if capacity is None else min(n, capacity)
+    out = np.zeros(rows, np.dtype([("src", "<u8"), ("work_pos", "<u8"), ("dst_delta", "<u8"), ("lo", "<u4"), ("hi", "<u4")]))
+    if rows:
+        L.hsrans_planes_gather_tasks(_p(arr), arr.shape[0], elements, _p(out), rows)
+    return np.stack([out[n].astype(np.uint64) for n in out.dtype.names], axis=1) if rows else np.zeros((0, 5), np.uint64)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU side
 # ---------------------------------------------------------------------------------------------------------------------
@@ -829,6 +871,30 @@ class Planes:
     def close(self):
         if self.handle:
             load_library().hsrans_planes_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlanesGather:
+    """hsrans_planes_gather: a Planes object bound to the frame it reads (Context.make_planes_gather / Context.decode_device_planes_gather)."""
+
+    def __init__(self, ctx: "Context", handle, planes: Planes, d_frame):
+        self.ctx, self.handle, self.planes, self.d_frame = ctx, handle, planes, d_frame  # (keeps the planes object and the frame alive)
+
+    def info(self) -> dict:
+        """coded and stored planes, and of the last call: the gather's rows, the merge's tasks and the kernels launched"""
+        info = PlanesGatherInfo()
+        load_library().hsrans_planes_gather_info(self.handle, ctypes.byref(info))
+        return {n: getattr(info, n) for n, _ in PlanesGatherInfo._fields_}
+
+    def close(self):
+        if self.handle:
+            load_library().hsrans_planes_gather_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1653,6 +1719,48 @@ class Context:
         codes = (ctypes.c_int * PLANES_MAX)()
         self.L.hsrans_planes_status(self.handle, planes.handle, ctypes.c_void_p(s.cuda_stream), codes)
         return list(codes)[: planes.desc.elem_size]
+
+    def make_planes_gather(self, planes: Planes, d_frame: torch.Tensor, frame_length: int | None = None) -> PlanesGather:
+        """hsrans_planes_gather_create: binds ``planes`` to the frame in the CUDA uint8 tensor ``d_frame`` (16-byte aligned) for
+        decode_device_planes_gather.  The object keeps ``planes`` and the tensor alive.  Raises HsransError (``.code``: 2 a bad argument, 3 a
+        plane's plan has no entry points)."""
+        h = _vp()
+        rc = self.L.hsrans_planes_gather_create(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length, ctypes.byref(h))
+        if rc != 0:
+            err = HsransError(f"hsrans_planes_gather_create failed with code {rc}")
+            err.code = rc
+            raise err
+        return PlanesGather(self, h, planes, d_frame)
+
+    def decode_device_planes_gather(self, pg: PlanesGather, ranges, out_tensor: torch.Tensor, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """Element ranges of a frame that stays compressed on the GPU (hsrans_decode_device_planes_gather): for every row (offset, length,
+        dst_offset) of ``ranges`` ((N, 3) uint64 or a sequence of such rows), all in elements, the elements [offset, offset + length) of the
+        tensor land at element ``dst_offset`` of ``out_tensor`` (contiguous, the frame's element size); nothing else of it is written.
+        ``d_work``: a CUDA uint8 tensor, 16-byte aligned, of planes_gather_workspace_bytes(itemsize, N, total elements) bytes.  Asynchronous on
+        ``stream`` (default: torch's current stream); ``ranges`` is read before the call returns.  Raises HsransError (``.code``: 2 a bad
+        range, destination or buffer; nothing was launched)."""
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes_gather takes a contiguous output tensor")
+        if out_tensor.element_size() != pg.planes.desc.elem_size:
+            raise HsransError(f"decode_device_planes_gather: the frame's elements are {pg.planes.desc.elem_size} bytes, the output tensor's {out_tensor.element_size()}")
+        if d_work.dtype != torch.uint8:
+            raise HsransError("decode_device_planes_gather takes a uint8 workspace tensor")
+        s = stream if stream is not None else torch.cuda.current_stream(out_tensor.device)
+        arr = _ranges_array(ranges)
+        rc = self.L.hsrans_decode_device_planes_gather(self.handle, pg.handle, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
+                                                       out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                       ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_planes_gather failed with code {rc}")
+            err.code = rc
+            raise err
+
+    def planes_gather_status(self, pg: PlanesGather, stream: torch.cuda.Stream | None = None) -> list:
+        """hsrans_planes_gather_status: synchronises ``stream`` and returns every plane's status (stored planes: 0)"""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        codes = (ctypes.c_int * PLANES_MAX)()
+        self.L.hsrans_planes_gather_status(self.handle, pg.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        return list(codes)[: pg.planes.desc.elem_size]
 
     def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
                              stream: torch.cuda.Stream | None = None) -> np.ndarray:

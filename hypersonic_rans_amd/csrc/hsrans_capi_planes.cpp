@@ -14,15 +14,6 @@
 
 #include "hsrans_internal.h"
 
-struct hsrans_planes
-{
-  hsrans_ctx *ctx = nullptr;
-  hsrans_planes_desc desc{};
-  hsrans_batch *batch = nullptr;   // over the coded planes; null when every plane is stored
-  std::vector<uint32_t> coded;     // plane of batch member k
-  std::vector<hsrans_dplan *> dplans; // of the coded planes, in batch order
-};
-
 namespace
 {
 constexpr uint32_t kMaxBatchTasks = 1u << 24; // hsrans_encode_device_batch: fewer mt_ blocks than this in one call

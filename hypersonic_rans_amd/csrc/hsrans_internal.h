@@ -267,6 +267,16 @@ struct hsrans_batch
   std::vector<uint32_t> order_run; // per member: the slot order its chains were dealt with (diagnostics)
 };
 
+// hsrans_planes (hsrans_capi_planes.cpp): a frame's descriptor bound to its planes' device plans; hsrans_capi_planes_gather.cpp reads it
+struct hsrans_planes
+{
+  hsrans_ctx *ctx = nullptr;
+  hsrans_planes_desc desc{};
+  hsrans_batch *batch = nullptr;   // over the coded planes; null when every plane is stored
+  std::vector<uint32_t> coded;     // plane of batch member k
+  std::vector<hsrans_dplan *> dplans; // of the coded planes, in batch order
+};
+
 // (Re)fills a device plan from a validated host plan blob; one launch of a filled device plan (hsrans_dplan.cpp)
 int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_size, const PlanHeader &h, hipStream_t s);
 int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity, hipStream_t s, uint64_t stream_lo = 0,

@@ -866,6 +866,77 @@ typedef struct hsrans_planes_info_t
   uint32_t launches;      /* kernels of one hsrans_decode_device_planes: the batch's launches + the merge */
 } hsrans_planes_info_t;
 int hsrans_planes_info(const hsrans_planes *planes, hsrans_planes_info_t *info);
+/* ------------------------------------------------------------------------------------------------------------
+ * Element ranges of a frame that stays compressed in device memory — embedding rows, one expert's slice, pages of a cache.
+ * For every r < count the elements [ranges[r].offset, + ranges[r].length) of the tensor land at
+ * (uint8_t *)d_out + ranges[r].dst_offset * elem_size; no other byte of d_out is written.  All three fields of hsrans_range
+ * are in ELEMENTS here.  Ranges may overlap in the source; destinations that overlap are the caller's responsibility; an
+ * empty range does nothing (hsrans_decode_device_gather's rules).
+ * hsrans_planes_gather_create binds a hsrans_planes object to the frame it will read and makes ONE hsrans_gather_set over
+ * the coded planes — member k is the k-th coded plane, its stream d_frame + desc.offset[p], desc.length[p] bytes — and none
+ * when every plane is stored.  The planes object, its plans and the frame must outlive the gather object.  Returns
+ * HSRANS_E_ARG: a null argument, a planes object of another context, d_frame not 16-byte aligned, frame_length below the
+ * descriptor's; HSRANS_E_FORMAT: as hsrans_gather_set_create (a plan without entry points).
+ * The call: one hsrans_decode_device_gather_batch on the set (count x coded rows) that fetches the coded planes' bytes into
+ * d_work, then ONE merge launch behind it on the same stream that interleaves the fetched bytes with the stored planes'
+ * bytes, read straight from the frame.  Asynchronous on hip_stream; `ranges` (host memory) is read before the call returns;
+ * no allocation beyond what the context's task buffer does.  The merge's tasks go through that buffer like the gather's:
+ * the call is ordered with the other gathers of the context.
+ * Workspace layout, a pure function of the ranges: with phase = offset & 15 a non-empty range r has the slot
+ * [B_r, B_r + up16(phase + length)) of every plane's region, B_r = the sum of the earlier slots; the regions lie
+ * up256(sum of all slots) apart, region p at d_work + p * that; the byte of plane p of element offset + i is at
+ * region p + B_r + phase + i.  A 16-element block of the tensor is thus aligned alike in the workspace and in a stored
+ * plane, and every gather row is 16-byte aligned against its source (the gather's word stores).  Slot bytes outside
+ * [phase, phase + length) and the regions of stored planes are never written.
+ * hsrans_planes_gather_workspace_bytes = elem_size * up256(total_elements + 30 * count): enough for every `count` ranges of
+ * `total_elements` elements in all; 0 for an elem_size that is not 2, 4 or 8 (or an overflow).
+ * Everything is checked before anything is launched or uploaded.  HSRANS_E_ARG: a null handle or pointer, a null `ranges`
+ * with count > 0; a gather object of another context; d_out or d_work not 16-byte aligned; a range beyond the descriptor's
+ * elements; (dst_offset + length) * elem_size beyond out_capacity, or any 64-bit overflow in these sums; work_bytes below
+ * what THIS call's layout needs (elem_size * up256(sum of slots)); count * elem_size or the merge's task total at or above
+ * 2^31; any intersection among the frame, the output and the workspace.  HSRANS_OK with nothing launched: count == 0 or
+ * only empty ranges.  HSRANS_E_HIP (the runtime refused an upload or a launch) may leave the workspace written and the
+ * output not: the gather may have been queued before the merge failed.
+ * Cost: the gather of the coded planes' bytes (hsrans_decode_device_gather_batch's cost model: each task plus at most one
+ * chain in front of it) and one pass over the fetched elements.  128 MiB of bf16 / fp32, rows of 4096 elements: 49-53 us
+ * for 1 % of the rows against 84-134 us for hsrans_decode_device_planes and a copy of the rows; level at 10 %.  Above about
+ * a tenth of the tensor (9.3-11.1 % measured) decode the whole frame instead (README).  Destinations that are
+ * only element-aligned cost the same at that size (rows of 1000 elements: 54-80 us either way).
+ * hsrans_planes_gather_status: hsrans_gather_set_status mapped back to planes (synchronises hip_stream); stored planes
+ * report HSRANS_OK; with every plane stored it only settles the stream, as hsrans_planes_status does.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct hsrans_planes_gather hsrans_planes_gather;
+int hsrans_planes_gather_create(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, hsrans_planes_gather **out);
+void hsrans_planes_gather_destroy(hsrans_planes_gather *pg);
+size_t hsrans_planes_gather_workspace_bytes(uint32_t elem_size, uint32_t count, uint64_t total_elements);
+int hsrans_decode_device_planes_gather(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges /* host, in elements */, uint32_t count,
+                                       void *d_out, size_t out_capacity /* bytes */, void *d_work, size_t work_bytes, void *hip_stream);
+int hsrans_planes_gather_status(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream, int *plane_status /* [elem_size] or NULL */);
+typedef struct hsrans_planes_gather_info_t
+{
+  uint32_t coded, stored; /* planes */
+  /* the last hsrans_decode_device_planes_gather on the object (all 0: none yet, or it had nothing to do) */
+  uint32_t rows;        /* of its hsrans_decode_device_gather_batch: count x coded */
+  uint32_t merge_tasks; /* workgroups of its merge launch */
+  uint32_t launches;    /* kernels: the set's launches + the merge */
+} hsrans_planes_gather_info_t;
+int hsrans_planes_gather_info(const hsrans_planes_gather *pg, hsrans_planes_gather_info_t *info);
+/* The host-side cut of the merge, a pure function (no GPU), as hsrans_gather_tasks is for the codec gather.  One task = one
+ * workgroup's work: at most 4096 elements of one range, cut on the source's 16-element grid — task t of a range covers the
+ * elements [A + 4096 t, A + 4096 (t + 1)) with A = offset - phase, clipped to the range.  src (a multiple of 16, in
+ * tensor coordinates) is that window's first element and work_pos (a multiple of 16, in region coordinates) where it lies
+ * in a workspace region; the valid elements are [src + lo, src + hi), lo < 16 (only a range's first task has lo != 0),
+ * hi <= 4096; element e goes to output element e + dst_delta.  The tasks of a range tile it in order; empty ranges
+ * give no task.  Returns the tasks the ranges need and writes at most `capacity` of them (out may be NULL when capacity is
+ * 0); 0 for a null `ranges` with count > 0, a range beyond `elements`, or 2^31 tasks or more (one launch's limit, which
+ * hsrans_decode_device_planes_gather refuses by this same function). */
+typedef struct hsrans_planes_gather_task
+{
+  uint64_t src, work_pos;
+  int64_t dst_delta; /* elements */
+  uint32_t lo, hi;
+} hsrans_planes_gather_task; /* 32 bytes */
+size_t hsrans_planes_gather_tasks(const hsrans_range *ranges, uint32_t count, uint64_t elements, hsrans_planes_gather_task *out, size_t capacity);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

@@ -146,6 +146,10 @@ class PlanesGatherInfo(ctypes.Structure):  # hsrans_planes_gather_info_t
     _fields_ = [(n, _u32) for n in ("coded", "stored", "rows", "merge_tasks", "launches")]
 
 
+class PlanesGatherIndirectInfo(ctypes.Structure):  # hsrans_planes_gather_indirect_info_t
+    _fields_ = [(n, _u32) for n in ("coded", "stored", "max_rows", "merge_grid", "launches", "set_launches")]
+
+
 class PlanesGatherTask(ctypes.Structure):  # hsrans_planes_gather_task
     _fields_ = [("src", ctypes.c_uint64), ("work_pos", ctypes.c_uint64), ("dst_delta", ctypes.c_int64), ("lo", _u32), ("hi", _u32)]
 
@@ -413,6 +417,14 @@ def load_library() -> ctypes.CDLL:
     L.hsrans_planes_gather_status.argtypes = [_vp, _vp, _vp, _vp]
     L.hsrans_planes_gather_info.restype = _i
     L.hsrans_planes_gather_info.argtypes = [_vp, ctypes.POINTER(PlanesGatherInfo)]
+    L.hsrans_planes_gather_indirect_workspace_bytes.restype = _sz
+    L.hsrans_planes_gather_indirect_workspace_bytes.argtypes = [_u32, _u32]
+    L.hsrans_decode_device_planes_gather_indirect.restype = _i
+    L.hsrans_decode_device_planes_gather_indirect.argtypes = [_vp, _vp, _vp, _vp, _u32, ctypes.c_uint64, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
+    L.hsrans_planes_gather_refused.restype = _i
+    L.hsrans_planes_gather_refused.argtypes = [_vp, _vp, _vp]
+    L.hsrans_planes_gather_indirect_info.restype = _i
+    L.hsrans_planes_gather_indirect_info.argtypes = [_vp, _u32, ctypes.c_uint64, _sz, ctypes.POINTER(PlanesGatherIndirectInfo)]
     L.hsrans_planes_gather_tasks.restype = _sz
     L.hsrans_planes_gather_tasks.argtypes = [_vp, _u32, ctypes.c_uint64, _vp, _sz]
     _LIB = L
@@ -812,6 +824,12 @@ def planes_gather_workspace_bytes(itemsize: int, count: int, total_elements: int
     return int(load_library().hsrans_planes_gather_workspace_bytes(itemsize, count, total_elements))
 
 
+def planes_gather_indirect_workspace_bytes(itemsize: int, max_count: int) -> int:
+    """hsrans_planes_gather_indirect_workspace_bytes: the control workspace a decode_device_planes_gather_indirect of up to ``max_count``
+    ranges needs (a multiple of 256; 0: an item size that is not 2, 4 or 8, or max_count * itemsize at or above 2^31)."""
+    return int(load_library().hsrans_planes_gather_indirect_workspace_bytes(itemsize, max_count))
+
+
 def planes_gather_tasks(ranges, elements: int, capacity: int | None = None) -> np.ndarray:
     """hsrans_planes_gather_tasks: the merge tasks ``ranges`` ((N, 3) uint64 or a list of (offset, length, dst_offset), in elements) of a
     tensor of ``elements`` elements are cut into, as an (M, 5) uint64 array of (src, work_pos, dst_delta modulo 2^64, lo, hi).  Pure host
@@ -891,6 +909,16 @@ class PlanesGather:
         info = PlanesGatherInfo()
         load_library().hsrans_planes_gather_info(self.handle, ctypes.byref(info))
         return {n: getattr(info, n) for n, _ in PlanesGatherInfo._fields_}
+
+    def indirect_info(self, max_count: int, max_elements: int, out_capacity: int) -> dict:
+        """hsrans_planes_gather_indirect_info: what a decode_device_planes_gather_indirect of up to ``max_count`` ranges and ``max_elements``
+        elements will launch — coded and stored planes, the set's rows at most, the merge's grid, all kernels of a call and the set's part
+        of them.  No device call."""
+        info = PlanesGatherIndirectInfo()
+        rc = load_library().hsrans_planes_gather_indirect_info(self.handle, max_count, max_elements, out_capacity, ctypes.byref(info))
+        if rc != 0:
+            raise HsransError(f"hsrans_planes_gather_indirect_info failed with code {rc}")
+        return {n: getattr(info, n) for n, _ in PlanesGatherIndirectInfo._fields_}
 
     def close(self):
         if self.handle:
@@ -1754,6 +1782,56 @@ class Context:
             err = HsransError(f"hsrans_decode_device_planes_gather failed with code {rc}")
             err.code = rc
             raise err
+
+    def decode_device_planes_gather_indirect(self, pg: PlanesGather, d_ranges: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                             count: torch.Tensor | None = None, max_count: int | None = None, max_elements: int | None = None,
+                                             workspace: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """decode_device_planes_gather for ranges that are on the GPU (hsrans_decode_device_planes_gather_indirect): ``d_ranges`` is a
+        contiguous CUDA tensor (N, 3) of int64 / uint64 rows (offset, length, dst_offset), in elements; ``count`` a CUDA int32 / uint32 scalar
+        tensor with the number of rows in use (None: ``max_count``, itself N when None).  Both are read when the launches run, not here:
+        nothing is copied to the host, nothing is waited for, and the call can be captured into a graph.  ``max_elements``: the most elements
+        the rows fetch in all — it fixes the regions of ``d_work`` (a CUDA uint8 tensor of planes_gather_workspace_bytes(itemsize, max_count,
+        max_elements) bytes); None: what ``d_work`` can hold for that ``max_count``.  ``workspace``: a CUDA uint8 tensor of at least
+        planes_gather_indirect_workspace_bytes(itemsize, max_count) bytes that no other call in flight uses; allocated here when None.
+        Returns the workspace.  Raises HsransError (``.code``) for what the host can check; rows or a count only the device can refuse leave
+        ``out_tensor`` and ``d_work`` untouched and are reported by ``planes_gather_refused(pg)`` (5)."""
+        W = pg.planes.desc.elem_size
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes_gather_indirect takes a contiguous output tensor")
+        if out_tensor.element_size() != W:
+            raise HsransError(f"decode_device_planes_gather_indirect: the frame's elements are {W} bytes, the output tensor's {out_tensor.element_size()}")
+        if d_work.dtype != torch.uint8:
+            raise HsransError("decode_device_planes_gather_indirect takes a uint8 workspace tensor")
+        if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == 3 and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
+            raise TypeError("d_ranges: a contiguous CUDA tensor (N, 3) of int64 or uint64")
+        if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
+            raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
+        s = stream if stream is not None else torch.cuda.current_stream(out_tensor.device)
+        if max_count is None:
+            max_count = d_ranges.shape[0]
+        if max_count > d_ranges.shape[0]:
+            raise ValueError("max_count is larger than d_ranges")
+        if max_elements is None:
+            max_elements = max(0, d_work.numel() // W // 256 * 256 - 30 * max_count)
+        if workspace is None:
+            with torch.cuda.stream(s):
+                workspace = torch.empty(planes_gather_indirect_workspace_bytes(W, max_count), dtype=torch.uint8, device=out_tensor.device)
+        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace: a contiguous CUDA uint8 tensor")
+        rc = self.L.hsrans_decode_device_planes_gather_indirect(self.handle, pg.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
+                                                                max_elements, out_tensor.data_ptr(), out_tensor.numel() * W, d_work.data_ptr(), d_work.numel(),
+                                                                workspace.data_ptr(), workspace.numel(), ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            err = HsransError(f"hsrans_decode_device_planes_gather_indirect failed with code {rc}")
+            err.code = rc
+            raise err
+        return workspace
+
+    def planes_gather_refused(self, pg: PlanesGather, stream: torch.cuda.Stream | None = None) -> int:
+        """hsrans_planes_gather_refused: synchronises ``stream`` and returns 5 once where a decode_device_planes_gather_indirect on the object
+        was refused on the device since the last look, else 0"""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return int(self.L.hsrans_planes_gather_refused(self.handle, pg.handle, ctypes.c_void_p(s.cuda_stream)))
 
     def planes_gather_status(self, pg: PlanesGather, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_planes_gather_status: synchronises ``stream`` and returns every plane's status (stored planes: 0)"""

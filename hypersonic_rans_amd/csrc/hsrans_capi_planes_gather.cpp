@@ -3,6 +3,8 @@
 // of the merge (hsrans_planes_gather_tasks, a pure function), the argument checks, and the call: hsrans_decode_device_gather_batch of the coded
 // planes' bytes into the workspace through its public entry, then one k_planes_merge_ranges launch (hsrans_planes_gather.hip) whose task list
 // goes through the context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
+// hsrans_decode_device_planes_gather_indirect, at the end of the file: the same for ranges in device memory — the device cuts
+// (hsrans_planes_gather_indirect.hip), by the rules of planes_cut.h that the host's cut above uses too.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -12,6 +14,7 @@
 
 #include "../../include/hsrans_hip.h"
 #include "hsrans_planes.h"
+#include "planes_cut.h"
 
 #include "hsrans_internal.h"
 
@@ -25,21 +28,22 @@ struct hsrans_planes_gather
   size_t frame_length = 0;
   hsrans_gather_set *set = nullptr; // over the coded planes, member k = plane planes->coded[k]; null when every plane is stored
   hsrans_planes_gather_info_t last{}; // the last call's part of hsrans_planes_gather_info (under ctx->lock)
+  uint32_t *d_refused = nullptr; // the object's own status word (kStatusBadRange: k_planes_cut refused an indirect call); no plan's word is involved
 };
 
 namespace
 {
-constexpr uint64_t kTask = kPlanesGatherTaskElements;
+static_assert(kPlanesCutTask == kPlanesGatherTaskElements, "planes_cut.h cuts at the merge kernels' task length");
 
 bool width_ok(uint32_t W) { return W == 2 || W == 4 || W == 8; }
 bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
 Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
 
-// a non-empty range's slot in every plane's region: up16(phase + length) bytes
-uint64_t slot_of(const hsrans_range &g) { return ((g.offset & 15) + g.length + 15) & ~(uint64_t)15; }
+// a range's slot in every plane's region (planes_cut.h: up16(phase + length) bytes, none for an empty range)
+uint64_t slot_of(const hsrans_range &g) { return planes_range_slot(g.offset, g.length); }
 
 // The cut of the merge (hsrans_planes_gather_tasks' body) for ranges known to lie inside the tensor: task(record) for every task in order;
-// returns the sum of the slots
+// returns the sum of the slots.  Slot, task count and task k of a range are planes_cut.h's, which the device's cut uses as they stand.
 template <typename Task>
 uint64_t cut_ranges(const hsrans_range *ranges, uint32_t count, Task &&task)
 {
@@ -47,12 +51,8 @@ uint64_t cut_ranges(const hsrans_range *ranges, uint32_t count, Task &&task)
   for (uint32_t r = 0; r < count; r++)
   {
     const hsrans_range &g = ranges[r];
-    if (g.length == 0)
-      continue;
-    const uint64_t phase = g.offset & 15, first = g.offset - phase, stop = g.offset + g.length;
-    const int64_t delta = (int64_t)(g.dst_offset - g.offset); // (modulo 2^64: the device adds it back the same way)
-    for (uint64_t src = first; src < stop; src += kTask)
-      task(hsrans_planes_gather_task{src, at + (src - first), delta, src == first ? (uint32_t)phase : 0, (uint32_t)(stop - src < kTask ? stop - src : kTask)});
+    for (uint64_t k = 0, n = planes_range_tasks(g.offset, g.length); k < n; k++)
+      task(planes_task_at<hsrans_planes_gather_task>(g.offset, g.length, g.dst_offset, at, k));
     at += slot_of(g);
   }
   return at;
@@ -66,15 +66,13 @@ bool measure_ranges(const hsrans_range *ranges, uint32_t count, uint64_t element
   for (uint32_t r = 0; r < count; r++)
   {
     const hsrans_range &g = ranges[r];
-    if (!gather_extent_ok(g.offset, g.length, elements))
+    if (!planes_source_ok(g.offset, g.length, elements))
       return false;
-    if (g.length == 0)
-      continue;
     const uint64_t slot = slot_of(g);
-    if (slot < g.length || *slots + slot < *slots)
+    if (*slots + slot < *slots)
       return false;
     *slots += slot;
-    *tasks += ((g.offset & 15) + g.length + kTask - 1) / kTask;
+    *tasks += planes_range_tasks(g.offset, g.length);
     if (*tasks >= 0x80000000u)
       return false;
   }
@@ -112,6 +110,8 @@ extern "C" void hsrans_planes_gather_destroy(hsrans_planes_gather *pg)
     return;
   if (pg->set != nullptr)
     hsrans_gather_set_destroy(pg->set);
+  if (pg->d_refused != nullptr)
+    (void)hipFree(pg->d_refused);
   delete pg;
 }
 
@@ -148,6 +148,13 @@ try
       delete pg;
       return rc;
     }
+  }
+  // the word hsrans_decode_device_planes_gather_indirect's cut reports a refusal in (as hsrans_gather_set_create makes the set's)
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&pg->d_refused, sizeof(uint32_t)) != hipSuccess || hipMemset(pg->d_refused, 0, sizeof(uint32_t)) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    hsrans_planes_gather_destroy(pg);
+    return HSRANS_E_HIP;
   }
   *out = pg;
   return HSRANS_OK;
@@ -285,4 +292,190 @@ extern "C" int hsrans_planes_gather_info(const hsrans_planes_gather *pg, hsrans_
   std::lock_guard<std::mutex> lk(pg->ctx->lock);
   *info = pg->last;
   return HSRANS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_planes_gather_indirect: the ranges are in device memory.  Nothing of the above is cut here: k_planes_cut checks the
+// ranges, lays out their slots and writes the set's rows, the set's indirect entry gathers the coded planes' bytes, k_planes_merge_indirect
+// derives its tasks from what the cut left (hsrans_planes_gather_indirect.hip).  No lock, no task buffer, no allocation: kernels and
+// nothing else.
+// ---------------------------------------------------------------------------------------------------------------
+namespace
+{
+static_assert(sizeof(PlanesRange) == sizeof(hsrans_range) && sizeof(PlanesSetRow) == sizeof(hsrans_member_range), "the device's view of the ranges and rows");
+
+// the regions' distance, host-known: up256(max_elements + 30 max_count); false where hsrans_planes_gather_workspace_bytes gives 0 or the
+// sum reaches 2^48 (beyond any device's memory; below it no sum of slots in k_planes_cut can wrap)
+bool indirect_stride(uint32_t W, uint32_t max_count, uint64_t max_elements, size_t *stride)
+{
+  const uint64_t bytes = max_elements + 30 * (uint64_t)max_count;
+  if (hsrans_planes_gather_workspace_bytes(W, max_count, max_elements) == 0 || bytes >= ((uint64_t)1 << 48))
+    return false;
+  *stride = up256((size_t)bytes);
+  return true;
+}
+
+// What one indirect call launches, from what the host knows: the entry and hsrans_planes_gather_indirect_info both go through here.
+struct IndirectShape
+{
+  uint32_t coded, set_rows, merge_grid, set_launches, launches;
+};
+bool indirect_shape(const hsrans_planes_gather *pg, uint32_t max_count, size_t stride, IndirectShape *shape)
+{
+  const uint32_t W = pg->planes->desc.elem_size;
+  *shape = IndirectShape{};
+  shape->coded = (uint32_t)pg->planes->coded.size();
+  shape->set_rows = max_count * shape->coded; // (max_count * W < 2^31)
+  if (max_count == 0)
+    return true;
+  shape->merge_grid = planes_merge_indirect_grid(pg->ctx->geom.num_cus, W, max_count, stride);
+  if (pg->set != nullptr)
+  {
+    hsrans_gather_set_info_t si{};
+    if (hsrans_gather_set_indirect_info(pg->set, shape->set_rows, W * stride, &si) != HSRANS_OK)
+      return false;
+    shape->set_launches = si.launches + 1; // (+ the set's cut)
+  }
+  shape->launches = shape->set_launches + 2; // (+ k_planes_cut and the merge)
+  return true;
+}
+} // namespace
+
+extern "C" size_t hsrans_planes_gather_indirect_workspace_bytes(uint32_t elem_size, uint32_t max_count)
+{
+  if (!width_ok(elem_size) || (uint64_t)max_count * elem_size >= 0x80000000u)
+    return 0;
+  const size_t set_bytes = hsrans_gather_batch_workspace_bytes(elem_size, max_count * elem_size); // (sized for all planes coded: it needs no object)
+  return set_bytes == 0 ? 0 : planes_cut_ws(elem_size, max_count).set + up256(set_bytes);
+}
+
+extern "C" int hsrans_planes_gather_indirect_info(const hsrans_planes_gather *pg, uint32_t max_count, uint64_t max_elements, size_t out_capacity,
+                                                  hsrans_planes_gather_indirect_info_t *info)
+try
+{
+  if (pg == nullptr || info == nullptr)
+    return HSRANS_E_ARG;
+  const uint32_t W = pg->planes->desc.elem_size;
+  size_t stride = 0;
+  IndirectShape shape{};
+  if (hsrans_planes_gather_indirect_workspace_bytes(W, max_count) == 0 || !indirect_stride(W, max_count, max_elements, &stride) || !indirect_shape(pg, max_count, stride, &shape))
+    return HSRANS_E_ARG;
+  (void)out_capacity; // (it bounds the destinations on the device; no launch is shaped by it)
+  *info = hsrans_planes_gather_indirect_info_t{shape.coded, W - shape.coded, shape.set_rows, shape.merge_grid, shape.launches, shape.set_launches};
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather_indirect(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count, uint32_t max_count,
+                                                           uint64_t max_elements, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
+                                                           size_t workspace_bytes, void *hip_stream)
+try
+{
+  if (ctx == nullptr || pg == nullptr || pg->ctx != ctx || d_ranges == nullptr || d_workspace == nullptr || !aligned16(d_out) || !aligned16(d_work))
+    return HSRANS_E_ARG;
+  if (((uintptr_t)d_ranges & 7) != 0 || ((uintptr_t)d_count & 3) != 0 || ((uintptr_t)d_workspace & 255) != 0)
+    return HSRANS_E_ARG;
+  const hsrans_planes &planes = *pg->planes;
+  const hsrans_planes_desc &desc = planes.desc;
+  const uint32_t W = desc.elem_size;
+  const size_t need_ws = hsrans_planes_gather_indirect_workspace_bytes(W, max_count), need_work = hsrans_planes_gather_workspace_bytes(W, max_count, max_elements);
+  size_t stride = 0;
+  if (need_ws == 0 || need_work == 0 || workspace_bytes < need_ws || work_bytes < need_work || !indirect_stride(W, max_count, max_elements, &stride))
+    return HSRANS_E_ARG;
+  {
+    std::vector<Span> spans{span_of(pg->d_frame, pg->frame_length, false), span_of(d_ranges, (size_t)max_count * sizeof(hsrans_range), false),
+                            span_of(d_out, out_capacity, true),            span_of(d_work, work_bytes, true),
+                            span_of(d_workspace, workspace_bytes, true)};
+    if (d_count != nullptr)
+      spans.push_back(span_of(d_count, sizeof(uint32_t), false));
+    if (!spans_disjoint(spans))
+      return HSRANS_E_ARG;
+  }
+  if (max_count == 0)
+    return HSRANS_OK;
+  IndirectShape shape{};
+  if (!indirect_shape(pg, max_count, stride, &shape))
+    return HSRANS_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return HSRANS_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+
+  // ---- the cut: slots, task prefix and the set's rows into the control workspace ----
+  const PlanesCutWs ws = planes_cut_ws(W, max_count);
+  uint8_t *const control = (uint8_t *)d_workspace;
+  PlanesCutParams cp{};
+  cp.ranges = (const PlanesRange *)d_ranges;
+  cp.count = d_count;
+  cp.max_count = max_count;
+  cp.coded = shape.coded;
+  for (uint32_t k = 0; k < shape.coded; k++)
+    cp.coded_planes |= planes.coded[k] << (4 * k);
+  cp.elements = desc.elements;
+  cp.out_elements = out_capacity / W;
+  cp.stride = stride;
+  cp.header = (uint32_t *)control;
+  cp.first_task = (uint32_t *)(control + ws.first_task);
+  cp.base = (uint64_t *)(control + ws.base);
+  cp.rows = (PlanesSetRow *)(control + ws.rows);
+  cp.status = pg->d_refused;
+  if (launch_planes_cut(cp, s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+
+  // ---- the coded planes' bytes into their regions, through the set's public entry as the host-ranges call goes through the batch entry ----
+  if (pg->set != nullptr)
+  {
+    const int rc = hsrans_decode_device_gather_batch_indirect(ctx, pg->set, (const hsrans_member_range *)cp.rows, cp.header + kPlanesWsRows, shape.set_rows, d_work, W * stride,
+                                                              control + ws.set, workspace_bytes - ws.set, hip_stream);
+    if (rc != HSRANS_OK)
+      return rc;
+  }
+
+  // ---- the merge behind it ----
+  PlanePtrs src{};
+  uint32_t work_mask = 0;
+  for (uint32_t p = 0; p < W; p++)
+  {
+    const bool is_stored = (desc.stored_mask >> p) & 1;
+    src.p[p] = is_stored ? (uint8_t *)pg->d_frame + desc.offset[p] : (uint8_t *)d_work + p * stride;
+    work_mask |= is_stored ? 0 : 1u << p;
+  }
+  if (launch_planes_merge_indirect(W, src, work_mask, cp.ranges, cp.header, cp.first_task, cp.base, shape.merge_grid, d_out, s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_gather_refused(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream)
+try
+{
+  if (ctx == nullptr || pg == nullptr || pg->ctx != ctx)
+    return HSRANS_E_ARG;
+  uint32_t status = 0xFFFFFFFF;
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMemcpyAsync(&status, pg->d_refused, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  if (status != 0)
+  {
+    if (hipMemsetAsync(pg->d_refused, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return HSRANS_E_HIP;
+    return HSRANS_E_DEVICE;
+  }
+  // (the set's own word: the planes cut has passed every row the set sees, so this should never fire; it is reported if it does)
+  return pg->set != nullptr ? hsrans_gather_set_refused(ctx, pg->set, hip_stream) : HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
 }

@@ -1,12 +1,14 @@
 // hsrans_planes.h — the streaming kernels of the byte-plane layer: elements of W bytes split into W byte planes and planes interleaved back
-// into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip).  plane[p][i] = elements[i * W + p];
-// W is 2, 4 or 8.
+// into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
+// hsrans_planes_gather_indirect.hip).  plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "hsrans_carve.h"
 
 namespace hsrans
 {
@@ -38,6 +40,58 @@ struct PlanesGatherTask
 // bit p of work_mask is set, else the stored plane; every pointer 16-byte aligned (hipErrorInvalidValue otherwise)
 hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, void *out,
                                       hipStream_t stream);
+
+// ---- the same for ranges in device memory (hsrans_decode_device_planes_gather_indirect): k_planes_cut, the set's indirect gather, then
+// k_planes_merge_indirect (hsrans_planes_gather_indirect.hip) ----
+struct PlanesRange // (hsrans_range: offset, length, dst_offset, in elements)
+{
+  uint64_t offset, length, dst_offset;
+};
+struct PlanesSetRow // (hsrans_member_range: a row of the set's gather)
+{
+  uint64_t offset, length, dst_offset;
+  uint32_t member, reserved;
+};
+// The control workspace, in bytes from its start: a header of uint32 words — [kPlanesWsTotal] the merge's tasks, 0 where the call was refused;
+// [kPlanesWsCount] the ranges in use; [kPlanesWsRows] the rows of the set's gather (its count word), 0 where refused — then
+// first_task[0 .. max_count] (uint32, the exclusive prefix of the ranges' task counts and their total), base[max_count] (uint64, B_r),
+// rows[max_count * elem_size] (PlanesSetRow; the first count * coded are in use) and, from `set` on, the workspace of the set's own call.
+constexpr uint32_t kPlanesWsTotal = 0, kPlanesWsCount = 1, kPlanesWsRows = 2;
+struct PlanesCutWs
+{
+  size_t first_task, base, rows, set;
+};
+inline PlanesCutWs planes_cut_ws(uint32_t W, uint32_t max_count) // (host: the kernels get pointers)
+{
+  Carve c;
+  PlanesCutWs ws;
+  c.take(256);
+  ws.first_task = c.take(((size_t)max_count + 1) * 4);
+  ws.base = c.take((size_t)max_count * 8);
+  ws.rows = c.take((size_t)max_count * W * sizeof(PlanesSetRow));
+  ws.set = c.close();
+  return ws;
+}
+struct PlanesCutParams
+{
+  const PlanesRange *ranges; // device
+  const uint32_t *count;     // device, or null: max_count
+  uint32_t max_count, coded; // coded planes, the set's members in order: member k is plane (coded_planes >> 4 k) & 15
+  uint32_t coded_planes;
+  uint64_t elements, out_elements; // the tensor's elements; the output's (out_capacity / elem_size)
+  uint64_t stride;                 // the workspace regions' distance: no sum of slots may exceed it
+  uint32_t *header, *first_task;   // the control workspace's parts
+  uint64_t *base;
+  PlanesSetRow *rows;
+  uint32_t *status; // the gather object's word: kStatusBadRange where the call is refused
+};
+// the workgroups of the merge: the most tasks the call can have, max_count + stride / 4096 (a range's tasks <= its slot / 4096 + 1, and the
+// slots fit in stride), capped at the workgroups of 256 lanes the device holds at once; k_planes_merge_indirect strides over the tasks
+uint32_t planes_merge_indirect_grid(uint32_t num_cus, uint32_t W, uint32_t max_count, uint64_t stride);
+// asynchronous on `stream`, one kernel each, nothing else (capturable); hipErrorInvalidValue for what launch_planes_merge_ranges refuses
+hipError_t launch_planes_cut(const PlanesCutParams &cp, hipStream_t stream);
+hipError_t launch_planes_merge_indirect(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesRange *d_ranges, const uint32_t *d_header,
+                                        const uint32_t *d_first_task, const uint64_t *d_base, uint32_t grid, void *out, hipStream_t stream);
 
 } // namespace hsrans
 

@@ -937,6 +937,72 @@ typedef struct hsrans_planes_gather_task
   uint32_t lo, hi;
 } hsrans_planes_gather_task; /* 32 bytes */
 size_t hsrans_planes_gather_tasks(const hsrans_range *ranges, uint32_t count, uint64_t elements, hsrans_planes_gather_task *out, size_t capacity);
+/* ------------------------------------------------------------------------------------------------------------
+ * The same for ranges that are in DEVICE memory — a router's choice, a page table, a sampler — with no host round trip:
+ * n = d_count ? *d_count : max_count, and for the ranges d_ranges[0 .. n) d_out receives, byte for byte, what
+ * hsrans_decode_device_planes_gather writes for the same ranges in host memory; no other byte of d_out is written.
+ *   - asynchronous on hip_stream: kernel launches and nothing else — no allocation, no synchronisation, no lock, no host
+ *     read of device memory, no use of the context's task buffer; the last call's part of hsrans_planes_gather_info is not
+ *     written.  The call can be captured into a graph: one line of kernels on one stream, no parallel branches.
+ *   - d_ranges and *d_count are read when the launches RUN: a replayed graph gathers whatever they hold then and inherits
+ *     nothing from the replay before it (every word the later launches read is written by every call).  Rows of
+ *     d_ranges from n on are never read.
+ *   - launches, in order: one cut (one workgroup: it checks the ranges, lays out their slots, counts the merge's tasks and
+ *     writes the count x coded rows of the set's gather); where the frame has coded planes,
+ *     hsrans_decode_device_gather_batch_indirect on the object's set, through that public entry, with those rows;
+ *     one merge launch that finds each task's range in the prefix the cut left and derives the task as
+ *     hsrans_planes_gather_tasks does.  With every plane stored: two kernels.  The merge's grid cannot depend on the
+ *     ranges: it is the most tasks the call can have, max_count + stride / 4096, capped at the workgroups the device
+ *     holds at once, and the workgroups stride over the tasks, so any total finishes.
+ *   - d_work, the data workspace: the ranges cannot decide the layout, so the regions lie
+ *     stride = up256(max_elements + 30 * max_count) apart, region p at d_work + p * stride, and work_bytes must be
+ *     hsrans_planes_gather_workspace_bytes(elem_size, max_count, max_elements).  Inside a region the layout is the host
+ *     call's (slot [B_r, B_r + up16(phase + length)), the byte of plane p of element offset + i at
+ *     region p + B_r + phase + i); slot bytes outside [phase, phase + length) and the regions of stored planes are never
+ *     written.  max_elements: the most elements the ranges fetch in all.
+ *   - d_workspace, the control workspace: hsrans_planes_gather_indirect_workspace_bytes(elem_size, max_count) bytes,
+ *     256-byte aligned, contents irrelevant; it belongs to one call in flight (calls with different workspace pairs on
+ *     one object are independent of each other whatever streams they are on).  It holds a header, the tasks' prefix
+ *     first_task[0 .. max_count], B_r per range, the max_count x elem_size rows of hsrans_member_range for the set with
+ *     their count word, and behind them hsrans_gather_batch_workspace_bytes(elem_size, max_count x elem_size) bytes
+ *     for the set's own call.
+ * What only the device can see is checked there, all or nothing: *d_count > max_count, a range beyond the descriptor's
+ * elements, (dst_offset + length) * elem_size beyond out_capacity, any 64-bit overflow in these sums, a sum of slots
+ * above stride, a merge task total of 2^31 or more.  Then the call moves NOTHING — not one byte of d_out or d_work is
+ * written — and sets bit 8 of a status word the gather object owns (no plan's word is touched):
+ * hsrans_planes_gather_refused synchronises hip_stream, returns HSRANS_E_DEVICE once and clears the word; otherwise it
+ * returns what hsrans_gather_set_refused returns for the object's set (whose word should never fire once the cut has
+ * passed the rows; HSRANS_OK when there is no set).  A malformed histogram still reaches only its plane's plan word
+ * (hsrans_planes_gather_status).
+ * Returns HSRANS_E_ARG, nothing queued: a null handle or pointer (d_count may be NULL); a gather object of another
+ *   context; d_out or d_work not 16-byte, d_ranges not 8-byte, d_count not 4-byte or d_workspace not 256-byte aligned;
+ *   workspace_bytes or work_bytes below the two size functions, either of them returning 0, or
+ *   max_elements + 30 * max_count at or above 2^48; any intersection in which a written span takes part among the frame,
+ *   d_ranges[0 .. max_count), d_count (read) and d_out over out_capacity, d_work over work_bytes, d_workspace (written).
+ * HSRANS_OK with nothing queued: max_count == 0.
+ * hsrans_planes_gather_indirect_workspace_bytes: a pure function, sized for all planes coded (it needs no object); > 0
+ *   and a multiple of 256 for elem_size 2, 4 or 8 with max_count * elem_size < 2^31, non-decreasing in max_count; 0
+ *   otherwise.
+ * hsrans_planes_gather_indirect_info: a pure function of the object, max_count and max_elements (no device call), through
+ *   the shape function the entry uses.  HSRANS_E_ARG where the entry would refuse these sizes.
+ * Cost: README and DESIGN 5b (two single-workgroup cuts stand in a line in front of the gather).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct hsrans_planes_gather_indirect_info_t
+{
+  uint32_t coded, stored; /* planes */
+  uint32_t max_rows;      /* of the set's gather: max_count x coded */
+  uint32_t merge_grid;    /* workgroups of the merge launch */
+  uint32_t launches;      /* all kernels of one call: the cut, the set's, the merge (0: max_count == 0) */
+  uint32_t set_launches;  /* what hsrans_gather_set_indirect_info reports + the set's cut (0: every plane stored) */
+} hsrans_planes_gather_indirect_info_t;
+size_t hsrans_planes_gather_indirect_workspace_bytes(uint32_t elem_size, uint32_t max_count);
+int hsrans_decode_device_planes_gather_indirect(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges /* DEVICE, 8-byte aligned, in elements */,
+                                                const uint32_t *d_count /* DEVICE, or NULL = max_count */, uint32_t max_count, uint64_t max_elements, void *d_out,
+                                                size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace /* DEVICE, 256-byte aligned */,
+                                                size_t workspace_bytes, void *hip_stream);
+int hsrans_planes_gather_refused(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream);
+int hsrans_planes_gather_indirect_info(const hsrans_planes_gather *pg, uint32_t max_count, uint64_t max_elements, size_t out_capacity,
+                                       hsrans_planes_gather_indirect_info_t *info);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

@@ -9,426 +9,16 @@ Mirrors the reference's codec interface (src/main.cpp:146-155): ``encode(bytes) 
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 import torch  # first: pins the HIP runtime (libamdhip64.so.7) this process uses before our library is loaded
 
-RAW, BLOCK, MT = 0, 1, 2
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_sz, _vp, _i, _u32 = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32
-
-
-class HsransError(RuntimeError):
-    pass
-
-
-class Hist(ctypes.Structure):
-    """reference hist_t (src/hist.h:16-20)"""
-    _fields_ = [("symbolCount", ctypes.c_uint16 * 256), ("cumul", ctypes.c_uint16 * 256)]
-
-
-class EncodeOpts(ctypes.Structure):
-    _fields_ = [("block_size", _u32), ("index_interval", _u32), ("plan_out", _vp), ("plan_capacity", _sz), ("plan_size", _sz), ("flags", _u32),
-                ("reserved", _u32), ("index_groups", _vp), ("n_index_groups", _sz)]
-
-
-class EncodeMember(ctypes.Structure):
-    """hsrans_encode_member: one stream of hsrans_encode_device_batch"""
-    _fields_ = [("container", _i), ("states", _i), ("bits", _u32), ("block_size", _u32), ("d_in", _vp), ("length", _sz), ("d_out", _vp),
-                ("out_capacity", _sz), ("hist", _vp), ("index_interval", _u32), ("index_groups", _vp), ("n_index_groups", _sz), ("stream_length", _sz)]
-
-
-class EncodeBatchStats(ctypes.Structure):
-    _fields_ = [(n, _u32) for n in ("launches", "raw_members", "mt_members", "mt_blocks")]
-
-
-class EncodeExMember(ctypes.Structure):
-    """hsrans_encode_ex_member: one stream of hsrans_encode_device_ex_batch"""
-    _fields_ = [("container", _i), ("states", _i), ("bits", _u32), ("d_in", _vp), ("length", _sz), ("d_out", _vp), ("out_capacity", _sz),
-                ("opts", ctypes.POINTER(EncodeOpts)), ("stream_length", _sz), ("rc", _i)]
-
-
-class EncodeExBatchStats(ctypes.Structure):
-    _fields_ = ([(n, _u32) for n in ("launches", "block_members", "mt_members", "units", "blocks")] +
-                [(n, ctypes.c_double) for n in ("summaries_us", "walk_us", "chain_us", "plans_us")])
-
-
-class IndexingMember(ctypes.Structure):
-    """hsrans_indexing_member: one stream of hsrans_decode_device_indexing_batch"""
-    _fields_ = [("dplan", _vp), ("d_stream", _vp), ("stream_length", _sz), ("d_out", _vp), ("out_capacity", _sz), ("index_interval", _u32), ("rc", _i),
-                ("indexed", _vp)]
-
-
-class IndexingBatchStats(ctypes.Structure):
-    _fields_ = [(n, _u32) for n in ("launches", "walk_members", "mt_members", "tasks")]
-
-
-class Calibration(ctypes.Structure):
-    _fields_ = [("class_weights", _u32 * 8), ("class_finish_us_last_iteration", ctypes.c_double * 8), ("last_wave_us_before", ctypes.c_double),
-                ("last_wave_us_after", ctypes.c_double), ("class_spread_us_before", ctypes.c_double), ("class_spread_us_after", ctypes.c_double),
-                ("iterations", _u32), ("reserved", _u32), ("bytes", ctypes.c_uint64)]
-
-
-class LaunchInfo(ctypes.Structure):
-    _fields_ = [(n, _u32) for n in ("grid", "block", "lds_bytes", "waves_per_block", "chains", "shared_table", "walk", "two_level", "table_mode", "chains_per_wave")] + \
-               [("class_weights", _u32 * 8), ("dynamic_groups", _u32), ("spread", _u32)]
-
-
-class PlanKind(ctypes.Structure):
-    _fields_ = [(n, _u32) for n in ("container", "states", "bits", "flags")] + [("decoded_len", ctypes.c_uint64)] + \
-               [(n, _u32) for n in ("n_chains", "n_pieces", "shared_hist", "interval")]
-
-
-class LaunchFacts(ctypes.Structure):
-    _fields_ = [(n, _u32) for n in ("persistent", "table_mode", "dual", "n_groups", "groups_lean", "spread_min_block", "tickets", "index_pass", "single_valid",
-                                    "single_ring_entries", "calibrating", "parts", "n_parts", "dealt")]
-
-
-class BatchInfo(ctypes.Structure):
-    _fields_ = [(n, _u32) for n in ("members", "launches", "direct_members", "solo_members", "grouped_members", "reserved", "grid", "block", "lds_bytes")] + \
-               [("class_weights", _u32 * 8), ("imbalance", ctypes.c_double)]
-
-
-class QueueStats(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_uint64) for n in ("submitted", "flushes", "launches", "batches_made", "batches_reused", "retargeted")]
-
-
-class Shard(ctypes.Structure):
-    _fields_ = [("first_chain", _u32), ("chain_count", _u32), ("out_begin", ctypes.c_uint64), ("out_end", ctypes.c_uint64)]
-
-
-class ShardedInfo(ctypes.Structure):
-    _fields_ = [("world", _u32), ("rank", _u32), ("parts", _u32), ("root", ctypes.c_int32), ("window_begin", ctypes.c_uint64), ("window_end", ctypes.c_uint64),
-                ("out_base", ctypes.c_uint64), ("out_length", ctypes.c_uint64), ("decoded_length", ctypes.c_uint64), ("stream_length", ctypes.c_uint64),
-                ("one_launch", _u32), ("reserved", _u32)]
-
-
-class Range(ctypes.Structure):  # hsrans_range
-    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64)]
-
-
-class GatherTask(ctypes.Structure):  # hsrans_gather_task
-    _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("dst_delta", ctypes.c_int64)]
-
-
-class MemberRange(ctypes.Structure):  # hsrans_member_range
-    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("member", _u32), ("reserved", _u32)]
-
-
-class GatherMember(ctypes.Structure):  # hsrans_gather_member
-    _fields_ = [("decoded_len", ctypes.c_uint64), ("n_chains", _u32), ("states", _u32), ("interval", _u32), ("kind", _u32)]
-
-
-class GatherBatchTask(ctypes.Structure):  # hsrans_gather_batch_task
-    _fields_ = [("begin", ctypes.c_uint64), ("end", ctypes.c_uint64), ("dst_delta", ctypes.c_int64), ("member", _u32), ("reserved", _u32)]
-
-
-class GatherSetInfo(ctypes.Structure):  # hsrans_gather_set_info_t
-    _fields_ = [("members", _u32), ("launches", _u32)] + \
-               [(n, _u32 * 6) for n in ("kind_members", "kind_tasks", "kind_entries", "kind_grid", "kind_waves", "kind_lds_bytes")]
-
-
-PLANES_MAX = 8
-PLANES_STORE_INCOMPRESSIBLE = 1
-
-
-class PlanesDesc(ctypes.Structure):  # hsrans_planes_desc
-    _fields_ = [(n, _u32) for n in ("elem_size", "states", "bits", "block_size", "index_interval", "stored_mask")] + \
-               [("elements", ctypes.c_uint64), ("offset", ctypes.c_uint64 * PLANES_MAX), ("length", ctypes.c_uint64 * PLANES_MAX), ("frame_length", ctypes.c_uint64)]
-
-
-class PlanesInfo(ctypes.Structure):  # hsrans_planes_info_t
-    _fields_ = [(n, _u32) for n in ("coded", "stored", "launches")]
-
-
-class PlanesGatherInfo(ctypes.Structure):  # hsrans_planes_gather_info_t
-    _fields_ = [(n, _u32) for n in ("coded", "stored", "rows", "merge_tasks", "launches")]
-
-
-class PlanesGatherIndirectInfo(ctypes.Structure):  # hsrans_planes_gather_indirect_info_t
-    _fields_ = [(n, _u32) for n in ("coded", "stored", "max_rows", "merge_grid", "launches", "set_launches")]
-
-
-class PlanesGatherTask(ctypes.Structure):  # hsrans_planes_gather_task
-    _fields_ = [("src", ctypes.c_uint64), ("work_pos", ctypes.c_uint64), ("dst_delta", ctypes.c_int64), ("lo", _u32), ("hi", _u32)]
-
-
-COMM_ID_BYTES = 128
-SHARD_DECODE_ONLY, SHARD_DECODE_AND_EXCHANGE, SHARD_EXCHANGE_ONLY = 0, 1, 2
-
-
-def lib_path() -> str:
-    # HSRANS_LIB: A/B a differently built libhsrans_hip.so in one process environment (kernel tuning only)
-    if os.environ.get("HSRANS_LIB"):
-        return os.environ["HSRANS_LIB"]
-    if os.environ.get("HSRANS_DEBUG_STAMPS"):  # the per-wave stamps only exist in the diagnostic build (make -C csrc stamps)
-        stamps = os.path.join(_HERE, "lib", "libhsrans_hip_stamps.so")
-        if not os.path.exists(stamps):
-            raise HsransError("HSRANS_DEBUG_STAMPS needs the diagnostic library: make -C hypersonic_rans_amd/csrc stamps")
-        main = os.path.join(_HERE, "lib", "libhsrans_hip.so")
-        # (`make` alone does not rebuild it: numbers from a diagnostic library older than the product one are numbers of old code)
-        if os.path.exists(main) and os.path.getmtime(stamps) + 1 < os.path.getmtime(main):
-            raise HsransError("libhsrans_hip_stamps.so is older than libhsrans_hip.so: make -C hypersonic_rans_amd/csrc all stamps")
-        return stamps
-    return os.path.join(_HERE, "lib", "libhsrans_hip.so")
-
-
-_LIB = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Loads lib/libhsrans_hip.so.  Fails loudly when it has not been built (python -c 'import __graft_entry__ as g; g.build()')."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = lib_path()
-    if not os.path.exists(path):
-        raise ImportError(f"{path} is missing: build it with `make -C {os.path.join(_HERE, 'csrc')}` (there is no fallback implementation)")
-    L = ctypes.CDLL(path)
-    L.hsrans_version.restype = ctypes.c_char_p
-    L.hsrans_capacity.restype = _sz
-    L.hsrans_capacity.argtypes = [_i, _i, _sz]
-    L.hsrans_make_hist.restype = None
-    L.hsrans_make_hist.argtypes = [ctypes.POINTER(Hist), _vp, _sz, _u32]
-    L.hsrans_encode.restype = _sz
-    L.hsrans_encode.argtypes = [_i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(Hist)]
-    L.hsrans_encode_ex.restype = _sz
-    L.hsrans_encode_ex.argtypes = [_i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(Hist), ctypes.POINTER(EncodeOpts)]
-    L.hsrans_plan_capacity.restype = _sz
-    L.hsrans_plan_capacity.argtypes = [_i, _i, _sz, _u32, _u32]
-    L.hsrans_plan_build.restype = _sz
-    L.hsrans_plan_build.argtypes = [_i, _i, _u32, _vp, _sz, _sz, _vp, _sz]
-    L.hsrans_plan_chain_count.restype = _u32
-    L.hsrans_plan_chain_count.argtypes = [_vp, _sz]
-    L.hsrans_plan_decoded_length.restype = ctypes.c_uint64
-    L.hsrans_plan_decoded_length.argtypes = [_vp, _sz]
-    L.hsrans_plan_slice.restype = _sz
-    L.hsrans_plan_slice.argtypes = [_vp, _sz, _u32, _u32, _vp, _sz]
-    L.hsrans_plan_stream_ranges.restype = _i
-    L.hsrans_plan_stream_ranges.argtypes = [_vp, _sz, _u32, _u32, ctypes.POINTER(ctypes.c_uint64)]
-    L.hsrans_plan_chain_range.restype = _i
-    L.hsrans_plan_chain_range.argtypes = [_vp, _sz, _u32, _u32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-    L.hsrans_cpu_level.restype = _i
-    L.hsrans_decode_cpu.restype = _sz
-    L.hsrans_decode_cpu.argtypes = [_i, _u32, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]
-    L.hsrans_index_build_host.restype = _sz
-    L.hsrans_index_build_host.argtypes = [_i, _u32, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]
-    L.hsrans_ctx_create.restype = _i
-    L.hsrans_ctx_create.argtypes = [_i, ctypes.POINTER(_vp)]
-    L.hsrans_ctx_destroy.restype = None
-    L.hsrans_ctx_destroy.argtypes = [_vp]
-    L.hsrans_ctx_host_index_chains.restype = _u32
-    L.hsrans_ctx_host_index_chains.argtypes = [_vp]
-    L.hsrans_ctx_device_name.restype = ctypes.c_char_p
-    L.hsrans_ctx_device_name.argtypes = [_vp]
-    L.hsrans_decode_host.restype = _sz
-    L.hsrans_decode_host.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]
-    L.hsrans_dplan_create.restype = _i
-    L.hsrans_dplan_create.argtypes = [_vp, _vp, _sz, ctypes.POINTER(_vp)]
-    L.hsrans_dplan_destroy.restype = None
-    L.hsrans_dplan_destroy.argtypes = [_vp]
-    L.hsrans_decode_device.restype = _i
-    L.hsrans_decode_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_decode_device_window.restype = _i
-    L.hsrans_decode_device_window.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp]
-    L.hsrans_decode_device_ranges.restype = _i
-    L.hsrans_decode_device_ranges.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp]
-    L.hsrans_decode_device_indexing.restype = _i
-    L.hsrans_decode_device_indexing.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _u32, _vp, ctypes.POINTER(_vp)]
-    L.hsrans_ctx_calibrate.restype = _i
-    L.hsrans_decode_device_indexing_batch.restype = _i
-    L.hsrans_decode_device_indexing_batch.argtypes = [_vp, ctypes.POINTER(IndexingMember), _u32, _vp, ctypes.POINTER(IndexingBatchStats)]
-    L.hsrans_ctx_calibrate.argtypes = [_vp, _u32, _u32, ctypes.POINTER(Calibration)]
-    L.hsrans_dplan_batch_create.restype = _i
-    L.hsrans_dplan_batch_create.argtypes = [_vp, _vp, _u32, ctypes.POINTER(_vp)]
-    L.hsrans_dplan_batch_destroy.restype = None
-    L.hsrans_dplan_batch_destroy.argtypes = [_vp]
-    L.hsrans_decode_device_batch.restype = _i
-    L.hsrans_decode_device_batch.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.hsrans_dplan_batch_status.restype = _i
-    L.hsrans_dplan_batch_status.argtypes = [_vp, _vp, _vp, _vp]
-    L.hsrans_dplan_batch_info.restype = _i
-    L.hsrans_dplan_batch_info.argtypes = [_vp, ctypes.POINTER(BatchInfo)]
-    L.hsrans_queue_create.restype = _i
-    L.hsrans_queue_create.argtypes = [_vp, _u32, ctypes.POINTER(_vp)]
-    L.hsrans_queue_destroy.restype = None
-    L.hsrans_queue_destroy.argtypes = [_vp]
-    L.hsrans_queue_submit.restype = _i
-    L.hsrans_queue_submit.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_queue_flush.restype = _i
-    L.hsrans_queue_flush.argtypes = [_vp, _vp]
-    L.hsrans_queue_pending.restype = _u32
-    L.hsrans_queue_pending.argtypes = [_vp]
-    L.hsrans_queue_stats.restype = _i
-    L.hsrans_queue_stats.argtypes = [_vp, ctypes.POINTER(QueueStats)]
-    L.hsrans_decode_device_gather.restype = _i
-    L.hsrans_decode_device_gather.argtypes = [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _sz, _vp]
-    L.hsrans_gather_workspace_bytes.restype = _sz
-    L.hsrans_gather_workspace_bytes.argtypes = [_u32]
-    L.hsrans_decode_device_gather_indirect.restype = _i
-    L.hsrans_decode_device_gather_indirect.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_gather_set_create.restype = _i
-    L.hsrans_gather_set_create.argtypes = [_vp, _vp, _vp, _vp, _u32, _vp]
-    L.hsrans_gather_set_destroy.restype = None
-    L.hsrans_gather_set_destroy.argtypes = [_vp]
-    L.hsrans_decode_device_gather_batch.restype = _i
-    L.hsrans_decode_device_gather_batch.argtypes = [_vp, _vp, _vp, _u32, _vp, _sz, _vp]
-    L.hsrans_gather_set_status.restype = _i
-    L.hsrans_gather_set_status.argtypes = [_vp, _vp, _vp, _vp]
-    L.hsrans_gather_set_info.restype = _i
-    L.hsrans_gather_set_info.argtypes = [_vp, _vp]
-    L.hsrans_gather_batch_workspace_bytes.restype = _sz
-    L.hsrans_gather_batch_workspace_bytes.argtypes = [_u32, _u32]
-    L.hsrans_decode_device_gather_batch_indirect.restype = _i
-    L.hsrans_decode_device_gather_batch_indirect.argtypes = [_vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_gather_set_refused.restype = _i
-    L.hsrans_gather_set_refused.argtypes = [_vp, _vp, _vp]
-    L.hsrans_gather_set_indirect_info.restype = _i
-    L.hsrans_gather_set_indirect_info.argtypes = [_vp, _u32, _sz, _vp]
-    L.hsrans_gather_batch_tasks.restype = _sz
-    L.hsrans_gather_batch_tasks.argtypes = [_vp, _u32, _vp, _u32, _u32, _u32, _vp, _sz]
-    L.hsrans_gather_segment.restype = ctypes.c_uint64
-    L.hsrans_gather_segment.argtypes = [ctypes.c_uint64, _u32, _u32, _u32]
-    L.hsrans_gather_tasks.restype = _sz
-    L.hsrans_gather_tasks.argtypes = [ctypes.c_uint64, _u32, _u32, _u32, _vp, _u32, _vp, _sz]
-    L.hsrans_launch_choice.restype = _i
-    L.hsrans_launch_choice.argtypes = [_vp, ctypes.POINTER(PlanKind), ctypes.POINTER(LaunchFacts), ctypes.POINTER(LaunchInfo), ctypes.c_char_p, ctypes.c_size_t]
-    L.hsrans_dealt_shares.restype = _i
-    L.hsrans_dealt_shares.argtypes = [_vp, _u32, _vp, _u32, _u32, ctypes.c_uint64, _vp, _vp]
-    L.hsrans_batch_deal.restype = ctypes.c_double
-    L.hsrans_batch_deal.argtypes = [_vp, _vp, _u32, _u32, _u32, _vp, _vp]
-    L.hsrans_dplan_batch_read_finish.restype = _sz
-    L.hsrans_dplan_batch_read_finish.argtypes = [_vp, _vp, _sz]
-    L.hsrans_ctx_calibrate_runs.restype = _i
-    L.hsrans_ctx_calibrate_runs.argtypes = [_vp, _u32, _u32, _u32, ctypes.POINTER(Calibration)]
-    L.hsrans_index_boundaries_batch.restype = _sz
-    L.hsrans_index_boundaries_batch.argtypes = [_vp, _i, _u32, _vp, _u32, _u32, _vp, _sz]
-    L.hsrans_comm_unique_id.restype = _i
-    L.hsrans_comm_unique_id.argtypes = [_vp]
-    L.hsrans_comm_create.restype = _i
-    L.hsrans_comm_create.argtypes = [_vp, _vp, _i, _i, ctypes.POINTER(_vp)]
-    L.hsrans_comm_destroy.restype = None
-    L.hsrans_comm_destroy.argtypes = [_vp]
-    L.hsrans_comm_rank.restype = _i
-    L.hsrans_comm_rank.argtypes = [_vp]
-    L.hsrans_comm_world.restype = _i
-    L.hsrans_comm_world.argtypes = [_vp]
-    L.hsrans_comm_rccl_version.restype = _i
-    L.hsrans_shard_layout.restype = _i
-    L.hsrans_shard_layout.argtypes = [_vp, _sz, _u32, _u32, _vp, _vp, _vp]
-    L.hsrans_sharded_create.restype = _i
-    L.hsrans_sharded_create.argtypes = [_vp, _vp, _vp, _sz, _u32, _vp, _i, ctypes.POINTER(_vp)]
-    L.hsrans_sharded_create_rank.restype = _i
-    L.hsrans_sharded_create_rank.argtypes = [_vp, _i, _i, _vp, _sz, _u32, _vp, _i, ctypes.POINTER(_vp)]
-    L.hsrans_sharded_destroy.restype = None
-    L.hsrans_sharded_destroy.argtypes = [_vp]
-    L.hsrans_sharded_info.restype = _i
-    L.hsrans_sharded_info.argtypes = [_vp, ctypes.POINTER(ShardedInfo), _vp, _sz]
-    L.hsrans_sharded_part_plan.restype = _vp
-    L.hsrans_sharded_part_plan.argtypes = [_vp, _u32]
-    L.hsrans_sharded_wait_part.restype = _i
-    L.hsrans_sharded_wait_part.argtypes = [_vp, _u32, _vp]
-    L.hsrans_sharded_whole_plan.restype = _vp
-    L.hsrans_sharded_whole_plan.argtypes = [_vp]
-    L.hsrans_decode_sharded.restype = _i
-    L.hsrans_decode_sharded.argtypes = [_vp, _vp, _vp, _i, _vp]
-    L.hsrans_sharded_status.restype = _i
-    L.hsrans_sharded_status.argtypes = [_vp, _vp]
-    L.hsrans_dplan_status.restype = _i
-    L.hsrans_dplan_status.argtypes = [_vp, _vp, _vp]
-    L.hsrans_dplan_launch_info.restype = _i
-    L.hsrans_dplan_launch_info.argtypes = [_vp, ctypes.POINTER(LaunchInfo)]
-    L.hsrans_dplan_create_from_device_stream.restype = _i
-    L.hsrans_dplan_create_from_device_stream.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _sz, _vp, ctypes.POINTER(_vp)]
-    L.hsrans_dplan_read_plan.restype = _sz
-    L.hsrans_dplan_read_plan.argtypes = [_vp, _vp, _sz]
-    L.hsrans_encode_device_raw.restype = _sz
-    L.hsrans_encode_device_raw.argtypes = [_vp, _i, _u32, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(_sz), _vp, ctypes.POINTER(_vp)]
-    L.hsrans_encode_device.restype = _sz
-    L.hsrans_encode_device.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _u32, _u32, _vp, ctypes.POINTER(_vp)]
-    L.hsrans_block_choices.restype = _sz
-    L.hsrans_block_choices.argtypes = [_i, _i, _u32, _vp, _sz, _u32, _vp, _sz]
-    L.hsrans_block_choices_device.restype = _sz
-    L.hsrans_block_choices_device.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz, _vp]
-    L.hsrans_encode_device_batch.restype = _i
-    L.hsrans_encode_device_batch.argtypes = [_vp, ctypes.POINTER(EncodeMember), _u32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(EncodeBatchStats)]
-    L.hsrans_encode_device_ex_batch.restype = _i
-    L.hsrans_encode_device_ex_batch.argtypes = [_vp, ctypes.POINTER(EncodeExMember), _u32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(EncodeExBatchStats)]
-    L.hsrans_encode_device_ex.restype = _sz
-    L.hsrans_encode_device_ex.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(Hist), ctypes.POINTER(EncodeOpts), _vp, ctypes.POINTER(_vp)]
-    L.hsrans_index_build.restype = _sz
-    L.hsrans_index_build.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz]
-    L.hsrans_index_build_at.restype = _sz
-    L.hsrans_index_build_at.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]
-    L.hsrans_index_boundaries.restype = _sz
-    L.hsrans_index_boundaries.argtypes = [_vp, _i, _u32, _sz, _vp, _sz]
-    L.hsrans_plan_thin.restype = _sz
-    L.hsrans_plan_thin.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz]
-    L.hsrans_plan_capacity_chains.restype = _sz
-    L.hsrans_plan_capacity_chains.argtypes = [_i, _i, _sz, _sz, _u32]
-    L.hsrans_hpipe_create.restype = _i
-    L.hsrans_hpipe_create.argtypes = [_vp, _vp, _sz, _u32, ctypes.POINTER(_vp)]
-    L.hsrans_hpipe_decode.restype = _sz
-    L.hsrans_hpipe_decode.argtypes = [_vp, _vp, _sz, _vp, _sz]
-    L.hsrans_hpipe_destroy.restype = None
-    L.hsrans_hpipe_destroy.argtypes = [_vp]
-    L.hsrans_decode_host_pipelined.restype = _sz
-    L.hsrans_decode_host_pipelined.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _u32]
-    L.hsrans_encode_host_pipelined.restype = _sz
-    L.hsrans_encode_host_pipelined.argtypes = [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, ctypes.POINTER(EncodeOpts), _u32]
-    L.hsrans_host_register.restype = _i
-    L.hsrans_host_register.argtypes = [_vp, _vp, _sz]
-    L.hsrans_host_unregister.restype = _i
-    L.hsrans_host_unregister.argtypes = [_vp, _vp]
-    L.hsrans_planes_capacity.restype = _sz
-    L.hsrans_planes_capacity.argtypes = [_u32, _i, _sz]
-    L.hsrans_planes_workspace_bytes.restype = _sz
-    L.hsrans_planes_workspace_bytes.argtypes = [_u32, _sz]
-    L.hsrans_planes_split.restype = _i
-    L.hsrans_planes_split.argtypes = [_u32, _vp, _sz, _vp]
-    L.hsrans_planes_merge.restype = _i
-    L.hsrans_planes_merge.argtypes = [_u32, _vp, _sz, _vp]
-    L.hsrans_planes_split_device.restype = _i
-    L.hsrans_planes_split_device.argtypes = [_vp, _u32, _vp, _sz, _vp, _vp]
-    L.hsrans_planes_merge_device.restype = _i
-    L.hsrans_planes_merge_device.argtypes = [_vp, _u32, _vp, _sz, _vp, _vp]
-    L.hsrans_encode_device_planes.restype = _sz
-    L.hsrans_encode_device_planes.argtypes = [_vp, _u32, _i, _u32, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, ctypes.POINTER(PlanesDesc), ctypes.POINTER(_vp)]
-    L.hsrans_planes_create.restype = _i
-    L.hsrans_planes_create.argtypes = [_vp, ctypes.POINTER(PlanesDesc), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]
-    L.hsrans_planes_destroy.restype = None
-    L.hsrans_planes_destroy.argtypes = [_vp]
-    L.hsrans_decode_device_planes.restype = _i
-    L.hsrans_decode_device_planes.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_planes_status.restype = _i
-    L.hsrans_planes_status.argtypes = [_vp, _vp, _vp, _vp]
-    L.hsrans_planes_info.restype = _i
-    L.hsrans_planes_info.argtypes = [_vp, ctypes.POINTER(PlanesInfo)]
-    L.hsrans_planes_gather_create.restype = _i
-    L.hsrans_planes_gather_create.argtypes = [_vp, _vp, _vp, _sz, ctypes.POINTER(_vp)]
-    L.hsrans_planes_gather_destroy.restype = None
-    L.hsrans_planes_gather_destroy.argtypes = [_vp]
-    L.hsrans_planes_gather_workspace_bytes.restype = _sz
-    L.hsrans_planes_gather_workspace_bytes.argtypes = [_u32, _u32, ctypes.c_uint64]
-    L.hsrans_decode_device_planes_gather.restype = _i
-    L.hsrans_decode_device_planes_gather.argtypes = [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_planes_gather_status.restype = _i
-    L.hsrans_planes_gather_status.argtypes = [_vp, _vp, _vp, _vp]
-    L.hsrans_planes_gather_info.restype = _i
-    L.hsrans_planes_gather_info.argtypes = [_vp, ctypes.POINTER(PlanesGatherInfo)]
-    L.hsrans_planes_gather_indirect_workspace_bytes.restype = _sz
-    L.hsrans_planes_gather_indirect_workspace_bytes.argtypes = [_u32, _u32]
-    L.hsrans_decode_device_planes_gather_indirect.restype = _i
-    L.hsrans_decode_device_planes_gather_indirect.argtypes = [_vp, _vp, _vp, _vp, _u32, ctypes.c_uint64, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
-    L.hsrans_planes_gather_refused.restype = _i
-    L.hsrans_planes_gather_refused.argtypes = [_vp, _vp, _vp]
-    L.hsrans_planes_gather_indirect_info.restype = _i
-    L.hsrans_planes_gather_indirect_info.argtypes = [_vp, _u32, ctypes.c_uint64, _sz, ctypes.POINTER(PlanesGatherIndirectInfo)]
-    L.hsrans_planes_gather_tasks.restype = _sz
-    L.hsrans_planes_gather_tasks.argtypes = [_vp, _u32, ctypes.c_uint64, _vp, _sz]
-    _LIB = L
-    return L
+from ._abi import (  # noqa: F401  (the structures, constants and loader are spelled api.<name> by the tests and tools)
+    BLOCK, COMM_ID_BYTES, ENC_INDEPENDENT_BLOCKS, MT, PLANES_MAX, PLANES_STORE_INCOMPRESSIBLE, RAW, SHARD_DECODE_AND_EXCHANGE, SHARD_DECODE_ONLY,
+    SHARD_EXCHANGE_ONLY, BatchInfo, Calibration, EncodeBatchStats, EncodeExBatchStats, EncodeExMember, EncodeMember, EncodeOpts, GatherBatchTask,
+    GatherMember, GatherSetInfo, GatherTask, Hist, HsransError, IndexingBatchStats, IndexingMember, LaunchFacts, LaunchInfo, MemberRange, PlanKind,
+    PlanesDesc, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherTask, PlanesInfo, QueueStats, Range, Shard, ShardedInfo, _sz, _vp, lib_path,
+    load_library)
 
 
 def _u8(a) -> np.ndarray:
@@ -438,6 +28,75 @@ def _u8(a) -> np.ndarray:
 
 def _p(a: np.ndarray):
     return a.ctypes.data_as(_vp)
+
+
+def _check(rc: int, what: str, suffix: str = ""):
+    """a C return code that is not HSRANS_OK raises HsransError("<what> failed with code <rc><suffix>") carrying it as ``.code``"""
+    if rc != 0:
+        raise HsransError(f"{what} failed with code {rc}{suffix}", code=rc)
+
+
+def _members_error(what: str, rc: int, failed, **got) -> HsransError:
+    """the error of a call over many members: names the first of ``failed`` (empty: none to name) and carries what the members got"""
+    err = HsransError(f"{what} failed with code {rc}" + (f": member {failed[0]} failed" if failed else ""), code=rc)
+    vars(err).update(got)
+    return err
+
+
+def _encode_member(entry: str, k: int, m, known) -> tuple:
+    """member k of a batch encoder as (container, states, bits, d_in, d_out, options dict); an option that is not ``known`` raises"""
+    o = dict(m[5]) if len(m) > 5 and m[5] is not None else {}
+    unknown = set(o) - set(known)
+    if unknown:
+        raise HsransError(f"{entry}: member {k}: unknown options {sorted(unknown)}")
+    return (*m[:5], o)
+
+
+def _torch_stream(stream, device=None):
+    return stream if stream is not None else torch.cuda.current_stream(device)
+
+
+def _stream(stream, device=None):
+    """the hipStream_t a C call takes: ``stream``, or torch's current stream on ``device`` (None: on the current device)"""
+    return _vp(_torch_stream(stream, device).cuda_stream)
+
+
+def _as_dict(s: ctypes.Structure) -> dict:
+    """the fields of a structure in their order: arrays as lists, scalars as they are"""
+    values = ((n, getattr(s, n)) for n, _ in s._fields_)
+    return {n: (list(v) if isinstance(v, ctypes.Array) else v) for n, v in values}
+
+
+def _handle_array(plans, size: int | None = None):
+    """the C array of the plans' handles (NULL for None), of ``size`` entries where that is more than the plans"""
+    handles = [None if d is None else (d.handle.value if isinstance(d.handle, _vp) else d.handle) for d in plans]
+    return (_vp * (len(handles) if size is None else size))(*handles)
+
+
+def _tensor_arrays(tensors, lengths=None):
+    """(data pointers, lengths) of a list of tensors as C arrays; a tensor's length is lengths[k] where given, else its numel()"""
+    K = len(tensors)
+    return (_vp * K)(*[t.data_ptr() for t in tensors]), (_sz * K)(*[(t.numel() if lengths is None else int(lengths[k])) for k, t in enumerate(tensors)])
+
+
+def _indirect_args(d_ranges, columns: int, count, max_count, workspace, workspace_bytes, device, stream):
+    """What the *_indirect calls check of their device-side ranges, and their workspace: returns (max_count, workspace) with max_count
+    defaulting to the rows of ``d_ranges`` and the workspace, where None, allocated on ``device`` under ``stream`` (``workspace_bytes``:
+    max_count -> bytes)."""
+    if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == columns and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
+        raise TypeError(f"d_ranges: a contiguous CUDA tensor (N, {columns}) of int64 or uint64")
+    if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
+        raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
+    if max_count is None:
+        max_count = d_ranges.shape[0]
+    if max_count > d_ranges.shape[0]:
+        raise ValueError("max_count is larger than d_ranges")
+    if workspace is None:
+        with torch.cuda.stream(_torch_stream(stream, device)):
+            workspace = torch.empty(workspace_bytes(max_count), dtype=torch.uint8, device=device)
+    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise TypeError("workspace: a contiguous CUDA uint8 tensor")
+    return max_count, workspace
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -462,9 +121,6 @@ def hist_from_counts(counts) -> Hist:
         h.cumul[k] = run & 0xFFFF
         run += int(counts[k])
     return h
-
-
-ENC_INDEPENDENT_BLOCKS = 1
 
 
 def index_boundaries(states: int, bits: int, decoded_size: int, ctx: "Context | None" = None) -> np.ndarray:
@@ -578,8 +234,9 @@ def plan_slice(plan, first: int, count: int) -> np.ndarray:
 def plan_chain_range(plan, first: int, count: int) -> tuple[int, int]:
     plan = _u8(plan)
     b, e = ctypes.c_uint64(), ctypes.c_uint64()
-    if load_library().hsrans_plan_chain_range(_p(plan), plan.size, first, count, ctypes.byref(b), ctypes.byref(e)) != 0:
-        raise HsransError("plan_chain_range failed")
+    rc = load_library().hsrans_plan_chain_range(_p(plan), plan.size, first, count, ctypes.byref(b), ctypes.byref(e))
+    if rc != 0:
+        raise HsransError("plan_chain_range failed", code=rc)
     return b.value, e.value
 
 
@@ -587,8 +244,9 @@ def plan_stream_ranges(plan, first: int, count: int) -> tuple[tuple[int, int], t
     """((head_begin, head_end), (body_begin, body_end)): the stream bytes chains [first, first+count) can read."""
     plan = _u8(plan)
     r = (ctypes.c_uint64 * 4)()
-    if load_library().hsrans_plan_stream_ranges(_p(plan), plan.size, first, count, r) != 0:
-        raise HsransError("plan_stream_ranges failed")
+    rc = load_library().hsrans_plan_stream_ranges(_p(plan), plan.size, first, count, r)
+    if rc != 0:
+        raise HsransError("plan_stream_ranges failed", code=rc)
     return (r[0], r[1]), (r[2], r[3])
 
 
@@ -658,7 +316,7 @@ def dealt_shares(block_begin, total_groups: int, ctx: "Context | None" = None, b
     begin, split = np.zeros(513, np.uint32), np.zeros(512, np.uint16)
     rc = load_library().hsrans_dealt_shares(ctx.handle if ctx is not None else None, bits, _p(bb), bb.size - 1, int(bb[-1]), int(total_groups), _p(begin), _p(split))
     if rc < 0:
-        raise HsransError("hsrans_dealt_shares: bad arguments")
+        raise HsransError("hsrans_dealt_shares: bad arguments", code=rc)
     return rc == 1, begin, split
 
 
@@ -674,8 +332,8 @@ def launch_choice(plan: dict, ctx: "Context | None" = None, **facts):
     if rc == 2:
         raise ValueError("hsrans_launch_choice: the launcher refuses these values")
     if rc != 0:
-        raise HsransError("hsrans_launch_choice: bad arguments")
-    return name.value.decode(), {n: (list(getattr(info, n)) if n == "class_weights" else getattr(info, n)) for n, _ in LaunchInfo._fields_}
+        raise HsransError("hsrans_launch_choice: bad arguments", code=rc)
+    return name.value.decode(), _as_dict(info)
 
 
 def index_boundaries_batch(states: int, bits: int, decoded_sizes, member: int, ctx: "Context | None" = None) -> np.ndarray:
@@ -695,9 +353,7 @@ def shard_layout(plan, world: int, parts: int = 1, weights=None):
     w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
     if w is not None and w.size != world:
         raise HsransError("shard_layout: one weight per rank")
-    rc = load_library().hsrans_shard_layout(_p(plan), plan.size, world, parts, None if w is None else _p(w), shards, _p(windows))
-    if rc != 0:
-        raise HsransError(f"hsrans_shard_layout failed with code {rc}")
+    _check(load_library().hsrans_shard_layout(_p(plan), plan.size, world, parts, None if w is None else _p(w), shards, _p(windows)), "hsrans_shard_layout")
     out = [[(int(shards[r * parts + k].first_chain), int(shards[r * parts + k].chain_count), int(shards[r * parts + k].out_begin), int(shards[r * parts + k].out_end))
             for k in range(parts)] for r in range(world)]
     return out, [(int(windows[2 * r]), int(windows[2 * r + 1])) for r in range(world)]
@@ -799,9 +455,7 @@ def planes_split(array) -> list:
     a = np.ascontiguousarray(array)
     planes = [np.empty(a.size, np.uint8) for _ in range(a.itemsize)]
     ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
-    rc = load_library().hsrans_planes_split(a.itemsize, a.ctypes.data if a.size else ptrs, a.size, ptrs)
-    if rc != 0:
-        raise HsransError(f"hsrans_planes_split failed with code {rc}")
+    _check(load_library().hsrans_planes_split(a.itemsize, a.ctypes.data if a.size else ptrs, a.size, ptrs), "hsrans_planes_split")
     return planes
 
 
@@ -812,9 +466,7 @@ def planes_merge(planes, itemsize: int) -> np.ndarray:
         raise HsransError("planes_merge: one plane per byte of an item, all of one length")
     out = np.empty(planes[0].size * itemsize, np.uint8)
     ptrs = (_vp * itemsize)(*[p.ctypes.data for p in planes])
-    rc = load_library().hsrans_planes_merge(itemsize, ptrs, planes[0].size, out.ctypes.data if out.size else ptrs)
-    if rc != 0:
-        raise HsransError(f"hsrans_planes_merge failed with code {rc}")
+    _check(load_library().hsrans_planes_merge(itemsize, ptrs, planes[0].size, out.ctypes.data if out.size else ptrs), "hsrans_planes_merge")
     return out
 
 
@@ -847,8 +499,31 @@ def planes_gather_tasks(ranges, elements: int, capacity: int | None = None) -> n
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU side
 # ---------------------------------------------------------------------------------------------------------------------
-class Batch:
+class _Handle:
+    """The owner of one C handle (``handle``, made by the library ``ctx.L``): ``_destroy`` names the C function that frees it.  close()
+    frees it once, however often it is called; an object with ``owned`` False frees nothing; __del__ closes and swallows every error."""
+    _destroy = ""
+    handle = None  # (until __init__ has one: a constructor that raised leaves nothing to free)
+    owned = True
+
+    def _library(self):
+        return self.ctx.L
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h and self.owned:
+            getattr(self._library(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Batch(_Handle):
     """hsrans_batch: K device plans decoded by one launch (Context.make_batch / Context.decode_device_batch)."""
+    _destroy = "hsrans_dplan_batch_destroy"
 
     def __init__(self, ctx: "Context", handle, dplans):
         self.ctx, self.handle, self.dplans = ctx, handle, list(dplans)  # (keeps the member plans alive)
@@ -856,27 +531,17 @@ class Batch:
     def info(self) -> dict:
         info = BatchInfo()
         load_library().hsrans_dplan_batch_info(self.handle, ctypes.byref(info))
-        return {n: (list(getattr(info, n)) if n == "class_weights" else getattr(info, n)) for n, _ in BatchInfo._fields_}
+        return _as_dict(info)
 
     def read_finish(self) -> np.ndarray:
         out = np.zeros(1 << 16, np.uint64)
         n = load_library().hsrans_dplan_batch_read_finish(self.handle, _p(out), out.size)
         return out[:n].copy()
 
-    def close(self):
-        if self.handle:
-            load_library().hsrans_dplan_batch_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Planes:
+class Planes(_Handle):
     """hsrans_planes: a frame's descriptor bound to its planes' device plans (Context.make_planes / Context.decode_device_planes)."""
+    _destroy = "hsrans_planes_destroy"
 
     def __init__(self, ctx: "Context", handle, desc: PlanesDesc, plans):
         self.ctx, self.handle, self.desc, self.plans = ctx, handle, desc, list(plans)  # (keeps the planes' plans alive)
@@ -884,22 +549,12 @@ class Planes:
     def info(self) -> dict:
         info = PlanesInfo()
         load_library().hsrans_planes_info(self.handle, ctypes.byref(info))
-        return {n: getattr(info, n) for n, _ in PlanesInfo._fields_}
-
-    def close(self):
-        if self.handle:
-            load_library().hsrans_planes_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _as_dict(info)
 
 
-class PlanesGather:
+class PlanesGather(_Handle):
     """hsrans_planes_gather: a Planes object bound to the frame it reads (Context.make_planes_gather / Context.decode_device_planes_gather)."""
+    _destroy = "hsrans_planes_gather_destroy"
 
     def __init__(self, ctx: "Context", handle, planes: Planes, d_frame):
         self.ctx, self.handle, self.planes, self.d_frame = ctx, handle, planes, d_frame  # (keeps the planes object and the frame alive)
@@ -908,32 +563,21 @@ class PlanesGather:
         """coded and stored planes, and of the last call: the gather's rows, the merge's tasks and the kernels launched"""
         info = PlanesGatherInfo()
         load_library().hsrans_planes_gather_info(self.handle, ctypes.byref(info))
-        return {n: getattr(info, n) for n, _ in PlanesGatherInfo._fields_}
+        return _as_dict(info)
 
     def indirect_info(self, max_count: int, max_elements: int, out_capacity: int) -> dict:
         """hsrans_planes_gather_indirect_info: what a decode_device_planes_gather_indirect of up to ``max_count`` ranges and ``max_elements``
         elements will launch — coded and stored planes, the set's rows at most, the merge's grid, all kernels of a call and the set's part
         of them.  No device call."""
         info = PlanesGatherIndirectInfo()
-        rc = load_library().hsrans_planes_gather_indirect_info(self.handle, max_count, max_elements, out_capacity, ctypes.byref(info))
-        if rc != 0:
-            raise HsransError(f"hsrans_planes_gather_indirect_info failed with code {rc}")
-        return {n: getattr(info, n) for n, _ in PlanesGatherIndirectInfo._fields_}
-
-    def close(self):
-        if self.handle:
-            load_library().hsrans_planes_gather_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _check(load_library().hsrans_planes_gather_indirect_info(self.handle, max_count, max_elements, out_capacity, ctypes.byref(info)),
+               "hsrans_planes_gather_indirect_info")
+        return _as_dict(info)
 
 
-class GatherSet:
+class GatherSet(_Handle):
     """hsrans_gather_set: K device plans bound to their compressed streams (Context.make_gather_set / Context.decode_device_gather_batch)."""
+    _destroy = "hsrans_gather_set_destroy"
 
     def __init__(self, ctx: "Context", handle, dplans, d_streams):
         self.ctx, self.handle, self.dplans, self.d_streams = ctx, handle, list(dplans), list(d_streams)  # (keeps the plans and the streams alive)
@@ -942,112 +586,70 @@ class GatherSet:
         """members, members per kind, and of the last gather: launches and per kind tasks, entries (tasks + padding), grid, waves, LDS bytes"""
         info = GatherSetInfo()
         load_library().hsrans_gather_set_info(self.handle, ctypes.byref(info))
-        return {n: (list(getattr(info, n)) if n.startswith("kind_") else getattr(info, n)) for n, _ in GatherSetInfo._fields_}
+        return _as_dict(info)
 
     def indirect_info(self, max_count: int, dst_capacity: int) -> dict:
         """hsrans_gather_set_indirect_info: what a decode_device_gather_batch_indirect of up to ``max_count`` ranges into ``dst_capacity``
         bytes will launch — members, members per kind, the launches behind the cut and per kind grid, waves and LDS bytes (tasks and
         entries are 0: only the device knows them).  Pure host arithmetic."""
         info = GatherSetInfo()
-        rc = load_library().hsrans_gather_set_indirect_info(self.handle, max_count, dst_capacity, ctypes.byref(info))
-        if rc != 0:
-            raise HsransError(f"hsrans_gather_set_indirect_info failed with code {rc}")
-        return {n: (list(getattr(info, n)) if n.startswith("kind_") else getattr(info, n)) for n, _ in GatherSetInfo._fields_}
-
-    def close(self):
-        if self.handle:
-            load_library().hsrans_gather_set_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _check(load_library().hsrans_gather_set_indirect_info(self.handle, max_count, dst_capacity, ctypes.byref(info)), "hsrans_gather_set_indirect_info")
+        return _as_dict(info)
 
 
-class DevicePlan:
+class DevicePlan(_Handle):
+    _destroy = "hsrans_dplan_destroy"
+
     def __init__(self, ctx: "Context", handle, owned: bool = True):
         self.ctx, self.handle, self.owned = ctx, handle, owned  # (owned False: a view of a plan another object destroys, e.g. a Sharded's sub-run)
 
     def launch_info(self) -> dict:
         info = LaunchInfo()
         load_library().hsrans_dplan_launch_info(self.handle, ctypes.byref(info))
-        return {n: (list(getattr(info, n)) if n == "class_weights" else getattr(info, n)) for n, _ in LaunchInfo._fields_}
-
-    def close(self):
-        if self.handle and self.owned:
-            load_library().hsrans_dplan_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _as_dict(info)
 
 
-class Comm:
+class Comm(_Handle):
     """hsrans_comm: this process's rank in a communicator over the GPUs of the node (RCCL, bound by the C library at run time)."""
+    _destroy = "hsrans_comm_destroy"
 
     def __init__(self, ctx: "Context", comm_id: bytes, rank: int, world: int):
         assert len(comm_id) == COMM_ID_BYTES
         self.ctx = ctx
         buf = (ctypes.c_uint8 * COMM_ID_BYTES).from_buffer_copy(comm_id)
         h = _vp()
-        rc = ctx.L.hsrans_comm_create(ctx.handle, buf, rank, world, ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_comm_create(rank {rank} of {world}) failed with code {rc}")
+        _check(ctx.L.hsrans_comm_create(ctx.handle, buf, rank, world, ctypes.byref(h)), f"hsrans_comm_create(rank {rank} of {world})")
         self.handle, self.rank, self.world = h, rank, world
 
     @staticmethod
     def unique_id() -> bytes:
         buf = (ctypes.c_uint8 * COMM_ID_BYTES)()
-        rc = load_library().hsrans_comm_unique_id(buf)
-        if rc != 0:
-            raise HsransError(f"hsrans_comm_unique_id failed with code {rc} (no RCCL could be bound?)")
+        _check(load_library().hsrans_comm_unique_id(buf), "hsrans_comm_unique_id", " (no RCCL could be bound?)")
         return bytes(buf)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.L.hsrans_comm_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Queue:
+class Queue(_Handle):
     """hsrans_queue: streams submitted one by one, decoded by ONE batch launch per flush (the dealing cached per shape)."""
+    _destroy = "hsrans_queue_destroy"
 
     def __init__(self, ctx: "Context", max_members: int = 32):
         self.ctx = ctx
         h = _vp()
-        rc = ctx.L.hsrans_queue_create(ctx.handle, max_members, ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_queue_create failed with code {rc}")
+        _check(ctx.L.hsrans_queue_create(ctx.handle, max_members, ctypes.byref(h)), "hsrans_queue_create")
         self.handle = h
         self._keep = []  # tensors and plans of the submissions still pending
 
     def submit(self, dplan: "DevicePlan", d_stream: torch.Tensor, d_out: torch.Tensor, stream_length: int | None = None, stream: torch.cuda.Stream | None = None):
-        s = stream if stream is not None else torch.cuda.current_stream(d_out.device)
-        rc = self.ctx.L.hsrans_queue_submit(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
-                                            d_out.data_ptr(), d_out.numel(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_queue_submit failed with code {rc}")
+        _check(self.ctx.L.hsrans_queue_submit(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                              d_out.data_ptr(), d_out.numel(), _stream(stream, d_out.device)), "hsrans_queue_submit")
         self._keep.append((dplan, d_stream, d_out))
         if self.pending() == 0:
             self._keep.clear()
 
     def flush(self, stream: torch.cuda.Stream | None = None):
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = self.ctx.L.hsrans_queue_flush(self.handle, ctypes.c_void_p(s.cuda_stream))
+        rc = self.ctx.L.hsrans_queue_flush(self.handle, _stream(stream))
         self._keep.clear()
-        if rc != 0:
-            raise HsransError(f"hsrans_queue_flush failed with code {rc}")
+        _check(rc, "hsrans_queue_flush")
 
     def pending(self) -> int:
         return int(self.ctx.L.hsrans_queue_pending(self.handle))
@@ -1055,22 +657,12 @@ class Queue:
     def stats(self) -> dict:
         st = QueueStats()
         self.ctx.L.hsrans_queue_stats(self.handle, ctypes.byref(st))
-        return {n: int(getattr(st, n)) for n, _ in QueueStats._fields_}
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.L.hsrans_queue_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _as_dict(st)  # (uint64 fields: Python ints)
 
 
-class Sharded:
+class Sharded(_Handle):
     """hsrans_sharded: this rank's share of ONE stream decoded by all ranks of a communicator (or, without one, decode only)."""
+    _destroy = "hsrans_sharded_destroy"
 
     def __init__(self, ctx: "Context", plan, parts: int = 1, weights=None, root: int | None = None, comm: Comm | None = None, rank: int | None = None,
                  world: int | None = None):
@@ -1083,13 +675,12 @@ class Sharded:
             rc = ctx.L.hsrans_sharded_create(ctx.handle, comm.handle, _p(plan), plan.size, parts, None if w is None else _p(w), r, ctypes.byref(h))
         else:
             rc = ctx.L.hsrans_sharded_create_rank(ctx.handle, rank, world, _p(plan), plan.size, parts, None if w is None else _p(w), r, ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_sharded_create failed with code {rc}")
+        _check(rc, "hsrans_sharded_create")
         self.handle = h
         info = ShardedInfo()
         shards = (Shard * (int(world if comm is None else comm.world) * parts))()
         ctx.L.hsrans_sharded_info(h, ctypes.byref(info), shards, len(shards))
-        self.info = {n: getattr(info, n) for n, _ in ShardedInfo._fields_}
+        self.info = _as_dict(info)
         self.shards = [[(int(shards[q * parts + k].first_chain), int(shards[q * parts + k].chain_count), int(shards[q * parts + k].out_begin), int(shards[q * parts + k].out_end))
                         for k in range(parts)] for q in range(info.world)]
 
@@ -1099,9 +690,7 @@ class Sharded:
 
     def wait_part(self, part: int, stream: torch.cuda.Stream):
         """hsrans_sharded_wait_part: `stream` waits until sub-run `part` of the last decode() is complete and visible"""
-        rc = self.ctx.L.hsrans_sharded_wait_part(self.handle, part, ctypes.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_sharded_wait_part failed with code {rc}")
+        _check(self.ctx.L.hsrans_sharded_wait_part(self.handle, part, _vp(stream.cuda_stream)), "hsrans_sharded_wait_part")
 
     def whole_plan(self) -> DevicePlan | None:
         """this rank's whole run when ONE launch decodes all its sub-runs (hsrans_sharded_info: one_launch), else None"""
@@ -1109,75 +698,48 @@ class Sharded:
         return DevicePlan(self.ctx, _vp(h), owned=False) if h else None
 
     def decode(self, d_window: torch.Tensor, d_out: torch.Tensor, mode: int = SHARD_DECODE_AND_EXCHANGE, stream: torch.cuda.Stream | None = None):
-        s = stream if stream is not None else torch.cuda.current_stream(d_out.device)
-        rc = self.ctx.L.hsrans_decode_sharded(self.handle, d_window.data_ptr(), d_out.data_ptr(), mode, ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_decode_sharded failed with code {rc}")
+        _check(self.ctx.L.hsrans_decode_sharded(self.handle, d_window.data_ptr(), d_out.data_ptr(), mode, _stream(stream, d_out.device)), "hsrans_decode_sharded")
 
     def status(self, stream: torch.cuda.Stream | None = None) -> int:
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return self.ctx.L.hsrans_sharded_status(self.handle, ctypes.c_void_p(s.cuda_stream))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.L.hsrans_sharded_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self.ctx.L.hsrans_sharded_status(self.handle, _stream(stream))
 
 
-class Context:
+def _calibration_report(rep: Calibration) -> dict:
+    return {"class_weights": list(rep.class_weights), "class_finish_us_last_iteration": [round(v, 3) for v in rep.class_finish_us_last_iteration],
+            "last_wave_us_before": rep.last_wave_us_before, "last_wave_us_after": rep.last_wave_us_after,
+            "class_spread_us_before": rep.class_spread_us_before, "class_spread_us_after": rep.class_spread_us_after,
+            "iterations": rep.iterations, "bytes": rep.bytes}
+
+
+class Context(_Handle):
     """hsrans_ctx: one per GPU.  Raises if no gfx950 device is usable (there is no CPU decode path)."""
+    _destroy = "hsrans_ctx_destroy"
 
     def __init__(self, device: int = 0):
         self.L = load_library()
         h = _vp()
-        rc = self.L.hsrans_ctx_create(device, ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_ctx_create(device={device}) failed with code {rc}: a gfx950 GPU is required")
+        _check(self.L.hsrans_ctx_create(device, ctypes.byref(h)), f"hsrans_ctx_create(device={device})", ": a gfx950 GPU is required")
         self.handle = h
         self.device = device
+
+    def _library(self):
+        return self.L
 
     @property
     def device_name(self) -> str:
         return self.L.hsrans_ctx_device_name(self.handle).decode()
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.hsrans_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def calibrate(self, bits: int = 11, iterations: int = 0) -> dict:
         """hsrans_ctx_calibrate: fits the one-chain-per-wave index's class lengths to this device; returns the report."""
         rep = Calibration()
-        rc = self.L.hsrans_ctx_calibrate(self.handle, bits, iterations, ctypes.byref(rep))
-        if rc != 0:
-            raise HsransError(f"hsrans_ctx_calibrate failed with code {rc}")
-        return {"class_weights": list(rep.class_weights), "class_finish_us_last_iteration": [round(v, 3) for v in rep.class_finish_us_last_iteration],
-                "last_wave_us_before": rep.last_wave_us_before, "last_wave_us_after": rep.last_wave_us_after,
-                "class_spread_us_before": rep.class_spread_us_before, "class_spread_us_after": rep.class_spread_us_after,
-                "iterations": rep.iterations, "bytes": rep.bytes}
+        _check(self.L.hsrans_ctx_calibrate(self.handle, bits, iterations, ctypes.byref(rep)), "hsrans_ctx_calibrate")
+        return _calibration_report(rep)
 
     def calibrate_runs(self, bits: int = 11, copies: int = 2, iterations: int = 0) -> dict:
         """hsrans_ctx_calibrate_runs: the same fit for runs ``copies`` times as long (``copies`` members of the calibration stream in one launch)."""
         rep = Calibration()
-        rc = self.L.hsrans_ctx_calibrate_runs(self.handle, bits, iterations, copies, ctypes.byref(rep))
-        if rc != 0:
-            raise HsransError(f"hsrans_ctx_calibrate_runs failed with code {rc}")
-        return {"copies": copies, "class_weights": list(rep.class_weights), "class_finish_us_last_iteration": [round(v, 3) for v in rep.class_finish_us_last_iteration],
-                "last_wave_us_before": rep.last_wave_us_before, "last_wave_us_after": rep.last_wave_us_after,
-                "class_spread_us_before": rep.class_spread_us_before, "class_spread_us_after": rep.class_spread_us_after,
-                "iterations": rep.iterations, "bytes": rep.bytes}
+        _check(self.L.hsrans_ctx_calibrate_runs(self.handle, bits, iterations, copies, ctypes.byref(rep)), "hsrans_ctx_calibrate_runs")
+        return {"copies": copies, **_calibration_report(rep)}
 
     # -- host-pointer drop-in: decodeFunc(pInData, inLength, pOutData, outCapacity) ------------------------------
     def decode_host(self, container: int, states: int, bits: int, stream, out_capacity: int, plan=None, in_length: int | None = None):
@@ -1208,9 +770,7 @@ class Context:
     def make_device_plan(self, plan) -> DevicePlan:
         plan = _u8(plan)
         h = _vp()
-        rc = self.L.hsrans_dplan_create(self.handle, _p(plan), plan.size, ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_dplan_create failed with code {rc}")
+        _check(self.L.hsrans_dplan_create(self.handle, _p(plan), plan.size, ctypes.byref(h)), "hsrans_dplan_create")
         return DevicePlan(self, h)
 
     def make_device_plan_from_stream(self, container: int, states: int, bits: int, d_stream: torch.Tensor, stream_length: int,
@@ -1218,12 +778,9 @@ class Context:
         """A plan for a stream that only exists in device memory.  mt_: the header chain is walked on the GPU.  block_: the walk plan
         (one wavefront follows the inline headers), made from the stream's first 16 + 4 * states bytes; :meth:`decode_device_indexing`
         turns it into a plan with checkpoints.  Raw streams are refused (plan_build needs their header only)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
         h = _vp()
-        rc = self.L.hsrans_dplan_create_from_device_stream(self.handle, container, states, bits, d_stream.data_ptr(), stream_length, out_capacity,
-                                                           ctypes.c_void_p(s.cuda_stream), ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_dplan_create_from_device_stream failed with code {rc}")
+        _check(self.L.hsrans_dplan_create_from_device_stream(self.handle, container, states, bits, d_stream.data_ptr(), stream_length, out_capacity,
+                                                             _stream(stream, d_stream.device), ctypes.byref(h)), "hsrans_dplan_create_from_device_stream")
         return DevicePlan(self, h)
 
     def read_device_plan(self, dplan: DevicePlan, capacity: int = 1 << 28) -> np.ndarray:
@@ -1236,11 +793,8 @@ class Context:
     def decode_device(self, dplan: DevicePlan, d_stream: torch.Tensor, d_out: torch.Tensor, stream: torch.cuda.Stream | None = None,
                       stream_length: int | None = None):
         """Asynchronous launch on ``stream`` (default: torch's current stream).  Tensors are uint8, on this context's GPU."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
-        rc = self.L.hsrans_decode_device(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
-                                         d_out.data_ptr(), d_out.numel(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_decode_device failed with code {rc}")
+        _check(self.L.hsrans_decode_device(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                           d_out.data_ptr(), d_out.numel(), _stream(stream, d_stream.device)), "hsrans_decode_device")
 
     def decode_device_indexing(self, dplan: DevicePlan, d_stream: torch.Tensor, d_out: torch.Tensor, index_interval: int,
                                stream: torch.cuda.Stream | None = None, stream_length: int | None = None) -> DevicePlan:
@@ -1248,12 +802,10 @@ class Context:
         ``index_interval`` groups for the later decodes (hsrans_decode_device_indexing; synchronises ``stream``).  ``dplan``: a raw or mt_
         base plan, or a block_ stream's walk plan (``make_device_plan_from_stream(BLOCK, ...)`` or ``make_device_plan(plan_build(BLOCK, ...))``).
         Raises HsransError; for a block_ stream with more than ``decoded_len / 4096 + 16`` blocks (code 3) ``d_out`` is complete all the same."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
         h = _vp()
-        rc = self.L.hsrans_decode_device_indexing(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
-                                                  d_out.data_ptr(), d_out.numel(), index_interval, ctypes.c_void_p(s.cuda_stream), ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_decode_device_indexing failed with code {rc}")
+        _check(self.L.hsrans_decode_device_indexing(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                                    d_out.data_ptr(), d_out.numel(), index_interval, _stream(stream, d_stream.device), ctypes.byref(h)),
+               "hsrans_decode_device_indexing")
         return DevicePlan(self, h)
 
     def decode_device_indexing_batch(self, members, stream: torch.cuda.Stream | None = None, stats: dict | None = None):
@@ -1284,41 +836,32 @@ class Context:
             e = arr[k]
             e.dplan, e.d_stream, e.d_out, e.index_interval = m[0].handle, m[1].data_ptr(), m[2].data_ptr(), m[3]
             e.stream_length, e.out_capacity = (m[4] if len(m) == 5 else m[1].numel()), m[2].numel()
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
         st = IndexingBatchStats()
-        rc = self.L.hsrans_decode_device_indexing_batch(self.handle, arr, K, ctypes.c_void_p(s.cuda_stream), ctypes.byref(st))
+        rc = self.L.hsrans_decode_device_indexing_batch(self.handle, arr, K, _stream(stream, dev), ctypes.byref(st))
         if stats is not None:
-            stats.update({n: getattr(st, n) for n, _ in IndexingBatchStats._fields_})
-        if rc != 0 and K == 0:
-            raise HsransError(f"hsrans_decode_device_indexing_batch failed with code {rc}")
+            stats.update(_as_dict(st))
+        if K == 0:
+            _check(rc, "hsrans_decode_device_indexing_batch")
         codes = [int(arr[k].rc) for k in range(K)]
         plans = [DevicePlan(self, _vp(arr[k].indexed)) if arr[k].indexed else None for k in range(K)]
         if rc != 0:
-            failed = [k for k in range(K) if codes[k] != 0]
-            err = HsransError(f"hsrans_decode_device_indexing_batch failed with code {rc}" + (f": member {failed[0]} failed" if failed and rc not in (2, 4) else ""))
-            err.code, err.codes, err.plans = rc, codes, plans
-            raise err
+            failed = [] if rc in (2, 4) else [k for k in range(K) if codes[k] != 0]  # (2, 4: the call as a whole was refused)
+            raise _members_error("hsrans_decode_device_indexing_batch", rc, failed, codes=codes, plans=plans)
         return plans
 
     def decode_device_window(self, dplan: DevicePlan, d_window: torch.Tensor, window_offset: int, window_length: int, d_out: torch.Tensor,
                              stream: torch.cuda.Stream | None = None):
         """As decode_device for a caller that holds only stream bytes [window_offset, window_offset + window_length) (hsrans_decode_device_window)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_window.device)
-        rc = self.L.hsrans_decode_device_window(self.handle, dplan.handle, d_window.data_ptr(), window_offset, window_length, d_out.data_ptr(), d_out.numel(),
-                                                ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_decode_device_window failed with code {rc}")
+        _check(self.L.hsrans_decode_device_window(self.handle, dplan.handle, d_window.data_ptr(), window_offset, window_length, d_out.data_ptr(), d_out.numel(),
+                                                  _stream(stream, d_window.device)), "hsrans_decode_device_window")
 
     def decode_device_ranges(self, dplan: DevicePlan, d_window: torch.Tensor, window_offset: int, window_length: int, d_out_window: torch.Tensor,
                              out_offset: int, out_length: int, stream: torch.cuda.Stream | None = None):
         """As decode_device_window for a caller that also holds only output bytes [out_offset, out_offset + out_length)
         (hsrans_decode_device_ranges): one rank's share of a sharded decode."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_window.device)
         assert d_out_window.numel() >= out_length
-        rc = self.L.hsrans_decode_device_ranges(self.handle, dplan.handle, d_window.data_ptr(), window_offset, window_length, d_out_window.data_ptr(),
-                                                out_offset, out_length, ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_decode_device_ranges failed with code {rc}")
+        _check(self.L.hsrans_decode_device_ranges(self.handle, dplan.handle, d_window.data_ptr(), window_offset, window_length, d_out_window.data_ptr(),
+                                                  out_offset, out_length, _stream(stream, d_window.device)), "hsrans_decode_device_ranges")
 
     def decode_device_gather(self, dplan: DevicePlan, d_stream: torch.Tensor, ranges, d_dst: torch.Tensor, stream_length: int | None = None,
                              stream: torch.cuda.Stream | None = None):
@@ -1327,14 +870,10 @@ class Context:
         d_dst[dst_offset:]; no other byte of ``d_dst`` is written.  Asynchronous on ``stream`` (default: torch's current stream); ``ranges`` is
         read before the call returns.  Destinations that overlap are the caller's responsibility.  Raises HsransError (``.code``: 2 bad
         argument or range, 3 a plan without entry points or a wrong stream length)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
         arr = _ranges_array(ranges)
-        rc = self.L.hsrans_decode_device_gather(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
-                                                _p(arr) if arr.size else None, arr.shape[0], d_dst.data_ptr(), d_dst.numel(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_gather failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_decode_device_gather(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                                  _p(arr) if arr.size else None, arr.shape[0], d_dst.data_ptr(), d_dst.numel(), _stream(stream, d_stream.device)),
+               "hsrans_decode_device_gather")
 
     def decode_device_gather_indirect(self, dplan: DevicePlan, d_stream: torch.Tensor, d_ranges: torch.Tensor, d_dst: torch.Tensor, count: torch.Tensor | None = None,
                                       max_count: int | None = None, workspace: torch.Tensor | None = None, stream_length: int | None = None,
@@ -1346,27 +885,11 @@ class Context:
         gather_workspace_bytes(max_count) bytes that no other call in flight uses; allocated here when None.  Returns the workspace.
         Raises HsransError (``.code``) for what the host can check; a range or count only the device can refuse leaves ``d_dst`` untouched
         and is reported by ``status(dplan)`` (5)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_stream.device)
-        if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == 3 and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
-            raise TypeError("d_ranges: a contiguous CUDA tensor (N, 3) of int64 or uint64")
-        if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
-            raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
-        if max_count is None:
-            max_count = d_ranges.shape[0]
-        if max_count > d_ranges.shape[0]:
-            raise ValueError("max_count is larger than d_ranges")
-        if workspace is None:
-            with torch.cuda.stream(s):
-                workspace = torch.empty(gather_workspace_bytes(max_count), dtype=torch.uint8, device=d_stream.device)
-        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace: a contiguous CUDA uint8 tensor")
-        rc = self.L.hsrans_decode_device_gather_indirect(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
-                                                         d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count, d_dst.data_ptr(), d_dst.numel(),
-                                                         workspace.data_ptr(), workspace.numel(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_gather_indirect failed with code {rc}")
-            err.code = rc
-            raise err
+        max_count, workspace = _indirect_args(d_ranges, 3, count, max_count, workspace, gather_workspace_bytes, d_stream.device, stream)
+        _check(self.L.hsrans_decode_device_gather_indirect(self.handle, dplan.handle, d_stream.data_ptr(), d_stream.numel() if stream_length is None else stream_length,
+                                                           d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count, d_dst.data_ptr(), d_dst.numel(),
+                                                           workspace.data_ptr(), workspace.numel(), _stream(stream, d_stream.device)),
+               "hsrans_decode_device_gather_indirect")
         return workspace
 
     def make_gather_set(self, dplans, d_streams, stream_lengths=None) -> GatherSet:
@@ -1377,15 +900,9 @@ class Context:
         K = len(dplans)
         if len(d_streams) != K:
             raise ValueError("one stream per device plan")
-        pa = (ctypes.c_void_p * K)(*[d.handle.value if isinstance(d.handle, ctypes.c_void_p) else d.handle for d in dplans])
-        sp = (ctypes.c_void_p * K)(*[t.data_ptr() for t in d_streams])
-        sl = (ctypes.c_size_t * K)(*[(t.numel() if stream_lengths is None else int(stream_lengths[k])) for k, t in enumerate(d_streams)])
+        sp, sl = _tensor_arrays(d_streams, stream_lengths)
         h = _vp()
-        rc = self.L.hsrans_gather_set_create(self.handle, pa, sp, sl, K, ctypes.byref(h))
-        if rc != 0:
-            err = HsransError(f"hsrans_gather_set_create failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_gather_set_create(self.handle, _handle_array(dplans), sp, sl, K, ctypes.byref(h)), "hsrans_gather_set_create")
         return GatherSet(self, h, dplans, d_streams)
 
     def decode_device_gather_batch(self, gset: GatherSet, ranges, d_dst: torch.Tensor, stream: torch.cuda.Stream | None = None):
@@ -1394,14 +911,9 @@ class Context:
         [offset, offset + length) of that member land at d_dst[dst_offset:]; no other byte of ``d_dst`` is written — byte for byte what one
         decode_device_gather per member gives.  Asynchronous on ``stream`` (default: torch's current stream); ``ranges`` is read before the
         call returns.  Raises HsransError (``.code``: 2 a bad member, range or destination; nothing was launched)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_dst.device)
         arr = _member_ranges_array(ranges)
-        rc = self.L.hsrans_decode_device_gather_batch(self.handle, gset.handle, _p(arr) if arr.size else None, arr.shape[0], d_dst.data_ptr(), d_dst.numel(),
-                                                      ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_gather_batch failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_decode_device_gather_batch(self.handle, gset.handle, _p(arr) if arr.size else None, arr.shape[0], d_dst.data_ptr(), d_dst.numel(),
+                                                        _stream(stream, d_dst.device)), "hsrans_decode_device_gather_batch")
 
     def decode_device_gather_batch_indirect(self, gset: GatherSet, d_ranges: torch.Tensor, d_dst: torch.Tensor, count: torch.Tensor | None = None,
                                             max_count: int | None = None, workspace: torch.Tensor | None = None,
@@ -1414,82 +926,54 @@ class Context:
         graph.  ``workspace``: a CUDA uint8 tensor of at least gather_batch_workspace_bytes(members, max_count) bytes that no other call in
         flight uses; allocated here when None.  Returns the workspace.  Raises HsransError (``.code``) for what the host can check; a row or
         count only the device can refuse leaves ``d_dst`` untouched and is reported by ``gather_set_refused(gset)`` (5)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_dst.device)
-        if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == 4 and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
-            raise TypeError("d_ranges: a contiguous CUDA tensor (N, 4) of int64 or uint64")
-        if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
-            raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
-        if max_count is None:
-            max_count = d_ranges.shape[0]
-        if max_count > d_ranges.shape[0]:
-            raise ValueError("max_count is larger than d_ranges")
-        if workspace is None:
-            with torch.cuda.stream(s):
-                workspace = torch.empty(gather_batch_workspace_bytes(len(gset.dplans), max_count), dtype=torch.uint8, device=d_dst.device)
-        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace: a contiguous CUDA uint8 tensor")
-        rc = self.L.hsrans_decode_device_gather_batch_indirect(self.handle, gset.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
-                                                               d_dst.data_ptr(), d_dst.numel(), workspace.data_ptr(), workspace.numel(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_gather_batch_indirect failed with code {rc}")
-            err.code = rc
-            raise err
+        max_count, workspace = _indirect_args(d_ranges, 4, count, max_count, workspace, lambda n: gather_batch_workspace_bytes(len(gset.dplans), n), d_dst.device,
+                                              stream)
+        _check(self.L.hsrans_decode_device_gather_batch_indirect(self.handle, gset.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
+                                                                 d_dst.data_ptr(), d_dst.numel(), workspace.data_ptr(), workspace.numel(), _stream(stream, d_dst.device)),
+               "hsrans_decode_device_gather_batch_indirect")
         return workspace
 
     def gather_set_refused(self, gset: GatherSet, stream: torch.cuda.Stream | None = None) -> int:
         """hsrans_gather_set_refused: synchronises ``stream`` and returns 5 once where a decode_device_gather_batch_indirect on the set was
         refused on the device since the last look, else 0"""
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return int(self.L.hsrans_gather_set_refused(self.handle, gset.handle, ctypes.c_void_p(s.cuda_stream)))
+        return int(self.L.hsrans_gather_set_refused(self.handle, gset.handle, _stream(stream)))
 
     def gather_set_status(self, gset: GatherSet, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_gather_set_status: synchronises ``stream`` and returns every member's status (0, or 5: its kernel found a malformed histogram)"""
-        s = stream if stream is not None else torch.cuda.current_stream()
         codes = (ctypes.c_int * len(gset.dplans))()
-        self.L.hsrans_gather_set_status(self.handle, gset.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        self.L.hsrans_gather_set_status(self.handle, gset.handle, _stream(stream), codes)
         return list(codes)
 
     # -- K independent streams, one launch -------------------------------------------------------------------------
     def make_batch(self, dplans) -> Batch:
         dplans = list(dplans)
-        arr = (ctypes.c_void_p * len(dplans))(*[d.handle.value if isinstance(d.handle, ctypes.c_void_p) else d.handle for d in dplans])
         h = _vp()
-        rc = self.L.hsrans_dplan_batch_create(self.handle, arr, len(dplans), ctypes.byref(h))
-        if rc != 0:
-            raise HsransError(f"hsrans_dplan_batch_create failed with code {rc}")
+        _check(self.L.hsrans_dplan_batch_create(self.handle, _handle_array(dplans), len(dplans), ctypes.byref(h)), "hsrans_dplan_batch_create")
         return Batch(self, h, dplans)
 
     def decode_device_batch(self, batch: Batch, d_streams, d_outs, stream: torch.cuda.Stream | None = None, stream_lengths=None):
         """Asynchronous on ``stream`` (default: torch's current stream): member k decodes d_streams[k] into d_outs[k]."""
         K = len(batch.dplans)
         assert len(d_streams) == K and len(d_outs) == K
-        s = stream if stream is not None else torch.cuda.current_stream(d_streams[0].device)
-        sp = (ctypes.c_void_p * K)(*[t.data_ptr() for t in d_streams])
-        op = (ctypes.c_void_p * K)(*[t.data_ptr() for t in d_outs])
-        sl = (ctypes.c_size_t * K)(*[(t.numel() if stream_lengths is None else int(stream_lengths[k])) for k, t in enumerate(d_streams)])
-        oc = (ctypes.c_size_t * K)(*[t.numel() for t in d_outs])
-        rc = self.L.hsrans_decode_device_batch(self.handle, batch.handle, sp, sl, op, oc, ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            raise HsransError(f"hsrans_decode_device_batch failed with code {rc}")
+        sp, sl = _tensor_arrays(d_streams, stream_lengths)
+        op, oc = _tensor_arrays(d_outs)
+        _check(self.L.hsrans_decode_device_batch(self.handle, batch.handle, sp, sl, op, oc, _stream(stream, d_streams[0].device)), "hsrans_decode_device_batch")
 
     def batch_status(self, batch: Batch, stream: torch.cuda.Stream | None = None) -> list:
-        s = stream if stream is not None else torch.cuda.current_stream()
         codes = (ctypes.c_int * len(batch.dplans))()
-        self.L.hsrans_dplan_batch_status(self.handle, batch.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        self.L.hsrans_dplan_batch_status(self.handle, batch.handle, _stream(stream), codes)
         return list(codes)
 
     def status(self, dplan: DevicePlan, stream: torch.cuda.Stream | None = None) -> int:
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return self.L.hsrans_dplan_status(self.handle, dplan.handle, ctypes.c_void_p(s.cuda_stream))
+        return self.L.hsrans_dplan_status(self.handle, dplan.handle, _stream(stream))
 
     def encode_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, d_out: torch.Tensor, block_size: int = 1 << 16,
                       index_interval: int = 0, want_plan: bool = False, stream: torch.cuda.Stream | None = None):
         """GPU encoder (mt_, independent fixed-size blocks).  Returns the stream length written to d_out, or
         ``(length, DevicePlan)`` with ``want_plan`` (plan with a checkpoint every ``index_interval`` groups, built on the device)."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
         h = _vp()
         n = self.L.hsrans_encode_device(self.handle, container, states, bits, d_in.data_ptr(), d_in.numel(), d_out.data_ptr(), d_out.numel(), block_size,
-                                        index_interval, ctypes.c_void_p(s.cuda_stream), ctypes.byref(h) if want_plan else None)
+                                        index_interval, _stream(stream, d_in.device), ctypes.byref(h) if want_plan else None)
         if n == 0:
             raise HsransError("hsrans_encode_device failed")
         return (n, DevicePlan(self, h)) if want_plan else n
@@ -1498,7 +982,6 @@ class Context:
                           want_plan: bool = False, want_device_plan: bool = False, stream: torch.cuda.Stream | None = None):
         """GPU encoder for the raw format (one wavefront: hsrans_encode_device_raw).  Returns the stream length, followed by the plan
         blob (``want_plan``) and/or a DevicePlan (``want_device_plan``) when an index (``index_interval`` or ``index_groups``) is asked for."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
         groups = np.ascontiguousarray(index_groups, dtype=np.uint64) if index_groups is not None else None
         n_groups = 0 if groups is None else groups.size
         plan, psize, h = None, _sz(0), _vp()
@@ -1509,7 +992,7 @@ class Context:
         n = self.L.hsrans_encode_device_raw(self.handle, states, bits, d_in.data_ptr(), d_in.numel(), d_out.data_ptr(), d_out.numel(),
                                             ctypes.addressof(hist) if hist is not None else None, index_interval, _p(groups) if n_groups else None, n_groups,
                                             _p(plan) if want_plan else None, plan.size if want_plan else 0, ctypes.byref(psize),
-                                            ctypes.c_void_p(s.cuda_stream), ctypes.byref(h) if want_device_plan else None)
+                                            _stream(stream, d_in.device), ctypes.byref(h) if want_device_plan else None)
         if n == 0:
             raise HsransError("hsrans_encode_device_raw failed")
         out = [n]
@@ -1525,7 +1008,6 @@ class Context:
         """GPU twin of :func:`encode` (hsrans_encode_device_ex): every container, the adaptive (``block_size=0``) or fixed blocks, the
         same stream bytes and plan.  Returns the stream length, followed by the plan blob (``want_plan``) and/or a DevicePlan
         (``want_device_plan``) when an index (``index_interval`` or ``index_groups``) is asked for."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
         groups = np.ascontiguousarray(index_groups, dtype=np.uint64) if index_groups is not None else None
         if groups is not None and groups.size == 0:  # a stream too short for more than one chain (as encode())
             groups, index_interval = None, 4
@@ -1540,7 +1022,7 @@ class Context:
                           ENC_INDEPENDENT_BLOCKS if independent_blocks else 0, 0, groups.ctypes.data if n_groups else None, n_groups)
         h = _vp()
         n = self.L.hsrans_encode_device_ex(self.handle, container, states, bits, d_in.data_ptr(), d_in.numel(), d_out.data_ptr(), d_out.numel(),
-                                           ctypes.byref(hist) if hist is not None else None, ctypes.byref(opts), ctypes.c_void_p(s.cuda_stream),
+                                           ctypes.byref(hist) if hist is not None else None, ctypes.byref(opts), _stream(stream, d_in.device),
                                            ctypes.byref(h) if want_device_plan and indexed else None)
         if n == 0:
             raise HsransError("hsrans_encode_device_ex failed")
@@ -1564,11 +1046,7 @@ class Context:
         keep = []  # (the hists and group lists must outlive the call)
         dev = None
         for k, m in enumerate(members):
-            container, states, bits, d_in, d_out = m[:5]
-            o = dict(m[5]) if len(m) > 5 and m[5] is not None else {}
-            unknown = set(o) - {"block_size", "index_interval", "hist", "index_groups", "length"}
-            if unknown:
-                raise HsransError(f"encode_device_batch: member {k}: unknown options {sorted(unknown)}")
+            container, states, bits, d_in, d_out, o = _encode_member("encode_device_batch", k, m, ("block_size", "index_interval", "hist", "index_groups", "length"))
             dev = d_in.device if dev is None else dev
             e = arr[k]
             e.container, e.states, e.bits = container, states, bits
@@ -1583,19 +1061,16 @@ class Context:
                 g = np.ascontiguousarray(o["index_groups"], dtype=np.uint64)
                 keep.append(g)
                 e.index_groups, e.n_index_groups = (g.ctypes.data if g.size else None), g.size
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
         handles = (_vp * max(K, 1))()
         st = EncodeBatchStats()
-        rc = self.L.hsrans_encode_device_batch(self.handle, arr, K, ctypes.c_void_p(s.cuda_stream), handles if want_plans else None, ctypes.byref(st))
+        rc = self.L.hsrans_encode_device_batch(self.handle, arr, K, _stream(stream, dev), handles if want_plans else None, ctypes.byref(st))
         if stats is not None:
-            stats.update({n: getattr(st, n) for n, _ in EncodeBatchStats._fields_})
+            stats.update(_as_dict(st))
         lengths = [int(arr[k].stream_length) for k in range(K)]
         plans = [DevicePlan(self, _vp(handles[k])) if want_plans and handles[k] else None for k in range(K)]
         if rc != 0:
-            failed = [k for k in range(K) if lengths[k] == 0]
-            err = HsransError(f"hsrans_encode_device_batch failed with code {rc}" + (f": member {failed[0]} failed" if failed and rc != 2 else ""))
-            err.code, err.lengths, err.plans = rc, lengths, plans
-            raise err
+            failed = [] if rc == 2 else [k for k in range(K) if lengths[k] == 0]  # (2: a check refused the call as a whole)
+            raise _members_error("hsrans_encode_device_batch", rc, failed, lengths=lengths, plans=plans)
         return (lengths, plans) if want_plans else lengths
 
     def encode_device_ex_batch(self, members, want_plans: bool = False, want_device_plans: bool = False, stream: torch.cuda.Stream | None = None,
@@ -1614,11 +1089,8 @@ class Context:
         blobs = [None] * K
         dev = None
         for k, m in enumerate(members):
-            container, states, bits, d_in, d_out = m[:5]
-            o = dict(m[5]) if len(m) > 5 and m[5] is not None else {}
-            unknown = set(o) - {"block_size", "independent_blocks", "index_interval", "index_groups", "length"}
-            if unknown:
-                raise HsransError(f"encode_device_ex_batch: member {k}: unknown options {sorted(unknown)}")
+            container, states, bits, d_in, d_out, o = _encode_member("encode_device_ex_batch", k, m,
+                                                                     ("block_size", "independent_blocks", "index_interval", "index_groups", "length"))
             dev = d_in.device if dev is None else dev
             length = int(o.get("length", d_in.numel()))
             block_size, index_interval = int(o.get("block_size", 0)), int(o.get("index_interval", 0))
@@ -1639,12 +1111,11 @@ class Context:
             e.d_in, e.length = d_in.data_ptr(), length
             e.d_out, e.out_capacity = d_out.data_ptr(), d_out.numel()
             e.opts = ctypes.pointer(opts)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
         handles = (_vp * max(K, 1))()
         st = EncodeExBatchStats()
-        rc = self.L.hsrans_encode_device_ex_batch(self.handle, arr, K, ctypes.c_void_p(s.cuda_stream), handles if want_device_plans else None, ctypes.byref(st))
+        rc = self.L.hsrans_encode_device_ex_batch(self.handle, arr, K, _stream(stream, dev), handles if want_device_plans else None, ctypes.byref(st))
         if stats is not None:
-            stats.update({n: getattr(st, n) for n, _ in EncodeExBatchStats._fields_})
+            stats.update(_as_dict(st))
         lengths = [int(arr[k].stream_length) for k in range(K)]
         plans = [blobs[k][: arr[k].opts.contents.plan_size].copy() if blobs[k] is not None and lengths[k] else None for k in range(K)]
         dplans = [DevicePlan(self, _vp(handles[k])) if want_device_plans and handles[k] else None for k in range(K)]
@@ -1652,9 +1123,7 @@ class Context:
         if rc != 0:
             rcs = [int(arr[k].rc) for k in range(K)]
             failed = [k for k in range(K) if rcs[k] != 0]
-            err = HsransError(f"hsrans_encode_device_ex_batch failed with code {rc}" + (f": member {failed[0]} failed" if failed and len(failed) < K else ""))
-            err.code, err.lengths, err.rcs, err.plans, err.device_plans = rc, lengths, rcs, plans, dplans
-            raise err
+            raise _members_error("hsrans_encode_device_ex_batch", rc, failed if len(failed) < K else [], lengths=lengths, rcs=rcs, plans=plans, device_plans=dplans)
         out = [lengths]
         if want_plans:
             out.append(plans)
@@ -1668,30 +1137,20 @@ class Context:
         d_planes = list(d_planes)
         if len(d_planes) != itemsize:
             raise HsransError(f"one plane per byte of an element: {itemsize} planes, not {len(d_planes)}")
-        return (_vp * max(itemsize, 1))(*[t.data_ptr() for t in d_planes])
+        return _tensor_arrays(d_planes)[0]  # (an element has at least one byte: never an empty array)
 
     def planes_split_device(self, tensor: torch.Tensor, d_planes, elements: int | None = None, stream: torch.cuda.Stream | None = None):
         """hsrans_planes_split_device: the elements of a contiguous CUDA tensor (2-, 4- or 8-byte items) into ``d_planes`` (one uint8
         tensor of at least ``elements`` bytes per byte of an item).  Asynchronous on ``stream`` (default: torch's current stream)."""
-        s = stream if stream is not None else torch.cuda.current_stream(tensor.device)
         W = tensor.element_size()
-        rc = self.L.hsrans_planes_split_device(self.handle, W, tensor.data_ptr(), tensor.numel() if elements is None else elements,
-                                               self._plane_ptrs(d_planes, W), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_planes_split_device failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_planes_split_device(self.handle, W, tensor.data_ptr(), tensor.numel() if elements is None else elements,
+                                                 self._plane_ptrs(d_planes, W), _stream(stream, tensor.device)), "hsrans_planes_split_device")
 
     def planes_merge_device(self, d_planes, out_tensor: torch.Tensor, elements: int | None = None, stream: torch.cuda.Stream | None = None):
         """hsrans_planes_merge_device: ``d_planes`` interleaved back into the elements of ``out_tensor``.  Asynchronous on ``stream``."""
-        s = stream if stream is not None else torch.cuda.current_stream(out_tensor.device)
         W = out_tensor.element_size()
-        rc = self.L.hsrans_planes_merge_device(self.handle, W, self._plane_ptrs(d_planes, W), out_tensor.numel() if elements is None else elements,
-                                               out_tensor.data_ptr(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_planes_merge_device failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_planes_merge_device(self.handle, W, self._plane_ptrs(d_planes, W), out_tensor.numel() if elements is None else elements,
+                                                 out_tensor.data_ptr(), _stream(stream, out_tensor.device)), "hsrans_planes_merge_device")
 
     def encode_device_planes(self, tensor: torch.Tensor, d_frame: torch.Tensor, d_work: torch.Tensor, states: int = 64, bits: int = 11,
                              block_size: int = 1 << 16, index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True,
@@ -1701,13 +1160,12 @@ class Context:
         plans)``: ``desc`` a PlanesDesc, ``plans`` a DevicePlan per plane (None for a stored plane; all None without ``want_plans``)."""
         if not tensor.is_contiguous():
             raise HsransError("encode_device_planes takes a contiguous tensor")
-        s = stream if stream is not None else torch.cuda.current_stream(tensor.device)
         W = tensor.element_size()
         desc = PlanesDesc()
         handles = (_vp * PLANES_MAX)()
         n = self.L.hsrans_encode_device_planes(self.handle, W, states, bits, tensor.data_ptr(), tensor.numel(), d_frame.data_ptr(), d_frame.numel(), block_size,
                                                index_interval, PLANES_STORE_INCOMPRESSIBLE if store_incompressible else 0, d_work.data_ptr(), d_work.numel(),
-                                               ctypes.c_void_p(s.cuda_stream), ctypes.byref(desc), handles if want_plans else None)
+                                               _stream(stream, tensor.device), ctypes.byref(desc), handles if want_plans else None)
         if n == 0:
             raise HsransError("hsrans_encode_device_planes failed")
         plans = [DevicePlan(self, _vp(handles[p])) if want_plans and handles[p] else None for p in range(W)]
@@ -1718,13 +1176,8 @@ class Context:
         plans = list(plans)
         if len(plans) != desc.elem_size:
             raise HsransError(f"one plan (or None) per plane: {desc.elem_size}, not {len(plans)}")
-        arr = (_vp * PLANES_MAX)(*[None if d is None else (d.handle.value if isinstance(d.handle, ctypes.c_void_p) else d.handle) for d in plans])
         h = _vp()
-        rc = self.L.hsrans_planes_create(self.handle, ctypes.byref(desc), arr, ctypes.byref(h))
-        if rc != 0:
-            err = HsransError(f"hsrans_planes_create failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_planes_create(self.handle, ctypes.byref(desc), _handle_array(plans, PLANES_MAX), ctypes.byref(h)), "hsrans_planes_create")
         return Planes(self, h, desc, plans)
 
     def decode_device_planes(self, planes: Planes, d_frame: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
@@ -1733,19 +1186,13 @@ class Context:
         were encoded).  Asynchronous on ``stream`` (default: torch's current stream)."""
         if not out_tensor.is_contiguous():
             raise HsransError("decode_device_planes takes a contiguous output tensor")
-        s = stream if stream is not None else torch.cuda.current_stream(d_frame.device)
-        rc = self.L.hsrans_decode_device_planes(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
-                                                out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
-                                                ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_planes failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_decode_device_planes(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
+                                                  out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                  _stream(stream, d_frame.device)), "hsrans_decode_device_planes")
 
     def planes_status(self, planes: Planes, stream: torch.cuda.Stream | None = None) -> list:
-        s = stream if stream is not None else torch.cuda.current_stream()
         codes = (ctypes.c_int * PLANES_MAX)()
-        self.L.hsrans_planes_status(self.handle, planes.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        self.L.hsrans_planes_status(self.handle, planes.handle, _stream(stream), codes)
         return list(codes)[: planes.desc.elem_size]
 
     def make_planes_gather(self, planes: Planes, d_frame: torch.Tensor, frame_length: int | None = None) -> PlanesGather:
@@ -1753,11 +1200,8 @@ class Context:
         decode_device_planes_gather.  The object keeps ``planes`` and the tensor alive.  Raises HsransError (``.code``: 2 a bad argument, 3 a
         plane's plan has no entry points)."""
         h = _vp()
-        rc = self.L.hsrans_planes_gather_create(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length, ctypes.byref(h))
-        if rc != 0:
-            err = HsransError(f"hsrans_planes_gather_create failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_planes_gather_create(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
+                                                  ctypes.byref(h)), "hsrans_planes_gather_create")
         return PlanesGather(self, h, planes, d_frame)
 
     def decode_device_planes_gather(self, pg: PlanesGather, ranges, out_tensor: torch.Tensor, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
@@ -1773,15 +1217,10 @@ class Context:
             raise HsransError(f"decode_device_planes_gather: the frame's elements are {pg.planes.desc.elem_size} bytes, the output tensor's {out_tensor.element_size()}")
         if d_work.dtype != torch.uint8:
             raise HsransError("decode_device_planes_gather takes a uint8 workspace tensor")
-        s = stream if stream is not None else torch.cuda.current_stream(out_tensor.device)
         arr = _ranges_array(ranges)
-        rc = self.L.hsrans_decode_device_planes_gather(self.handle, pg.handle, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
-                                                       out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
-                                                       ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_planes_gather failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_decode_device_planes_gather(self.handle, pg.handle, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
+                                                         out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                         _stream(stream, out_tensor.device)), "hsrans_decode_device_planes_gather")
 
     def decode_device_planes_gather_indirect(self, pg: PlanesGather, d_ranges: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
                                              count: torch.Tensor | None = None, max_count: int | None = None, max_elements: int | None = None,
@@ -1802,54 +1241,37 @@ class Context:
             raise HsransError(f"decode_device_planes_gather_indirect: the frame's elements are {W} bytes, the output tensor's {out_tensor.element_size()}")
         if d_work.dtype != torch.uint8:
             raise HsransError("decode_device_planes_gather_indirect takes a uint8 workspace tensor")
-        if not (d_ranges.is_cuda and d_ranges.dim() == 2 and d_ranges.shape[1] == 3 and d_ranges.dtype in (torch.int64, torch.uint64) and d_ranges.is_contiguous()):
-            raise TypeError("d_ranges: a contiguous CUDA tensor (N, 3) of int64 or uint64")
-        if count is not None and not (count.is_cuda and count.numel() == 1 and count.dtype in (torch.int32, torch.uint32)):
-            raise TypeError("count: a CUDA int32 or uint32 scalar tensor")
-        s = stream if stream is not None else torch.cuda.current_stream(out_tensor.device)
-        if max_count is None:
-            max_count = d_ranges.shape[0]
-        if max_count > d_ranges.shape[0]:
-            raise ValueError("max_count is larger than d_ranges")
+        max_count, workspace = _indirect_args(d_ranges, 3, count, max_count, workspace, lambda n: planes_gather_indirect_workspace_bytes(W, n), out_tensor.device,
+                                              stream)
         if max_elements is None:
             max_elements = max(0, d_work.numel() // W // 256 * 256 - 30 * max_count)
-        if workspace is None:
-            with torch.cuda.stream(s):
-                workspace = torch.empty(planes_gather_indirect_workspace_bytes(W, max_count), dtype=torch.uint8, device=out_tensor.device)
-        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace: a contiguous CUDA uint8 tensor")
-        rc = self.L.hsrans_decode_device_planes_gather_indirect(self.handle, pg.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
-                                                                max_elements, out_tensor.data_ptr(), out_tensor.numel() * W, d_work.data_ptr(), d_work.numel(),
-                                                                workspace.data_ptr(), workspace.numel(), ctypes.c_void_p(s.cuda_stream))
-        if rc != 0:
-            err = HsransError(f"hsrans_decode_device_planes_gather_indirect failed with code {rc}")
-            err.code = rc
-            raise err
+        _check(self.L.hsrans_decode_device_planes_gather_indirect(self.handle, pg.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
+                                                                  max_elements, out_tensor.data_ptr(), out_tensor.numel() * W, d_work.data_ptr(), d_work.numel(),
+                                                                  workspace.data_ptr(), workspace.numel(), _stream(stream, out_tensor.device)),
+               "hsrans_decode_device_planes_gather_indirect")
         return workspace
 
     def planes_gather_refused(self, pg: PlanesGather, stream: torch.cuda.Stream | None = None) -> int:
         """hsrans_planes_gather_refused: synchronises ``stream`` and returns 5 once where a decode_device_planes_gather_indirect on the object
         was refused on the device since the last look, else 0"""
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return int(self.L.hsrans_planes_gather_refused(self.handle, pg.handle, ctypes.c_void_p(s.cuda_stream)))
+        return int(self.L.hsrans_planes_gather_refused(self.handle, pg.handle, _stream(stream)))
 
     def planes_gather_status(self, pg: PlanesGather, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_planes_gather_status: synchronises ``stream`` and returns every plane's status (stored planes: 0)"""
-        s = stream if stream is not None else torch.cuda.current_stream()
         codes = (ctypes.c_int * PLANES_MAX)()
-        self.L.hsrans_planes_gather_status(self.handle, pg.handle, ctypes.c_void_p(s.cuda_stream), codes)
+        self.L.hsrans_planes_gather_status(self.handle, pg.handle, _stream(stream), codes)
         return list(codes)[: pg.planes.desc.elem_size]
 
     def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
                              stream: torch.cuda.Stream | None = None) -> np.ndarray:
         """The block choice hsrans_encode_device_ex makes (hsrans_block_choices_device): BLOCK_CHOICE records, as block_choices()."""
-        s = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+        s = _stream(stream, d_in.device)
         args = (self.handle, container, states, bits, d_in.data_ptr(), d_in.numel(), block_size)
-        n = self.L.hsrans_block_choices_device(*args, None, 0, ctypes.c_void_p(s.cuda_stream))
+        n = self.L.hsrans_block_choices_device(*args, None, 0, s)
         if n == 0:
             raise HsransError("hsrans_block_choices_device failed")
         out = np.zeros(n, BLOCK_CHOICE)
-        self.L.hsrans_block_choices_device(*args, out.ctypes.data, n, ctypes.c_void_p(s.cuda_stream))
+        self.L.hsrans_block_choices_device(*args, out.ctypes.data, n, s)
         return out
 
     def index_build_at(self, container: int, states: int, bits: int, stream, groups) -> np.ndarray:

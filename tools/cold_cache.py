@@ -5,7 +5,7 @@ the per-wave stamps of a cold launch (HSRANS_DEBUG_STAMPS=1).
 
     python tools/cold_cache.py [--pairs 4] [--steps 40]
 """
-import argparse, ctypes, json, os, sys
+import argparse, json, os, sys
 os.environ["HSRANS_DEBUG_STAMPS"] = "1" if "--stamps" in sys.argv else os.environ.get("HSRANS_DEBUG_STAMPS", "")
 if not os.environ["HSRANS_DEBUG_STAMPS"]:
     del os.environ["HSRANS_DEBUG_STAMPS"]
@@ -131,8 +131,6 @@ run("one pair, 512 MiB written between launches (single-launch events)", lambda 
 run("warm, single-launch events (for comparison with the line above)", lambda i: 0, lambda i: 0, flush_between=False)
 if a.stamps:
     L = H.load_library()
-    L.hsrans_debug_read_stamps.restype = ctypes.c_size_t
-    L.hsrans_debug_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     for label, cold in (("warm", False), ("cold", True)):
         for i in range(3 * P):
             k = i % P if cold else 0

@@ -138,6 +138,20 @@ class PlanesInfo(ctypes.Structure):  # hsrans_planes_info_t
     _fields_ = [(n, _u32) for n in ("coded", "stored", "launches")]
 
 
+class PlanesMember(ctypes.Structure):
+    """hsrans_planes_member: one tensor of hsrans_encode_device_planes_batch"""
+    _fields_ = [("elem_size", _u32), ("states", _i), ("bits", _u32), ("block_size", _u32), ("index_interval", _u32), ("flags", _u32), ("d_in", _vp),
+                ("elements", _sz), ("d_frame", _vp), ("frame_capacity", _sz), ("desc", PlanesDesc), ("frame_length", _sz), ("rc", _i)]
+
+
+class PlanesBatchStats(ctypes.Structure):  # hsrans_planes_batch_stats
+    _fields_ = [(n, _u32) for n in ("launches", "members", "planes", "stored")]
+
+
+class PlanesSetInfo(ctypes.Structure):  # hsrans_planes_set_info_t
+    _fields_ = [(n, _u32) for n in ("members", "coded", "stored", "launches", "merge_tasks", "reserved")] + [("work_bytes", _sz)]
+
+
 class PlanesGatherInfo(ctypes.Structure):  # hsrans_planes_gather_info_t
     _fields_ = [(n, _u32) for n in ("coded", "stored", "rows", "merge_tasks", "launches")]
 
@@ -269,6 +283,14 @@ SIGNATURES = {
     "hsrans_decode_device_planes": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsrans_planes_status": (_i, [_vp, _vp, _vp, _vp]),
     "hsrans_planes_info": (_i, [_vp, _P(PlanesInfo)]),
+    "hsrans_planes_batch_workspace_bytes": (_sz, [_vp, _vp, _u32]),
+    "hsrans_planes_batch_tasks": (_sz, [_vp, _u32, _vp]),
+    "hsrans_encode_device_planes_batch": (_i, [_vp, _P(PlanesMember), _u32, _vp, _sz, _vp, _P(_vp), _P(PlanesBatchStats)]),
+    "hsrans_planes_set_create": (_i, [_vp, _P(PlanesDesc), _P(_vp), _u32, _P(_vp)]),
+    "hsrans_planes_set_destroy": (None, [_vp]),
+    "hsrans_planes_set_info": (_i, [_vp, _P(PlanesSetInfo)]),
+    "hsrans_decode_device_planes_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hsrans_planes_set_status": (_i, [_vp, _vp, _vp, _vp]),
     "hsrans_planes_gather_create": (_i, [_vp, _vp, _vp, _sz, _P(_vp)]),
     "hsrans_planes_gather_destroy": (None, [_vp]),
     "hsrans_planes_gather_workspace_bytes": (_sz, [_u32, _u32, _u64]),

@@ -17,7 +17,7 @@ from ._abi import (  # noqa: F401  (the structures, constants and loader are spe
     BLOCK, COMM_ID_BYTES, ENC_INDEPENDENT_BLOCKS, MT, PLANES_MAX, PLANES_STORE_INCOMPRESSIBLE, RAW, SHARD_DECODE_AND_EXCHANGE, SHARD_DECODE_ONLY,
     SHARD_EXCHANGE_ONLY, BatchInfo, Calibration, EncodeBatchStats, EncodeExBatchStats, EncodeExMember, EncodeMember, EncodeOpts, GatherBatchTask,
     GatherMember, GatherSetInfo, GatherTask, Hist, HsransError, IndexingBatchStats, IndexingMember, LaunchFacts, LaunchInfo, MemberRange, PlanKind,
-    PlanesDesc, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherTask, PlanesInfo, QueueStats, Range, Shard, ShardedInfo, _sz, _vp, lib_path,
+    PlanesBatchStats, PlanesDesc, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherTask, PlanesInfo, PlanesMember, PlanesSetInfo, QueueStats, Range, Shard, ShardedInfo, _sz, _vp, lib_path,
     load_library)
 
 
@@ -449,6 +449,30 @@ def planes_workspace_bytes(itemsize: int, elements: int) -> int:
     return load_library().hsrans_planes_workspace_bytes(itemsize, elements)
 
 
+def planes_batch_workspace_bytes(itemsizes, elements) -> int:
+    """hsrans_planes_batch_workspace_bytes: the workspace of encode_device_planes_batch / decode_device_planes_batch over tensors of
+    ``itemsizes[k]``-byte items and ``elements[k]`` elements — the sum of the members' planes_workspace_bytes (0: a bad member, no member,
+    lists of different lengths, an overflow)."""
+    itemsizes, elements = list(itemsizes), list(elements)
+    if len(itemsizes) != len(elements) or any(not 0 <= int(v) < 1 << 32 for v in itemsizes) or any(not 0 <= int(v) < 1 << 64 for v in elements):
+        return 0
+    K = len(elements)
+    return int(load_library().hsrans_planes_batch_workspace_bytes((ctypes.c_uint32 * max(K, 1))(*itemsizes), (_sz * max(K, 1))(*elements), K))
+
+
+def planes_batch_tasks(elements) -> tuple:
+    """hsrans_planes_batch_tasks: ``(total, first_task)`` — the workgroups of the one split or merge launch over tensors of ``elements[k]``
+    elements and their exclusive prefix (K + 1 entries, the last the total).  ``(0, [])``: no member, a member without elements or with
+    more than 2^42, or 2^31 tasks or more."""
+    elements = list(elements)
+    K = len(elements)
+    if any(not 0 <= int(v) < 1 << 64 for v in elements):
+        return 0, []
+    first = (ctypes.c_uint32 * (K + 1))()
+    total = int(load_library().hsrans_planes_batch_tasks((_sz * max(K, 1))(*elements), K, first))
+    return total, (list(first) if total else [])
+
+
 def planes_split(array) -> list:
     """hsrans_planes_split on the host: the byte planes of a contiguous array of 2-, 4- or 8-byte items (plane p = byte p of every
     item, in memory order), a uint8 array of ``array.size`` bytes each."""
@@ -550,6 +574,24 @@ class Planes(_Handle):
         info = PlanesInfo()
         load_library().hsrans_planes_info(self.handle, ctypes.byref(info))
         return _as_dict(info)
+
+
+class PlanesSet(_Handle):
+    """hsrans_planes_set: many frames' descriptors bound to their planes' device plans (Context.make_planes_set /
+    Context.decode_device_planes_batch)."""
+    _destroy = "hsrans_planes_set_destroy"
+
+    def __init__(self, ctx: "Context", handle, descs, plans_lists):
+        self.ctx, self.handle, self.descs, self.plans = ctx, handle, list(descs), [list(p) for p in plans_lists]  # (keeps the planes' plans alive)
+
+    def info(self) -> dict:
+        """members; coded and stored planes of all members; the kernels of one decode (the batch's launches + the merge); the merge's
+        workgroups; the workspace a decode needs"""
+        info = PlanesSetInfo()
+        load_library().hsrans_planes_set_info(self.handle, ctypes.byref(info))
+        d = _as_dict(info)
+        del d["reserved"]
+        return d
 
 
 class PlanesGather(_Handle):
@@ -1194,6 +1236,82 @@ class Context(_Handle):
         codes = (ctypes.c_int * PLANES_MAX)()
         self.L.hsrans_planes_status(self.handle, planes.handle, _stream(stream), codes)
         return list(codes)[: planes.desc.elem_size]
+
+    def encode_device_planes_batch(self, tensors, d_frames, d_work: torch.Tensor, states: int = 64, bits: int = 11, block_size: int = 1 << 16,
+                                   index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True, options=None,
+                                   stream: torch.cuda.Stream | None = None, stats: dict | None = None) -> list:
+        """hsrans_encode_device_planes_batch: many contiguous CUDA tensors (``element_size()`` 2, 4 or 8, any mix) into their frames
+        ``d_frames[k]`` (``planes_capacity`` bytes each) in one call; ``d_work``: ``planes_batch_workspace_bytes`` bytes.  The keywords are
+        every member's settings; ``options`` (a list with a dict or None per member) overrides ``states``, ``bits``, ``block_size``,
+        ``index_interval`` and ``store_incompressible`` for single members.  Each member gets what ``encode_device_planes`` gives it.
+        Returns a list of ``(frame_length, desc, plans)`` as that call's.  ``stats``: filled with hsrans_planes_batch_stats.  Synchronous.
+        Raises HsransError naming the first member at fault; the error carries ``code`` and ``rcs``."""
+        tensors, d_frames = list(tensors), list(d_frames)
+        K = len(tensors)
+        if len(d_frames) != K or (options is not None and len(options) != K):
+            raise HsransError(f"encode_device_planes_batch: one frame (and one options entry) per tensor: {K} tensors")
+        if any(not t.is_contiguous() for t in tensors):
+            raise HsransError("encode_device_planes_batch takes contiguous tensors")
+        defaults = dict(states=states, bits=bits, block_size=block_size, index_interval=index_interval, store_incompressible=store_incompressible)
+        arr = (PlanesMember * max(K, 1))()
+        for k, t in enumerate(tensors):
+            o = dict(options[k]) if options is not None and options[k] is not None else {}
+            unknown = set(o) - set(defaults)
+            if unknown:
+                raise HsransError(f"encode_device_planes_batch: member {k}: unknown options {sorted(unknown)}")
+            o = dict(defaults, **o)
+            e = arr[k]
+            e.elem_size, e.states, e.bits, e.block_size, e.index_interval = t.element_size(), o["states"], o["bits"], o["block_size"], o["index_interval"]
+            e.flags = PLANES_STORE_INCOMPRESSIBLE if o["store_incompressible"] else 0
+            e.d_in, e.elements = t.data_ptr(), t.numel()
+            e.d_frame, e.frame_capacity = d_frames[k].data_ptr(), d_frames[k].numel()
+        handles = (_vp * (max(K, 1) * PLANES_MAX))()
+        st = PlanesBatchStats()
+        rc = self.L.hsrans_encode_device_planes_batch(self.handle, arr, K, d_work.data_ptr(), d_work.numel(), _stream(stream, d_work.device),
+                                                      handles if want_plans else None, ctypes.byref(st))
+        if stats is not None:
+            stats.update(_as_dict(st))
+        if rc != 0:
+            rcs = [int(arr[k].rc) for k in range(K)]
+            failed = [k for k in range(K) if rcs[k] != 0]
+            raise _members_error("hsrans_encode_device_planes_batch", rc, failed if len(failed) < K else [], rcs=rcs)
+        return [(int(arr[k].frame_length), PlanesDesc.from_buffer_copy(arr[k].desc),
+                 [DevicePlan(self, _vp(handles[k * PLANES_MAX + p])) if want_plans and handles[k * PLANES_MAX + p] else None for p in range(arr[k].elem_size)])
+                for k in range(K)]
+
+    def make_planes_set(self, descs, plans_lists) -> PlanesSet:
+        """hsrans_planes_set_create: ``descs[k]`` and ``plans_lists[k]`` are member k's PlanesDesc and its planes' DevicePlans (None exactly
+        for the stored planes), as ``make_planes`` takes them for one frame."""
+        descs, plans_lists = list(descs), [list(p) for p in plans_lists]
+        K = len(descs)
+        if len(plans_lists) != K or any(len(p) != d.elem_size for d, p in zip(descs, plans_lists)):
+            raise HsransError("make_planes_set: one list of plans per descriptor, one plan (or None) per plane")
+        darr = (PlanesDesc * max(K, 1))(*descs)
+        harr = (_vp * (max(K, 1) * PLANES_MAX))()
+        for k, plans in enumerate(plans_lists):
+            harr[k * PLANES_MAX: k * PLANES_MAX + len(plans)] = list(_handle_array(plans))
+        h = _vp()
+        _check(self.L.hsrans_planes_set_create(self.handle, darr, harr, K, ctypes.byref(h)), "hsrans_planes_set_create")
+        return PlanesSet(self, h, descs, plans_lists)
+
+    def decode_device_planes_batch(self, pset: PlanesSet, d_frames, out_tensors, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """hsrans_decode_device_planes_batch: the frames ``d_frames[k]`` back into the elements of ``out_tensors[k]`` (contiguous, as many
+        bytes as were encoded); ``d_work``: ``pset.info()["work_bytes"]`` bytes.  Asynchronous on ``stream`` (default: torch's current stream)."""
+        d_frames, out_tensors = list(d_frames), list(out_tensors)
+        if len(d_frames) != len(pset.descs) or len(out_tensors) != len(pset.descs):
+            raise HsransError(f"decode_device_planes_batch: one frame and one output per member: {len(pset.descs)}")
+        if any(not t.is_contiguous() for t in out_tensors):
+            raise HsransError("decode_device_planes_batch takes contiguous output tensors")
+        frames, frame_lengths = _tensor_arrays(d_frames)
+        outs, out_caps = _tensor_arrays(out_tensors, [t.numel() * t.element_size() for t in out_tensors])
+        _check(self.L.hsrans_decode_device_planes_batch(self.handle, pset.handle, frames, frame_lengths, outs, out_caps, d_work.data_ptr(), d_work.numel(),
+                                                        _stream(stream, d_work.device)), "hsrans_decode_device_planes_batch")
+
+    def planes_set_status(self, pset: PlanesSet, stream: torch.cuda.Stream | None = None) -> list:
+        """hsrans_planes_set_status: synchronises ``stream`` and returns every member's status (its first failing plane's, else 0)"""
+        codes = (ctypes.c_int * max(len(pset.descs), 1))()
+        self.L.hsrans_planes_set_status(self.handle, pset.handle, _stream(stream), codes)
+        return list(codes)[: len(pset.descs)]
 
     def make_planes_gather(self, planes: Planes, d_frame: torch.Tensor, frame_length: int | None = None) -> PlanesGather:
         """hsrans_planes_gather_create: binds ``planes`` to the frame in the CUDA uint8 tensor ``d_frame`` (16-byte aligned) for

@@ -60,6 +60,48 @@ void drop_plans(hsrans_dplan **plans, uint32_t W)
 }
 } // namespace
 
+bool planes_encode_check(uint32_t W, int states, uint32_t bits, const void *d_in, size_t elements, const void *d_frame, size_t frame_capacity, uint32_t block_size,
+                         uint32_t index_interval, uint32_t flags, bool want_plans, PlanesEncShape *out)
+{
+  if (!width_ok(W) || (flags & ~HSRANS_PLANES_STORE_INCOMPRESSIBLE) != 0 || !aligned16(d_in) || !aligned16(d_frame))
+    return false;
+  if (!(states == 32 || states == 64) || elements == 0 || elements > kPlanesMaxElements)
+    return false;
+  out->stride = plane_stride(states, elements);
+  out->work_stride = up256(elements);
+  EncShape sh;
+  if (!mt_shape(states, bits, elements, out->stride, block_size, index_interval, want_plans, &sh) || frame_capacity < W * out->stride)
+    return false;
+  out->n_blocks = sh.n_blocks;
+  return true;
+}
+
+int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans)
+{
+  if (ctx == nullptr || desc == nullptr || dplans == nullptr || !width_ok(desc->elem_size) || !valid_codec(HSRANS_MT, (int)desc->states, desc->bits) ||
+      desc->elements == 0 || desc->elements > kPlanesMaxElements || (desc->stored_mask >> desc->elem_size) != 0)
+    return HSRANS_E_ARG;
+  const uint32_t W = desc->elem_size;
+  std::vector<Span> spans;
+  uint64_t end = 0;
+  for (uint32_t p = 0; p < W; p++)
+  {
+    const bool is_stored = (desc->stored_mask >> p) & 1;
+    const hsrans_dplan *d = dplans[p];
+    if ((desc->offset[p] & 15) != 0 || desc->length[p] == 0 || desc->offset[p] + desc->length[p] < desc->offset[p] || is_stored != (d == nullptr))
+      return HSRANS_E_ARG;
+    if (is_stored ? desc->length[p] != desc->elements
+                  : (d->ctx != ctx || d->hdr.decoded_len != desc->elements || d->hdr.stream_len != desc->length[p] || d->hdr.states != desc->states ||
+                     d->hdr.bits != desc->bits))
+      return HSRANS_E_ARG;
+    spans.push_back(Span{(uintptr_t)desc->offset[p], (uintptr_t)(desc->offset[p] + up16(desc->length[p])), true}); // (as writes: no two planes share bytes)
+    end = std::max<uint64_t>(end, desc->offset[p] + desc->length[p]);
+  }
+  if (!spans_disjoint(spans) || desc->frame_length < end)
+    return HSRANS_E_ARG;
+  return HSRANS_OK;
+}
+
 extern "C" size_t hsrans_planes_capacity(uint32_t elem_size, int states, size_t elements)
 {
   if (!width_ok(elem_size) || (states != 32 && states != 64) || elements == 0)
@@ -144,16 +186,15 @@ try
   const uint32_t W = elem_size;
   for (uint32_t p = 0; out_dplans != nullptr && p < W; p++)
     out_dplans[p] = nullptr; // (the caller's array may hold anything: nothing to destroy yet)
-  if (ctx == nullptr || desc == nullptr || (flags & ~HSRANS_PLANES_STORE_INCOMPRESSIBLE) != 0 || !aligned16(d_in) || !aligned16(d_frame) || !aligned16(d_work))
+  if (ctx == nullptr || desc == nullptr || !aligned16(d_work))
     return 0;
 
   // ---- everything checked before anything is launched: each plane by its single call's rules (mt_shape), then the call's own ----
-  EncShape sh;
-  if (!(states == 32 || states == 64) || elements == 0 || elements > kPlanesMaxElements)
+  PlanesEncShape ps;
+  if (!planes_encode_check(W, states, bits, d_in, elements, d_frame, frame_capacity, block_size, index_interval, flags, out_dplans != nullptr, &ps) ||
+      (uint64_t)ps.n_blocks * W >= kMaxBatchTasks)
     return 0;
-  const size_t stride = plane_stride(states, elements), work_stride = up256(elements);
-  if (!mt_shape(states, bits, elements, stride, block_size, index_interval, out_dplans != nullptr, &sh) || (uint64_t)sh.n_blocks * W >= kMaxBatchTasks)
-    return 0;
+  const size_t stride = ps.stride, work_stride = ps.work_stride;
   Carve frame, work; // (the frame and the workspace: W regions each)
   size_t offset[HSRANS_PLANES_MAX] = {};
   for (uint32_t p = 0; p < W; p++)
@@ -257,27 +298,9 @@ try
   if (out_planes == nullptr)
     return HSRANS_E_ARG;
   *out_planes = nullptr;
-  if (ctx == nullptr || desc == nullptr || dplans == nullptr || !width_ok(desc->elem_size) || !valid_codec(HSRANS_MT, (int)desc->states, desc->bits) ||
-      desc->elements == 0 || desc->elements > kPlanesMaxElements || (desc->stored_mask >> desc->elem_size) != 0)
+  if (planes_desc_check(ctx, desc, dplans) != HSRANS_OK)
     return HSRANS_E_ARG;
   const uint32_t W = desc->elem_size;
-  std::vector<Span> spans;
-  uint64_t end = 0;
-  for (uint32_t p = 0; p < W; p++)
-  {
-    const bool is_stored = (desc->stored_mask >> p) & 1;
-    const hsrans_dplan *d = dplans[p];
-    if ((desc->offset[p] & 15) != 0 || desc->length[p] == 0 || desc->offset[p] + desc->length[p] < desc->offset[p] || is_stored != (d == nullptr))
-      return HSRANS_E_ARG;
-    if (is_stored ? desc->length[p] != desc->elements
-                  : (d->ctx != ctx || d->hdr.decoded_len != desc->elements || d->hdr.stream_len != desc->length[p] || d->hdr.states != desc->states ||
-                     d->hdr.bits != desc->bits))
-      return HSRANS_E_ARG;
-    spans.push_back(Span{(uintptr_t)desc->offset[p], (uintptr_t)(desc->offset[p] + up16(desc->length[p])), true}); // (as writes: no two planes share bytes)
-    end = std::max<uint64_t>(end, desc->offset[p] + desc->length[p]);
-  }
-  if (!spans_disjoint(spans) || desc->frame_length < end)
-    return HSRANS_E_ARG;
 
   hsrans_planes *pl = new (std::nothrow) hsrans_planes;
   if (pl == nullptr)

@@ -277,6 +277,20 @@ struct hsrans_planes
   std::vector<hsrans_dplan *> dplans; // of the coded planes, in batch order
 };
 
+// What hsrans_encode_device_planes and every member of hsrans_encode_device_planes_batch share (hsrans_capi_planes.cpp): the single call's
+// rules for one tensor but the workspace's and the overlap rule — element size, flags, d_in and d_frame set and 16-byte aligned, states,
+// elements, each plane by mt_shape, frame_capacity >= elem_size * stride.  *out: a coded plane's room in the frame, a plane's room in the
+// workspace, a plane's mt_ blocks.
+struct PlanesEncShape
+{
+  size_t stride = 0, work_stride = 0;
+  uint32_t n_blocks = 0;
+};
+bool planes_encode_check(uint32_t W, int states, uint32_t bits, const void *d_in, size_t elements, const void *d_frame, size_t frame_capacity, uint32_t block_size,
+                         uint32_t index_interval, uint32_t flags, bool want_plans, PlanesEncShape *out);
+// hsrans_planes_create's rules for a descriptor and its planes' plans (dplans[p] null exactly for the stored planes): HSRANS_OK or HSRANS_E_ARG
+int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans);
+
 // (Re)fills a device plan from a validated host plan blob; one launch of a filled device plan (hsrans_dplan.cpp)
 int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_size, const PlanHeader &h, hipStream_t s);
 int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity, hipStream_t s, uint64_t stream_lo = 0,

@@ -26,6 +26,29 @@ struct PlanePtrs // (by value in the kernel arguments; entries >= W unused)
 hipError_t launch_planes_split(uint32_t W, const void *in, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
 hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, uint64_t n, void *out, hipStream_t stream);
 
+// ---- many tensors in one launch (hsrans_*_device_planes_batch): k_planes_split_batch, k_planes_merge_batch, k_planes_store_batch
+// (hsrans_planes_batch.hip), each driven by a table of these records in device memory, one workgroup per task ----
+// A member's tasks are the workgroups of its single launch — planes_tasks_of(n), the last one moving the n % 16 tail elements — and
+// first_task is the exclusive prefix of them over the table: a workgroup finds its member as the last one with first_task <= its index.
+// W may differ from member to member.  k_planes_store_batch copies: W is 1, plane[0] the n bytes read, `elements` where they go.
+struct PlanesBatchMember
+{
+  uint8_t *elements;         // split: read; merge and store: written
+  uint8_t *plane[kPlanesMax]; // split: written; merge and store: read (entries >= W unused)
+  uint64_t n;                // elements (store: bytes)
+  uint32_t W, first_task;
+};
+constexpr uint32_t planes_tasks_of(uint64_t n) // (host and device; n <= kPlanesMaxElements: at most 2^30)
+{
+  return n / 16 > 256 ? (uint32_t)((n / 16 + 255) / 256) : 1;
+}
+// asynchronous on `stream`, one kernel each, n_tasks workgroups (the table's task total, 1 .. 2^31 - 1); the table's pointers are the
+// caller's to check: set, 16-byte aligned, W in {2, 4, 8} (store: 1), n in 1..kPlanesMaxElements (hipErrorInvalidValue: a null table, no
+// member, a task total out of range)
+hipError_t launch_planes_split_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+hipError_t launch_planes_merge_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+hipError_t launch_planes_store_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+
 // One workgroup's work of k_planes_merge_ranges (hsrans_planes_gather_task, include/hsrans_hip.h): the elements [src + lo, src + hi) of the
 // tensor — src a multiple of 16, lo < 16, hi <= kPlanesGatherTaskElements — whose bytes lie at work_pos + (element - src) of a workspace region
 // and at the element's own index of a stored plane, and go to output element (element + dst_delta)

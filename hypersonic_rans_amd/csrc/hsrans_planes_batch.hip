@@ -1,0 +1,194 @@
+// hsrans_planes_batch.hip — k_planes_split_batch, k_planes_merge_batch and k_planes_store_batch: the byte-plane kernels for many tensors in
+// ONE launch (hsrans_*_device_planes_batch).  A table of PlanesBatchMember records in device memory drives each: a workgroup finds its
+// member by a binary search over the records' first_task — the same on every lane, on scalar loads — and then does exactly what workgroup
+// (blockIdx.x - first_task) of the member's single launch does (hsrans_planes.hip: 16 elements per lane through planes_shuffle.h, the last
+// n % 16 elements byte by byte by the first lanes of the member's last workgroup).  W is read from the record: 2-, 4- and 8-byte members
+// share a launch.  The store kernel is the same walk with nothing to shuffle: 16 bytes per lane, the tail byte by byte.
+#include "hsrans_planes.h"
+#include "planes_shuffle.h"
+
+namespace hsrans
+{
+namespace
+{
+using namespace planes_detail;
+
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
+// a pointer read from a record, the same on every lane; it is to device memory, which the compiler cannot see of a pointer that comes out
+// of memory: made a pointer to the global address space first, it is addressed through with global_ instead of flat_ instructions
+__device__ __forceinline__ uint8_t *uni_ptr(uint8_t *p)
+{
+  typedef __attribute__((address_space(1))) uint8_t global_u8;
+  return (uint8_t *)(global_u8 *)uni64((uint64_t)p);
+}
+
+// the member of task t: the last record with first_task <= t (first_task[0] is 0 and t is below the table's total)
+__device__ __forceinline__ const PlanesBatchMember *member_of(const PlanesBatchMember *__restrict__ members, uint32_t count, uint32_t t)
+{
+  uint32_t lo = 0, hi = count;
+  while (hi - lo > 1)
+  {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (uni(members[mid].first_task) <= t)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return members + lo;
+}
+
+// What one workgroup sees of its member: its index among the member's workgroups, whether it is the last of them, and the lane's 16 elements
+struct Task
+{
+  uint64_t n, whole, lane;
+  bool last;
+};
+__device__ __forceinline__ Task task_of(const PlanesBatchMember *m)
+{
+  Task t;
+  t.n = uni64(m->n);
+  t.whole = t.n / kLaneElements;
+  const uint32_t block = blockIdx.x - uni(m->first_task);
+  t.lane = (uint64_t)block * kThreads + threadIdx.x;
+  t.last = block + 1 == planes_tasks_of(t.n);
+  return t;
+}
+
+template <uint32_t W>
+__device__ __forceinline__ void split_task(const PlanesBatchMember *m)
+{
+  const Task t = task_of(m);
+  const uint8_t *in = uni_ptr(m->elements);
+  uint8_t *planes[W];
+#pragma unroll
+  for (uint32_t p = 0; p < W; p++)
+    planes[p] = uni_ptr(m->plane[p]);
+  if (t.lane < t.whole)
+  {
+    uint32_t e[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(in + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+    split16<W>(e, pl);
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      store16(planes[p] + t.lane * kLaneElements, pl[p]);
+  }
+  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
+  if (t.last && threadIdx.x < tail)
+  {
+    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      planes[p][i] = in[i * W + p];
+  }
+}
+
+template <uint32_t W>
+__device__ __forceinline__ void merge_task(const PlanesBatchMember *m)
+{
+  const Task t = task_of(m);
+  uint8_t *out = uni_ptr(m->elements);
+  const uint8_t *planes[W];
+#pragma unroll
+  for (uint32_t p = 0; p < W; p++)
+    planes[p] = uni_ptr(m->plane[p]);
+  if (t.lane < t.whole)
+  {
+    uint32_t e[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      load16(planes[p] + t.lane * kLaneElements, pl[p]);
+    merge16<W>(pl, e);
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      store16(out + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+  }
+  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
+  if (t.last && threadIdx.x < tail)
+  {
+    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      out[i * W + p] = planes[p][i];
+  }
+}
+
+// grid: the table's task total; count: its records
+__global__ __launch_bounds__(kThreads) void k_planes_split_batch(const PlanesBatchMember *__restrict__ members, uint32_t count)
+{
+  const PlanesBatchMember *m = member_of(members, count, blockIdx.x);
+  const uint32_t W = uni(m->W);
+  if (W == 2)
+    split_task<2>(m);
+  else if (W == 4)
+    split_task<4>(m);
+  else if (W == 8)
+    split_task<8>(m);
+}
+
+__global__ __launch_bounds__(kThreads) void k_planes_merge_batch(const PlanesBatchMember *__restrict__ members, uint32_t count)
+{
+  const PlanesBatchMember *m = member_of(members, count, blockIdx.x);
+  const uint32_t W = uni(m->W);
+  if (W == 2)
+    merge_task<2>(m);
+  else if (W == 4)
+    merge_task<4>(m);
+  else if (W == 8)
+    merge_task<8>(m);
+}
+
+// plane[0] -> elements, n bytes: not one byte past them
+__global__ __launch_bounds__(kThreads) void k_planes_store_batch(const PlanesBatchMember *__restrict__ members, uint32_t count)
+{
+  const PlanesBatchMember *m = member_of(members, count, blockIdx.x);
+  const Task t = task_of(m);
+  const uint8_t *src = uni_ptr(m->plane[0]);
+  uint8_t *dst = uni_ptr(m->elements);
+  if (t.lane < t.whole)
+  {
+    uint32_t w[4];
+    load16(src + t.lane * 16, w);
+    store16(dst + t.lane * 16, w);
+  }
+  const uint32_t tail = (uint32_t)(t.n % 16);
+  if (t.last && threadIdx.x < tail)
+  {
+    const uint64_t i = t.whole * 16 + threadIdx.x;
+    dst[i] = src[i];
+  }
+}
+
+bool launch_ok(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks)
+{
+  return d_members != nullptr && ((uintptr_t)d_members & 7) == 0 && count != 0 && n_tasks >= count && n_tasks <= 0x7FFFFFFFu;
+}
+} // namespace
+
+hipError_t launch_planes_split_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
+{
+  if (!launch_ok(d_members, count, n_tasks))
+    return hipErrorInvalidValue;
+  k_planes_split_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_merge_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
+{
+  if (!launch_ok(d_members, count, n_tasks))
+    return hipErrorInvalidValue;
+  k_planes_merge_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_store_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
+{
+  if (!launch_ok(d_members, count, n_tasks))
+    return hipErrorInvalidValue;
+  k_planes_store_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
+  return hipGetLastError();
+}
+
+} // namespace hsrans

@@ -867,6 +867,97 @@ typedef struct hsrans_planes_info_t
 } hsrans_planes_info_t;
 int hsrans_planes_info(const hsrans_planes *planes, hsrans_planes_info_t *info);
 /* ------------------------------------------------------------------------------------------------------------
+ * Many tensors' frames in one call — a checkpoint's parameters, a layer's experts, the pages of a cache — as the codec
+ * batches stand to their single calls: K tensors pay the split, the codec batch, the store and the merge once, not K times.
+ *
+ * Member equivalence.  Member k of hsrans_encode_device_planes_batch gets byte for byte what hsrans_encode_device_planes
+ * gives it with the same arguments (its own frame, and its region of the workspace as d_work): the same frame bytes, the same
+ * desc, the same stored planes (stream_length >= elements, by the member's own flags) and the same plans, at
+ * out_dplans[HSRANS_PLANES_MAX * k + p] — NULL for a stored plane and for p >= elem_size.  frame_length is desc.frame_length.
+ * elem_size, states, bits, block_size, index_interval and flags may differ from member to member.
+ * Workspace, a pure function of the shapes: member k's region starts at the sum of the earlier members'
+ * hsrans_planes_workspace_bytes (multiples of 256) and holds plane p at p * up256(elements), as the single call's.
+ * hsrans_planes_batch_workspace_bytes is that sum; 0 for count 0, a NULL array, a member whose own value is 0, or an overflow.
+ * Tasks.  The split and the merge are one launch each over all members, one workgroup per task: member k's tasks are the
+ * workgroups of its single launch, max(1, ceil(floor(elements / 16) / 256)).  hsrans_planes_batch_tasks writes their exclusive
+ * prefix and total to first_task[0 .. count] (may be NULL) and returns the total; 0 for a NULL `elements`, count 0, a member
+ * with 0 elements or more than 2^42, or a total of 2^31 or more (one launch's limit: the entries refuse by this same function).
+ * Launches, independent of count: one split launch, ONE hsrans_encode_device_batch over all the planes as mt_ members
+ * (through that public entry: its launch count, limits and synchronisations are that call's), one store launch that copies the
+ * stored planes from the workspace into their frames (none when nothing is stored), one settle of the stream behind it.  The
+ * member table goes up in one copy, the store's records in one more; both pass through the context's task buffers (below).
+ * stats: launches = the planes kernels + the codec batch's; members; planes = the sum of elem_size; stored.
+ * Validation before anything is launched or written.  HSRANS_E_ARG: a NULL ctx or members, count 0; any member that
+ * hsrans_encode_device_planes refuses (see there); d_work NULL or not 16-byte aligned; work_bytes below
+ * hsrans_planes_batch_workspace_bytes; more than 65,536 planes or 2^24 mt_ blocks or more in all (the codec batch's limits);
+ * 2^31 tasks or more; any intersection in which a written span takes part among the members' element buffers (read), their
+ * frames over frame_capacity and the workspace over work_bytes (written).  Then every frame_length is 0, every desc zero, every
+ * plan NULL and no device byte has changed; rc is HSRANS_E_ARG for the members whose own arguments were refused.
+ * Failure after launch.  Whatever makes hsrans_encode_device_batch return other than HSRANS_OK — a plane whose stream outgrows
+ * hsrans_capacity, as in the single call; the runtime — fails the whole call with that code: every frame_length 0, every desc
+ * zero, every rc that code, the plans destroyed.  The workspace and the frames may have been written.
+ * Synchronisation.  hsrans_encode_device_planes_batch synchronises hip_stream, like every encoder here.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct hsrans_planes_member
+{
+  uint32_t elem_size;      /* 2, 4 or 8 */
+  int states;              /* 32 or 64 */
+  uint32_t bits;           /* 10..15 */
+  uint32_t block_size, index_interval, flags; /* as hsrans_encode_device_planes */
+  const void *d_in;        /* device, 16-byte aligned, elem_size * elements bytes */
+  size_t elements;
+  void *d_frame;           /* device, 16-byte aligned, frame_capacity >= hsrans_planes_capacity(elem_size, states, elements) */
+  size_t frame_capacity;
+  hsrans_planes_desc desc; /* out */
+  size_t frame_length;     /* out: desc.frame_length, 0 = the call failed */
+  int rc;                  /* out: HSRANS_OK, or why this member made the call fail */
+} hsrans_planes_member;
+typedef struct hsrans_planes_batch_stats
+{
+  uint32_t launches, members, planes, stored;
+} hsrans_planes_batch_stats;
+size_t hsrans_planes_batch_workspace_bytes(const uint32_t *elem_sizes, const size_t *elements, uint32_t count);
+size_t hsrans_planes_batch_tasks(const size_t *elements, uint32_t count, uint32_t *first_task /* [count + 1] or NULL */);
+int hsrans_encode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_member *members, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
+                                      hsrans_dplan **out_dplans /* [count * HSRANS_PLANES_MAX] or NULL */, hsrans_planes_batch_stats *stats /* may be NULL */);
+/* The decode side: `count` descriptors bound to their planes' device plans, dplans[HSRANS_PLANES_MAX * k + p] plane p of
+ * member k.  Every member is checked by hsrans_planes_create's rules (HSRANS_E_ARG); ONE hsrans_batch is made over all coded
+ * planes of all members, in member and plane order (none when every plane is stored); a plan that appears twice is refused as
+ * hsrans_dplan_batch_create refuses it.  The plans must outlive the set.
+ * hsrans_decode_device_planes_batch: member k's frame d_frames[k] -> d_outs[k] (elem_size * elements bytes).  ONE
+ * hsrans_decode_device_batch of all coded planes into d_work (the encoder's layout), then ONE merge launch over all members
+ * behind it on the same stream; stored planes are read by the merge straight from their frames.  Asynchronous on hip_stream,
+ * no device allocation, no synchronisation.  Launch count: the batch's + 1, as hsrans_planes_set_info reports it — not a
+ * constant: the codec batch packs at most 32 grouped members into one launch (kBatchMax), so a set of many coded planes
+ * takes ceil(planes / 32) grouped launches per histogram width, and members no shared kernel takes (no checkpoints) one each.
+ * The per-call member table (the frames' and outputs' addresses) goes up through a region of the context's task buffers, as
+ * hsrans_decode_device_planes_gather sends its tasks: the arrays are read before the call returns, no allocation beyond what
+ * that buffer does, and the call is ordered with the other gathers of the context.
+ * HSRANS_E_ARG, nothing launched: a NULL handle or array, a set of another context; any d_frames[k], d_outs[k] or d_work NULL
+ * or not 16-byte aligned; frame_lengths[k] below the descriptor's; out_capacities[k] < elem_size * elements; work_bytes below
+ * the set's (hsrans_planes_set_info: hsrans_planes_batch_workspace_bytes of its members); any intersection in which an output
+ * or the workspace takes part among all frames over frame_lengths (read; frames may share), all outputs over out_capacities
+ * and the workspace over work_bytes (written).  HSRANS_E_HIP (the runtime refused an upload or a launch) may leave the
+ * workspace written and the outputs not.
+ * hsrans_planes_set_status synchronises hip_stream; member_status[k] is the status of member k's first failing plane, or
+ * HSRANS_OK; returns the first failure.  With no batch it only settles the stream.
+ * Limits: the codec batches' (65,536 planes, fewer than 2^24 mt_ blocks per encode) and fewer than 2^31 tasks per launch. */
+typedef struct hsrans_planes_set hsrans_planes_set;
+int hsrans_planes_set_create(hsrans_ctx *ctx, const hsrans_planes_desc *descs, hsrans_dplan *const *dplans /* [count * HSRANS_PLANES_MAX] */, uint32_t count,
+                             hsrans_planes_set **out);
+void hsrans_planes_set_destroy(hsrans_planes_set *set);
+typedef struct hsrans_planes_set_info_t
+{
+  uint32_t members, coded, stored; /* members; planes of all members */
+  uint32_t launches;               /* kernels of one hsrans_decode_device_planes_batch: the batch's launches + the merge */
+  uint32_t merge_tasks, reserved;  /* workgroups of the merge launch */
+  size_t work_bytes;               /* the workspace a decode needs */
+} hsrans_planes_set_info_t;
+int hsrans_planes_set_info(const hsrans_planes_set *set, hsrans_planes_set_info_t *info);
+int hsrans_decode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, void *const *d_outs,
+                                      const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream);
+int hsrans_planes_set_status(hsrans_ctx *ctx, hsrans_planes_set *set, void *hip_stream, int *member_status /* [count] or NULL */);
+/* ------------------------------------------------------------------------------------------------------------
  * Element ranges of a frame that stays compressed in device memory — embedding rows, one expert's slice, pages of a cache.
  * For every r < count the elements [ranges[r].offset, + ranges[r].length) of the tensor land at
  * (uint8_t *)d_out + ranges[r].dst_offset * elem_size; no other byte of d_out is written.  All three fields of hsrans_range

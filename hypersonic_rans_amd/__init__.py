@@ -50,9 +50,14 @@ from .api import (  # noqa: F401
     planes_batch_workspace_bytes,
     planes_batch_tasks,
     PlanesSet,
+    planes_gather_batch_workspace_bytes,
+    planes_gather_batch_tasks,
+    PlanesGatherSet,
+    PlanesGatherBatchTask,
+    PlanesGatherSetInfo,
 )
 
 __all__ = [
     "RAW", "BLOCK", "MT", "Context", "HsransError", "capacity", "encode", "block_choices", "BLOCK_CHOICE", "make_hist", "plan_build", "plan_chain_count",
-    "plan_chain_range", "plan_decoded_length", "plan_slice", "plan_stream_ranges", "plan_thin", "index_boundaries", "batch_deal", "index_boundaries_batch", "gather_segment", "gather_tasks", "gather_workspace_bytes", "gather_batch_workspace_bytes", "gather_batch_tasks", "GatherSet", "IndexingMember", "IndexingBatchStats", "planes_capacity", "planes_workspace_bytes", "planes_split", "planes_merge", "PlanesDesc", "Planes", "planes_gather_workspace_bytes", "planes_gather_tasks", "PlanesGather", "planes_gather_indirect_workspace_bytes", "PlanesGatherIndirectInfo", "planes_batch_workspace_bytes", "planes_batch_tasks", "PlanesSet", "lib_path", "load_library",
+    "plan_chain_range", "plan_decoded_length", "plan_slice", "plan_stream_ranges", "plan_thin", "index_boundaries", "batch_deal", "index_boundaries_batch", "gather_segment", "gather_tasks", "gather_workspace_bytes", "gather_batch_workspace_bytes", "gather_batch_tasks", "GatherSet", "IndexingMember", "IndexingBatchStats", "planes_capacity", "planes_workspace_bytes", "planes_split", "planes_merge", "PlanesDesc", "Planes", "planes_gather_workspace_bytes", "planes_gather_tasks", "PlanesGather", "planes_gather_indirect_workspace_bytes", "PlanesGatherIndirectInfo", "planes_batch_workspace_bytes", "planes_batch_tasks", "PlanesSet", "planes_gather_batch_workspace_bytes", "planes_gather_batch_tasks", "PlanesGatherSet", "PlanesGatherBatchTask", "PlanesGatherSetInfo", "lib_path", "load_library",
 ]

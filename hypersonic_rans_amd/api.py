@@ -17,8 +17,8 @@ from ._abi import (  # noqa: F401  (the structures, constants and loader are spe
     BLOCK, COMM_ID_BYTES, ENC_INDEPENDENT_BLOCKS, MT, PLANES_MAX, PLANES_STORE_INCOMPRESSIBLE, RAW, SHARD_DECODE_AND_EXCHANGE, SHARD_DECODE_ONLY,
     SHARD_EXCHANGE_ONLY, BatchInfo, Calibration, EncodeBatchStats, EncodeExBatchStats, EncodeExMember, EncodeMember, EncodeOpts, GatherBatchTask,
     GatherMember, GatherSetInfo, GatherTask, Hist, HsransError, IndexingBatchStats, IndexingMember, LaunchFacts, LaunchInfo, MemberRange, PlanKind,
-    PlanesBatchStats, PlanesDesc, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherTask, PlanesInfo, PlanesMember, PlanesSetInfo, QueueStats, Range, Shard, ShardedInfo, _sz, _vp, lib_path,
-    load_library)
+    PlanesBatchStats, PlanesDesc, PlanesGatherBatchTask, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherSetInfo, PlanesGatherTask, PlanesInfo, PlanesMember,
+    PlanesSetInfo, QueueStats, Range, Shard, ShardedInfo, _sz, _vp, lib_path, load_library)
 
 
 def _u8(a) -> np.ndarray:
@@ -520,6 +520,33 @@ def planes_gather_tasks(ranges, elements: int, capacity: int | None = None) -> n
     return np.stack([out[n].astype(np.uint64) for n in out.dtype.names], axis=1) if rows else np.zeros((0, 5), np.uint64)
 
 
+def planes_gather_batch_workspace_bytes(max_itemsize: int, count: int, total_elements: int) -> int:
+    """hsrans_planes_gather_batch_workspace_bytes: a workspace that takes every decode_device_planes_gather_batch of ``count`` rows with
+    ``total_elements`` elements in all over members of at most ``max_itemsize`` bytes an item:
+    up256(max_itemsize * (total_elements + 30 * count)) (0: an item size that is not 2, 4 or 8, or an overflow)."""
+    return int(load_library().hsrans_planes_gather_batch_workspace_bytes(max_itemsize, count, total_elements))
+
+
+def planes_gather_batch_tasks(rows, itemsizes, elements, capacity: int | None = None) -> np.ndarray:
+    """hsrans_planes_gather_batch_tasks: the merge tasks ``rows`` ((member, offset, length, dst_offset), in the member's elements) over
+    members of ``itemsizes[m]``-byte items and ``elements[m]`` elements are cut into, as an (M, 7) uint64 array of (src, work_pos,
+    plane_step, dst_delta modulo 2^64, lo, hi, member).  Pure host arithmetic; an empty array for invalid input.  ``capacity``: as
+    gather_tasks."""
+    L = load_library()
+    arr = _member_ranges_array(rows)
+    sizes, elems = np.ascontiguousarray(itemsizes, np.uint32).reshape(-1), np.ascontiguousarray(elements, np.uint64).reshape(-1)
+    if sizes.size != elems.size:
+        raise ValueError("one item size and one element count per member")
+    args = (_p(arr) if arr.size else None, arr.shape[0], _p(sizes) if sizes.size else None, _p(elems) if elems.size else None, sizes.size)
+    n = L.hsrans_planes_gather_batch_tasks(*args, None, 0)
+    got = n if capacity is None else min(n, capacity)
+    out = np.zeros(got, np.dtype([("src", "<u8"), ("work_pos", "<u8"), ("plane_step", "<u8"), ("dst_delta", "<u8"), ("lo", "<u4"), ("hi", "<u4"), ("member", "<u4"),
+                                  ("reserved", "<u4")]))
+    if got:
+        L.hsrans_planes_gather_batch_tasks(*args, _p(out), got)
+    return np.stack([out[n].astype(np.uint64) for n in out.dtype.names[:7]], axis=1) if got else np.zeros((0, 7), np.uint64)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU side
 # ---------------------------------------------------------------------------------------------------------------------
@@ -614,6 +641,21 @@ class PlanesGather(_Handle):
         info = PlanesGatherIndirectInfo()
         _check(load_library().hsrans_planes_gather_indirect_info(self.handle, max_count, max_elements, out_capacity, ctypes.byref(info)),
                "hsrans_planes_gather_indirect_info")
+        return _as_dict(info)
+
+
+class PlanesGatherSet(_Handle):
+    """hsrans_planes_gather_set: a PlanesSet bound to the frames it reads (Context.make_planes_gather_set /
+    Context.decode_device_planes_gather_batch)."""
+    _destroy = "hsrans_planes_gather_set_destroy"
+
+    def __init__(self, ctx: "Context", handle, pset: PlanesSet, d_frames):
+        self.ctx, self.handle, self.pset, self.d_frames = ctx, handle, pset, list(d_frames)  # (keeps the planes set and the frames alive)
+
+    def info(self) -> dict:
+        """members, coded and stored planes of all members, and of the last call: the gather's rows, the merge's tasks and the kernels launched"""
+        info = PlanesGatherSetInfo()
+        load_library().hsrans_planes_gather_set_info(self.handle, ctypes.byref(info))
         return _as_dict(info)
 
 
@@ -1379,6 +1421,42 @@ class Context(_Handle):
         codes = (ctypes.c_int * PLANES_MAX)()
         self.L.hsrans_planes_gather_status(self.handle, pg.handle, _stream(stream), codes)
         return list(codes)[: pg.planes.desc.elem_size]
+
+    def make_planes_gather_set(self, pset: PlanesSet, d_frames, frame_lengths=None) -> PlanesGatherSet:
+        """hsrans_planes_gather_set_create: binds member k of ``pset`` to the frame in the CUDA uint8 tensor ``d_frames[k]`` (16-byte
+        aligned) for decode_device_planes_gather_batch.  The object keeps ``pset`` and the tensors alive.  Raises HsransError (``.code``: 2 a
+        bad argument, 3 a plane's plan has no entry points)."""
+        d_frames = list(d_frames)
+        if len(d_frames) != len(pset.descs) or (frame_lengths is not None and len(frame_lengths) != len(d_frames)):
+            raise HsransError(f"make_planes_gather_set: one frame (and one length) per member: {len(pset.descs)}", code=2)
+        frames, lengths = _tensor_arrays(d_frames, frame_lengths)
+        h = _vp()
+        _check(self.L.hsrans_planes_gather_set_create(self.handle, pset.handle, frames, lengths, ctypes.byref(h)), "hsrans_planes_gather_set_create")
+        return PlanesGatherSet(self, h, pset, d_frames)
+
+    def decode_device_planes_gather_batch(self, pgs: PlanesGatherSet, rows, out_tensor: torch.Tensor, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """Element ranges of many frames that stay compressed on the GPU, in one call (hsrans_decode_device_planes_gather_batch): for every
+        row (member, offset, length, dst_offset) of ``rows``, the last three in that member's elements, the elements [offset, offset +
+        length) of member ``member`` land at byte ``dst_offset * itemsize(member)`` of ``out_tensor`` (contiguous, any dtype: all rows
+        share it); nothing else of it is written.  ``d_work``: a CUDA uint8 tensor, 16-byte aligned, of
+        planes_gather_batch_workspace_bytes(largest itemsize, N, total elements) bytes.  Asynchronous on ``stream`` (default: torch's current
+        stream); ``rows`` is read before the call returns.  Raises HsransError (``.code``: 2 a bad row, destination or buffer; nothing was
+        launched)."""
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes_gather_batch takes a contiguous output tensor")
+        if d_work.dtype != torch.uint8:
+            raise HsransError("decode_device_planes_gather_batch takes a uint8 workspace tensor")
+        arr = _member_ranges_array(rows)
+        _check(self.L.hsrans_decode_device_planes_gather_batch(self.handle, pgs.handle, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
+                                                               out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                               _stream(stream, out_tensor.device)), "hsrans_decode_device_planes_gather_batch")
+
+    def planes_gather_set_status(self, pgs: PlanesGatherSet, stream: torch.cuda.Stream | None = None) -> list:
+        """hsrans_planes_gather_set_status: synchronises ``stream`` and returns every member's status (its first failing plane's, else 0)"""
+        K = len(pgs.pset.descs)
+        codes = (ctypes.c_int * max(K, 1))()
+        self.L.hsrans_planes_gather_set_status(self.handle, pgs.handle, _stream(stream), codes)
+        return list(codes)[:K]
 
     def block_choices_device(self, container: int, states: int, bits: int, d_in: torch.Tensor, block_size: int = 0,
                              stream: torch.cuda.Stream | None = None) -> np.ndarray:

@@ -18,18 +18,6 @@
 
 static_assert(sizeof(hsrans_planes_member) == 240 && sizeof(hsrans_planes_set_info_t) == 32 && sizeof(PlanesBatchMember) == 88, "planes batch ABI and table layout");
 
-struct hsrans_planes_set
-{
-  hsrans_ctx *ctx = nullptr;
-  std::vector<hsrans_planes_desc> descs;
-  hsrans_batch *batch = nullptr;      // over the coded planes of all members; null when every plane is stored
-  std::vector<uint32_t> coded_member; // member and plane of batch member j
-  std::vector<uint32_t> coded_plane;
-  std::vector<size_t> work_at;        // [count + 1]: the members' regions of the workspace, then its size
-  std::vector<uint32_t> first_task;   // [count + 1]: the merge's task prefix, then its total
-  uint32_t batch_launches = 0;
-};
-
 namespace
 {
 constexpr uint32_t kMaxBatchMembers = 65536;  // hsrans_encode_device_batch: members of one call
@@ -370,6 +358,7 @@ try
   if (hsrans_planes_batch_workspace_bytes(widths.data(), elements.data(), count) != set->work_at[count] ||
       hsrans_planes_batch_tasks(elements.data(), count, set->first_task.data()) == 0 || coded.size() > 0xFFFFFFFFu)
     return HSRANS_E_ARG;
+  set->coded_plans = coded;
   if (!coded.empty())
   {
     const int rc = hsrans_dplan_batch_create(ctx, coded.data(), (uint32_t)coded.size(), &set->batch); // (refuses a plan that appears twice)

@@ -1,0 +1,352 @@
+// hsrans_capi_planes_gather_batch.cpp — hsrans_decode_device_planes_gather_batch (include/hsrans_hip.h): element ranges of MANY frames of
+// byte planes in one call.  For K tensors what hsrans_capi_planes_gather.cpp is for one: the object (a hsrans_planes_set bound to its
+// frames, ONE hsrans_gather_set over all coded planes of all members, one record per member in device memory for the merge), the workspace
+// layout for rows of mixed element sizes and the host-side cut of the merge (hsrans_planes_gather_batch_tasks, a pure function on the rules
+// of planes_cut.h), the argument checks, and the call: hsrans_decode_device_gather_batch of the coded planes' bytes into the workspace
+// through its public entry, then one k_planes_merge_ranges_batch launch (hsrans_planes_gather_batch.hip) whose task list goes through the
+// context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/hsrans_hip.h"
+#include "hsrans_planes.h"
+#include "planes_cut.h"
+
+#include "hsrans_internal.h"
+
+static_assert(sizeof(hsrans_planes_gather_batch_task) == 48 && sizeof(PlanesGatherBatchTask) == sizeof(hsrans_planes_gather_batch_task) &&
+                  sizeof(hsrans_member_range) == 32 && sizeof(hsrans_planes_gather_set_info_t) == 24,
+              "planes gather batch ABI layout");
+
+struct hsrans_planes_gather_set
+{
+  hsrans_ctx *ctx = nullptr;
+  hsrans_planes_set *planes = nullptr;
+  hsrans_gather_set *set = nullptr; // over the coded planes of all members, in the planes set's coded order; null when every plane is stored
+  std::vector<uint32_t> widths;     // per member: elem_size ...
+  std::vector<uint64_t> elements;   // ... elements ...
+  std::vector<uint32_t> coded_mask; // ... which planes are coded ...
+  std::vector<uint32_t> coded_at;   // [members + 1] ... and where its coded planes begin among the set's members
+  std::vector<Span> frames;         // the frames over frame_lengths, sorted by address
+  PlanesGatherBatchMember *d_members = nullptr; // the merge's records, uploaded once
+  hsrans_planes_gather_set_info_t last{};       // members, coded, stored; the last call's part (under ctx->lock)
+};
+
+namespace
+{
+static_assert(kPlanesCutTask == kPlanesGatherTaskElements, "planes_cut.h cuts at the merge kernels' task length");
+
+bool width_ok(uint32_t W) { return W == 2 || W == 4 || W == 8; }
+bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
+Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
+bool wraps(const void *p, size_t bytes) { return (uintptr_t)p + bytes < (uintptr_t)p; }
+
+// What the rows come to: the merge's tasks, the workspace's bytes (the sum of W * slot) and, with `coded_at`, the rows of the set's gather
+struct BatchCut
+{
+  uint64_t tasks = 0, work = 0, rows = 0;
+};
+// whether every row names a member, lies inside it and leaves every total in range (tasks and gather rows below 2^31, a launch's workgroups
+// and the set's limit; no sum wraps)
+bool measure_rows(const hsrans_member_range *ranges, uint32_t count, const uint32_t *elem_sizes, const uint64_t *elements, uint32_t members, const uint32_t *coded_at,
+                  BatchCut *cut)
+{
+  *cut = BatchCut{};
+  for (uint32_t r = 0; r < count; r++)
+  {
+    const hsrans_member_range &g = ranges[r];
+    if (g.member >= members || g.reserved != 0 || !width_ok(elem_sizes[g.member]) || !planes_source_ok(g.offset, g.length, elements[g.member]))
+      return false;
+    const uint64_t W = elem_sizes[g.member], slot = planes_range_slot(g.offset, g.length);
+    if (slot > (~(uint64_t)0 - cut->work) / W)
+      return false;
+    cut->work += W * slot;
+    cut->tasks += planes_range_tasks(g.offset, g.length);
+    cut->rows += coded_at != nullptr && g.length != 0 ? coded_at[g.member + 1] - coded_at[g.member] : 0;
+    if (cut->tasks >= 0x80000000u || cut->rows >= 0x80000000u)
+      return false;
+  }
+  return true;
+}
+
+// The cut of the merge for rows that passed measure_rows: task(record) for every task, in row order.  Slot, task count and task k of a row
+// are planes_cut.h's with the row's base C_r; the row's sub-slots lie slot_r apart.
+template <typename Task>
+void cut_rows(const hsrans_member_range *ranges, uint32_t count, const uint32_t *elem_sizes, Task &&task)
+{
+  uint64_t at = 0; // C_r
+  for (uint32_t r = 0; r < count; r++)
+  {
+    const hsrans_member_range &g = ranges[r];
+    const uint64_t slot = planes_range_slot(g.offset, g.length);
+    for (uint64_t k = 0, n = planes_range_tasks(g.offset, g.length); k < n; k++)
+    {
+      const hsrans_planes_gather_task t = planes_task_at<hsrans_planes_gather_task>(g.offset, g.length, g.dst_offset, at, k);
+      task(hsrans_planes_gather_batch_task{t.src, t.work_pos, slot, t.dst_delta, t.lo, t.hi, g.member, 0});
+    }
+    at += elem_sizes[g.member] * slot;
+  }
+}
+} // namespace
+
+extern "C" size_t hsrans_planes_gather_batch_workspace_bytes(uint32_t max_elem_size, uint32_t count, uint64_t total_elements)
+{
+  const uint64_t bytes = total_elements + 30 * (uint64_t)count;
+  if (!width_ok(max_elem_size) || bytes < total_elements || bytes > (~(uint64_t)0 - 255) / max_elem_size)
+    return 0;
+  return up256((size_t)(max_elem_size * bytes));
+}
+
+extern "C" size_t hsrans_planes_gather_batch_tasks(const hsrans_member_range *ranges, uint32_t count, const uint32_t *elem_sizes, const uint64_t *elements, uint32_t members,
+                                                   hsrans_planes_gather_batch_task *out, size_t capacity)
+{
+  BatchCut cut;
+  if ((ranges == nullptr && count > 0) || ((elem_sizes == nullptr || elements == nullptr) && members > 0) || (out == nullptr && capacity > 0) ||
+      !measure_rows(ranges, count, elem_sizes, elements, members, nullptr, &cut))
+    return 0;
+  if (capacity == 0) // (the count alone: no walk over up to 2^31 tasks)
+    return (size_t)cut.tasks;
+  size_t n = 0;
+  cut_rows(ranges, count, elem_sizes, [&](const hsrans_planes_gather_batch_task &t) {
+    if (n < capacity)
+      out[n] = t;
+    n++;
+  });
+  return n;
+}
+
+extern "C" void hsrans_planes_gather_set_destroy(hsrans_planes_gather_set *pgs)
+{
+  if (pgs == nullptr)
+    return;
+  if (pgs->set != nullptr)
+    hsrans_gather_set_destroy(pgs->set);
+  if (pgs->d_members != nullptr)
+    (void)hipFree(pgs->d_members);
+  delete pgs;
+}
+
+extern "C" int hsrans_planes_gather_set_create(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, hsrans_planes_gather_set **out)
+try
+{
+  if (out == nullptr)
+    return HSRANS_E_ARG;
+  *out = nullptr;
+  if (ctx == nullptr || set == nullptr || set->ctx != ctx || d_frames == nullptr || frame_lengths == nullptr)
+    return HSRANS_E_ARG;
+  const uint32_t members = (uint32_t)set->descs.size();
+  for (uint32_t k = 0; k < members; k++)
+    if (!aligned16(d_frames[k]) || frame_lengths[k] < set->descs[k].frame_length || wraps(d_frames[k], frame_lengths[k]))
+      return HSRANS_E_ARG;
+
+  hsrans_planes_gather_set *pgs = new (std::nothrow) hsrans_planes_gather_set;
+  if (pgs == nullptr)
+    return HSRANS_E_HIP;
+  struct Guard // (an exception on its way to the handler below must not leak the object, its set and its records)
+  {
+    hsrans_planes_gather_set *pgs;
+    bool armed = true;
+    ~Guard()
+    {
+      if (armed)
+        hsrans_planes_gather_set_destroy(pgs);
+    }
+  } guard{pgs};
+  pgs->ctx = ctx;
+  pgs->planes = set;
+  pgs->coded_at.assign(members + 1, 0);
+  std::vector<PlanesGatherBatchMember> records(members);
+  for (uint32_t k = 0; k < members; k++)
+  {
+    const hsrans_planes_desc &desc = set->descs[k];
+    const uint32_t all = (1u << desc.elem_size) - 1, mask = all & ~desc.stored_mask;
+    pgs->widths.push_back(desc.elem_size);
+    pgs->elements.push_back(desc.elements);
+    pgs->coded_mask.push_back(mask);
+    pgs->coded_at[k + 1] = pgs->coded_at[k] + (uint32_t)__builtin_popcount(mask);
+    pgs->frames.push_back(span_of(d_frames[k], frame_lengths[k], false));
+    records[k].W = desc.elem_size;
+    records[k].coded_mask = mask;
+    for (uint32_t p = 0; p < desc.elem_size; p++)
+      records[k].stored[p] = (mask >> p) & 1 ? nullptr : (const uint8_t *)d_frames[k] + desc.offset[p];
+  }
+  const size_t coded = set->coded_plans.size();
+  if (pgs->coded_at[members] != coded) // (the planes set lists exactly the planes its descriptors call coded, in member and plane order)
+    return HSRANS_E_ARG;
+  std::sort(pgs->frames.begin(), pgs->frames.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; }); // (a call's spans_disjoint finds them sorted)
+  pgs->last.members = members;
+  pgs->last.coded = (uint32_t)coded;
+  pgs->last.stored = 0;
+  for (uint32_t k = 0; k < members; k++)
+    pgs->last.stored += pgs->widths[k];
+  pgs->last.stored -= pgs->last.coded;
+
+  if (coded != 0)
+  {
+    if (coded > 0xFFFFFFFFu)
+      return HSRANS_E_ARG;
+    std::vector<const void *> streams(coded);
+    std::vector<size_t> lengths(coded);
+    for (size_t j = 0; j < coded; j++)
+    {
+      const uint32_t k = set->coded_member[j], p = set->coded_plane[j];
+      streams[j] = (const uint8_t *)d_frames[k] + set->descs[k].offset[p];
+      lengths[j] = (size_t)set->descs[k].length[p];
+    }
+    const int rc = hsrans_gather_set_create(ctx, set->coded_plans.data(), streams.data(), lengths.data(), (uint32_t)coded, &pgs->set); // (E_ARG beyond 65,536)
+    if (rc != HSRANS_OK)
+      return rc;
+  }
+  // the merge's records, once (as hsrans_gather_set_create uploads the set's)
+  const size_t bytes = records.size() * sizeof(PlanesGatherBatchMember);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&pgs->d_members, bytes) != hipSuccess ||
+      hipMemcpy(pgs->d_members, records.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  guard.armed = false;
+  *out = pgs;
+  return HSRANS_OK;
+}
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather_batch(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *ranges, uint32_t count, void *d_out,
+                                                        size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+try
+{
+  if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx || !aligned16(d_out) || !aligned16(d_work) || (ranges == nullptr && count > 0) || wraps(d_out, out_capacity) ||
+      wraps(d_work, work_bytes))
+    return HSRANS_E_ARG;
+  const uint32_t members = (uint32_t)pgs->widths.size();
+
+  // ---- everything checked before anything is launched or uploaded ----
+  BatchCut cut; // (measure_rows is what hsrans_planes_gather_batch_tasks refuses by; here it counts the set's rows too)
+  if (!measure_rows(ranges, count, pgs->widths.data(), pgs->elements.data(), members, pgs->coded_at.data(), &cut))
+    return HSRANS_E_ARG;
+  for (uint32_t r = 0; r < count; r++)
+    if (!planes_dest_ok(ranges[r].dst_offset, ranges[r].length, out_capacity / pgs->widths[ranges[r].member]))
+      return HSRANS_E_ARG;
+  if (cut.work > ~(uint64_t)0 - 255)
+    return HSRANS_E_ARG;
+  const size_t need = up256((size_t)cut.work); // what this call's layout takes
+  if (work_bytes < need)
+    return HSRANS_E_ARG;
+  {
+    std::vector<Span> spans;
+    spans.reserve(pgs->frames.size() + 2);
+    spans.assign(pgs->frames.begin(), pgs->frames.end());
+    spans.push_back(span_of(d_out, out_capacity, true));
+    spans.push_back(span_of(d_work, work_bytes, true));
+    if (!spans_disjoint(spans))
+      return HSRANS_E_ARG;
+  }
+  {
+    std::lock_guard<std::mutex> lk(ctx->lock);
+    pgs->last.rows = pgs->last.merge_tasks = pgs->last.launches = 0;
+  }
+  if (cut.tasks == 0)
+    return HSRANS_OK;
+
+  // ---- the coded planes' bytes into their sub-slots: every non-empty row gives one gather row per coded plane of its member, to
+  // C_r + p * slot_r + phase ----
+  uint32_t set_launches = 0;
+  if (cut.rows != 0)
+  {
+    std::vector<hsrans_member_range> rows;
+    rows.reserve((size_t)cut.rows);
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < count; r++)
+    {
+      const hsrans_member_range &g = ranges[r];
+      if (g.length == 0)
+        continue;
+      const uint64_t slot = planes_range_slot(g.offset, g.length), phase = g.offset & 15;
+      uint32_t j = pgs->coded_at[g.member];
+      for (uint32_t p = 0, mask = pgs->coded_mask[g.member]; (mask >> p) != 0; p++)
+        if ((mask >> p) & 1)
+          rows.push_back(hsrans_member_range{g.offset, g.length, at + p * slot + phase, j++, 0});
+      at += pgs->widths[g.member] * slot;
+    }
+    // (ctx->lock is not held here: hsrans_decode_device_gather_batch takes it, and it is not recursive)
+    const int rc = hsrans_decode_device_gather_batch(ctx, pgs->set, rows.data(), (uint32_t)rows.size(), d_work, need, hip_stream);
+    if (rc != HSRANS_OK)
+      return rc;
+    hsrans_gather_set_info_t si{};
+    if (hsrans_gather_set_info(pgs->set, &si) != HSRANS_OK)
+      return HSRANS_E_HIP;
+    set_launches = si.launches;
+  }
+
+  // ---- the merge behind it: its task list through the context's task buffer, ordered with the context's gathers ----
+  std::lock_guard<std::mutex> lk(ctx->lock);
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return HSRANS_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const size_t list_bytes = (size_t)cut.tasks * sizeof(PlanesGatherBatchTask);
+  GatherRegion region;
+  const int rc = gather_region_take(ctx, up256(list_bytes), &region);
+  if (rc != HSRANS_OK)
+    return rc;
+  hsrans_planes_gather_batch_task *list = (hsrans_planes_gather_batch_task *)region.host;
+  size_t n = 0;
+  cut_rows(ranges, count, pgs->widths.data(), [&](const hsrans_planes_gather_batch_task &t) { list[n++] = t; });
+  if (gather_region_order(ctx, s) != HSRANS_OK)
+    return HSRANS_E_HIP;
+  if (hipMemcpyAsync(region.dev, region.host, list_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+      launch_planes_merge_ranges_batch((const PlanesGatherBatchTask *)region.dev, (uint32_t)cut.tasks, pgs->d_members, d_work, d_out, s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  const int rc_commit = gather_region_commit(ctx, region, s);
+  if (rc_commit != HSRANS_OK)
+    return rc_commit;
+  pgs->last.rows = (uint32_t)cut.rows;
+  pgs->last.merge_tasks = (uint32_t)cut.tasks;
+  pgs->last.launches = set_launches + 1;
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_gather_set_status(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream, int *member_status)
+try
+{
+  if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx)
+    return HSRANS_E_ARG;
+  for (size_t k = 0; member_status != nullptr && k < pgs->widths.size(); k++)
+    member_status[k] = HSRANS_OK;
+  if (pgs->set == nullptr) // (every plane stored: nothing to report, but the call still waits for the stream as the set's does)
+    return hipSetDevice(ctx->device) == hipSuccess && stream_settle((hipStream_t)hip_stream, true) ? HSRANS_OK : HSRANS_E_HIP;
+  const std::vector<uint32_t> &coded_member = pgs->planes->coded_member;
+  std::vector<int> plane_status(coded_member.size(), HSRANS_OK);
+  const int rc = hsrans_gather_set_status(ctx, pgs->set, hip_stream, plane_status.data());
+  for (size_t j = 0; member_status != nullptr && j < plane_status.size(); j++)
+    if (plane_status[j] != HSRANS_OK && member_status[coded_member[j]] == HSRANS_OK)
+      member_status[coded_member[j]] = plane_status[j];
+  return rc;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_gather_set_info(const hsrans_planes_gather_set *pgs, hsrans_planes_gather_set_info_t *info)
+{
+  if (pgs == nullptr || info == nullptr)
+    return HSRANS_E_ARG;
+  std::lock_guard<std::mutex> lk(pgs->ctx->lock);
+  *info = pgs->last;
+  return HSRANS_OK;
+}

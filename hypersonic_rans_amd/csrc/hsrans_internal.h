@@ -277,6 +277,21 @@ struct hsrans_planes
   std::vector<hsrans_dplan *> dplans; // of the coded planes, in batch order
 };
 
+// hsrans_planes_set (hsrans_capi_planes_batch.cpp): many frames' descriptors bound to their planes' device plans;
+// hsrans_capi_planes_gather_batch.cpp reads it
+struct hsrans_planes_set
+{
+  hsrans_ctx *ctx = nullptr;
+  std::vector<hsrans_planes_desc> descs;
+  hsrans_batch *batch = nullptr;      // over the coded planes of all members; null when every plane is stored
+  std::vector<uint32_t> coded_member; // member and plane of batch member j
+  std::vector<uint32_t> coded_plane;
+  std::vector<hsrans_dplan *> coded_plans; // ... and its plan
+  std::vector<size_t> work_at;        // [count + 1]: the members' regions of the workspace, then its size
+  std::vector<uint32_t> first_task;   // [count + 1]: the merge's task prefix, then its total
+  uint32_t batch_launches = 0;
+};
+
 // What hsrans_encode_device_planes and every member of hsrans_encode_device_planes_batch share (hsrans_capi_planes.cpp): the single call's
 // rules for one tensor but the workspace's and the overlap rule — element size, flags, d_in and d_frame set and 16-byte aligned, states,
 // elements, each plane by mt_shape, frame_capacity >= elem_size * stride.  *out: a coded plane's room in the frame, a plane's room in the

@@ -1,6 +1,6 @@
 // hsrans_planes.h — the streaming kernels of the byte-plane layer: elements of W bytes split into W byte planes and planes interleaved back
 // into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
-// hsrans_planes_gather_indirect.hip).  plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
+// hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip).  plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
 
@@ -63,6 +63,29 @@ struct PlanesGatherTask
 // bit p of work_mask is set, else the stored plane; every pointer 16-byte aligned (hipErrorInvalidValue otherwise)
 hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, void *out,
                                       hipStream_t stream);
+
+// ---- rows of many frames in one launch (hsrans_decode_device_planes_gather_batch): k_planes_merge_ranges_batch
+// (hsrans_planes_gather_batch.hip) ----
+// A task as above with its row's sub-slot distance and member (hsrans_planes_gather_batch_task, include/hsrans_hip.h): plane p of the
+// window lies at work_pos + p * plane_step of the call's workspace where the member's plane p was coded
+struct PlanesGatherBatchTask
+{
+  uint64_t src, work_pos, plane_step;
+  int64_t dst_delta;
+  uint32_t lo, hi, member, reserved;
+};
+// a member's record, in device memory for the lifetime of the gather set: stored[p] where plane p lies in the member's frame (bit p of
+// coded_mask clear), unused where it was coded
+struct PlanesGatherBatchMember
+{
+  const uint8_t *stored[kPlanesMax];
+  uint32_t W, coded_mask;
+};
+// asynchronous on `stream`, one workgroup per task (1 .. 2^31 - 1 of them, in device memory); the tasks' members index d_members, whose
+// records are the caller's to check (W in {2, 4, 8}, stored planes set and 16-byte aligned); work and out 16-byte aligned
+// (hipErrorInvalidValue otherwise)
+hipError_t launch_planes_merge_ranges_batch(const PlanesGatherBatchTask *d_tasks, uint32_t n_tasks, const PlanesGatherBatchMember *d_members, const void *work, void *out,
+                                            hipStream_t stream);
 
 // ---- the same for ranges in device memory (hsrans_decode_device_planes_gather_indirect): k_planes_cut, the set's indirect gather, then
 // k_planes_merge_indirect (hsrans_planes_gather_indirect.hip) ----

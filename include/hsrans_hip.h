@@ -1094,6 +1094,82 @@ int hsrans_decode_device_planes_gather_indirect(hsrans_ctx *ctx, hsrans_planes_g
 int hsrans_planes_gather_refused(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream);
 int hsrans_planes_gather_indirect_info(const hsrans_planes_gather *pg, uint32_t max_count, uint64_t max_elements, size_t out_capacity,
                                        hsrans_planes_gather_indirect_info_t *info);
+/* ------------------------------------------------------------------------------------------------------------
+ * Element ranges of MANY frames that stay compressed in device memory — rows of many experts' weights, pages of every
+ * layer's cache, slices of many parameters — in one call: what hsrans_decode_device_gather_batch is to
+ * hsrans_decode_device_gather, for the byte-plane layer.  A planes gather set binds the members of a hsrans_planes_set
+ * to their frames once; a call then takes rows of hsrans_member_range whose `member` is the tensor's index in the planes
+ * set and whose offset, length and dst_offset are in THAT member's elements: the elements [offset, offset + length) of
+ * member m land at (uint8_t *)d_out + dst_offset * elem_size(m), and no other byte of d_out is written.  All rows share
+ * the one d_out.  Rows may come in any member order, a member may appear many times or not at all, sources may overlap;
+ * destinations that overlap are the caller's responsibility; an empty row does nothing; reserved must be 0.  For every
+ * row d_out receives, byte for byte, what hsrans_decode_device_planes_gather on that member's own gather object writes
+ * for the same range, and the row's merge tasks are those hsrans_planes_gather_tasks reports for it.
+ * hsrans_planes_gather_set_create binds member k to d_frames[k] (16-byte aligned, frame_lengths[k] at least the
+ * descriptor's frame length), makes ONE hsrans_gather_set over all coded planes of all members, in member and plane order
+ * (none when every plane is stored), and uploads, once, one record per member for the merge: its element size, which
+ * planes are coded and the stored planes' addresses (d_frames[k] + desc.offset[p]).  The planes set, its plans and the
+ * frames must outlive the object.  Returns HSRANS_E_ARG: a null argument, a set of another context, a misaligned or short
+ * frame, more than 65,536 coded planes (hsrans_gather_set_create's limit); HSRANS_E_FORMAT: as hsrans_gather_set_create.
+ * The call: ONE hsrans_decode_device_gather_batch on that set, through its public entry — every non-empty row gives one
+ * gather row per coded plane of its member — then ONE merge launch behind it on the same stream that interleaves rows of
+ * 2-, 4- and 8-byte members alike; stored planes are read by the merge straight from their frames.  Launch count: the
+ * set's (one per table layout that has tasks, at most six) + 1, whatever the number of members or rows.  Asynchronous on
+ * hip_stream; `ranges` (host memory) is read before the call returns; no device allocation, no synchronisation.  The
+ * merge's task list goes through the context's task buffer: the call is ordered with the other gathers of the context.
+ * Workspace layout, a pure function of the rows: with phase = offset & 15 a non-empty row r has
+ * slot_r = up16(phase + length) and owns W(m_r) consecutive sub-slots of slot_r bytes from C_r on, C_r = the sum of
+ * W * slot over the earlier rows; the byte of plane p of element offset + i is at d_work + C_r + p * slot_r + phase + i.
+ * Everything is a multiple of 16: a 16-element block of a tensor is aligned alike in the workspace and in a stored plane,
+ * and every gather row is 16-byte aligned against its source.  Sub-slots of stored planes and sub-slot bytes outside
+ * [phase, phase + length) are never written.  A call needs up256(sum of W * slot) bytes;
+ * hsrans_planes_gather_batch_workspace_bytes = up256(max_elem_size * (total_elements + 30 * count)) bounds it for every
+ * `count` rows of `total_elements` elements in all over members of at most max_elem_size bytes an element; 0 for a
+ * max_elem_size that is not 2, 4 or 8 (or an overflow).
+ * Everything is checked before anything is uploaded or launched.  HSRANS_E_ARG, nothing written: a null handle or pointer,
+ * a null `ranges` with count > 0; an object of another context; d_out or d_work not 16-byte aligned; member >= the set's
+ * members or reserved != 0; a range beyond the member's elements; (dst_offset + length) * elem_size(m) beyond
+ * out_capacity, or any 64-bit overflow in these sums; work_bytes below what THIS call's layout needs; gather rows or merge
+ * tasks at or above 2^31; any intersection among the frames (over frame_lengths), the output and the workspace.
+ * HSRANS_OK with nothing launched: count == 0 or only empty rows.  HSRANS_E_HIP (the runtime refused an upload or a
+ * launch) may leave the workspace written and the output not.
+ * hsrans_planes_gather_set_status: hsrans_gather_set_status mapped back to members (synchronises hip_stream):
+ * member_status[k] is the status of member k's first failing plane, or HSRANS_OK; returns the first failure.  With every
+ * plane stored it only settles the stream.
+ * Cost: README and DESIGN 5b.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct hsrans_planes_gather_set hsrans_planes_gather_set;
+int hsrans_planes_gather_set_create(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, hsrans_planes_gather_set **out);
+void hsrans_planes_gather_set_destroy(hsrans_planes_gather_set *pgs);
+size_t hsrans_planes_gather_batch_workspace_bytes(uint32_t max_elem_size, uint32_t count, uint64_t total_elements);
+int hsrans_decode_device_planes_gather_batch(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *ranges /* host, in elements */, uint32_t count,
+                                             void *d_out, size_t out_capacity /* bytes */, void *d_work, size_t work_bytes, void *hip_stream);
+int hsrans_planes_gather_set_status(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream, int *member_status /* [members] or NULL */);
+typedef struct hsrans_planes_gather_set_info_t
+{
+  uint32_t members, coded, stored; /* members; planes of all members */
+  /* the last hsrans_decode_device_planes_gather_batch on the object (all 0: none yet, or it had nothing to do) */
+  uint32_t rows;        /* of its hsrans_decode_device_gather_batch: the coded planes of every non-empty row's member */
+  uint32_t merge_tasks; /* workgroups of its merge launch */
+  uint32_t launches;    /* kernels: the set's launches + the merge */
+} hsrans_planes_gather_set_info_t;
+int hsrans_planes_gather_set_info(const hsrans_planes_gather_set *pgs, hsrans_planes_gather_set_info_t *info);
+/* The host-side cut of the merge, a pure function (no GPU): member m has elem_sizes[m]-byte elements (2, 4 or 8) and
+ * elements[m] of them.  The tasks come in row order, a row's tasks are those hsrans_planes_gather_tasks gives for the row
+ * alone — src, dst_delta, lo and hi as there, work_pos counted from the row's C_r — with plane_step = slot_r (plane p of
+ * the task's window lies at work_pos + p * plane_step of the workspace) and the row's member.  Returns the task total and
+ * writes at most `capacity` of them (out may be NULL when capacity is 0); 0 for a null `ranges` with count > 0, null
+ * member arrays with members > 0, a member whose element size is not 2, 4 or 8, member >= members, reserved != 0, a
+ * range beyond its member's elements, a sum of W * slot that overflows, or 2^31 tasks or more (one launch's limit);
+ * hsrans_decode_device_planes_gather_batch refuses by this same function. */
+typedef struct hsrans_planes_gather_batch_task
+{
+  uint64_t src, work_pos, plane_step;
+  int64_t dst_delta; /* elements */
+  uint32_t lo, hi, member, reserved;
+} hsrans_planes_gather_batch_task; /* 48 bytes */
+size_t hsrans_planes_gather_batch_tasks(const hsrans_member_range *ranges, uint32_t count, const uint32_t *elem_sizes, const uint64_t *elements, uint32_t members,
+                                        hsrans_planes_gather_batch_task *out, size_t capacity);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

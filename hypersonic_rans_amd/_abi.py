@@ -168,6 +168,10 @@ class PlanesGatherSetInfo(ctypes.Structure):  # hsrans_planes_gather_set_info_t
     _fields_ = [(n, _u32) for n in ("members", "coded", "stored", "rows", "merge_tasks", "launches")]
 
 
+class PlanesGatherSetIndirectInfo(ctypes.Structure):  # hsrans_planes_gather_set_indirect_info_t
+    _fields_ = [(n, _u32) for n in ("members", "coded", "stored", "max_rows", "merge_grid", "launches", "set_launches")]
+
+
 class PlanesGatherBatchTask(ctypes.Structure):  # hsrans_planes_gather_batch_task
     _fields_ = [("src", ctypes.c_uint64), ("work_pos", ctypes.c_uint64), ("plane_step", ctypes.c_uint64), ("dst_delta", ctypes.c_int64), ("lo", _u32), ("hi", _u32),
                 ("member", _u32), ("reserved", _u32)]
@@ -318,6 +322,10 @@ SIGNATURES = {
     "hsrans_planes_gather_set_status": (_i, [_vp, _vp, _vp, _vp]),
     "hsrans_planes_gather_set_info": (_i, [_vp, _P(PlanesGatherSetInfo)]),
     "hsrans_planes_gather_batch_tasks": (_sz, [_vp, _u32, _vp, _vp, _u32, _vp, _sz]),
+    "hsrans_planes_gather_batch_indirect_workspace_bytes": (_sz, [_u32, _u32, _u32]),
+    "hsrans_decode_device_planes_gather_batch_indirect": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_planes_gather_set_refused": (_i, [_vp, _vp, _vp]),
+    "hsrans_planes_gather_set_indirect_info": (_i, [_vp, _u32, _sz, _sz, _P(PlanesGatherSetIndirectInfo)]),
     "hsrans_index_build": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz]),
     "hsrans_index_build_at": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]),
     "hsrans_hpipe_create": (_i, [_vp, _vp, _sz, _u32, _P(_vp)]),

@@ -17,7 +17,7 @@ from ._abi import (  # noqa: F401  (the structures, constants and loader are spe
     BLOCK, COMM_ID_BYTES, ENC_INDEPENDENT_BLOCKS, MT, PLANES_MAX, PLANES_STORE_INCOMPRESSIBLE, RAW, SHARD_DECODE_AND_EXCHANGE, SHARD_DECODE_ONLY,
     SHARD_EXCHANGE_ONLY, BatchInfo, Calibration, EncodeBatchStats, EncodeExBatchStats, EncodeExMember, EncodeMember, EncodeOpts, GatherBatchTask,
     GatherMember, GatherSetInfo, GatherTask, Hist, HsransError, IndexingBatchStats, IndexingMember, LaunchFacts, LaunchInfo, MemberRange, PlanKind,
-    PlanesBatchStats, PlanesDesc, PlanesGatherBatchTask, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherSetInfo, PlanesGatherTask, PlanesInfo, PlanesMember,
+    PlanesBatchStats, PlanesDesc, PlanesGatherBatchTask, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherSetIndirectInfo, PlanesGatherSetInfo, PlanesGatherTask, PlanesInfo, PlanesMember,
     PlanesSetInfo, QueueStats, Range, Shard, ShardedInfo, _sz, _vp, lib_path, load_library)
 
 
@@ -527,6 +527,13 @@ def planes_gather_batch_workspace_bytes(max_itemsize: int, count: int, total_ele
     return int(load_library().hsrans_planes_gather_batch_workspace_bytes(max_itemsize, count, total_elements))
 
 
+def planes_gather_batch_indirect_workspace_bytes(coded_planes: int, max_itemsize: int, max_count: int) -> int:
+    """hsrans_planes_gather_batch_indirect_workspace_bytes: the control workspace a decode_device_planes_gather_batch_indirect of up to
+    ``max_count`` rows needs on a set with ``coded_planes`` coded planes in all (0: every plane stored) and members of at most
+    ``max_itemsize`` bytes an element (0: another element size, more than 65,536 coded planes, or max_count * max_itemsize >= 2^31)"""
+    return int(load_library().hsrans_planes_gather_batch_indirect_workspace_bytes(coded_planes, max_itemsize, max_count))
+
+
 def planes_gather_batch_tasks(rows, itemsizes, elements, capacity: int | None = None) -> np.ndarray:
     """hsrans_planes_gather_batch_tasks: the merge tasks ``rows`` ((member, offset, length, dst_offset), in the member's elements) over
     members of ``itemsizes[m]``-byte items and ``elements[m]`` elements are cut into, as an (M, 7) uint64 array of (src, work_pos,
@@ -651,11 +658,23 @@ class PlanesGatherSet(_Handle):
 
     def __init__(self, ctx: "Context", handle, pset: PlanesSet, d_frames):
         self.ctx, self.handle, self.pset, self.d_frames = ctx, handle, pset, list(d_frames)  # (keeps the planes set and the frames alive)
+        # what sizes the indirect call's control workspace: the coded planes of all members and the largest element size
+        self.coded = sum(p is not None for plans in pset.plans for p in plans)
+        self.max_itemsize = max((int(d.elem_size) for d in pset.descs), default=0)
 
     def info(self) -> dict:
         """members, coded and stored planes of all members, and of the last call: the gather's rows, the merge's tasks and the kernels launched"""
         info = PlanesGatherSetInfo()
         load_library().hsrans_planes_gather_set_info(self.handle, ctypes.byref(info))
+        return _as_dict(info)
+
+    def indirect_info(self, max_count: int, out_capacity: int, work_bytes: int) -> dict:
+        """hsrans_planes_gather_set_indirect_info: what a decode_device_planes_gather_batch_indirect of up to ``max_count`` rows with a data
+        workspace of ``work_bytes`` will launch — members, coded and stored planes, the set's rows at most, the merge's grid, all kernels of
+        a call and the set's part of them.  No device call."""
+        info = PlanesGatherSetIndirectInfo()
+        _check(load_library().hsrans_planes_gather_set_indirect_info(self.handle, max_count, out_capacity, work_bytes, ctypes.byref(info)),
+               "hsrans_planes_gather_set_indirect_info")
         return _as_dict(info)
 
 
@@ -1450,6 +1469,36 @@ class Context(_Handle):
         _check(self.L.hsrans_decode_device_planes_gather_batch(self.handle, pgs.handle, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
                                                                out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
                                                                _stream(stream, out_tensor.device)), "hsrans_decode_device_planes_gather_batch")
+
+    def decode_device_planes_gather_batch_indirect(self, pgs: PlanesGatherSet, d_rows: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                                   count: torch.Tensor | None = None, max_count: int | None = None, workspace: torch.Tensor | None = None,
+                                                   stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """decode_device_planes_gather_batch for rows that are on the GPU (hsrans_decode_device_planes_gather_batch_indirect): ``d_rows`` is a
+        contiguous CUDA tensor (N, 4) of int64 / uint64 rows (offset, length, dst_offset, member) — the memory layout of
+        decode_device_gather_batch_indirect's rows, the first three in that member's elements; ``count`` a CUDA int32 / uint32 scalar tensor
+        with the number of rows in use (None: ``max_count``, itself N when None).  Both are read when the launches run, not here: nothing is
+        copied to the host, nothing is waited for, and the call can be captured into a graph.  ``d_work``: a CUDA uint8 tensor, 16-byte
+        aligned, its size the capacity (planes_gather_batch_workspace_bytes bounds what any rows need).  ``workspace``: a CUDA uint8 tensor
+        of at least planes_gather_batch_indirect_workspace_bytes(the set's coded planes, its largest itemsize, max_count) bytes that no
+        other call in flight uses; allocated here when None.  Returns the workspace.  Raises HsransError (``.code``) for what the host can
+        check; rows or a count only the device can refuse leave ``out_tensor`` and ``d_work`` untouched and are reported by
+        ``planes_gather_set_refused(pgs)`` (5)."""
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes_gather_batch_indirect takes a contiguous output tensor")
+        if d_work.dtype != torch.uint8:
+            raise HsransError("decode_device_planes_gather_batch_indirect takes a uint8 workspace tensor")
+        max_count, workspace = _indirect_args(d_rows, 4, count, max_count, workspace,
+                                              lambda n: planes_gather_batch_indirect_workspace_bytes(pgs.coded, pgs.max_itemsize, n), out_tensor.device, stream)
+        _check(self.L.hsrans_decode_device_planes_gather_batch_indirect(self.handle, pgs.handle, d_rows.data_ptr(), None if count is None else count.data_ptr(), max_count,
+                                                                        out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(),
+                                                                        d_work.numel(), workspace.data_ptr(), workspace.numel(), _stream(stream, out_tensor.device)),
+               "hsrans_decode_device_planes_gather_batch_indirect")
+        return workspace
+
+    def planes_gather_set_refused(self, pgs: PlanesGatherSet, stream: torch.cuda.Stream | None = None) -> int:
+        """hsrans_planes_gather_set_refused: synchronises ``stream`` and returns 5 once where a decode_device_planes_gather_batch_indirect on
+        the object was refused on the device since the last look, else 0"""
+        return int(self.L.hsrans_planes_gather_set_refused(self.handle, pgs.handle, _stream(stream)))
 
     def planes_gather_set_status(self, pgs: PlanesGatherSet, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_planes_gather_set_status: synchronises ``stream`` and returns every member's status (its first failing plane's, else 0)"""

@@ -5,6 +5,8 @@
 // of planes_cut.h), the argument checks, and the call: hsrans_decode_device_gather_batch of the coded planes' bytes into the workspace
 // through its public entry, then one k_planes_merge_ranges_batch launch (hsrans_planes_gather_batch.hip) whose task list goes through the
 // context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
+// hsrans_decode_device_planes_gather_batch_indirect, at the end of the file: the same for rows in device memory — the device cuts
+// (hsrans_planes_gather_batch_indirect.hip), by the rules of planes_cut_batch.h that measure_rows above uses too.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -15,7 +17,7 @@
 
 #include "../../include/hsrans_hip.h"
 #include "hsrans_planes.h"
-#include "planes_cut.h"
+#include "planes_cut_batch.h"
 
 #include "hsrans_internal.h"
 
@@ -34,6 +36,9 @@ struct hsrans_planes_gather_set
   std::vector<uint32_t> coded_at;   // [members + 1] ... and where its coded planes begin among the set's members
   std::vector<Span> frames;         // the frames over frame_lengths, sorted by address
   PlanesGatherBatchMember *d_members = nullptr; // the merge's records, uploaded once
+  PlanesCutBatchMember *d_cut_members = nullptr; // ... and what k_planes_cut_batch reads of a member (hsrans_decode_device_planes_gather_batch_indirect)
+  uint32_t min_width = 0, max_width = 0;         // the smallest and the largest element size among the members
+  uint32_t *d_refused = nullptr; // the object's own status word (kStatusBadRange: k_planes_cut_batch refused an indirect call); no plan's word is involved
   hsrans_planes_gather_set_info_t last{};       // members, coded, stored; the last call's part (under ctx->lock)
 };
 
@@ -41,7 +46,7 @@ namespace
 {
 static_assert(kPlanesCutTask == kPlanesGatherTaskElements, "planes_cut.h cuts at the merge kernels' task length");
 
-bool width_ok(uint32_t W) { return W == 2 || W == 4 || W == 8; }
+bool width_ok(uint32_t W) { return planes_width_ok(W); }
 bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
 Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
 bool wraps(const void *p, size_t bytes) { return (uintptr_t)p + bytes < (uintptr_t)p; }
@@ -57,20 +62,17 @@ bool measure_rows(const hsrans_member_range *ranges, uint32_t count, const uint3
                   BatchCut *cut)
 {
   *cut = BatchCut{};
+  PlanesRowsSum sum{0, 0, 0};
   for (uint32_t r = 0; r < count; r++)
   {
     const hsrans_member_range &g = ranges[r];
-    if (g.member >= members || g.reserved != 0 || !width_ok(elem_sizes[g.member]) || !planes_source_ok(g.offset, g.length, elements[g.member]))
-      return false;
-    const uint64_t W = elem_sizes[g.member], slot = planes_range_slot(g.offset, g.length);
-    if (slot > (~(uint64_t)0 - cut->work) / W)
-      return false;
-    cut->work += W * slot;
-    cut->tasks += planes_range_tasks(g.offset, g.length);
-    cut->rows += coded_at != nullptr && g.length != 0 ? coded_at[g.member + 1] - coded_at[g.member] : 0;
-    if (cut->tasks >= 0x80000000u || cut->rows >= 0x80000000u)
+    PlanesRowCut row;
+    if (g.member >= members || g.reserved != 0 ||
+        !planes_row_cut(g.offset, g.length, elements[g.member], elem_sizes[g.member], coded_at != nullptr ? coded_at[g.member + 1] - coded_at[g.member] : 0, &row) ||
+        !planes_rows_add(&sum, row))
       return false;
   }
+  *cut = BatchCut{sum.tasks, sum.work, sum.rows};
   return true;
 }
 
@@ -128,6 +130,10 @@ extern "C" void hsrans_planes_gather_set_destroy(hsrans_planes_gather_set *pgs)
     hsrans_gather_set_destroy(pgs->set);
   if (pgs->d_members != nullptr)
     (void)hipFree(pgs->d_members);
+  if (pgs->d_cut_members != nullptr)
+    (void)hipFree(pgs->d_cut_members);
+  if (pgs->d_refused != nullptr)
+    (void)hipFree(pgs->d_refused);
   delete pgs;
 }
 
@@ -161,6 +167,7 @@ try
   pgs->planes = set;
   pgs->coded_at.assign(members + 1, 0);
   std::vector<PlanesGatherBatchMember> records(members);
+  std::vector<PlanesCutBatchMember> cut_records(std::max(members, 1u)); // (never empty: the cut reads record 0 for a member beyond the set's)
   for (uint32_t k = 0; k < members; k++)
   {
     const hsrans_planes_desc &desc = set->descs[k];
@@ -174,6 +181,9 @@ try
     records[k].coded_mask = mask;
     for (uint32_t p = 0; p < desc.elem_size; p++)
       records[k].stored[p] = (mask >> p) & 1 ? nullptr : (const uint8_t *)d_frames[k] + desc.offset[p];
+    cut_records[k] = PlanesCutBatchMember{desc.elements, pgs->coded_at[k], (uint16_t)desc.elem_size, (uint16_t)mask};
+    pgs->min_width = k == 0 ? desc.elem_size : std::min(pgs->min_width, desc.elem_size);
+    pgs->max_width = std::max(pgs->max_width, desc.elem_size);
   }
   const size_t coded = set->coded_plans.size();
   if (pgs->coded_at[members] != coded) // (the planes set lists exactly the planes its descriptors call coded, in member and plane order)
@@ -202,10 +212,13 @@ try
     if (rc != HSRANS_OK)
       return rc;
   }
-  // the merge's records, once (as hsrans_gather_set_create uploads the set's)
-  const size_t bytes = records.size() * sizeof(PlanesGatherBatchMember);
+  // the merge's records and the cut's, once (as hsrans_gather_set_create uploads the set's), and the word the indirect call's cut reports a
+  // refusal in
+  const size_t bytes = records.size() * sizeof(PlanesGatherBatchMember), cut_bytes = cut_records.size() * sizeof(PlanesCutBatchMember);
   if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&pgs->d_members, bytes) != hipSuccess ||
-      hipMemcpy(pgs->d_members, records.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy(pgs->d_members, records.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void **)&pgs->d_cut_members, cut_bytes) != hipSuccess ||
+      hipMemcpy(pgs->d_cut_members, cut_records.data(), cut_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMalloc((void **)&pgs->d_refused, sizeof(uint32_t)) != hipSuccess || hipMemset(pgs->d_refused, 0, sizeof(uint32_t)) != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -349,4 +362,174 @@ extern "C" int hsrans_planes_gather_set_info(const hsrans_planes_gather_set *pgs
   std::lock_guard<std::mutex> lk(pgs->ctx->lock);
   *info = pgs->last;
   return HSRANS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_decode_device_planes_gather_batch_indirect: the rows are in device memory.  Nothing of the above is cut here: k_planes_cut_batch
+// checks the rows against their members, lays out the workspace and writes the set's rows, the set's indirect entry gathers the coded planes'
+// bytes, k_planes_merge_batch_indirect derives its tasks from what the cut left (hsrans_planes_gather_batch_indirect.hip).  No lock, no task
+// buffer, no allocation: kernels and nothing else.
+// ---------------------------------------------------------------------------------------------------------------
+namespace
+{
+static_assert(sizeof(PlanesSetRow) == sizeof(hsrans_member_range) && sizeof(hsrans_planes_gather_set_indirect_info_t) == 28, "the device's view of the rows; the info's layout");
+
+constexpr uint64_t kWorkLimitMax = (uint64_t)1 << 48; // beyond any device's memory; up to it no sum of W * slot in k_planes_cut_batch can wrap
+
+// What one indirect call launches, from what the host knows: the entry and hsrans_planes_gather_set_indirect_info both go through here.
+struct BatchIndirectShape
+{
+  uint32_t max_rows, merge_grid, set_launches, launches;
+};
+bool batch_indirect_shape(const hsrans_planes_gather_set *pgs, uint32_t max_count, size_t work_bytes, BatchIndirectShape *shape)
+{
+  *shape = BatchIndirectShape{};
+  const uint32_t coded = pgs->last.coded;
+  if (hsrans_planes_gather_batch_indirect_workspace_bytes(coded, pgs->max_width, max_count) == 0) // (no member, or max_count * max_width >= 2^31)
+    return false;
+  if (max_count == 0)
+    return true;
+  shape->max_rows = pgs->set != nullptr ? max_count * pgs->max_width : 0;
+  shape->merge_grid = planes_merge_batch_indirect_grid(pgs->ctx->geom.num_cus, pgs->min_width, max_count, work_bytes);
+  if (pgs->set != nullptr)
+  {
+    hsrans_gather_set_info_t si{};
+    if (hsrans_gather_set_indirect_info(pgs->set, shape->max_rows, work_bytes, &si) != HSRANS_OK)
+      return false;
+    shape->set_launches = si.launches + 1; // (+ the set's cut)
+  }
+  shape->launches = shape->set_launches + 2; // (+ k_planes_cut_batch and the merge)
+  return true;
+}
+} // namespace
+
+extern "C" size_t hsrans_planes_gather_batch_indirect_workspace_bytes(uint32_t coded_planes, uint32_t max_elem_size, uint32_t max_count)
+{
+  if (!width_ok(max_elem_size) || coded_planes > 65536 || (uint64_t)max_count * max_elem_size >= 0x80000000u)
+    return 0;
+  const size_t control = planes_cut_batch_ws(max_elem_size, max_count).set;
+  if (coded_planes == 0) // (every plane stored: no set, no call of its own)
+    return control;
+  const size_t set_bytes = hsrans_gather_batch_workspace_bytes(coded_planes, max_count * max_elem_size);
+  return set_bytes == 0 ? 0 : control + up256(set_bytes);
+}
+
+extern "C" int hsrans_planes_gather_set_indirect_info(const hsrans_planes_gather_set *pgs, uint32_t max_count, size_t out_capacity, size_t work_bytes,
+                                                      hsrans_planes_gather_set_indirect_info_t *info)
+try
+{
+  if (pgs == nullptr || info == nullptr)
+    return HSRANS_E_ARG;
+  BatchIndirectShape shape{};
+  if (!batch_indirect_shape(pgs, max_count, work_bytes, &shape))
+    return HSRANS_E_ARG;
+  (void)out_capacity; // (it bounds the destinations on the device; no launch is shaped by it)
+  *info = hsrans_planes_gather_set_indirect_info_t{pgs->last.members, pgs->last.coded, pgs->last.stored, shape.max_rows, shape.merge_grid, shape.launches, shape.set_launches};
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather_batch_indirect(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *d_ranges, const uint32_t *d_count,
+                                                                 uint32_t max_count, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
+                                                                 size_t workspace_bytes, void *hip_stream)
+try
+{
+  if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx || d_ranges == nullptr || d_workspace == nullptr || !aligned16(d_out) || !aligned16(d_work))
+    return HSRANS_E_ARG;
+  if (((uintptr_t)d_ranges & 7) != 0 || ((uintptr_t)d_count & 3) != 0 || ((uintptr_t)d_workspace & 255) != 0)
+    return HSRANS_E_ARG;
+  const size_t need_ws = hsrans_planes_gather_batch_indirect_workspace_bytes(pgs->last.coded, pgs->max_width, max_count);
+  if (need_ws == 0 || workspace_bytes < need_ws || wraps(d_out, out_capacity) || wraps(d_work, work_bytes) || wraps(d_workspace, workspace_bytes))
+    return HSRANS_E_ARG;
+  {
+    std::vector<Span> spans;
+    spans.reserve(pgs->frames.size() + 5);
+    spans.assign(pgs->frames.begin(), pgs->frames.end());
+    spans.push_back(span_of(d_ranges, (size_t)max_count * sizeof(hsrans_member_range), false));
+    if (d_count != nullptr)
+      spans.push_back(span_of(d_count, sizeof(uint32_t), false));
+    spans.push_back(span_of(d_out, out_capacity, true));
+    spans.push_back(span_of(d_work, work_bytes, true));
+    spans.push_back(span_of(d_workspace, workspace_bytes, true));
+    if (!spans_disjoint(spans))
+      return HSRANS_E_ARG;
+  }
+  if (max_count == 0)
+    return HSRANS_OK;
+  BatchIndirectShape shape{};
+  if (!batch_indirect_shape(pgs, max_count, work_bytes, &shape))
+    return HSRANS_E_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess)
+    return HSRANS_E_HIP;
+  hipStream_t s = (hipStream_t)hip_stream;
+
+  // ---- the cut: C_r, the task prefix and the set's rows into the control workspace ----
+  const PlanesCutBatchWs ws = planes_cut_batch_ws(pgs->max_width, max_count);
+  uint8_t *const control = (uint8_t *)d_workspace;
+  PlanesCutBatchParams cp{};
+  cp.ranges = (const PlanesSetRow *)d_ranges;
+  cp.count = d_count;
+  cp.members = pgs->d_cut_members;
+  cp.max_count = max_count;
+  cp.n_members = (uint32_t)pgs->widths.size();
+  cp.out_capacity = out_capacity;
+  cp.work_limit = std::min<uint64_t>((uint64_t)work_bytes & ~(uint64_t)255, kWorkLimitMax); // (up256(sum) <= work_bytes)
+  cp.header = (uint32_t *)control;
+  cp.first_task = (uint32_t *)(control + ws.first_task);
+  cp.base = (uint64_t *)(control + ws.base);
+  cp.first_row = (uint32_t *)(control + ws.first_row);
+  cp.rows = (PlanesSetRow *)(control + ws.rows);
+  cp.status = pgs->d_refused;
+  if (launch_planes_cut_batch(cp, s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+
+  // ---- the coded planes' bytes into their sub-slots, through the set's public entry as the host-rows call goes through the batch entry ----
+  if (pgs->set != nullptr)
+  {
+    const int rc = hsrans_decode_device_gather_batch_indirect(ctx, pgs->set, (const hsrans_member_range *)cp.rows, cp.header + kPlanesWsRows, shape.max_rows, d_work, work_bytes,
+                                                              control + ws.set, workspace_bytes - ws.set, hip_stream);
+    if (rc != HSRANS_OK)
+      return rc;
+  }
+
+  // ---- the merge behind it ----
+  if (launch_planes_merge_batch_indirect(cp.ranges, cp.header, cp.first_task, cp.base, pgs->d_members, d_work, d_out, shape.merge_grid, s) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  return HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_planes_gather_set_refused(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream)
+try
+{
+  if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx)
+    return HSRANS_E_ARG;
+  uint32_t status = 0xFFFFFFFF;
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMemcpyAsync(&status, pgs->d_refused, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  if (status != 0)
+  {
+    if (hipMemsetAsync(pgs->d_refused, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return HSRANS_E_HIP;
+    return HSRANS_E_DEVICE;
+  }
+  // (the set's own word: the planes cut has passed every row the set sees, so this should never fire; it is reported if it does)
+  return pgs->set != nullptr ? hsrans_gather_set_refused(ctx, pgs->set, hip_stream) : HSRANS_OK;
+}
+catch (...)
+{
+  return HSRANS_E_HIP;
 }

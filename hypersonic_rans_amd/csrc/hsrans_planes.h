@@ -1,6 +1,7 @@
 // hsrans_planes.h — the streaming kernels of the byte-plane layer: elements of W bytes split into W byte planes and planes interleaved back
 // into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
-// hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip).  plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
+// hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip, and with those rows in device memory
+// hsrans_planes_gather_batch_indirect.hip).  plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
 
@@ -138,6 +139,57 @@ uint32_t planes_merge_indirect_grid(uint32_t num_cus, uint32_t W, uint32_t max_c
 hipError_t launch_planes_cut(const PlanesCutParams &cp, hipStream_t stream);
 hipError_t launch_planes_merge_indirect(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesRange *d_ranges, const uint32_t *d_header,
                                         const uint32_t *d_first_task, const uint64_t *d_base, uint32_t grid, void *out, hipStream_t stream);
+
+// ---- rows of many frames in device memory (hsrans_decode_device_planes_gather_batch_indirect): k_planes_cut_batch, the set's indirect
+// gather, then k_planes_merge_batch_indirect (hsrans_planes_gather_batch_indirect.hip) ----
+// what the cut reads of a row's member, in device memory for the lifetime of the gather set beside the merge's records: one 16-byte load
+struct alignas(16) PlanesCutBatchMember
+{
+  uint64_t elements;
+  uint32_t coded_at;       // the member's first coded plane among the set's members
+  uint16_t W, coded_mask;  // element size; bit p: plane p was coded
+};
+// The control workspace, in bytes from its start: the header's words as above ([kPlanesWsRows]: the count word of the set's call), then
+// first_task[0 .. max_count] (uint32), base[max_count] (uint64, C_r), first_row[max_count] (uint32: where the row's gather rows begin),
+// rows[max_count * max_elem_size] (PlanesSetRow; the first header[kPlanesWsRows] are in use) and, from `set` on, the workspace of the set's
+// own call.
+struct PlanesCutBatchWs
+{
+  size_t first_task, base, first_row, rows, set;
+};
+inline PlanesCutBatchWs planes_cut_batch_ws(uint32_t max_elem_size, uint32_t max_count) // (host: the kernels get pointers)
+{
+  Carve c;
+  PlanesCutBatchWs ws;
+  c.take(256);
+  ws.first_task = c.take(((size_t)max_count + 1) * 4);
+  ws.base = c.take((size_t)max_count * 8);
+  ws.first_row = c.take((size_t)max_count * 4);
+  ws.rows = c.take((size_t)max_count * max_elem_size * sizeof(PlanesSetRow));
+  ws.set = c.close();
+  return ws;
+}
+struct PlanesCutBatchParams
+{
+  const PlanesSetRow *ranges;          // device: the call's rows (hsrans_member_range, in elements)
+  const uint32_t *count;               // device, or null: max_count
+  const PlanesCutBatchMember *members; // device: the set's cut records
+  uint32_t max_count, n_members;
+  uint64_t out_capacity; // bytes
+  uint64_t work_limit;   // no sum of W * slot may exceed it: work_bytes rounded down to 256, at most 2^48 (so that no sum in the cut wraps)
+  uint32_t *header, *first_task, *first_row; // the control workspace's parts
+  uint64_t *base;
+  PlanesSetRow *rows;
+  uint32_t *status; // the gather set object's word: kStatusBadRange where the call is refused
+};
+// the workgroups of the merge: the most tasks the call can have, max_count + work_bytes / (min_W * 4096) (a row's tasks <= its slot / 4096
+// + 1, and the rows' W * slot fit in work_bytes), capped at the workgroups of 256 lanes the device holds at once;
+// k_planes_merge_batch_indirect strides over the tasks
+uint32_t planes_merge_batch_indirect_grid(uint32_t num_cus, uint32_t min_W, uint32_t max_count, uint64_t work_bytes);
+// asynchronous on `stream`, one kernel each, nothing else (capturable); hipErrorInvalidValue for a null or misaligned pointer or grid 0
+hipError_t launch_planes_cut_batch(const PlanesCutBatchParams &cp, hipStream_t stream);
+hipError_t launch_planes_merge_batch_indirect(const PlanesSetRow *d_ranges, const uint32_t *d_header, const uint32_t *d_first_task, const uint64_t *d_base,
+                                              const PlanesGatherBatchMember *d_members, const void *work, void *out, uint32_t grid, hipStream_t stream);
 
 } // namespace hsrans
 

@@ -1170,6 +1170,76 @@ typedef struct hsrans_planes_gather_batch_task
 } hsrans_planes_gather_batch_task; /* 48 bytes */
 size_t hsrans_planes_gather_batch_tasks(const hsrans_member_range *ranges, uint32_t count, const uint32_t *elem_sizes, const uint64_t *elements, uint32_t members,
                                         hsrans_planes_gather_batch_task *out, size_t capacity);
+/* ------------------------------------------------------------------------------------------------------------
+ * The same for rows that are in DEVICE memory — a router's choice among many experts, a page table over every layer's
+ * cache, a sampler — with no host round trip: n = d_count ? *d_count : max_count, and for the rows d_ranges[0 .. n) d_out
+ * AND d_work receive, byte for byte, what hsrans_decode_device_planes_gather_batch writes for the same rows in host
+ * memory; no other byte of either buffer is written.
+ *   - asynchronous on hip_stream: kernel launches and nothing else — no allocation, no synchronisation, no lock, no host
+ *     read of device memory, no use of the context's task buffer; the last call's part of hsrans_planes_gather_set_info is
+ *     not written.  The call can be captured into a graph: one line of kernels on one stream, no parallel branches.
+ *   - d_ranges and *d_count are read when the launches RUN: a replayed graph gathers whatever they hold then and inherits
+ *     nothing from the replay before it (every word the later launches read is written by every call).  Rows of
+ *     d_ranges from n on are never read.
+ *   - launches, in order: one cut (one workgroup: it checks every row against its member, lays out the workspace, counts
+ *     the merge's tasks and writes, for every non-empty row, one row of the set's gather per coded plane of its member,
+ *     in the form the host call builds: {offset, length, C_r + p * slot_r + phase, the plane's member of the set, 0});
+ *     where the set has coded planes, hsrans_decode_device_gather_batch_indirect on the object's set, through that
+ *     public entry, with those rows, their count word and dst_capacity = work_bytes; one merge launch that finds each
+ *     task's row in the prefix the cut left and derives the task as hsrans_planes_gather_batch_tasks does.  With every
+ *     plane stored: two kernels.  The merge's grid cannot depend on the rows: it is the most tasks the call can have,
+ *     max_count + work_bytes / (the smallest member's elem_size * 4096), capped at the workgroups the device holds at
+ *     once, and the workgroups stride over the tasks, so any total finishes.  Pass the work_bytes the rows really need.
+ *   - d_work, the data workspace: the layout is the host call's (row r owns W(m_r) sub-slots of slot_r = up16(phase +
+ *     length) bytes from C_r on, C_r = the sum of W * slot over the earlier rows) — the device forms C_r by a prefix sum,
+ *     so, unlike hsrans_decode_device_planes_gather_indirect, there is no stride and no max_elements.  work_bytes is the
+ *     capacity: hsrans_planes_gather_batch_workspace_bytes bounds what any rows can need.
+ *   - d_workspace, the control workspace: hsrans_planes_gather_batch_indirect_workspace_bytes(the set's coded planes,
+ *     its largest elem_size, max_count) bytes, 256-byte aligned, contents irrelevant; it belongs to one call in flight
+ *     (calls with different workspace pairs on one object are independent of each other whatever streams they are on).
+ *     It holds a header, the tasks' prefix first_task[0 .. max_count], C_r per row, the position of each row's first
+ *     gather row, the max_count x max_elem_size rows of hsrans_member_range for the set with their count word, and behind
+ *     them hsrans_gather_batch_workspace_bytes(coded_planes, max_count x max_elem_size) bytes for the set's own call.
+ * What only the device can see is checked there, all or nothing, by the rules that make the host call return
+ * HSRANS_E_ARG: *d_count > max_count; member >= the set's members or reserved != 0 (of empty rows too); a range beyond
+ * its member's elements; (dst_offset + length) * elem_size(m) beyond out_capacity; any 64-bit overflow in these sums;
+ * up256(the sum of W * slot) above work_bytes (or above 2^48); a merge task total or a gather row total of 2^31 or more.
+ * Then the call moves NOTHING — not one byte of d_out or d_work is written — and sets bit 8 of a status word the
+ * gather set object owns, allocated by hsrans_planes_gather_set_create (no plan's word is touched):
+ * hsrans_planes_gather_set_refused synchronises hip_stream, returns HSRANS_E_DEVICE once and clears the word; otherwise
+ * it returns what hsrans_gather_set_refused returns for the object's set (whose word should never fire once the cut has
+ * passed the rows; HSRANS_OK when there is no set).  A malformed histogram still reaches only its plane's plan word
+ * (hsrans_planes_gather_set_status).
+ * Returns HSRANS_E_ARG, nothing queued: a null handle or pointer (d_count may be NULL); an object of another context;
+ *   d_out or d_work not 16-byte, d_ranges not 8-byte, d_count not 4-byte or d_workspace not 256-byte aligned;
+ *   workspace_bytes below the size function (or the size function returning 0); any intersection in which a written
+ *   span takes part among the frames, d_ranges[0 .. max_count), d_count (read) and d_out over out_capacity, d_work over
+ *   work_bytes, d_workspace (written).
+ * HSRANS_OK with nothing queued: max_count == 0.
+ * hsrans_planes_gather_batch_indirect_workspace_bytes: a pure function (it needs no object); > 0 and a multiple of 256
+ *   for max_elem_size 2, 4 or 8 with max_count * max_elem_size < 2^31 and coded_planes <= 65,536, non-decreasing in
+ *   max_count and coded_planes; coded_planes == 0 (every plane stored) leaves out the set's part; 0 otherwise.
+ * hsrans_planes_gather_set_indirect_info: a pure function of the object, max_count and work_bytes (no device call),
+ *   through the shape function the entry uses.  HSRANS_E_ARG where the entry would refuse these sizes.
+ * Cost: README and DESIGN 5b (two single-workgroup cuts stand in a line in front of the gather).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct hsrans_planes_gather_set_indirect_info_t
+{
+  uint32_t members, coded, stored; /* members; planes of all members */
+  uint32_t max_rows;               /* of the set's gather: max_count x the largest elem_size (0: every plane stored) */
+  uint32_t merge_grid;             /* workgroups of the merge launch */
+  uint32_t launches;               /* all kernels of one call: the cut, the set's, the merge (0: max_count == 0) */
+  uint32_t set_launches;           /* what hsrans_gather_set_indirect_info reports + the set's cut (0: every plane stored) */
+} hsrans_planes_gather_set_indirect_info_t;
+size_t hsrans_planes_gather_batch_indirect_workspace_bytes(uint32_t coded_planes, uint32_t max_elem_size, uint32_t max_count);
+int hsrans_decode_device_planes_gather_batch_indirect(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs,
+                                                      const hsrans_member_range *d_ranges /* DEVICE, 8-byte aligned, in elements */,
+                                                      const uint32_t *d_count /* DEVICE, or NULL = max_count */, uint32_t max_count, void *d_out, size_t out_capacity,
+                                                      void *d_work, size_t work_bytes, void *d_workspace /* DEVICE, 256-byte aligned */, size_t workspace_bytes,
+                                                      void *hip_stream);
+int hsrans_planes_gather_set_refused(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream);
+int hsrans_planes_gather_set_indirect_info(const hsrans_planes_gather_set *pgs, uint32_t max_count, size_t out_capacity, size_t work_bytes,
+                                           hsrans_planes_gather_set_indirect_info_t *info);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

@@ -396,6 +396,7 @@ int hsrans_dplan_batch_info(const hsrans_batch *b, hsrans_batch_info *info)
   info->launches = (uint32_t)(b->direct.size() + b->grouped.size() + b->solo.size());
   for (const hsrans_batch::GroupedLaunch &G : b->grouped)
     info->grouped_members += (uint32_t)G.member_idx.size();
+  info->groups = b->grouped.empty() ? 0 : b->grouped[0].n_groups;
   info->solo_members = (uint32_t)b->solo.size();
   for (const hsrans_batch::DirectLaunch &L : b->direct)
   {
@@ -409,6 +410,12 @@ int hsrans_dplan_batch_info(const hsrans_batch *b, hsrans_batch_info *info)
     info->lds_bytes = b->direct[0].shape.lds;
     for (int k = 0; k < 8; k++)
       info->class_weights[k] = b->direct[0].shape.weights[k];
+  }
+  else if (!b->grouped.empty()) // no one-chain-per-wave launch: the first grouped one is the first shared launch
+  {
+    info->grid = b->grouped[0].shape.grid;
+    info->block = b->grouped[0].shape.waves * 64;
+    info->lds_bytes = b->grouped[0].shape.lds;
   }
   return HSRANS_OK;
 }

@@ -39,7 +39,7 @@ struct PersistentArgs
 constexpr uint32_t kDynQueues = 64;
 constexpr uint32_t kDynQueueStride = 32; // in uint64: one head per 256 B, so that heads never share a line / atomic unit
 // A device plan owns kCounterSets sets of queue heads and every launch takes the next one (round robin): launches of one
-// plan may overlap (several streams, double-buffered outputs) as long as fewer than kCounterSets are in flight at once.
+// plan may overlap (several streams, double-buffered outputs), up to kCounterSets of them in flight at once (include/hsrans_hip.h).
 constexpr uint32_t kCounterSets = 32;
 
 // Grouped launch (block_/mt_ plans with checkpoints): chains [begin, begin+count) share one histogram = one LDS table

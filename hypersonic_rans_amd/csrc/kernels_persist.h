@@ -86,8 +86,9 @@ __device__ void run_persistent(const WaveCtx &c, const KParams &kp, uint32_t wav
   const uint64_t t_static = HSRANS_STAMPS(kp) ? __builtin_amdgcn_s_memrealtime() : 0;
 
   // Dynamic part: queue k hands out chains [lo, hi) in order.  Its 64-bit head is never reset: every launch draws
-  // exactly H = (hi - lo) + (waves on this queue) tickets from it (each wave fails exactly once), and launches on one
-  // plan are serialised by their stream, so ticket mod H is this launch's ticket.  No memset node, no exit protocol.
+  // exactly H = (hi - lo) + (waves on this queue) tickets from it (each wave fails exactly once), and every launch of a
+  // plan takes the next of its kCounterSets sets of heads, round robin (launches may overlap, up to kCounterSets of them
+  // in flight at once: include/hsrans_hip.h), so ticket mod H is this launch's ticket.  No memset node, no exit protocol.
   const uint32_t dyn0 = pa.static_total;
   const uint64_t D = pa.n_chains - dyn0;
   const uint32_t nq = W < kDynQueues ? W : kDynQueues; // queues in use: every one of them needs a wave

@@ -441,10 +441,11 @@ typedef struct hsrans_batch_info
 {
   uint32_t members, launches;            /* kernel launches one hsrans_decode_device_batch call makes */
   uint32_t direct_members, solo_members; /* members in the shared one-chain-per-wave launch(es) / with a launch of their own */
-  uint32_t grouped_members, reserved;    /* block_/mt_ members with checkpoints sharing a grouped launch (one per histogram width) */
-  uint32_t grid, block, lds_bytes;       /* the (first) shared launch */
-  uint32_t class_weights[8];             /* per-mille run lengths of the 8 wave scheduling classes it was dealt with */
-  double imbalance;                      /* its most loaded wave slot (groups / class weight) over the mean: 1.0 = all waves end together */
+  uint32_t grouped_members, groups;      /* block_/mt_ members with checkpoints sharing a grouped launch (one per histogram width); the groups (blocks,
+                                          * parts of blocks, runs of single-symbol blocks) of the first grouped launch: more than its grid = by ticket */
+  uint32_t grid, block, lds_bytes;       /* the (first) shared launch: the one-chain-per-wave one, or the grouped one where there is none */
+  uint32_t class_weights[8];             /* one-chain-per-wave launch only (else 0): per-mille run lengths of the 8 wave scheduling classes it was dealt with */
+  double imbalance;                      /* one-chain-per-wave launches only (else 0): the most loaded wave slot (groups / class weight) over the mean: 1.0 = all waves end together */
 } hsrans_batch_info;
 int hsrans_dplan_batch_info(const hsrans_batch *batch, hsrans_batch_info *info);
 /* hsrans_index_boundaries for a stream that will be decoded as member `member` of a batch of `count` streams of the given decoded

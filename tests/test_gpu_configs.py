@@ -100,8 +100,9 @@ def test_config4_block_1gib_in_256k_blocks_on_one_gpu(gpu_ctx, oracle):
 def test_dynamic_block_order_with_many_small_blocks(gpu_ctx, oracle):
     """More blocks than resident workgroups: the grouped launch hands the blocks behind the first round out through its ticket
     counter (k_decode_grouped, launch info `dynamic_groups`).  Non-stationary data so that single-symbol (fill) blocks are in the
-    list; several launches of one plan back to back (the counter is never reset: ticket mod n_groups); the same through a device
-    plan written by the GPU encoder; bit-exact against the oracle."""
+    list; several launches of one plan back to back; the same through a device plan written by the GPU encoder; bit-exact against the
+    oracle.  (The 5 launches take 5 fresh sets of the plan's kCounterSets ticket counters, each still zero: "ticket mod n_groups" on a
+    counter that is never reset is what tests/test_gpu_launch_history.py runs, past the sets.)"""
     import torch
     n = 40 << 20
     data = synth.nonstationary(n, seed=77)

@@ -200,26 +200,15 @@ int hsrans_decode_device_gather(hsrans_ctx *ctx, hsrans_dplan *d, const void *d_
 
   // The task list goes up with one stream-ordered copy in front of the launch, through a region of the context's task buffers
   std::lock_guard<std::mutex> lk(ctx->lock);
-  GatherRegion region;
-  const int rc = gather_region_take(ctx, up256(n_tasks * sizeof(GatherTask)), &region);
-  if (rc != HSRANS_OK)
-    return rc;
-  hsrans_gather_task *h_tasks = (hsrans_gather_task *)region.host;
-  if (cut_tasks(L, h.decoded_len, ranges, count, h_tasks, n_tasks) != n_tasks)
-    return HSRANS_E_ARG;
-  if (gather_region_order(ctx, s) != HSRANS_OK)
-    return HSRANS_E_HIP;
-
-  GatherParams gp = gather_params_of(d, d_stream, stream_length, d_dst);
-  gp.tasks = (const GatherTask *)region.dev;
-  gp.n_tasks = (uint32_t)n_tasks;
-  const GatherShape shape = gather_shape(d->tuning, h, ctx->geom, gather_table_mode(d), gp.n_tasks);
-  if (hipMemcpyAsync(region.dev, h_tasks, n_tasks * sizeof(GatherTask), hipMemcpyHostToDevice, s) != hipSuccess || launch_gather(gp, shape, s) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return HSRANS_E_HIP;
-  }
-  return gather_region_commit(ctx, region, s);
+  return gather_region_upload(
+      ctx, n_tasks * sizeof(GatherTask), s,
+      [&](uint8_t *list) { return cut_tasks(L, h.decoded_len, ranges, count, (hsrans_gather_task *)list, n_tasks) == n_tasks ? HSRANS_OK : HSRANS_E_ARG; },
+      [&](const uint8_t *d_list) {
+        GatherParams gp = gather_params_of(d, d_stream, stream_length, d_dst);
+        gp.tasks = (const GatherTask *)d_list;
+        gp.n_tasks = (uint32_t)n_tasks;
+        return launch_gather(gp, gather_shape(d->tuning, h, ctx->geom, gather_table_mode(d), gp.n_tasks), s);
+      });
 }
 
 size_t hsrans_gather_workspace_bytes(uint32_t max_count)

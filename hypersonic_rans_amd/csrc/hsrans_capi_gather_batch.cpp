@@ -108,6 +108,29 @@ static size_t cut_batch(const hsrans_gather_member *members, uint32_t n_members,
   return (size_t)total;
 }
 
+// the set's status word, and the byte-plane gather objects' (hsrans_internal.h)
+int refusal_word_create(hsrans_ctx *ctx, uint32_t **word)
+{
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)word, sizeof(uint32_t)) != hipSuccess || hipMemset(*word, 0, sizeof(uint32_t)) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  return HSRANS_OK;
+}
+
+int refusal_word_take(uint32_t *word, hipStream_t s)
+{
+  uint32_t status = 0xFFFFFFFF;
+  if (hipMemcpyAsync(&status, word, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  if (status == 0)
+    return HSRANS_OK;
+  if (hipMemsetAsync(word, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return HSRANS_E_HIP;
+  return HSRANS_E_DEVICE;
+}
+
 extern "C"
 {
 
@@ -200,7 +223,7 @@ int hsrans_gather_set_create(hsrans_ctx *ctx, hsrans_dplan *const *dplans, const
       hipMemcpy(set->d_members, recs.data(), count * sizeof(GatherSetMember), hipMemcpyHostToDevice) != hipSuccess ||
       hipMalloc((void **)&set->d_position, (size_t)count * sizeof(uint32_t)) != hipSuccess ||
       hipMemcpy(set->d_position, position.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc((void **)&set->d_refused, sizeof(uint32_t)) != hipSuccess || hipMemset(set->d_refused, 0, sizeof(uint32_t)) != hipSuccess)
+      refusal_word_create(ctx, &set->d_refused) != HSRANS_OK)
   {
     (void)hipGetLastError();
     hsrans_gather_set_destroy(set);
@@ -292,6 +315,7 @@ int hsrans_decode_device_gather_batch(hsrans_ctx *ctx, hsrans_gather_set *set, c
   hipStream_t s = (hipStream_t)hip_stream;
 
   // all kinds' lists in one region of the context's task buffers: one stream-ordered copy in front of the launches
+  // (not gather_region_upload: this call queues several launches and commits after a partial failure)
   GatherRegion region;
   const int rc = gather_region_take(ctx, need, &region);
   if (rc != HSRANS_OK)
@@ -433,15 +457,7 @@ int hsrans_gather_set_refused(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip
 {
   if (ctx == nullptr || set == nullptr || set->ctx != ctx)
     return HSRANS_E_ARG;
-  uint32_t status = 0xFFFFFFFF;
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (hipMemcpyAsync(&status, set->d_refused, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return HSRANS_E_HIP;
-  if (status == 0)
-    return HSRANS_OK;
-  if (hipMemsetAsync(set->d_refused, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return HSRANS_E_HIP;
-  return HSRANS_E_DEVICE;
+  return refusal_word_take(set->d_refused, (hipStream_t)hip_stream);
 }
 
 int hsrans_gather_set_status(hsrans_ctx *ctx, hsrans_gather_set *set, void *hip_stream, int *member_status)

@@ -11,6 +11,7 @@
 
 #include "../../include/hsrans_hip.h"
 #include "hsrans_planes.h"
+#include "planes_cut_batch.h"
 
 #include "hsrans_internal.h"
 
@@ -18,10 +19,7 @@ namespace
 {
 constexpr uint32_t kMaxBatchTasks = 1u << 24; // hsrans_encode_device_batch: fewer mt_ blocks than this in one call
 
-bool width_ok(uint32_t W) { return W == 2 || W == 4 || W == 8; }
-bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
 size_t plane_stride(int states, size_t elements) { return up256(capacity(HSRANS_MT, states, elements)); } // a coded plane's room in the frame
-Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
 
 // the planes of a workspace: plane p at p * up256(elements)
 PlanePtrs work_planes(uint32_t W, void *d_work, size_t elements)
@@ -35,7 +33,7 @@ PlanePtrs work_planes(uint32_t W, void *d_work, size_t elements)
 // the checks of the two kernel entries: W pointers to `elements` bytes each and the element buffer, all 16-byte aligned, none meeting another
 bool kernel_args_ok(uint32_t W, const void *d_elements, size_t elements, const void *const *d_planes, bool planes_written, PlanePtrs *pp)
 {
-  if (!width_ok(W) || !aligned16(d_elements) || d_planes == nullptr || elements == 0 || elements > kPlanesMaxElements)
+  if (!planes_width_ok(W) || !aligned16(d_elements) || d_planes == nullptr || elements == 0 || elements > kPlanesMaxElements)
     return false;
   std::vector<Span> spans;
   spans.push_back(span_of(d_elements, elements * W, !planes_written));
@@ -63,7 +61,7 @@ void drop_plans(hsrans_dplan **plans, uint32_t W)
 bool planes_encode_check(uint32_t W, int states, uint32_t bits, const void *d_in, size_t elements, const void *d_frame, size_t frame_capacity, uint32_t block_size,
                          uint32_t index_interval, uint32_t flags, bool want_plans, PlanesEncShape *out)
 {
-  if (!width_ok(W) || (flags & ~HSRANS_PLANES_STORE_INCOMPRESSIBLE) != 0 || !aligned16(d_in) || !aligned16(d_frame))
+  if (!planes_width_ok(W) || (flags & ~HSRANS_PLANES_STORE_INCOMPRESSIBLE) != 0 || !aligned16(d_in) || !aligned16(d_frame))
     return false;
   if (!(states == 32 || states == 64) || elements == 0 || elements > kPlanesMaxElements)
     return false;
@@ -78,7 +76,7 @@ bool planes_encode_check(uint32_t W, int states, uint32_t bits, const void *d_in
 
 int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans)
 {
-  if (ctx == nullptr || desc == nullptr || dplans == nullptr || !width_ok(desc->elem_size) || !valid_codec(HSRANS_MT, (int)desc->states, desc->bits) ||
+  if (ctx == nullptr || desc == nullptr || dplans == nullptr || !planes_width_ok(desc->elem_size) || !valid_codec(HSRANS_MT, (int)desc->states, desc->bits) ||
       desc->elements == 0 || desc->elements > kPlanesMaxElements || (desc->stored_mask >> desc->elem_size) != 0)
     return HSRANS_E_ARG;
   const uint32_t W = desc->elem_size;
@@ -104,21 +102,21 @@ int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsr
 
 extern "C" size_t hsrans_planes_capacity(uint32_t elem_size, int states, size_t elements)
 {
-  if (!width_ok(elem_size) || (states != 32 && states != 64) || elements == 0)
+  if (!planes_width_ok(elem_size) || (states != 32 && states != 64) || elements == 0)
     return 0;
   return elem_size * plane_stride(states, elements);
 }
 
 extern "C" size_t hsrans_planes_workspace_bytes(uint32_t elem_size, size_t elements)
 {
-  if (!width_ok(elem_size) || elements == 0)
+  if (!planes_width_ok(elem_size) || elements == 0)
     return 0;
   return elem_size * up256(elements);
 }
 
 extern "C" int hsrans_planes_split(uint32_t elem_size, const void *in, size_t elements, uint8_t *const *planes)
 {
-  if (!width_ok(elem_size) || in == nullptr || planes == nullptr)
+  if (!planes_width_ok(elem_size) || in == nullptr || planes == nullptr)
     return HSRANS_E_ARG;
   for (uint32_t p = 0; p < elem_size; p++)
     if (planes[p] == nullptr)
@@ -132,7 +130,7 @@ extern "C" int hsrans_planes_split(uint32_t elem_size, const void *in, size_t el
 
 extern "C" int hsrans_planes_merge(uint32_t elem_size, const uint8_t *const *planes, size_t elements, void *out)
 {
-  if (!width_ok(elem_size) || out == nullptr || planes == nullptr)
+  if (!planes_width_ok(elem_size) || out == nullptr || planes == nullptr)
     return HSRANS_E_ARG;
   for (uint32_t p = 0; p < elem_size; p++)
     if (planes[p] == nullptr)
@@ -181,7 +179,7 @@ try
 {
   if (desc != nullptr)
     *desc = hsrans_planes_desc{};
-  if (!width_ok(elem_size))
+  if (!planes_width_ok(elem_size))
     return 0;
   const uint32_t W = elem_size;
   for (uint32_t p = 0; out_dplans != nullptr && p < W; p++)
@@ -278,7 +276,7 @@ catch (...) // (thrown only after the caller's arrays were reset, or before elem
 {
   if (desc != nullptr)
     *desc = hsrans_planes_desc{};
-  if (width_ok(elem_size))
+  if (planes_width_ok(elem_size))
     drop_plans(out_dplans, elem_size);
   return 0;
 }

@@ -23,15 +23,11 @@ namespace
 constexpr uint32_t kMaxBatchMembers = 65536;  // hsrans_encode_device_batch: members of one call
 constexpr uint64_t kMaxBatchTasks = 1u << 24; // ... and fewer mt_ blocks than this
 
-bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
-Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
-bool wraps(const void *p, size_t bytes) { return (uintptr_t)p + bytes < (uintptr_t)p; }
-
 // a member's region of the workspace: hsrans_planes_workspace_bytes, 0 for what that function refuses
 size_t region_bytes(uint32_t W, size_t elements) { return hsrans_planes_workspace_bytes(W, elements); }
 
 // Uploads `table` through a region of the context's task buffers and launches `launch(device table)` behind it on `s`, under ctx->lock:
-// the gathers' protocol (take, fill, order, copy, launch, commit).
+// the gathers' protocol (gather_region_upload).
 template <typename Launch>
 int launch_with_table(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &table, hipStream_t s, Launch &&launch)
 {
@@ -39,19 +35,13 @@ int launch_with_table(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &tab
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   const size_t bytes = table.size() * sizeof(PlanesBatchMember);
-  GatherRegion region;
-  const int rc = gather_region_take(ctx, up256(bytes), &region);
-  if (rc != HSRANS_OK)
-    return rc;
-  memcpy(region.host, table.data(), bytes);
-  if (gather_region_order(ctx, s) != HSRANS_OK)
-    return HSRANS_E_HIP;
-  if (hipMemcpyAsync(region.dev, region.host, bytes, hipMemcpyHostToDevice, s) != hipSuccess || launch((const PlanesBatchMember *)region.dev) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return HSRANS_E_HIP;
-  }
-  return gather_region_commit(ctx, region, s);
+  return gather_region_upload(
+      ctx, bytes, s,
+      [&](uint8_t *host) {
+        memcpy(host, table.data(), bytes);
+        return HSRANS_OK;
+      },
+      [&](const uint8_t *dev) { return launch((const PlanesBatchMember *)dev); });
 }
 
 // every output of a failed encode: no frame, no descriptor, no plan (one already made is destroyed)

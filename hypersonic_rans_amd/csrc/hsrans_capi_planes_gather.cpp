@@ -14,7 +14,7 @@
 
 #include "../../include/hsrans_hip.h"
 #include "hsrans_planes.h"
-#include "planes_cut.h"
+#include "planes_cut_batch.h"
 
 #include "hsrans_internal.h"
 
@@ -34,10 +34,6 @@ struct hsrans_planes_gather
 namespace
 {
 static_assert(kPlanesCutTask == kPlanesGatherTaskElements, "planes_cut.h cuts at the merge kernels' task length");
-
-bool width_ok(uint32_t W) { return W == 2 || W == 4 || W == 8; }
-bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
-Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
 
 // a range's slot in every plane's region (planes_cut.h: up16(phase + length) bytes, none for an empty range)
 uint64_t slot_of(const hsrans_range &g) { return planes_range_slot(g.offset, g.length); }
@@ -73,17 +69,31 @@ bool measure_ranges(const hsrans_range *ranges, uint32_t count, uint64_t element
       return false;
     *slots += slot;
     *tasks += planes_range_tasks(g.offset, g.length);
-    if (*tasks >= 0x80000000u)
+    if (*tasks >= kPlanesCutLimit)
       return false;
   }
   return true;
+}
+
+// what the merges read plane p from: the stored plane in the frame, or region p of the workspace (p * stride), whose bit of *work_mask is set
+PlanePtrs merge_sources(const hsrans_planes_desc &desc, const uint8_t *d_frame, void *d_work, size_t stride, uint32_t *work_mask)
+{
+  PlanePtrs src{};
+  *work_mask = 0;
+  for (uint32_t p = 0; p < desc.elem_size; p++)
+  {
+    const bool is_stored = (desc.stored_mask >> p) & 1;
+    src.p[p] = is_stored ? (uint8_t *)d_frame + desc.offset[p] : (uint8_t *)d_work + p * stride;
+    *work_mask |= is_stored ? 0 : 1u << p;
+  }
+  return src;
 }
 } // namespace
 
 extern "C" size_t hsrans_planes_gather_workspace_bytes(uint32_t elem_size, uint32_t count, uint64_t total_elements)
 {
   const uint64_t bytes = total_elements + 30 * (uint64_t)count;
-  if (!width_ok(elem_size) || bytes < total_elements || bytes > (~(uint64_t)0 - 255) / elem_size)
+  if (!planes_width_ok(elem_size) || bytes < total_elements || bytes > (~(uint64_t)0 - 255) / elem_size)
     return 0;
   return elem_size * up256((size_t)bytes);
 }
@@ -150,9 +160,8 @@ try
     }
   }
   // the word hsrans_decode_device_planes_gather_indirect's cut reports a refusal in (as hsrans_gather_set_create makes the set's)
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&pg->d_refused, sizeof(uint32_t)) != hipSuccess || hipMemset(pg->d_refused, 0, sizeof(uint32_t)) != hipSuccess)
+  if (refusal_word_create(ctx, &pg->d_refused) != HSRANS_OK)
   {
-    (void)hipGetLastError();
     hsrans_planes_gather_destroy(pg);
     return HSRANS_E_HIP;
   }
@@ -223,37 +232,22 @@ try
   }
 
   // ---- the merge behind it: its task list through the context's task buffer, ordered with the context's gathers ----
-  PlanePtrs src{};
   uint32_t work_mask = 0;
-  for (uint32_t p = 0; p < W; p++)
-  {
-    const bool is_stored = (desc.stored_mask >> p) & 1;
-    src.p[p] = is_stored ? (uint8_t *)pg->d_frame + desc.offset[p] : (uint8_t *)d_work + p * stride;
-    work_mask |= is_stored ? 0 : 1u << p;
-  }
+  const PlanePtrs src = merge_sources(desc, pg->d_frame, d_work, stride, &work_mask);
   std::lock_guard<std::mutex> lk(ctx->lock);
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const size_t list_bytes = (size_t)n_tasks * sizeof(PlanesGatherTask), need = up256(list_bytes);
-  GatherRegion region;
-  const int rc = gather_region_take(ctx, need, &region);
+  const int rc = gather_region_upload(
+      ctx, (size_t)n_tasks * sizeof(PlanesGatherTask), s,
+      [&](uint8_t *host) {
+        hsrans_planes_gather_task *list = (hsrans_planes_gather_task *)host;
+        cut_ranges(ranges, count, [&](const hsrans_planes_gather_task &t) { *list++ = t; });
+        return HSRANS_OK;
+      },
+      [&](const uint8_t *dev) { return launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, d_out, s); });
   if (rc != HSRANS_OK)
     return rc;
-  hsrans_planes_gather_task *list = (hsrans_planes_gather_task *)region.host;
-  size_t n = 0;
-  cut_ranges(ranges, count, [&](const hsrans_planes_gather_task &t) { list[n++] = t; });
-  if (gather_region_order(ctx, s) != HSRANS_OK)
-    return HSRANS_E_HIP;
-  if (hipMemcpyAsync(region.dev, region.host, list_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-      launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)region.dev, (uint32_t)n_tasks, d_out, s) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return HSRANS_E_HIP;
-  }
-  const int rc_commit = gather_region_commit(ctx, region, s);
-  if (rc_commit != HSRANS_OK)
-    return rc_commit;
   pg->last.rows = count * coded;
   pg->last.merge_tasks = (uint32_t)n_tasks;
   pg->last.launches = set_launches + 1;
@@ -272,8 +266,8 @@ try
   const hsrans_planes &planes = *pg->planes;
   for (uint32_t p = 0; plane_status != nullptr && p < planes.desc.elem_size; p++)
     plane_status[p] = HSRANS_OK;
-  if (pg->set == nullptr) // (every plane stored: nothing to report, but the call still waits for the stream as the set's does)
-    return hipSetDevice(ctx->device) == hipSuccess && stream_settle((hipStream_t)hip_stream, true) ? HSRANS_OK : HSRANS_E_HIP;
+  if (pg->set == nullptr)
+    return planes_all_stored_status(ctx, hip_stream);
   int member_status[HSRANS_PLANES_MAX] = {};
   const int rc = hsrans_gather_set_status(ctx, pg->set, hip_stream, member_status);
   for (size_t k = 0; plane_status != nullptr && k < planes.coded.size(); k++)
@@ -343,7 +337,7 @@ bool indirect_shape(const hsrans_planes_gather *pg, uint32_t max_count, size_t s
 
 extern "C" size_t hsrans_planes_gather_indirect_workspace_bytes(uint32_t elem_size, uint32_t max_count)
 {
-  if (!width_ok(elem_size) || (uint64_t)max_count * elem_size >= 0x80000000u)
+  if (!planes_width_ok(elem_size) || (uint64_t)max_count * elem_size >= 0x80000000u)
     return 0;
   const size_t set_bytes = hsrans_gather_batch_workspace_bytes(elem_size, max_count * elem_size); // (sized for all planes coded: it needs no object)
   return set_bytes == 0 ? 0 : planes_cut_ws(elem_size, max_count).set + up256(set_bytes);
@@ -437,14 +431,8 @@ try
   }
 
   // ---- the merge behind it ----
-  PlanePtrs src{};
   uint32_t work_mask = 0;
-  for (uint32_t p = 0; p < W; p++)
-  {
-    const bool is_stored = (desc.stored_mask >> p) & 1;
-    src.p[p] = is_stored ? (uint8_t *)pg->d_frame + desc.offset[p] : (uint8_t *)d_work + p * stride;
-    work_mask |= is_stored ? 0 : 1u << p;
-  }
+  const PlanePtrs src = merge_sources(desc, pg->d_frame, d_work, stride, &work_mask);
   if (launch_planes_merge_indirect(W, src, work_mask, cp.ranges, cp.header, cp.first_task, cp.base, shape.merge_grid, d_out, s) != hipSuccess)
   {
     (void)hipGetLastError();
@@ -462,16 +450,11 @@ try
 {
   if (ctx == nullptr || pg == nullptr || pg->ctx != ctx)
     return HSRANS_E_ARG;
-  uint32_t status = 0xFFFFFFFF;
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMemcpyAsync(&status, pg->d_refused, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
-  if (status != 0)
-  {
-    if (hipMemsetAsync(pg->d_refused, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return HSRANS_E_HIP;
-    return HSRANS_E_DEVICE;
-  }
+  const int rc = refusal_word_take(pg->d_refused, (hipStream_t)hip_stream);
+  if (rc != HSRANS_OK)
+    return rc;
   // (the set's own word: the planes cut has passed every row the set sees, so this should never fire; it is reported if it does)
   return pg->set != nullptr ? hsrans_gather_set_refused(ctx, pg->set, hip_stream) : HSRANS_OK;
 }

@@ -46,11 +46,6 @@ namespace
 {
 static_assert(kPlanesCutTask == kPlanesGatherTaskElements, "planes_cut.h cuts at the merge kernels' task length");
 
-bool width_ok(uint32_t W) { return planes_width_ok(W); }
-bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
-Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
-bool wraps(const void *p, size_t bytes) { return (uintptr_t)p + bytes < (uintptr_t)p; }
-
 // What the rows come to: the merge's tasks, the workspace's bytes (the sum of W * slot) and, with `coded_at`, the rows of the set's gather
 struct BatchCut
 {
@@ -99,7 +94,7 @@ void cut_rows(const hsrans_member_range *ranges, uint32_t count, const uint32_t 
 extern "C" size_t hsrans_planes_gather_batch_workspace_bytes(uint32_t max_elem_size, uint32_t count, uint64_t total_elements)
 {
   const uint64_t bytes = total_elements + 30 * (uint64_t)count;
-  if (!width_ok(max_elem_size) || bytes < total_elements || bytes > (~(uint64_t)0 - 255) / max_elem_size)
+  if (!planes_width_ok(max_elem_size) || bytes < total_elements || bytes > (~(uint64_t)0 - 255) / max_elem_size)
     return 0;
   return up256((size_t)(max_elem_size * bytes));
 }
@@ -218,7 +213,7 @@ try
   if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&pgs->d_members, bytes) != hipSuccess ||
       hipMemcpy(pgs->d_members, records.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMalloc((void **)&pgs->d_cut_members, cut_bytes) != hipSuccess ||
       hipMemcpy(pgs->d_cut_members, cut_records.data(), cut_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc((void **)&pgs->d_refused, sizeof(uint32_t)) != hipSuccess || hipMemset(pgs->d_refused, 0, sizeof(uint32_t)) != hipSuccess)
+      refusal_word_create(ctx, &pgs->d_refused) != HSRANS_OK)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -304,25 +299,16 @@ try
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
   hipStream_t s = (hipStream_t)hip_stream;
-  const size_t list_bytes = (size_t)cut.tasks * sizeof(PlanesGatherBatchTask);
-  GatherRegion region;
-  const int rc = gather_region_take(ctx, up256(list_bytes), &region);
+  const int rc = gather_region_upload(
+      ctx, (size_t)cut.tasks * sizeof(PlanesGatherBatchTask), s,
+      [&](uint8_t *host) {
+        hsrans_planes_gather_batch_task *list = (hsrans_planes_gather_batch_task *)host;
+        cut_rows(ranges, count, pgs->widths.data(), [&](const hsrans_planes_gather_batch_task &t) { *list++ = t; });
+        return HSRANS_OK;
+      },
+      [&](const uint8_t *dev) { return launch_planes_merge_ranges_batch((const PlanesGatherBatchTask *)dev, (uint32_t)cut.tasks, pgs->d_members, d_work, d_out, s); });
   if (rc != HSRANS_OK)
     return rc;
-  hsrans_planes_gather_batch_task *list = (hsrans_planes_gather_batch_task *)region.host;
-  size_t n = 0;
-  cut_rows(ranges, count, pgs->widths.data(), [&](const hsrans_planes_gather_batch_task &t) { list[n++] = t; });
-  if (gather_region_order(ctx, s) != HSRANS_OK)
-    return HSRANS_E_HIP;
-  if (hipMemcpyAsync(region.dev, region.host, list_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-      launch_planes_merge_ranges_batch((const PlanesGatherBatchTask *)region.dev, (uint32_t)cut.tasks, pgs->d_members, d_work, d_out, s) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return HSRANS_E_HIP;
-  }
-  const int rc_commit = gather_region_commit(ctx, region, s);
-  if (rc_commit != HSRANS_OK)
-    return rc_commit;
   pgs->last.rows = (uint32_t)cut.rows;
   pgs->last.merge_tasks = (uint32_t)cut.tasks;
   pgs->last.launches = set_launches + 1;
@@ -340,8 +326,8 @@ try
     return HSRANS_E_ARG;
   for (size_t k = 0; member_status != nullptr && k < pgs->widths.size(); k++)
     member_status[k] = HSRANS_OK;
-  if (pgs->set == nullptr) // (every plane stored: nothing to report, but the call still waits for the stream as the set's does)
-    return hipSetDevice(ctx->device) == hipSuccess && stream_settle((hipStream_t)hip_stream, true) ? HSRANS_OK : HSRANS_E_HIP;
+  if (pgs->set == nullptr)
+    return planes_all_stored_status(ctx, hip_stream);
   const std::vector<uint32_t> &coded_member = pgs->planes->coded_member;
   std::vector<int> plane_status(coded_member.size(), HSRANS_OK);
   const int rc = hsrans_gather_set_status(ctx, pgs->set, hip_stream, plane_status.data());
@@ -405,7 +391,7 @@ bool batch_indirect_shape(const hsrans_planes_gather_set *pgs, uint32_t max_coun
 
 extern "C" size_t hsrans_planes_gather_batch_indirect_workspace_bytes(uint32_t coded_planes, uint32_t max_elem_size, uint32_t max_count)
 {
-  if (!width_ok(max_elem_size) || coded_planes > 65536 || (uint64_t)max_count * max_elem_size >= 0x80000000u)
+  if (!planes_width_ok(max_elem_size) || coded_planes > 65536 || (uint64_t)max_count * max_elem_size >= 0x80000000u)
     return 0;
   const size_t control = planes_cut_batch_ws(max_elem_size, max_count).set;
   if (coded_planes == 0) // (every plane stored: no set, no call of its own)
@@ -516,16 +502,11 @@ try
 {
   if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx)
     return HSRANS_E_ARG;
-  uint32_t status = 0xFFFFFFFF;
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMemcpyAsync(&status, pgs->d_refused, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
-  if (status != 0)
-  {
-    if (hipMemsetAsync(pgs->d_refused, 0, 4, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return HSRANS_E_HIP;
-    return HSRANS_E_DEVICE;
-  }
+  const int rc = refusal_word_take(pgs->d_refused, (hipStream_t)hip_stream);
+  if (rc != HSRANS_OK)
+    return rc;
   // (the set's own word: the planes cut has passed every row the set sees, so this should never fire; it is reported if it does)
   return pgs->set != nullptr ? hsrans_gather_set_refused(ctx, pgs->set, hip_stream) : HSRANS_OK;
 }

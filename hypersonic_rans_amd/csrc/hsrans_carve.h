@@ -32,6 +32,10 @@ struct Span
   uintptr_t lo, hi;
   bool write;
 };
+inline Span span_of(const void *p, size_t bytes, bool write) { return Span{(uintptr_t)p, (uintptr_t)p + bytes, write}; }
+// what the entries ask of a buffer before they form its span: set and 16-byte aligned; p + bytes does not pass the end of the address space
+inline bool aligned16(const void *p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
+inline bool wraps(const void *p, size_t bytes) { return (uintptr_t)p + bytes < (uintptr_t)p; }
 
 // The overlap rule of every batch entry:
 //   two writes never intersect; a write never intersects a read; reads may share.

@@ -333,6 +333,12 @@ void ck_region(EncParams *ep, uint8_t *at, size_t ck_slots, uint32_t S); // ep->
 // Synchronises `s` whether or not everything before it was queued (what was queued may still read the caller's host buffers); on a failure of
 // either kind the runtime's sticky error is consumed.  True: all was queued and has run.
 bool stream_settle(hipStream_t s, bool queued);
+// the status of a byte-plane gather object all of whose planes were stored: no plan has anything to report, but the call still waits for the
+// stream as the gather set's status call does
+inline int planes_all_stored_status(hsrans_ctx *ctx, void *hip_stream)
+{
+  return hipSetDevice(ctx->device) == hipSuccess && stream_settle((hipStream_t)hip_stream, true) ? HSRANS_OK : HSRANS_E_HIP;
+}
 // an encode's result words (EncParams::result): word 1, it was coded and fitted d_out; with check_refusal also word 2, the listed checkpoints
 // the pass did not meet, which must be 0.  The one-wavefront-per-block mt_ encodes keep their chain count in word 2: no check_refusal there.
 inline bool enc_result_ok(const uint64_t *result, bool check_refusal) { return result[1] == 1 && (!check_refusal || result[2] == 0); }
@@ -490,6 +496,32 @@ int gather_region_take(hsrans_ctx *ctx, size_t need, GatherRegion *region);
 int gather_region_order(hsrans_ctx *ctx, hipStream_t s);
 // records the region's event behind the launches on `s` and moves the cursor; HSRANS_E_HIP: nothing is recorded, the region is free again
 int gather_region_commit(hsrans_ctx *ctx, const GatherRegion &region, hipStream_t s);
+// The whole protocol for a list of `bytes` bytes that one launch (or one chain of launches that fails as a whole) reads: take a region of
+// up256(bytes), fill(host pointer) -> HSRANS_* writes the list, order, one stream-ordered copy, launch(device pointer) -> hipError_t,
+// commit.  The caller holds ctx->lock and has set the device.  What take, fill and commit return is returned as it is; a failed order,
+// copy or launch gives HSRANS_E_HIP, the last two with HIP's error cleared and nothing committed: the region is free again.
+template <typename Fill, typename Launch>
+inline int gather_region_upload(hsrans_ctx *ctx, size_t bytes, hipStream_t s, Fill &&fill, Launch &&launch)
+{
+  GatherRegion region;
+  int rc = gather_region_take(ctx, up256(bytes), &region);
+  if (rc != HSRANS_OK || (rc = fill(region.host)) != HSRANS_OK)
+    return rc;
+  if (gather_region_order(ctx, s) != HSRANS_OK)
+    return HSRANS_E_HIP;
+  if (hipMemcpyAsync(region.dev, region.host, bytes, hipMemcpyHostToDevice, s) != hipSuccess || launch(region.dev) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return HSRANS_E_HIP;
+  }
+  return gather_region_commit(ctx, region, s);
+}
+
+// The status word of an object whose indirect calls the device can refuse (kStatusBadRange), in device memory: made and zeroed on ctx's
+// device; read on `stream`, which is waited for — a word that is set is cleared again and reported as HSRANS_E_DEVICE (the caller has set
+// the device).  hsrans_capi_gather_batch.cpp; hidden: the library's list of exported symbols stays as it was.
+__attribute__((visibility("hidden"))) int refusal_word_create(hsrans_ctx *ctx, uint32_t **word);
+__attribute__((visibility("hidden"))) int refusal_word_take(uint32_t *word, hipStream_t stream);
 
 // ---- what the first decodes share (hsrans_capi_index.cpp): hsrans_decode_device_indexing and hsrans_decode_device_indexing_batch ----
 // What a recording pass writes besides the output: checkpoint states and read cursors, and for a block_ walk the block records, the states

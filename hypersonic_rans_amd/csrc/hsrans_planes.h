@@ -22,6 +22,16 @@ struct PlanePtrs // (by value in the kernel arguments; entries >= W unused)
 {
   uint8_t *p[kPlanesMax];
 };
+// what every launcher that takes them asks of them: W in {2, 4, 8}, planes 0 .. W - 1 set and 16-byte aligned
+inline bool planes_ptrs_ok(uint32_t W, const PlanePtrs &planes)
+{
+  if (W != 2 && W != 4 && W != 8)
+    return false;
+  for (uint32_t p = 0; p < W; p++)
+    if (planes.p[p] == nullptr || ((uintptr_t)planes.p[p] & 15) != 0)
+      return false;
+  return true;
+}
 
 // asynchronous on `stream`; every pointer 16-byte aligned, n in 1..kPlanesMaxElements, W in {2, 4, 8} (hipErrorInvalidValue otherwise)
 hipError_t launch_planes_split(uint32_t W, const void *in, uint64_t n, const PlanePtrs &planes, hipStream_t stream);

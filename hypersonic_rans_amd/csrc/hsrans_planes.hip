@@ -67,12 +67,7 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge(PlanePtrs planes, uin
 
 bool launch_ok(uint32_t W, const void *elements, uint64_t n, const PlanePtrs &planes)
 {
-  if ((W != 2 && W != 4 && W != 8) || elements == nullptr || ((uintptr_t)elements & 15) != 0 || n == 0 || n > kPlanesMaxElements)
-    return false;
-  for (uint32_t p = 0; p < W; p++)
-    if (planes.p[p] == nullptr || ((uintptr_t)planes.p[p] & 15) != 0)
-      return false;
-  return true;
+  return planes_ptrs_ok(W, planes) && elements != nullptr && ((uintptr_t)elements & 15) == 0 && n != 0 && n <= kPlanesMaxElements;
 }
 uint32_t grid_of(uint64_t n)
 {

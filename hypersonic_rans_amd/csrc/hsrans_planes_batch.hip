@@ -13,17 +13,11 @@ namespace
 {
 using namespace planes_detail;
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
-// a pointer read from a record, the same on every lane; it is to device memory, which the compiler cannot see of a pointer that comes out
-// of memory: made a pointer to the global address space first, it is addressed through with global_ instead of flat_ instructions
-__device__ __forceinline__ uint8_t *uni_ptr(uint8_t *p)
-{
-  typedef __attribute__((address_space(1))) uint8_t global_u8;
-  return (uint8_t *)(global_u8 *)uni64((uint64_t)p);
-}
+// a pointer read from a record, the same on every lane
+__device__ __forceinline__ uint8_t *uni_ptr(uint8_t *p) { return global_at(uni64((uint64_t)p)); }
 
-// the member of task t: the last record with first_task <= t (first_task[0] is 0 and t is below the table's total)
+// the member of task t: the last record with first_task <= t (first_task[0] is 0 and t is below the table's total); task_row's search
+// (planes_shuffle.h) over a field of the records
 __device__ __forceinline__ const PlanesBatchMember *member_of(const PlanesBatchMember *__restrict__ members, uint32_t count, uint32_t t)
 {
   uint32_t lo = 0, hi = count;

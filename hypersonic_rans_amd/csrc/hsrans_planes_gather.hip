@@ -17,22 +17,6 @@ using namespace planes_detail;
 
 static_assert(kThreads * kLaneElements == kPlanesGatherTaskElements, "one lane per 16-element block of a task");
 
-// e[4 W]: 16 elements as they lie in memory, to `at` (a multiple of W)
-template <uint32_t W>
-__device__ __forceinline__ void store_elements(uint8_t *at, const uint32_t *e)
-{
-#pragma unroll
-  for (uint32_t i = 0; i < kLaneElements; i++)
-  {
-    if constexpr (W == 2)
-      *(uint16_t *)(at + 2 * i) = (uint16_t)(e[i / 2] >> (16 * (i % 2)));
-    else if constexpr (W == 4)
-      *(uint32_t *)(at + 4 * i) = e[i];
-    else
-      *(uint2 *)(at + 8 * i) = make_uint2(e[2 * i], e[2 * i + 1]);
-  }
-}
-
 // grid: one workgroup per task; work_mask bit p: planes.p[p] is a workspace region (indexed by work_pos), else a stored plane (indexed by src)
 template <uint32_t W>
 __global__ __launch_bounds__(kThreads) void k_planes_merge_ranges(PlanePtrs planes, uint32_t work_mask, const PlanesGatherTask *__restrict__ tasks, uint8_t *__restrict__ out)
@@ -75,12 +59,9 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_ranges(PlanePtrs plan
 hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, void *out,
                                       hipStream_t stream)
 {
-  if ((W != 2 && W != 4 && W != 8) || out == nullptr || ((uintptr_t)out & 15) != 0 || d_tasks == nullptr || ((uintptr_t)d_tasks & 7) != 0 || n_tasks == 0 ||
+  if (!planes_ptrs_ok(W, planes) || out == nullptr || ((uintptr_t)out & 15) != 0 || d_tasks == nullptr || ((uintptr_t)d_tasks & 7) != 0 || n_tasks == 0 ||
       n_tasks > 0x7FFFFFFFu || (work_mask >> W) != 0)
     return hipErrorInvalidValue;
-  for (uint32_t p = 0; p < W; p++)
-    if (planes.p[p] == nullptr || ((uintptr_t)planes.p[p] & 15) != 0)
-      return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   if (W == 2)
     k_planes_merge_ranges<2><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, dst);

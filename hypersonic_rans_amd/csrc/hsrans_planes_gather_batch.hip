@@ -2,8 +2,8 @@
 // frames in ONE launch (hsrans_decode_device_planes_gather_batch).  One workgroup serves one task — at most 4096 elements of one row, cut on
 // the source's 16-element grid (hsrans_planes_gather_batch_tasks) — and reads, the same on every lane and on scalar loads, its 48-byte task
 // and then the record of the task's member: the element size W, which planes were coded and where the stored planes lie.  It branches once
-// on W into the body of k_planes_merge_ranges<W>, of which this unit has its own copy: a lane per aligned 16-element block, each plane one
-// 16-byte load — a coded plane from the call's workspace (work_pos + p * plane_step: the row's sub-slot of plane p), a stored plane straight
+// on W into the body of k_planes_merge_ranges<W>, of which this unit has its own copy (planes_shuffle.h says why): a lane per aligned
+// 16-element block, each plane one 16-byte load — a coded plane from the call's workspace (work_pos + p * plane_step: the row's sub-slot of plane p), a stored plane straight
 // from its frame (the record's address + src) —, merge16, and W 16-byte stores where the output address allows it, element-wide stores
 // otherwise; heads and tails move byte by byte, so nothing outside a range is read from a stored plane or written.  2-, 4- and 8-byte
 // members share the launch.
@@ -18,32 +18,6 @@ using namespace planes_detail;
 
 static_assert(kThreads * kLaneElements == kPlanesGatherTaskElements, "one lane per 16-element block of a task");
 static_assert(sizeof(PlanesGatherBatchTask) == 48 && sizeof(PlanesGatherBatchMember) == 72, "the task list's and the member table's layout");
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
-// an address that came out of memory (a record's pointer) or was formed from one, the same on every lane: made a pointer to the global
-// address space, it is addressed through with global_ instead of flat_ instructions (hsrans_planes_batch.hip: uni_ptr)
-__device__ __forceinline__ const uint8_t *global_at(uint64_t address)
-{
-  typedef __attribute__((address_space(1))) uint8_t global_u8;
-  return (const uint8_t *)(const global_u8 *)address;
-}
-
-// e[4 W]: 16 elements as they lie in memory, to `at` (a multiple of W)
-template <uint32_t W>
-__device__ __forceinline__ void store_elements(uint8_t *at, const uint32_t *e)
-{
-#pragma unroll
-  for (uint32_t i = 0; i < kLaneElements; i++)
-  {
-    if constexpr (W == 2)
-      *(uint16_t *)(at + 2 * i) = (uint16_t)(e[i / 2] >> (16 * (i % 2)));
-    else if constexpr (W == 4)
-      *(uint32_t *)(at + 4 * i) = e[i];
-    else
-      *(uint2 *)(at + 8 * i) = make_uint2(e[2 * i], e[2 * i + 1]);
-  }
-}
 
 // the task as the workgroup holds it: every field the same on every lane
 struct Task

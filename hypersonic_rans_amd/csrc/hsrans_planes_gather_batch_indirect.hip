@@ -5,7 +5,7 @@
 // by planes_task_at (planes_cut.h) with base C_r and the sub-slot distance slot_r, and reads the member's record as the list-driven batch
 // merge does (hsrans_planes_gather_batch.hip).  The row rules are planes_cut_batch.h's, which the host's cut uses too.  Control workspace:
 // PlanesCutBatchWs (hsrans_planes.h).
-// The merge's body is k_planes_merge_ranges_batch's, restated here as every unit of the byte-plane layer has its own copy.
+// The merge's body is k_planes_merge_ranges_batch's, restated here (planes_shuffle.h says why).
 #include "hsrans_planes.h"
 #include "hsrans_plan.h"
 #include "planes_cut_batch.h"
@@ -21,17 +21,6 @@ using namespace planes_detail;
 
 static_assert(kThreads * kLaneElements == kPlanesGatherTaskElements && kPlanesCutTask == kPlanesGatherTaskElements, "one lane per 16-element block of a task");
 static_assert(sizeof(PlanesSetRow) == 32 && sizeof(PlanesCutBatchMember) == 16 && sizeof(PlanesGatherBatchMember) == 72, "the rows' and the records' layout");
-
-// a value that is the same on every lane, moved to a scalar register
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
-// an address that came out of memory (a record's pointer) or was formed from one, the same on every lane: made a pointer to the global
-// address space, it is addressed through with global_ instead of flat_ instructions (hsrans_planes_gather_batch.hip)
-__device__ __forceinline__ const uint8_t *global_at(uint64_t address)
-{
-  typedef __attribute__((address_space(1))) uint8_t global_u8;
-  return (const uint8_t *)(const global_u8 *)address;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // One workgroup of 1024 threads, shaped like k_planes_cut: a round is kPlanesCutBatchRows consecutive rows per thread.  A row costs two
@@ -183,25 +172,9 @@ __global__ void __launch_bounds__(1024) k_planes_cut_batch(PlanesCutBatchParams 
 // ---------------------------------------------------------------------------------------------------------------
 // The merge.  Any grid: workgroup b serves tasks b, b + grid, ... below the total the cut left; a workgroup whose first task lies beyond it
 // returns.  A task's row is the last r with first_task[r] <= t (rows without tasks share their successor's entry and are passed over),
-// found by a binary search that is the same on every lane.  The row, C_r and then the member's record are read the same on every lane, on
-// scalar paths; the task is planes_task_at's with base C_r, its planes slot_r apart.  One branch on W into the body.
+// found by task_row (planes_shuffle.h).  The row, C_r and then the member's record are read the same on every lane, on scalar paths; the
+// task is planes_task_at's with base C_r, its planes slot_r apart.  One branch on W into the body.
 // ---------------------------------------------------------------------------------------------------------------
-
-// e[4 W]: 16 elements as they lie in memory, to `at` (a multiple of W)
-template <uint32_t W>
-__device__ __forceinline__ void store_elements(uint8_t *at, const uint32_t *e)
-{
-#pragma unroll
-  for (uint32_t i = 0; i < kLaneElements; i++)
-  {
-    if constexpr (W == 2)
-      *(uint16_t *)(at + 2 * i) = (uint16_t)(e[i / 2] >> (16 * (i % 2)));
-    else if constexpr (W == 4)
-      *(uint32_t *)(at + 4 * i) = e[i];
-    else
-      *(uint2 *)(at + 8 * i) = make_uint2(e[2 * i], e[2 * i + 1]);
-  }
-}
 
 // the task as the workgroup holds it: every field the same on every lane
 struct Task
@@ -262,19 +235,11 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_batch_indirect(const 
   const uint32_t n = uni(header[kPlanesWsCount]);
   for (uint32_t t = blockIdx.x; t < total; t += gridDim.x)
   {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1)
-    {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (uni(first_task[mid]) <= t)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    const PlanesSetRow *row = ranges + lo;
+    const uint32_t r = task_row(first_task, n, t);
+    const PlanesSetRow *row = ranges + r;
     const uint64_t offset = uni64(row->offset), length = uni64(row->length), dst_offset = uni64(row->dst_offset);
     const PlanesGatherBatchMember *m = members + uni(row->member);
-    const PlanesGatherTask cut = planes_task_at<PlanesGatherTask>(offset, length, dst_offset, uni64(bases[lo]), t - uni(first_task[lo]));
+    const PlanesGatherTask cut = planes_task_at<PlanesGatherTask>(offset, length, dst_offset, uni64(bases[r]), t - uni(first_task[r]));
     const Task task{cut.src, cut.work_pos, planes_range_slot(offset, length), (uint64_t)cut.dst_delta, cut.lo, cut.hi};
     const uint32_t W = uni(m->W);
     if (W == 2)

@@ -3,8 +3,7 @@
 // behind the set's own indirect call, k_planes_merge_indirect<W> interleaves the ranges: it finds each task's range in the prefix the cut
 // left and derives the task by planes_task_at (planes_cut.h), the function the host's cut lists its tasks with.  Control workspace:
 // PlanesCutWs (hsrans_planes.h).
-// The merge's body is k_planes_merge_ranges' (hsrans_planes_gather.hip), restated here: called from both kernels as one function it changed
-// the code of the three list-driven kernels, so those keep their own text and this unit has its copy.
+// The merge's body is k_planes_merge_ranges' (hsrans_planes_gather.hip), restated here (planes_shuffle.h says why).
 #include "hsrans_planes.h"
 #include "hsrans_plan.h"
 #include "planes_cut.h"
@@ -30,12 +29,7 @@ static_assert(sizeof(PlanesRange) == 24 && sizeof(PlanesSetRow) == 32, "the rang
 // the regions' stride or 2^31 tasks or more refuses the whole call: task total and row count are written as 0 after the last round and
 // kStatusBadRange is set.  Every word the set's launches and the merge read is written by every call.
 // ---------------------------------------------------------------------------------------------------------------
-// a value that is the same on every lane, moved to a scalar register
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
-
 constexpr uint32_t kPlanesCutBatch = 2;
-constexpr uint64_t kTaskLimit = 1ull << 31;
 
 __global__ void __launch_bounds__(1024) k_planes_cut(PlanesCutParams cp)
 {
@@ -127,7 +121,7 @@ __global__ void __launch_bounds__(1024) k_planes_cut(PlanesCutParams cp)
       bad = true;
       slot_carry = 0;
     }
-    if (task_carry >= kTaskLimit)
+    if (task_carry >= kPlanesCutLimit)
     {
       bad = true;
       task_carry = 0;
@@ -151,24 +145,8 @@ __global__ void __launch_bounds__(1024) k_planes_cut(PlanesCutParams cp)
 // ---------------------------------------------------------------------------------------------------------------
 // The merge.  Any grid: workgroup b serves tasks b, b + grid, ... below the total the cut left; a workgroup whose first task lies beyond it
 // returns.  A task's range is the last r with first_task[r] <= t (ranges without tasks share their successor's entry and are passed
-// over), found by a binary search that is the same on every lane; the task is planes_task_at's.
+// over), found by task_row (planes_shuffle.h); the task is planes_task_at's.
 // ---------------------------------------------------------------------------------------------------------------
-
-// e[4 W]: 16 elements as they lie in memory, to `at` (a multiple of W)
-template <uint32_t W>
-__device__ __forceinline__ void store_elements(uint8_t *at, const uint32_t *e)
-{
-#pragma unroll
-  for (uint32_t i = 0; i < kLaneElements; i++)
-  {
-    if constexpr (W == 2)
-      *(uint16_t *)(at + 2 * i) = (uint16_t)(e[i / 2] >> (16 * (i % 2)));
-    else if constexpr (W == 4)
-      *(uint32_t *)(at + 4 * i) = e[i];
-    else
-      *(uint2 *)(at + 8 * i) = make_uint2(e[2 * i], e[2 * i + 1]);
-  }
-}
 
 // this lane's aligned 16-element block of task t (k_planes_merge_ranges' body): a whole block is one aligned 16-byte load per plane, merge16
 // and W 16-byte stores where its output address allows it, 16 element-wide stores otherwise; the head and the tail of a range move element
@@ -219,17 +197,9 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_indirect(PlanePtrs pl
   const uint32_t n = uni(header[kPlanesWsCount]);
   for (uint32_t t = blockIdx.x; t < total; t += gridDim.x)
   {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1)
-    {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (uni(first_task[mid]) <= t)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    const uint64_t offset = uni64(ranges[lo].offset), length = uni64(ranges[lo].length), dst_offset = uni64(ranges[lo].dst_offset);
-    const PlanesGatherTask task = planes_task_at<PlanesGatherTask>(offset, length, dst_offset, uni64(bases[lo]), t - uni(first_task[lo]));
+    const uint32_t r = task_row(first_task, n, t);
+    const uint64_t offset = uni64(ranges[r].offset), length = uni64(ranges[r].length), dst_offset = uni64(ranges[r].dst_offset);
+    const PlanesGatherTask task = planes_task_at<PlanesGatherTask>(offset, length, dst_offset, uni64(bases[r]), t - uni(first_task[r]));
     merge_task<W>(planes, work_mask, task, out);
   }
 }
@@ -257,12 +227,9 @@ hipError_t launch_planes_cut(const PlanesCutParams &cp, hipStream_t stream)
 hipError_t launch_planes_merge_indirect(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesRange *d_ranges, const uint32_t *d_header,
                                         const uint32_t *d_first_task, const uint64_t *d_base, uint32_t grid, void *out, hipStream_t stream)
 {
-  if ((W != 2 && W != 4 && W != 8) || out == nullptr || ((uintptr_t)out & 15) != 0 || d_ranges == nullptr || ((uintptr_t)d_ranges & 7) != 0 || d_header == nullptr ||
+  if (!planes_ptrs_ok(W, planes) || out == nullptr || ((uintptr_t)out & 15) != 0 || d_ranges == nullptr || ((uintptr_t)d_ranges & 7) != 0 || d_header == nullptr ||
       d_first_task == nullptr || d_base == nullptr || grid == 0 || grid > 0x7FFFFFFFu || (work_mask >> W) != 0)
     return hipErrorInvalidValue;
-  for (uint32_t p = 0; p < W; p++)
-    if (planes.p[p] == nullptr || ((uintptr_t)planes.p[p] & 15) != 0)
-      return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   (void)hipGetLastError();
   if (W == 2)

@@ -14,6 +14,8 @@
 #endif
 
 constexpr uint64_t kPlanesCutTask = 4096; // elements of a task (kPlanesGatherTaskElements, hsrans_planes.h)
+// what a call may come to: fewer merge tasks and fewer gather rows than this (a launch's workgroups, the set's limit)
+constexpr uint64_t kPlanesCutLimit = (uint64_t)1 << 31;
 
 // [offset, offset + length) lies inside [0, extent]: (extent, 0) passes, (extent + 1, 0) does not (gather_extent_ok's form, hsrans_kernels.h)
 HSRANS_PLANES_CUT_FN bool planes_extent_ok(uint64_t offset, uint64_t length, uint64_t extent) { return offset <= extent && length <= extent - offset; }

@@ -9,9 +9,6 @@
 
 #include "planes_cut.h"
 
-// what a call may come to: fewer merge tasks and fewer gather rows than this (a launch's workgroups, the set's limit)
-constexpr uint64_t kPlanesCutLimit = (uint64_t)1 << 31;
-
 // What one row comes to: its slot in each of its member's W sub-slots, the W * slot bytes it takes of the workspace, its merge tasks and —
 // one per coded plane of its member, none for an empty row — its rows of the set's gather.
 struct PlanesRowCut

@@ -1,6 +1,15 @@
-// planes_shuffle.h — the in-register byte shuffles of the byte-plane kernels (hsrans_planes.hip, hsrans_planes_gather.hip): 16 elements of W
-// bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  Device code only;
-// every function is inlined into the kernel that calls it.  Everything is in hsrans::planes_detail; the two units say `using namespace`.
+// planes_shuffle.h — what the byte-plane kernels (the six hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
+// bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  And the small
+// helpers of the table- and list-driven kernels: wave-uniform values as scalars, the global-address cast, the element-wide stores of a
+// block whose output is not 16-byte aligned, and the search of a task's row in a prefix of task counts.  Device code only; every function
+// is inlined into the kernel that calls it.  Everything is in hsrans::planes_detail; every unit says `using namespace`.
+//
+// What is NOT here: the range merges' 16-element block body — from the full-block path (load16 per plane, merge16, the 16-byte or
+// element-wide stores) down to the byte-by-byte head and tail — which each of the four hsrans_planes_gather*.hip units writes out.  As one
+// __forceinline__ template (plane pointers by array reference or in a by-value struct, the output pointer __restrict__ or not) it changed
+// the kernels' code every time: with __restrict__ k_planes_merge_ranges<2> went from 20 to 38 VGPRs and its unit from 513 to 688
+// instructions, and in all four forms the stores to a misaligned destination were merged differently in every kernel (fewer dwordx4, more
+// dword and dwordx2).  Nobody has measured what that costs, so the four copies stay until somebody does.
 #ifndef HSRANS_PLANES_SHUFFLE_H
 #define HSRANS_PLANES_SHUFFLE_H
 
@@ -13,6 +22,33 @@ namespace planes_detail
 {
 inline constexpr uint32_t kThreads = 256;     // lanes of a workgroup of every byte-plane kernel
 inline constexpr uint32_t kLaneElements = 16; // elements a lane moves
+
+// a value that is the same on every lane, moved to a scalar register
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
+// an address that came out of memory (a record's pointer) or was formed from one: that it is to device memory the compiler cannot see, so
+// it is made a pointer to the global address space first and is addressed through with global_ instead of flat_ instructions
+__device__ __forceinline__ uint8_t *global_at(uint64_t address)
+{
+  typedef __attribute__((address_space(1))) uint8_t global_u8;
+  return (uint8_t *)(global_u8 *)address;
+}
+
+// the row of task t in the exclusive prefix of n rows' task counts: the last r with first_task[r] <= t (first_task[0] is 0 and t is below
+// the total; rows without tasks share their successor's entry and are passed over).  A binary search that is the same on every lane.
+__device__ __forceinline__ uint32_t task_row(const uint32_t *__restrict__ first_task, uint32_t n, uint32_t t)
+{
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1)
+  {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (uni(first_task[mid]) <= t)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
 
 // __builtin_amdgcn_perm(hi, lo, sel): result byte k = byte sel[k] of {lo: 0..3, hi: 4..7}
 __device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
@@ -34,6 +70,22 @@ __device__ __forceinline__ void load16(const uint8_t *at, uint32_t *w)
   w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
 }
 __device__ __forceinline__ void store16(uint8_t *at, const uint32_t *w) { *(uint4 *)at = make_uint4(w[0], w[1], w[2], w[3]); }
+
+// e[4 W]: 16 elements as they lie in memory, to `at` (a multiple of W, not of 16) as 16 element-wide stores
+template <uint32_t W>
+__device__ __forceinline__ void store_elements(uint8_t *at, const uint32_t *e)
+{
+#pragma unroll
+  for (uint32_t i = 0; i < kLaneElements; i++)
+  {
+    if constexpr (W == 2)
+      *(uint16_t *)(at + 2 * i) = (uint16_t)(e[i / 2] >> (16 * (i % 2)));
+    else if constexpr (W == 4)
+      *(uint32_t *)(at + 4 * i) = e[i];
+    else
+      *(uint2 *)(at + 8 * i) = make_uint2(e[2 * i], e[2 * i + 1]);
+  }
+}
 
 // e[4 W]: 16 elements as they lie in memory; pl[p][j]: bytes 4 j .. 4 j + 3 of plane p's 16
 template <uint32_t W>

@@ -1,38 +1,20 @@
 """Build-time guard for hsrans_encode_device_ex_batch: the compiler's resource report (csrc/build/hsrans_encode.remarks) lists its four
 kernels — the chain for both state counts — none spills to scratch, and a batched kernel needs no more registers and LDS than the single
 call's kernel whose code it runs."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "hypersonic_rans_amd", "csrc", "build")
+import kernel_remarks
+
 NS = "_ZN6hsrans12_GLOBAL__N_1"
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    path = os.path.join(BUILD, "hsrans_encode.remarks")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "hypersonic_rans_amd", "csrc")])
-    out, cur = {}, None
-    for line in open(path).read().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
+    return kernel_remarks.read("hsrans_encode")
 
 
 def _one(kernels, mangled_prefix):
-    found = [r for name, r in kernels.items() if name.startswith(NS + mangled_prefix)]
-    assert len(found) == 1, (mangled_prefix, sorted(kernels))
-    return found[0]
+    return kernel_remarks.one(kernels, NS + mangled_prefix)
 
 
 # (mangled: length-prefixed name, then for the chain the state count as a template argument)

@@ -8,26 +8,8 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "hypersonic_rans_amd", "csrc", "build")
-
-
-def _report(name):
-    path = os.path.join(BUILD, name + ".remarks")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "hypersonic_rans_amd", "csrc")])
-    text = open(path).read()
-    kernels = {}
-    cur = None
-    for line in text.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return kernels
+from kernel_remarks import BUILD, ROOT
+from kernel_remarks import read as _report
 
 
 @pytest.mark.parametrize("unit", ("hsrans_kernels", "hsrans_encode"))

@@ -1,33 +1,17 @@
 """Build-time guard for the multi-tensor byte-plane kernels: the compiler's resource report (csrc/build/hsrans_planes_batch.remarks) lists
 exactly the three kernels — k_planes_split_batch, k_planes_merge_batch, k_planes_store_batch — and none of them spills to scratch (the
 split and the merge hold the 8-byte body's 32 dwords of elements and 32 of planes in registers, whatever the member's element size)."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "hypersonic_rans_amd", "csrc", "build")
+import kernel_remarks
+
 NS = "_ZN6hsrans12_GLOBAL__N_1"
 KERNELS = {kind: f"20k_planes_{kind}_batchE" for kind in ("split", "merge", "store")}  # (mangled: length-prefixed name, then the arguments)
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    path = os.path.join(BUILD, "hsrans_planes_batch.remarks")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "hypersonic_rans_amd", "csrc")])
-    out, cur = {}, None
-    for line in open(path).read().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
+    return kernel_remarks.read("hsrans_planes_batch")
 
 
 def test_the_report_lists_exactly_the_three_kernels(kernels):

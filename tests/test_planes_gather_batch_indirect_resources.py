@@ -4,13 +4,12 @@ scratch; the merge — one kernel for 2-, 4- and 8-byte members — uses no LDS 
 (planes_merge_batch_indirect_grid: a workgroup is one wave per SIMD, so a CU holds that many workgroups)."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "hypersonic_rans_amd", "csrc")
-BUILD = os.path.join(CSRC, "build")
+import kernel_remarks
+from kernel_remarks import CSRC
+
 NS = "_ZN6hsrans12_GLOBAL__N_1"
 # (mangled: length-prefixed name, then the argument types)
 CUT = "18k_planes_cut_batchE"
@@ -19,25 +18,11 @@ MERGE = "29k_planes_merge_batch_indirectE"
 
 @pytest.fixture(scope="module")
 def kernels():
-    path = os.path.join(BUILD, "hsrans_planes_gather_batch_indirect.remarks")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-s", "-C", CSRC])
-    out, cur = {}, None
-    for line in open(path).read().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
+    return kernel_remarks.read("hsrans_planes_gather_batch_indirect")
 
 
 def _one(kernels, mangled):
-    found = [r for name, r in kernels.items() if name.startswith(NS + mangled)]
-    assert len(found) == 1, (mangled, sorted(kernels))
-    return found[0]
+    return kernel_remarks.one(kernels, NS + mangled)
 
 
 def _grid_constant():

@@ -2,14 +2,10 @@
 (csrc/build/hsrans_planes_gather_indirect.remarks) lists exactly k_planes_cut and k_planes_merge_indirect for 2-, 4- and 8-byte elements; none
 spills to scratch; the merge kernels use no LDS and keep the waves per SIMD the merge's grid is sized from (planes_merge_indirect_grid: a
 workgroup is one wave per SIMD, so a CU holds that many workgroups)."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "hypersonic_rans_amd", "csrc", "build")
+import kernel_remarks
+
 NS = "_ZN6hsrans12_GLOBAL__N_1"
 # (mangled: length-prefixed name, then the element size as a template argument)
 CUT = "12k_planes_cutE"
@@ -19,25 +15,11 @@ WAVES_PER_SIMD = {"W2": 8, "W4": 8, "W8": 7}
 
 @pytest.fixture(scope="module")
 def kernels():
-    path = os.path.join(BUILD, "hsrans_planes_gather_indirect.remarks")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "hypersonic_rans_amd", "csrc")])
-    out, cur = {}, None
-    for line in open(path).read().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
+    return kernel_remarks.read("hsrans_planes_gather_indirect")
 
 
 def _one(kernels, mangled):
-    found = [r for name, r in kernels.items() if name.startswith(NS + mangled)]
-    assert len(found) == 1, (mangled, sorted(kernels))
-    return found[0]
+    return kernel_remarks.one(kernels, NS + mangled)
 
 
 def test_the_report_lists_exactly_the_four_kernels(kernels):

@@ -1,14 +1,10 @@
 """Build-time guard for the range-merge kernels: the compiler's resource report (csrc/build/hsrans_planes_gather.remarks) lists exactly the
 three kernels — k_planes_merge_ranges for 2-, 4- and 8-byte elements — and none of them spills to scratch or uses LDS (like the two
 whole-frame kernels, they hold a block's elements and planes in registers)."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "hypersonic_rans_amd", "csrc", "build")
+import kernel_remarks
+
 NS = "_ZN6hsrans12_GLOBAL__N_1"
 # (mangled: length-prefixed name, then the element size as a template argument)
 KERNELS = {f"W{W}": f"21k_planes_merge_rangesILj{W}EE" for W in (2, 4, 8)}
@@ -16,19 +12,7 @@ KERNELS = {f"W{W}": f"21k_planes_merge_rangesILj{W}EE" for W in (2, 4, 8)}
 
 @pytest.fixture(scope="module")
 def kernels():
-    path = os.path.join(BUILD, "hsrans_planes_gather.remarks")
-    if not os.path.exists(path):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "hypersonic_rans_amd", "csrc")])
-    out, cur = {}, None
-    for line in open(path).read().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][\w /\[\]]*?): (\d+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
+    return kernel_remarks.read("hsrans_planes_gather")
 
 
 def test_the_report_lists_exactly_the_three_kernels(kernels):

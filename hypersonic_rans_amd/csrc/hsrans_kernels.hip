@@ -898,7 +898,8 @@ LaunchChoice choose_launch(const Tuning &tn, const PlanHeader &h, const DeviceGe
     uint16_t spread_cum[2][17];
     // k_decode_spread's wave weights: the one-chain-per-wave launch's (the device's own once calibrated); one snapshot, the same weights
     // for the check below and for the kernel
-    cum_from_weights(dg.have_direct_weights ? dg.direct_weights : tn.direct_weights, spread_cum);
+    const uint32_t *const spread_weights = dg.have_direct_weights ? dg.direct_weights : tn.direct_weights;
+    cum_from_weights(spread_weights, spread_cum);
     const uint32_t longest = spread_longest_share_of(dg, h.n_chains, spread_cum);
     const uint32_t slds = kSpreadWaves * kFastRingBytes + 2 * table_bytes_for(kModePack64, h.bits) + (kSpreadMaxShare + 1) * (uint32_t)sizeof(Piece);
     if (longest != 0 && longest < f.spread_min_block && 2 * slds <= dg.max_lds) // (a share shorter than every block touches at most two)
@@ -909,6 +910,7 @@ LaunchChoice choose_launch(const Tuning &tn, const PlanHeader &h, const DeviceGe
       c.waves = kSpreadWaves;
       c.lds = slds;
       memcpy(c.cum, spread_cum, sizeof(c.cum));
+      memcpy(c.shape.weights, spread_weights, sizeof(c.shape.weights)); // (launch info: the lengths the table above was made from, not the grouped shape's)
     }
   }
   if (f.parts)

@@ -28,13 +28,24 @@ Tuning read_tuning()
   auto number = [&](const char *name, uint32_t *out) { if (set(name)) *out = (uint32_t)atoi(e); };
   auto unless_0 = [&](const char *name, bool *out) { if (set(name)) *out = atoi(e) != 0; };
   auto list = [&](const char *name, uint32_t n) { return set(name) && parse_list(e, v, n); };
-  auto weights = [&](const char *name, uint32_t *w) { // 8 per-mille values, rescaled to a sum of 8000 (a sum of 0 leaves the defaults)
+  // a list of 8 class lengths inside the domain (hsrans_tuning.h: kClassLengthMin .. kClassLengthMax each); any other list is ignored as a whole
+  auto class_list = [&](const char *name) {
+    if (!list(name, 8))
+      return false;
+    for (uint32_t k = 0; k < 8; k++)
+      if (v[k] < kClassLengthMin || v[k] > kClassLengthMax)
+        return false;
+    return true;
+  };
+  auto weights = [&](const char *name, uint32_t *w) { // ... rescaled to a sum of 8000 (rounded down: never above it)
+    if (!class_list(name))
+      return false;
     uint64_t sum = 0;
-    if (list(name, 8))
-      for (uint32_t k = 0; k < 8; k++)
-        sum += v[k];
-    for (uint32_t k = 0; k < 8 && sum > 0; k++)
+    for (uint32_t k = 0; k < 8; k++)
+      sum += v[k];
+    for (uint32_t k = 0; k < 8; k++)
       w[k] = (uint32_t)((uint64_t)v[k] * 8000 / sum);
+    return true;
   };
   t.waves_per_wg_set = set("HSRANS_WAVES_PER_WG");
   if (t.waves_per_wg_set && atoi(e) >= 4 && atoi(e) <= 16)
@@ -42,8 +53,7 @@ Tuning read_tuning()
   unless_0("HSRANS_SPREAD", &t.spread);
   weights("HSRANS_SLOT_WEIGHTS", t.slot_weights);
   weights("HSRANS_SLOT_WEIGHTS4", t.slot_weights4);
-  weights("HSRANS_DIRECT_WEIGHTS", t.direct_weights);
-  t.direct_weights_set = set("HSRANS_DIRECT_WEIGHTS");
+  t.direct_weights_set = weights("HSRANS_DIRECT_WEIGHTS", t.direct_weights);
   weights("HSRANS_DIRECT_WEIGHTS4", t.direct_weights4);
   weights("HSRANS_DIRECT_WEIGHTS6", t.direct_weights6);
   weights("HSRANS_DIRECT_WEIGHTS3", t.direct_weights3);
@@ -64,17 +74,17 @@ Tuning read_tuning()
   unless_0("HSRANS_DEALT_WIDE", &t.dealt_wide);
   if (set("HSRANS_DEALT_MIN_CHAINS") && atoi(e) > 0)
     t.dealt_min_chains = (uint32_t)atoi(e);
-  if ((t.dealt_weights_set = list("HSRANS_DEALT_WEIGHTS", 8)))
+  if ((t.dealt_weights_set = class_list("HSRANS_DEALT_WEIGHTS"))) // (as given: not rescaled)
     for (uint32_t k = 0; k < 8; k++)
-      t.dealt_weights[k] = v[k] >= 10 ? v[k] : 10;
+      t.dealt_weights[k] = v[k];
   number("HSRANS_DEALT_WT", &t.dealt_wt);
   if (set("HSRANS_DEALT_GAP_GROUPS"))
     t.dealt_gap_groups = (uint64_t)atoi(e);
   t.dealt_trace = set("HSRANS_DEALT_TRACE");
 
-  if ((t.batch_weights_set = list("HSRANS_BATCH_WEIGHTS", 8)))
+  if ((t.batch_weights_set = class_list("HSRANS_BATCH_WEIGHTS"))) // (as given: not rescaled)
     for (uint32_t k = 0; k < 8; k++)
-      t.batch_weights[k] = v[k] ? v[k] : 1;
+      t.batch_weights[k] = v[k];
   t.batch_stamps = set("HSRANS_BATCH_STAMPS");
   unless_0("HSRANS_SHARD_ONE_LAUNCH", &t.shard_one_launch);
   t.calibrate = set("HSRANS_CALIBRATE") && atoi(e) != 0;

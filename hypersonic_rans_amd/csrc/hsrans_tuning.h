@@ -11,6 +11,23 @@
 namespace hsrans
 {
 
+// The domain of a list of class lengths (the nine HSRANS_*_WEIGHTS lists of 8 per-mille values, HSRANS_DEALT_WEIGHTS and
+// HSRANS_BATCH_WEIGHTS): eight values, EVERY one of them kClassLengthMin .. kClassLengthMax as written — the bounds the suite holds
+// hsrans_ctx_calibrate's fits to (tests/test_gpu_calibrate.py; its lengths always sum to 8000, so no fit can wrap a table).  read_tuning
+// ignores any other list as a whole (as it ignores a list of fewer than eight values): the defaults stay, nothing is clamped or
+// reshaped.  The nine lists are then rescaled to a sum of at most 8000 (33 .. 6486 a class), the two others
+// are taken as written.  What the launches need of a list and the domain gives them (tests/test_geometry_domain.py holds a model of every
+// share rule to it):
+//   - a class of at least 10 in each half, so that no cumulative table (w / 10 per wave: cum_from_weights, group_cum_of) ends in 0.
+//     With a zero half k_decode_grouped's weighted split gives every wave of the grid's second half the share [0, 0) of its block — the
+//     block is never decoded — and k_decode_dealt divides by the table's last entry.  A zero CLASS beside live ones is safe in every
+//     kernel (a wave whose share is empty skips its run: `first >= last` in run_grouped, run_spread's `while (i < last)`, `have` in
+//     run_dealt, a run_len of 0 in run_persistent), but the domain keeps it out as well: one rule for all eight values;
+//   - a table that fits its uint16_t entries: 16 waves x 3000 / 10 = 4800 at the most (unbounded values wrapped it, and the kernel's wave
+//     shares were no longer the ones deal_shares had dealt);
+//   - a sum of at most 8000 where static shares are cut (static_shares: static_total <= n_chains).
+constexpr uint32_t kClassLengthMin = 100, kClassLengthMax = 3000;
+
 struct Tuning
 {
   uint32_t waves_per_wg = 16;    // HSRANS_WAVES_PER_WG (4-16): waves per workgroup of the shared-table launches
@@ -33,7 +50,7 @@ struct Tuning
   // (Re-fitted after the decode loops stopped draining the memory queue every iteration: the oldest class now runs three times as
   // many groups as the youngest in the same time.  The same fit with the buffers rotated through HBM lands within 2 % of these.)
   uint32_t direct_weights[8] = {1396, 1332, 1244, 1131, 960, 809, 643, 484}; // (round 3, after the loop's scalar bookkeeping was trimmed: between the fits of two boxes; hsrans_ctx_calibrate fits them to the device at hand)
-  bool direct_weights_set = false; // HSRANS_DIRECT_WEIGHTS set at all: it rules over the calibrated sets (direct_weights_for)
+  bool direct_weights_set = false; // HSRANS_DIRECT_WEIGHTS set to a list inside the domain: it rules over the calibrated sets (direct_weights_for)
   uint32_t direct_weights6[8] = {1192, 1159, 1120, 1072, 976, 907, 829, 745};
   uint32_t direct_weights4[8] = {1097, 1053, 977, 873, 1098, 1053, 977, 873};
   uint32_t direct_weights3[8] = {1052, 1025, 986, 936, 1052, 1025, 986, 936};
@@ -60,12 +77,12 @@ struct Tuning
   uint32_t dealt = 1;        // HSRANS_DEALT=0: grouped plans keep k_decode_spread / k_decode_grouped (comparison)
   bool dealt_wide = true;    // HSRANS_DEALT_WIDE=0: 13 / 14 bits keep the grouped launch (comparison)
   uint32_t dealt_min_chains = 1400; // HSRANS_DEALT_MIN_CHAINS: chains per 1,000 waves of the launch below which a plan is not dealt (tuning; 100 MB in 256 KiB blocks, G = 128 — 1.49 chains a wave — 58.5 us grouped, 47.4 dealt; one chain a wave leaves the class weights nothing to work with)
-  uint32_t dealt_weights[8] = {};   // HSRANS_DEALT_WEIGHTS: 8 per-mille class lengths of the dealt launch (each at least 10), where set
+  uint32_t dealt_weights[8] = {};   // HSRANS_DEALT_WEIGHTS: 8 per-mille class lengths of the dealt launch (inside the domain above, as written), where set
   bool dealt_weights_set = false;
   uint32_t dealt_wt = 1;            // HSRANS_DEALT_WT=0: k_decode_dealt's stores as `nt` instead of written through (comparison)
   uint64_t dealt_gap_groups = 17;   // HSRANS_DEALT_GAP_GROUPS: a second prologue is ~2.5 us = ~17 groups of decoding at 8 waves per SIMD (tuning)
   bool dealt_trace = false;         // HSRANS_DEALT_TRACE: why a plan is or is not dealt, on stderr
-  uint32_t batch_weights[8] = {}; // HSRANS_BATCH_WEIGHTS: 8 per-mille run lengths of a batch's one-chain-per-wave launch (0 counts as 1), where set
+  uint32_t batch_weights[8] = {}; // HSRANS_BATCH_WEIGHTS: 8 per-mille run lengths of a batch's one-chain-per-wave launch (inside the domain above, as written), where set
   bool batch_weights_set = false;
   bool batch_stamps = false;          // HSRANS_BATCH_STAMPS: per-wave finish times of a batch's first shared launch
   bool shard_one_launch = true;       // HSRANS_SHARD_ONE_LAUNCH=0: a launch per sub-run (comparison: tools/shard_projection.py)

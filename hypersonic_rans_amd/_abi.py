@@ -127,6 +127,8 @@ class GatherSetInfo(ctypes.Structure):  # hsrans_gather_set_info_t
 
 PLANES_MAX = 8
 PLANES_STORE_INCOMPRESSIBLE = 1
+PACK_CHUNK = 8192  # HSRANS_PACK_CHUNK
+PACK_MAX_ITEMS = 65536 * PLANES_MAX
 
 
 class PlanesDesc(ctypes.Structure):  # hsrans_planes_desc
@@ -304,6 +306,11 @@ SIGNATURES = {
     "hsrans_planes_set_info": (_i, [_vp, _P(PlanesSetInfo)]),
     "hsrans_decode_device_planes_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "hsrans_planes_set_status": (_i, [_vp, _vp, _vp, _vp]),
+    "hsrans_pack_layout": (_sz, [_vp, _u32, _vp]),
+    "hsrans_pack_tasks": (_sz, [_vp, _u32, _vp]),
+    "hsrans_pack_device": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp]),
+    "hsrans_planes_pack_layout": (_sz, [_P(PlanesDesc), _u32, _P(PlanesDesc), _vp]),
+    "hsrans_planes_pack_device": (_i, [_vp, _P(PlanesDesc), _vp, _vp, _u32, _vp, _sz, _vp, _P(PlanesDesc), _vp]),
     "hsrans_planes_gather_create": (_i, [_vp, _vp, _vp, _sz, _P(_vp)]),
     "hsrans_planes_gather_destroy": (None, [_vp]),
     "hsrans_planes_gather_workspace_bytes": (_sz, [_u32, _u32, _u64]),

@@ -14,7 +14,7 @@ import numpy as np
 import torch  # first: pins the HIP runtime (libamdhip64.so.7) this process uses before our library is loaded
 
 from ._abi import (  # noqa: F401  (the structures, constants and loader are spelled api.<name> by the tests and tools)
-    BLOCK, COMM_ID_BYTES, ENC_INDEPENDENT_BLOCKS, MT, PLANES_MAX, PLANES_STORE_INCOMPRESSIBLE, RAW, SHARD_DECODE_AND_EXCHANGE, SHARD_DECODE_ONLY,
+    BLOCK, COMM_ID_BYTES, ENC_INDEPENDENT_BLOCKS, MT, PACK_CHUNK, PACK_MAX_ITEMS, PLANES_MAX, PLANES_STORE_INCOMPRESSIBLE, RAW, SHARD_DECODE_AND_EXCHANGE, SHARD_DECODE_ONLY,
     SHARD_EXCHANGE_ONLY, BatchInfo, Calibration, EncodeBatchStats, EncodeExBatchStats, EncodeExMember, EncodeMember, EncodeOpts, GatherBatchTask,
     GatherMember, GatherSetInfo, GatherTask, Hist, HsransError, IndexingBatchStats, IndexingMember, LaunchFacts, LaunchInfo, MemberRange, PlanKind,
     PlanesBatchStats, PlanesDesc, PlanesGatherBatchTask, PlanesGatherIndirectInfo, PlanesGatherInfo, PlanesGatherSetIndirectInfo, PlanesGatherSetInfo, PlanesGatherTask, PlanesInfo, PlanesMember,
@@ -471,6 +471,57 @@ def planes_batch_tasks(elements) -> tuple:
     first = (ctypes.c_uint32 * (K + 1))()
     total = int(load_library().hsrans_planes_batch_tasks((_sz * max(K, 1))(*elements), K, first))
     return total, (list(first) if total else [])
+
+
+def _pack_lengths(lengths):
+    """the C array of an arena's item lengths, None where no call could take them (too many, or a value no size_t holds)"""
+    lengths = list(lengths)
+    if len(lengths) > PACK_MAX_ITEMS or any(not 0 <= int(v) < 1 << 64 for v in lengths):
+        return None, 0
+    return (_sz * max(len(lengths), 1))(*[int(v) for v in lengths]), len(lengths)
+
+
+def _pack_buffers(entry: str, tensors):
+    """what the pack wrappers ask of their sources and their arena: CUDA uint8 tensors, contiguous, so that numel() is their bytes"""
+    if any(not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()) for t in tensors):
+        raise TypeError(f"{entry}: the sources and the arena are contiguous CUDA uint8 tensors")
+
+
+def pack_layout(lengths) -> tuple:
+    """hsrans_pack_layout: ``(total, offsets)`` — the exact bytes of an arena that holds items of ``lengths[k]`` bytes, each at a multiple
+    of 16, and where they begin (K + 1 entries, the last the total).  ``(0, [])``: no item, an item of 0 bytes, more than 524,288 items,
+    or an overflow."""
+    arr, K = _pack_lengths(lengths)
+    if arr is None:
+        return 0, []
+    offsets = (ctypes.c_uint64 * (K + 1))()
+    total = int(load_library().hsrans_pack_layout(arr, K, offsets))
+    return total, (list(offsets) if total else [])
+
+
+def pack_tasks(lengths) -> tuple:
+    """hsrans_pack_tasks: ``(total, first_task)`` — the workgroups of the one pack launch over items of ``lengths[k]`` bytes
+    (ceil(up16(length) / PACK_CHUNK) each) and their exclusive prefix.  ``(0, [])``: what pack_layout refuses, or 2^31 tasks or more."""
+    arr, K = _pack_lengths(lengths)
+    if arr is None:
+        return 0, []
+    first = (ctypes.c_uint32 * (K + 1))()
+    total = int(load_library().hsrans_pack_tasks(arr, K, first))
+    return total, (list(first) if total else [])
+
+
+def planes_pack_layout(descs) -> tuple:
+    """hsrans_planes_pack_layout: ``(descs, bases, total)`` — the descriptors of the frames packed plane after plane (offsets
+    member-relative, every plane at a multiple of 16), where each member's frame begins in the arena (K + 1 entries, the last the total)
+    and the arena's exact bytes.  ``([], [], 0)``: no member, more than 65,536, a descriptor hsrans_planes_create's rules refuse, an overflow."""
+    descs = list(descs)
+    K = len(descs)
+    if K == 0 or K > 65536:
+        return [], [], 0
+    src, out = (PlanesDesc * K)(*descs), (PlanesDesc * K)()
+    bases = (ctypes.c_uint64 * (K + 1))()
+    total = int(load_library().hsrans_planes_pack_layout(src, K, out, bases))
+    return ([PlanesDesc.from_buffer_copy(d) for d in out], list(bases), total) if total else ([], [], 0)
 
 
 def planes_split(array) -> list:
@@ -1373,6 +1424,36 @@ class Context(_Handle):
         codes = (ctypes.c_int * max(len(pset.descs), 1))()
         self.L.hsrans_planes_set_status(self.handle, pset.handle, _stream(stream), codes)
         return list(codes)[: len(pset.descs)]
+
+    def pack_device(self, srcs, lengths, arena: torch.Tensor, stream: torch.cuda.Stream | None = None) -> list:
+        """hsrans_pack_device: the first ``lengths[k]`` bytes of the CUDA uint8 tensors ``srcs[k]`` (``lengths`` None: all of each) side by
+        side into ``arena``, each at a multiple of 16 and completed with zeros up to the next, in one launch.  Returns the offsets
+        (K + 1 entries, the last the bytes used: ``pack_layout``'s).  Asynchronous on ``stream`` (default: torch's current stream)."""
+        srcs = list(srcs)
+        _pack_buffers("pack_device", srcs + [arena])
+        if lengths is not None and (len(lengths) != len(srcs) or any(not 0 <= int(n) <= t.numel() for n, t in zip(lengths, srcs))):
+            raise HsransError("pack_device: one length per source, none beyond its tensor", code=2)
+        ptrs, lens = _tensor_arrays(srcs, lengths) if srcs else ((_vp * 1)(), (_sz * 1)())
+        _check(self.L.hsrans_pack_device(self.handle, ptrs, lens, len(srcs), arena.data_ptr(), arena.numel(), _stream(stream, arena.device)), "hsrans_pack_device")
+        return pack_layout(list(lens)[: len(srcs)])[1]
+
+    def planes_pack_device(self, descs, d_frames, arena: torch.Tensor, stream: torch.cuda.Stream | None = None) -> tuple:
+        """hsrans_planes_pack_device: the planes of the frames ``d_frames[k]`` (CUDA uint8 tensors, described by ``descs[k]``) into
+        ``arena`` in one launch.  Returns ``(descs, frames)``: the packed descriptors and ``frames[k]``, the arena's slice that is member
+        k's frame — what make_planes_set's decode, decode_device_planes and the gather creators take in place of the unpacked frame, with
+        the same plans.  ``planes_pack_layout(descs)[2]`` is the arena's exact size.  Asynchronous on ``stream``."""
+        descs, d_frames = list(descs), list(d_frames)
+        K = len(descs)
+        if len(d_frames) != K:
+            raise HsransError(f"planes_pack_device: one frame per descriptor: {K}")
+        _pack_buffers("planes_pack_device", d_frames + [arena])
+        src, out = (PlanesDesc * max(K, 1))(*descs), (PlanesDesc * max(K, 1))()
+        bases = (ctypes.c_uint64 * (K + 1))()
+        frames, frame_lengths = _tensor_arrays(d_frames) if K else ((_vp * 1)(), (_sz * 1)())
+        _check(self.L.hsrans_planes_pack_device(self.handle, src, frames, frame_lengths, K, arena.data_ptr(), arena.numel(), _stream(stream, arena.device), out, bases),
+               "hsrans_planes_pack_device")
+        packed = [PlanesDesc.from_buffer_copy(d) for d in out][:K]
+        return packed, [arena[bases[k]: bases[k] + packed[k].frame_length] for k in range(K)]
 
     def make_planes_gather(self, planes: Planes, d_frame: torch.Tensor, frame_length: int | None = None) -> PlanesGather:
         """hsrans_planes_gather_create: binds ``planes`` to the frame in the CUDA uint8 tensor ``d_frame`` (16-byte aligned) for

@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/hsrans_hip.h" // HSRANS_PACK_CHUNK
 #include "hsrans_carve.h"
 
 namespace hsrans
@@ -59,6 +60,32 @@ constexpr uint32_t planes_tasks_of(uint64_t n) // (host and device; n <= kPlanes
 hipError_t launch_planes_split_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_merge_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_store_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+
+// ---- many byte ranges into one arena in one launch (hsrans_pack_device, hsrans_planes_pack_device): k_pack (hsrans_planes_pack.hip) ----
+// An item's `length` bytes at src go to dst, and the bytes from there up to up16(length) are written as zero; its tasks are the chunks of
+// kPackChunk bytes of those up16(length) bytes, one workgroup each, and first_task is their exclusive prefix over the table.
+// (HSRANS_PACK_CHUNK_BUILD: the chunk of a tuning build of the library, `make pack_variants`; such a library's hsrans_pack_tasks counts in
+// its own chunk, not in the header's)
+#ifdef HSRANS_PACK_CHUNK_BUILD
+constexpr uint32_t kPackChunk = HSRANS_PACK_CHUNK_BUILD;
+#else
+constexpr uint32_t kPackChunk = HSRANS_PACK_CHUNK; // (include/hsrans_hip.h)
+#endif
+static_assert(kPackChunk >= 4096 && (kPackChunk & (kPackChunk - 1)) == 0, "a power of two, at least one round of a workgroup's 16-byte lanes");
+struct PackItem
+{
+  const uint8_t *src; // 16-byte aligned; not one byte at or behind src + length is read
+  uint8_t *dst;       // 16-byte aligned
+  uint64_t length;    // > 0
+  uint32_t first_task, reserved;
+};
+constexpr uint64_t pack_tasks_of(uint64_t length) // (host and device; length <= 2^64 - 16)
+{
+  return (((length + 15) & ~(uint64_t)15) + kPackChunk - 1) / kPackChunk;
+}
+// asynchronous on `stream`, one kernel, n_tasks workgroups (the table's task total, 1 .. 2^31 - 1); the table's records are the caller's
+// to check (hipErrorInvalidValue: a null table, no item, a task total out of range)
+hipError_t launch_pack(const PackItem *d_items, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 
 // One workgroup's work of k_planes_merge_ranges (hsrans_planes_gather_task, include/hsrans_hip.h): the elements [src + lo, src + hi) of the
 // tensor — src a multiple of 16, lo < 16, hi <= kPlanesGatherTaskElements — whose bytes lie at work_pos + (element - src) of a workspace region

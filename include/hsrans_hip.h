@@ -959,6 +959,70 @@ int hsrans_decode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_set *set, c
                                       const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream);
 int hsrans_planes_set_status(hsrans_ctx *ctx, hsrans_planes_set *set, void *hip_stream, int *member_status /* [count] or NULL */);
 /* ------------------------------------------------------------------------------------------------------------
+ * Many streams, or many frames, into one exact-size arena.  The encoders leave every stream in a buffer of hsrans_capacity
+ * bytes and every frame in one of hsrans_planes_capacity bytes — more than the tensor, with gaps between short streams; what
+ * makes the coded size the size in HBM is one more step: the streams' bytes side by side in a buffer of exactly their sum.
+ * These entries are that step, in ONE launch whatever the count, where a caller would otherwise queue a device copy per
+ * stream and rewrite every descriptor.  Two layers, as elsewhere: the codec's streams, and the element layer's frames.
+ *
+ * Streams.  Layout, a pure function of the lengths: offsets[0] = 0, offsets[k + 1] = offsets[k] + up16(lengths[k]) (up16:
+ * rounded up to a multiple of 16); hsrans_pack_layout writes offsets[0 .. count] (may be NULL) and returns offsets[count], the
+ * arena's exact size.  0 for a NULL array, count 0, a length of 0, more than 524,288 items (65,536 members x
+ * HSRANS_PLANES_MAX, the planes sets' limit) or an overflow.
+ * No slack behind the last item: no decode or gather kernel here fetches a stream byte at or beyond up16(length) of its
+ * stream.  Stream words are fetched through a buffer descriptor that begins on a 16-byte boundary of the stream and whose
+ * range ends at the stream's length rounded up to 16 (win_open, csrc/kernels_common.h: a 16-byte request that straddles the
+ * range is dropped as a whole) — the gathers' prologues open the same window (ring_init, csrc/kernels_gather.h) — and the one
+ * wavefront that loads words itself tests each against the length (csrc/kernels_single.h); histograms and block headers are
+ * read only where they end within the length.  So a stream may end next to another stream or at the end of an allocation.
+ * Tasks.  One launch, one workgroup per task: item k's tasks are the chunks of HSRANS_PACK_CHUNK bytes of its up16(length)
+ * bytes, ceil(up16(lengths[k]) / HSRANS_PACK_CHUNK).  hsrans_pack_tasks writes their exclusive prefix and total to
+ * first_task[0 .. count] (may be NULL) and returns the total; 0 under the layout's conditions and for a total of 2^31 or more
+ * (one launch's limit).  The entry refuses by these same two functions.
+ * hsrans_pack_device: for every k the bytes [d_srcs[k], + lengths[k]) land at (uint8_t *)d_arena + offsets[k], and the bytes
+ * from there up to up16(lengths[k]) are written as zero: an arena is a pure function of its items' bytes and can be compared
+ * or hashed.  No byte at or behind d_srcs[k] + lengths[k] is read; no byte of the arena outside [0, offsets[count]) is
+ * written.  A caller who packs in several calls — one chunk of a checkpoint at a time — passes d_arena + its running offset.
+ * Validation before anything is launched or written.  HSRANS_E_ARG: a NULL ctx, array or arena; a layout or task count of 0;
+ * any d_srcs[k] or d_arena NULL or not 16-byte aligned; arena_capacity < offsets[count]; any intersection between
+ * [d_arena, + arena_capacity) and a source [d_srcs[k], + lengths[k]).  Sources may overlap each other (they are only read);
+ * packing in place is not supported.
+ * Synchronisation.  Asynchronous on hip_stream: no synchronisation, and no device allocation beyond what the context's task
+ * buffer does.  The item table goes up through a region of that buffer in one copy, as hsrans_decode_device_planes_batch
+ * sends its member table: the arrays are read before the call returns, and the call is ordered with the context's gathers.
+ * HSRANS_E_HIP: the runtime refused the upload or the launch; nothing was written.
+ *
+ * Frames.  hsrans_planes_pack_layout: out_descs[k] is descs[k] with offset[p] = the sum of up16(length[q]) over q < p (member-
+ * relative, the planes in order) and frame_length = offset[W - 1] + length[W - 1]; bases[0] = 0 and bases[k + 1] = bases[k] +
+ * the sum of up16(length[p]) over member k's planes.  Member k's packed frame is (uint8_t *)d_arena + bases[k] — 16-byte
+ * aligned — and has out_descs[k].frame_length bytes; every entry that takes a descriptor and a frame pointer takes
+ * out_descs[k] with that pointer (hsrans_planes_create, hsrans_planes_set_create, both gather creators; the plans are those
+ * of the unpacked frame: a plan knows its stream, not where it lies).  Returns bases[count], the arena's bytes; out_descs and
+ * bases may be NULL, and out_descs may be descs itself.  The layout is idempotent: of its own output it returns the same.
+ * A descriptor is checked by hsrans_planes_create's rules without the plans — elem_size 2, 4 or 8; offsets that are multiples
+ * of 16; lengths that are not 0; ranges [offset, offset + up16(length)) that do not overlap; frame_length not below the last
+ * byte of a plane — and the layout returns 0, with nothing written, for anything else, for a NULL descs, count 0, more than
+ * 65,536 members, or an overflow.  Every descriptor it accepts is a valid source: an encoder's, one the caller compacted, one
+ * that came out of an earlier pack — packing the survivors of one arena into another is this same call.
+ * hsrans_planes_pack_device: the layout, then hsrans_pack_device's launch over all planes of all members, in member and
+ * plane order, plane p of member k read at (uint8_t *)d_frames[k] + descs[k].offset[p]: one launch for the whole set, stored
+ * planes and coded planes alike.  out_descs and bases (may be NULL) get the layout's.  Asynchronous as above.
+ * HSRANS_E_ARG with nothing launched and nothing written, and out_descs zeroed: a NULL ctx, array, arena or out_descs; a
+ * layout or task count of 0; any d_frames[k] or d_arena NULL or not 16-byte aligned; frame_lengths[k] < descs[k].frame_length;
+ * arena_capacity below the layout's; any intersection of [d_arena, + arena_capacity) with a frame [d_frames[k], +
+ * frame_lengths[k]).  out_descs is zeroed on HSRANS_E_HIP too.
+ * Limits: 524,288 items, 65,536 members, fewer than 2^31 tasks per launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define HSRANS_PACK_CHUNK 8192 /* bytes one workgroup moves */
+size_t hsrans_pack_layout(const size_t *lengths, uint32_t count, uint64_t *offsets /* [count + 1] or NULL */);
+size_t hsrans_pack_tasks(const size_t *lengths, uint32_t count, uint32_t *first_task /* [count + 1] or NULL */);
+int hsrans_pack_device(hsrans_ctx *ctx, const void *const *d_srcs, const size_t *lengths, uint32_t count, void *d_arena, size_t arena_capacity, void *hip_stream);
+size_t hsrans_planes_pack_layout(const hsrans_planes_desc *descs, uint32_t count, hsrans_planes_desc *out_descs /* [count] or NULL */,
+                                 uint64_t *bases /* [count + 1] or NULL */);
+int hsrans_planes_pack_device(hsrans_ctx *ctx, const hsrans_planes_desc *descs, const void *const *d_frames, const size_t *frame_lengths, uint32_t count,
+                              void *d_arena, size_t arena_capacity, void *hip_stream, hsrans_planes_desc *out_descs /* [count] */,
+                              uint64_t *bases /* [count + 1] or NULL */);
+/* ------------------------------------------------------------------------------------------------------------
  * Element ranges of a frame that stays compressed in device memory — embedding rows, one expert's slice, pages of a cache.
  * For every r < count the elements [ranges[r].offset, + ranges[r].length) of the tensor land at
  * (uint8_t *)d_out + ranges[r].dst_offset * elem_size; no other byte of d_out is written.  All three fields of hsrans_range

@@ -333,6 +333,15 @@ SIGNATURES = {
     "hsrans_decode_device_planes_gather_batch_indirect": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsrans_planes_gather_set_refused": (_i, [_vp, _vp, _vp]),
     "hsrans_planes_gather_set_indirect_info": (_i, [_vp, _u32, _sz, _sz, _P(PlanesGatherSetIndirectInfo)]),
+    "hsrans_planes_split_delta": (_i, [_u32, _vp, _vp, _sz, _vp]),
+    "hsrans_planes_merge_delta": (_i, [_u32, _vp, _vp, _sz, _vp]),
+    "hsrans_planes_split_delta_device": (_i, [_vp, _u32, _vp, _vp, _sz, _vp, _vp]),
+    "hsrans_planes_merge_delta_device": (_i, [_vp, _u32, _vp, _vp, _sz, _vp, _vp]),
+    "hsrans_encode_device_planes_delta": (_sz, [_vp, _u32, _i, _u32, _vp, _vp, _sz, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _P(PlanesDesc), _P(_vp)]),
+    "hsrans_decode_device_planes_delta": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_encode_device_planes_delta_batch": (_i, [_vp, _P(PlanesMember), _vp, _vp, _u32, _vp, _sz, _vp, _P(_vp), _P(PlanesBatchStats)]),
+    "hsrans_decode_device_planes_delta_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hsrans_decode_device_planes_gather_delta": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsrans_index_build": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz]),
     "hsrans_index_build_at": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]),
     "hsrans_hpipe_create": (_i, [_vp, _vp, _sz, _u32, _P(_vp)]),

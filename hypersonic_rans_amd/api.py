@@ -545,6 +545,41 @@ def planes_merge(planes, itemsize: int) -> np.ndarray:
     return out
 
 
+def planes_split_delta(array, base) -> list:
+    """hsrans_planes_split_delta on the host: the byte planes of ``array ^ base`` (two contiguous arrays of the same item size and
+    count, XORed byte by byte), as ``planes_split`` gives them."""
+    a, b = np.ascontiguousarray(array), np.ascontiguousarray(base)
+    if a.itemsize != b.itemsize or a.size != b.size:
+        raise HsransError("planes_split_delta: the base has the array's item size and count", code=2)
+    planes = [np.empty(a.size, np.uint8) for _ in range(a.itemsize)]
+    ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
+    _check(load_library().hsrans_planes_split_delta(a.itemsize, a.ctypes.data if a.size else ptrs, b.ctypes.data if b.size else ptrs, a.size, ptrs),
+           "hsrans_planes_split_delta")
+    return planes
+
+
+def planes_merge_delta(planes, base) -> np.ndarray:
+    """hsrans_planes_merge_delta on the host: the planes interleaved back into items' bytes and XORed with ``base``'s (a contiguous
+    array of ``len(planes)``-byte items, as many as a plane has bytes): uint8."""
+    planes, b = [_u8(p) for p in planes], np.ascontiguousarray(base)
+    if len(planes) != b.itemsize or any(p.size != b.size for p in planes):
+        raise HsransError("planes_merge_delta: one plane per byte of the base's items, each of the base's item count", code=2)
+    out = np.empty(b.size * b.itemsize, np.uint8)
+    ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
+    _check(load_library().hsrans_planes_merge_delta(b.itemsize, ptrs, b.ctypes.data if b.size else ptrs, b.size, out.ctypes.data if out.size else ptrs),
+           "hsrans_planes_merge_delta")
+    return out
+
+
+def _base_of(entry: str, base, tensor, optional: bool = False):
+    """(pointer, bytes) of a delta call's base: a contiguous CUDA tensor of ``tensor``'s element size and element count"""
+    if base is None and optional:
+        return None, 0
+    if not (isinstance(base, torch.Tensor) and base.is_cuda and base.is_contiguous() and base.element_size() == tensor.element_size() and base.numel() == tensor.numel()):
+        raise HsransError(f"{entry}: a base is a contiguous CUDA tensor of the tensor's element size and element count", code=2)
+    return base.data_ptr(), base.numel() * base.element_size()
+
+
 def planes_gather_workspace_bytes(itemsize: int, count: int, total_elements: int) -> int:
     """hsrans_planes_gather_workspace_bytes: a workspace that takes every decode_device_planes_gather of ``count`` ranges with
     ``total_elements`` elements in all: itemsize * up256(total_elements + 30 * count) (0: an item size that is not 2, 4 or 8)."""
@@ -1312,16 +1347,21 @@ class Context(_Handle):
         """hsrans_encode_device_planes: a contiguous CUDA tensor whose ``element_size()`` is 2, 4 or 8, taken as bytes, into a frame of
         byte planes at ``d_frame`` (``planes_capacity`` bytes; ``d_work``: ``planes_workspace_bytes``).  Returns ``(frame_length, desc,
         plans)``: ``desc`` a PlanesDesc, ``plans`` a DevicePlan per plane (None for a stored plane; all None without ``want_plans``)."""
+        return self._encode_planes("encode_device_planes", tensor, None, d_frame, d_work, states, bits, block_size, index_interval, store_incompressible, want_plans, stream)
+
+    def _encode_planes(self, entry, tensor, based, d_frame, d_work, states, bits, block_size, index_interval, store_incompressible, want_plans, stream):
+        """encode_device_planes (``based`` None) and encode_device_planes_delta (the base's pointer and bytes): one tensor into its frame"""
         if not tensor.is_contiguous():
-            raise HsransError("encode_device_planes takes a contiguous tensor")
+            raise HsransError(f"{entry} takes a contiguous tensor")
         W = tensor.element_size()
         desc = PlanesDesc()
         handles = (_vp * PLANES_MAX)()
-        n = self.L.hsrans_encode_device_planes(self.handle, W, states, bits, tensor.data_ptr(), tensor.numel(), d_frame.data_ptr(), d_frame.numel(), block_size,
-                                               index_interval, PLANES_STORE_INCOMPRESSIBLE if store_incompressible else 0, d_work.data_ptr(), d_work.numel(),
-                                               _stream(stream, tensor.device), ctypes.byref(desc), handles if want_plans else None)
+        head = (self.handle, W, states, bits, tensor.data_ptr())
+        tail = (tensor.numel(), d_frame.data_ptr(), d_frame.numel(), block_size, index_interval, PLANES_STORE_INCOMPRESSIBLE if store_incompressible else 0,
+                d_work.data_ptr(), d_work.numel(), _stream(stream, tensor.device), ctypes.byref(desc), handles if want_plans else None)
+        n = self.L.hsrans_encode_device_planes(*head, *tail) if based is None else self.L.hsrans_encode_device_planes_delta(*head, *based, *tail)
         if n == 0:
-            raise HsransError("hsrans_encode_device_planes failed")
+            raise HsransError(f"hsrans_{entry} failed")
         plans = [DevicePlan(self, _vp(handles[p])) if want_plans and handles[p] else None for p in range(W)]
         return n, desc, plans
 
@@ -1358,19 +1398,23 @@ class Context(_Handle):
         ``index_interval`` and ``store_incompressible`` for single members.  Each member gets what ``encode_device_planes`` gives it.
         Returns a list of ``(frame_length, desc, plans)`` as that call's.  ``stats``: filled with hsrans_planes_batch_stats.  Synchronous.
         Raises HsransError naming the first member at fault; the error carries ``code`` and ``rcs``."""
+        return self._encode_planes_batch("encode_device_planes_batch", tensors, None, d_frames, d_work, options, want_plans, stream, stats, states=states, bits=bits,
+                                         block_size=block_size, index_interval=index_interval, store_incompressible=store_incompressible)
+
+    def _encode_planes_batch(self, entry, tensors, bases, d_frames, d_work, options, want_plans, stream, stats, **defaults) -> list:
+        """encode_device_planes_batch (``bases`` None) and encode_device_planes_delta_batch: many tensors into their frames"""
         tensors, d_frames = list(tensors), list(d_frames)
         K = len(tensors)
-        if len(d_frames) != K or (options is not None and len(options) != K):
-            raise HsransError(f"encode_device_planes_batch: one frame (and one options entry) per tensor: {K} tensors")
+        if len(d_frames) != K or (options is not None and len(options) != K) or (bases is not None and len(bases) != K):
+            raise HsransError(f"{entry}: one frame (and one options entry) per tensor: {K} tensors" + ("" if bases is None else ", and one base or None"))
         if any(not t.is_contiguous() for t in tensors):
-            raise HsransError("encode_device_planes_batch takes contiguous tensors")
-        defaults = dict(states=states, bits=bits, block_size=block_size, index_interval=index_interval, store_incompressible=store_incompressible)
+            raise HsransError(f"{entry} takes contiguous tensors")
         arr = (PlanesMember * max(K, 1))()
         for k, t in enumerate(tensors):
             o = dict(options[k]) if options is not None and options[k] is not None else {}
             unknown = set(o) - set(defaults)
             if unknown:
-                raise HsransError(f"encode_device_planes_batch: member {k}: unknown options {sorted(unknown)}")
+                raise HsransError(f"{entry}: member {k}: unknown options {sorted(unknown)}")
             o = dict(defaults, **o)
             e = arr[k]
             e.elem_size, e.states, e.bits, e.block_size, e.index_interval = t.element_size(), o["states"], o["bits"], o["block_size"], o["index_interval"]
@@ -1379,14 +1423,18 @@ class Context(_Handle):
             e.d_frame, e.frame_capacity = d_frames[k].data_ptr(), d_frames[k].numel()
         handles = (_vp * (max(K, 1) * PLANES_MAX))()
         st = PlanesBatchStats()
-        rc = self.L.hsrans_encode_device_planes_batch(self.handle, arr, K, d_work.data_ptr(), d_work.numel(), _stream(stream, d_work.device),
-                                                      handles if want_plans else None, ctypes.byref(st))
+        tail = (K, d_work.data_ptr(), d_work.numel(), _stream(stream, d_work.device), handles if want_plans else None, ctypes.byref(st))
+        if bases is None:
+            rc = self.L.hsrans_encode_device_planes_batch(self.handle, arr, *tail)
+        else:
+            based = [_base_of(entry, b, t, optional=True) for b, t in zip(bases, tensors)]
+            rc = self.L.hsrans_encode_device_planes_delta_batch(self.handle, arr, (_vp * max(K, 1))(*[p for p, _ in based]), (_sz * max(K, 1))(*[n for _, n in based]), *tail)
         if stats is not None:
             stats.update(_as_dict(st))
         if rc != 0:
             rcs = [int(arr[k].rc) for k in range(K)]
             failed = [k for k in range(K) if rcs[k] != 0]
-            raise _members_error("hsrans_encode_device_planes_batch", rc, failed if len(failed) < K else [], rcs=rcs)
+            raise _members_error(f"hsrans_{entry}", rc, failed if len(failed) < K else [], rcs=rcs)
         return [(int(arr[k].frame_length), PlanesDesc.from_buffer_copy(arr[k].desc),
                  [DevicePlan(self, _vp(handles[k * PLANES_MAX + p])) if want_plans and handles[k * PLANES_MAX + p] else None for p in range(arr[k].elem_size)])
                 for k in range(K)]
@@ -1424,6 +1472,88 @@ class Context(_Handle):
         codes = (ctypes.c_int * max(len(pset.descs), 1))()
         self.L.hsrans_planes_set_status(self.handle, pset.handle, _stream(stream), codes)
         return list(codes)[: len(pset.descs)]
+
+    # -- tensors coded against a base: a delta frame is the ordinary frame of tensor ^ base, and does not name its base ----------------
+    def planes_split_delta_device(self, tensor: torch.Tensor, base: torch.Tensor, d_planes, elements: int | None = None, stream: torch.cuda.Stream | None = None):
+        """hsrans_planes_split_delta_device: ``planes_split_device`` of ``tensor ^ base`` (``base``: a contiguous CUDA tensor of the
+        tensor's element size and element count).  Asynchronous on ``stream``."""
+        W = tensor.element_size()
+        _check(self.L.hsrans_planes_split_delta_device(self.handle, W, tensor.data_ptr(), _base_of("planes_split_delta_device", base, tensor)[0],
+                                                       tensor.numel() if elements is None else elements, self._plane_ptrs(d_planes, W), _stream(stream, tensor.device)),
+               "hsrans_planes_split_delta_device")
+
+    def planes_merge_delta_device(self, d_planes, base: torch.Tensor, out_tensor: torch.Tensor, elements: int | None = None, stream: torch.cuda.Stream | None = None):
+        """hsrans_planes_merge_delta_device: ``d_planes`` interleaved and XORed with ``base`` into ``out_tensor``, which may be ``base``
+        itself (the delta applied in place).  Asynchronous on ``stream``."""
+        W = out_tensor.element_size()
+        _check(self.L.hsrans_planes_merge_delta_device(self.handle, W, self._plane_ptrs(d_planes, W), _base_of("planes_merge_delta_device", base, out_tensor)[0],
+                                                       out_tensor.numel() if elements is None else elements, out_tensor.data_ptr(), _stream(stream, out_tensor.device)),
+               "hsrans_planes_merge_delta_device")
+
+    def encode_device_planes_delta(self, tensor: torch.Tensor, base: torch.Tensor, d_frame: torch.Tensor, d_work: torch.Tensor, states: int = 64, bits: int = 11,
+                                   block_size: int = 1 << 16, index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True,
+                                   stream: torch.cuda.Stream | None = None):
+        """hsrans_encode_device_planes_delta: ``encode_device_planes`` of ``tensor ^ base`` without the buffer that holds it — byte for
+        byte the same frame, descriptor and plans.  The frame does not name its base: decode it with the same base
+        (``decode_device_planes_delta``); ``decode_device_planes`` gives ``tensor ^ base``.  Returns ``(frame_length, desc, plans)``."""
+        return self._encode_planes("encode_device_planes_delta", tensor, _base_of("encode_device_planes_delta", base, tensor), d_frame, d_work, states, bits, block_size,
+                                   index_interval, store_incompressible, want_plans, stream)
+
+    def decode_device_planes_delta(self, planes: Planes, d_frame: torch.Tensor, base: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                   stream: torch.cuda.Stream | None = None, frame_length: int | None = None):
+        """hsrans_decode_device_planes_delta: the frame at ``d_frame``, XORed with ``base``, into ``out_tensor`` — which may be ``base``
+        itself: the delta is then applied in place.  Launches and workspace as ``decode_device_planes``.  Asynchronous on ``stream``."""
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes_delta takes a contiguous output tensor")
+        _check(self.L.hsrans_decode_device_planes_delta(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
+                                                        *_base_of("decode_device_planes_delta", base, out_tensor), out_tensor.data_ptr(),
+                                                        out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(), _stream(stream, d_frame.device)),
+               "hsrans_decode_device_planes_delta")
+
+    def encode_device_planes_delta_batch(self, tensors, bases, d_frames, d_work: torch.Tensor, states: int = 64, bits: int = 11, block_size: int = 1 << 16,
+                                         index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True, options=None,
+                                         stream: torch.cuda.Stream | None = None, stats: dict | None = None) -> list:
+        """hsrans_encode_device_planes_delta_batch: ``encode_device_planes_batch`` with member k coded against ``bases[k]``, or as it is
+        where ``bases[k]`` is None; one base may serve many members.  Each member gets what ``encode_device_planes_delta`` (None:
+        ``encode_device_planes``) gives it.  Returns, fills ``stats`` and raises as that call."""
+        return self._encode_planes_batch("encode_device_planes_delta_batch", tensors, list(bases), d_frames, d_work, options, want_plans, stream, stats, states=states,
+                                         bits=bits, block_size=block_size, index_interval=index_interval, store_incompressible=store_incompressible)
+
+    def decode_device_planes_delta_batch(self, pset: PlanesSet, d_frames, bases, out_tensors, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """hsrans_decode_device_planes_delta_batch: ``decode_device_planes_batch`` with member k XORed with ``bases[k]`` (None: as it
+        is); ``out_tensors[k]`` may be ``bases[k]`` itself.  Asynchronous on ``stream`` (default: torch's current stream)."""
+        d_frames, bases, out_tensors = list(d_frames), list(bases), list(out_tensors)
+        K = len(pset.descs)
+        if len(d_frames) != K or len(out_tensors) != K or len(bases) != K:
+            raise HsransError(f"decode_device_planes_delta_batch: one frame, one base (or None) and one output per member: {K}")
+        if any(not t.is_contiguous() for t in out_tensors):
+            raise HsransError("decode_device_planes_delta_batch takes contiguous output tensors")
+        frames, frame_lengths = _tensor_arrays(d_frames)
+        outs, out_caps = _tensor_arrays(out_tensors, [t.numel() * t.element_size() for t in out_tensors])
+        based = [_base_of("decode_device_planes_delta_batch", b, t, optional=True) for b, t in zip(bases, out_tensors)]
+        _check(self.L.hsrans_decode_device_planes_delta_batch(self.handle, pset.handle, frames, frame_lengths, (_vp * K)(*[p for p, _ in based]),
+                                                              (_sz * K)(*[n for _, n in based]), outs, out_caps, d_work.data_ptr(), d_work.numel(),
+                                                              _stream(stream, d_work.device)), "hsrans_decode_device_planes_delta_batch")
+
+    def decode_device_planes_gather_delta(self, pg: PlanesGather, ranges, base: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                          stream: torch.cuda.Stream | None = None):
+        """hsrans_decode_device_planes_gather_delta: ``decode_device_planes_gather`` of a delta frame — element ``offset + i`` of the
+        frame XORed with element ``offset + i`` of ``base``, the WHOLE base tensor (the frame's element size and element count), which may
+        not share memory with ``out_tensor`` or ``d_work``.  Asynchronous on ``stream``; ``ranges`` is read before the call returns."""
+        desc = pg.planes.desc
+        if not out_tensor.is_contiguous():
+            raise HsransError("decode_device_planes_gather_delta takes a contiguous output tensor")
+        if out_tensor.element_size() != desc.elem_size:
+            raise HsransError(f"decode_device_planes_gather_delta: the frame's elements are {desc.elem_size} bytes, the output tensor's {out_tensor.element_size()}")
+        if d_work.dtype != torch.uint8:
+            raise HsransError("decode_device_planes_gather_delta takes a uint8 workspace tensor")
+        if not (isinstance(base, torch.Tensor) and base.is_cuda and base.is_contiguous() and base.element_size() == desc.elem_size and base.numel() == desc.elements):
+            raise HsransError("decode_device_planes_gather_delta: the base is a contiguous CUDA tensor of the frame's element size and element count", code=2)
+        arr = _ranges_array(ranges)
+        _check(self.L.hsrans_decode_device_planes_gather_delta(self.handle, pg.handle, _p(arr) if arr.size else None, arr.shape[0], base.data_ptr(),
+                                                               base.numel() * base.element_size(), out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(),
+                                                               d_work.data_ptr(), d_work.numel(), _stream(stream, out_tensor.device)),
+               "hsrans_decode_device_planes_gather_delta")
 
     def pack_device(self, srcs, lengths, arena: torch.Tensor, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_pack_device: the first ``lengths[k]`` bytes of the CUDA uint8 tensors ``srcs[k]`` (``lengths`` None: all of each) side by

@@ -3,6 +3,8 @@
 // of the planes as mt_ members and, where asked for, a copy over the planes that did not shrink; hsrans_decode_device_planes is
 // hsrans_decode_device_batch of the coded planes and one merge launch behind it.  Both codecs are used as they are, through their public
 // entries: a coded plane is byte for byte what hsrans_encode_device(HSRANS_MT, ...) writes for the plane's bytes.
+// The two entries' bodies are planes_encode_flow and planes_decode_flow (hsrans_internal.h), which take an optional base: without one they are
+// the entries as they always were; with one the split or the merge is the delta kernel (hsrans_capi_planes_delta.cpp calls them so).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -172,9 +174,30 @@ catch (...)
   return HSRANS_E_HIP;
 }
 
-extern "C" size_t hsrans_encode_device_planes(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, size_t elements, void *d_frame,
-                                              size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags, void *d_work, size_t work_bytes,
-                                              void *hip_stream, hsrans_planes_desc *desc, hsrans_dplan **out_dplans)
+bool planes_base_spans(const PlanesBase &base, uint32_t W, size_t elements, const void *d_out, size_t out_capacity, std::vector<Span> *spans)
+{
+  if (!base.on)
+    return true;
+  if (!aligned16(base.d) || base.bytes < elements * W || wraps(base.d, base.bytes))
+    return false;
+  if (d_out != nullptr && base.d == d_out && out_capacity <= base.bytes) // in place: the output's span stands for the base's bytes it covers
+    spans->push_back(span_of((const uint8_t *)base.d + out_capacity, base.bytes - out_capacity, false));
+  else
+    spans->push_back(span_of(base.d, base.bytes, false));
+  return true;
+}
+
+bool planes_base_meets_frame(const PlanesBase &base, const void *d_frame, size_t frame_length)
+{
+  if (!base.on)
+    return false;
+  std::vector<Span> frames{span_of(d_frame, frame_length, false)};
+  return spans_meet({span_of(base.d, base.bytes, false)}, frames);
+}
+
+size_t planes_encode_flow(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, const PlanesBase &base, size_t elements, void *d_frame,
+                          size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags, void *d_work, size_t work_bytes, void *hip_stream,
+                          hsrans_planes_desc *desc, hsrans_dplan **out_dplans)
 try
 {
   if (desc != nullptr)
@@ -204,13 +227,14 @@ try
     return 0;
   {
     std::vector<Span> spans{span_of(d_in, elements * W, false), span_of(d_frame, frame_capacity, true), span_of(d_work, work_bytes, true)};
-    if (!spans_disjoint(spans))
+    if (!planes_base_spans(base, W, elements, nullptr, 0, &spans) || !spans_disjoint(spans))
       return 0;
   }
 
   hipStream_t s = (hipStream_t)hip_stream;
   const PlanePtrs pp = work_planes(W, d_work, elements);
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(W, d_in, elements, pp, s) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess ||
+      (base.on ? launch_planes_split_delta(W, d_in, base.d, elements, pp, s) : launch_planes_split(W, d_in, elements, pp, s)) != hipSuccess)
   {
     (void)hipGetLastError();
     return 0;
@@ -281,6 +305,14 @@ catch (...) // (thrown only after the caller's arrays were reset, or before elem
   return 0;
 }
 
+extern "C" size_t hsrans_encode_device_planes(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, size_t elements, void *d_frame,
+                                              size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags, void *d_work, size_t work_bytes,
+                                              void *hip_stream, hsrans_planes_desc *desc, hsrans_dplan **out_dplans)
+{
+  return planes_encode_flow(ctx, elem_size, states, bits, d_in, PlanesBase{}, elements, d_frame, frame_capacity, block_size, index_interval, flags, d_work, work_bytes,
+                            hip_stream, desc, out_dplans);
+}
+
 extern "C" void hsrans_planes_destroy(hsrans_planes *planes)
 {
   if (planes == nullptr)
@@ -336,8 +368,8 @@ catch (...)
   return HSRANS_E_HIP;
 }
 
-extern "C" int hsrans_decode_device_planes(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, void *d_out, size_t out_capacity,
-                                           void *d_work, size_t work_bytes, void *hip_stream)
+int planes_decode_flow(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const PlanesBase &base, void *d_out, size_t out_capacity,
+                       void *d_work, size_t work_bytes, void *hip_stream)
 try
 {
   if (ctx == nullptr || planes == nullptr || planes->ctx != ctx || !aligned16(d_frame) || !aligned16(d_out) || !aligned16(d_work))
@@ -349,7 +381,7 @@ try
     return HSRANS_E_ARG;
   {
     std::vector<Span> spans{span_of(d_frame, frame_length, false), span_of(d_out, out_capacity, true), span_of(d_work, work_bytes, true)};
-    if (!spans_disjoint(spans))
+    if (!planes_base_spans(base, W, elements, d_out, out_capacity, &spans) || !spans_disjoint(spans) || planes_base_meets_frame(base, d_frame, frame_length))
       return HSRANS_E_ARG;
   }
   // the merge's sources: a coded plane decoded into the workspace, a stored one where it lies in the frame
@@ -374,7 +406,9 @@ try
     if (rc != HSRANS_OK)
       return rc;
   }
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(W, src, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (hipSetDevice(ctx->device) != hipSuccess ||
+      (base.on ? launch_planes_merge_delta(W, src, base.d, elements, d_out, s) : launch_planes_merge(W, src, elements, d_out, s)) != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -384,6 +418,12 @@ try
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, void *d_out, size_t out_capacity,
+                                           void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_decode_flow(ctx, planes, d_frame, frame_length, PlanesBase{}, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_status(hsrans_ctx *ctx, hsrans_planes *planes, void *hip_stream, int *plane_status)

@@ -4,6 +4,8 @@
 // its public entry, one k_planes_store_batch launch over the planes that did not shrink — and the decode set: ONE hsrans_batch over all coded
 // planes, hsrans_decode_device_batch through its public entry and one k_planes_merge_batch launch behind it (hsrans_planes_batch.hip).  The
 // kernels' member tables go through the context's task buffers as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
+// The two entries' bodies are planes_encode_batch_flow and planes_decode_batch_flow (hsrans_internal.h), which hsrans_capi_planes_delta.cpp
+// runs with a base (or none) per member: then the split and the merge are the delta kernels over the same table with the bases beside it.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -28,20 +30,29 @@ size_t region_bytes(uint32_t W, size_t elements) { return hsrans_planes_workspac
 
 // Uploads `table` through a region of the context's task buffers and launches `launch(device table)` behind it on `s`, under ctx->lock:
 // the gathers' protocol (gather_region_upload).
-template <typename Launch>
-int launch_with_table(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &table, hipStream_t s, Launch &&launch)
+template <typename Record, typename Launch>
+int launch_with_table(hsrans_ctx *ctx, const std::vector<Record> &table, hipStream_t s, Launch &&launch)
 {
   std::lock_guard<std::mutex> lk(ctx->lock);
   if (hipSetDevice(ctx->device) != hipSuccess)
     return HSRANS_E_HIP;
-  const size_t bytes = table.size() * sizeof(PlanesBatchMember);
+  const size_t bytes = table.size() * sizeof(Record);
   return gather_region_upload(
       ctx, bytes, s,
       [&](uint8_t *host) {
         memcpy(host, table.data(), bytes);
         return HSRANS_OK;
       },
-      [&](const uint8_t *dev) { return launch((const PlanesBatchMember *)dev); });
+      [&](const uint8_t *dev) { return launch((const Record *)dev); });
+}
+
+// the delta kernels' table: the plain records with every member's base (null: none)
+std::vector<PlanesDeltaBatchMember> with_bases(const std::vector<PlanesBatchMember> &table, const void *const *d_bases)
+{
+  std::vector<PlanesDeltaBatchMember> out(table.size());
+  for (size_t k = 0; k < table.size(); k++)
+    out[k] = PlanesDeltaBatchMember{table[k], (const uint8_t *)d_bases[k]};
+  return out;
 }
 
 // every output of a failed encode: no frame, no descriptor, no plan (one already made is destroyed)
@@ -106,8 +117,8 @@ extern "C" size_t hsrans_planes_batch_tasks(const size_t *elements, uint32_t cou
   return (size_t)total;
 }
 
-extern "C" int hsrans_encode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_member *members, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
-                                                 hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
+int planes_encode_batch_flow(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes, bool delta, uint32_t count,
+                             void *d_work, size_t work_bytes, void *hip_stream, hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
 try
 {
   if (stats != nullptr)
@@ -117,7 +128,7 @@ try
   for (size_t j = 0; out_dplans != nullptr && j < (size_t)count * HSRANS_PLANES_MAX; j++)
     out_dplans[j] = nullptr; // (the caller's array may hold anything: nothing to destroy yet)
   fail_encode(members, count, out_dplans, HSRANS_OK);
-  if (ctx == nullptr)
+  if (ctx == nullptr || (delta && (d_bases == nullptr || base_bytes == nullptr)))
     return HSRANS_E_ARG;
 
   // ---- everything checked before anything is launched: each member by its single call's rules, then the call's own ----
@@ -155,6 +166,11 @@ try
     {
       spans.push_back(span_of(members[k].d_in, members[k].elements * members[k].elem_size, false));
       spans.push_back(span_of(members[k].d_frame, members[k].frame_capacity, true));
+      if (delta && d_bases[k] != nullptr && !planes_base_spans(PlanesBase{true, d_bases[k], base_bytes[k]}, members[k].elem_size, members[k].elements, nullptr, 0, &spans))
+      {
+        members[k].rc = HSRANS_E_ARG;
+        return HSRANS_E_ARG;
+      }
     }
     if (!spans_disjoint(spans))
       return HSRANS_E_ARG;
@@ -173,7 +189,9 @@ try
     t.W = members[k].elem_size;
     t.first_task = first_task[k];
   }
-  int rc = launch_with_table(ctx, table, s, [&](const PlanesBatchMember *d) { return launch_planes_split_batch(d, count, (uint32_t)n_tasks, s); });
+  int rc = delta ? launch_with_table(ctx, with_bases(table, d_bases), s,
+                                     [&](const PlanesDeltaBatchMember *d) { return launch_planes_split_delta_batch(d, count, (uint32_t)n_tasks, s); })
+                 : launch_with_table(ctx, table, s, [&](const PlanesBatchMember *d) { return launch_planes_split_batch(d, count, (uint32_t)n_tasks, s); });
   if (rc != HSRANS_OK)
   {
     fail_encode(members, count, out_dplans, rc);
@@ -290,6 +308,12 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI; 
   return HSRANS_E_HIP;
 }
 
+extern "C" int hsrans_encode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_member *members, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
+                                                 hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
+{
+  return planes_encode_batch_flow(ctx, members, nullptr, nullptr, false, count, d_work, work_bytes, hip_stream, out_dplans, stats);
+}
+
 extern "C" void hsrans_planes_set_destroy(hsrans_planes_set *set)
 {
   if (set == nullptr)
@@ -384,17 +408,17 @@ extern "C" int hsrans_planes_set_info(const hsrans_planes_set *set, hsrans_plane
   return HSRANS_OK;
 }
 
-extern "C" int hsrans_decode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, void *const *d_outs,
-                                                 const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
+int planes_decode_batch_flow(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, const void *const *d_bases,
+                             const size_t *base_bytes, bool delta, void *const *d_outs, const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
 try
 {
-  if (ctx == nullptr || set == nullptr || set->ctx != ctx || d_frames == nullptr || frame_lengths == nullptr || d_outs == nullptr || out_capacities == nullptr ||
+  if (ctx == nullptr || (delta && (d_bases == nullptr || base_bytes == nullptr)) || set == nullptr || set->ctx != ctx || d_frames == nullptr || frame_lengths == nullptr || d_outs == nullptr || out_capacities == nullptr ||
       !aligned16(d_work) || wraps(d_work, work_bytes) || work_bytes < set->work_at.back())
     return HSRANS_E_ARG;
   const uint32_t count = (uint32_t)set->descs.size();
 
   // ---- everything checked before anything is launched or uploaded ----
-  std::vector<Span> spans;
+  std::vector<Span> spans, frame_spans, base_spans; // (the last two: a base keeps clear of every member's frame, reads though both are)
   spans.reserve(2 * (size_t)count + 1);
   spans.push_back(span_of(d_work, work_bytes, true));
   for (uint32_t k = 0; k < count; k++)
@@ -405,8 +429,15 @@ try
       return HSRANS_E_ARG;
     spans.push_back(span_of(d_frames[k], frame_lengths[k], false));
     spans.push_back(span_of(d_outs[k], out_capacities[k], true));
+    if (delta && d_bases[k] != nullptr &&
+        !planes_base_spans(PlanesBase{true, d_bases[k], base_bytes[k]}, desc.elem_size, (size_t)desc.elements, d_outs[k], out_capacities[k], &spans))
+      return HSRANS_E_ARG;
+    if (delta)
+      frame_spans.push_back(span_of(d_frames[k], frame_lengths[k], false));
+    if (delta && d_bases[k] != nullptr)
+      base_spans.push_back(span_of(d_bases[k], base_bytes[k], false));
   }
-  if (!spans_disjoint(spans))
+  if (!spans_disjoint(spans) || spans_meet(base_spans, frame_spans))
     return HSRANS_E_ARG;
 
   // ---- the merge's sources: a coded plane decoded into its member's region of the workspace, a stored one where it lies in its frame ----
@@ -441,11 +472,20 @@ try
       return rc;
   }
   hipStream_t s = (hipStream_t)hip_stream;
+  if (delta)
+    return launch_with_table(ctx, with_bases(table, d_bases), s,
+                             [&](const PlanesDeltaBatchMember *d) { return launch_planes_merge_delta_batch(d, count, set->first_task.back(), s); });
   return launch_with_table(ctx, table, s, [&](const PlanesBatchMember *d) { return launch_planes_merge_batch(d, count, set->first_task.back(), s); });
 }
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, void *const *d_outs,
+                                                 const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, nullptr, nullptr, false, d_outs, out_capacities, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_set_status(hsrans_ctx *ctx, hsrans_planes_set *set, void *hip_stream, int *member_status)

@@ -2,7 +2,8 @@
 // gather object (a hsrans_planes bound to its frame, ONE hsrans_gather_set over the coded planes), the workspace layout and the host-side cut
 // of the merge (hsrans_planes_gather_tasks, a pure function), the argument checks, and the call: hsrans_decode_device_gather_batch of the coded
 // planes' bytes into the workspace through its public entry, then one k_planes_merge_ranges launch (hsrans_planes_gather.hip) whose task list
-// goes through the context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
+// goes through the context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).  The call's body is
+// planes_gather_flow (hsrans_internal.h), which hsrans_capi_planes_delta.cpp runs with a base: then the merge is k_planes_merge_ranges_delta.
 // hsrans_decode_device_planes_gather_indirect, at the end of the file: the same for ranges in device memory — the device cuts
 // (hsrans_planes_gather_indirect.hip), by the rules of planes_cut.h that the host's cut above uses too.
 #include <hip/hip_runtime.h>
@@ -173,8 +174,8 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
   return HSRANS_E_HIP;
 }
 
-extern "C" int hsrans_decode_device_planes_gather(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, void *d_out, size_t out_capacity,
-                                                  void *d_work, size_t work_bytes, void *hip_stream)
+int planes_gather_flow(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const PlanesBase &base, void *d_out, size_t out_capacity,
+                       void *d_work, size_t work_bytes, void *hip_stream)
 try
 {
   if (ctx == nullptr || pg == nullptr || pg->ctx != ctx || !aligned16(d_out) || !aligned16(d_work) || (ranges == nullptr && count > 0))
@@ -198,7 +199,8 @@ try
     return HSRANS_E_ARG;
   {
     std::vector<Span> spans{span_of(pg->d_frame, pg->frame_length, false), span_of(d_out, out_capacity, true), span_of(d_work, work_bytes, true)};
-    if (!spans_disjoint(spans))
+    if (!planes_base_spans(base, W, (size_t)desc.elements, nullptr, 0, &spans) || !spans_disjoint(spans) ||
+        planes_base_meets_frame(base, pg->d_frame, pg->frame_length))
       return HSRANS_E_ARG;
   }
   {
@@ -245,7 +247,10 @@ try
         cut_ranges(ranges, count, [&](const hsrans_planes_gather_task &t) { *list++ = t; });
         return HSRANS_OK;
       },
-      [&](const uint8_t *dev) { return launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, d_out, s); });
+      [&](const uint8_t *dev) {
+        return base.on ? launch_planes_merge_ranges_delta(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, base.d, d_out, s)
+                       : launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, d_out, s);
+      });
   if (rc != HSRANS_OK)
     return rc;
   pg->last.rows = count * coded;
@@ -256,6 +261,12 @@ try
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, void *d_out, size_t out_capacity,
+                                                  void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_gather_flow(ctx, pg, ranges, count, PlanesBase{}, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_gather_status(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream, int *plane_status)

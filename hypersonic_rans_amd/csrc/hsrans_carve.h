@@ -58,4 +58,25 @@ inline bool spans_disjoint(std::vector<Span> &spans)
   return true;
 }
 
+// Whether a span of `a` intersects a span of `b`, whatever either reads or writes (empty spans meet nothing): for two groups that the rule
+// above would let share, both being reads, and that still must stay apart.  One sort of b by start with the furthest end so far beside it,
+// then for every span of a a binary search for the spans of b that begin below its end; b comes back sorted.
+inline bool spans_meet(const std::vector<Span> &a, std::vector<Span> &b)
+{
+  std::sort(b.begin(), b.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
+  std::vector<uintptr_t> reach(b.size()); // the furthest end among b[0 .. k]'s non-empty spans
+  uintptr_t hi = 0;
+  for (size_t k = 0; k < b.size(); k++)
+    reach[k] = hi = b[k].lo < b[k].hi ? std::max(hi, b[k].hi) : hi;
+  for (const Span &sp : a)
+  {
+    if (sp.lo >= sp.hi)
+      continue;
+    const size_t below = std::lower_bound(b.begin(), b.end(), sp.hi, [](const Span &x, uintptr_t end) { return x.lo < end; }) - b.begin();
+    if (below != 0 && reach[below - 1] > sp.lo)
+      return true;
+  }
+  return false;
+}
+
 #endif // HSRANS_CARVE_H

@@ -306,6 +306,43 @@ bool planes_encode_check(uint32_t W, int states, uint32_t bits, const void *d_in
 // hsrans_planes_create's rules for a descriptor and its planes' plans (dplans[p] null exactly for the stored planes): HSRANS_OK or HSRANS_E_ARG
 int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans);
 
+// ---- what the plain byte-plane entries and their delta forms (hsrans_capi_planes_delta.cpp) share: each plain entry's whole body, taking an
+// optional base.  Without one (`on` false) a flow is the plain entry, check for check and launch for launch; with one the split or the merge
+// is the delta kernel (hsrans_planes_delta.hip) and the base joins the checks.  Hidden: the library's exported symbols are the header's. ----
+struct PlanesBase
+{
+  bool on = false; // a delta call (a plain one never looks at the rest)
+  const void *d = nullptr;
+  size_t bytes = 0;
+};
+// The base's own checks and its part in the overlap rule: set, 16-byte aligned, at least W * elements bytes (false otherwise); a read span,
+// pushed onto *spans.  d_out (null: the call has no in-place form): where the output is exactly the base — the same address, out_capacity
+// within the base's bytes — the output's span stands for those bytes and only the base's remainder behind it is pushed.
+__attribute__((visibility("hidden"))) bool planes_base_spans(const PlanesBase &base, uint32_t W, size_t elements, const void *d_out, size_t out_capacity,
+                                                             std::vector<Span> *spans);
+// A decode reads its frame, and by the overlap rule two reads may share; a base may still not meet the frame it is decoded against (a base
+// over compressed bytes is never a meaningful call): whether base.d over base.bytes intersects the frame.  False without a base.
+__attribute__((visibility("hidden"))) bool planes_base_meets_frame(const PlanesBase &base, const void *d_frame, size_t frame_length);
+// hsrans_encode_device_planes, hsrans_decode_device_planes (hsrans_capi_planes.cpp)
+__attribute__((visibility("hidden"))) size_t planes_encode_flow(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, const PlanesBase &base,
+                                                                size_t elements, void *d_frame, size_t frame_capacity, uint32_t block_size, uint32_t index_interval,
+                                                                uint32_t flags, void *d_work, size_t work_bytes, void *hip_stream, hsrans_planes_desc *desc,
+                                                                hsrans_dplan **out_dplans);
+__attribute__((visibility("hidden"))) int planes_decode_flow(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const PlanesBase &base,
+                                                             void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+// hsrans_encode_device_planes_batch, hsrans_decode_device_planes_batch (hsrans_capi_planes_batch.cpp); delta: d_bases and base_bytes are
+// arrays of one entry per member, a null d_bases[k] a member without a base
+__attribute__((visibility("hidden"))) int planes_encode_batch_flow(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes,
+                                                                   bool delta, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
+                                                                   hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats);
+__attribute__((visibility("hidden"))) int planes_decode_batch_flow(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
+                                                                   const void *const *d_bases, const size_t *base_bytes, bool delta, void *const *d_outs,
+                                                                   const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream);
+// hsrans_decode_device_planes_gather (hsrans_capi_planes_gather.cpp); no in-place form
+struct hsrans_planes_gather;
+__attribute__((visibility("hidden"))) int planes_gather_flow(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const PlanesBase &base,
+                                                             void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+
 // (Re)fills a device plan from a validated host plan blob; one launch of a filled device plan (hsrans_dplan.cpp)
 int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_size, const PlanHeader &h, hipStream_t s);
 int dplan_launch(hsrans_dplan *d, const void *d_stream, size_t stream_length, void *d_out, size_t out_capacity, hipStream_t s, uint64_t stream_lo = 0,

@@ -1,7 +1,8 @@
 // hsrans_planes.h — the streaming kernels of the byte-plane layer: elements of W bytes split into W byte planes and planes interleaved back
 // into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
 // hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip, and with those rows in device memory
-// hsrans_planes_gather_batch_indirect.hip).  plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
+// hsrans_planes_gather_batch_indirect.hip), and the forms of the split and the merges that XOR a base in (hsrans_planes_delta.hip).
+// plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
 
@@ -227,6 +228,23 @@ uint32_t planes_merge_batch_indirect_grid(uint32_t num_cus, uint32_t min_W, uint
 hipError_t launch_planes_cut_batch(const PlanesCutBatchParams &cp, hipStream_t stream);
 hipError_t launch_planes_merge_batch_indirect(const PlanesSetRow *d_ranges, const uint32_t *d_header, const uint32_t *d_first_task, const uint64_t *d_base,
                                               const PlanesGatherBatchMember *d_members, const void *work, void *out, uint32_t grid, hipStream_t stream);
+
+// ---- tensors coded against a base (hsrans_*_device_planes_delta): hsrans_planes_delta.hip.  The planes hold in ^ base; every launcher is
+// its plain counterpart above with the base beside the element buffer: set, 16-byte aligned, as many bytes as the elements ----
+// (the merge's base may be `out` itself: the delta applied in place; any other overlap of the two is the caller's to refuse)
+hipError_t launch_planes_split_delta(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
+hipError_t launch_planes_merge_delta(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream);
+// a PlanesBatchMember and the member's base; null: the member is split or merged as it is
+struct PlanesDeltaBatchMember
+{
+  PlanesBatchMember m;
+  const uint8_t *base;
+};
+hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+// launch_planes_merge_ranges with output element (element + dst_delta) XORed with base element `element`; base: the whole base tensor
+hipError_t launch_planes_merge_ranges_delta(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
+                                            void *out, hipStream_t stream);
 
 } // namespace hsrans
 

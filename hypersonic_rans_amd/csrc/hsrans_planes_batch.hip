@@ -13,42 +13,7 @@ namespace
 {
 using namespace planes_detail;
 
-// a pointer read from a record, the same on every lane
-__device__ __forceinline__ uint8_t *uni_ptr(uint8_t *p) { return global_at(uni64((uint64_t)p)); }
-
-// the member of task t: the last record with first_task <= t (first_task[0] is 0 and t is below the table's total); task_row's search
-// (planes_shuffle.h) over a field of the records
-__device__ __forceinline__ const PlanesBatchMember *member_of(const PlanesBatchMember *__restrict__ members, uint32_t count, uint32_t t)
-{
-  uint32_t lo = 0, hi = count;
-  while (hi - lo > 1)
-  {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (uni(members[mid].first_task) <= t)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return members + lo;
-}
-
-// What one workgroup sees of its member: its index among the member's workgroups, whether it is the last of them, and the lane's 16 elements
-struct Task
-{
-  uint64_t n, whole, lane;
-  bool last;
-};
-__device__ __forceinline__ Task task_of(const PlanesBatchMember *m)
-{
-  Task t;
-  t.n = uni64(m->n);
-  t.whole = t.n / kLaneElements;
-  const uint32_t block = blockIdx.x - uni(m->first_task);
-  t.lane = (uint64_t)block * kThreads + threadIdx.x;
-  t.last = block + 1 == planes_tasks_of(t.n);
-  return t;
-}
-
+// (the table walk — member_of, task_of, uni_ptr — is planes_shuffle.h's, shared with hsrans_planes_delta.hip)
 template <uint32_t W>
 __device__ __forceinline__ void split_task(const PlanesBatchMember *m)
 {

@@ -1,0 +1,345 @@
+// hsrans_planes_delta.hip — the byte-plane kernels for a tensor coded against a base (hsrans_*_device_planes_delta): what goes into the
+// planes is in ^ base, what comes out of them is XORed with the base again.  k_planes_split_delta<W> and k_planes_merge_delta<W> are
+// k_planes_split and k_planes_merge (hsrans_planes.hip) with the lane's 16 W base bytes loaded beside its 16 W element bytes — one more
+// 16-byte load per 16 bytes moved, nothing else; k_planes_split_delta_batch and k_planes_merge_delta_batch are the table-driven forms
+// (hsrans_planes_batch.hip) whose records carry a base pointer, null for a member that is coded as it is; k_planes_merge_ranges_delta<W> is
+// k_planes_merge_ranges (hsrans_planes_gather.hip) with the base read at the SOURCE element's index.
+// In place.  The whole-tensor merges take out == base: neither is __restrict__, a lane has loaded all of its base bytes before its first
+// store (the tail: the base byte is read, then written), and no lane reads bytes another lane writes.  Partial overlap is not safe, and
+// the entries refuse it.
+#include "hsrans_planes.h"
+#include "planes_shuffle.h"
+
+#include <algorithm>
+
+namespace hsrans
+{
+namespace
+{
+using namespace planes_detail;
+
+// ---- one tensor: the grids and the lanes' work of hsrans_planes.hip ----
+template <uint32_t W>
+__global__ __launch_bounds__(kThreads) void k_planes_split_delta(const uint8_t *__restrict__ in, const uint8_t *__restrict__ base, uint64_t n, PlanePtrs planes)
+{
+  const uint64_t whole = n / kLaneElements, lane = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (lane < whole)
+  {
+    uint32_t e[4 * W], b[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(in + lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(base + lane * (kLaneElements * W) + 16 * k, b + 4 * k);
+#pragma unroll
+    for (uint32_t k = 0; k < 4 * W; k++)
+      e[k] ^= b[k];
+    split16<W>(e, pl);
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      store16(planes.p[p] + lane * kLaneElements, pl[p]);
+  }
+  const uint32_t tail = (uint32_t)(n % kLaneElements);
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x < tail)
+  {
+    const uint64_t i = whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      planes.p[p][i] = in[i * W + p] ^ base[i * W + p];
+  }
+}
+
+// (base and out may be the same buffer: not __restrict__)
+template <uint32_t W>
+__global__ __launch_bounds__(kThreads) void k_planes_merge_delta(PlanePtrs planes, const uint8_t *base, uint64_t n, uint8_t *out)
+{
+  const uint64_t whole = n / kLaneElements, lane = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (lane < whole)
+  {
+    uint32_t e[4 * W], b[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      load16(planes.p[p] + lane * kLaneElements, pl[p]);
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(base + lane * (kLaneElements * W) + 16 * k, b + 4 * k);
+    merge16<W>(pl, e);
+#pragma unroll
+    for (uint32_t k = 0; k < 4 * W; k++)
+      e[k] ^= b[k];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      store16(out + lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+  }
+  const uint32_t tail = (uint32_t)(n % kLaneElements);
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x < tail)
+  {
+    const uint64_t i = whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+    {
+      const uint8_t b = base[i * W + p];
+      out[i * W + p] = planes.p[p][i] ^ b;
+    }
+  }
+}
+
+// ---- many tensors: the table walk of hsrans_planes_batch.hip (member_of, task_of, uni_ptr: planes_shuffle.h) over records with a base ----
+// kDelta: the member has a base (decided per workgroup, from the record)
+template <uint32_t W, bool kDelta>
+__device__ __forceinline__ void split_task(const PlanesDeltaBatchMember *m)
+{
+  const Task t = task_of(&m->m);
+  const uint8_t *in = uni_ptr(m->m.elements), *base = uni_ptr(m->base);
+  uint8_t *planes[W];
+#pragma unroll
+  for (uint32_t p = 0; p < W; p++)
+    planes[p] = uni_ptr(m->m.plane[p]);
+  if (t.lane < t.whole)
+  {
+    uint32_t e[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(in + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+    if constexpr (kDelta)
+    {
+      uint32_t b[4 * W];
+#pragma unroll
+      for (uint32_t k = 0; k < W; k++)
+        load16(base + t.lane * (kLaneElements * W) + 16 * k, b + 4 * k);
+#pragma unroll
+      for (uint32_t k = 0; k < 4 * W; k++)
+        e[k] ^= b[k];
+    }
+    split16<W>(e, pl);
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      store16(planes[p] + t.lane * kLaneElements, pl[p]);
+  }
+  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
+  if (t.last && threadIdx.x < tail)
+  {
+    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      planes[p][i] = kDelta ? in[i * W + p] ^ base[i * W + p] : in[i * W + p];
+  }
+}
+
+template <uint32_t W, bool kDelta>
+__device__ __forceinline__ void merge_task(const PlanesDeltaBatchMember *m)
+{
+  const Task t = task_of(&m->m);
+  uint8_t *out = uni_ptr(m->m.elements);
+  const uint8_t *base = uni_ptr(m->base); // (may be `out`)
+  const uint8_t *planes[W];
+#pragma unroll
+  for (uint32_t p = 0; p < W; p++)
+    planes[p] = uni_ptr(m->m.plane[p]);
+  if (t.lane < t.whole)
+  {
+    uint32_t e[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      load16(planes[p] + t.lane * kLaneElements, pl[p]);
+    if constexpr (kDelta)
+    {
+      uint32_t b[4 * W];
+#pragma unroll
+      for (uint32_t k = 0; k < W; k++)
+        load16(base + t.lane * (kLaneElements * W) + 16 * k, b + 4 * k);
+      merge16<W>(pl, e);
+#pragma unroll
+      for (uint32_t k = 0; k < 4 * W; k++)
+        e[k] ^= b[k];
+    }
+    else
+      merge16<W>(pl, e);
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      store16(out + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+  }
+  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
+  if (t.last && threadIdx.x < tail)
+  {
+    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+    {
+      const uint8_t b = kDelta ? base[i * W + p] : 0;
+      out[i * W + p] = planes[p][i] ^ b;
+    }
+  }
+}
+
+template <bool kDelta>
+__device__ __forceinline__ void split_member(const PlanesDeltaBatchMember *m, uint32_t W)
+{
+  if (W == 2)
+    split_task<2, kDelta>(m);
+  else if (W == 4)
+    split_task<4, kDelta>(m);
+  else if (W == 8)
+    split_task<8, kDelta>(m);
+}
+template <bool kDelta>
+__device__ __forceinline__ void merge_member(const PlanesDeltaBatchMember *m, uint32_t W)
+{
+  if (W == 2)
+    merge_task<2, kDelta>(m);
+  else if (W == 4)
+    merge_task<4, kDelta>(m);
+  else if (W == 8)
+    merge_task<8, kDelta>(m);
+}
+
+// grid: the table's task total; count: its records
+__global__ __launch_bounds__(kThreads) void k_planes_split_delta_batch(const PlanesDeltaBatchMember *__restrict__ members, uint32_t count)
+{
+  const PlanesDeltaBatchMember *m = member_of(members, count, blockIdx.x);
+  const uint32_t W = uni(m->m.W);
+  if (uni64((uint64_t)m->base) != 0)
+    split_member<true>(m, W);
+  else
+    split_member<false>(m, W);
+}
+
+__global__ __launch_bounds__(kThreads) void k_planes_merge_delta_batch(const PlanesDeltaBatchMember *__restrict__ members, uint32_t count)
+{
+  const PlanesDeltaBatchMember *m = member_of(members, count, blockIdx.x);
+  const uint32_t W = uni(m->m.W);
+  if (uni64((uint64_t)m->base) != 0)
+    merge_member<true>(m, W);
+  else
+    merge_member<false>(m, W);
+}
+
+// ---- element ranges of one frame: k_planes_merge_ranges' body (hsrans_planes_gather.hip) in its own copy ----
+static_assert(kThreads * kLaneElements == kPlanesGatherTaskElements, "one lane per 16-element block of a task");
+
+// grid: one workgroup per task; xbase: the whole base tensor, in the frame's element coordinates (never the output: __restrict__)
+template <uint32_t W>
+__global__ __launch_bounds__(kThreads) void k_planes_merge_ranges_delta(PlanePtrs planes, uint32_t work_mask, const PlanesGatherTask *__restrict__ tasks,
+                                                                        const uint8_t *__restrict__ xbase, uint8_t *__restrict__ out)
+{
+  const PlanesGatherTask t = tasks[blockIdx.x];
+  const uint32_t first = threadIdx.x * kLaneElements; // the lane's block: elements [src + first, src + first + 16)
+  if (first >= t.hi)
+    return;
+  const uint32_t lo = first < t.lo ? t.lo - first : 0, hi = t.hi - first < kLaneElements ? t.hi - first : kLaneElements; // (t.lo < 16: only lane 0 has a head)
+  const uint8_t *src[W];
+#pragma unroll
+  for (uint32_t p = 0; p < W; p++)
+    src[p] = planes.p[p] + (((work_mask >> p) & 1) != 0 ? t.work_pos : t.src) + first;
+  const uint8_t *bsrc = xbase + (t.src + first) * W; // the block's base bytes: 16-byte aligned (src a multiple of 16 elements)
+  const uint64_t base = t.src + first + (uint64_t)t.dst_delta; // the output element of the block's element 0 (modulo 2^64: a head's may lie below 0)
+  if (lo == 0 && hi == kLaneElements)
+  {
+    uint32_t e[4 * W], b[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      load16(src[p], pl[p]);
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(bsrc + 16 * k, b + 4 * k);
+    merge16<W>(pl, e);
+#pragma unroll
+    for (uint32_t k = 0; k < 4 * W; k++)
+      e[k] ^= b[k];
+    uint8_t *dst = out + base * W;
+    if (((uintptr_t)dst & 15) == 0)
+    {
+#pragma unroll
+      for (uint32_t k = 0; k < W; k++)
+        store16(dst + 16 * k, e + 4 * k);
+    }
+    else
+      store_elements<W>(dst, e);
+    return;
+  }
+  for (uint32_t i = lo; i < hi; i++) // (base bytes of the range's own elements only)
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      out[(base + i) * W + p] = src[p][i] ^ bsrc[i * W + p];
+}
+
+bool launch_ok(uint32_t W, const void *elements, const void *base, uint64_t n, const PlanePtrs &planes)
+{
+  return planes_ptrs_ok(W, planes) && elements != nullptr && ((uintptr_t)elements & 15) == 0 && base != nullptr && ((uintptr_t)base & 15) == 0 && n != 0 &&
+         n <= kPlanesMaxElements;
+}
+uint32_t grid_of(uint64_t n)
+{
+  const uint64_t whole = n / kLaneElements;
+  return (uint32_t)std::max<uint64_t>((whole + kThreads - 1) / kThreads, 1);
+}
+bool table_ok(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks)
+{
+  return d_members != nullptr && ((uintptr_t)d_members & 7) == 0 && count != 0 && n_tasks >= count && n_tasks <= 0x7FFFFFFFu;
+}
+} // namespace
+
+hipError_t launch_planes_split_delta(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
+{
+  if (!launch_ok(W, in, base, n, planes))
+    return hipErrorInvalidValue;
+  const uint8_t *src = (const uint8_t *)in, *b = (const uint8_t *)base;
+  if (W == 2)
+    k_planes_split_delta<2><<<grid_of(n), kThreads, 0, stream>>>(src, b, n, planes);
+  else if (W == 4)
+    k_planes_split_delta<4><<<grid_of(n), kThreads, 0, stream>>>(src, b, n, planes);
+  else
+    k_planes_split_delta<8><<<grid_of(n), kThreads, 0, stream>>>(src, b, n, planes);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_merge_delta(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream)
+{
+  if (!launch_ok(W, out, base, n, planes))
+    return hipErrorInvalidValue;
+  const uint8_t *b = (const uint8_t *)base;
+  uint8_t *dst = (uint8_t *)out;
+  if (W == 2)
+    k_planes_merge_delta<2><<<grid_of(n), kThreads, 0, stream>>>(planes, b, n, dst);
+  else if (W == 4)
+    k_planes_merge_delta<4><<<grid_of(n), kThreads, 0, stream>>>(planes, b, n, dst);
+  else
+    k_planes_merge_delta<8><<<grid_of(n), kThreads, 0, stream>>>(planes, b, n, dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
+{
+  if (!table_ok(d_members, count, n_tasks))
+    return hipErrorInvalidValue;
+  k_planes_split_delta_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
+{
+  if (!table_ok(d_members, count, n_tasks))
+    return hipErrorInvalidValue;
+  k_planes_merge_delta_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_merge_ranges_delta(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
+                                            void *out, hipStream_t stream)
+{
+  if (!planes_ptrs_ok(W, planes) || out == nullptr || ((uintptr_t)out & 15) != 0 || base == nullptr || ((uintptr_t)base & 15) != 0 || d_tasks == nullptr ||
+      ((uintptr_t)d_tasks & 7) != 0 || n_tasks == 0 || n_tasks > 0x7FFFFFFFu || (work_mask >> W) != 0)
+    return hipErrorInvalidValue;
+  const uint8_t *b = (const uint8_t *)base;
+  uint8_t *dst = (uint8_t *)out;
+  if (W == 2)
+    k_planes_merge_ranges_delta<2><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, b, dst);
+  else if (W == 4)
+    k_planes_merge_ranges_delta<4><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, b, dst);
+  else
+    k_planes_merge_ranges_delta<8><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, b, dst);
+  return hipGetLastError();
+}
+
+} // namespace hsrans

@@ -1,7 +1,8 @@
-// planes_shuffle.h — what the byte-plane kernels (the six hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
+// planes_shuffle.h — what the byte-plane kernels (the eight hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
 // bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  And the small
 // helpers of the table- and list-driven kernels: wave-uniform values as scalars, the global-address cast, the element-wide stores of a
-// block whose output is not 16-byte aligned, and the search of a task's row in a prefix of task counts.  Device code only; every function
+// block whose output is not 16-byte aligned, the search of a task's row in a prefix of task counts, and the walk of the member tables
+// (a workgroup's member and its place in it).  Device code only; every function
 // is inlined into the kernel that calls it.  Everything is in hsrans::planes_detail; every unit says `using namespace`.
 //
 // What is NOT here: the range merges' 16-element block body — from the full-block path (load16 per plane, merge16, the 16-byte or
@@ -15,6 +16,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "hsrans_planes.h"
 
 namespace hsrans
 {
@@ -48,6 +51,45 @@ __device__ __forceinline__ uint32_t task_row(const uint32_t *__restrict__ first_
       hi = mid;
   }
   return lo;
+}
+
+// ---- the member tables of hsrans_planes_batch.hip and hsrans_planes_delta.hip: one workgroup per task ----
+// a pointer read from a record, the same on every lane
+__device__ __forceinline__ uint8_t *uni_ptr(const uint8_t *p) { return global_at(uni64((uint64_t)p)); }
+// the plain record of a table's record
+__device__ __forceinline__ const PlanesBatchMember &batch_member(const PlanesBatchMember &r) { return r; }
+__device__ __forceinline__ const PlanesBatchMember &batch_member(const PlanesDeltaBatchMember &r) { return r.m; }
+// the record of task t: the last one with first_task <= t (first_task[0] is 0 and t is below the table's total); task_row's search over a
+// field of the records
+template <typename Record>
+__device__ __forceinline__ const Record *member_of(const Record *__restrict__ members, uint32_t count, uint32_t t)
+{
+  uint32_t lo = 0, hi = count;
+  while (hi - lo > 1)
+  {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (uni(batch_member(members[mid]).first_task) <= t)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return members + lo;
+}
+// What one workgroup sees of its member: its index among the member's workgroups, whether it is the last of them, and the lane's 16 elements
+struct Task
+{
+  uint64_t n, whole, lane;
+  bool last;
+};
+__device__ __forceinline__ Task task_of(const PlanesBatchMember *m)
+{
+  Task t;
+  t.n = uni64(m->n);
+  t.whole = t.n / kLaneElements;
+  const uint32_t block = blockIdx.x - uni(m->first_task);
+  t.lane = (uint64_t)block * kThreads + threadIdx.x;
+  t.last = block + 1 == planes_tasks_of(t.n);
+  return t;
 }
 
 // __builtin_amdgcn_perm(hi, lo, sel): result byte k = byte sel[k] of {lo: 0..3, hi: 4..7}

@@ -1305,6 +1305,75 @@ int hsrans_decode_device_planes_gather_batch_indirect(hsrans_ctx *ctx, hsrans_pl
 int hsrans_planes_gather_set_refused(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream);
 int hsrans_planes_gather_set_indirect_info(const hsrans_planes_gather_set *pgs, uint32_t max_count, size_t out_capacity, size_t work_bytes,
                                            hsrans_planes_gather_set_indirect_info_t *info);
+/* ------------------------------------------------------------------------------------------------------------
+ * Tensors coded against a base.  The tensors this layer is for are rarely alone: a checkpoint's parameters sit next to the
+ * previous checkpoint's, a fine-tuned model next to its base, a layer's experts next to a shared initialisation.  XORed with a
+ * close relative, a bf16 tensor's sign/exponent byte is almost always zero and its mantissa byte's upper bits mostly are: the
+ * residue codes far smaller than the tensor.  XOR, not an arithmetic difference: it is dtype-free (the library takes no view on
+ * endianness or dtype), exactly invertible and needs no carries across bytes.
+ *
+ * The invariant.  A delta frame of `in` against `base` is, byte for byte, the ordinary frame of the tensor in ^ base: the same
+ * frame bytes, the same descriptor, the same plans as hsrans_encode_device_planes gives for a buffer that holds in ^ base.
+ * hsrans_planes_desc does not change and a frame does NOT record its base: keeping track of the base is the caller's business,
+ * like the descriptor itself.  Every other entry of this layer therefore takes a delta frame unchanged and yields the residue —
+ * hsrans_planes_create, hsrans_planes_pack_device, the gathers, the batches; in particular hsrans_decode_device_planes of a delta
+ * frame gives in ^ base.  That is intended, not an error the library could detect.
+ *
+ * Cost.  The XOR rides in the split and the merge kernels, which touch every element once anyway: one more 16-byte load per 16
+ * bytes moved.  No extra launch, no extra workspace, no codec kernel changes: each entry below has the launch count, the
+ * workspace, the return value and the synchronisation of its plain counterpart, and checks everything that one checks.
+ *
+ * The base: a device buffer, 16-byte aligned, base_bytes >= elem_size * elements, element i of the base against element i of
+ * the tensor.  HSRANS_E_ARG (the encoders: 0) before anything is launched or written for a NULL or misaligned base or a short
+ * base_bytes.  Overlap: the base is a READ span over base_bytes.  It may coincide with other read spans — one base shared by
+ * many members, or d_in == d_base (every plane is then one symbol) — and any intersection with a written span (a frame, the
+ * workspace, an output) is refused.  A frame counts as one on the decode side too, where it is only read: a base that meets the
+ * frame it is decoded against — in the batch any member's frame, in the gather the frame the object is bound to — is refused.
+ * In place.  One exception, for the whole-tensor decodes (hsrans_planes_merge_delta_device, hsrans_decode_device_planes_delta and
+ * hsrans_decode_device_planes_delta_batch): a member's output may be exactly its own base — the same address, out_capacity <=
+ * base_bytes — and the delta is then applied in place: every lane reads its base bytes before it writes, and no lane reads
+ * another's.  Any other overlap of an output and a base (an offset of 16 bytes, another member's base) is refused.  The gather
+ * allows no aliasing at all.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* the rule on the host, in plain C++: planes[p][i] = in[i * W + p] ^ base[i * W + p], and back (out may be base);
+ * HSRANS_OK or HSRANS_E_ARG (elem_size not 2, 4 or 8; a NULL pointer) */
+int hsrans_planes_split_delta(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes);
+int hsrans_planes_merge_delta(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out);
+/* the two kernels alone, as hsrans_planes_split_device / hsrans_planes_merge_device: asynchronous on `hip_stream`, no allocation,
+ * no synchronisation.  d_base: elem_size * elements bytes, 16-byte aligned, clear of the planes; the merge's d_out may be d_base. */
+int hsrans_planes_split_delta_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, const void *d_base, size_t elements, void *const *d_planes,
+                                     void *hip_stream);
+int hsrans_planes_merge_delta_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, const void *d_base, size_t elements, void *d_out,
+                                     void *hip_stream);
+/* hsrans_encode_device_planes of in ^ base without the buffer that holds it: the same flow with the delta split in front, the
+ * same return value, descriptor, plans, refusals and synchronisation; a stored plane holds the residue's bytes. */
+size_t hsrans_encode_device_planes_delta(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, const void *d_base, size_t base_bytes,
+                                         size_t elements, void *d_frame, size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags,
+                                         void *d_work, size_t work_bytes, void *hip_stream, hsrans_planes_desc *desc,
+                                         hsrans_dplan **out_dplans /* [elem_size] or NULL */);
+/* hsrans_decode_device_planes with the delta merge behind the codec batch: d_out = (what the frame holds) ^ base.  The same
+ * launch count (hsrans_planes_info) and workspace; asynchronous.  d_out may be d_base (in place, above). */
+int hsrans_decode_device_planes_delta(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const void *d_base, size_t base_bytes,
+                                      void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+/* hsrans_encode_device_planes_batch with a base per member: member k is coded against d_bases[k] over base_bytes[k], or as it
+ * is where d_bases[k] is NULL (base_bytes[k] is then ignored).  Member equivalence: member k gets byte for byte what
+ * hsrans_encode_device_planes_delta gives it — hsrans_encode_device_planes where its base is NULL.  One delta split launch over
+ * all members (the NULL-base choice is taken per workgroup), then the plain call's launches: the same stats.  A NULL d_bases or
+ * base_bytes array is HSRANS_E_ARG. */
+int hsrans_encode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases /* [count], entries may be NULL */,
+                                            const size_t *base_bytes /* [count] */, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
+                                            hsrans_dplan **out_dplans /* [count * HSRANS_PLANES_MAX] or NULL */, hsrans_planes_batch_stats *stats /* may be NULL */);
+/* hsrans_decode_device_planes_batch with ONE delta merge launch in place of the merge: the set's launch count and workspace.
+ * d_outs[k] may be d_bases[k] (in place, above); it may not meet another member's base. */
+int hsrans_decode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
+                                            const void *const *d_bases /* [count], entries may be NULL */, const size_t *base_bytes /* [count] */, void *const *d_outs,
+                                            const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream);
+/* hsrans_decode_device_planes_gather (ranges in host memory) of a delta frame: element offset + i of the frame, XORed with
+ * element offset + i of the base, lands at element dst_offset + i of d_out.  d_base is the WHOLE base tensor, in the frame's
+ * element coordinates (base_bytes >= elem_size * the frame's elements), whatever the ranges are; heads and tails read base bytes
+ * of their own elements only.  No aliasing: the base may not meet d_out or d_work. */
+int hsrans_decode_device_planes_gather_delta(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const void *d_base, size_t base_bytes,
+                                             void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

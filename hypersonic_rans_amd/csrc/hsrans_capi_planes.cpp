@@ -4,7 +4,10 @@
 // hsrans_decode_device_batch of the coded planes and one merge launch behind it.  Both codecs are used as they are, through their public
 // entries: a coded plane is byte for byte what hsrans_encode_device(HSRANS_MT, ...) writes for the plane's bytes.
 // The two entries' bodies are planes_encode_flow and planes_decode_flow (hsrans_internal.h), which take an optional base: without one they are
-// the entries as they always were; with one the split or the merge is the delta kernel (hsrans_capi_planes_delta.cpp calls them so).
+// the entries as they always were; with one the split or the merge is the delta kernel (hsrans_planes_delta.hip).
+// hsrans_*_device_planes_delta — tensors coded against a base — are these entries given a base, each beside its plain form (here, and in
+// hsrans_capi_planes_batch.cpp and hsrans_capi_planes_gather.cpp).  A delta frame of `in` against `base` is byte for byte the ordinary frame
+// of in ^ base, so nothing of the frame, the descriptor or the codec is new: the XOR rides in the split and the merge.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -32,13 +35,17 @@ PlanePtrs work_planes(uint32_t W, void *d_work, size_t elements)
   return pp;
 }
 
-// the checks of the two kernel entries: W pointers to `elements` bytes each and the element buffer, all 16-byte aligned, none meeting another
-bool kernel_args_ok(uint32_t W, const void *d_elements, size_t elements, const void *const *d_planes, bool planes_written, PlanePtrs *pp)
+// the checks of the kernel entries: W pointers to `elements` bytes each and the element buffer, all 16-byte aligned, none meeting another.
+// base.on: the base joins them as a read span of the element buffer's size.  The merge's element buffer is written and may be the base
+// itself; the split's is read, and reads may share.
+bool kernel_args_ok(uint32_t W, const void *d_elements, const PlanesBase &base, size_t elements, const void *const *d_planes, bool planes_written, PlanePtrs *pp)
 {
   if (!planes_width_ok(W) || !aligned16(d_elements) || d_planes == nullptr || elements == 0 || elements > kPlanesMaxElements)
     return false;
   std::vector<Span> spans;
   spans.push_back(span_of(d_elements, elements * W, !planes_written));
+  if (!planes_base_spans(base, W, elements, planes_written ? nullptr : d_elements, elements * W, &spans))
+    return false;
   for (uint32_t p = 0; p < W; p++)
   {
     if (!aligned16(d_planes[p]))
@@ -116,41 +123,50 @@ extern "C" size_t hsrans_planes_workspace_bytes(uint32_t elem_size, size_t eleme
   return elem_size * up256(elements);
 }
 
-extern "C" int hsrans_planes_split(uint32_t elem_size, const void *in, size_t elements, uint8_t *const *planes)
+// ---- the split and the merge alone, on the host in plain C++ and as one kernel: each plain entry is the delta entry's body without a base ----
+namespace
 {
-  if (!planes_width_ok(elem_size) || in == nullptr || planes == nullptr)
-    return HSRANS_E_ARG;
+bool host_args_ok(uint32_t elem_size, const void *elements, const uint8_t *const *planes)
+{
+  if (!planes_width_ok(elem_size) || elements == nullptr || planes == nullptr)
+    return false;
   for (uint32_t p = 0; p < elem_size; p++)
     if (planes[p] == nullptr)
-      return HSRANS_E_ARG;
-  const uint8_t *src = (const uint8_t *)in;
+      return false;
+  return true;
+}
+
+// base: null, or what is XORed into every byte on its way
+int host_split(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes)
+{
+  if (!host_args_ok(elem_size, in, planes))
+    return HSRANS_E_ARG;
+  const uint8_t *src = (const uint8_t *)in, *b = (const uint8_t *)base;
   for (size_t i = 0; i < elements; i++)
     for (uint32_t p = 0; p < elem_size; p++)
-      planes[p][i] = src[i * elem_size + p];
+      planes[p][i] = src[i * elem_size + p] ^ (b != nullptr ? b[i * elem_size + p] : 0);
   return HSRANS_OK;
 }
 
-extern "C" int hsrans_planes_merge(uint32_t elem_size, const uint8_t *const *planes, size_t elements, void *out)
+int host_merge(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out)
 {
-  if (!planes_width_ok(elem_size) || out == nullptr || planes == nullptr)
+  if (!host_args_ok(elem_size, out, planes))
     return HSRANS_E_ARG;
-  for (uint32_t p = 0; p < elem_size; p++)
-    if (planes[p] == nullptr)
-      return HSRANS_E_ARG;
+  const uint8_t *b = (const uint8_t *)base; // (may be `out`: every byte is read, then written)
   uint8_t *dst = (uint8_t *)out;
   for (size_t i = 0; i < elements; i++)
     for (uint32_t p = 0; p < elem_size; p++)
-      dst[i * elem_size + p] = planes[p][i];
+      dst[i * elem_size + p] = planes[p][i] ^ (b != nullptr ? b[i * elem_size + p] : 0);
   return HSRANS_OK;
 }
 
-extern "C" int hsrans_planes_split_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, size_t elements, void *const *d_planes, void *hip_stream)
+int split_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, const PlanesBase &base, size_t elements, void *const *d_planes, void *hip_stream)
 try
 {
   PlanePtrs pp{};
-  if (ctx == nullptr || !kernel_args_ok(elem_size, d_in, elements, (const void *const *)d_planes, true, &pp))
+  if (ctx == nullptr || !kernel_args_ok(elem_size, d_in, base, elements, (const void *const *)d_planes, true, &pp))
     return HSRANS_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(elem_size, d_in, elements, pp, (hipStream_t)hip_stream) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(elem_size, d_in, base.on ? base.d : nullptr, elements, pp, (hipStream_t)hip_stream) != hipSuccess)
     return HSRANS_E_HIP;
   return HSRANS_OK;
 }
@@ -159,19 +175,63 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
   return HSRANS_E_HIP;
 }
 
-extern "C" int hsrans_planes_merge_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, size_t elements, void *d_out, void *hip_stream)
+int merge_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, const PlanesBase &base, size_t elements, void *d_out, void *hip_stream)
 try
 {
   PlanePtrs pp{};
-  if (ctx == nullptr || !kernel_args_ok(elem_size, d_out, elements, d_planes, false, &pp))
+  if (ctx == nullptr || !kernel_args_ok(elem_size, d_out, base, elements, d_planes, false, &pp))
     return HSRANS_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(elem_size, pp, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(elem_size, pp, base.on ? base.d : nullptr, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
     return HSRANS_E_HIP;
   return HSRANS_OK;
 }
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+} // namespace
+
+extern "C" int hsrans_planes_split(uint32_t elem_size, const void *in, size_t elements, uint8_t *const *planes)
+{
+  return host_split(elem_size, in, nullptr, elements, planes);
+}
+
+extern "C" int hsrans_planes_split_delta(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes)
+{
+  return base == nullptr ? HSRANS_E_ARG : host_split(elem_size, in, base, elements, planes);
+}
+
+extern "C" int hsrans_planes_merge(uint32_t elem_size, const uint8_t *const *planes, size_t elements, void *out)
+{
+  return host_merge(elem_size, planes, nullptr, elements, out);
+}
+
+extern "C" int hsrans_planes_merge_delta(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out)
+{
+  return base == nullptr ? HSRANS_E_ARG : host_merge(elem_size, planes, base, elements, out);
+}
+
+extern "C" int hsrans_planes_split_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, size_t elements, void *const *d_planes, void *hip_stream)
+{
+  return split_device(ctx, elem_size, d_in, PlanesBase{}, elements, d_planes, hip_stream);
+}
+
+// (a null d_base is refused with the base's other checks, planes_base_spans; elements * elem_size: read only once both are known to be in range)
+extern "C" int hsrans_planes_split_delta_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, const void *d_base, size_t elements, void *const *d_planes,
+                                                void *hip_stream)
+{
+  return split_device(ctx, elem_size, d_in, PlanesBase{true, d_base, elements * elem_size}, elements, d_planes, hip_stream);
+}
+
+extern "C" int hsrans_planes_merge_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, size_t elements, void *d_out, void *hip_stream)
+{
+  return merge_device(ctx, elem_size, d_planes, PlanesBase{}, elements, d_out, hip_stream);
+}
+
+extern "C" int hsrans_planes_merge_delta_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, const void *d_base, size_t elements, void *d_out,
+                                                void *hip_stream)
+{
+  return merge_device(ctx, elem_size, d_planes, PlanesBase{true, d_base, elements * elem_size}, elements, d_out, hip_stream);
 }
 
 bool planes_base_spans(const PlanesBase &base, uint32_t W, size_t elements, const void *d_out, size_t out_capacity, std::vector<Span> *spans)
@@ -233,8 +293,7 @@ try
 
   hipStream_t s = (hipStream_t)hip_stream;
   const PlanePtrs pp = work_planes(W, d_work, elements);
-  if (hipSetDevice(ctx->device) != hipSuccess ||
-      (base.on ? launch_planes_split_delta(W, d_in, base.d, elements, pp, s) : launch_planes_split(W, d_in, elements, pp, s)) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(W, d_in, base.on ? base.d : nullptr, elements, pp, s) != hipSuccess)
   {
     (void)hipGetLastError();
     return 0;
@@ -311,6 +370,14 @@ extern "C" size_t hsrans_encode_device_planes(hsrans_ctx *ctx, uint32_t elem_siz
 {
   return planes_encode_flow(ctx, elem_size, states, bits, d_in, PlanesBase{}, elements, d_frame, frame_capacity, block_size, index_interval, flags, d_work, work_bytes,
                             hip_stream, desc, out_dplans);
+}
+
+extern "C" size_t hsrans_encode_device_planes_delta(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, const void *d_base, size_t base_bytes,
+                                                    size_t elements, void *d_frame, size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags,
+                                                    void *d_work, size_t work_bytes, void *hip_stream, hsrans_planes_desc *desc, hsrans_dplan **out_dplans)
+{
+  return planes_encode_flow(ctx, elem_size, states, bits, d_in, PlanesBase{true, d_base, base_bytes}, elements, d_frame, frame_capacity, block_size, index_interval, flags,
+                            d_work, work_bytes, hip_stream, desc, out_dplans);
 }
 
 extern "C" void hsrans_planes_destroy(hsrans_planes *planes)
@@ -407,8 +474,7 @@ try
       return rc;
   }
   hipStream_t s = (hipStream_t)hip_stream;
-  if (hipSetDevice(ctx->device) != hipSuccess ||
-      (base.on ? launch_planes_merge_delta(W, src, base.d, elements, d_out, s) : launch_planes_merge(W, src, elements, d_out, s)) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(W, src, base.on ? base.d : nullptr, elements, d_out, s) != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -424,6 +490,12 @@ extern "C" int hsrans_decode_device_planes(hsrans_ctx *ctx, hsrans_planes *plane
                                            void *d_work, size_t work_bytes, void *hip_stream)
 {
   return planes_decode_flow(ctx, planes, d_frame, frame_length, PlanesBase{}, d_out, out_capacity, d_work, work_bytes, hip_stream);
+}
+
+extern "C" int hsrans_decode_device_planes_delta(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const void *d_base, size_t base_bytes,
+                                                 void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_decode_flow(ctx, planes, d_frame, frame_length, PlanesBase{true, d_base, base_bytes}, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_status(hsrans_ctx *ctx, hsrans_planes *planes, void *hip_stream, int *plane_status)

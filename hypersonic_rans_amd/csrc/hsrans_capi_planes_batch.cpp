@@ -46,13 +46,19 @@ int launch_with_table(hsrans_ctx *ctx, const std::vector<Record> &table, hipStre
       [&](const uint8_t *dev) { return launch((const Record *)dev); });
 }
 
-// the delta kernels' table: the plain records with every member's base (null: none)
-std::vector<PlanesDeltaBatchMember> with_bases(const std::vector<PlanesBatchMember> &table, const void *const *d_bases)
+// The split or the merge of a batch: `plain(device table, members, tasks, stream)` over the table as it is, or with d_bases `delta(...)` over
+// the delta kernels' table — the plain records with every member's base (null: none).  (Two record types, so two kernels: the choice stays.)
+template <typename Plain, typename Delta>
+int launch_split_or_merge(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &table, const void *const *d_bases, uint32_t n_tasks, hipStream_t s, Plain plain,
+                          Delta delta)
 {
-  std::vector<PlanesDeltaBatchMember> out(table.size());
-  for (size_t k = 0; k < table.size(); k++)
-    out[k] = PlanesDeltaBatchMember{table[k], (const uint8_t *)d_bases[k]};
-  return out;
+  const uint32_t count = (uint32_t)table.size();
+  if (d_bases == nullptr)
+    return launch_with_table(ctx, table, s, [&](const PlanesBatchMember *d) { return plain(d, count, n_tasks, s); });
+  std::vector<PlanesDeltaBatchMember> with_bases(count);
+  for (uint32_t k = 0; k < count; k++)
+    with_bases[k] = PlanesDeltaBatchMember{table[k], (const uint8_t *)d_bases[k]};
+  return launch_with_table(ctx, with_bases, s, [&](const PlanesDeltaBatchMember *d) { return delta(d, count, n_tasks, s); });
 }
 
 // every output of a failed encode: no frame, no descriptor, no plan (one already made is destroyed)
@@ -189,9 +195,7 @@ try
     t.W = members[k].elem_size;
     t.first_task = first_task[k];
   }
-  int rc = delta ? launch_with_table(ctx, with_bases(table, d_bases), s,
-                                     [&](const PlanesDeltaBatchMember *d) { return launch_planes_split_delta_batch(d, count, (uint32_t)n_tasks, s); })
-                 : launch_with_table(ctx, table, s, [&](const PlanesBatchMember *d) { return launch_planes_split_batch(d, count, (uint32_t)n_tasks, s); });
+  int rc = launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, (uint32_t)n_tasks, s, launch_planes_split_batch, launch_planes_split_delta_batch);
   if (rc != HSRANS_OK)
   {
     fail_encode(members, count, out_dplans, rc);
@@ -312,6 +316,12 @@ extern "C" int hsrans_encode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_
                                                  hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
 {
   return planes_encode_batch_flow(ctx, members, nullptr, nullptr, false, count, d_work, work_bytes, hip_stream, out_dplans, stats);
+}
+
+extern "C" int hsrans_encode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes, uint32_t count,
+                                                       void *d_work, size_t work_bytes, void *hip_stream, hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
+{
+  return planes_encode_batch_flow(ctx, members, d_bases, base_bytes, true, count, d_work, work_bytes, hip_stream, out_dplans, stats);
 }
 
 extern "C" void hsrans_planes_set_destroy(hsrans_planes_set *set)
@@ -471,11 +481,8 @@ try
     if (rc != HSRANS_OK)
       return rc;
   }
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (delta)
-    return launch_with_table(ctx, with_bases(table, d_bases), s,
-                             [&](const PlanesDeltaBatchMember *d) { return launch_planes_merge_delta_batch(d, count, set->first_task.back(), s); });
-  return launch_with_table(ctx, table, s, [&](const PlanesBatchMember *d) { return launch_planes_merge_batch(d, count, set->first_task.back(), s); });
+  return launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, set->first_task.back(), (hipStream_t)hip_stream, launch_planes_merge_batch,
+                               launch_planes_merge_delta_batch);
 }
 catch (...)
 {
@@ -486,6 +493,13 @@ extern "C" int hsrans_decode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_
                                                  const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
 {
   return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, nullptr, nullptr, false, d_outs, out_capacities, d_work, work_bytes, hip_stream);
+}
+
+extern "C" int hsrans_decode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
+                                                       const void *const *d_bases, const size_t *base_bytes, void *const *d_outs, const size_t *out_capacities, void *d_work,
+                                                       size_t work_bytes, void *hip_stream)
+{
+  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, d_bases, base_bytes, true, d_outs, out_capacities, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_set_status(hsrans_ctx *ctx, hsrans_planes_set *set, void *hip_stream, int *member_status)

@@ -248,8 +248,7 @@ try
         return HSRANS_OK;
       },
       [&](const uint8_t *dev) {
-        return base.on ? launch_planes_merge_ranges_delta(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, base.d, d_out, s)
-                       : launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, d_out, s);
+        return launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, base.on ? base.d : nullptr, d_out, s);
       });
   if (rc != HSRANS_OK)
     return rc;
@@ -267,6 +266,12 @@ extern "C" int hsrans_decode_device_planes_gather(hsrans_ctx *ctx, hsrans_planes
                                                   void *d_work, size_t work_bytes, void *hip_stream)
 {
   return planes_gather_flow(ctx, pg, ranges, count, PlanesBase{}, d_out, out_capacity, d_work, work_bytes, hip_stream);
+}
+
+extern "C" int hsrans_decode_device_planes_gather_delta(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const void *d_base,
+                                                        size_t base_bytes, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_gather_flow(ctx, pg, ranges, count, PlanesBase{true, d_base, base_bytes}, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_gather_status(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream, int *plane_status)

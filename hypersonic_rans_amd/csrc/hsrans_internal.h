@@ -306,9 +306,9 @@ bool planes_encode_check(uint32_t W, int states, uint32_t bits, const void *d_in
 // hsrans_planes_create's rules for a descriptor and its planes' plans (dplans[p] null exactly for the stored planes): HSRANS_OK or HSRANS_E_ARG
 int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsrans_dplan *const *dplans);
 
-// ---- what the plain byte-plane entries and their delta forms (hsrans_capi_planes_delta.cpp) share: each plain entry's whole body, taking an
-// optional base.  Without one (`on` false) a flow is the plain entry, check for check and launch for launch; with one the split or the merge
-// is the delta kernel (hsrans_planes_delta.hip) and the base joins the checks.  Hidden: the library's exported symbols are the header's. ----
+// ---- what the plain byte-plane entries and their delta forms (hsrans_*_device_planes_delta, each beside its plain entry) share: each plain
+// entry's whole body, taking an optional base.  Without one (`on` false) a flow is the plain entry, check for check and launch for launch;
+// with one the launcher is handed the base, so the split or the merge is the delta kernel (hsrans_planes_delta.hip), and the base joins the checks.  Hidden: the library's exported symbols are the header's. ----
 struct PlanesBase
 {
   bool on = false; // a delta call (a plain one never looks at the rest)

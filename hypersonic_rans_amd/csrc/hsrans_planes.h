@@ -10,6 +10,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/hsrans_hip.h" // HSRANS_PACK_CHUNK
 #include "hsrans_carve.h"
 
@@ -34,10 +36,26 @@ inline bool planes_ptrs_ok(uint32_t W, const PlanePtrs &planes)
       return false;
   return true;
 }
+// The launchers' step from W (planes_ptrs_ok has passed) to a kernel's template argument: f(std::integral_constant<uint32_t, W>), so that
+// `[&](auto w) { k<w()><<<grid, 256, 0, stream>>>(...); }` is the whole dispatch.  hipcc takes a kernel launch inside a generic lambda (host
+// and device pass both instantiate the three kernels from it), so no macro and no table of kernel pointers is needed.
+template <typename F>
+inline void planes_with_width(uint32_t W, F &&f)
+{
+  if (W == 2)
+    f(std::integral_constant<uint32_t, 2>{});
+  else if (W == 4)
+    f(std::integral_constant<uint32_t, 4>{});
+  else
+    f(std::integral_constant<uint32_t, 8>{});
+}
 
-// asynchronous on `stream`; every pointer 16-byte aligned, n in 1..kPlanesMaxElements, W in {2, 4, 8} (hipErrorInvalidValue otherwise)
-hipError_t launch_planes_split(uint32_t W, const void *in, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
-hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, uint64_t n, void *out, hipStream_t stream);
+// asynchronous on `stream`; every pointer 16-byte aligned, n in 1..kPlanesMaxElements, W in {2, 4, 8} (hipErrorInvalidValue otherwise).
+// base: null, or as many bytes as the elements (hsrans_*_device_planes_delta): the planes hold in ^ base — k_planes_split_delta and
+// k_planes_merge_delta (hsrans_planes_delta.hip) instead of the plain kernels.  The merge's base may be `out` itself: the delta applied in
+// place; any other overlap of the two is the caller's to refuse.
+hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
+hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream);
 
 // ---- many tensors in one launch (hsrans_*_device_planes_batch): k_planes_split_batch, k_planes_merge_batch, k_planes_store_batch
 // (hsrans_planes_batch.hip), each driven by a table of these records in device memory, one workgroup per task ----
@@ -57,7 +75,11 @@ constexpr uint32_t planes_tasks_of(uint64_t n) // (host and device; n <= kPlanes
 }
 // asynchronous on `stream`, one kernel each, n_tasks workgroups (the table's task total, 1 .. 2^31 - 1); the table's pointers are the
 // caller's to check: set, 16-byte aligned, W in {2, 4, 8} (store: 1), n in 1..kPlanesMaxElements (hipErrorInvalidValue: a null table, no
-// member, a task total out of range)
+// member, a task total out of range — planes_table_ok, for the tables of either record type)
+inline bool planes_table_ok(const void *d_members, uint32_t count, uint32_t n_tasks)
+{
+  return d_members != nullptr && ((uintptr_t)d_members & 7) == 0 && count != 0 && n_tasks >= count && n_tasks <= 0x7FFFFFFFu;
+}
 hipError_t launch_planes_split_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_merge_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_store_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
@@ -99,9 +121,11 @@ struct PlanesGatherTask
   uint32_t lo, hi;
 };
 // asynchronous on `stream`, one workgroup per task (1 .. 2^31 - 1 of them, in device memory); planes.p[p]: plane p's workspace region where
-// bit p of work_mask is set, else the stored plane; every pointer 16-byte aligned (hipErrorInvalidValue otherwise)
-hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, void *out,
-                                      hipStream_t stream);
+// bit p of work_mask is set, else the stored plane; every pointer 16-byte aligned (hipErrorInvalidValue otherwise).  base: null, or the
+// whole base tensor (hsrans_decode_device_planes_gather_delta): output element (element + dst_delta) is XORed with base element `element`
+// — k_planes_merge_ranges_delta (hsrans_planes_delta.hip) instead of the plain kernel
+hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
+                                      void *out, hipStream_t stream);
 
 // ---- rows of many frames in one launch (hsrans_decode_device_planes_gather_batch): k_planes_merge_ranges_batch
 // (hsrans_planes_gather_batch.hip) ----
@@ -229,11 +253,13 @@ hipError_t launch_planes_cut_batch(const PlanesCutBatchParams &cp, hipStream_t s
 hipError_t launch_planes_merge_batch_indirect(const PlanesSetRow *d_ranges, const uint32_t *d_header, const uint32_t *d_first_task, const uint64_t *d_base,
                                               const PlanesGatherBatchMember *d_members, const void *work, void *out, uint32_t grid, hipStream_t stream);
 
-// ---- tensors coded against a base (hsrans_*_device_planes_delta): hsrans_planes_delta.hip.  The planes hold in ^ base; every launcher is
-// its plain counterpart above with the base beside the element buffer: set, 16-byte aligned, as many bytes as the elements ----
-// (the merge's base may be `out` itself: the delta applied in place; any other overlap of the two is the caller's to refuse)
-hipError_t launch_planes_split_delta(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
-hipError_t launch_planes_merge_delta(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream);
+// ---- tensors coded against a base (hsrans_*_device_planes_delta): hsrans_planes_delta.hip.  The planes hold in ^ base.  The one-tensor
+// launchers are the plain ones above, given a base; what that unit adds to them is the launch of its kernels alone — arguments checked and
+// grid formed by the caller, nothing returned: the caller asks hipGetLastError ----
+void planes_delta_split_kernel(uint32_t W, uint32_t grid, const uint8_t *in, const uint8_t *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
+void planes_delta_merge_kernel(uint32_t W, uint32_t grid, const PlanePtrs &planes, const uint8_t *base, uint64_t n, uint8_t *out, hipStream_t stream);
+void planes_delta_merge_ranges_kernel(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const uint8_t *base,
+                                      uint8_t *out, hipStream_t stream);
 // a PlanesBatchMember and the member's base; null: the member is split or merged as it is
 struct PlanesDeltaBatchMember
 {
@@ -242,9 +268,6 @@ struct PlanesDeltaBatchMember
 };
 hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
-// launch_planes_merge_ranges with output element (element + dst_delta) XORed with base element `element`; base: the whole base tensor
-hipError_t launch_planes_merge_ranges_delta(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
-                                            void *out, hipStream_t stream);
 
 } // namespace hsrans
 

@@ -14,32 +14,16 @@ namespace
 {
 using namespace planes_detail;
 
-// grid: one lane per 16 whole elements (at least one workgroup); n: elements
+// grid: one lane per 16 whole elements (at least one workgroup); n: elements.  (The lanes' work: split_lanes, planes_shuffle.h.)
 template <uint32_t W>
 __global__ __launch_bounds__(kThreads) void k_planes_split(const uint8_t *__restrict__ in, uint64_t n, PlanePtrs planes)
 {
-  const uint64_t whole = n / kLaneElements, lane = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (lane < whole)
-  {
-    uint32_t e[4 * W], pl[W][4];
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      load16(in + lane * (kLaneElements * W) + 16 * k, e + 4 * k);
-    split16<W>(e, pl);
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      store16(planes.p[p] + lane * kLaneElements, pl[p]);
-  }
-  const uint32_t tail = (uint32_t)(n % kLaneElements);
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x < tail)
-  {
-    const uint64_t i = whole * kLaneElements + threadIdx.x;
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      planes.p[p][i] = in[i * W + p];
-  }
+  split_lanes<W, false>(in, nullptr, planes.p, n, n / kLaneElements, (uint64_t)blockIdx.x * kThreads + threadIdx.x, blockIdx.x == gridDim.x - 1);
 }
 
+// merge_lanes<W, false> written out: as a call to it these three kernels read all their arguments on entry and came out 3 to 4 instructions
+// shorter and SLOWER — on 128 MiB, medians of 48 over three rounds, 58.5 against 57.1 µs (W = 2), 66.8 against 66.2 (4), 75.0 against 74.0 (8),
+// the first and the last beyond the quartiles of this form (CHANGELOG.md has the runs).  The splits lost nothing by the call.
 template <uint32_t W>
 __global__ __launch_bounds__(kThreads) void k_planes_merge(PlanePtrs planes, uint64_t n, uint8_t *__restrict__ out)
 {
@@ -65,9 +49,10 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge(PlanePtrs planes, uin
   }
 }
 
-bool launch_ok(uint32_t W, const void *elements, uint64_t n, const PlanePtrs &planes)
+// the whole-tensor launchers' check, with or without a base
+bool launch_ok(uint32_t W, const void *elements, const void *base, uint64_t n, const PlanePtrs &planes)
 {
-  return planes_ptrs_ok(W, planes) && elements != nullptr && ((uintptr_t)elements & 15) == 0 && n != 0 && n <= kPlanesMaxElements;
+  return planes_ptrs_ok(W, planes) && elements != nullptr && ((uintptr_t)elements & 15) == 0 && ((uintptr_t)base & 15) == 0 && n != 0 && n <= kPlanesMaxElements;
 }
 uint32_t grid_of(uint64_t n)
 {
@@ -76,31 +61,27 @@ uint32_t grid_of(uint64_t n)
 }
 } // namespace
 
-hipError_t launch_planes_split(uint32_t W, const void *in, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
+hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
 {
-  if (!launch_ok(W, in, n, planes))
+  if (!launch_ok(W, in, base, n, planes))
     return hipErrorInvalidValue;
   const uint8_t *src = (const uint8_t *)in;
-  if (W == 2)
-    k_planes_split<2><<<grid_of(n), kThreads, 0, stream>>>(src, n, planes);
-  else if (W == 4)
-    k_planes_split<4><<<grid_of(n), kThreads, 0, stream>>>(src, n, planes);
+  if (base != nullptr)
+    planes_delta_split_kernel(W, grid_of(n), src, (const uint8_t *)base, n, planes, stream);
   else
-    k_planes_split<8><<<grid_of(n), kThreads, 0, stream>>>(src, n, planes);
+    planes_with_width(W, [&](auto w) { k_planes_split<w()><<<grid_of(n), kThreads, 0, stream>>>(src, n, planes); });
   return hipGetLastError();
 }
 
-hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, uint64_t n, void *out, hipStream_t stream)
+hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream)
 {
-  if (!launch_ok(W, out, n, planes))
+  if (!launch_ok(W, out, base, n, planes))
     return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
-  if (W == 2)
-    k_planes_merge<2><<<grid_of(n), kThreads, 0, stream>>>(planes, n, dst);
-  else if (W == 4)
-    k_planes_merge<4><<<grid_of(n), kThreads, 0, stream>>>(planes, n, dst);
+  if (base != nullptr)
+    planes_delta_merge_kernel(W, grid_of(n), planes, (const uint8_t *)base, n, dst, stream);
   else
-    k_planes_merge<8><<<grid_of(n), kThreads, 0, stream>>>(planes, n, dst);
+    planes_with_width(W, [&](auto w) { k_planes_merge<w()><<<grid_of(n), kThreads, 0, stream>>>(planes, n, dst); });
   return hipGetLastError();
 }
 

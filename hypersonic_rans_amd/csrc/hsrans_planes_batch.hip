@@ -13,7 +13,8 @@ namespace
 {
 using namespace planes_detail;
 
-// (the table walk — member_of, task_of, uni_ptr — is planes_shuffle.h's, shared with hsrans_planes_delta.hip)
+// (the table walk — member_of, task_of, uni_ptr — and a task's lanes' work — split_lanes, merge_lanes — are planes_shuffle.h's, shared with
+// hsrans_planes_delta.hip)
 template <uint32_t W>
 __device__ __forceinline__ void split_task(const PlanesBatchMember *m)
 {
@@ -23,25 +24,7 @@ __device__ __forceinline__ void split_task(const PlanesBatchMember *m)
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     planes[p] = uni_ptr(m->plane[p]);
-  if (t.lane < t.whole)
-  {
-    uint32_t e[4 * W], pl[W][4];
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      load16(in + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
-    split16<W>(e, pl);
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      store16(planes[p] + t.lane * kLaneElements, pl[p]);
-  }
-  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
-  if (t.last && threadIdx.x < tail)
-  {
-    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      planes[p][i] = in[i * W + p];
-  }
+  split_lanes<W, false>(in, nullptr, planes, t.n, t.whole, t.lane, t.last);
 }
 
 template <uint32_t W>
@@ -53,25 +36,7 @@ __device__ __forceinline__ void merge_task(const PlanesBatchMember *m)
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     planes[p] = uni_ptr(m->plane[p]);
-  if (t.lane < t.whole)
-  {
-    uint32_t e[4 * W], pl[W][4];
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      load16(planes[p] + t.lane * kLaneElements, pl[p]);
-    merge16<W>(pl, e);
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      store16(out + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
-  }
-  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
-  if (t.last && threadIdx.x < tail)
-  {
-    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      out[i * W + p] = planes[p][i];
-  }
+  merge_lanes<W, false>(planes, nullptr, out, t.n, t.whole, t.lane, t.last);
 }
 
 // grid: the table's task total; count: its records
@@ -119,16 +84,11 @@ __global__ __launch_bounds__(kThreads) void k_planes_store_batch(const PlanesBat
     dst[i] = src[i];
   }
 }
-
-bool launch_ok(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks)
-{
-  return d_members != nullptr && ((uintptr_t)d_members & 7) == 0 && count != 0 && n_tasks >= count && n_tasks <= 0x7FFFFFFFu;
-}
 } // namespace
 
 hipError_t launch_planes_split_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
 {
-  if (!launch_ok(d_members, count, n_tasks))
+  if (!planes_table_ok(d_members, count, n_tasks))
     return hipErrorInvalidValue;
   k_planes_split_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
   return hipGetLastError();
@@ -136,7 +96,7 @@ hipError_t launch_planes_split_batch(const PlanesBatchMember *d_members, uint32_
 
 hipError_t launch_planes_merge_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
 {
-  if (!launch_ok(d_members, count, n_tasks))
+  if (!planes_table_ok(d_members, count, n_tasks))
     return hipErrorInvalidValue;
   k_planes_merge_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
   return hipGetLastError();
@@ -144,7 +104,7 @@ hipError_t launch_planes_merge_batch(const PlanesBatchMember *d_members, uint32_
 
 hipError_t launch_planes_store_batch(const PlanesBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
 {
-  if (!launch_ok(d_members, count, n_tasks))
+  if (!planes_table_ok(d_members, count, n_tasks))
     return hipErrorInvalidValue;
   k_planes_store_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
   return hipGetLastError();

@@ -4,13 +4,13 @@
 // 16-byte load per 16 bytes moved, nothing else; k_planes_split_delta_batch and k_planes_merge_delta_batch are the table-driven forms
 // (hsrans_planes_batch.hip) whose records carry a base pointer, null for a member that is coded as it is; k_planes_merge_ranges_delta<W> is
 // k_planes_merge_ranges (hsrans_planes_gather.hip) with the base read at the SOURCE element's index.
-// In place.  The whole-tensor merges take out == base: neither is __restrict__, a lane has loaded all of its base bytes before its first
-// store (the tail: the base byte is read, then written), and no lane reads bytes another lane writes.  Partial overlap is not safe, and
-// the entries refuse it.
+// The splits and the table-driven kernels run the body the plain ones run — split_lanes / merge_lanes (planes_shuffle.h), with the base
+// switched on; k_planes_merge_delta<W> has merge_lanes written out, and the range merge k_planes_merge_ranges' block body in its own copy
+// (planes_shuffle.h says why, for both).
+// In place.  The whole-tensor merges take out == base: neither is __restrict__, and the order that makes it safe is merge_lanes' (stated
+// there).  Partial overlap is not safe, and the entries refuse it.
 #include "hsrans_planes.h"
 #include "planes_shuffle.h"
-
-#include <algorithm>
 
 namespace hsrans
 {
@@ -18,39 +18,17 @@ namespace
 {
 using namespace planes_detail;
 
-// ---- one tensor: the grids and the lanes' work of hsrans_planes.hip ----
+// ---- one tensor: the grids of hsrans_planes.hip, the lanes' work with a base (split_lanes / merge_lanes, planes_shuffle.h) ----
 template <uint32_t W>
 __global__ __launch_bounds__(kThreads) void k_planes_split_delta(const uint8_t *__restrict__ in, const uint8_t *__restrict__ base, uint64_t n, PlanePtrs planes)
 {
-  const uint64_t whole = n / kLaneElements, lane = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (lane < whole)
-  {
-    uint32_t e[4 * W], b[4 * W], pl[W][4];
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      load16(in + lane * (kLaneElements * W) + 16 * k, e + 4 * k);
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      load16(base + lane * (kLaneElements * W) + 16 * k, b + 4 * k);
-#pragma unroll
-    for (uint32_t k = 0; k < 4 * W; k++)
-      e[k] ^= b[k];
-    split16<W>(e, pl);
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      store16(planes.p[p] + lane * kLaneElements, pl[p]);
-  }
-  const uint32_t tail = (uint32_t)(n % kLaneElements);
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x < tail)
-  {
-    const uint64_t i = whole * kLaneElements + threadIdx.x;
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      planes.p[p][i] = in[i * W + p] ^ base[i * W + p];
-  }
+  split_lanes<W, true>(in, base, planes.p, n, n / kLaneElements, (uint64_t)blockIdx.x * kThreads + threadIdx.x, blockIdx.x == gridDim.x - 1);
 }
 
-// (base and out may be the same buffer: not __restrict__)
+// merge_lanes<W, true> written out, like k_planes_merge<W> (hsrans_planes.hip) and for its reason: as a call to it the kernel reads all its
+// arguments on entry and at W = 4 took 85.6 against 84.6 µs on 128 MiB (medians of 96, three rounds; 124.7 against 123.9 in place).
+// (base and out may be the same buffer: not __restrict__, all base loads of a lane before its first store, the tail's base byte read and
+// then written — merge_lanes' order, planes_shuffle.h)
 template <uint32_t W>
 __global__ __launch_bounds__(kThreads) void k_planes_merge_delta(PlanePtrs planes, const uint8_t *base, uint64_t n, uint8_t *out)
 {
@@ -96,35 +74,7 @@ __device__ __forceinline__ void split_task(const PlanesDeltaBatchMember *m)
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     planes[p] = uni_ptr(m->m.plane[p]);
-  if (t.lane < t.whole)
-  {
-    uint32_t e[4 * W], pl[W][4];
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      load16(in + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
-    if constexpr (kDelta)
-    {
-      uint32_t b[4 * W];
-#pragma unroll
-      for (uint32_t k = 0; k < W; k++)
-        load16(base + t.lane * (kLaneElements * W) + 16 * k, b + 4 * k);
-#pragma unroll
-      for (uint32_t k = 0; k < 4 * W; k++)
-        e[k] ^= b[k];
-    }
-    split16<W>(e, pl);
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      store16(planes[p] + t.lane * kLaneElements, pl[p]);
-  }
-  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
-  if (t.last && threadIdx.x < tail)
-  {
-    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      planes[p][i] = kDelta ? in[i * W + p] ^ base[i * W + p] : in[i * W + p];
-  }
+  split_lanes<W, kDelta>(in, base, planes, t.n, t.whole, t.lane, t.last);
 }
 
 template <uint32_t W, bool kDelta>
@@ -137,40 +87,7 @@ __device__ __forceinline__ void merge_task(const PlanesDeltaBatchMember *m)
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     planes[p] = uni_ptr(m->m.plane[p]);
-  if (t.lane < t.whole)
-  {
-    uint32_t e[4 * W], pl[W][4];
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-      load16(planes[p] + t.lane * kLaneElements, pl[p]);
-    if constexpr (kDelta)
-    {
-      uint32_t b[4 * W];
-#pragma unroll
-      for (uint32_t k = 0; k < W; k++)
-        load16(base + t.lane * (kLaneElements * W) + 16 * k, b + 4 * k);
-      merge16<W>(pl, e);
-#pragma unroll
-      for (uint32_t k = 0; k < 4 * W; k++)
-        e[k] ^= b[k];
-    }
-    else
-      merge16<W>(pl, e);
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++)
-      store16(out + t.lane * (kLaneElements * W) + 16 * k, e + 4 * k);
-  }
-  const uint32_t tail = (uint32_t)(t.n % kLaneElements);
-  if (t.last && threadIdx.x < tail)
-  {
-    const uint64_t i = t.whole * kLaneElements + threadIdx.x;
-#pragma unroll
-    for (uint32_t p = 0; p < W; p++)
-    {
-      const uint8_t b = kDelta ? base[i * W + p] : 0;
-      out[i * W + p] = planes[p][i] ^ b;
-    }
-  }
+  merge_lanes<W, kDelta>(planes, base, out, t.n, t.whole, t.lane, t.last);
 }
 
 template <bool kDelta>
@@ -215,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_delta_batch(const Pla
     merge_member<false>(m, W);
 }
 
-// ---- element ranges of one frame: k_planes_merge_ranges' body (hsrans_planes_gather.hip) in its own copy ----
+// ---- element ranges of one frame: k_planes_merge_ranges' body (hsrans_planes_gather.hip) with the base, its fifth copy (planes_shuffle.h) ----
 static_assert(kThreads * kLaneElements == kPlanesGatherTaskElements, "one lane per 16-element block of a task");
 
 // grid: one workgroup per task; xbase: the whole base tensor, in the frame's element coordinates (never the output: __restrict__)
@@ -264,54 +181,28 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_ranges_delta(PlanePtr
       out[(base + i) * W + p] = src[p][i] ^ bsrc[i * W + p];
 }
 
-bool launch_ok(uint32_t W, const void *elements, const void *base, uint64_t n, const PlanePtrs &planes)
-{
-  return planes_ptrs_ok(W, planes) && elements != nullptr && ((uintptr_t)elements & 15) == 0 && base != nullptr && ((uintptr_t)base & 15) == 0 && n != 0 &&
-         n <= kPlanesMaxElements;
-}
-uint32_t grid_of(uint64_t n)
-{
-  const uint64_t whole = n / kLaneElements;
-  return (uint32_t)std::max<uint64_t>((whole + kThreads - 1) / kThreads, 1);
-}
-bool table_ok(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks)
-{
-  return d_members != nullptr && ((uintptr_t)d_members & 7) == 0 && count != 0 && n_tasks >= count && n_tasks <= 0x7FFFFFFFu;
-}
 } // namespace
 
-hipError_t launch_planes_split_delta(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
+// ---- the launches alone: launch_planes_split, _merge and _merge_ranges check the arguments and form the grid, and come here with a base ----
+void planes_delta_split_kernel(uint32_t W, uint32_t grid, const uint8_t *in, const uint8_t *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
 {
-  if (!launch_ok(W, in, base, n, planes))
-    return hipErrorInvalidValue;
-  const uint8_t *src = (const uint8_t *)in, *b = (const uint8_t *)base;
-  if (W == 2)
-    k_planes_split_delta<2><<<grid_of(n), kThreads, 0, stream>>>(src, b, n, planes);
-  else if (W == 4)
-    k_planes_split_delta<4><<<grid_of(n), kThreads, 0, stream>>>(src, b, n, planes);
-  else
-    k_planes_split_delta<8><<<grid_of(n), kThreads, 0, stream>>>(src, b, n, planes);
-  return hipGetLastError();
+  planes_with_width(W, [&](auto w) { k_planes_split_delta<w()><<<grid, kThreads, 0, stream>>>(in, base, n, planes); });
 }
 
-hipError_t launch_planes_merge_delta(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream)
+void planes_delta_merge_kernel(uint32_t W, uint32_t grid, const PlanePtrs &planes, const uint8_t *base, uint64_t n, uint8_t *out, hipStream_t stream)
 {
-  if (!launch_ok(W, out, base, n, planes))
-    return hipErrorInvalidValue;
-  const uint8_t *b = (const uint8_t *)base;
-  uint8_t *dst = (uint8_t *)out;
-  if (W == 2)
-    k_planes_merge_delta<2><<<grid_of(n), kThreads, 0, stream>>>(planes, b, n, dst);
-  else if (W == 4)
-    k_planes_merge_delta<4><<<grid_of(n), kThreads, 0, stream>>>(planes, b, n, dst);
-  else
-    k_planes_merge_delta<8><<<grid_of(n), kThreads, 0, stream>>>(planes, b, n, dst);
-  return hipGetLastError();
+  planes_with_width(W, [&](auto w) { k_planes_merge_delta<w()><<<grid, kThreads, 0, stream>>>(planes, base, n, out); });
+}
+
+void planes_delta_merge_ranges_kernel(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const uint8_t *base,
+                                      uint8_t *out, hipStream_t stream)
+{
+  planes_with_width(W, [&](auto w) { k_planes_merge_ranges_delta<w()><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, base, out); });
 }
 
 hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
 {
-  if (!table_ok(d_members, count, n_tasks))
+  if (!planes_table_ok(d_members, count, n_tasks))
     return hipErrorInvalidValue;
   k_planes_split_delta_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
   return hipGetLastError();
@@ -319,26 +210,9 @@ hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_membe
 
 hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream)
 {
-  if (!table_ok(d_members, count, n_tasks))
+  if (!planes_table_ok(d_members, count, n_tasks))
     return hipErrorInvalidValue;
   k_planes_merge_delta_batch<<<n_tasks, kThreads, 0, stream>>>(d_members, count);
-  return hipGetLastError();
-}
-
-hipError_t launch_planes_merge_ranges_delta(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
-                                            void *out, hipStream_t stream)
-{
-  if (!planes_ptrs_ok(W, planes) || out == nullptr || ((uintptr_t)out & 15) != 0 || base == nullptr || ((uintptr_t)base & 15) != 0 || d_tasks == nullptr ||
-      ((uintptr_t)d_tasks & 7) != 0 || n_tasks == 0 || n_tasks > 0x7FFFFFFFu || (work_mask >> W) != 0)
-    return hipErrorInvalidValue;
-  const uint8_t *b = (const uint8_t *)base;
-  uint8_t *dst = (uint8_t *)out;
-  if (W == 2)
-    k_planes_merge_ranges_delta<2><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, b, dst);
-  else if (W == 4)
-    k_planes_merge_ranges_delta<4><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, b, dst);
-  else
-    k_planes_merge_ranges_delta<8><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, b, dst);
   return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // frames in ONE launch (hsrans_decode_device_planes_gather_batch).  One workgroup serves one task — at most 4096 elements of one row, cut on
 // the source's 16-element grid (hsrans_planes_gather_batch_tasks) — and reads, the same on every lane and on scalar loads, its 48-byte task
 // and then the record of the task's member: the element size W, which planes were coded and where the stored planes lie.  It branches once
-// on W into the body of k_planes_merge_ranges<W>, of which this unit has its own copy (planes_shuffle.h says why): a lane per aligned
+// on W into the body of k_planes_merge_ranges<W>, of which this unit has its own copy (one of five; planes_shuffle.h's note on what is NOT shared says why): a lane per aligned
 // 16-element block, each plane one 16-byte load — a coded plane from the call's workspace (work_pos + p * plane_step: the row's sub-slot of plane p), a stored plane straight
 // from its frame (the record's address + src) —, merge16, and W 16-byte stores where the output address allows it, element-wide stores
 // otherwise; heads and tails move byte by byte, so nothing outside a range is read from a stored plane or written.  2-, 4- and 8-byte

@@ -232,12 +232,7 @@ hipError_t launch_planes_merge_indirect(uint32_t W, const PlanePtrs &planes, uin
     return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   (void)hipGetLastError();
-  if (W == 2)
-    k_planes_merge_indirect<2><<<grid, kThreads, 0, stream>>>(planes, work_mask, d_ranges, d_header, d_first_task, d_base, dst);
-  else if (W == 4)
-    k_planes_merge_indirect<4><<<grid, kThreads, 0, stream>>>(planes, work_mask, d_ranges, d_header, d_first_task, d_base, dst);
-  else
-    k_planes_merge_indirect<8><<<grid, kThreads, 0, stream>>>(planes, work_mask, d_ranges, d_header, d_first_task, d_base, dst);
+  planes_with_width(W, [&](auto w) { k_planes_merge_indirect<w()><<<grid, kThreads, 0, stream>>>(planes, work_mask, d_ranges, d_header, d_first_task, d_base, dst); });
   return hipGetLastError();
 }
 

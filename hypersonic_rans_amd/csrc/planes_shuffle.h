@@ -1,16 +1,30 @@
 // planes_shuffle.h — what the byte-plane kernels (the eight hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
-// bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  And the small
+// bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  The small
 // helpers of the table- and list-driven kernels: wave-uniform values as scalars, the global-address cast, the element-wide stores of a
 // block whose output is not 16-byte aligned, the search of a task's row in a prefix of task counts, and the walk of the member tables
-// (a workgroup's member and its place in it).  Device code only; every function
-// is inlined into the kernel that calls it.  Everything is in hsrans::planes_detail; every unit says `using namespace`.
+// (a workgroup's member and its place in it).  And, at the end, what one lane of a WHOLE-TENSOR split or merge does, with or without a
+// base: split_lanes and merge_lanes, the body of the one-tensor kernels (hsrans_planes.hip, hsrans_planes_delta.hip) and of the
+// table-driven ones (hsrans_planes_batch.hip, hsrans_planes_delta.hip).  Device code only; every function is inlined into the kernel that
+// calls it.  Everything is in hsrans::planes_detail; every unit says `using namespace`.
+// (Sharing the whole-tensor body left the five table-driven kernels instruction for instruction as they were.  The one-tensor kernels
+// came out 3 to 5 instructions shorter: with the plane pointers handed over by reference the compiler reads the kernel arguments once, on
+// entry, where each kernel's own copy read them block by block and again in the tail; loads, v_perm_b32, XORs and stores are the same, in
+// the same order.  The tail flag as a callable evaluated in the tail, or the pointers in a local array, gave the same kind of difference,
+// never identity.  The six splits took it at no cost.  The merges did not, on 128 MiB against the written-out form: k_planes_merge<W> as
+// a call to merge_lanes<W, false> 58.5 against 57.1 µs at W = 2, 66.8 against 66.2 at 4, 75.0 against 74.0 at 8 (medians of 48, three
+// rounds; k_planes_merge<8> at 52 VGPRs for 51), k_planes_merge_delta<4> as a call to merge_lanes<4, true> 85.6 against 84.6 µs (medians of
+// 96, three rounds; W = 2 and 8 level).  So k_planes_merge<W> and k_planes_merge_delta<W> keep merge_lanes written out, each in its unit:
+// what merge_lanes says about the in-place order holds for k_planes_merge_delta's copy word for word.)
 //
 // What is NOT here: the range merges' 16-element block body — from the full-block path (load16 per plane, merge16, the 16-byte or
-// element-wide stores) down to the byte-by-byte head and tail — which each of the four hsrans_planes_gather*.hip units writes out.  As one
-// __forceinline__ template (plane pointers by array reference or in a by-value struct, the output pointer __restrict__ or not) it changed
-// the kernels' code every time: with __restrict__ k_planes_merge_ranges<2> went from 20 to 38 VGPRs and its unit from 513 to 688
-// instructions, and in all four forms the stores to a misaligned destination were merged differently in every kernel (fewer dwordx4, more
-// dword and dwordx2).  Nobody has measured what that costs, so the four copies stay until somebody does.
+// element-wide stores) down to the byte-by-byte head and tail — which each of the four hsrans_planes_gather*.hip units writes out, and
+// k_planes_merge_ranges_delta (hsrans_planes_delta.hip) a fifth time with the base.  As one __forceinline__ template (plane pointers by
+// array reference or in a by-value struct, the output pointer __restrict__ or not) it changed the kernels' code every time: with
+// __restrict__ k_planes_merge_ranges<2> went from 20 to 38 VGPRs and its unit from 513 to 688 instructions, and in all four forms the
+// stores to a misaligned destination were merged differently in every kernel (fewer dwordx4, more dword and dwordx2).  Tried once more
+// with the base as `merge_block<W, kDelta>(src[W], bsrc, out, base, lo, hi)` across all five: every kernel but k_planes_merge_indirect<2>
+// and the cut changed, and grew — k_planes_merge_ranges<4> 162 -> 170 instructions, k_planes_merge_ranges_delta<4> 196 -> 211,
+// k_planes_merge_ranges_batch 783 -> 788.  Nobody has measured what that costs, so the five copies stay until somebody does.
 #ifndef HSRANS_PLANES_SHUFFLE_H
 #define HSRANS_PLANES_SHUFFLE_H
 
@@ -185,6 +199,94 @@ __device__ __forceinline__ void merge16(const uint32_t pl[W][4], uint32_t *e)
         for (uint32_t i = 0; i < 4; i++)
           e[(4 * j + i) * DW + h] = o[i];
       }
+  }
+}
+
+// ---- the whole-tensor split and merge: what one lane does, for every kernel that moves whole tensors (k_planes_split / _merge<W> of
+// hsrans_planes.hip, their delta forms and the table-driven kernels of hsrans_planes_batch.hip and hsrans_planes_delta.hip) ----
+// n: the tensor's elements; whole: n / 16; lane: the lane's index among the tensor's lanes (its 16 elements are 16 lane ..); last: this is
+// the tensor's last workgroup, whose first n % 16 lanes move the tail byte by byte, one element each.  planes: anything indexed 0 .. W - 1.
+// kDelta: what enters the planes is in ^ base, what leaves them is XORed with the base again; without it `base` is not looked at.
+template <uint32_t W, bool kDelta, typename Planes>
+__device__ __forceinline__ void split_lanes(const uint8_t *in, const uint8_t *base, const Planes &planes, uint64_t n, uint64_t whole, uint64_t lane, bool last)
+{
+  if (lane < whole)
+  {
+    uint32_t e[4 * W], pl[W][4];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      load16(in + lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+    if constexpr (kDelta)
+    {
+      uint32_t b[4 * W];
+#pragma unroll
+      for (uint32_t k = 0; k < W; k++)
+        load16(base + lane * (kLaneElements * W) + 16 * k, b + 4 * k);
+#pragma unroll
+      for (uint32_t k = 0; k < 4 * W; k++)
+        e[k] ^= b[k];
+    }
+    split16<W>(e, pl);
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      store16(planes[p] + lane * kLaneElements, pl[p]);
+  }
+  const uint32_t tail = (uint32_t)(n % kLaneElements);
+  if (last && threadIdx.x < tail)
+  {
+    const uint64_t i = whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+    {
+      if constexpr (kDelta)
+        planes[p][i] = in[i * W + p] ^ base[i * W + p];
+      else
+        planes[p][i] = in[i * W + p];
+    }
+  }
+}
+
+// IN PLACE: with kDelta `out` may be `base` itself, so neither is __restrict__ here or in a kernel that passes them.  What makes that safe
+// is the order below and nothing else: a lane loads ALL of its base bytes before its first store, in the tail the base byte is read and
+// then the output byte is written, and no lane reads a byte another lane writes.
+template <uint32_t W, bool kDelta, typename Planes>
+__device__ __forceinline__ void merge_lanes(const Planes &planes, const uint8_t *base, uint8_t *out, uint64_t n, uint64_t whole, uint64_t lane, bool last)
+{
+  if (lane < whole)
+  {
+    uint32_t e[4 * W], b[kDelta ? 4 * W : 1], pl[W][4];
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+      load16(planes[p] + lane * kLaneElements, pl[p]);
+    if constexpr (kDelta)
+    {
+#pragma unroll
+      for (uint32_t k = 0; k < W; k++)
+        load16(base + lane * (kLaneElements * W) + 16 * k, b + 4 * k);
+    }
+    merge16<W>(pl, e);
+    if constexpr (kDelta)
+    {
+#pragma unroll
+      for (uint32_t k = 0; k < 4 * W; k++)
+        e[k] ^= b[k];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++)
+      store16(out + lane * (kLaneElements * W) + 16 * k, e + 4 * k);
+  }
+  const uint32_t tail = (uint32_t)(n % kLaneElements);
+  if (last && threadIdx.x < tail)
+  {
+    const uint64_t i = whole * kLaneElements + threadIdx.x;
+#pragma unroll
+    for (uint32_t p = 0; p < W; p++)
+    {
+      uint8_t b = 0;
+      if constexpr (kDelta)
+        b = base[i * W + p];
+      out[i * W + p] = planes[p][i] ^ b;
+    }
   }
 }
 } // namespace planes_detail

@@ -342,6 +342,11 @@ SIGNATURES = {
     "hsrans_encode_device_planes_delta_batch": (_i, [_vp, _P(PlanesMember), _vp, _vp, _u32, _vp, _sz, _vp, _P(_vp), _P(PlanesBatchStats)]),
     "hsrans_decode_device_planes_delta_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "hsrans_decode_device_planes_gather_delta": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_decode_device_planes_gather_indirect_delta": (_i, [_vp, _vp, _vp, _vp, _u32, _u64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_planes_base_set_create": (_i, [_vp, _vp, _vp, _vp, _P(_vp)]),
+    "hsrans_planes_base_set_destroy": (None, [_vp]),
+    "hsrans_decode_device_planes_gather_batch_delta": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_decode_device_planes_gather_batch_indirect_delta": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsrans_index_build": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz]),
     "hsrans_index_build_at": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]),
     "hsrans_hpipe_create": (_i, [_vp, _vp, _sz, _u32, _P(_vp)]),

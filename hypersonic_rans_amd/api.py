@@ -764,6 +764,15 @@ class PlanesGatherSet(_Handle):
         return _as_dict(info)
 
 
+class PlanesBaseSet(_Handle):
+    """hsrans_planes_base_set: one base (or None) per member of a PlanesGatherSet, for decode_device_planes_gather_batch_delta and
+    decode_device_planes_gather_batch_indirect_delta (Context.make_planes_base_set).  Close it before its gather set."""
+    _destroy = "hsrans_planes_base_set_destroy"
+
+    def __init__(self, ctx: "Context", handle, pgs: PlanesGatherSet, bases):
+        self.ctx, self.handle, self.pgs, self.bases = ctx, handle, pgs, list(bases)  # (keeps the gather set and the bases alive)
+
+
 class GatherSet(_Handle):
     """hsrans_gather_set: K device plans bound to their compressed streams (Context.make_gather_set / Context.decode_device_gather_batch)."""
     _destroy = "hsrans_gather_set_destroy"
@@ -1624,21 +1633,37 @@ class Context(_Handle):
         planes_gather_indirect_workspace_bytes(itemsize, max_count) bytes that no other call in flight uses; allocated here when None.
         Returns the workspace.  Raises HsransError (``.code``) for what the host can check; rows or a count only the device can refuse leave
         ``out_tensor`` and ``d_work`` untouched and are reported by ``planes_gather_refused(pg)`` (5)."""
+        return self._planes_gather_indirect("decode_device_planes_gather_indirect", pg, d_ranges, (), out_tensor, d_work, count, max_count, max_elements, workspace, stream)
+
+    def decode_device_planes_gather_indirect_delta(self, pg: PlanesGather, d_ranges: torch.Tensor, base: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                                   count: torch.Tensor | None = None, max_count: int | None = None, max_elements: int | None = None,
+                                                   workspace: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """hsrans_decode_device_planes_gather_indirect_delta: ``decode_device_planes_gather_indirect`` of a delta frame — element
+        ``offset + i`` of the frame XORed with element ``offset + i`` of ``base``, the WHOLE base tensor (the frame's element size and
+        element count), which may not share memory with any other buffer of the call.  Everything else — arguments, workspaces, launches,
+        what is returned, raised and reported — is ``decode_device_planes_gather_indirect``'s."""
+        desc = pg.planes.desc
+        if not (isinstance(base, torch.Tensor) and base.is_cuda and base.is_contiguous() and base.element_size() == desc.elem_size and base.numel() == desc.elements):
+            raise HsransError("decode_device_planes_gather_indirect_delta: the base is a contiguous CUDA tensor of the frame's element size and element count", code=2)
+        return self._planes_gather_indirect("decode_device_planes_gather_indirect_delta", pg, d_ranges, (base.data_ptr(), base.numel() * base.element_size()), out_tensor,
+                                            d_work, count, max_count, max_elements, workspace, stream)
+
+    def _planes_gather_indirect(self, entry: str, pg, d_ranges, based: tuple, out_tensor, d_work, count, max_count, max_elements, workspace, stream):
+        """decode_device_planes_gather_indirect and its delta form: ``based`` is empty, or the base's (pointer, bytes)"""
         W = pg.planes.desc.elem_size
         if not out_tensor.is_contiguous():
-            raise HsransError("decode_device_planes_gather_indirect takes a contiguous output tensor")
+            raise HsransError(f"{entry} takes a contiguous output tensor")
         if out_tensor.element_size() != W:
-            raise HsransError(f"decode_device_planes_gather_indirect: the frame's elements are {W} bytes, the output tensor's {out_tensor.element_size()}")
+            raise HsransError(f"{entry}: the frame's elements are {W} bytes, the output tensor's {out_tensor.element_size()}")
         if d_work.dtype != torch.uint8:
-            raise HsransError("decode_device_planes_gather_indirect takes a uint8 workspace tensor")
+            raise HsransError(f"{entry} takes a uint8 workspace tensor")
         max_count, workspace = _indirect_args(d_ranges, 3, count, max_count, workspace, lambda n: planes_gather_indirect_workspace_bytes(W, n), out_tensor.device,
                                               stream)
         if max_elements is None:
             max_elements = max(0, d_work.numel() // W // 256 * 256 - 30 * max_count)
-        _check(self.L.hsrans_decode_device_planes_gather_indirect(self.handle, pg.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count,
-                                                                  max_elements, out_tensor.data_ptr(), out_tensor.numel() * W, d_work.data_ptr(), d_work.numel(),
-                                                                  workspace.data_ptr(), workspace.numel(), _stream(stream, out_tensor.device)),
-               "hsrans_decode_device_planes_gather_indirect")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, pg.handle, d_ranges.data_ptr(), None if count is None else count.data_ptr(), max_count, max_elements, *based,
+                                                   out_tensor.data_ptr(), out_tensor.numel() * W, d_work.data_ptr(), d_work.numel(), workspace.data_ptr(),
+                                                   workspace.numel(), _stream(stream, out_tensor.device)), "hsrans_" + entry)
         return workspace
 
     def planes_gather_refused(self, pg: PlanesGather, stream: torch.cuda.Stream | None = None) -> int:
@@ -1672,14 +1697,51 @@ class Context(_Handle):
         planes_gather_batch_workspace_bytes(largest itemsize, N, total elements) bytes.  Asynchronous on ``stream`` (default: torch's current
         stream); ``rows`` is read before the call returns.  Raises HsransError (``.code``: 2 a bad row, destination or buffer; nothing was
         launched)."""
+        self._planes_gather_batch("decode_device_planes_gather_batch", pgs, (), rows, out_tensor, d_work, stream)
+
+    def make_planes_base_set(self, pgs: PlanesGatherSet, bases) -> PlanesBaseSet:
+        """hsrans_planes_base_set_create: ``bases[k]`` is the base member k of ``pgs`` is decoded against by the delta forms of the batch
+        gathers — a contiguous CUDA tensor of the member's element size and element count — or None for a member that goes as it is.  One
+        tensor may serve many members.  The object keeps ``pgs`` and the tensors alive.  Raises HsransError (``.code``: 2 a bad argument,
+        among them a base that shares memory with a member's frame)."""
+        bases = list(bases)
+        descs = pgs.pset.descs
+        K = len(descs)
+        if len(bases) != K:
+            raise HsransError(f"make_planes_base_set: one base (or None) per member: {K}", code=2)
+        for b, d in zip(bases, descs):
+            if b is not None and not (isinstance(b, torch.Tensor) and b.is_cuda and b.is_contiguous() and b.element_size() == d.elem_size and b.numel() == d.elements):
+                raise HsransError("make_planes_base_set: a base is a contiguous CUDA tensor of its member's element size and element count, or None", code=2)
+        h = _vp()
+        _check(self.L.hsrans_planes_base_set_create(self.handle, pgs.handle, (_vp * max(K, 1))(*[None if b is None else b.data_ptr() for b in bases]),
+                                                    (_sz * max(K, 1))(*[0 if b is None else b.numel() * b.element_size() for b in bases]), ctypes.byref(h)),
+               "hsrans_planes_base_set_create")
+        return PlanesBaseSet(self, h, pgs, bases)
+
+    @staticmethod
+    def _base_set_args(entry: str, pgs: PlanesGatherSet, base_set) -> tuple:
+        if not (isinstance(base_set, PlanesBaseSet) and base_set.pgs is pgs and base_set.handle):
+            raise HsransError(f"{entry}: a base set made for this gather set (make_planes_base_set)", code=2)
+        return (base_set.handle,)
+
+    def decode_device_planes_gather_batch_delta(self, pgs: PlanesGatherSet, base_set: PlanesBaseSet, rows, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                                stream: torch.cuda.Stream | None = None):
+        """hsrans_decode_device_planes_gather_batch_delta: ``decode_device_planes_gather_batch`` with every row of member k XORed with the
+        same elements of ``base_set``'s base k (None there: the row as it is).  No base may share memory with ``out_tensor`` or ``d_work``.
+        Everything else is ``decode_device_planes_gather_batch``'s."""
+        self._planes_gather_batch("decode_device_planes_gather_batch_delta", pgs, self._base_set_args("decode_device_planes_gather_batch_delta", pgs, base_set), rows,
+                                  out_tensor, d_work, stream)
+
+    def _planes_gather_batch(self, entry: str, pgs, based: tuple, rows, out_tensor, d_work, stream):
+        """decode_device_planes_gather_batch and its delta form: ``based`` is empty, or holds the base set's handle"""
         if not out_tensor.is_contiguous():
-            raise HsransError("decode_device_planes_gather_batch takes a contiguous output tensor")
+            raise HsransError(f"{entry} takes a contiguous output tensor")
         if d_work.dtype != torch.uint8:
-            raise HsransError("decode_device_planes_gather_batch takes a uint8 workspace tensor")
+            raise HsransError(f"{entry} takes a uint8 workspace tensor")
         arr = _member_ranges_array(rows)
-        _check(self.L.hsrans_decode_device_planes_gather_batch(self.handle, pgs.handle, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
-                                                               out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
-                                                               _stream(stream, out_tensor.device)), "hsrans_decode_device_planes_gather_batch")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, pgs.handle, *based, _p(arr) if arr.size else None, arr.shape[0], out_tensor.data_ptr(),
+                                                   out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(), _stream(stream, out_tensor.device)),
+               "hsrans_" + entry)
 
     def decode_device_planes_gather_batch_indirect(self, pgs: PlanesGatherSet, d_rows: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
                                                    count: torch.Tensor | None = None, max_count: int | None = None, workspace: torch.Tensor | None = None,
@@ -1694,16 +1756,30 @@ class Context(_Handle):
         other call in flight uses; allocated here when None.  Returns the workspace.  Raises HsransError (``.code``) for what the host can
         check; rows or a count only the device can refuse leave ``out_tensor`` and ``d_work`` untouched and are reported by
         ``planes_gather_set_refused(pgs)`` (5)."""
+        return self._planes_gather_batch_indirect("decode_device_planes_gather_batch_indirect", pgs, (), d_rows, out_tensor, d_work, count, max_count, workspace, stream)
+
+    def decode_device_planes_gather_batch_indirect_delta(self, pgs: PlanesGatherSet, base_set: PlanesBaseSet, d_rows: torch.Tensor, out_tensor: torch.Tensor,
+                                                         d_work: torch.Tensor, count: torch.Tensor | None = None, max_count: int | None = None,
+                                                         workspace: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """hsrans_decode_device_planes_gather_batch_indirect_delta: ``decode_device_planes_gather_batch_indirect`` with every row of
+        member k XORed with the same elements of ``base_set``'s base k (None there: the row as it is).  No base may share memory with any
+        other buffer of the call.  Everything else — arguments, workspaces, launches, capturability, what is returned, raised and reported
+        — is ``decode_device_planes_gather_batch_indirect``'s."""
+        return self._planes_gather_batch_indirect("decode_device_planes_gather_batch_indirect_delta", pgs,
+                                                  self._base_set_args("decode_device_planes_gather_batch_indirect_delta", pgs, base_set), d_rows, out_tensor, d_work, count,
+                                                  max_count, workspace, stream)
+
+    def _planes_gather_batch_indirect(self, entry: str, pgs, based: tuple, d_rows, out_tensor, d_work, count, max_count, workspace, stream):
+        """decode_device_planes_gather_batch_indirect and its delta form: ``based`` is empty, or holds the base set's handle"""
         if not out_tensor.is_contiguous():
-            raise HsransError("decode_device_planes_gather_batch_indirect takes a contiguous output tensor")
+            raise HsransError(f"{entry} takes a contiguous output tensor")
         if d_work.dtype != torch.uint8:
-            raise HsransError("decode_device_planes_gather_batch_indirect takes a uint8 workspace tensor")
+            raise HsransError(f"{entry} takes a uint8 workspace tensor")
         max_count, workspace = _indirect_args(d_rows, 4, count, max_count, workspace,
                                               lambda n: planes_gather_batch_indirect_workspace_bytes(pgs.coded, pgs.max_itemsize, n), out_tensor.device, stream)
-        _check(self.L.hsrans_decode_device_planes_gather_batch_indirect(self.handle, pgs.handle, d_rows.data_ptr(), None if count is None else count.data_ptr(), max_count,
-                                                                        out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(),
-                                                                        d_work.numel(), workspace.data_ptr(), workspace.numel(), _stream(stream, out_tensor.device)),
-               "hsrans_decode_device_planes_gather_batch_indirect")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, pgs.handle, *based, d_rows.data_ptr(), None if count is None else count.data_ptr(), max_count,
+                                                   out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                   workspace.data_ptr(), workspace.numel(), _stream(stream, out_tensor.device)), "hsrans_" + entry)
         return workspace
 
     def planes_gather_set_refused(self, pgs: PlanesGatherSet, stream: torch.cuda.Stream | None = None) -> int:

@@ -5,7 +5,9 @@
 // goes through the context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).  The call's body is
 // planes_gather_flow (hsrans_internal.h), which hsrans_capi_planes_delta.cpp runs with a base: then the merge is k_planes_merge_ranges_delta.
 // hsrans_decode_device_planes_gather_indirect, at the end of the file: the same for ranges in device memory — the device cuts
-// (hsrans_planes_gather_indirect.hip), by the rules of planes_cut.h that the host's cut above uses too.
+// (hsrans_planes_gather_indirect.hip), by the rules of planes_cut.h that the host's cut above uses too; its body is
+// planes_gather_indirect_flow, which hsrans_decode_device_planes_gather_indirect_delta runs with a base: then the merge is
+// k_planes_merge_indirect_delta (hsrans_planes_gather_delta.hip).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -379,9 +381,11 @@ catch (...)
   return HSRANS_E_HIP;
 }
 
-extern "C" int hsrans_decode_device_planes_gather_indirect(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count, uint32_t max_count,
-                                                           uint64_t max_elements, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
-                                                           size_t workspace_bytes, void *hip_stream)
+// the entry's whole body, and with a base hsrans_decode_device_planes_gather_indirect_delta's: the base joins the overlap rule as a read span
+// that keeps clear of the frame, the ranges and the count word too, and the merge is k_planes_merge_indirect_delta on its own grid
+int planes_gather_indirect_flow(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count, uint32_t max_count, uint64_t max_elements,
+                                const PlanesBase &base, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes,
+                                void *hip_stream)
 try
 {
   if (ctx == nullptr || pg == nullptr || pg->ctx != ctx || d_ranges == nullptr || d_workspace == nullptr || !aligned16(d_out) || !aligned16(d_work))
@@ -401,7 +405,12 @@ try
                             span_of(d_workspace, workspace_bytes, true)};
     if (d_count != nullptr)
       spans.push_back(span_of(d_count, sizeof(uint32_t), false));
-    if (!spans_disjoint(spans))
+    std::vector<Span> inputs; // (what a base may not meet although it is only read, as the base is)
+    if (base.on)
+      inputs = spans;
+    if (!planes_base_spans(base, W, (size_t)desc.elements, nullptr, 0, &spans) || !spans_disjoint(spans))
+      return HSRANS_E_ARG;
+    if (base.on && spans_meet({span_of(base.d, base.bytes, false)}, inputs)) // (the written ones among them have been refused above)
       return HSRANS_E_ARG;
   }
   if (max_count == 0)
@@ -449,7 +458,11 @@ try
   // ---- the merge behind it ----
   uint32_t work_mask = 0;
   const PlanePtrs src = merge_sources(desc, pg->d_frame, d_work, stride, &work_mask);
-  if (launch_planes_merge_indirect(W, src, work_mask, cp.ranges, cp.header, cp.first_task, cp.base, shape.merge_grid, d_out, s) != hipSuccess)
+  const hipError_t merged =
+      base.on ? launch_planes_merge_indirect_delta(W, src, work_mask, cp.ranges, cp.header, cp.first_task, cp.base, base.d,
+                                                   planes_merge_indirect_delta_grid(ctx->geom.num_cus, W, max_count, stride), d_out, s)
+              : launch_planes_merge_indirect(W, src, work_mask, cp.ranges, cp.header, cp.first_task, cp.base, shape.merge_grid, d_out, s);
+  if (merged != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -459,6 +472,22 @@ try
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather_indirect(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count, uint32_t max_count,
+                                                           uint64_t max_elements, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
+                                                           size_t workspace_bytes, void *hip_stream)
+{
+  return planes_gather_indirect_flow(ctx, pg, d_ranges, d_count, max_count, max_elements, PlanesBase{}, d_out, out_capacity, d_work, work_bytes, d_workspace, workspace_bytes,
+                                     hip_stream);
+}
+
+extern "C" int hsrans_decode_device_planes_gather_indirect_delta(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count,
+                                                                 uint32_t max_count, uint64_t max_elements, const void *d_base, size_t base_bytes, void *d_out,
+                                                                 size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+  return planes_gather_indirect_flow(ctx, pg, d_ranges, d_count, max_count, max_elements, PlanesBase{true, d_base, base_bytes}, d_out, out_capacity, d_work, work_bytes,
+                                     d_workspace, workspace_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_gather_refused(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream)

@@ -7,6 +7,9 @@
 // context's task buffer as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
 // hsrans_decode_device_planes_gather_batch_indirect, at the end of the file: the same for rows in device memory — the device cuts
 // (hsrans_planes_gather_batch_indirect.hip), by the rules of planes_cut_batch.h that measure_rows above uses too.
+// Both calls' bodies are flows (planes_gather_batch_flow, planes_gather_batch_indirect_flow: hsrans_internal.h) that take an optional
+// hsrans_planes_base_set, defined here too: with one they are hsrans_decode_device_planes_gather_batch_delta and
+// hsrans_decode_device_planes_gather_batch_indirect_delta, whose merges XOR each member's base in (hsrans_planes_gather_delta.hip).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -227,8 +230,95 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
   return HSRANS_E_HIP;
 }
 
-extern "C" int hsrans_decode_device_planes_gather_batch(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *ranges, uint32_t count, void *d_out,
-                                                        size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+// ---------------------------------------------------------------------------------------------------------------
+// hsrans_planes_base_set: one base per member of a gather set, for the delta forms of the two calls below.  The addresses are uploaded
+// once, one uint64 per member (0: the member goes as it is), so that the device-rows call stays kernels and nothing else; the host keeps
+// the bases' spans for the calls' overlap checks.  Neither the gather set nor the planes set is touched.
+// ---------------------------------------------------------------------------------------------------------------
+struct hsrans_planes_base_set
+{
+  hsrans_ctx *ctx = nullptr;
+  hsrans_planes_gather_set *pgs = nullptr;
+  std::vector<Span> bases;      // the members' bases over base_bytes, those that are set: read spans
+  uint64_t *d_xbases = nullptr; // [members]: what the delta merges read
+};
+
+extern "C" void hsrans_planes_base_set_destroy(hsrans_planes_base_set *bs)
+{
+  if (bs == nullptr)
+    return;
+  if (bs->d_xbases != nullptr)
+    (void)hipFree(bs->d_xbases);
+  delete bs;
+}
+
+extern "C" int hsrans_planes_base_set_create(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const void *const *d_bases, const size_t *base_bytes, hsrans_planes_base_set **out)
+try
+{
+  if (out == nullptr)
+    return HSRANS_E_ARG;
+  *out = nullptr;
+  if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx || d_bases == nullptr || base_bytes == nullptr)
+    return HSRANS_E_ARG;
+  const uint32_t members = (uint32_t)pgs->widths.size();
+  std::vector<Span> bases;
+  std::vector<uint64_t> table(std::max(members, 1u), 0);
+  for (uint32_t k = 0; k < members; k++)
+  {
+    if (d_bases[k] == nullptr)
+      continue;
+    std::vector<Span> one;
+    if (!planes_base_spans(PlanesBase{true, d_bases[k], base_bytes[k]}, pgs->widths[k], (size_t)pgs->elements[k], nullptr, 0, &one))
+      return HSRANS_E_ARG;
+    bases.push_back(one[0]);
+    table[k] = (uint64_t)(uintptr_t)d_bases[k];
+  }
+  {
+    std::vector<Span> frames(pgs->frames); // (a base over compressed bytes is never a meaningful call, reads though both are)
+    if (spans_meet(bases, frames))
+      return HSRANS_E_ARG;
+  }
+  hsrans_planes_base_set *bs = new (std::nothrow) hsrans_planes_base_set;
+  if (bs == nullptr)
+    return HSRANS_E_HIP;
+  bs->ctx = ctx;
+  bs->pgs = pgs;
+  bs->bases.swap(bases);
+  const size_t bytes = table.size() * sizeof(uint64_t);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&bs->d_xbases, bytes) != hipSuccess ||
+      hipMemcpy(bs->d_xbases, table.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    hsrans_planes_base_set_destroy(bs);
+    return HSRANS_E_HIP;
+  }
+  *out = bs;
+  return HSRANS_OK;
+}
+catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI)
+{
+  return HSRANS_E_HIP;
+}
+
+namespace
+{
+// A call's base set: none (the plain call), or one of this gather set and context.  Its bases join *spans as reads — they may coincide with
+// one another and may not meet anything the call writes (spans_disjoint, the caller's next step)
+bool base_set_spans(const hsrans_ctx *ctx, const hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs, std::vector<Span> *spans)
+{
+  if (bs == nullptr)
+    return true;
+  if (bs->ctx != ctx || bs->pgs != pgs)
+    return false;
+  spans->insert(spans->end(), bs->bases.begin(), bs->bases.end());
+  return true;
+}
+} // namespace
+
+// hsrans_decode_device_planes_gather_batch's whole body, and with a base set hsrans_decode_device_planes_gather_batch_delta's: the bases join
+// the overlap rule and the merge is k_planes_merge_ranges_batch_delta (hsrans_planes_gather_delta.hip)
+int planes_gather_batch_flow(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs, const hsrans_member_range *ranges, uint32_t count, void *d_out,
+                             size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
 try
 {
   if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx || !aligned16(d_out) || !aligned16(d_work) || (ranges == nullptr && count > 0) || wraps(d_out, out_capacity) ||
@@ -254,7 +344,7 @@ try
     spans.assign(pgs->frames.begin(), pgs->frames.end());
     spans.push_back(span_of(d_out, out_capacity, true));
     spans.push_back(span_of(d_work, work_bytes, true));
-    if (!spans_disjoint(spans))
+    if (!base_set_spans(ctx, pgs, bs, &spans) || !spans_disjoint(spans))
       return HSRANS_E_ARG;
   }
   {
@@ -306,7 +396,11 @@ try
         cut_rows(ranges, count, pgs->widths.data(), [&](const hsrans_planes_gather_batch_task &t) { *list++ = t; });
         return HSRANS_OK;
       },
-      [&](const uint8_t *dev) { return launch_planes_merge_ranges_batch((const PlanesGatherBatchTask *)dev, (uint32_t)cut.tasks, pgs->d_members, d_work, d_out, s); });
+      [&](const uint8_t *dev) {
+        const PlanesGatherBatchTask *tasks = (const PlanesGatherBatchTask *)dev;
+        return bs != nullptr ? launch_planes_merge_ranges_batch_delta(tasks, (uint32_t)cut.tasks, pgs->d_members, bs->d_xbases, d_work, d_out, s)
+                             : launch_planes_merge_ranges_batch(tasks, (uint32_t)cut.tasks, pgs->d_members, d_work, d_out, s);
+      });
   if (rc != HSRANS_OK)
     return rc;
   pgs->last.rows = (uint32_t)cut.rows;
@@ -317,6 +411,19 @@ try
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather_batch(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *ranges, uint32_t count, void *d_out,
+                                                        size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_gather_batch_flow(ctx, pgs, nullptr, ranges, count, d_out, out_capacity, d_work, work_bytes, hip_stream);
+}
+
+// (a NULL base set is refused here: the flow reads one as "no bases")
+extern "C" int hsrans_decode_device_planes_gather_batch_delta(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs, const hsrans_member_range *ranges,
+                                                              uint32_t count, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return bs == nullptr ? HSRANS_E_ARG : planes_gather_batch_flow(ctx, pgs, bs, ranges, count, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_gather_set_status(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream, int *member_status)
@@ -418,9 +525,11 @@ catch (...)
   return HSRANS_E_HIP;
 }
 
-extern "C" int hsrans_decode_device_planes_gather_batch_indirect(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *d_ranges, const uint32_t *d_count,
-                                                                 uint32_t max_count, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
-                                                                 size_t workspace_bytes, void *hip_stream)
+// the entry's whole body, and with a base set hsrans_decode_device_planes_gather_batch_indirect_delta's: the bases join the overlap rule,
+// keep clear of the rows and the count word too, and the merge is k_planes_merge_batch_indirect_delta on its own grid
+int planes_gather_batch_indirect_flow(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs, const hsrans_member_range *d_ranges,
+                                      const uint32_t *d_count, uint32_t max_count, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
+                                      size_t workspace_bytes, void *hip_stream)
 try
 {
   if (ctx == nullptr || pgs == nullptr || pgs->ctx != ctx || d_ranges == nullptr || d_workspace == nullptr || !aligned16(d_out) || !aligned16(d_work))
@@ -440,8 +549,14 @@ try
     spans.push_back(span_of(d_out, out_capacity, true));
     spans.push_back(span_of(d_work, work_bytes, true));
     spans.push_back(span_of(d_workspace, workspace_bytes, true));
-    if (!spans_disjoint(spans))
+    if (!base_set_spans(ctx, pgs, bs, &spans) || !spans_disjoint(spans))
       return HSRANS_E_ARG;
+    if (bs != nullptr) // (the rows and the count word are only read, as a base is, and a base over them is no more meaningful than one over a frame)
+    {
+      std::vector<Span> inputs{span_of(d_ranges, (size_t)max_count * sizeof(hsrans_member_range), false), span_of(d_count, d_count != nullptr ? sizeof(uint32_t) : 0, false)};
+      if (spans_meet(bs->bases, inputs))
+        return HSRANS_E_ARG;
+    }
   }
   if (max_count == 0)
     return HSRANS_OK;
@@ -485,7 +600,11 @@ try
   }
 
   // ---- the merge behind it ----
-  if (launch_planes_merge_batch_indirect(cp.ranges, cp.header, cp.first_task, cp.base, pgs->d_members, d_work, d_out, shape.merge_grid, s) != hipSuccess)
+  const hipError_t merged =
+      bs != nullptr ? launch_planes_merge_batch_indirect_delta(cp.ranges, cp.header, cp.first_task, cp.base, pgs->d_members, bs->d_xbases, d_work, d_out,
+                                                               planes_merge_batch_indirect_delta_grid(ctx->geom.num_cus, pgs->min_width, max_count, work_bytes), s)
+                    : launch_planes_merge_batch_indirect(cp.ranges, cp.header, cp.first_task, cp.base, pgs->d_members, d_work, d_out, shape.merge_grid, s);
+  if (merged != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -495,6 +614,24 @@ try
 catch (...)
 {
   return HSRANS_E_HIP;
+}
+
+extern "C" int hsrans_decode_device_planes_gather_batch_indirect(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_member_range *d_ranges, const uint32_t *d_count,
+                                                                 uint32_t max_count, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace,
+                                                                 size_t workspace_bytes, void *hip_stream)
+{
+  return planes_gather_batch_indirect_flow(ctx, pgs, nullptr, d_ranges, d_count, max_count, d_out, out_capacity, d_work, work_bytes, d_workspace, workspace_bytes, hip_stream);
+}
+
+// (a NULL base set is refused here: the flow reads one as "no bases")
+extern "C" int hsrans_decode_device_planes_gather_batch_indirect_delta(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs,
+                                                                       const hsrans_member_range *d_ranges, const uint32_t *d_count, uint32_t max_count, void *d_out,
+                                                                       size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes,
+                                                                       void *hip_stream)
+{
+  return bs == nullptr ? HSRANS_E_ARG
+                       : planes_gather_batch_indirect_flow(ctx, pgs, bs, d_ranges, d_count, max_count, d_out, out_capacity, d_work, work_bytes, d_workspace, workspace_bytes,
+                                                           hip_stream);
 }
 
 extern "C" int hsrans_planes_gather_set_refused(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, void *hip_stream)

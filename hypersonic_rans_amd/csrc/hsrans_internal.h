@@ -342,6 +342,22 @@ __attribute__((visibility("hidden"))) int planes_decode_batch_flow(hsrans_ctx *c
 struct hsrans_planes_gather;
 __attribute__((visibility("hidden"))) int planes_gather_flow(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const PlanesBase &base,
                                                              void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+// hsrans_decode_device_planes_gather_indirect (hsrans_capi_planes_gather.cpp): with a base the merge is k_planes_merge_indirect_delta
+// (hsrans_planes_gather_delta.hip), and the base keeps clear of the frame, the ranges and the count word as well as of what is written
+__attribute__((visibility("hidden"))) int planes_gather_indirect_flow(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count,
+                                                                      uint32_t max_count, uint64_t max_elements, const PlanesBase &base, void *d_out, size_t out_capacity,
+                                                                      void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+// hsrans_decode_device_planes_gather_batch and _gather_batch_indirect (hsrans_capi_planes_gather_batch.cpp); bs: null (the plain call), or a
+// base set of this gather set and context, one base per member: the merges are then the table-driven ones of hsrans_planes_gather_delta.hip
+struct hsrans_planes_gather_set;
+struct hsrans_planes_base_set;
+__attribute__((visibility("hidden"))) int planes_gather_batch_flow(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs,
+                                                                   const hsrans_member_range *ranges, uint32_t count, void *d_out, size_t out_capacity, void *d_work,
+                                                                   size_t work_bytes, void *hip_stream);
+__attribute__((visibility("hidden"))) int planes_gather_batch_indirect_flow(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs,
+                                                                            const hsrans_member_range *d_ranges, const uint32_t *d_count, uint32_t max_count, void *d_out,
+                                                                            size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes,
+                                                                            void *hip_stream);
 
 // (Re)fills a device plan from a validated host plan blob; one launch of a filled device plan (hsrans_dplan.cpp)
 int dplan_fill(hsrans_dplan *d, const uint8_t *plan, size_t plan_size, const PlanHeader &h, hipStream_t s);

@@ -1,7 +1,8 @@
 // hsrans_planes.h — the streaming kernels of the byte-plane layer: elements of W bytes split into W byte planes and planes interleaved back
 // into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
 // hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip, and with those rows in device memory
-// hsrans_planes_gather_batch_indirect.hip), and the forms of the split and the merges that XOR a base in (hsrans_planes_delta.hip).
+// hsrans_planes_gather_batch_indirect.hip), and the forms of the split and the merges that XOR a base in (hsrans_planes_delta.hip;
+// of the last three range merges hsrans_planes_gather_delta.hip).
 // plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
@@ -268,6 +269,24 @@ struct PlanesDeltaBatchMember
 };
 hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+
+// ---- the gathers that undo a delta while they fetch (hsrans_decode_device_planes_gather_indirect_delta, _gather_batch_delta,
+// _gather_batch_indirect_delta): hsrans_planes_gather_delta.hip.  Each launcher is its plain twin's above — the same arguments, the same
+// checks — with the base: xbase, the whole base tensor in the frame's element coordinates (set and 16-byte aligned), or d_xbases, one base
+// address per member of d_members in device memory, 0 for a member that goes as it is (the table set and 8-byte aligned; its entries are
+// the caller's to check: 16-byte aligned, elem_size * elements bytes, clear of everything the call writes).  Output element
+// (element + dst_delta) is XORed with base element `element`.  The cuts, task lists and control workspaces are the plain calls'. ----
+// the workgroups of the two indirect merges: the plain grid functions' formula for the most tasks, capped by what the device holds of the
+// DELTA kernels, which keep more registers than the plain ones
+uint32_t planes_merge_indirect_delta_grid(uint32_t num_cus, uint32_t W, uint32_t max_count, uint64_t stride);
+uint32_t planes_merge_batch_indirect_delta_grid(uint32_t num_cus, uint32_t min_W, uint32_t max_count, uint64_t work_bytes);
+hipError_t launch_planes_merge_indirect_delta(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesRange *d_ranges, const uint32_t *d_header,
+                                              const uint32_t *d_first_task, const uint64_t *d_base, const void *xbase, uint32_t grid, void *out, hipStream_t stream);
+hipError_t launch_planes_merge_ranges_batch_delta(const PlanesGatherBatchTask *d_tasks, uint32_t n_tasks, const PlanesGatherBatchMember *d_members, const uint64_t *d_xbases,
+                                                  const void *work, void *out, hipStream_t stream);
+hipError_t launch_planes_merge_batch_indirect_delta(const PlanesSetRow *d_ranges, const uint32_t *d_header, const uint32_t *d_first_task, const uint64_t *d_base,
+                                                    const PlanesGatherBatchMember *d_members, const uint64_t *d_xbases, const void *work, void *out, uint32_t grid,
+                                                    hipStream_t stream);
 
 } // namespace hsrans
 

@@ -1,4 +1,4 @@
-// planes_shuffle.h — what the byte-plane kernels (the eight hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
+// planes_shuffle.h — what the byte-plane kernels (the nine hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
 // bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  The small
 // helpers of the table- and list-driven kernels: wave-uniform values as scalars, the global-address cast, the element-wide stores of a
 // block whose output is not 16-byte aligned, the search of a task's row in a prefix of task counts, and the walk of the member tables
@@ -25,6 +25,7 @@
 // with the base as `merge_block<W, kDelta>(src[W], bsrc, out, base, lo, hi)` across all five: every kernel but k_planes_merge_indirect<2>
 // and the cut changed, and grew — k_planes_merge_ranges<4> 162 -> 170 instructions, k_planes_merge_ranges_delta<4> 196 -> 211,
 // k_planes_merge_ranges_batch 783 -> 788.  Nobody has measured what that costs, so the five copies stay until somebody does.
+// A sixth, merge_block<W, kDelta>, lives in hsrans_planes_gather_delta.hip and is shared by that unit's three kernels, which were new with it.
 #ifndef HSRANS_PLANES_SHUFFLE_H
 #define HSRANS_PLANES_SHUFFLE_H
 

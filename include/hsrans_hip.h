@@ -1374,6 +1374,42 @@ int hsrans_decode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_set *
  * of their own elements only.  No aliasing: the base may not meet d_out or d_work. */
 int hsrans_decode_device_planes_gather_delta(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const void *d_base, size_t base_bytes,
                                              void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+/* The other three gathers of a delta frame: each is its plain twin with the XOR in its merge kernel (hsrans_planes_gather_delta.hip)
+ * — the same launch count, both workspaces and their size functions, the same *_info / *_indirect_info answers, device-side checks,
+ * refused word, *_status, return codes, asynchrony, and for the two indirect forms the same "kernels and nothing else" (capturable).
+ * d_work receives exactly what the plain twin writes there: the residue's plane bytes; the XOR happens behind them.  Every row of
+ * d_out receives byte for byte what hsrans_decode_device_planes_gather_delta on that member's own gather object writes for the same
+ * range against the same base.  (The merge's grid of an indirect delta call is sized from the delta kernel's registers and may be
+ * smaller than the merge_grid that *_indirect_info reports for the plain call; the workgroups stride over the tasks either way.)
+ * Added refusals, all HSRANS_E_ARG with nothing queued or written: a NULL, misaligned or short base; a base set that is NULL or of
+ * another gather set or context; a base that meets d_out over out_capacity, d_work over work_bytes or d_workspace; a base that meets
+ * a frame; and — reads though they are, like a frame — a base that meets d_ranges[0 .. max_count) or d_count.  Bases may coincide
+ * with one another.  No gather allows in-place or any other aliasing. */
+/* ranges in device memory, one frame: hsrans_decode_device_planes_gather_indirect with d_base, the WHOLE base tensor in the frame's
+ * element coordinates (base_bytes >= elem_size * the frame's elements), read when the launches run */
+int hsrans_decode_device_planes_gather_indirect_delta(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *d_ranges, const uint32_t *d_count, uint32_t max_count,
+                                                      uint64_t max_elements, const void *d_base, size_t base_bytes, void *d_out, size_t out_capacity, void *d_work,
+                                                      size_t work_bytes, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* member m of a gather set is decoded against d_bases[m] over base_bytes[m], or as it is where d_bases[m] is NULL (base_bytes[m] is
+ * then ignored).  The addresses are uploaded here, once and synchronously, one uint64_t per member, so that the device-rows call
+ * stays kernels and nothing else; the object keeps a host copy for the calls' overlap checks.  It is bound to ONE gather set, which
+ * may have several base sets and is not modified (nor is its planes set); destroy it before that set; the bases must outlive it.
+ * HSRANS_E_ARG, with nothing allocated: a NULL argument, a set of another context, a non-NULL base that is not 16-byte aligned,
+ * base_bytes[m] < elem_size(m) * elements(m), a base that meets any member's frame.  Bases may coincide with each other.  All entries
+ * NULL is valid: the calls then write what the plain calls write. */
+typedef struct hsrans_planes_base_set hsrans_planes_base_set;
+int hsrans_planes_base_set_create(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const void *const *d_bases /* [members], entries may be NULL */,
+                                  const size_t *base_bytes /* [members] */, hsrans_planes_base_set **out);
+void hsrans_planes_base_set_destroy(hsrans_planes_base_set *bs); /* NULL: nothing */
+/* rows of many frames on the host: hsrans_decode_device_planes_gather_batch with member m's rows XORed with its base; the task list
+ * goes through the context's task buffer like the plain call's; hsrans_planes_gather_set_info answers as for the plain call */
+int hsrans_decode_device_planes_gather_batch_delta(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs, const hsrans_member_range *ranges,
+                                                   uint32_t count, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+/* rows of many frames in device memory: hsrans_decode_device_planes_gather_batch_indirect likewise; a refusal on the device is
+ * reported by hsrans_planes_gather_set_refused as the plain call's is */
+int hsrans_decode_device_planes_gather_batch_indirect_delta(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs,
+                                                            const hsrans_member_range *d_ranges, const uint32_t *d_count, uint32_t max_count, void *d_out,
+                                                            size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

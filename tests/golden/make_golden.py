@@ -9,7 +9,8 @@
                       and the reference's capacity() values
   reference_calls.json.gz  what the reference returned for every call the tests make of the ``ref`` fixture (oracle_lib.RecordedRef):
                       tests/test_oracle_vs_ref.py run against the compiled reference, plus the reference-encoded streams of the
-                      GPU tests (tests/test_gpu_parity.py), enumerated below.  `make_golden.py --calls` writes this file only.
+                      GPU tests (tests/test_gpu_parity.py) and the reference's histograms of the designed blocks of
+                      tests/test_normalise_host.py, enumerated below.  `make_golden.py --calls` writes this file only.
 """
 import hashlib
 import json
@@ -119,6 +120,14 @@ def _gpu_test_encodes(rec: RecordedRef):
                 rec.encode(RAW, S, bits, src[:n])
 
 
+def _normalise_hists(rec: RecordedRef):
+    """The ref.make_hist calls of tests/test_normalise_host.py: the boundary and extreme blocks of tests/normalise_inputs.py."""
+    import normalise_inputs
+
+    for bits, block in normalise_inputs.reference_subset():
+        rec.make_hist(block, bits)
+
+
 def record_calls():
     """reference_calls.json.gz: the CPU differential tests run against the compiled reference, then the GPU tests' encodes; every
     entry is then replayed once (the product encoder must reproduce each recorded stream)."""
@@ -129,8 +138,10 @@ def record_calls():
         rec = RecordedRef(live=Ref())
         rec.calls = RecordedRef(path=path).calls
     _gpu_test_encodes(rec)
+    _normalise_hists(rec)
     rec.save()
     _gpu_test_encodes(RecordedRef())
+    _normalise_hists(RecordedRef())
     subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py")], cwd=ROOT)
     print("wrote", len(rec.calls), "reference calls;", os.path.getsize(rec.path), "bytes")
 

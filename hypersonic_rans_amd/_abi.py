@@ -347,6 +347,15 @@ SIGNATURES = {
     "hsrans_planes_base_set_destroy": (None, [_vp]),
     "hsrans_decode_device_planes_gather_batch_delta": (_i, [_vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]),
     "hsrans_decode_device_planes_gather_batch_indirect_delta": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_planes_split_diff": (_i, [_u32, _vp, _vp, _sz, _vp]),
+    "hsrans_planes_merge_diff": (_i, [_u32, _vp, _vp, _sz, _vp]),
+    "hsrans_planes_split_diff_device": (_i, [_vp, _u32, _vp, _vp, _sz, _vp, _vp]),
+    "hsrans_planes_merge_diff_device": (_i, [_vp, _u32, _vp, _vp, _sz, _vp, _vp]),
+    "hsrans_encode_device_planes_diff": (_sz, [_vp, _u32, _i, _u32, _vp, _vp, _sz, _sz, _vp, _sz, _u32, _u32, _u32, _vp, _sz, _vp, _P(PlanesDesc), _P(_vp)]),
+    "hsrans_decode_device_planes_diff": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsrans_encode_device_planes_diff_batch": (_i, [_vp, _P(PlanesMember), _vp, _vp, _u32, _vp, _sz, _vp, _P(_vp), _P(PlanesBatchStats)]),
+    "hsrans_decode_device_planes_diff_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hsrans_decode_device_planes_gather_diff": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsrans_index_build": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _u32, _vp, _sz]),
     "hsrans_index_build_at": (_sz, [_vp, _i, _i, _u32, _vp, _sz, _vp, _sz, _vp, _sz]),
     "hsrans_hpipe_create": (_i, [_vp, _vp, _sz, _u32, _P(_vp)]),

@@ -548,26 +548,49 @@ def planes_merge(planes, itemsize: int) -> np.ndarray:
 def planes_split_delta(array, base) -> list:
     """hsrans_planes_split_delta on the host: the byte planes of ``array ^ base`` (two contiguous arrays of the same item size and
     count, XORed byte by byte), as ``planes_split`` gives them."""
-    a, b = np.ascontiguousarray(array), np.ascontiguousarray(base)
-    if a.itemsize != b.itemsize or a.size != b.size:
-        raise HsransError("planes_split_delta: the base has the array's item size and count", code=2)
-    planes = [np.empty(a.size, np.uint8) for _ in range(a.itemsize)]
-    ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
-    _check(load_library().hsrans_planes_split_delta(a.itemsize, a.ctypes.data if a.size else ptrs, b.ctypes.data if b.size else ptrs, a.size, ptrs),
-           "hsrans_planes_split_delta")
-    return planes
+    return _planes_split_against("planes_split_delta", array, base)
 
 
 def planes_merge_delta(planes, base) -> np.ndarray:
     """hsrans_planes_merge_delta on the host: the planes interleaved back into items' bytes and XORed with ``base``'s (a contiguous
     array of ``len(planes)``-byte items, as many as a plane has bytes): uint8."""
+    return _planes_merge_against("planes_merge_delta", planes, base)
+
+
+def planes_split_diff(array, base) -> list:
+    """hsrans_planes_split_diff on the host: the byte planes of z, the zigzag of ``array - base`` (two contiguous arrays of the same
+    item size and count, their items read as little-endian unsigned integers, the difference modulo 2^(8 * itemsize) with its sign
+    folded into the lowest bit), as ``planes_split`` gives them."""
+    return _planes_split_against("planes_split_diff", array, base)
+
+
+def planes_merge_diff(planes, base) -> np.ndarray:
+    """hsrans_planes_merge_diff on the host: the planes interleaved back into z, the zigzag undone and the difference added to
+    ``base``'s items (a contiguous array of ``len(planes)``-byte items, as many as a plane has bytes): the items' bytes, uint8."""
+    return _planes_merge_against("planes_merge_diff", planes, base)
+
+
+def _planes_split_against(entry: str, array, base) -> list:
+    """planes_split_delta and planes_split_diff: the host split of ``array`` against ``base`` by hsrans_<entry>"""
+    a, b = np.ascontiguousarray(array), np.ascontiguousarray(base)
+    if a.itemsize != b.itemsize or a.size != b.size:
+        raise HsransError(f"{entry}: the base has the array's item size and count", code=2)
+    planes = [np.empty(a.size, np.uint8) for _ in range(a.itemsize)]
+    ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
+    _check(getattr(load_library(), "hsrans_" + entry)(a.itemsize, a.ctypes.data if a.size else ptrs, b.ctypes.data if b.size else ptrs, a.size, ptrs),
+           "hsrans_" + entry)
+    return planes
+
+
+def _planes_merge_against(entry: str, planes, base) -> np.ndarray:
+    """planes_merge_delta and planes_merge_diff: the host merge of ``planes`` against ``base`` by hsrans_<entry>"""
     planes, b = [_u8(p) for p in planes], np.ascontiguousarray(base)
     if len(planes) != b.itemsize or any(p.size != b.size for p in planes):
-        raise HsransError("planes_merge_delta: one plane per byte of the base's items, each of the base's item count", code=2)
+        raise HsransError(f"{entry}: one plane per byte of the base's items, each of the base's item count", code=2)
     out = np.empty(b.size * b.itemsize, np.uint8)
     ptrs = (_vp * max(len(planes), 1))(*[p.ctypes.data for p in planes])
-    _check(load_library().hsrans_planes_merge_delta(b.itemsize, ptrs, b.ctypes.data if b.size else ptrs, b.size, out.ctypes.data if out.size else ptrs),
-           "hsrans_planes_merge_delta")
+    _check(getattr(load_library(), "hsrans_" + entry)(b.itemsize, ptrs, b.ctypes.data if b.size else ptrs, b.size, out.ctypes.data if out.size else ptrs),
+           "hsrans_" + entry)
     return out
 
 
@@ -1359,7 +1382,7 @@ class Context(_Handle):
         return self._encode_planes("encode_device_planes", tensor, None, d_frame, d_work, states, bits, block_size, index_interval, store_incompressible, want_plans, stream)
 
     def _encode_planes(self, entry, tensor, based, d_frame, d_work, states, bits, block_size, index_interval, store_incompressible, want_plans, stream):
-        """encode_device_planes (``based`` None) and encode_device_planes_delta (the base's pointer and bytes): one tensor into its frame"""
+        """encode_device_planes (``based`` None) and encode_device_planes_delta / _diff (the base's pointer and bytes): one tensor into its frame"""
         if not tensor.is_contiguous():
             raise HsransError(f"{entry} takes a contiguous tensor")
         W = tensor.element_size()
@@ -1368,7 +1391,7 @@ class Context(_Handle):
         head = (self.handle, W, states, bits, tensor.data_ptr())
         tail = (tensor.numel(), d_frame.data_ptr(), d_frame.numel(), block_size, index_interval, PLANES_STORE_INCOMPRESSIBLE if store_incompressible else 0,
                 d_work.data_ptr(), d_work.numel(), _stream(stream, tensor.device), ctypes.byref(desc), handles if want_plans else None)
-        n = self.L.hsrans_encode_device_planes(*head, *tail) if based is None else self.L.hsrans_encode_device_planes_delta(*head, *based, *tail)
+        n = self.L.hsrans_encode_device_planes(*head, *tail) if based is None else getattr(self.L, "hsrans_" + entry)(*head, *based, *tail)
         if n == 0:
             raise HsransError(f"hsrans_{entry} failed")
         plans = [DevicePlan(self, _vp(handles[p])) if want_plans and handles[p] else None for p in range(W)]
@@ -1411,7 +1434,7 @@ class Context(_Handle):
                                          block_size=block_size, index_interval=index_interval, store_incompressible=store_incompressible)
 
     def _encode_planes_batch(self, entry, tensors, bases, d_frames, d_work, options, want_plans, stream, stats, **defaults) -> list:
-        """encode_device_planes_batch (``bases`` None) and encode_device_planes_delta_batch: many tensors into their frames"""
+        """encode_device_planes_batch (``bases`` None) and encode_device_planes_delta_batch / _diff_batch: many tensors into their frames"""
         tensors, d_frames = list(tensors), list(d_frames)
         K = len(tensors)
         if len(d_frames) != K or (options is not None and len(options) != K) or (bases is not None and len(bases) != K):
@@ -1437,7 +1460,7 @@ class Context(_Handle):
             rc = self.L.hsrans_encode_device_planes_batch(self.handle, arr, *tail)
         else:
             based = [_base_of(entry, b, t, optional=True) for b, t in zip(bases, tensors)]
-            rc = self.L.hsrans_encode_device_planes_delta_batch(self.handle, arr, (_vp * max(K, 1))(*[p for p, _ in based]), (_sz * max(K, 1))(*[n for _, n in based]), *tail)
+            rc = getattr(self.L, "hsrans_" + entry)(self.handle, arr, (_vp * max(K, 1))(*[p for p, _ in based]), (_sz * max(K, 1))(*[n for _, n in based]), *tail)
         if stats is not None:
             stats.update(_as_dict(st))
         if rc != 0:
@@ -1486,18 +1509,25 @@ class Context(_Handle):
     def planes_split_delta_device(self, tensor: torch.Tensor, base: torch.Tensor, d_planes, elements: int | None = None, stream: torch.cuda.Stream | None = None):
         """hsrans_planes_split_delta_device: ``planes_split_device`` of ``tensor ^ base`` (``base``: a contiguous CUDA tensor of the
         tensor's element size and element count).  Asynchronous on ``stream``."""
+        self._planes_split_against("planes_split_delta_device", tensor, base, d_planes, elements, stream)
+
+    def _planes_split_against(self, entry, tensor, base, d_planes, elements, stream):
+        """planes_split_delta_device and planes_split_diff_device"""
         W = tensor.element_size()
-        _check(self.L.hsrans_planes_split_delta_device(self.handle, W, tensor.data_ptr(), _base_of("planes_split_delta_device", base, tensor)[0],
-                                                       tensor.numel() if elements is None else elements, self._plane_ptrs(d_planes, W), _stream(stream, tensor.device)),
-               "hsrans_planes_split_delta_device")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, W, tensor.data_ptr(), _base_of(entry, base, tensor)[0], tensor.numel() if elements is None else elements,
+                                                  self._plane_ptrs(d_planes, W), _stream(stream, tensor.device)), "hsrans_" + entry)
 
     def planes_merge_delta_device(self, d_planes, base: torch.Tensor, out_tensor: torch.Tensor, elements: int | None = None, stream: torch.cuda.Stream | None = None):
         """hsrans_planes_merge_delta_device: ``d_planes`` interleaved and XORed with ``base`` into ``out_tensor``, which may be ``base``
         itself (the delta applied in place).  Asynchronous on ``stream``."""
+        self._planes_merge_against("planes_merge_delta_device", d_planes, base, out_tensor, elements, stream)
+
+    def _planes_merge_against(self, entry, d_planes, base, out_tensor, elements, stream):
+        """planes_merge_delta_device and planes_merge_diff_device"""
         W = out_tensor.element_size()
-        _check(self.L.hsrans_planes_merge_delta_device(self.handle, W, self._plane_ptrs(d_planes, W), _base_of("planes_merge_delta_device", base, out_tensor)[0],
-                                                       out_tensor.numel() if elements is None else elements, out_tensor.data_ptr(), _stream(stream, out_tensor.device)),
-               "hsrans_planes_merge_delta_device")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, W, self._plane_ptrs(d_planes, W), _base_of(entry, base, out_tensor)[0],
+                                                  out_tensor.numel() if elements is None else elements, out_tensor.data_ptr(), _stream(stream, out_tensor.device)),
+               "hsrans_" + entry)
 
     def encode_device_planes_delta(self, tensor: torch.Tensor, base: torch.Tensor, d_frame: torch.Tensor, d_work: torch.Tensor, states: int = 64, bits: int = 11,
                                    block_size: int = 1 << 16, index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True,
@@ -1512,12 +1542,15 @@ class Context(_Handle):
                                    stream: torch.cuda.Stream | None = None, frame_length: int | None = None):
         """hsrans_decode_device_planes_delta: the frame at ``d_frame``, XORed with ``base``, into ``out_tensor`` — which may be ``base``
         itself: the delta is then applied in place.  Launches and workspace as ``decode_device_planes``.  Asynchronous on ``stream``."""
+        self._decode_planes_against("decode_device_planes_delta", planes, d_frame, base, out_tensor, d_work, stream, frame_length)
+
+    def _decode_planes_against(self, entry, planes, d_frame, base, out_tensor, d_work, stream, frame_length):
+        """decode_device_planes_delta and decode_device_planes_diff"""
         if not out_tensor.is_contiguous():
-            raise HsransError("decode_device_planes_delta takes a contiguous output tensor")
-        _check(self.L.hsrans_decode_device_planes_delta(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
-                                                        *_base_of("decode_device_planes_delta", base, out_tensor), out_tensor.data_ptr(),
-                                                        out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(), _stream(stream, d_frame.device)),
-               "hsrans_decode_device_planes_delta")
+            raise HsransError(f"{entry} takes a contiguous output tensor")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, planes.handle, d_frame.data_ptr(), d_frame.numel() if frame_length is None else frame_length,
+                                                  *_base_of(entry, base, out_tensor), out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(),
+                                                  d_work.data_ptr(), d_work.numel(), _stream(stream, d_frame.device)), "hsrans_" + entry)
 
     def encode_device_planes_delta_batch(self, tensors, bases, d_frames, d_work: torch.Tensor, states: int = 64, bits: int = 11, block_size: int = 1 << 16,
                                          index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True, options=None,
@@ -1531,38 +1564,93 @@ class Context(_Handle):
     def decode_device_planes_delta_batch(self, pset: PlanesSet, d_frames, bases, out_tensors, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """hsrans_decode_device_planes_delta_batch: ``decode_device_planes_batch`` with member k XORed with ``bases[k]`` (None: as it
         is); ``out_tensors[k]`` may be ``bases[k]`` itself.  Asynchronous on ``stream`` (default: torch's current stream)."""
+        self._decode_planes_batch_against("decode_device_planes_delta_batch", pset, d_frames, bases, out_tensors, d_work, stream)
+
+    def _decode_planes_batch_against(self, entry, pset, d_frames, bases, out_tensors, d_work, stream):
+        """decode_device_planes_delta_batch and decode_device_planes_diff_batch"""
         d_frames, bases, out_tensors = list(d_frames), list(bases), list(out_tensors)
         K = len(pset.descs)
         if len(d_frames) != K or len(out_tensors) != K or len(bases) != K:
-            raise HsransError(f"decode_device_planes_delta_batch: one frame, one base (or None) and one output per member: {K}")
+            raise HsransError(f"{entry}: one frame, one base (or None) and one output per member: {K}")
         if any(not t.is_contiguous() for t in out_tensors):
-            raise HsransError("decode_device_planes_delta_batch takes contiguous output tensors")
+            raise HsransError(f"{entry} takes contiguous output tensors")
         frames, frame_lengths = _tensor_arrays(d_frames)
         outs, out_caps = _tensor_arrays(out_tensors, [t.numel() * t.element_size() for t in out_tensors])
-        based = [_base_of("decode_device_planes_delta_batch", b, t, optional=True) for b, t in zip(bases, out_tensors)]
-        _check(self.L.hsrans_decode_device_planes_delta_batch(self.handle, pset.handle, frames, frame_lengths, (_vp * K)(*[p for p, _ in based]),
-                                                              (_sz * K)(*[n for _, n in based]), outs, out_caps, d_work.data_ptr(), d_work.numel(),
-                                                              _stream(stream, d_work.device)), "hsrans_decode_device_planes_delta_batch")
+        based = [_base_of(entry, b, t, optional=True) for b, t in zip(bases, out_tensors)]
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, pset.handle, frames, frame_lengths, (_vp * K)(*[p for p, _ in based]), (_sz * K)(*[n for _, n in based]),
+                                                  outs, out_caps, d_work.data_ptr(), d_work.numel(), _stream(stream, d_work.device)), "hsrans_" + entry)
 
     def decode_device_planes_gather_delta(self, pg: PlanesGather, ranges, base: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
                                           stream: torch.cuda.Stream | None = None):
         """hsrans_decode_device_planes_gather_delta: ``decode_device_planes_gather`` of a delta frame — element ``offset + i`` of the
         frame XORed with element ``offset + i`` of ``base``, the WHOLE base tensor (the frame's element size and element count), which may
         not share memory with ``out_tensor`` or ``d_work``.  Asynchronous on ``stream``; ``ranges`` is read before the call returns."""
+        self._planes_gather_against("decode_device_planes_gather_delta", pg, ranges, base, out_tensor, d_work, stream)
+
+    def _planes_gather_against(self, entry, pg, ranges, base, out_tensor, d_work, stream):
+        """decode_device_planes_gather_delta and decode_device_planes_gather_diff"""
         desc = pg.planes.desc
         if not out_tensor.is_contiguous():
-            raise HsransError("decode_device_planes_gather_delta takes a contiguous output tensor")
+            raise HsransError(f"{entry} takes a contiguous output tensor")
         if out_tensor.element_size() != desc.elem_size:
-            raise HsransError(f"decode_device_planes_gather_delta: the frame's elements are {desc.elem_size} bytes, the output tensor's {out_tensor.element_size()}")
+            raise HsransError(f"{entry}: the frame's elements are {desc.elem_size} bytes, the output tensor's {out_tensor.element_size()}")
         if d_work.dtype != torch.uint8:
-            raise HsransError("decode_device_planes_gather_delta takes a uint8 workspace tensor")
+            raise HsransError(f"{entry} takes a uint8 workspace tensor")
         if not (isinstance(base, torch.Tensor) and base.is_cuda and base.is_contiguous() and base.element_size() == desc.elem_size and base.numel() == desc.elements):
-            raise HsransError("decode_device_planes_gather_delta: the base is a contiguous CUDA tensor of the frame's element size and element count", code=2)
+            raise HsransError(f"{entry}: the base is a contiguous CUDA tensor of the frame's element size and element count", code=2)
         arr = _ranges_array(ranges)
-        _check(self.L.hsrans_decode_device_planes_gather_delta(self.handle, pg.handle, _p(arr) if arr.size else None, arr.shape[0], base.data_ptr(),
-                                                               base.numel() * base.element_size(), out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(),
-                                                               d_work.data_ptr(), d_work.numel(), _stream(stream, out_tensor.device)),
-               "hsrans_decode_device_planes_gather_delta")
+        _check(getattr(self.L, "hsrans_" + entry)(self.handle, pg.handle, _p(arr) if arr.size else None, arr.shape[0], base.data_ptr(), base.numel() * base.element_size(),
+                                                  out_tensor.data_ptr(), out_tensor.numel() * out_tensor.element_size(), d_work.data_ptr(), d_work.numel(),
+                                                  _stream(stream, out_tensor.device)), "hsrans_" + entry)
+
+    # -- tensors coded against a base as a zigzag difference: a diff frame is the ordinary frame of z = zigzag(tensor - base), the items read
+    # as little-endian unsigned integers; it names neither its base nor its rule, and a delta call makes garbage of it -------------------
+    def planes_split_diff_device(self, tensor: torch.Tensor, base: torch.Tensor, d_planes, elements: int | None = None, stream: torch.cuda.Stream | None = None):
+        """hsrans_planes_split_diff_device: ``planes_split_device`` of z, the zigzag of ``tensor - base`` (``base``: a contiguous CUDA
+        tensor of the tensor's element size and element count).  Asynchronous on ``stream``."""
+        self._planes_split_against("planes_split_diff_device", tensor, base, d_planes, elements, stream)
+
+    def planes_merge_diff_device(self, d_planes, base: torch.Tensor, out_tensor: torch.Tensor, elements: int | None = None, stream: torch.cuda.Stream | None = None):
+        """hsrans_planes_merge_diff_device: ``d_planes`` interleaved into z, the zigzag undone and the difference added to ``base`` into
+        ``out_tensor``, which may be ``base`` itself (in place).  Asynchronous on ``stream``."""
+        self._planes_merge_against("planes_merge_diff_device", d_planes, base, out_tensor, elements, stream)
+
+    def encode_device_planes_diff(self, tensor: torch.Tensor, base: torch.Tensor, d_frame: torch.Tensor, d_work: torch.Tensor, states: int = 64, bits: int = 11,
+                                  block_size: int = 1 << 16, index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True,
+                                  stream: torch.cuda.Stream | None = None):
+        """hsrans_encode_device_planes_diff: ``encode_device_planes`` of z, the zigzag of ``tensor - base``, without the buffer that holds
+        it — byte for byte the same frame, descriptor and plans.  The frame names neither its base nor its rule: decode it with the same
+        base by ``decode_device_planes_diff``; ``decode_device_planes`` gives z.  Returns ``(frame_length, desc, plans)``."""
+        return self._encode_planes("encode_device_planes_diff", tensor, _base_of("encode_device_planes_diff", base, tensor), d_frame, d_work, states, bits, block_size,
+                                   index_interval, store_incompressible, want_plans, stream)
+
+    def decode_device_planes_diff(self, planes: Planes, d_frame: torch.Tensor, base: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                  stream: torch.cuda.Stream | None = None, frame_length: int | None = None):
+        """hsrans_decode_device_planes_diff: ``base`` plus the difference the frame at ``d_frame`` holds, into ``out_tensor`` — which may
+        be ``base`` itself (in place).  Launches and workspace as ``decode_device_planes``.  Asynchronous on ``stream``."""
+        self._decode_planes_against("decode_device_planes_diff", planes, d_frame, base, out_tensor, d_work, stream, frame_length)
+
+    def encode_device_planes_diff_batch(self, tensors, bases, d_frames, d_work: torch.Tensor, states: int = 64, bits: int = 11, block_size: int = 1 << 16,
+                                        index_interval: int = 32, store_incompressible: bool = True, want_plans: bool = True, options=None,
+                                        stream: torch.cuda.Stream | None = None, stats: dict | None = None) -> list:
+        """hsrans_encode_device_planes_diff_batch: ``encode_device_planes_delta_batch`` under the diff rule — member k gets what
+        ``encode_device_planes_diff`` gives it against ``bases[k]``, ``encode_device_planes`` where ``bases[k]`` is None.  A call is
+        all-diff.  Returns, fills ``stats`` and raises as that call."""
+        return self._encode_planes_batch("encode_device_planes_diff_batch", tensors, list(bases), d_frames, d_work, options, want_plans, stream, stats, states=states,
+                                         bits=bits, block_size=block_size, index_interval=index_interval, store_incompressible=store_incompressible)
+
+    def decode_device_planes_diff_batch(self, pset: PlanesSet, d_frames, bases, out_tensors, d_work: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """hsrans_decode_device_planes_diff_batch: ``decode_device_planes_batch`` with member k's difference added to ``bases[k]`` (None:
+        as it is); ``out_tensors[k]`` may be ``bases[k]`` itself.  Asynchronous on ``stream`` (default: torch's current stream)."""
+        self._decode_planes_batch_against("decode_device_planes_diff_batch", pset, d_frames, bases, out_tensors, d_work, stream)
+
+    def decode_device_planes_gather_diff(self, pg: PlanesGather, ranges, base: torch.Tensor, out_tensor: torch.Tensor, d_work: torch.Tensor,
+                                         stream: torch.cuda.Stream | None = None):
+        """hsrans_decode_device_planes_gather_diff: ``decode_device_planes_gather`` of a diff frame — element ``offset + i`` of ``base``,
+        the WHOLE base tensor (the frame's element size and element count), plus the difference element ``offset + i`` of the frame
+        holds; the base may not share memory with ``out_tensor`` or ``d_work``.  Asynchronous on ``stream``; ``ranges`` is read before
+        the call returns."""
+        self._planes_gather_against("decode_device_planes_gather_diff", pg, ranges, base, out_tensor, d_work, stream)
 
     def pack_device(self, srcs, lengths, arena: torch.Tensor, stream: torch.cuda.Stream | None = None) -> list:
         """hsrans_pack_device: the first ``lengths[k]`` bytes of the CUDA uint8 tensors ``srcs[k]`` (``lengths`` None: all of each) side by

@@ -8,6 +8,8 @@
 // hsrans_*_device_planes_delta — tensors coded against a base — are these entries given a base, each beside its plain form (here, and in
 // hsrans_capi_planes_batch.cpp and hsrans_capi_planes_gather.cpp).  A delta frame of `in` against `base` is byte for byte the ordinary frame
 // of in ^ base, so nothing of the frame, the descriptor or the codec is new: the XOR rides in the split and the merge.
+// hsrans_*_device_planes_diff are the delta entries under the other residue rule (PlanesBase::rule): the zigzag of the elements' wrapped
+// difference in place of the XOR, by the kernels of hsrans_planes_diff.hip; every check, span and launch count is the delta path's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -136,24 +138,60 @@ bool host_args_ok(uint32_t elem_size, const void *elements, const uint8_t *const
   return true;
 }
 
-// base: null, or what is XORed into every byte on its way
-int host_split(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes)
+// element i of a tensor of W-byte elements as the little-endian unsigned integer the diff rule reads it as
+uint64_t host_element(const uint8_t *elements, size_t i, uint32_t W)
+{
+  uint64_t v = 0;
+  for (uint32_t p = 0; p < W; p++)
+    v |= (uint64_t)elements[i * W + p] << (8 * p);
+  return v;
+}
+
+// base: null, or what is XORed into every byte on its way (PlanesRule::kXor), or what is subtracted from every element, modulo 2^(8 W),
+// before the difference's sign is folded into its lowest bit (PlanesRule::kDiff)
+int host_split(uint32_t elem_size, const void *in, const void *base, PlanesRule rule, size_t elements, uint8_t *const *planes)
 {
   if (!host_args_ok(elem_size, in, planes))
     return HSRANS_E_ARG;
   const uint8_t *src = (const uint8_t *)in, *b = (const uint8_t *)base;
+  if (b != nullptr && rule == PlanesRule::kDiff)
+  {
+    const uint32_t top = 8 * elem_size - 1; // (a bit above 8 W - 1 of z is never stored: only its low W bytes are)
+    for (size_t i = 0; i < elements; i++)
+    {
+      const uint64_t d = host_element(src, i, elem_size) - host_element(b, i, elem_size);
+      const uint64_t z = (d << 1) ^ (0 - ((d >> top) & 1));
+      for (uint32_t p = 0; p < elem_size; p++)
+        planes[p][i] = (uint8_t)(z >> (8 * p));
+    }
+    return HSRANS_OK;
+  }
   for (size_t i = 0; i < elements; i++)
     for (uint32_t p = 0; p < elem_size; p++)
       planes[p][i] = src[i * elem_size + p] ^ (b != nullptr ? b[i * elem_size + p] : 0);
   return HSRANS_OK;
 }
 
-int host_merge(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out)
+int host_merge(uint32_t elem_size, const uint8_t *const *planes, const void *base, PlanesRule rule, size_t elements, void *out)
 {
   if (!host_args_ok(elem_size, out, planes))
     return HSRANS_E_ARG;
-  const uint8_t *b = (const uint8_t *)base; // (may be `out`: every byte is read, then written)
+  const uint8_t *b = (const uint8_t *)base; // (may be `out`: every byte, or with kDiff every element, is read, then written)
   uint8_t *dst = (uint8_t *)out;
+  if (b != nullptr && rule == PlanesRule::kDiff)
+  {
+    const uint64_t low = elem_size == 8 ? ~(uint64_t)0 : ((uint64_t)1 << (8 * elem_size)) - 1;
+    for (size_t i = 0; i < elements; i++)
+    {
+      uint64_t z = 0;
+      for (uint32_t p = 0; p < elem_size; p++)
+        z |= (uint64_t)planes[p][i] << (8 * p);
+      const uint64_t d = ((z >> 1) ^ (0 - (z & 1))) & low, v = host_element(b, i, elem_size) + d;
+      for (uint32_t p = 0; p < elem_size; p++)
+        dst[i * elem_size + p] = (uint8_t)(v >> (8 * p));
+    }
+    return HSRANS_OK;
+  }
   for (size_t i = 0; i < elements; i++)
     for (uint32_t p = 0; p < elem_size; p++)
       dst[i * elem_size + p] = planes[p][i] ^ (b != nullptr ? b[i * elem_size + p] : 0);
@@ -166,7 +204,7 @@ try
   PlanePtrs pp{};
   if (ctx == nullptr || !kernel_args_ok(elem_size, d_in, base, elements, (const void *const *)d_planes, true, &pp))
     return HSRANS_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(elem_size, d_in, base.on ? base.d : nullptr, elements, pp, (hipStream_t)hip_stream) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(elem_size, d_in, base.on ? base.d : nullptr, base.rule, elements, pp, (hipStream_t)hip_stream) != hipSuccess)
     return HSRANS_E_HIP;
   return HSRANS_OK;
 }
@@ -181,7 +219,7 @@ try
   PlanePtrs pp{};
   if (ctx == nullptr || !kernel_args_ok(elem_size, d_out, base, elements, d_planes, false, &pp))
     return HSRANS_E_ARG;
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(elem_size, pp, base.on ? base.d : nullptr, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(elem_size, pp, base.on ? base.d : nullptr, base.rule, elements, d_out, (hipStream_t)hip_stream) != hipSuccess)
     return HSRANS_E_HIP;
   return HSRANS_OK;
 }
@@ -193,22 +231,22 @@ catch (...)
 
 extern "C" int hsrans_planes_split(uint32_t elem_size, const void *in, size_t elements, uint8_t *const *planes)
 {
-  return host_split(elem_size, in, nullptr, elements, planes);
+  return host_split(elem_size, in, nullptr, PlanesRule::kXor, elements, planes);
 }
 
 extern "C" int hsrans_planes_split_delta(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes)
 {
-  return base == nullptr ? HSRANS_E_ARG : host_split(elem_size, in, base, elements, planes);
+  return base == nullptr ? HSRANS_E_ARG : host_split(elem_size, in, base, PlanesRule::kXor, elements, planes);
 }
 
 extern "C" int hsrans_planes_merge(uint32_t elem_size, const uint8_t *const *planes, size_t elements, void *out)
 {
-  return host_merge(elem_size, planes, nullptr, elements, out);
+  return host_merge(elem_size, planes, nullptr, PlanesRule::kXor, elements, out);
 }
 
 extern "C" int hsrans_planes_merge_delta(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out)
 {
-  return base == nullptr ? HSRANS_E_ARG : host_merge(elem_size, planes, base, elements, out);
+  return base == nullptr ? HSRANS_E_ARG : host_merge(elem_size, planes, base, PlanesRule::kXor, elements, out);
 }
 
 extern "C" int hsrans_planes_split_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, size_t elements, void *const *d_planes, void *hip_stream)
@@ -232,6 +270,29 @@ extern "C" int hsrans_planes_merge_delta_device(hsrans_ctx *ctx, uint32_t elem_s
                                                 void *hip_stream)
 {
   return merge_device(ctx, elem_size, d_planes, PlanesBase{true, d_base, elements * elem_size}, elements, d_out, hip_stream);
+}
+
+// ---- the diff forms of the four entries above: the delta entries' bodies under the other residue rule ----
+extern "C" int hsrans_planes_split_diff(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes)
+{
+  return base == nullptr ? HSRANS_E_ARG : host_split(elem_size, in, base, PlanesRule::kDiff, elements, planes);
+}
+
+extern "C" int hsrans_planes_merge_diff(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out)
+{
+  return base == nullptr ? HSRANS_E_ARG : host_merge(elem_size, planes, base, PlanesRule::kDiff, elements, out);
+}
+
+extern "C" int hsrans_planes_split_diff_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, const void *d_base, size_t elements, void *const *d_planes,
+                                               void *hip_stream)
+{
+  return split_device(ctx, elem_size, d_in, PlanesBase{true, d_base, elements * elem_size, PlanesRule::kDiff}, elements, d_planes, hip_stream);
+}
+
+extern "C" int hsrans_planes_merge_diff_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, const void *d_base, size_t elements, void *d_out,
+                                               void *hip_stream)
+{
+  return merge_device(ctx, elem_size, d_planes, PlanesBase{true, d_base, elements * elem_size, PlanesRule::kDiff}, elements, d_out, hip_stream);
 }
 
 bool planes_base_spans(const PlanesBase &base, uint32_t W, size_t elements, const void *d_out, size_t out_capacity, std::vector<Span> *spans)
@@ -293,7 +354,7 @@ try
 
   hipStream_t s = (hipStream_t)hip_stream;
   const PlanePtrs pp = work_planes(W, d_work, elements);
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(W, d_in, base.on ? base.d : nullptr, elements, pp, s) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_split(W, d_in, base.on ? base.d : nullptr, base.rule, elements, pp, s) != hipSuccess)
   {
     (void)hipGetLastError();
     return 0;
@@ -378,6 +439,14 @@ extern "C" size_t hsrans_encode_device_planes_delta(hsrans_ctx *ctx, uint32_t el
 {
   return planes_encode_flow(ctx, elem_size, states, bits, d_in, PlanesBase{true, d_base, base_bytes}, elements, d_frame, frame_capacity, block_size, index_interval, flags,
                             d_work, work_bytes, hip_stream, desc, out_dplans);
+}
+
+extern "C" size_t hsrans_encode_device_planes_diff(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, const void *d_base, size_t base_bytes,
+                                                   size_t elements, void *d_frame, size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags,
+                                                   void *d_work, size_t work_bytes, void *hip_stream, hsrans_planes_desc *desc, hsrans_dplan **out_dplans)
+{
+  return planes_encode_flow(ctx, elem_size, states, bits, d_in, PlanesBase{true, d_base, base_bytes, PlanesRule::kDiff}, elements, d_frame, frame_capacity, block_size,
+                            index_interval, flags, d_work, work_bytes, hip_stream, desc, out_dplans);
 }
 
 extern "C" void hsrans_planes_destroy(hsrans_planes *planes)
@@ -474,7 +543,7 @@ try
       return rc;
   }
   hipStream_t s = (hipStream_t)hip_stream;
-  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(W, src, base.on ? base.d : nullptr, elements, d_out, s) != hipSuccess)
+  if (hipSetDevice(ctx->device) != hipSuccess || launch_planes_merge(W, src, base.on ? base.d : nullptr, base.rule, elements, d_out, s) != hipSuccess)
   {
     (void)hipGetLastError();
     return HSRANS_E_HIP;
@@ -496,6 +565,13 @@ extern "C" int hsrans_decode_device_planes_delta(hsrans_ctx *ctx, hsrans_planes 
                                                  void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
 {
   return planes_decode_flow(ctx, planes, d_frame, frame_length, PlanesBase{true, d_base, base_bytes}, d_out, out_capacity, d_work, work_bytes, hip_stream);
+}
+
+extern "C" int hsrans_decode_device_planes_diff(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const void *d_base, size_t base_bytes,
+                                                void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_decode_flow(ctx, planes, d_frame, frame_length, PlanesBase{true, d_base, base_bytes, PlanesRule::kDiff}, d_out, out_capacity, d_work, work_bytes,
+                            hip_stream);
 }
 
 extern "C" int hsrans_planes_status(hsrans_ctx *ctx, hsrans_planes *planes, void *hip_stream, int *plane_status)

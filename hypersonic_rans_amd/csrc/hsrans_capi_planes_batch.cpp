@@ -4,8 +4,9 @@
 // its public entry, one k_planes_store_batch launch over the planes that did not shrink — and the decode set: ONE hsrans_batch over all coded
 // planes, hsrans_decode_device_batch through its public entry and one k_planes_merge_batch launch behind it (hsrans_planes_batch.hip).  The
 // kernels' member tables go through the context's task buffers as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
-// The two entries' bodies are planes_encode_batch_flow and planes_decode_batch_flow (hsrans_internal.h), which hsrans_capi_planes_delta.cpp
-// runs with a base (or none) per member: then the split and the merge are the delta kernels over the same table with the bases beside it.
+// The two entries' bodies are planes_encode_batch_flow and planes_decode_batch_flow (hsrans_internal.h), which the delta and the diff
+// entries below run with a base (or none) per member: then the split and the merge are the delta kernels (hsrans_planes_delta.hip) or, by
+// the call's residue rule, the diff kernels (hsrans_planes_diff.hip) over the same table with the bases beside it.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -47,7 +48,8 @@ int launch_with_table(hsrans_ctx *ctx, const std::vector<Record> &table, hipStre
 }
 
 // The split or the merge of a batch: `plain(device table, members, tasks, stream)` over the table as it is, or with d_bases `delta(...)` over
-// the delta kernels' table — the plain records with every member's base (null: none).  (Two record types, so two kernels: the choice stays.)
+// the delta or the diff kernels' table — the plain records with every member's base (null: none).  (Two record types, so two kernels: the
+// choice stays.)
 template <typename Plain, typename Delta>
 int launch_split_or_merge(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &table, const void *const *d_bases, uint32_t n_tasks, hipStream_t s, Plain plain,
                           Delta delta)
@@ -123,7 +125,7 @@ extern "C" size_t hsrans_planes_batch_tasks(const size_t *elements, uint32_t cou
   return (size_t)total;
 }
 
-int planes_encode_batch_flow(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes, bool delta, uint32_t count,
+int planes_encode_batch_flow(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes, bool delta, PlanesRule rule, uint32_t count,
                              void *d_work, size_t work_bytes, void *hip_stream, hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
 try
 {
@@ -195,7 +197,8 @@ try
     t.W = members[k].elem_size;
     t.first_task = first_task[k];
   }
-  int rc = launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, (uint32_t)n_tasks, s, launch_planes_split_batch, launch_planes_split_delta_batch);
+  int rc = launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, (uint32_t)n_tasks, s, launch_planes_split_batch,
+                                 rule == PlanesRule::kDiff ? launch_planes_split_diff_batch : launch_planes_split_delta_batch);
   if (rc != HSRANS_OK)
   {
     fail_encode(members, count, out_dplans, rc);
@@ -315,13 +318,19 @@ catch (...) // (std::bad_alloc and friends: nothing is thrown across the C ABI; 
 extern "C" int hsrans_encode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_member *members, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
                                                  hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
 {
-  return planes_encode_batch_flow(ctx, members, nullptr, nullptr, false, count, d_work, work_bytes, hip_stream, out_dplans, stats);
+  return planes_encode_batch_flow(ctx, members, nullptr, nullptr, false, PlanesRule::kXor, count, d_work, work_bytes, hip_stream, out_dplans, stats);
 }
 
 extern "C" int hsrans_encode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes, uint32_t count,
                                                        void *d_work, size_t work_bytes, void *hip_stream, hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
 {
-  return planes_encode_batch_flow(ctx, members, d_bases, base_bytes, true, count, d_work, work_bytes, hip_stream, out_dplans, stats);
+  return planes_encode_batch_flow(ctx, members, d_bases, base_bytes, true, PlanesRule::kXor, count, d_work, work_bytes, hip_stream, out_dplans, stats);
+}
+
+extern "C" int hsrans_encode_device_planes_diff_batch(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes, uint32_t count,
+                                                      void *d_work, size_t work_bytes, void *hip_stream, hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats)
+{
+  return planes_encode_batch_flow(ctx, members, d_bases, base_bytes, true, PlanesRule::kDiff, count, d_work, work_bytes, hip_stream, out_dplans, stats);
 }
 
 extern "C" void hsrans_planes_set_destroy(hsrans_planes_set *set)
@@ -419,7 +428,7 @@ extern "C" int hsrans_planes_set_info(const hsrans_planes_set *set, hsrans_plane
 }
 
 int planes_decode_batch_flow(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, const void *const *d_bases,
-                             const size_t *base_bytes, bool delta, void *const *d_outs, const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
+                             const size_t *base_bytes, bool delta, PlanesRule rule, void *const *d_outs, const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
 try
 {
   if (ctx == nullptr || (delta && (d_bases == nullptr || base_bytes == nullptr)) || set == nullptr || set->ctx != ctx || d_frames == nullptr || frame_lengths == nullptr || d_outs == nullptr || out_capacities == nullptr ||
@@ -482,7 +491,7 @@ try
       return rc;
   }
   return launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, set->first_task.back(), (hipStream_t)hip_stream, launch_planes_merge_batch,
-                               launch_planes_merge_delta_batch);
+                               rule == PlanesRule::kDiff ? launch_planes_merge_diff_batch : launch_planes_merge_delta_batch);
 }
 catch (...)
 {
@@ -492,14 +501,21 @@ catch (...)
 extern "C" int hsrans_decode_device_planes_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths, void *const *d_outs,
                                                  const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream)
 {
-  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, nullptr, nullptr, false, d_outs, out_capacities, d_work, work_bytes, hip_stream);
+  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, nullptr, nullptr, false, PlanesRule::kXor, d_outs, out_capacities, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_decode_device_planes_delta_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
                                                        const void *const *d_bases, const size_t *base_bytes, void *const *d_outs, const size_t *out_capacities, void *d_work,
                                                        size_t work_bytes, void *hip_stream)
 {
-  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, d_bases, base_bytes, true, d_outs, out_capacities, d_work, work_bytes, hip_stream);
+  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, d_bases, base_bytes, true, PlanesRule::kXor, d_outs, out_capacities, d_work, work_bytes, hip_stream);
+}
+
+extern "C" int hsrans_decode_device_planes_diff_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
+                                                      const void *const *d_bases, const size_t *base_bytes, void *const *d_outs, const size_t *out_capacities, void *d_work,
+                                                      size_t work_bytes, void *hip_stream)
+{
+  return planes_decode_batch_flow(ctx, set, d_frames, frame_lengths, d_bases, base_bytes, true, PlanesRule::kDiff, d_outs, out_capacities, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_set_status(hsrans_ctx *ctx, hsrans_planes_set *set, void *hip_stream, int *member_status)

@@ -250,7 +250,7 @@ try
         return HSRANS_OK;
       },
       [&](const uint8_t *dev) {
-        return launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, base.on ? base.d : nullptr, d_out, s);
+        return launch_planes_merge_ranges(W, src, work_mask, (const PlanesGatherTask *)dev, (uint32_t)n_tasks, base.on ? base.d : nullptr, base.rule, d_out, s);
       });
   if (rc != HSRANS_OK)
     return rc;
@@ -274,6 +274,13 @@ extern "C" int hsrans_decode_device_planes_gather_delta(hsrans_ctx *ctx, hsrans_
                                                         size_t base_bytes, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
 {
   return planes_gather_flow(ctx, pg, ranges, count, PlanesBase{true, d_base, base_bytes}, d_out, out_capacity, d_work, work_bytes, hip_stream);
+}
+
+// the delta entry under the other residue rule: the merge is k_planes_merge_ranges_diff (hsrans_planes_diff.hip)
+extern "C" int hsrans_decode_device_planes_gather_diff(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const void *d_base,
+                                                       size_t base_bytes, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
+{
+  return planes_gather_flow(ctx, pg, ranges, count, PlanesBase{true, d_base, base_bytes, PlanesRule::kDiff}, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
 extern "C" int hsrans_planes_gather_status(hsrans_ctx *ctx, hsrans_planes_gather *pg, void *hip_stream, int *plane_status)

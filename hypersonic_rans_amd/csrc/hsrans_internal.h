@@ -17,6 +17,7 @@
 #include "hsrans_encode.h"
 #include "hsrans_host.h"
 #include "hsrans_kernels.h"
+#include "hsrans_planes.h" // PlanesRule
 
 using namespace hsrans;
 
@@ -308,12 +309,15 @@ int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsr
 
 // ---- what the plain byte-plane entries and their delta forms (hsrans_*_device_planes_delta, each beside its plain entry) share: each plain
 // entry's whole body, taking an optional base.  Without one (`on` false) a flow is the plain entry, check for check and launch for launch;
-// with one the launcher is handed the base, so the split or the merge is the delta kernel (hsrans_planes_delta.hip), and the base joins the checks.  Hidden: the library's exported symbols are the header's. ----
+// with one the launcher is handed the base, so the split or the merge is the delta kernel (hsrans_planes_delta.hip), and the base joins the checks.  Hidden: the library's exported symbols are the header's.
+// The diff forms (hsrans_*_device_planes_diff) are the delta forms with the other residue rule: the same flows, checks, spans, refusals and
+// launch counts, the launcher handed PlanesRule::kDiff, so the kernel is hsrans_planes_diff.hip's. ----
 struct PlanesBase
 {
-  bool on = false; // a delta call (a plain one never looks at the rest)
+  bool on = false; // a delta or diff call (a plain one never looks at the rest)
   const void *d = nullptr;
   size_t bytes = 0;
+  PlanesRule rule = PlanesRule::kXor; // what the planes hold of the tensor and the base (hsrans_planes.h)
 };
 // The base's own checks and its part in the overlap rule: set, 16-byte aligned, at least W * elements bytes (false otherwise); a read span,
 // pushed onto *spans.  d_out (null: the call has no in-place form): where the output is exactly the base — the same address, out_capacity
@@ -331,12 +335,12 @@ __attribute__((visibility("hidden"))) size_t planes_encode_flow(hsrans_ctx *ctx,
 __attribute__((visibility("hidden"))) int planes_decode_flow(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const PlanesBase &base,
                                                              void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
 // hsrans_encode_device_planes_batch, hsrans_decode_device_planes_batch (hsrans_capi_planes_batch.cpp); delta: d_bases and base_bytes are
-// arrays of one entry per member, a null d_bases[k] a member without a base
+// arrays of one entry per member, a null d_bases[k] a member without a base; rule: the one residue rule of all members with a base
 __attribute__((visibility("hidden"))) int planes_encode_batch_flow(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases, const size_t *base_bytes,
-                                                                   bool delta, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
+                                                                   bool delta, PlanesRule rule, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
                                                                    hsrans_dplan **out_dplans, hsrans_planes_batch_stats *stats);
 __attribute__((visibility("hidden"))) int planes_decode_batch_flow(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
-                                                                   const void *const *d_bases, const size_t *base_bytes, bool delta, void *const *d_outs,
+                                                                   const void *const *d_bases, const size_t *base_bytes, bool delta, PlanesRule rule, void *const *d_outs,
                                                                    const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream);
 // hsrans_decode_device_planes_gather (hsrans_capi_planes_gather.cpp); no in-place form
 struct hsrans_planes_gather;

@@ -2,7 +2,8 @@
 // into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
 // hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip, and with those rows in device memory
 // hsrans_planes_gather_batch_indirect.hip), and the forms of the split and the merges that XOR a base in (hsrans_planes_delta.hip;
-// of the last three range merges hsrans_planes_gather_delta.hip).
+// of the last three range merges hsrans_planes_gather_delta.hip), or that take the zigzag of the difference against it
+// (hsrans_planes_diff.hip).
 // plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
@@ -51,12 +52,21 @@ inline void planes_with_width(uint32_t W, F &&f)
     f(std::integral_constant<uint32_t, 8>{});
 }
 
+// What a tensor coded against a base leaves in its planes, the residue rule: in ^ base (hsrans_*_device_planes_delta), or the zigzag of
+// the wrapped difference in - base of the elements read as little-endian unsigned integers (hsrans_*_device_planes_diff).  Looked at only
+// where there is a base.
+enum class PlanesRule : uint32_t
+{
+  kXor,
+  kDiff
+};
+
 // asynchronous on `stream`; every pointer 16-byte aligned, n in 1..kPlanesMaxElements, W in {2, 4, 8} (hipErrorInvalidValue otherwise).
-// base: null, or as many bytes as the elements (hsrans_*_device_planes_delta): the planes hold in ^ base — k_planes_split_delta and
-// k_planes_merge_delta (hsrans_planes_delta.hip) instead of the plain kernels.  The merge's base may be `out` itself: the delta applied in
-// place; any other overlap of the two is the caller's to refuse.
-hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
-hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream);
+// base: null, or as many bytes as the elements: the planes hold the residue by `rule` — k_planes_split_delta and k_planes_merge_delta
+// (hsrans_planes_delta.hip) or k_planes_split_diff and k_planes_merge_diff (hsrans_planes_diff.hip) instead of the plain kernels.  The
+// merge's base may be `out` itself: the residue undone in place; any other overlap of the two is the caller's to refuse.
+hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, PlanesRule rule, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
+hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, PlanesRule rule, uint64_t n, void *out, hipStream_t stream);
 
 // ---- many tensors in one launch (hsrans_*_device_planes_batch): k_planes_split_batch, k_planes_merge_batch, k_planes_store_batch
 // (hsrans_planes_batch.hip), each driven by a table of these records in device memory, one workgroup per task ----
@@ -123,10 +133,11 @@ struct PlanesGatherTask
 };
 // asynchronous on `stream`, one workgroup per task (1 .. 2^31 - 1 of them, in device memory); planes.p[p]: plane p's workspace region where
 // bit p of work_mask is set, else the stored plane; every pointer 16-byte aligned (hipErrorInvalidValue otherwise).  base: null, or the
-// whole base tensor (hsrans_decode_device_planes_gather_delta): output element (element + dst_delta) is XORed with base element `element`
-// — k_planes_merge_ranges_delta (hsrans_planes_delta.hip) instead of the plain kernel
+// whole base tensor (hsrans_decode_device_planes_gather_delta, _gather_diff): output element (element + dst_delta) is what `rule` makes of
+// the planes' element and base element `element` — k_planes_merge_ranges_delta (hsrans_planes_delta.hip) or k_planes_merge_ranges_diff
+// (hsrans_planes_diff.hip) instead of the plain kernel
 hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
-                                      void *out, hipStream_t stream);
+                                      PlanesRule rule, void *out, hipStream_t stream);
 
 // ---- rows of many frames in one launch (hsrans_decode_device_planes_gather_batch): k_planes_merge_ranges_batch
 // (hsrans_planes_gather_batch.hip) ----
@@ -269,6 +280,16 @@ struct PlanesDeltaBatchMember
 };
 hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+
+// ---- tensors coded against a base as a zigzag difference (hsrans_*_device_planes_diff): hsrans_planes_diff.hip.  The planes hold the
+// zigzag of in - base (PlanesRule::kDiff).  The same five launches as the delta unit's above, to the same contracts, over the same
+// PlanesDeltaBatchMember tables ----
+void planes_diff_split_kernel(uint32_t W, uint32_t grid, const uint8_t *in, const uint8_t *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
+void planes_diff_merge_kernel(uint32_t W, uint32_t grid, const PlanePtrs &planes, const uint8_t *base, uint64_t n, uint8_t *out, hipStream_t stream);
+void planes_diff_merge_ranges_kernel(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const uint8_t *base,
+                                     uint8_t *out, hipStream_t stream);
+hipError_t launch_planes_split_diff_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+hipError_t launch_planes_merge_diff_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 
 // ---- the gathers that undo a delta while they fetch (hsrans_decode_device_planes_gather_indirect_delta, _gather_batch_delta,
 // _gather_batch_indirect_delta): hsrans_planes_gather_delta.hip.  Each launcher is its plain twin's above — the same arguments, the same

@@ -61,25 +61,25 @@ uint32_t grid_of(uint64_t n)
 }
 } // namespace
 
-hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
+hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, PlanesRule rule, uint64_t n, const PlanePtrs &planes, hipStream_t stream)
 {
   if (!launch_ok(W, in, base, n, planes))
     return hipErrorInvalidValue;
   const uint8_t *src = (const uint8_t *)in;
   if (base != nullptr)
-    planes_delta_split_kernel(W, grid_of(n), src, (const uint8_t *)base, n, planes, stream);
+    (rule == PlanesRule::kDiff ? planes_diff_split_kernel : planes_delta_split_kernel)(W, grid_of(n), src, (const uint8_t *)base, n, planes, stream);
   else
     planes_with_width(W, [&](auto w) { k_planes_split<w()><<<grid_of(n), kThreads, 0, stream>>>(src, n, planes); });
   return hipGetLastError();
 }
 
-hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, uint64_t n, void *out, hipStream_t stream)
+hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, PlanesRule rule, uint64_t n, void *out, hipStream_t stream)
 {
   if (!launch_ok(W, out, base, n, planes))
     return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   if (base != nullptr)
-    planes_delta_merge_kernel(W, grid_of(n), planes, (const uint8_t *)base, n, dst, stream);
+    (rule == PlanesRule::kDiff ? planes_diff_merge_kernel : planes_delta_merge_kernel)(W, grid_of(n), planes, (const uint8_t *)base, n, dst, stream);
   else
     planes_with_width(W, [&](auto w) { k_planes_merge<w()><<<grid_of(n), kThreads, 0, stream>>>(planes, n, dst); });
   return hipGetLastError();

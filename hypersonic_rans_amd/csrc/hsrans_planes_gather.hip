@@ -57,14 +57,14 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_ranges(PlanePtrs plan
 } // namespace
 
 hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
-                                      void *out, hipStream_t stream)
+                                      PlanesRule rule, void *out, hipStream_t stream)
 {
   if (!planes_ptrs_ok(W, planes) || out == nullptr || ((uintptr_t)out & 15) != 0 || ((uintptr_t)base & 15) != 0 || d_tasks == nullptr ||
       ((uintptr_t)d_tasks & 7) != 0 || n_tasks == 0 || n_tasks > 0x7FFFFFFFu || (work_mask >> W) != 0)
     return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   if (base != nullptr)
-    planes_delta_merge_ranges_kernel(W, planes, work_mask, d_tasks, n_tasks, (const uint8_t *)base, dst, stream);
+    (rule == PlanesRule::kDiff ? planes_diff_merge_ranges_kernel : planes_delta_merge_ranges_kernel)(W, planes, work_mask, d_tasks, n_tasks, (const uint8_t *)base, dst, stream);
   else
     planes_with_width(W, [&](auto w) { k_planes_merge_ranges<w()><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, dst); });
   return hipGetLastError();

@@ -1,10 +1,11 @@
-// planes_shuffle.h — what the byte-plane kernels (the nine hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
+// planes_shuffle.h — what the byte-plane kernels (the ten hsrans_planes*.hip units) share.  The in-register byte shuffles: 16 elements of W
 // bytes as they lie in memory <-> 16 bytes of each of the W planes, with v_perm_b32 (a 4 x 4 byte transpose is 8 of them).  The small
 // helpers of the table- and list-driven kernels: wave-uniform values as scalars, the global-address cast, the element-wide stores of a
 // block whose output is not 16-byte aligned, the search of a task's row in a prefix of task counts, and the walk of the member tables
 // (a workgroup's member and its place in it).  And, at the end, what one lane of a WHOLE-TENSOR split or merge does, with or without a
 // base: split_lanes and merge_lanes, the body of the one-tensor kernels (hsrans_planes.hip, hsrans_planes_delta.hip) and of the
-// table-driven ones (hsrans_planes_batch.hip, hsrans_planes_delta.hip).  Device code only; every function is inlined into the kernel that
+// table-driven ones (hsrans_planes_batch.hip, hsrans_planes_delta.hip; hsrans_planes_diff.hip takes them without a base, for its members
+// that have none, and keeps its own bodies for the zigzag difference, split_lanes_diff and merge_lanes_diff).  Device code only; every function is inlined into the kernel that
 // calls it.  Everything is in hsrans::planes_detail; every unit says `using namespace`.
 // (Sharing the whole-tensor body left the five table-driven kernels instruction for instruction as they were.  The one-tensor kernels
 // came out 3 to 5 instructions shorter: with the plane pointers handed over by reference the compiler reads the kernel arguments once, on

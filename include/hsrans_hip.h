@@ -1309,8 +1309,12 @@ int hsrans_planes_gather_set_indirect_info(const hsrans_planes_gather_set *pgs, 
  * Tensors coded against a base.  The tensors this layer is for are rarely alone: a checkpoint's parameters sit next to the
  * previous checkpoint's, a fine-tuned model next to its base, a layer's experts next to a shared initialisation.  XORed with a
  * close relative, a bf16 tensor's sign/exponent byte is almost always zero and its mantissa byte's upper bits mostly are: the
- * residue codes far smaller than the tensor.  XOR, not an arithmetic difference: it is dtype-free (the library takes no view on
- * endianness or dtype), exactly invertible and needs no carries across bytes.
+ * residue codes far smaller than the tensor.  XOR here, not an arithmetic difference: it is dtype-free (these entries take no view
+ * on endianness or dtype), exactly invertible and needs no carries across bytes.  It pays for every carry the real difference
+ * causes, though — two bf16 values one ulp apart XOR to 2^(k+1) - 1, k the low mantissa bits that flip — so a second residue rule,
+ * the zigzag of the elements' wrapped integer difference, has entries of its own in the section behind this one
+ * (hsrans_*_device_planes_diff); that is the one place the library reads an element as a little-endian integer.  XOR stays, for
+ * callers who want no such view.
  *
  * The invariant.  A delta frame of `in` against `base` is, byte for byte, the ordinary frame of the tensor in ^ base: the same
  * frame bytes, the same descriptor, the same plans as hsrans_encode_device_planes gives for a buffer that holds in ^ base.
@@ -1410,6 +1414,72 @@ int hsrans_decode_device_planes_gather_batch_delta(hsrans_ctx *ctx, hsrans_plane
 int hsrans_decode_device_planes_gather_batch_indirect_delta(hsrans_ctx *ctx, hsrans_planes_gather_set *pgs, const hsrans_planes_base_set *bs,
                                                             const hsrans_member_range *d_ranges, const uint32_t *d_count, uint32_t max_count, void *d_out,
                                                             size_t out_capacity, void *d_work, size_t work_bytes, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Tensors coded against a base as a zigzag difference.  The second residue rule of this layer, for relatives that lie a few ulps
+ * apart: a fine-tune next to its base, a checkpoint next to its predecessor.  There the XOR residue above pays for every carry
+ * (one ulp across k low mantissa bits XORs to 2^(k+1) - 1); the difference does not.
+ *
+ * The rule.  An element is read as a LITTLE-ENDIAN UNSIGNED INTEGER of W = elem_size bytes, W in {2, 4, 8}: this is the one place
+ * the library takes a view on byte order (nothing is read as a float: bf16, fp16, fp32, fp64 and the integers all go by their bit
+ * patterns).  All arithmetic is modulo 2^(8 W):
+ *   split:  d = in - base,  z = (d << 1) ^ (0 - (d >> (8 W - 1))),  planes[p][i] = byte p of z[i]
+ *   merge:  d = (z >> 1) ^ (0 - (z & 1)),  out = base + d
+ * — the wrapped difference with its sign folded into the lowest bit, so that small differences of either sign leave small z.
+ * Exactly invertible for every pair of bit patterns, NaNs and values of opposite sign included.
+ *
+ * The invariant mirrors the delta one.  A diff frame of `in` against `base` is, byte for byte, the ordinary frame of the tensor z:
+ * the same frame bytes, the same descriptor, the same plans as hsrans_encode_device_planes gives for a buffer that holds z.  A frame
+ * records neither its base NOR ITS RULE.  Every other entry of this layer therefore takes a diff frame unchanged and yields z; in
+ * particular hsrans_decode_device_planes of a diff frame gives z.  Decoding a diff frame with a _delta entry, or a delta frame with
+ * a _diff entry, gives garbage, not an error: which rule a frame was coded by is the caller's to keep, like its base.
+ *
+ * Each entry below has the argument list, return value, launch count, workspace, synchronisation, refusals and overlap rule of its
+ * _delta twin above, word for word — the base a 16-byte aligned device buffer of base_bytes >= elem_size * elements, a READ span
+ * that may coincide with other reads and may meet nothing written nor a frame it is decoded against; the in-place exception
+ * d_out == d_base (out_capacity <= base_bytes) for the three whole-tensor decodes (hsrans_planes_merge_diff_device,
+ * hsrans_decode_device_planes_diff, hsrans_decode_device_planes_diff_batch: every lane reads its base elements before it writes,
+ * and no lane reads another's); no aliasing at all in the gather.  The kernels are those of hsrans_planes_diff.hip: the delta
+ * kernels' loads and stores with a handful of integer instructions per word between them.
+ * The diff forms of the other three gathers (_gather_indirect, _gather_batch, _gather_batch_indirect) are not offered yet.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* the rule on the host, in plain C++ (out may be base); HSRANS_OK or HSRANS_E_ARG (elem_size not 2, 4 or 8; a NULL pointer) */
+int hsrans_planes_split_diff(uint32_t elem_size, const void *in, const void *base, size_t elements, uint8_t *const *planes);
+int hsrans_planes_merge_diff(uint32_t elem_size, const uint8_t *const *planes, const void *base, size_t elements, void *out);
+/* the two kernels alone, as hsrans_planes_split_delta_device / hsrans_planes_merge_delta_device: asynchronous on `hip_stream`, no
+ * allocation, no synchronisation.  d_base: elem_size * elements bytes, 16-byte aligned, clear of the planes; the merge's d_out may
+ * be d_base. */
+int hsrans_planes_split_diff_device(hsrans_ctx *ctx, uint32_t elem_size, const void *d_in, const void *d_base, size_t elements, void *const *d_planes,
+                                    void *hip_stream);
+int hsrans_planes_merge_diff_device(hsrans_ctx *ctx, uint32_t elem_size, const void *const *d_planes, const void *d_base, size_t elements, void *d_out,
+                                    void *hip_stream);
+/* hsrans_encode_device_planes of z without the buffer that holds it: hsrans_encode_device_planes_delta with the diff split in front;
+ * a stored plane holds z's bytes. */
+size_t hsrans_encode_device_planes_diff(hsrans_ctx *ctx, uint32_t elem_size, int states, uint32_t bits, const void *d_in, const void *d_base, size_t base_bytes,
+                                        size_t elements, void *d_frame, size_t frame_capacity, uint32_t block_size, uint32_t index_interval, uint32_t flags,
+                                        void *d_work, size_t work_bytes, void *hip_stream, hsrans_planes_desc *desc,
+                                        hsrans_dplan **out_dplans /* [elem_size] or NULL */);
+/* hsrans_decode_device_planes_delta with the diff merge behind the codec batch: d_out = base + (the difference the frame holds).
+ * d_out may be d_base (in place, above). */
+int hsrans_decode_device_planes_diff(hsrans_ctx *ctx, hsrans_planes *planes, const void *d_frame, size_t frame_length, const void *d_base, size_t base_bytes,
+                                     void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
+/* hsrans_encode_device_planes_delta_batch under this rule: member k gets byte for byte what hsrans_encode_device_planes_diff gives
+ * it — hsrans_encode_device_planes where d_bases[k] is NULL: such a member goes as it is.  A call is all-diff: XOR and diff members
+ * cannot be mixed in one call. */
+int hsrans_encode_device_planes_diff_batch(hsrans_ctx *ctx, hsrans_planes_member *members, const void *const *d_bases /* [count], entries may be NULL */,
+                                           const size_t *base_bytes /* [count] */, uint32_t count, void *d_work, size_t work_bytes, void *hip_stream,
+                                           hsrans_dplan **out_dplans /* [count * HSRANS_PLANES_MAX] or NULL */, hsrans_planes_batch_stats *stats /* may be NULL */);
+/* hsrans_decode_device_planes_delta_batch under this rule: ONE diff merge launch in place of the merge.  d_outs[k] may be d_bases[k]
+ * (in place, above); it may not meet another member's base. */
+int hsrans_decode_device_planes_diff_batch(hsrans_ctx *ctx, hsrans_planes_set *set, const void *const *d_frames, const size_t *frame_lengths,
+                                           const void *const *d_bases /* [count], entries may be NULL */, const size_t *base_bytes /* [count] */, void *const *d_outs,
+                                           const size_t *out_capacities, void *d_work, size_t work_bytes, void *hip_stream);
+/* hsrans_decode_device_planes_gather_delta (ranges in host memory) under this rule: base element offset + i plus the difference that
+ * element offset + i of the frame holds lands at element dst_offset + i of d_out.  d_base is the WHOLE base tensor, in the frame's
+ * element coordinates (base_bytes >= elem_size * the frame's elements), whatever the ranges are; heads and tails read base
+ * elements of their own range only.  No aliasing: the base may not meet d_out or d_work. */
+int hsrans_decode_device_planes_gather_diff(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const void *d_base, size_t base_bytes,
+                                            void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream);
 
 /* Build a plan with checkpoints every `index_interval` groups for an EXISTING stream (e.g. one written by the
  * reference's encoder) by one decode pass on the GPU that records the states at the checkpoints: HSRANS_RAW (one

@@ -4,12 +4,12 @@
 // hsrans_decode_device_batch of the coded planes and one merge launch behind it.  Both codecs are used as they are, through their public
 // entries: a coded plane is byte for byte what hsrans_encode_device(HSRANS_MT, ...) writes for the plane's bytes.
 // The two entries' bodies are planes_encode_flow and planes_decode_flow (hsrans_internal.h), which take an optional base: without one they are
-// the entries as they always were; with one the split or the merge is the delta kernel (hsrans_planes_delta.hip).
+// the entries as they always were; with one the split or the merge is the delta kernel (hsrans_planes_base.hip).
 // hsrans_*_device_planes_delta — tensors coded against a base — are these entries given a base, each beside its plain form (here, and in
 // hsrans_capi_planes_batch.cpp and hsrans_capi_planes_gather.cpp).  A delta frame of `in` against `base` is byte for byte the ordinary frame
 // of in ^ base, so nothing of the frame, the descriptor or the codec is new: the XOR rides in the split and the merge.
 // hsrans_*_device_planes_diff are the delta entries under the other residue rule (PlanesBase::rule): the zigzag of the elements' wrapped
-// difference in place of the XOR, by the kernels of hsrans_planes_diff.hip; every check, span and launch count is the delta path's.
+// difference in place of the XOR, by the _diff kernels of the same unit; every check, span and launch count is the delta path's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 

@@ -5,8 +5,8 @@
 // planes, hsrans_decode_device_batch through its public entry and one k_planes_merge_batch launch behind it (hsrans_planes_batch.hip).  The
 // kernels' member tables go through the context's task buffers as the gathers' lists do (gather_region_*, hsrans_capi_gather.cpp).
 // The two entries' bodies are planes_encode_batch_flow and planes_decode_batch_flow (hsrans_internal.h), which the delta and the diff
-// entries below run with a base (or none) per member: then the split and the merge are the delta kernels (hsrans_planes_delta.hip) or, by
-// the call's residue rule, the diff kernels (hsrans_planes_diff.hip) over the same table with the bases beside it.
+// entries below run with a base (or none) per member: then the split and the merge are, by the call's residue rule, the delta or the diff
+// kernels (hsrans_planes_base.hip) over the same table with the bases beside it.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -47,12 +47,12 @@ int launch_with_table(hsrans_ctx *ctx, const std::vector<Record> &table, hipStre
       [&](const uint8_t *dev) { return launch((const Record *)dev); });
 }
 
-// The split or the merge of a batch: `plain(device table, members, tasks, stream)` over the table as it is, or with d_bases `delta(...)` over
-// the delta or the diff kernels' table — the plain records with every member's base (null: none).  (Two record types, so two kernels: the
-// choice stays.)
-template <typename Plain, typename Delta>
-int launch_split_or_merge(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &table, const void *const *d_bases, uint32_t n_tasks, hipStream_t s, Plain plain,
-                          Delta delta)
+// The split or the merge of a batch: `plain(device table, members, tasks, stream)` over the table as it is, or with d_bases
+// `with_base(rule, ...)` over the table of the kernels that take a base (hsrans_planes_base.hip) — the plain records with every member's
+// base (null: none).  (Two record types, so two kernels: the choice stays.)
+template <typename Plain, typename WithBase>
+int launch_split_or_merge(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> &table, const void *const *d_bases, PlanesRule rule, uint32_t n_tasks, hipStream_t s,
+                          Plain plain, WithBase with_base)
 {
   const uint32_t count = (uint32_t)table.size();
   if (d_bases == nullptr)
@@ -60,7 +60,7 @@ int launch_split_or_merge(hsrans_ctx *ctx, const std::vector<PlanesBatchMember> 
   std::vector<PlanesDeltaBatchMember> with_bases(count);
   for (uint32_t k = 0; k < count; k++)
     with_bases[k] = PlanesDeltaBatchMember{table[k], (const uint8_t *)d_bases[k]};
-  return launch_with_table(ctx, with_bases, s, [&](const PlanesDeltaBatchMember *d) { return delta(d, count, n_tasks, s); });
+  return launch_with_table(ctx, with_bases, s, [&](const PlanesDeltaBatchMember *d) { return with_base(rule, d, count, n_tasks, s); });
 }
 
 // every output of a failed encode: no frame, no descriptor, no plan (one already made is destroyed)
@@ -197,8 +197,7 @@ try
     t.W = members[k].elem_size;
     t.first_task = first_task[k];
   }
-  int rc = launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, (uint32_t)n_tasks, s, launch_planes_split_batch,
-                                 rule == PlanesRule::kDiff ? launch_planes_split_diff_batch : launch_planes_split_delta_batch);
+  int rc = launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, rule, (uint32_t)n_tasks, s, launch_planes_split_batch, launch_planes_split_base_batch);
   if (rc != HSRANS_OK)
   {
     fail_encode(members, count, out_dplans, rc);
@@ -490,8 +489,8 @@ try
     if (rc != HSRANS_OK)
       return rc;
   }
-  return launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, set->first_task.back(), (hipStream_t)hip_stream, launch_planes_merge_batch,
-                               rule == PlanesRule::kDiff ? launch_planes_merge_diff_batch : launch_planes_merge_delta_batch);
+  return launch_split_or_merge(ctx, table, delta ? d_bases : nullptr, rule, set->first_task.back(), (hipStream_t)hip_stream, launch_planes_merge_batch,
+                               launch_planes_merge_base_batch);
 }
 catch (...)
 {

@@ -276,7 +276,7 @@ extern "C" int hsrans_decode_device_planes_gather_delta(hsrans_ctx *ctx, hsrans_
   return planes_gather_flow(ctx, pg, ranges, count, PlanesBase{true, d_base, base_bytes}, d_out, out_capacity, d_work, work_bytes, hip_stream);
 }
 
-// the delta entry under the other residue rule: the merge is k_planes_merge_ranges_diff (hsrans_planes_diff.hip)
+// the delta entry under the other residue rule: the merge is k_planes_merge_ranges_diff (hsrans_planes_base.hip)
 extern "C" int hsrans_decode_device_planes_gather_diff(hsrans_ctx *ctx, hsrans_planes_gather *pg, const hsrans_range *ranges, uint32_t count, const void *d_base,
                                                        size_t base_bytes, void *d_out, size_t out_capacity, void *d_work, size_t work_bytes, void *hip_stream)
 {

@@ -309,9 +309,9 @@ int planes_desc_check(const hsrans_ctx *ctx, const hsrans_planes_desc *desc, hsr
 
 // ---- what the plain byte-plane entries and their delta forms (hsrans_*_device_planes_delta, each beside its plain entry) share: each plain
 // entry's whole body, taking an optional base.  Without one (`on` false) a flow is the plain entry, check for check and launch for launch;
-// with one the launcher is handed the base, so the split or the merge is the delta kernel (hsrans_planes_delta.hip), and the base joins the checks.  Hidden: the library's exported symbols are the header's.
+// with one the launcher is handed the base, so the split or the merge is the delta kernel (hsrans_planes_base.hip), and the base joins the checks.  Hidden: the library's exported symbols are the header's.
 // The diff forms (hsrans_*_device_planes_diff) are the delta forms with the other residue rule: the same flows, checks, spans, refusals and
-// launch counts, the launcher handed PlanesRule::kDiff, so the kernel is hsrans_planes_diff.hip's. ----
+// launch counts, the launcher handed PlanesRule::kDiff, so the kernel is that unit's _diff one. ----
 struct PlanesBase
 {
   bool on = false; // a delta or diff call (a plain one never looks at the rest)

@@ -1,9 +1,8 @@
 // hsrans_planes.h — the streaming kernels of the byte-plane layer: elements of W bytes split into W byte planes and planes interleaved back
 // into elements (hsrans_planes.hip), and the interleave of element ranges (hsrans_planes_gather.hip; with the ranges in device memory
 // hsrans_planes_gather_indirect.hip; of many frames at once hsrans_planes_gather_batch.hip, and with those rows in device memory
-// hsrans_planes_gather_batch_indirect.hip), and the forms of the split and the merges that XOR a base in (hsrans_planes_delta.hip;
-// of the last three range merges hsrans_planes_gather_delta.hip), or that take the zigzag of the difference against it
-// (hsrans_planes_diff.hip).
+// hsrans_planes_gather_batch_indirect.hip), and the forms of the split and the merges that XOR a base in or take the zigzag of the
+// difference against it (hsrans_planes_base.hip; the XOR forms of the last three range merges hsrans_planes_gather_delta.hip).
 // plane[p][i] = elements[i * W + p]; W is 2, 4 or 8.
 #ifndef HSRANS_PLANES_H
 #define HSRANS_PLANES_H
@@ -62,8 +61,8 @@ enum class PlanesRule : uint32_t
 };
 
 // asynchronous on `stream`; every pointer 16-byte aligned, n in 1..kPlanesMaxElements, W in {2, 4, 8} (hipErrorInvalidValue otherwise).
-// base: null, or as many bytes as the elements: the planes hold the residue by `rule` — k_planes_split_delta and k_planes_merge_delta
-// (hsrans_planes_delta.hip) or k_planes_split_diff and k_planes_merge_diff (hsrans_planes_diff.hip) instead of the plain kernels.  The
+// base: null, or as many bytes as the elements: the planes hold the residue by `rule` — k_planes_split_delta and k_planes_merge_delta or
+// k_planes_split_diff and k_planes_merge_diff (hsrans_planes_base.hip) instead of the plain kernels.  The
 // merge's base may be `out` itself: the residue undone in place; any other overlap of the two is the caller's to refuse.
 hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, PlanesRule rule, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
 hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *base, PlanesRule rule, uint64_t n, void *out, hipStream_t stream);
@@ -134,8 +133,8 @@ struct PlanesGatherTask
 // asynchronous on `stream`, one workgroup per task (1 .. 2^31 - 1 of them, in device memory); planes.p[p]: plane p's workspace region where
 // bit p of work_mask is set, else the stored plane; every pointer 16-byte aligned (hipErrorInvalidValue otherwise).  base: null, or the
 // whole base tensor (hsrans_decode_device_planes_gather_delta, _gather_diff): output element (element + dst_delta) is what `rule` makes of
-// the planes' element and base element `element` — k_planes_merge_ranges_delta (hsrans_planes_delta.hip) or k_planes_merge_ranges_diff
-// (hsrans_planes_diff.hip) instead of the plain kernel
+// the planes' element and base element `element` — k_planes_merge_ranges_delta or k_planes_merge_ranges_diff (hsrans_planes_base.hip)
+// instead of the plain kernel
 hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const void *base,
                                       PlanesRule rule, void *out, hipStream_t stream);
 
@@ -265,31 +264,22 @@ hipError_t launch_planes_cut_batch(const PlanesCutBatchParams &cp, hipStream_t s
 hipError_t launch_planes_merge_batch_indirect(const PlanesSetRow *d_ranges, const uint32_t *d_header, const uint32_t *d_first_task, const uint64_t *d_base,
                                               const PlanesGatherBatchMember *d_members, const void *work, void *out, uint32_t grid, hipStream_t stream);
 
-// ---- tensors coded against a base (hsrans_*_device_planes_delta): hsrans_planes_delta.hip.  The planes hold in ^ base.  The one-tensor
-// launchers are the plain ones above, given a base; what that unit adds to them is the launch of its kernels alone — arguments checked and
-// grid formed by the caller, nothing returned: the caller asks hipGetLastError ----
-void planes_delta_split_kernel(uint32_t W, uint32_t grid, const uint8_t *in, const uint8_t *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
-void planes_delta_merge_kernel(uint32_t W, uint32_t grid, const PlanePtrs &planes, const uint8_t *base, uint64_t n, uint8_t *out, hipStream_t stream);
-void planes_delta_merge_ranges_kernel(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const uint8_t *base,
-                                      uint8_t *out, hipStream_t stream);
+// ---- tensors coded against a base (hsrans_*_device_planes_delta, hsrans_*_device_planes_diff): hsrans_planes_base.hip, the kernels of
+// both residue rules.  The one-tensor launchers are the plain ones above, given a base; what that unit adds to them is the launch of its
+// kernels alone, picked by `rule` — arguments checked and grid formed by the caller, nothing returned: the caller asks hipGetLastError ----
+void planes_base_split_kernel(PlanesRule rule, uint32_t W, uint32_t grid, const uint8_t *in, const uint8_t *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
+void planes_base_merge_kernel(PlanesRule rule, uint32_t W, uint32_t grid, const PlanePtrs &planes, const uint8_t *base, uint64_t n, uint8_t *out, hipStream_t stream);
+void planes_base_merge_ranges_kernel(PlanesRule rule, uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks,
+                                     const uint8_t *base, uint8_t *out, hipStream_t stream);
 // a PlanesBatchMember and the member's base; null: the member is split or merged as it is
 struct PlanesDeltaBatchMember
 {
   PlanesBatchMember m;
   const uint8_t *base;
 };
-hipError_t launch_planes_split_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
-hipError_t launch_planes_merge_delta_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
-
-// ---- tensors coded against a base as a zigzag difference (hsrans_*_device_planes_diff): hsrans_planes_diff.hip.  The planes hold the
-// zigzag of in - base (PlanesRule::kDiff).  The same five launches as the delta unit's above, to the same contracts, over the same
-// PlanesDeltaBatchMember tables ----
-void planes_diff_split_kernel(uint32_t W, uint32_t grid, const uint8_t *in, const uint8_t *base, uint64_t n, const PlanePtrs &planes, hipStream_t stream);
-void planes_diff_merge_kernel(uint32_t W, uint32_t grid, const PlanePtrs &planes, const uint8_t *base, uint64_t n, uint8_t *out, hipStream_t stream);
-void planes_diff_merge_ranges_kernel(uint32_t W, const PlanePtrs &planes, uint32_t work_mask, const PlanesGatherTask *d_tasks, uint32_t n_tasks, const uint8_t *base,
-                                     uint8_t *out, hipStream_t stream);
-hipError_t launch_planes_split_diff_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
-hipError_t launch_planes_merge_diff_batch(const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+// launch_planes_split_batch's and _merge_batch's contracts, over these records and under `rule`
+hipError_t launch_planes_split_base_batch(PlanesRule rule, const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
+hipError_t launch_planes_merge_base_batch(PlanesRule rule, const PlanesDeltaBatchMember *d_members, uint32_t count, uint32_t n_tasks, hipStream_t stream);
 
 // ---- the gathers that undo a delta while they fetch (hsrans_decode_device_planes_gather_indirect_delta, _gather_batch_delta,
 // _gather_batch_indirect_delta): hsrans_planes_gather_delta.hip.  Each launcher is its plain twin's above — the same arguments, the same

@@ -18,10 +18,10 @@ using namespace planes_detail;
 template <uint32_t W>
 __global__ __launch_bounds__(kThreads) void k_planes_split(const uint8_t *__restrict__ in, uint64_t n, PlanePtrs planes)
 {
-  split_lanes<W, false>(in, nullptr, planes.p, n, n / kLaneElements, (uint64_t)blockIdx.x * kThreads + threadIdx.x, blockIdx.x == gridDim.x - 1);
+  split_lanes<W, RuleNone>(in, nullptr, planes.p, n, n / kLaneElements, (uint64_t)blockIdx.x * kThreads + threadIdx.x, blockIdx.x == gridDim.x - 1);
 }
 
-// merge_lanes<W, false> written out: as a call to it these three kernels read all their arguments on entry and came out 3 to 4 instructions
+// merge_lanes<W, RuleNone> written out: as a call to it these three kernels read all their arguments on entry and came out 3 to 4 instructions
 // shorter and SLOWER — on 128 MiB, medians of 48 over three rounds, 58.5 against 57.1 µs (W = 2), 66.8 against 66.2 (4), 75.0 against 74.0 (8),
 // the first and the last beyond the quartiles of this form (CHANGELOG.md has the runs).  The splits lost nothing by the call.
 template <uint32_t W>
@@ -67,7 +67,7 @@ hipError_t launch_planes_split(uint32_t W, const void *in, const void *base, Pla
     return hipErrorInvalidValue;
   const uint8_t *src = (const uint8_t *)in;
   if (base != nullptr)
-    (rule == PlanesRule::kDiff ? planes_diff_split_kernel : planes_delta_split_kernel)(W, grid_of(n), src, (const uint8_t *)base, n, planes, stream);
+    planes_base_split_kernel(rule, W, grid_of(n), src, (const uint8_t *)base, n, planes, stream);
   else
     planes_with_width(W, [&](auto w) { k_planes_split<w()><<<grid_of(n), kThreads, 0, stream>>>(src, n, planes); });
   return hipGetLastError();
@@ -79,7 +79,7 @@ hipError_t launch_planes_merge(uint32_t W, const PlanePtrs &planes, const void *
     return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   if (base != nullptr)
-    (rule == PlanesRule::kDiff ? planes_diff_merge_kernel : planes_delta_merge_kernel)(W, grid_of(n), planes, (const uint8_t *)base, n, dst, stream);
+    planes_base_merge_kernel(rule, W, grid_of(n), planes, (const uint8_t *)base, n, dst, stream);
   else
     planes_with_width(W, [&](auto w) { k_planes_merge<w()><<<grid_of(n), kThreads, 0, stream>>>(planes, n, dst); });
   return hipGetLastError();

@@ -14,7 +14,7 @@ namespace
 using namespace planes_detail;
 
 // (the table walk — member_of, task_of, uni_ptr — and a task's lanes' work — split_lanes, merge_lanes — are planes_shuffle.h's, shared with
-// hsrans_planes_delta.hip)
+// hsrans_planes_base.hip)
 template <uint32_t W>
 __device__ __forceinline__ void split_task(const PlanesBatchMember *m)
 {
@@ -24,7 +24,7 @@ __device__ __forceinline__ void split_task(const PlanesBatchMember *m)
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     planes[p] = uni_ptr(m->plane[p]);
-  split_lanes<W, false>(in, nullptr, planes, t.n, t.whole, t.lane, t.last);
+  split_lanes<W, RuleNone>(in, nullptr, planes, t.n, t.whole, t.lane, t.last);
 }
 
 template <uint32_t W>
@@ -36,7 +36,7 @@ __device__ __forceinline__ void merge_task(const PlanesBatchMember *m)
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     planes[p] = uni_ptr(m->plane[p]);
-  merge_lanes<W, false>(planes, nullptr, out, t.n, t.whole, t.lane, t.last);
+  merge_lanes<W, RuleNone>(planes, nullptr, out, t.n, t.whole, t.lane, t.last);
 }
 
 // grid: the table's task total; count: its records

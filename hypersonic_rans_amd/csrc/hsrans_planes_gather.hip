@@ -64,7 +64,7 @@ hipError_t launch_planes_merge_ranges(uint32_t W, const PlanePtrs &planes, uint3
     return hipErrorInvalidValue;
   uint8_t *dst = (uint8_t *)out;
   if (base != nullptr)
-    (rule == PlanesRule::kDiff ? planes_diff_merge_ranges_kernel : planes_delta_merge_ranges_kernel)(W, planes, work_mask, d_tasks, n_tasks, (const uint8_t *)base, dst, stream);
+    planes_base_merge_ranges_kernel(rule, W, planes, work_mask, d_tasks, n_tasks, (const uint8_t *)base, dst, stream);
   else
     planes_with_width(W, [&](auto w) { k_planes_merge_ranges<w()><<<n_tasks, kThreads, 0, stream>>>(planes, work_mask, d_tasks, dst); });
   return hipGetLastError();

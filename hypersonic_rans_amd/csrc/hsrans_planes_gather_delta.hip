@@ -1,13 +1,18 @@
 // hsrans_planes_gather_delta.hip — the merges of the three gathers that undo a delta while they fetch
 // (hsrans_decode_device_planes_gather_indirect_delta, _gather_batch_delta, _gather_batch_indirect_delta): what comes out of the planes is
-// XORed with the base at the SOURCE element's index, as k_planes_merge_ranges_delta (hsrans_planes_delta.hip) does for one frame and ranges
+// XORed with the base at the SOURCE element's index, as k_planes_merge_ranges_delta (hsrans_planes_base.hip) does for one frame and ranges
 // on the host.  k_planes_merge_indirect_delta<W> is k_planes_merge_indirect<W> (hsrans_planes_gather_indirect.hip) with the base tensor as
 // one more argument; k_planes_merge_ranges_batch_delta and k_planes_merge_batch_indirect_delta are k_planes_merge_ranges_batch
 // (hsrans_planes_gather_batch.hip) and k_planes_merge_batch_indirect (hsrans_planes_gather_batch_indirect.hip) with a table of one base
 // address per member beside the member records, 0 for a member that goes as it is.  The cuts, the task lists and the control workspaces
 // are the plain calls': a base moves no row, no slot and no task.
-// The range merges' block body is written ONCE here, merge_block<W, kDelta>, for the three kernels (planes_shuffle.h says why the five
-// earlier copies are not shared; these three are new, so nothing had to stay as it was).
+// The range merges' block body is written ONCE here, merge_block<W, Rule>, for the three kernels (planes_shuffle.h says why the six
+// earlier copies are not shared; these three were new with it, so nothing had to stay as it was).  Rule is the residue rule as a type
+// (planes_shuffle.h): RuleNone for a member without a base, RuleXor with one.  The body still spells the XOR itself, in both places: with
+// the full block's step as Rule::restore_words, k_planes_merge_indirect_delta<2> came out at 304 instructions for 306, the two table-driven
+// kernels at 1768 for 1770 and 1909 for 1911 (one v_bfi_b32 that changes nothing and its constant gone; <4> and <8> as they were), and with
+// the head's and tail's step as Rule::merge_element too all five changed (304, 406, 398, 1767, 1900 for 306, 406, 404, 1770, 1911).
+// Nobody has measured either form, so neither is in; the diff forms of these gathers need both, and the measurement with them.
 // No aliasing: a base is never an output, so both are __restrict__.
 #include "hsrans_planes.h"
 #include "hsrans_plan.h"
@@ -30,28 +35,29 @@ static_assert(sizeof(PlanesGatherBatchTask) == 48 && sizeof(PlanesGatherBatchMem
 // The lane body.  src[p]: plane p's byte of the block's element 0 (a workspace region, a sub-slot or a stored plane); bsrc: the base's bytes
 // of the block's element 0, xbase + (t.src + first) * W — 16-byte aligned, src being a multiple of 16 elements and the base 16-byte aligned;
 // at: the output element of the block's element 0 (modulo 2^64: a head's may lie below 0); [lo, hi): the block's elements inside the range.
-// A whole block: W 16-byte plane loads and, with kDelta, W 16-byte base loads, all before the first use; merge16, the XOR, and W 16-byte
+// A whole block: W 16-byte plane loads and, with a base, W 16-byte base loads, all before the first use; merge16, the XOR, and W 16-byte
 // stores where the output address allows it, 16 element-wide stores otherwise.  The head and the tail of a range move element by element,
 // byte by byte, and read base bytes of their own elements only: nothing outside the range is read from a stored plane or from the base —
-// so nothing at or beyond elem_size * elements of a base — and nothing outside it is written.  Without kDelta `bsrc` is not looked at.
+// so nothing at or beyond elem_size * elements of a base — and nothing outside it is written.  With RuleNone `bsrc` is not looked at.
 // ---------------------------------------------------------------------------------------------------------------
-template <uint32_t W, bool kDelta>
+template <uint32_t W, typename Rule>
 __device__ __forceinline__ void merge_block(const uint8_t *const (&src)[W], const uint8_t *__restrict__ bsrc, uint64_t at, uint32_t lo, uint32_t hi, uint8_t *__restrict__ out)
 {
+  static_assert(std::is_same<Rule, RuleNone>::value || std::is_same<Rule, RuleXor>::value, "the XOR is spelled out below: no other rule yet");
   if (lo == 0 && hi == kLaneElements)
   {
-    uint32_t e[4 * W], b[kDelta ? 4 * W : 1], pl[W][4];
+    uint32_t e[4 * W], b[Rule::kBase ? 4 * W : 1], pl[W][4];
 #pragma unroll
     for (uint32_t p = 0; p < W; p++)
       load16(src[p], pl[p]);
-    if constexpr (kDelta)
+    if constexpr (Rule::kBase)
     {
 #pragma unroll
       for (uint32_t k = 0; k < W; k++)
         load16(bsrc + 16 * k, b + 4 * k);
     }
     merge16<W>(pl, e);
-    if constexpr (kDelta)
+    if constexpr (Rule::kBase)
     {
 #pragma unroll
       for (uint32_t k = 0; k < 4 * W; k++)
@@ -73,7 +79,7 @@ __device__ __forceinline__ void merge_block(const uint8_t *const (&src)[W], cons
     for (uint32_t p = 0; p < W; p++)
     {
       uint8_t b = 0;
-      if constexpr (kDelta)
+      if constexpr (Rule::kBase)
         b = bsrc[i * W + p]; // (a base byte of the range's own element)
       out[(at + i) * W + p] = src[p][i] ^ b;
     }
@@ -108,7 +114,7 @@ __device__ __forceinline__ void merge_task_single(const PlanePtrs &planes, uint3
 #pragma unroll
   for (uint32_t p = 0; p < W; p++)
     src[p] = planes.p[p] + (((work_mask >> p) & 1) != 0 ? t.work_pos : t.src) + b.first;
-  merge_block<W, true>(src, xbase + (t.src + b.first) * W, t.src + b.first + (uint64_t)t.dst_delta, b.lo, b.hi, out);
+  merge_block<W, RuleXor>(src, xbase + (t.src + b.first) * W, t.src + b.first + (uint64_t)t.dst_delta, b.lo, b.hi, out);
 }
 
 // Any grid: workgroup g serves tasks g, g + grid, ... below the total the cut left (k_planes_merge_indirect's walk)
@@ -131,14 +137,14 @@ __global__ __launch_bounds__(kThreads) void k_planes_merge_indirect_delta(PlaneP
 }
 
 // ---- rows of many frames: the task as the workgroup holds it (every field the same on every lane) and its member's record, as the plain
-// batch merges read them; xbase: the member's base, 0 (never looked at) without kDelta ----
+// batch merges read them; xbase: the member's base, 0 (never looked at) under RuleNone ----
 struct Task
 {
   uint64_t src, work_pos, plane_step, dst_delta;
   uint32_t lo, hi;
 };
 
-template <uint32_t W, bool kDelta>
+template <uint32_t W, typename Rule>
 __device__ __forceinline__ void merge_task_member(const Task &t, const PlanesGatherBatchMember *m, uint64_t xbase, const uint8_t *work, uint8_t *__restrict__ out)
 {
   Block b;
@@ -153,20 +159,20 @@ __device__ __forceinline__ void merge_task_member(const Task &t, const PlanesGat
     const uint64_t at = ((coded_mask >> p) & 1) != 0 ? (uint64_t)work + t.work_pos + p * t.plane_step : stored + t.src;
     src[p] = global_at(at) + b.first;
   }
-  const uint8_t *bsrc = kDelta ? global_at(xbase) + (t.src + b.first) * W : nullptr;
-  merge_block<W, kDelta>(src, bsrc, t.src + b.first + t.dst_delta, b.lo, b.hi, out);
+  const uint8_t *bsrc = Rule::kBase ? global_at(xbase) + (t.src + b.first) * W : nullptr;
+  merge_block<W, Rule>(src, bsrc, t.src + b.first + t.dst_delta, b.lo, b.hi, out);
 }
 
-template <bool kDelta>
+template <typename Rule>
 __device__ __forceinline__ void merge_member(const Task &t, const PlanesGatherBatchMember *m, uint64_t xbase, const uint8_t *work, uint8_t *__restrict__ out)
 {
   const uint32_t W = uni(m->W);
   if (W == 2)
-    merge_task_member<2, kDelta>(t, m, xbase, work, out);
+    merge_task_member<2, Rule>(t, m, xbase, work, out);
   else if (W == 4)
-    merge_task_member<4, kDelta>(t, m, xbase, work, out);
+    merge_task_member<4, Rule>(t, m, xbase, work, out);
   else if (W == 8)
-    merge_task_member<8, kDelta>(t, m, xbase, work, out);
+    merge_task_member<8, Rule>(t, m, xbase, work, out);
 }
 
 // a member with a base takes the delta body, one without the plain one: a branch on a scalar, per workgroup (k_planes_merge_delta_batch's)
@@ -175,9 +181,9 @@ __device__ __forceinline__ void merge_with_base(const Task &t, const PlanesGathe
 {
   const uint64_t xbase = uni64(xbases[member]);
   if (xbase != 0)
-    merge_member<true>(t, members + member, xbase, work, out);
+    merge_member<RuleXor>(t, members + member, xbase, work, out);
   else
-    merge_member<false>(t, members + member, 0, work, out);
+    merge_member<RuleNone>(t, members + member, 0, work, out);
 }
 
 // grid: one workgroup per task of the list

@@ -1439,7 +1439,7 @@ int hsrans_decode_device_planes_gather_batch_indirect_delta(hsrans_ctx *ctx, hsr
  * that may coincide with other reads and may meet nothing written nor a frame it is decoded against; the in-place exception
  * d_out == d_base (out_capacity <= base_bytes) for the three whole-tensor decodes (hsrans_planes_merge_diff_device,
  * hsrans_decode_device_planes_diff, hsrans_decode_device_planes_diff_batch: every lane reads its base elements before it writes,
- * and no lane reads another's); no aliasing at all in the gather.  The kernels are those of hsrans_planes_diff.hip: the delta
+ * and no lane reads another's); no aliasing at all in the gather.  The kernels are the _diff ones of hsrans_planes_base.hip: the delta
  * kernels' loads and stores with a handful of integer instructions per word between them.
  * The diff forms of the other three gathers (_gather_indirect, _gather_batch, _gather_batch_indirect) are not offered yet.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "hsrans_batch.h"
+#include "kernels_layout.h"
 
 namespace hsrans
 {
@@ -71,11 +72,10 @@ size_t batch_boundaries(const uint64_t *total_groups, uint32_t M, uint32_t membe
     return 1;
   if (chains - 1 > cap)
     return 0;
-  const uint32_t per_class = waves >= 4 ? waves / 4 : 1;
   auto weight_of = [&](uint64_t i) { // slot i of the member in natural order: its first-half workgroups' waves, then its second-half ones
     const uint64_t slot = i / chains_per_slot, wg_local = slot / waves;
     const uint32_t wave = (uint32_t)(slot % waves);
-    return (uint64_t)weights[(wg_local >= n[member] ? 4 : 0) + std::min(3u, wave / per_class)];
+    return (uint64_t)weights[wave_class(wg_local >= n[member], wave, waves)];
   };
   uint64_t all = 0;
   for (uint64_t k = 0; k < chains; k++)
@@ -153,9 +153,7 @@ BatchDeal batch_deal(const std::vector<BatchDealMember> &members, uint32_t grid,
       for (uint32_t i = 0; i < nslots; i++)
       {
         const uint32_t wg = slot_of[i] / waves, wave = slot_of[i] % waves;
-        const uint32_t per_class = waves >= 4 ? waves / 4 : 1;
-        const uint32_t cls = (wg >= first_half ? 4 : 0) + std::min(3u, wave / per_class);
-        cumw[i + 1] = cumw[i] + weights[cls];
+        cumw[i + 1] = cumw[i] + weights[wave_class(wg >= first_half, wave, waves)];
       }
       const uint64_t G = mem.chain_start[nc];
       bounds[0] = 0;

@@ -18,6 +18,7 @@
 #include "hsrans_cpu.h"
 #include "hsrans_encode.h"
 #include "hsrans_kernels.h"
+#include "kernels_layout.h"
 
 using namespace hsrans;
 
@@ -284,7 +285,7 @@ static int calibrate_impl(hsrans_ctx *ctx, uint32_t bits, uint32_t iterations, u
           for (uint32_t w = 0; w < W; w++)
           {
             const double t = (double)(f[w] - f[W]) / 100.0; // us
-            const uint32_t cls = (w / waves >= first_half ? 4 : 0) + (w % waves) / 4;
+            const uint32_t cls = wave_class(w / waves >= first_half, w % waves, waves); // (waves == 16: four of a class in a row)
             cls_t[cls] += t, cls_n[cls] += 1;
             launch_last = t > launch_last ? t : launch_last;
           }

@@ -1,4 +1,5 @@
-// Launch interface between the C ABI (hsrans_capi.cpp) and the gfx950 kernels (hsrans_kernels.hip).
+// Launch interface between the C ABI (hsrans_capi.cpp) and the gfx950 kernels (hsrans_kernels.hip): the kernels' parameter structs and the
+// launch_* functions.  What decides a launch — shapes, the kernel choice, shares — is hsrans_launch.h (hsrans_launch.cpp), included here.
 #ifndef HSRANS_KERNELS_H
 #define HSRANS_KERNELS_H
 
@@ -7,6 +8,7 @@
 
 #include "hsrans_plan.h"
 #include "hsrans_tuning.h"
+#include "hsrans_launch.h"
 
 namespace hsrans
 {
@@ -28,7 +30,7 @@ struct PersistentArgs
   // half_base[h] + b' * wg_chains[h] + class_off[k] + (j & 3) * run_len[k].  static_total = all static chains.
   uint32_t run_len[8], class_off[8], wg_chains[2], half_base[2], static_total;
   const uint2 *table;       // host-built decode table (kPlanHasHist plans) or null: build it in the kernel
-  uint32_t table_mode;      // 3: one uint2 per slot; 4: coarse + fine tables (bits 13..15); 5: as 3, left in global memory; see hsrans_kernels.hip
+  uint32_t table_mode;      // 3: one uint2 per slot; 4: the rank table (bits 13..15); 5: as 3, left in global memory; see kMode* in kernels_layout.h
   uint32_t dual;            // two chains per wave: k_decode_dual
   const uint16_t *hist_copy; // the 256 counts that table was built from (device copy inside the plan)
   unsigned long long *counters; // [kDynQueues * kDynQueueStride] monotonic queue heads of THIS launch's counter set (never reset, see run_persistent)
@@ -78,13 +80,7 @@ struct PartArgs
 // part of one; sub-runs are cut at chain boundaries, so a group can straddle two of them)
 constexpr uint32_t kGroupPartShift = 16;
 
-// k_decode_dealt (kernels_dealt.h): the host-dealt one-round launch of block_/mt_ plans with checkpoints
-constexpr uint32_t kDealtGridMax = 512;
-struct DealtTable
-{
-  uint32_t begin[kDealtGridMax + 1]; // chains; begin[grid] = n_chains
-  uint16_t split[kDealtGridMax];     // chains of the share that belong to its first block (>= the share's length: one block only)
-};
+// k_decode_dealt (kernels_dealt.h): its parameters beside the dealing (DealtTable, hsrans_launch.h)
 struct DealtParams
 {
   const uint8_t *stream;
@@ -146,7 +142,7 @@ struct KParams
   uint32_t spread;        // grouped plans of single-piece chains: the fewest chains of a coded block that is not the last (k_decode_spread takes the launch when its longest share is shorter); 0 = never
   uint32_t groups_lean;   // 64-state plan, every group a mergeable run or fills only: the lean instantiation of k_decode_grouped
   uint32_t group_prio;    // grouped launches: per mille of its run the younger half of a workgroup's waves decodes at raised priority (s_setprio)
-  // ... per wave class (class = (workgroup in the grid's second half) * 4 + wave / (waves / 4), as everywhere): [0..7] where a group's chains are
+  // ... per wave class (wave_class, kernels_layout.h): [0..7] where a group's chains are
   // split evenly over the waves, [8..9] (by grid half) where the split already follows the class weights.  All zero: group_prio's rule.
   uint16_t group_prio_class[10];
   // grouped launches: wave k of a workgroup in grid half h takes chains [count * cum[h][k] / cum[h][waves], count * cum[h][k+1] / cum[h][waves])
@@ -215,125 +211,9 @@ struct BatchGroupParams
   uint32_t n_groups, bits, group_prio, reserved;
   uint16_t group_cum[2][17];
 };
-struct BatchGroupShape
-{
-  uint32_t grid, waves, lds;
-  uint16_t group_cum[2][17];
-};
-BatchGroupShape batch_grouped_shape(const Tuning &tn, const struct DeviceGeom &dg, uint32_t bits, uint32_t n_groups, uint64_t n_chains);
+// (the two launches' shapes: batch_grouped_shape, batch_direct_shape)
 hipError_t launch_batch_grouped(const BatchGroupParams &bp, const BatchGroupShape &shape, hipStream_t stream);
-
-constexpr uint32_t kBatchDirect = 0, kBatchPair = 1, kBatchDualPack = 2, kBatchDualRank = 3; // which kernel a shared launch runs
-struct BatchShape
-{
-  uint32_t grid, waves, lds, states, kind;
-  uint32_t weights[8]; // per-mille run lengths of the 8 wave classes (class = (workgroup in the grid's second half) * 4 + wave / 4)
-};
-
-struct LaunchInfo
-{
-  uint32_t grid, block, lds_bytes, waves_per_block, chains, shared_table, walk, two_level, table_mode, chains_per_wave;
-  uint32_t class_weights[8]; // the per-mille run lengths of the 8 wave classes this launch was shaped with (LaunchShape::weights)
-  uint32_t dynamic_groups;   // grouped launches: groups handed out by the ticket counter (1) or in static order (0)
-  uint32_t spread;           // grouped plan launched by k_decode_spread (chains dealt out evenly, two tables per workgroup); 2: by k_decode_dealt (host-dealt shares)
-};
-
-// what the launcher needs to know about the device a context lives on
-struct DeviceGeom
-{
-  uint32_t num_cus, max_lds;
-  // per-mille chain lengths of the 8 wave classes of the 64-state one-chain-per-wave launch, fitted to THIS device by
-  // hsrans_ctx_calibrate (0 = not calibrated: the constants fitted on the development box, g_direct_weights)
-  uint32_t have_direct_weights;
-  uint32_t direct_weights[8];
-  // The same fit at several RUN LENGTHS (mean groups per wave of the launch; ascending): a wave's time is its prologue plus its groups
-  // at its class's rate, so the lengths that make all classes finish together depend on how long the runs are — an old wave's
-  // head start counts for less in a long run.  hsrans_ctx_calibrate fits the 48 MiB launch (96 groups per wave),
-  // hsrans_ctx_calibrate_runs longer ones; direct_weights_for interpolates between the fitted lengths (in log run length).
-  uint32_t n_weight_sets;
-  uint32_t set_run[4];
-  uint32_t set_weights[4][8];
-};
-// the per-mille chain lengths of the 8 wave classes for a 64-state one-chain-per-wave launch whose runs average run_groups
-void direct_weights_for(const Tuning &tn, const DeviceGeom &dg, uint64_t run_groups, uint32_t out[8]);
-
-// the launch all members of a batch of 64-state plans with 8-byte tables (bits <= 12) share; max_bits = the widest member
-// (total_groups: all members' groups together — the class weights follow the launch's mean run length; 0 = the default set)
-BatchShape batch_direct_shape(const Tuning &tn, const DeviceGeom &dg, uint32_t max_bits, uint64_t total_groups = 0, uint32_t states = 64);
 hipError_t launch_batch_direct(const BatchParams &bp, const BatchShape &shape, hipStream_t stream);
-
-// a launch's shape as it follows from plan header + device (launch_shape)
-struct LaunchShape
-{
-  int mode;         // decode-table layout (kMode* in hsrans_kernels.hip)
-  bool shared, walk, dual;
-  uint32_t waves, lds, grid, resident, private_pair;
-  uint32_t weights[8]; // per-mille run length of the 8 wave classes
-};
-
-// What decides a launch besides the plan header, the device and the tuning: scalars only.  launch_facts reads them off a KParams, so
-// every caller of launch_decode describes its launch the same way; hsrans_launch_choice takes them as they are (tests, planning).
-struct LaunchFacts
-{
-  bool persistent = false;       // a kPlanMergeable plan: PersistentArgs is filled
-  uint32_t table_mode = 0;       // ... its host-built decode table (kMode*); 0: the kernel builds its own
-  uint32_t interval = 0;         // ... uniform chains of this many groups; 0: chains of any length, one (run) per wave
-  bool dual = false;             // ... two chains per wave (choose_table)
-  uint32_t n_groups = 0;         // grouped plan (block_/mt_ with checkpoints): its groups; 0: none
-  bool groups_lean = false;      // ... 64 states, every group a mergeable run or fills only
-  uint32_t spread_min_block = 0; // ... KParams::spread
-  bool index_pass = false;       // the launch records checkpoints (hsrans_capi_index.cpp)
-  bool single_valid = false;     // one chain of one rANS piece (SingleArgs::valid)
-  uint32_t single_ring_entries = 0;
-  bool calibrating = false;      // hsrans_ctx_calibrate's launches: per-wave finish times
-  bool tickets = false;          // grouped: the launch has a ticket counter
-  bool parts = false;            // a rank's sub-runs in one launch (PartPlan) ...
-  uint32_t n_parts = 0;          // ... so many: 1 .. kMaxLaunchParts, anything else is refused
-  bool dealt = false;            // the plan has a valid dealing (deal_shares) ...
-  uint32_t dealt_weights[8] = {}; // ... made with these class weights
-};
-
-// one value per kernel instantiation a single-plan decode launch can run (the table in hsrans_kernels.hip: name + launch)
-enum KernelId : uint32_t
-{
-  kKDecodePrivate,                   // + mode (kModePack .. kModeTwoLevel): k_decode<mode, false>
-  kKDecodeShared = kKDecodePrivate + 3, // + mode (kModePack .. kModeSpill): k_decode<mode, true>
-  kKDual = kKDecodeShared + 6,       // + 1: the rank table
-  kKPersist = kKDual + 2,            // + 1: the rank table
-  kKDirect = kKPersist + 2,          // + mode (kModePack .. kModeSpill)
-  kKCalibrate = kKDirect + 6,
-  kKGrouped,                         // + mode (kModePack .. kModeRank): k_decode_grouped<mode, false>
-  kKGroupedLean = kKGrouped + 5,     // + mode - kModeTwoLevel (.. kModeRank): <mode, true>
-  kKGroupedParts = kKGroupedLean + 3, // + mode - kModePack64 (.. kModeRank): <mode, true, true>
-  kKSpread = kKGroupedParts + 2,     // + 1: PARTS
-  kKDealtNt = kKSpread + 2,          // k_decode_dealt<false, false>
-  kKDealt,                           // <true, false>
-  kKDealtParts,                      // <true, true>
-  kKDealtRank,                       // + 2 * (bits - 13) + PARTS: k_decode_dealt_rank<bits, PARTS>
-  kKSingle = kKDealtRank + 4,
-  kKernelCount
-};
-
-// the static shares of a uniform-interval launch (PersistentArgs' fields of the same names)
-struct StaticShares
-{
-  uint32_t static_per_wave, run_len[8], class_off[8], wg_chains[2], half_base[2], static_total;
-};
-
-// Which kernel a single-plan launch runs and how: everything launch_decode needs that is not a pointer.
-struct LaunchChoice
-{
-  hipError_t error;      // hipSuccess, or what launch_decode returns without launching anything
-  KernelId kernel;
-  uint32_t grid, waves, lds; // of the launch (the spread and dealt launches have their own, not the shape's)
-  LaunchShape shape;     // (weights: what the launch's shares were sized with — the dealing's for k_decode_dealt)
-  uint32_t spread;       // LaunchInfo::spread: 0, 1 = k_decode_spread, 2 = k_decode_dealt
-  bool dynamic_groups;   // grouped: groups behind the first round go by ticket
-  uint16_t cum[2][17];   // grouped / spread: KParams::group_cum; dealt: DealtParams::cum
-  StaticShares shares;   // uniform-interval launches
-  uint32_t run_chains;   // one-chain-per-wave launches: PersistentArgs::run_chains
-  uint32_t gap_chains;   // dealt: DealtParams::gap_chains
-};
 
 // K2: device-side walk of an mt_ stream's header chain (mt_rANS32x64_16w_decode.cpp:41-96), the device twin of the host
 // planner.  Pass 1 (k_mt_chase, one wavefront) follows the chain with one 16-byte read per block and lists the blocks;
@@ -474,19 +354,6 @@ __host__ __device__ inline IndexPart index_block_part(const IndexBlock &b, uint3
   return r;
 }
 
-// k_decode_spread (kernels_spread.h): G = two 16-wave workgroups per CU; workgroup b's share of the plan's N chains starts at
-// spread_share_begin(b): the first half of the grid weighs w1 per workgroup, the second half w2 (the sums of their waves' age-class
-// weights).  A share's piece records are kept in LDS: at most kSpreadMaxShare chains.
-constexpr uint32_t kSpreadMaxShare = 127;
-inline uint32_t spread_grid(const DeviceGeom &dg) { return 2 * dg.num_cus; }
-__host__ __device__ inline uint32_t spread_share_begin(uint32_t n_chains, uint32_t b, uint32_t grid, uint32_t w1, uint32_t w2)
-{
-  const uint32_t fh = (grid + 1) / 2;
-  const uint64_t total = (uint64_t)fh * w1 + (uint64_t)(grid - fh) * w2;
-  const uint64_t cum = b <= fh ? (uint64_t)b * w1 : (uint64_t)fh * w1 + (uint64_t)(b - fh) * w2;
-  return (uint32_t)((uint64_t)n_chains * cum / total);
-}
-
 // what the count kernels leave for the fill kernels and the host (in the new plan's arena: zeroed)
 constexpr uint32_t kIndexNoFewest = 0xFFFFFFFFu;
 struct IndexResult
@@ -563,8 +430,6 @@ struct IndexPassTask
   uint32_t member, chain;
 };
 constexpr uint32_t kIndexPassModes = 3; // the table layouts waves build for themselves: <= 11 bits, 12 bits, 13-15 bits
-// the layout a recording pass over a plan of `bits` decodes with (launch_shape's rule for private tables)
-int index_pass_mode(uint32_t bits);
 // tasks [0, n_tasks) at d_tasks, all of layout `mode`, the widest histogram among their members max_bits wide: one launch, one wavefront a task
 hipError_t launch_index_pass_batch(int mode, uint32_t max_bits, const IndexPassTask *d_tasks, uint32_t n_tasks, const IndexPassMember *d_members, hipStream_t stream);
 // count and fill for n members' argument structs at d_args; most_blocks: the largest n_base (max_blocks) among them; d_status_of[k]: member
@@ -626,15 +491,6 @@ __host__ __device__ inline uint64_t gather_range_tasks(uint64_t offset, uint64_t
 {
   return length == 0 ? 0 : (offset + length - 1) / segment - offset / segment + 1;
 }
-struct GatherShape
-{
-  int mode;    // decode-table layout (kMode*)
-  bool shared; // one LDS table per workgroup, copied from the plan's host-built table; else a table per wave, built from the pieces' histograms
-  uint32_t waves, lds, grid;
-};
-// the launch of n_tasks tasks on a plan: table_mode = the plan's host-built table (PersistentArgs::table_mode; 0: it has none).  The table
-// layout is the one the plan decodes with: its host-built table's, else what launch_shape gives a plan whose waves build their own.
-GatherShape gather_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t n_tasks);
 // asynchronous on `stream`; one launch
 hipError_t launch_gather(const GatherParams &gp, const GatherShape &shape, hipStream_t stream);
 
@@ -665,10 +521,6 @@ struct GatherRangesParams
   uint64_t segment;
   uint32_t segment_shift; // log2(segment) where it is a power of two, else 0: offset / segment without a division
 };
-// the launch shape for ranges only the device knows.  The grid is sized from what the host does know — no more tasks can have
-// destinations of their own than max_count + dst_capacity / segment — and capped at the waves the device holds at once; the kernel
-// strides over the tasks, so a total above either bound still finishes.
-GatherShape gather_ranges_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, uint32_t table_mode, uint32_t max_count, uint64_t dst_capacity, uint64_t segment);
 // asynchronous on `stream`; two launches, nothing else (capturable)
 hipError_t launch_gather_ranges(const GatherParams &gp, const GatherCutParams &cp, const GatherShape &shape, hipStream_t stream);
 
@@ -696,11 +548,6 @@ struct GatherSetParams
   uint8_t *dst; // device, any alignment
   uint32_t table_bytes; // the largest table among the kind's members: what the LDS layout leaves room for per workgroup (shared) or wave (a multiple of 16)
 };
-// the LDS a decode table of layout `mode` takes at `bits`, rounded up to 16 bytes (0: the layout that stays in global memory)
-uint32_t gather_table_bytes(int mode, uint32_t bits);
-// the launch of n_tasks tasks of one kind (mode, shared): waves per workgroup and LDS by gather_shape's rule for table_bytes, the kind's
-// largest table; the grid is that of n_tasks entries (a launch whose entries are padded is given its own by the caller)
-GatherShape gather_set_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t n_tasks);
 // asynchronous on `stream`; one launch
 hipError_t launch_gather_set(const GatherSetParams &sp, const GatherShape &shape, hipStream_t stream);
 
@@ -762,43 +609,12 @@ struct GatherSetRangesParams
   uint32_t kind, pos_lo, pos_hi; // the launch's kind and its positions [pos_lo, pos_hi)
   uint32_t table_bytes;          // as GatherSetParams::table_bytes
 };
-// the launch shape of one kind for ranges only the device knows: layout, waves and LDS are gather_set_shape's for the most tasks the kind
-// can have — max_count + dst_capacity / min_segment (the kind's smallest member segment; 0: no member can have a task) have destinations
-// of their own, gather_ranges_shape's bound — the shared kinds add one unit of padding per member that can be named; the grid is capped at
-// the workgroups the device holds at once, and the kernels loop
-GatherShape gather_set_ranges_shape(const DeviceGeom &dg, int mode, bool shared, uint32_t table_bytes, uint32_t max_count, uint64_t dst_capacity, uint64_t min_segment,
-                                    uint32_t kind_members);
 // asynchronous on `stream`; one k_set_cut and one k_set_ranges per kind whose shape has a grid, nothing else (capturable)
 hipError_t launch_gather_set_ranges(const GatherSetCutParams &cp, uint8_t *dst, const GatherShape shapes[kGatherKinds], const uint32_t table_bytes[kGatherKinds], hipStream_t stream);
 
-DeviceGeom default_geom(); // MI355X: 256 CUs, 160 KiB LDS (used where no device is at hand: host-side index sizing)
-LaunchShape launch_shape(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f); // (reads persistent, table_mode, interval, dual, n_groups, index_pass)
-struct TableChoice
-{
-  uint32_t mode; // 0: none (the kernel builds its own), else kMode* of the host-built table
-  bool dual;     // two chains per wave (k_decode_dual)
-};
-TableChoice choose_table(const Tuning &tn, uint32_t bits, uint32_t states, bool direct);
-// chain boundaries (in groups) of the direct launch: one chain per resident wave, sized by class weight; see hsrans_kernels.hip
-size_t direct_boundaries(const Tuning &tn, const DeviceGeom &dg, uint32_t states, uint32_t bits, uint64_t total_groups, uint64_t *out, size_t cap);
-// host-side builder of the bits >= 13 coarse/fine decode table (layout: kModeCoarse in hsrans_kernels.hip); returns entries written
-size_t build_rank_table(const uint16_t counts[256], uint32_t bits, uint2 *out, size_t capacity_entries);
-size_t rank_table_entries(uint32_t bits);
-// widest histogram the shared 8-byte-per-slot table (MODE 3) is used for
-uint32_t pack64_max_bits();
 // per device (call with the device current): raise the dynamic-LDS limit of every kernel variant to the gfx950 maximum
 // (160 KiB) and report the device's geometry
 hipError_t prepare_kernels(DeviceGeom *geom);
-// A single-plan decode launch is decided in ONE place, choose_launch: a pure function of the tuning, the plan header, the device and the
-// LaunchFacts — no pointer, no HIP call, nothing written — that names the kernel (KernelId), its grid, workgroup and LDS, and the scalars
-// the kernel's parameters still need.  It is also where the launch is refused: `parts` with n == 0 or n > kMaxLaunchParts and shares a
-// uniform-interval launch cannot address are hipErrorInvalidValue, `parts` with a kernel that cannot count them (plans without groups,
-// groups that are not lean, tables other than the 8-byte and the rank table) hipErrorNotSupported.
-LaunchChoice choose_launch(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f);
-// whether k_decode_dealt can take the plan at all (lean grouped, single-piece chains, 64 states, <= 11 bits or 13 / 14 bits with
-// Tuning::dealt_wide, no index pass, two workgroups' LDS per CU): choose_launch's test, and dplan_launch's for whether dealing is worth doing
-bool dealt_eligible(const Tuning &tn, const PlanHeader &h, const DeviceGeom &dg, const LaunchFacts &f);
-LaunchInfo launch_info_of(const LaunchChoice &c, uint32_t chains); // what hsrans_dplan_launch_info reports of the launch
 const char *kernel_name(KernelId k); // as rocprofv3 --kernel-trace prints it, without return type and parameter list
 // `parts` (may be null): the launch decodes a rank's sub-runs and publishes a completion word per sub-run (PartArgs).  In: n,
 // chain_end[], group_units[k] = groups of the plan's group list that overlap part k, cum[k] = the units counted into part k by all
@@ -810,7 +626,6 @@ struct PartPlan
   const uint32_t *group_units;
   uint32_t *cum;
 };
-LaunchFacts launch_facts(const KParams &kp, const PartPlan *parts, const uint32_t *dealt_weights /* null: no valid dealing */);
 // asynchronous on `stream` of the current device; no allocation, no synchronisation (graph-capturable).
 // facts (launch_facts) -> choice (choose_launch) -> the launch-dependent kernel parameters -> one launch through the kernel table ->
 // *info from the choice.  `dealt` + `dealt_weights` (both or neither): the plan's shares for k_decode_dealt and the class weights
@@ -818,14 +633,6 @@ LaunchFacts launch_facts(const KParams &kp, const PartPlan *parts, const uint32_
 // cum[] itself moves only once the launch has been queued (hipSuccess), so a refused launch leaves host and device totals in step.
 hipError_t launch_decode(const Tuning &tn, const KParams &kp, const PlanHeader &h, const DeviceGeom &dg, hipStream_t stream, LaunchInfo *info, const PartPlan *parts = nullptr,
                          const DealtTable *dealt = nullptr, const uint32_t *dealt_weights = nullptr);
-// The dealing of k_decode_dealt: block k = chains [block_begin[k], block_begin[k + 1]) (n_blocks + 1 entries, the last = n_chains), every one a coded
-// block of single-piece mergeable chains.  Workgroup shares by age-class weight (the one-chain-per-wave launch's, this device's own once
-// calibrated), each cut back where it would reach into a third block.  false: the plan does not suit the launch (too few chains for the
-// device's waves, shares that would have to span more than two blocks, a share beyond 65,535 chains).  weights_out: the 8 class weights used
-// (the caller's cache key: a calibration changes them).
-bool deal_shares(const Tuning &tn, const DeviceGeom &dg, const uint32_t *block_begin, uint32_t n_blocks, uint32_t n_chains, uint64_t total_groups, uint32_t bits, DealtTable *out,
-                 uint32_t weights_out[8]);
-void dealt_weights_now(const Tuning &tn, const DeviceGeom &dg, uint64_t run_groups, uint32_t bits, uint32_t weights_out[8]); // run_groups: groups per wave of the launch, on average
 
 } // namespace hsrans
 

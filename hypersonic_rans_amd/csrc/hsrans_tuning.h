@@ -18,7 +18,7 @@ namespace hsrans
 // reshaped.  The nine lists are then rescaled to a sum of at most 8000 (33 .. 6486 a class), the two others
 // are taken as written.  What the launches need of a list and the domain gives them (tests/test_geometry_domain.py holds a model of every
 // share rule to it):
-//   - a class of at least 10 in each half, so that no cumulative table (w / 10 per wave: cum_from_weights, group_cum_of) ends in 0.
+//   - a class of at least 10 in each half, so that no cumulative table (w / 10 per wave: class_cum_of, hsrans_launch.cpp) ends in 0.
 //     With a zero half k_decode_grouped's weighted split gives every wave of the grid's second half the share [0, 0) of its block — the
 //     block is never decoded — and k_decode_dealt divides by the table's last entry.  A zero CLASS beside live ones is safe in every
 //     kernel (a wave whose share is empty skips its run: `first >= last` in run_grouped, run_spread's `while (i < last)`, `have` in

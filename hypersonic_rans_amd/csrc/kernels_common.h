@@ -1,7 +1,10 @@
-// kernels_common.h — Shared device code of the decode kernels: constants, table layouts, the stream ring (LDS-DMA), the in-kernel table build, the group step and its hand-scheduled forms, the output path, the generic chain runner.
-// Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the host-side launcher).
+// kernels_common.h — Shared device code of the decode kernels: the stream ring (LDS-DMA), the in-kernel table build, the group step and its hand-scheduled forms, the output path, the generic chain runner.
+// The ring's sizes, the table layouts and the LDS layout, which the host's launch policy shares, are in kernels_layout.h.
+// Part of the one device translation unit hsrans_kernels.hip (which includes the parts in dependency order and holds the kernel table and the launches).
 #ifndef HSRANS_KERNELS_COMMON_H
 #define HSRANS_KERNELS_COMMON_H
+
+#include "kernels_layout.h"
 
 namespace hsrans
 {
@@ -9,14 +12,6 @@ namespace hsrans
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t kRingSlots = 4;
-constexpr uint32_t kChunkBytes = 512; // 32 lanes x 16 B
-constexpr uint32_t kRingBytes = kRingSlots * kChunkBytes; // 2 KiB
-// (the mirror is 128 bytes: the first 64 words of the ring, copied behind its end)
-constexpr uint32_t kWaveRingBytes = kRingBytes + 256;     // per wave (ring + mirror, 256-byte granular)
-// the hand-scheduled loop of k_decode_direct (run_groups_fast) keeps its read cursor as a plain LDS address that is only
-// re-based every 4 groups, so it can run up to one chunk past the ring's end: the mirror there is a whole chunk
-constexpr uint32_t kFastRingBytes = kRingBytes + kChunkBytes;
 constexpr uint32_t kConsume = 1u << 15; // rans.h:8 DecodeConsumePoint16
 // Per-wave time stamps (tools/stamps.py, tools/stamps_grouped.py, tools/tune_weights.py) exist only in the diagnostic build
 // (`make stamps` -> lib/libhsrans_hip_stamps.so: -DHSRANS_HAVE_STAMPS=1 -DHSRANS_GROUP_STAMPS=1; the Python layer loads it when
@@ -26,69 +21,6 @@ constexpr uint32_t kConsume = 1u << 15; // rans.h:8 DecodeConsumePoint16
 #define HSRANS_HAVE_STAMPS 0
 #endif
 #define HSRANS_STAMPS(kp) (HSRANS_HAVE_STAMPS && (kp).stamps != nullptr)
-constexpr uint32_t kSingleMirror = 256;  // k_decode_single: ring entries mirrored behind the ring's end (4 groups x 64 words)
-
-// decode-table layouts
-constexpr int kModePack = 0;     // bits <= 11: uint32 per slot = sym | freq << 8 | (slot - cumul) << 20
-constexpr int kModePackM1 = 1;   // bits == 12: same with freq - 1 (freq == 4096 must fit 12 bits)
-constexpr int kModeTwoLevel = 2; // bits >= 13: uint8 sym[2^bits] + uint32 {freq | cumul << 16}[256]
-constexpr int kModePack64 = 3;   // bits <= 14, table shared by a workgroup: uint2 per slot = {freq | sym << 24, slot - cumul}:
-                                 // v_mad_u32_u24 takes freq (low 24 bits) and the bias operand as they are, v_perm takes byte 3
-
-// bits >= 14 with a host-built table (persistent 64-state launches): uint8 rank[2^bits] — the slot's symbol as its RANK by
-// frequency — followed by 256 x uint2 {freq | sym << 24, -cumul} ordered by rank.  A byte gather (the slot is the LDS address in
-// k_decode_dual), then an 8-byte gather from a 2 KiB table in which the 32 most frequent symbols — nearly every lane of a group —
-// sit in 32 different bank pairs; x' = freq * (x >> bits) + slot - cumul.  18 / 34 KiB at 14 / 15 bits instead of 128 / 256 KiB.
-// (Round 2's layout for these widths was a coarse table of 4096 granules + a fine table for the granules that straddle a symbol
-// boundary: 16.4 vector instructions and 11.2 LDS cycles per group against 12.3 and 13.3 here — 62.2 -> 56.7 us at 15 bits.)
-constexpr int kModeRank = 4;
-// The MODE 3 entries left in global memory ("spilled" table: L1/L2-resident, gathered with global_load_dwordx2): the
-// comparison point BASELINE config 3 asks for next to the LDS-resident tables (HSRANS_TABLE_SPILL=1, host-built tables only)
-constexpr int kModeSpill = 5;
-
-__host__ __device__ constexpr uint32_t table_bytes_for(int mode, uint32_t bits)
-{
-  return mode == kModeSpill ? 0u
-         : mode == kModeTwoLevel ? (1u << bits) + 1024
-         : mode == kModePack64 ? 8u << bits
-         : mode == kModeRank ? (1u << bits) + 2048u
-                               : 4u << bits;
-}
-
-// Modes whose 64-state loop is hand-scheduled: their rings carry a whole-chunk mirror (kFastRingBytes per wave) ...
-__host__ __device__ constexpr bool fast_ring_mode(int mode) { return mode == kModePack64 || mode == kModeRank; }
-// ... and the one whose table sits at the START of the workgroup's LDS (address 0: the slot is the address of its rank byte)
-__host__ __device__ constexpr bool table_first_mode(int mode) { return mode == kModeRank; }
-
-// The LDS of a workgroup that shares ONE table, as byte offsets from its start: [waves x rings][table][extra], or with the table
-// first [table][extra][waves x rings].  The launcher sizes the workgroup by total(), the kernels place their pointers by the rest
-// (wave_ctx_lds), so the two cannot drift apart.
-//   rings_per_wave: 2 in the dual kernels (one ring per chain)
-//   extra: bytes behind the table; kGroupedExtra = run_grouped's two next-group words (64 B) and a table-build scratch of its own
-//          (1 KiB, the last of them: a round's first stream chunks are requested before its table is built).  Without extra bytes
-//          the build scratch is wave 0's ring: no request is in flight while a table is built
-//   whole_mirror: every ring carries a whole-chunk mirror (the gather kernels never run the hand-scheduled loops: false)
-//   table_given: the table's size where it is not worked out from mode and bits: a gather over many plans makes room for their largest
-constexpr uint32_t kBuildScratchBytes = 1024; // counts + prefix sums, 512 B each
-constexpr uint32_t kGroupedExtra = 64 + kBuildScratchBytes;
-struct LdsLayout
-{
-  int mode;
-  uint32_t bits, waves, rings_per_wave, extra;
-  bool whole_mirror, given;
-  uint32_t table_given;
-  constexpr uint32_t table_bytes() const { return given ? table_given : table_bytes_for(mode, bits); }
-  constexpr uint32_t ring_stride() const { return rings_per_wave * (whole_mirror ? kFastRingBytes : kWaveRingBytes); } // from one wave's rings to the next wave's
-  constexpr uint32_t rings() const { return table_first_mode(mode) ? table_bytes() + extra : 0; }
-  constexpr uint32_t table() const { return table_first_mode(mode) ? 0 : waves * ring_stride(); }
-  constexpr uint32_t total() const { return waves * ring_stride() + table_bytes() + extra; }
-};
-__host__ __device__ constexpr LdsLayout lds_layout(int mode, uint32_t bits, uint32_t waves, uint32_t rings_per_wave = 1, uint32_t extra = 0)
-{
-  return LdsLayout{mode, bits, waves, rings_per_wave, extra, fast_ring_mode(mode), false, 0};
-}
-// (plain rings: the gather kernels never run the hand-scheduled loops)
-__host__ __device__ constexpr LdsLayout lds_layout_gather(int mode, uint32_t table_bytes, uint32_t waves) { return LdsLayout{mode, 0, waves, 1, 0, false, true, table_bytes}; }
 
 __device__ __forceinline__ uint32_t lds_address(const void *p)
 {

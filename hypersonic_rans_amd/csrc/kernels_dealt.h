@@ -13,7 +13,7 @@ namespace hsrans
 // move work between them.  k_decode_spread (round 4) deals the chain list out by age-class weight instead, but only while its longest
 // share is shorter than every block (so that no share needs a third table) and shorter than 128 chains (its LDS record area), and it
 // pays three dependent trips to memory before its first group: piece records -> histograms -> states and stream chunks.
-// Here the HOST deals (deal_shares, hsrans_kernels.hip; once per plan and weight set): workgroup b's share is chains
+// Here the HOST deals (deal_shares, hsrans_launch.cpp; once per plan and weight set): workgroup b's share is chains
 // [begin[b], begin[b + 1]), sized by the workgroups' age-class weights and cut back where it would reach into a third block, and
 // `split[b]` says where inside the share the second block starts.  The table rides in the kernel arguments, so a wave knows its chains —
 // and with them the addresses of its piece records, its start states and its workgroup's one or two histograms — from arithmetic alone:

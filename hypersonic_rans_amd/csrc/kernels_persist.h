@@ -55,8 +55,8 @@ __device__ void run_persistent(const WaveCtx &c, const KParams &kp, uint32_t wav
   const uint32_t wave_in_wg = w % waves, blk = w / waves;
   const uint32_t first_half = (gridDim.x + 1) / 2;
   const uint32_t half = blk >= first_half ? 1 : 0;
-  const uint32_t per_class = waves >= 4 ? waves / 4 : 1; // waves of one class in a workgroup
-  const uint32_t cls = half * 4 + wave_in_wg / per_class;
+  const uint32_t per_class = waves >= 4 ? waves / 4 : 1; // waves of one class in a workgroup (waves_per_class, kernels_layout.h)
+  const uint32_t cls = half * 4 + wave_in_wg / per_class; // (wave_class's rule, kernels_layout.h, without its cap at the fourth class)
   const uint32_t q0 = pa.run_len[cls];
   const uint32_t c_first = pa.half_base[half] + (blk - half * first_half) * pa.wg_chains[half] + pa.class_off[cls] + (wave_in_wg % per_class) * q0;
   const bool host_table = host_table_mode<MODE> && pa.table != nullptr; // kModeRank / kModeSpill are host-built only
@@ -138,7 +138,7 @@ __device__ void run_persistent_pair(const WaveCtx &c, const KParams &kp, uint32_
   const uint32_t first_half = (gridDim.x + 1) / 2;
   const uint32_t half = blk >= first_half ? 1 : 0;
   const uint32_t per_class = waves >= 4 ? waves / 4 : 1;
-  const uint32_t cls = half * 4 + wave_in_wg / per_class;
+  const uint32_t cls = half * 4 + wave_in_wg / per_class; // (as run_persistent: wave_class's rule)
   const uint32_t q0 = pa.run_len[cls];
   const uint32_t c_first = pa.half_base[half] + (blk - half * first_half) * pa.wg_chains[half] + pa.class_off[cls] + (wave_in_wg % per_class) * 2 * q0;
   const bool host_table = host_table_mode<MODE> && pa.table != nullptr;

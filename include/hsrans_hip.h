@@ -1587,7 +1587,7 @@ int hsrans_dealt_shares(const hsrans_ctx *ctx, uint32_t bits /* the class length
                         uint16_t *split_out /* [512] */);
 
 /* Which kernel a single-plan decode launch of a plan would run, and with what geometry, without a device (tests, planning): the launcher's
- * own decision (choose_launch in csrc/hsrans_kernels.hip), on the MI355X defaults (ctx != NULL: that context's device and switches).
+ * own decision (choose_launch in csrc/hsrans_launch.cpp), on the MI355X defaults (ctx != NULL: that context's device and switches).
  * `plan`: the plan-header fields that matter.  `facts`: what the launcher otherwise reads off the device plan it is handed.
  * Returns 0 and fills *info and kernel_name (the demangled name as a kernel trace prints it, without return type and parameter list,
  * e.g. "hsrans::k_decode_direct<3>"); 1: the launch would be refused as not supported, 2: as an invalid value (nothing is filled in);

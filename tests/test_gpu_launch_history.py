@@ -114,7 +114,7 @@ def _kind(hdr):
 
 
 def static_total(n_chains, states, info):
-    """static_shares (csrc/hsrans_kernels.hip) from the launch info: the chains the waves of a uniform-interval launch decode without a
+    """static_shares (csrc/hsrans_launch.cpp) from the launch info: the chains the waves of a uniform-interval launch decode without a
     ticket; the rest, n_chains - static_total, go through the queues (two runs per wave at 32 states)"""
     grid, waves, weights = info["grid"], info["waves_per_block"], info["class_weights"]
     W, runs = grid * waves, 2 if states == 32 else 1
